@@ -534,6 +534,19 @@ class cpu_rollout_rows:
         return OG.compute_returns(rewards, gamma), OG.compute_advantages(rewards, values_be, gamma, lambda_, 2.0)
 
 
+def dump_outputs(out_dir, eng):
+    """--dump-outputs: the state one update-step leaves to its caller (DataParallelLearner.update_step returns nothing; it updates
+    the engine's arenas in place), copied to the host after the timed region.  The arenas do not depend on the batch or image size
+    (44 MB in all).  metrics_<pass>.npy: the values of LearnerEngine.metrics(<pass>) in its key order (policy: loss, policy_loss,
+    entropy, speed_loss, similarity_loss, ratio, log_prob; value: loss, value_loss, speed_loss, similarity_loss)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (('params', eng.params), ('grads', eng.grads), ('adam_m', eng.adam_m), ('adam_v', eng.adam_v)):
+        np.save(os.path.join(out_dir, f'{name}.npy'), t.detach().float().cpu().numpy())
+    for which in ('policy', 'value'):
+        np.save(os.path.join(out_dir, f'metrics_{which}.npy'), np.array(list(eng.metrics(which).values()), dtype=np.float64))
+
+
 def spawn_ranks(n, argv):
     """`bench.py --gpus N` started as a plain process: start the N ranks as CHILDREN through torch.distributed.run (one
     process per GPU, RCCL rendezvous on 127.0.0.1) BEFORE anything in this process touches the GPU, relay their output and
@@ -580,7 +593,14 @@ def main():
     ap.add_argument('--cpu-baseline-only', action='store_true')
     ap.add_argument('--stored-actions', action='store_true',
                     help='time the textbook-PPO loss on the stored rollout actions instead of the reference-faithful re-sampled loss')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed update-steps, write what the last one left to the caller as DIR/<name>.npy (rank 0): the '
+                         'parameter arena (weights, BatchNorm moving statistics, old policy), the gradient arena, both Adam moments '
+                         '(float32, 44 MB at the default shape) and the policy / value loss metrics (float64).  Inputs and weights are '
+                         'seeded: the same arguments give the same inputs on every run')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args.cpu_sample_batch, 4, args.height, args.width, args.cpu_threads)))
         return
@@ -700,6 +720,8 @@ def main():
         elapsed = float(t.item())
     loss_p = eng.metrics('policy')['loss']
     loss_v = eng.metrics('value')['loss']
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3

@@ -1,9 +1,11 @@
 """TF-checkpoint-V2 reader + Keras-order key mapping.  The mapping is pinned against the reference's
 own checkpoint indices (committed inventory fixture: every `layer_with_weights-N/<var>` shape must equal
-the shape of the engine parameter it maps to); reading real shards is exercised when the reference
-checkout is present (build container only)."""
+the shape of the engine parameter it maps to); reading and re-writing real shards is exercised on the
+reference's shipped checkpoint, rebuilt byte for byte from committed fixtures (see `ref` below)."""
+import hashlib
 import json
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -12,7 +14,32 @@ from carla_driving_rl_agent_amd import tf_checkpoint as tfc
 from carla_driving_rl_agent_amd.engine import LearnerEngine
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = '/root/reference/weights/stage-s5-curriculum'
+GOLDEN = os.path.join(HERE, 'golden')
+
+
+@pytest.fixture(scope='module')
+def ref(tmp_path_factory):
+    """The reference's shipped checkpoint directory (weights/stage-s5-curriculum), rebuilt from tests/golden/: the `.index` files
+    and object-graph shards as shipped (ref_ckpt/, tests/golden/make_ref_ckpt.py), the policy / value tensor shards re-assembled
+    from ref_trained_heads.npz at the offsets their index records and held to the size and SHA-256 of the shipped files."""
+    d = tmp_path_factory.mktemp('stage-s5-curriculum')
+    src = os.path.join(GOLDEN, 'ref_ckpt')
+    shards = json.load(open(os.path.join(src, 'shards.json')))
+    for f in os.listdir(src):
+        if f != 'shards.json':
+            shutil.copyfile(os.path.join(src, f), str(d / f))
+    heads = np.load(os.path.join(GOLDEN, 'ref_trained_heads.npz'))
+    for model, ckpt in (('policy', 'policy_net'), ('value', 'value_net')):
+        name = ckpt + '.data-00001-of-00002'
+        mapping = tfc.key_map(model)
+        buf = bytearray(shards[name]['size'])
+        for e in tfc.read_index(str(d / (ckpt + '.index'))):
+            blob = np.ascontiguousarray(heads[f'{model}/{mapping[e["key"]]}'], dtype=np.float32).tobytes()
+            assert e['shard'] == 1 and len(blob) == e['size'], e
+            buf[e['offset']:e['offset'] + e['size']] = blob
+        assert hashlib.sha256(buf).hexdigest() == shards[name]['sha256'], name
+        (d / name).write_bytes(bytes(buf))
+    return str(d)
 
 
 @pytest.mark.parametrize('model,ckpt', [('trunk', 'dynamics_model'), ('policy', 'policy_net'), ('value', 'value_net')])
@@ -105,26 +132,24 @@ def test_keras_key_mapping_matches_reference_variable_names():
         assert num(order[f'{p}.bn1']) == num(order[f'{p}.bn0']) + 1 and num(order[f'{p}.fc1']) == num(order[f'{p}.fc0']) + 1
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not present on this machine')
-def test_object_graph_reader_matches_inventory():
+def test_object_graph_reader_matches_inventory(ref):
     inv = json.load(open(os.path.join(HERE, 'golden', 'ref_ckpt_inventory.json')))['full']
     for ckpt in ('policy_net', 'value_net', 'dynamics_model'):
-        og = tfc.read_object_graph(os.path.join(REF, ckpt))
+        og = tfc.read_object_graph(os.path.join(ref, ckpt))
         assert [og[k] for k, _ in inv[ckpt]['tensors']] == inv[ckpt]['names']
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not present on this machine')
-def test_reads_reference_policy_and_value_shards():
+def test_reads_reference_policy_and_value_shards(ref):
     stats = json.load(open(os.path.join(HERE, 'golden', 'ref_ckpt_inventory.json')))['full']
     for ckpt in ('policy_net', 'value_net'):
-        t = tfc.load_checkpoint(os.path.join(REF, ckpt))
+        t = tfc.load_checkpoint(os.path.join(ref, ckpt))
         keys = [k for k, _ in stats[ckpt]['tensors']]
         assert sorted(t) == sorted(keys)
         for (k, shape), (mean, std, mn, mx) in zip(stats[ckpt]['tensors'], stats[ckpt]['stats']):
             assert t[k].shape == tuple(shape)
             assert abs(t[k].mean() - mean) < 1e-6 + 1e-5 * abs(mean) and abs(t[k].max() - mx) < 1e-6
     # the trunk's data shard is not shipped (.MISSING_LARGE_BLOBS): the reader must not invent tensors
-    assert tfc.load_checkpoint(os.path.join(REF, 'dynamics_model')) == {}
+    assert tfc.load_checkpoint(os.path.join(ref, 'dynamics_model')) == {}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -160,13 +185,12 @@ def test_writer_round_trip_and_reference_key_set(model, ckpt, tmp_path):
             assert strip(full) == strip(ref_names[k]), (k, full, ref_names[k])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not present on this machine')
 @pytest.mark.parametrize('ckpt', ['policy_net', 'value_net'])
-def test_writer_reproduces_reference_files_byte_for_byte(ckpt, tmp_path):
+def test_writer_reproduces_reference_files_byte_for_byte(ckpt, tmp_path, ref):
     """Decode the shipped checkpoint, re-encode it with save_checkpoint: `.index` (SSTable blocks, prefix compression, restart
     arrays, masked CRC-32C of every block and tensor), the object-graph shard and the tensor shard are byte-identical to the
     files Keras / TensorFlow 2.3 wrote."""
-    src = os.path.join(REF, ckpt)
+    src = os.path.join(ref, ckpt)
     tensors = tfc.load_checkpoint(src)
     raw = open(src + '.data-00000-of-00002', 'rb').read()
     n, pos = tfc._varint(raw, 0)
