@@ -18,7 +18,8 @@ class Config(C.Structure):
                 ('road', C.c_int32), ('vehicle', C.c_int32), ('navigation', C.c_int32), ('A', C.c_int32),
                 ('stem', C.c_int32), ('stage_c', C.c_int32 * 3), ('stage_n', C.c_int32 * 3), ('last', C.c_int32),
                 ('feat', C.c_int32), ('rnn_image', C.c_int32), ('rnn_small', C.c_int32), ('dyn', C.c_int32),
-                ('head', C.c_int32), ('exp_scale', C.c_float), ('compute', C.c_int32)]
+                ('head', C.c_int32), ('exp_scale', C.c_float), ('compute', C.c_int32),
+                ('freeze_trunk', C.c_int32)]
 
 
 COMPUTE_F32, COMPUTE_BF16_OPERANDS, COMPUTE_BF16_STORAGE = 0, 1, 2

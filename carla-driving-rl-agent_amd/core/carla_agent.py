@@ -98,16 +98,18 @@ class CARLAgent(PPOAgent):
         the NEW policy with pathwise gradients, as PolicyNetwork.call does (reference core/networks.py:96-110, SURVEY.md F8);
         the sample is drawn on the device.  `False` is the textbook-PPO variant on the stored rollout actions
         (rl/agents/ppo.py:322-325 semantics; deterministic, same cost).
-        `compute='bf16'`: the engine's bf16-operand mode (not in the reference; CARLANetwork docstring)."""
+        `compute='bf16'`: the engine's bf16-operand mode (not in the reference; CARLANetwork docstring).
+        `update_dynamics=False`: frozen trunk -- every minibatch step runs the trunk forward in training mode (its BatchNorm moving
+        statistics update) and trains the policy / value heads only; `dynamics_lr` is then accepted and unused, as in the
+        reference (core/carla_agent.py:351-373,430-463).  Typical use: load a trained trunk with `load_full=False`, fine-tune the heads."""
         assert aug_intensity >= 0.0
-        if not update_dynamics:
-            raise NotImplementedError('update_dynamics=False (frozen trunk) is not implemented natively')
         network_spec = dict(kwargs.pop('network', {}))
         network_spec.setdefault('network', CARLANetwork)
         network_spec.setdefault('control_policy', self.DEFAULT_CONTROL)
         network_spec.setdefault('control_value', self.DEFAULT_CONTROL_VALUE)
         network_spec.setdefault('dynamics', self.DEFAULT_DYNAMICS)
         network_spec.setdefault('compute', compute)
+        network_spec.setdefault('update_dynamics', update_dynamics)
         self.should_update_dynamics = update_dynamics
         self.dynamics_path = os.path.join(kwargs.get('weights_dir', 'weights'), name, 'dynamics_model')
         self.load_full = load_full
@@ -298,7 +300,7 @@ class CARLAgent(PPOAgent):
         return eng.buffer(2)[0].clone(), 'policy'  # device scalar (copy of CDRL_BUF_METRICS_P[0]); gradients stay in the arena
 
     def apply_policy_gradients(self, gradients):
-        self._step_engine.policy_apply()          # trunk Adam -> clip -> old_policy <- policy -> policy Adam
+        self._step_engine.policy_apply()          # trunk Adam (not when frozen) -> clip -> old_policy <- policy -> policy Adam
         return gradients
 
     def get_value_gradients(self, batch):

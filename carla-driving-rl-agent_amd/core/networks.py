@@ -57,9 +57,12 @@ class PolicyNetwork:
 
 
 class CARLANetwork(Network):
-    def __init__(self, agent, control_policy: dict, control_value: dict, dynamics: dict, update_dynamics=False, compute='f32'):
+    def __init__(self, agent, control_policy: dict, control_value: dict, dynamics: dict, update_dynamics=True, compute='f32'):
         """compute: 'f32' (the reference's arithmetic) or 'bf16' -- bf16 MFMA operands in the tower's 1x1 convolutions
-        (include/cdrl.h CDRL_COMPUTE_BF16_OPERANDS, BASELINE.json configs[2]; see DESIGN.md section 7 for what it costs numerically)."""
+        (include/cdrl.h CDRL_COMPUTE_BF16_OPERANDS, BASELINE.json configs[2]; see DESIGN.md section 7 for what it costs numerically).
+        update_dynamics=False: frozen trunk -- the learner engines train the policy / value heads only (cdrl_config.freeze_trunk);
+        CARLAgent passes its own update_dynamics.  (The reference's keyword defaults to False but is never read there; here it
+        drives the engine, so the default is the agent's.)"""
         super().__init__(agent)
         env = agent.env
         T = env.time_horizon
@@ -82,7 +85,7 @@ class CARLANetwork(Network):
                         stem=img['stem'], stage_c=img['stage_c'], stage_n=img['stage_n'], last=img['last'],
                         feat=self.dynamics_spec['features']['road']['units'], rnn_image=self.dynamics_spec['rnn']['image'],
                         rnn_small=self.dynamics_spec['rnn']['road'], dyn=self.dynamics_spec['units'],
-                        head=p_branch['units'], exp_scale=self.exp_scale, compute=compute)
+                        head=p_branch['units'], exp_scale=self.exp_scale, compute=compute, freeze_trunk=not update_dynamics)
         self.device = agent.device
         self.engine = LearnerEngine(agent.batch_size, device=self.device, **self.cfg)          # learner minibatches
         self._rollouts = {}                # number of environments E -> inference engine over the same arenas
@@ -177,8 +180,10 @@ class CARLANetwork(Network):
             self.engine.load_params(m, w)
 
     def trainable_variables(self):
+        """Trainable tensors per model; the trunk's only when it is updated (frozen: the heads alone)."""
+        models = ('policy', 'value', 'trunk') if self.update_dynamics else ('policy', 'value')
         return {m: {k: v for k, v in self.engine.param_views(m).items() if self.engine.tables[m].by_name[k]['trainable']}
-                for m in ('policy', 'value', 'trunk')}
+                for m in models}
 
     def _paths(self):
         return dict(policy=self.agent.weights_path['policy'] + '.npz', value=self.agent.weights_path['value'] + '.npz',

@@ -82,6 +82,7 @@ void cdrl_config_default(cdrl_config* c) {
     c->last = d.last; c->feat = d.feat; c->rnn_image = d.rnn_image; c->rnn_small = d.rnn_small;
     c->dyn = d.dyn; c->head = d.head; c->exp_scale = d.exp_scale;
     c->compute = d.compute;
+    c->freeze_trunk = d.freeze_trunk;
 }
 
 int cdrl_learner_create(const cdrl_config* c, cdrl_learner** out) {
@@ -110,6 +111,11 @@ int cdrl_learner_create(const cdrl_config* c, cdrl_learner** out) {
         return -1;
     }
     d.compute = c->compute;
+    if (c->freeze_trunk != 0 && c->freeze_trunk != 1) {
+        cdrl::set_error("cdrl_learner_create: freeze_trunk must be 0 or 1 (got %d)", c->freeze_trunk);
+        return -1;
+    }
+    d.freeze_trunk = c->freeze_trunk;
     if (cdrl::diag_active()) {      // loud, every time: results of this learner are WRONG by request (timing diagnostics)
         char ov[2048];
         cdrl::env_overrides(ov, (int)sizeof(ov));

@@ -30,6 +30,8 @@ struct Config {
     int compute = 0;        // 0: float32 products; 1: bf16 MFMA operands in the tower's 1x1 convolutions (configuration 3);
                             // 2: 1 + bf16 ACTIVATION STORAGE: every activation / activation-gradient tensor of the image tower
                             //    is bf16 in HBM (statistics, partials, coefficients, weights, accumulators stay float32 / double)
+    int freeze_trunk = 0;   // 1: the passes train the heads only on a fixed trunk (reference CARLAgent(update_dynamics=False)): train-mode
+                            //    trunk forward (batch statistics, moving statistics updated), no trunk backward, no trunk Adam step
 };
 
 enum Model : int { M_TRUNK = 0, M_POLICY = 1, M_VALUE = 2, M_OLD_POLICY = 3 };
@@ -177,7 +179,9 @@ public:
     void set_comm_stream(hipStream_t s) { comm_ = s; }
     // First element (inside the trunk's trainable region) of the TAIL tensors: everything registered behind the image tower,
     // i.e. exactly the gradients that are final at the point the communication stream is released.  Fixed by the op list.
-    int64_t tail_offset() const { return tail_off_; }
+    // Frozen trunk: no trunk gradient is ever written and the stream is never released; the whole trunk counts as "not final".
+    int64_t tail_offset() const { return frozen() ? tr_size_[M_TRUNK] : tail_off_; }
+    bool frozen() const { return cfg_.freeze_trunk != 0; }
     bool graphs_enabled() const { return graphs_enabled_; }
     // Named internal tensors (parity tests: the raw BatchNorm inputs, statistics blocks, max-pool argmax codes and dense
     // pre-activations from which the discrete ReLU6 / max-pool decisions of the last forward are reconstructed)
@@ -310,6 +314,11 @@ private:
     void add_guard();
     // scratch maxima (from the dry build) and pointers
     size_t max_part_ = 0, max_part2_ = 0, max_dy_ = 0, max_tn_ = 0, max_fpart_ = 0;
+    // the same maxima over the ops built outside the trunk (heads): what the rotating slots must hold on a frozen learner
+    bool building_trunk_ = false;
+    size_t head_part2_ = 0, head_tn_ = 0;
+    struct SlotSizes { size_t dy, part2, tn, fpart, qpart, dbpart, fintot; };
+    SlotSizes slot_sizes() const;
     // reduction scratch of the ops on the main stream / of the auxiliary ops (feature nets + small GRUs),
     // which run concurrently on the side stream and therefore need their own
     struct Scratch {

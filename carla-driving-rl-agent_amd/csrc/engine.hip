@@ -600,9 +600,10 @@ int Learner::run_trunk_fwd(hipStream_t st, int training) {
     // conv plus a join packet cost what they save; they stay in front of the stem.
     // ... and in ONE launch, with the W^T transposes of the backward (training passes) riding along: four dependent 4-13 us launches per
     // pass became one (pack_all; the weights do not change between here and the backward)
-    packs_have_wt_ = training != 0;
+    // (frozen trunk: no backward follows, and the planner registered no backward operand at all)
+    packs_have_wt_ = training != 0 && !frozen();
     CDRL_TRY(pack_all(d_gpack_, (int)h_gpack_.size(), d_pack_, (int)h_pack_.size(), d_pack3_, (int)h_pack3_.size(), d_pwt_,
-                      training ? (int)h_pwt_.size() : 0, pwt_tiles_, st));
+                      packs_have_wt_ ? (int)h_pwt_.size() : 0, pwt_tiles_, st));
     return run_fwd(trunk_ops_, st, training);
 }
 
@@ -612,6 +613,18 @@ void Learner::note_scratch(size_t part_d, size_t part2_d, size_t dy_f, size_t tn
     if (dy_f > max_dy_) max_dy_ = dy_f;
     if (tn_f > max_tn_) max_tn_ = tn_f;
     if (fpart_d > max_fpart_) max_fpart_ = fpart_d;
+    if (!building_trunk_) {
+        if (part2_d > head_part2_) head_part2_ = part2_d;
+        if (tn_f > head_tn_) head_tn_ = tn_f;
+    }
+}
+
+// Sizes of the rotating backward scratch (NSLOT slots, NQ fused-conv ring).  A frozen learner runs the backward of the heads only:
+// their dense layers use the slots' part2 / tn blocks (side-stream weight gradients); dy, the filter partials and the ring are
+// tower-backward scratch and get no bytes (the allocations stay, empty, so that the guard-band count does not depend on the flag)
+Learner::SlotSizes Learner::slot_sizes() const {
+    if (frozen()) return SlotSizes{0, head_part2_, head_tn_, 0, 0, 0, 0};
+    return SlotSizes{max_dy_, max_part2_, max_tn_, max_fpart_, max_qpart_, max_dbpart_, (size_t)8 * 2 * 128};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -728,13 +741,13 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
     const bool use_g3f = g3 && !fuse.fwd_pw && gemm_x3_supported(in, Cin);
     const bool use_g3b = g3 && !fuse.bwd_pw && !fuse.bb && Cout % 4 == 0;
     const void* g3f = use_g3f ? gemm_x3_packed(w.p, Cin, Cout, Cout, 1) : nullptr;
-    const void* g3b = use_g3b ? gemm_x3_packed(w.p, Cout, Cin, 1, Cout) : nullptr;
+    const void* g3b = (use_g3b && !frozen()) ? gemm_x3_packed(w.p, Cout, Cin, 1, Cout) : nullptr;       // (frozen: no backward)
     if (bfc && ((!fuse.fwd_pw && !use_g3f) || (!fuse.bwd_pw && !fuse.bb && !use_g3b) || (fuse.bb && !fuse.bwd_pw)))
         build_fail("bf16-operand mode: 1x1 convolution %s (%d -> %d, fwd %d bwd %d bb %d; input ld %d coff %d) has no bf16 kernel",
                    prefix.c_str(), Cin, Cout, (int)fuse.fwd_pw, (int)fuse.bwd_pw, (int)fuse.bb, in.ld, in.coff);
     if (bfc && !pack_env) build_fail("bf16-operand mode needs the packed-weight path (CDRL_PW_PACK=0 is set)");
     const float* wpf = (pack_env && fuse.fwd_pw && !w3f) ? pw_packed(w.p, Cin, Cout, Cout, 1, bfc) : nullptr;      // forward: B(k = cin, n = cout)
-    const float* wpb = (pack_env && fuse.bwd_pw) ? pw_packed(w.p, Cout, Cin, 1, Cout, bfc) : nullptr;      // backward-data: W^T
+    const float* wpb = (pack_env && fuse.bwd_pw && !frozen()) ? pw_packed(w.p, Cout, Cin, 1, Cout, bfc) : nullptr;      // backward-data: W^T
     const int tn_groups = (fuse.pro_stats || fuse.bb) ? G : 1;
     note_scratch(0, 0, (size_t)rows * Cout, (size_t)gemm_tn_part_elems(rows, Cout, Cin, tn_groups));
     if (fuse.epi_stats) note_scratch((size_t)G * nb_fwd * 2 * Cout, 0, 0, 0);
@@ -770,7 +783,7 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
     if (wbw && !pw_x3_wide_bwd_supported(dz_probe, din, Cin, Cout, fuse.bb_shuffle))
         build_fail("%s: the wide split-precision backward needs even / 16-byte aligned gradient rows (ld %d, offset %d, shuffle %d)", prefix.c_str(),
                    dz_probe.ld, dz_probe.coff, fuse.bb_shuffle);
-    const void* wpx = (fbwd || wbw) ? pw_x3_packed(w.p, Cout, Cin, 1, Cout) : nullptr;      // W^T planes: B(k = cout, n = cin)
+    const void* wpx = ((fbwd || wbw) && !frozen()) ? pw_x3_packed(w.p, Cout, Cin, 1, Cout) : nullptr;      // W^T planes: B(k = cout, n = cin)
     if (fbwd) {
         max_qpart_ = std::max(max_qpart_, (size_t)pw_bwd_fused_qpart_elems(G, Mg, Cout, Cin, at));
         max_dbpart_ = std::max(max_dbpart_, (size_t)pw_bwd_fused_dbpart_elems(G, Mg, Cout, Cin, at));
@@ -1064,7 +1077,7 @@ void Learner::add_gru(std::vector<Op>& ops, const std::string& name, Tens& x, in
     float* dHb = alloc((size_t)B * u);
     if (!dry_) zero_once_.push_back(std::make_pair(Hs, (size_t)B * u * sizeof(float)));
     if (!gru_step_supported(u)) build_fail("GRU units %d unsupported by the fused step kernels", u);
-    const float* RT = pw_transposed(name + ".recurrent", Rp.p, u, U3);        // [3u][u], refreshed with the conv W^T copies
+    const float* RT = frozen() ? nullptr : pw_transposed(name + ".recurrent", Rp.p, u, U3);        // [3u][u], refreshed with the conv W^T copies
     note_scratch((size_t)vcol_geom(T * B, U3).nb * U3, (size_t)vcol_geom(T * B, U3).nb * U3, 0,
                  (size_t)std::max(gemm_tn_part_elems(T * B, U3, In), gemm_tn_part_elems(T * B, U3, u)));
     const int nbc = vcol_geom(T * B, U3).nb;
@@ -1737,6 +1750,7 @@ void Learner::build(bool dry) {
     policy_ops_.clear();
     value_ops_.clear();
     old_policy_ops_.clear();
+    const SlotSizes ss = slot_sizes();
     if (!dry) {
         scr_main_.part = alloc_d(max_part_);
         scr_main_.part2 = alloc_d(max_part2_);
@@ -1748,15 +1762,15 @@ void Learner::build(bool dry) {
         scr_sc_.part2 = alloc_d(max_part2_);
         scr_sc_.tn = scr_aux_.tn;           // (unused by the shortcut ops)
         for (int i = 0; i < NSLOT; ++i) {
-            dys_[i] = alloc((max_dy_ * esz() + 3) / 4);      // tower gradients: activation-typed
-            part2s_[i] = alloc_d(max_part2_);
-            tns_[i] = alloc(max_tn_);
-            fparts_[i] = alloc_d(max_fpart_);
+            dys_[i] = alloc((ss.dy * esz() + 3) / 4);      // tower gradients: activation-typed
+            part2s_[i] = alloc_d(ss.part2);
+            tns_[i] = alloc(ss.tn);
+            fparts_[i] = alloc_d(ss.fpart);
         }
         for (int i = 0; i < NQ; ++i) {
-            qparts_[i] = alloc(max_qpart_);
-            dbparts_[i] = alloc_d(max_dbpart_);
-            fintots_[i] = alloc_d((size_t)8 * 2 * 128);
+            qparts_[i] = alloc(ss.qpart);
+            dbparts_[i] = alloc_d(ss.dbpart);
+            fintots_[i] = alloc_d(ss.fintot);
         }
     }
     h_pwt_.clear();
@@ -1768,7 +1782,9 @@ void Learner::build(bool dry) {
     h_gpack_.clear();
     h_bninf_.clear();
     bninf_max_c_ = 0;
+    building_trunk_ = true;
     build_trunk(trunk_ops_);
+    building_trunk_ = false;
     const int A = cfg_.A;
     const int pdims[4] = {A, A, 1, 1};
     const char* const pnames[4] = {"alpha", "beta", "similarity", "speed"};
@@ -1820,14 +1836,15 @@ void Learner::build(bool dry) {
         if (!dry && guard_off_.size() > GUARD_TABLE_MAX) build_fail("CDRL_GUARD: %zu bands exceed the table", guard_off_.size());
     }
     if (dry) {
-        // scratch goes first in the real layout; account for it here
+        // scratch goes first in the real layout; account for it here (maxima of the whole dry build, hence a fresh slot_sizes())
+        const SlotSizes ss2 = slot_sizes();
         ws_off_ += 512 + 2 * (align_up(max_part_ * sizeof(double), 256) + align_up(max_part2_ * sizeof(double), 256) +
                         align_up(max_tn_ * sizeof(float), 256)) +
                    align_up(max_part_ * sizeof(double), 256) + align_up(max_part2_ * sizeof(double), 256) +
-                   NSLOT * (align_up((max_dy_ * esz() + 3) / 4 * sizeof(float), 256) + align_up(max_part2_ * sizeof(double), 256) +
-                            align_up(max_tn_ * sizeof(float), 256) + align_up(max_fpart_ * sizeof(double), 256)) +
-                   NQ * (align_up(max_qpart_ * sizeof(float), 256) + align_up(max_dbpart_ * sizeof(double), 256) +
-                         align_up((size_t)8 * 2 * 128 * sizeof(double), 256));
+                   NSLOT * (align_up((ss2.dy * esz() + 3) / 4 * sizeof(float), 256) + align_up(ss2.part2 * sizeof(double), 256) +
+                            align_up(ss2.tn * sizeof(float), 256) + align_up(ss2.fpart * sizeof(double), 256)) +
+                   NQ * (align_up(ss2.qpart * sizeof(float), 256) + align_up(ss2.dbpart * sizeof(double), 256) +
+                         align_up(ss2.fintot * sizeof(double), 256));
         if (guard_) ws_off_ += (size_t)(8 + 4 * NSLOT + 3 * NQ) * GUARD_BYTES;      // one band per scratch allocation above
         ws_bytes_ = ws_off_ + 4096;
     }
@@ -2071,6 +2088,10 @@ int Learner::policy_backward_impl(const PolicyBatch& b, float inv_world, hipStre
     a.inv_world = inv_world;
     CDRL_TRY(policy_loss(a, st));
     CDRL_TRY(run_bwd(policy_ops_, st));
+    // Frozen trunk: the heads' backward ends in the BatchNorm of pi.bn0, which also writes d(loss)/d(dynamics) into the trunk's
+    // output gradient.  That write has no consumer here, but up to 2048 rows it comes out of the same launch that produces the
+    // BatchNorm's dgamma / dbeta (bn_small_bwd, one launch per direction): it stays, and the head gradients are those of a full pass.
+    if (frozen()) return join_side(st);
     if (!packs_have_wt_) CDRL_TRY(transpose_many(d_pwt_, (int)h_pwt_.size(), pwt_tiles_, st));      // W^T of the pointwise convs (normally packed with the forward's operands)
     CDRL_TRY(run_bwd(trunk_ops_, st));
     return join_side(st);
@@ -2135,6 +2156,7 @@ int Learner::value_forward_backward_impl(const ValueBatch& b, float inv_world, h
     a.inv_world = inv_world;
     CDRL_TRY(value_loss(a, st));
     CDRL_TRY(run_bwd(value_ops_, st));
+    if (frozen()) return join_side(st);        // (see policy_backward_impl)
     if (!packs_have_wt_) CDRL_TRY(transpose_many(d_pwt_, (int)h_pwt_.size(), pwt_tiles_, st));
     CDRL_TRY(run_bwd(trunk_ops_, st));
     return join_side(st);
@@ -2157,14 +2179,16 @@ int Learner::policy_apply(hipStream_t caller) {
 
 int Learner::policy_apply_impl(hipStream_t st) {
     // order: trunk Adam (unclipped, F9) -> clip -> old_policy <- policy -> policy Adam
+    // frozen trunk: no trunk Adam step, and the trunk's step counter stays where it is (reference ppo.py:238-252 on the heads only)
     const int64_t to = tr_offset(M_TRUNK), po = tr_offset(M_POLICY);
-    CDRL_TRY(clip_adam(buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK], nullptr,
-                       nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
+    if (!frozen())
+        CDRL_TRY(clip_adam(buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK], nullptr,
+                           nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
     SegTable& s = seg_[M_POLICY];
     // four launches instead of seven (round 6): the chunk kernel of the norms also advances the trunk's step counter (its update ran in front)
     // and the policy's (its update runs behind and is told so); the per-tensor fold of the chunk partials happens inside clip_adam
     CDRL_TRY(tensor_sqnorms(buf_.grads + po, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part,
-                            s.sqnorms, st, hp_dev_, 4 | 1, true));
+                            s.sqnorms, st, hp_dev_, frozen() ? 1 : 4 | 1, true));
     CDRL_TRY(update_old_policy_impl(st));
     return clip_adam(buf_.params + po, buf_.grads + po, buf_.adam_m + po, buf_.adam_v + po, tr_size_[M_POLICY], s.chunk_tensor,
                      s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 0, st, s.chunk_part, 1);
@@ -2176,11 +2200,12 @@ int Learner::value_apply(hipStream_t caller) {
 
 int Learner::value_apply_impl(hipStream_t st) {
     const int64_t to = tr_offset(M_TRUNK), vo = tr_offset(M_VALUE);
-    CDRL_TRY(clip_adam(buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK], nullptr,
-                       nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
+    if (!frozen())
+        CDRL_TRY(clip_adam(buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK], nullptr,
+                           nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
     SegTable& s = seg_[M_VALUE];
     CDRL_TRY(tensor_sqnorms(buf_.grads + vo, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part,
-                            s.sqnorms, st, hp_dev_, 4 | 2, true));       // (see policy_apply_impl)
+                            s.sqnorms, st, hp_dev_, frozen() ? 2 : 4 | 2, true));       // (see policy_apply_impl)
     return clip_adam(buf_.params + vo, buf_.grads + vo, buf_.adam_m + vo, buf_.adam_v + vo, tr_size_[M_VALUE], s.chunk_tensor,
                      s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 1, st, s.chunk_part, 1);
 }

@@ -27,6 +27,8 @@ def make_config(B, T=4, H=90, W=120, road=9, vehicle=4, navigation=5, A=2, **kw)
             # 'f32' | 'bf16' (bf16 MFMA operands in the tower's 1x1 convs, float32 tensors) | 'bf16s' (+ bf16 activation STORAGE in
             # the tower: configuration 3 in full)
             v = {'f32': _lib.COMPUTE_F32, 'bf16': _lib.COMPUTE_BF16_OPERANDS, 'bf16s': _lib.COMPUTE_BF16_STORAGE}[v]
+        if k == 'freeze_trunk' and isinstance(v, bool):
+            v = int(v)
         if k in ('stage_c', 'stage_n'):
             for i in range(3):
                 getattr(cfg, k)[i] = v[i]
@@ -55,12 +57,17 @@ class ParamTable:
 class LearnerEngine:
     def __init__(self, B, device: Optional[str] = 'cuda:0', share_with: 'LearnerEngine' = None, **cfg):
         """device=None -> host-only inspection (parameter tables, workspace size; no HIP calls).
-        share_with -> reuse another engine's parameter arenas (e.g. a B=1 rollout engine)."""
+        share_with -> reuse another engine's parameter arenas (e.g. a B=1 rollout engine); the new engine inherits its
+        freeze_trunk unless one is given.
+        freeze_trunk=True -> the passes train the heads only on a fixed trunk (cdrl_config.freeze_trunk, include/cdrl.h)."""
         self.lib = _lib.load()
+        if share_with is not None and 'freeze_trunk' not in cfg:
+            cfg['freeze_trunk'] = share_with.frozen
         self.cfg = make_config(B, **cfg)
         h = C.c_void_p()
         _lib.check(self.lib.cdrl_learner_create(C.byref(self.cfg), C.byref(h)), 'cdrl_learner_create')
         self.h = h
+        self.frozen = bool(self.cfg.freeze_trunk)
         self.tables = {m: ParamTable(self.lib, h, mid) for m, mid in (('trunk', TRUNK), ('policy', POLICY), ('value', VALUE))}
         self.params_total = int(self.lib.cdrl_learner_params_total(h))
         self.grads_total = int(self.lib.cdrl_learner_grads_total(h))

@@ -33,12 +33,15 @@ class DataParallelLearner:
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.sync_bn_stats = sync_bn_stats
         self.force = force_collectives and dist.is_initialized()     # run the collectives even at world 1 (smoke tests)
+        # frozen trunk (engine.frozen): the passes write the head gradients only -- each pass all-reduces its head's slice after the
+        # pass on the caller's stream (~1 MB: no early buckets, no communication stream); the trunk's gradient slice is never touched
+        self.frozen = bool(getattr(engine, 'frozen', False))
         p_off, p_n = engine.region('policy', True)
         t_off, t_n = engine.region('trunk', True)
         v_off, v_n = engine.region('value', True)
         assert p_off == 0 and t_off == p_n and v_off == p_n + t_n, 'gradient arena must be [policy|trunk|value]'
-        self._policy_slice = (0, p_n + t_n)
-        self._value_slice = (t_off, t_off + t_n + v_n)
+        self._policy_slice = (0, p_n) if self.frozen else (0, p_n + t_n)
+        self._value_slice = (t_off + t_n, t_off + t_n + v_n) if self.frozen else (t_off, t_off + t_n + v_n)
         # Overlap: the trunk's tail tensors (everything behind the image tower: feature nets, GRUs, concat
         # BN + Dense) sit at the END of the trunk region and are final ~1 ms into the backward, like the head's; they go out
         # as early buckets on a communication stream that the engine releases at that point, and only the tower's slice
@@ -46,7 +49,7 @@ class DataParallelLearner:
         # The boundary comes from the ENGINE (cdrl_learner_tail_offset: the same op-list position that releases the
         # communication stream), so the early bucket can never contain a tensor whose gradient is still being written; the
         # parameter table is only used to cross-check it.
-        tower_n = engine.tail_offset() if hasattr(engine, 'tail_offset') else t_n
+        tower_n = engine.tail_offset() if hasattr(engine, 'tail_offset') and not self.frozen else t_n
         assert 0 <= tower_n <= t_n, (tower_n, t_n)
         table = getattr(engine, 'tables', None)
         if table is not None and tower_n < t_n:
@@ -61,7 +64,7 @@ class DataParallelLearner:
         self._comm = None
         if os.environ.get('CDRL_DP_OVERLAP', '1') == '0':       # one fused all-reduce per pass after the backward (round 1 form)
             overlap = False
-        if self.use_comm_stream(overlap, self.world, self.force, tower_n, t_n,
+        if not self.frozen and self.use_comm_stream(overlap, self.world, self.force, tower_n, t_n,
                                 bool(getattr(engine, 'device', None)) and hasattr(engine, 'set_comm_stream') and engine.grads.is_cuda):
             self._comm = torch.cuda.Stream(device=engine.grads.device)
             engine.set_comm_stream(self._comm)
@@ -186,7 +189,8 @@ class DataParallelLearner:
 
     def update_step(self, policy_batch, value_batch, resample=None):
         """One PPO update-step = one policy minibatch step + one value minibatch step
-        (reference rl/agents/ppo.py:199-224)."""
+        (reference rl/agents/ppo.py:199-224).  Frozen trunk: the moving statistics are averaged behind the update with the
+        coalesced sync_moving_statistics() (the value pass has no early group to carry them)."""
         if self.world == 1 and not self.force and os.environ.get('CDRL_SEQUENCE', '1') != '0':
             # no collective between the four calls: one hand-over between the caller's stream and the engine's around all of them
             with self.engine.sequence():

@@ -38,7 +38,21 @@ typedef struct cdrl_config {
     int32_t feat, rnn_image, rnn_small, dyn, head; /* 16, 256, 32, 512, 320                     */
     float exp_scale;                       /* 6.0 (core/networks.py:169)                        */
     int32_t compute;                       /* CDRL_COMPUTE_*: arithmetic of the tower's 1x1 convolutions (default float32) */
+    int32_t freeze_trunk;                  /* 0 (default) or 1: frozen trunk, see below; other values fail at create       */
 } cdrl_config;
+
+/* freeze_trunk = 1 -- CARLAgent(update_dynamics=False) (reference core/carla_agent.py:77-80,351-373,430-463): the learner trains the
+ * policy and value heads on a fixed trunk.  Fixed at create (the planner then leaves out the trunk-backward scratch:
+ * cdrl_learner_workspace_bytes is smaller); parameter tables, region offsets and arena layouts are those of freeze_trunk = 0, so
+ * checkpoints and arenas interchange.  Every compute mode is supported.  On a frozen learner:
+ *   policy_forward_backward(_resample), policy_backward, value_forward_backward: train-mode trunk forward (batch statistics; every
+ *     trunk BatchNorm updates its moving statistics as in a full pass), the head's loss and backward.  No trunk backward runs:
+ *     the trunk's slice of the gradient arena is NOT written, and a communication stream set with cdrl_learner_set_comm_stream is
+ *     never released mid-pass (the whole arena is final when the pass's own stream is).
+ *   policy_apply, value_apply: per-tensor clip and Adam of the head (policy: old_policy <- policy in between) only; the trunk's
+ *     parameters, Adam moments and Adam step counter are untouched.
+ *   cdrl_learner_tail_offset: the trunk size (no trunk gradient becomes final mid-pass).
+ *   predict, update_old_policy, trunk_forward_train: unchanged. */
 
 /* CDRL_COMPUTE_BF16_OPERANDS (BASELINE.json configs[2]): the 1x1 convolutions of the image tower (core/architectures.py:130,140,
  * 170) multiply bf16-rounded operands on v_mfma_f32_32x32x16_bf16 -- forward, backward-data and filter gradient; float32
@@ -136,7 +150,8 @@ int cdrl_learner_share_hparams(cdrl_learner* l, const cdrl_learner* owner);
 int cdrl_learner_set_comm_stream(cdrl_learner* l, void* stream);
 /* Element offset, inside the trunk's trainable region, of the first TAIL tensor: gradients [tail_offset, trunk size) plus the
  * head's are final when the communication stream is released, gradients [0, tail_offset) (the image tower) only when the
- * pass's own stream is.  Equals the trunk size when the stream is never released mid-pass (hipGraph replay, CDRL_GRAPH=1). */
+ * pass's own stream is.  Equals the trunk size when the stream is never released mid-pass (hipGraph replay, CDRL_GRAPH=1; a learner
+ * created with freeze_trunk = 1, which writes no trunk gradient at all). */
 int64_t cdrl_learner_tail_offset(const cdrl_learner* l);
 int cdrl_learner_reset_optimizer_steps(cdrl_learner* l, void* stream);
 
@@ -165,7 +180,7 @@ int cdrl_learner_policy_forward_backward_resample(cdrl_learner* l, const cdrl_po
 int cdrl_learner_sequence_begin(cdrl_learner* l, void* stream);
 int cdrl_learner_sequence_end(cdrl_learner* l, void* stream);
 /* CARLAgent.apply_policy_gradients (core/carla_agent.py:375-388) + PPOAgent.apply_policy_gradients
- * (rl/agents/ppo.py:238-252): trunk Adam, per-tensor clip, old_policy <- policy, policy Adam. */
+ * (rl/agents/ppo.py:238-252): trunk Adam, per-tensor clip, old_policy <- policy, policy Adam (freeze_trunk = 1: no trunk Adam). */
 int cdrl_learner_policy_apply(cdrl_learner* l, void* stream);
 /* CARLAgent.get_value_gradients / apply_value_gradients (core/carla_agent.py:430-463;
  * rl/agents/ppo.py:264-275). */
