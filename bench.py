@@ -8,6 +8,10 @@ loss + per-tensor clip + old-policy copy + Adam, value head likewise (SURVEY.md 
 Inputs are resident in HBM when the timed region starts.  N>1: one process per GPU (torchrun),
 rollout buffer sharded by env shard, one RCCL all-reduce of the fused gradient arena per pass.
 
+A plain run sets up, warms up, times --steps update-steps, writes --dump-outputs if given and prints the line.  --full
+adds what the headline figure does not need: isolated-kernel rooflines, the configs[2] measurement (`secondary`), the
+CPU-oracle baseline and the figures read from the committed profiles (`mfma`, `dominant_kernel`).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -487,7 +491,7 @@ def cpu_baseline(B_sample, T, H, W, threads, one_thread_batch=32):
 
 def run_cpu_baseline_child(B_sample, T, H, W, threads, timeout=420):
     """The oracle runs in a CHILD process (plain subprocess, never exec from the GPU-initialised
-    process) with a hard wall-clock limit, so the default bench always finishes within minutes."""
+    process) with a hard wall-clock limit, so a --full run always finishes within minutes."""
     import subprocess
     env = dict(os.environ, OMP_NUM_THREADS=str(threads), MKL_NUM_THREADS=str(threads), HIP_VISIBLE_DEVICES='')
     cmd = [sys.executable, os.path.abspath(__file__), '--cpu-baseline-only', '--cpu-sample-batch', str(B_sample),
@@ -580,12 +584,16 @@ def main():
     ap.add_argument('--rollout-rows', action='store_true',
                     help='measure the rollout-side rows (predict for E environments, Beta sampling, augmentation, GAE, checkpoint I/O, '
                          'the agent-level collect / update cycle) with their CPU stand-ins and print that JSON instead of the benchmark line')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline timing, also measure what it does not need (1 GPU): the isolated-kernel rooflines, the '
+                         'configs[2] measurement (bf16 storage, B = 1024) as `secondary` and the CPU-oracle baseline in a child '
+                         'process; and report the MFMA / dominant-kernel figures of the committed profiles.  Without it the run '
+                         'sets up, warms up, times the update-steps, writes --dump-outputs and prints the line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU-oracle baseline')
     ap.add_argument('--no-kernel-rooflines', action='store_true',
-                    help='skip the isolated-kernel roofline launches (profiling passes: PMC totals and trace call counts then contain '
-                         'only the update-steps)')
+                    help='with --full: skip the isolated-kernel roofline launches (and the `secondary` measurement)')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='skip the configs[2] measurement (bf16 storage, B = 1024) that the default run appends as `secondary`')
+                    help='with --full: skip the configs[2] measurement (bf16 storage, B = 1024) appended as `secondary`')
     ap.add_argument('--cpu-sample-batch', type=int, default=256)
     ap.add_argument('--cpu-threads', type=int, default=min(16, os.cpu_count() or 1),
                     help='oracle intra-op threads; measured on the 2x64-core EPYC GPU host: 16 threads is the '
@@ -748,20 +756,23 @@ def main():
                                per_gpu_batch=B, global_batch=B * world, time_horizon=T, image=[H, W, 3],
                                parallelism=f'dp{world}', passes_per_step=2,
                                policy_loss='stored-actions' if args.stored_actions else 'resampled (reference-faithful)'),
-                   roofline=roof, mfma=pmc_mfma(ms_per_step), dominant_kernel=dominant_kernel(B, T, H, W), kernel_rooflines=kernel_rooflines(B, T) if (world == 1 and not args.no_kernel_rooflines) else None, gae_ms=round(gae_ms, 3), device_ms_per_step=round(dev_ms / args.steps, 3),
+                   roofline=roof, mfma=pmc_mfma(ms_per_step) if args.full else None,
+                   dominant_kernel=dominant_kernel(B, T, H, W) if args.full else None,
+                   kernel_rooflines=kernel_rooflines(B, T) if (args.full and world == 1 and not args.no_kernel_rooflines) else None, gae_ms=round(gae_ms, 3), device_ms_per_step=round(dev_ms / args.steps, 3),
                    device_ms_per_step_blocks=dict(blocks=[round(x, 3) for x in block_ms], min=round(min(block_ms), 3), median=round(sorted(block_ms)[len(block_ms) // 2], 3)),
                    host_enqueue_ms_per_step=round(host_ms, 3), env_overrides=env_overrides,
                    **(dict(shared_device='all ranks on cuda:0, collectives through gloo: a functional check of the N > 1 path, not a scaling figure') if share_device else {}),
                    final_losses=dict(policy=loss_p, value=loss_v))
-        # (--no-kernel-rooflines marks a profiling pass: PMC totals and trace call counts must contain only the headline update-steps)
-        if world == 1 and not args.no_secondary and not args.no_kernel_rooflines and (B, H, W, args.dtype) == (256, 90, 120, 'f32'):
+        # (with --full, --no-kernel-rooflines marks a profiling pass: PMC totals and trace call counts must contain only the headline
+        # update-steps)
+        if args.full and world == 1 and not args.no_secondary and not args.no_kernel_rooflines and (B, H, W, args.dtype) == (256, 90, 120, 'f32'):
             del dp, eng, states, pol, val                   # (the headline engine's 6 GB workspace is not needed any more)
             torch.cuda.empty_cache()
             try:
                 out['secondary'] = secondary_config3(dev)
             except Exception as e:                          # the headline line must survive a failure of the extra measurement
                 out['secondary'] = dict(error=repr(e))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = run_cpu_baseline_child(args.cpu_sample_batch, T, H, W, args.cpu_threads)
     else:
         out = None

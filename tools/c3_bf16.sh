@@ -8,7 +8,7 @@ out=gpurun_out/c3_$r
 mkdir -p $out
 for a in "--dtype f32 --batch 1024 --steps 8" "--dtype bf16 --batch 1024 --steps 8" "--dtype f32 --steps 30" "--dtype bf16 --steps 30"; do
   echo "== $a" >> $out/bench_lines.txt
-  timeout 600 python bench.py --no-cpu-baseline $a 2>/dev/null | tail -1 >> $out/bench_lines.txt
+  timeout 600 python bench.py --full --no-cpu-baseline $a 2>/dev/null | tail -1 >> $out/bench_lines.txt
 done
 bash tools/prof_bench.sh c3$r --dtype bf16 --batch 1024 > $out/prof.log 2>&1
 cp gpurun_out/prof_c3$r/summary.md $out/kernel_trace_summary.md

@@ -4,7 +4,7 @@ r=$1
 cd $GRAFT_REPO_ROOT
 out=gpurun_out/final_$r
 mkdir -p $out
-timeout 900 python bench.py > $out/bench_full.log 2>$out/bench_full.err
+timeout 900 python bench.py --full > $out/bench_full.log 2>$out/bench_full.err
 tail -1 $out/bench_full.log > $out/bench.json
 bash tools/prof_bench.sh $r > $out/prof.log 2>&1
 cp gpurun_out/prof_$r/summary.md $out/kernel_trace_summary.md
@@ -35,7 +35,7 @@ run --batch 1024 --steps 8
 run --batch 64 --steps 30
 echo "== RCCL path (early buckets on the communication stream) forced on 1 GPU (CDRL_FORCE_COLLECTIVES=1, torchrun-style env)" >> $cfg
 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 CDRL_FORCE_COLLECTIVES=1 timeout 600 python bench.py --no-cpu-baseline --steps 30 --warmup 5 2>/dev/null | grep '^{"metric' | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['value'])" >> $cfg 2>&1
-echo "== isolated kernels (scratch-free: bench.py kernel_rooflines of the default run)" >> $cfg
+echo "== isolated kernels (scratch-free: bench.py kernel_rooflines of the --full run)" >> $cfg
 python3 -c "
 import json
 d=json.load(open('$out/bench.json'))

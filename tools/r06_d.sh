@@ -3,8 +3,7 @@
 mkdir -p gpurun_out/r06d
 python -m pytest tests -q -m gpu -x --durations=40 > gpurun_out/r06d/gpu_tests.log 2>&1; echo "gpu tests rc=$?" >> gpurun_out/r06d/gpu_tests.log
 tail -n 5 gpurun_out/r06d/gpu_tests.log
-python bench.py --no-cpu-baseline --no-secondary --steps 200 > gpurun_out/r06d/bench.log 2>&1
-tail -n 1 gpurun_out/r06d/bench.log | python -c "
+python bench.py --full --no-cpu-baseline --no-secondary --steps 200 2>/dev/null | tail -n 1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print(d['ms_per_step'], d['value'])
