@@ -19,10 +19,15 @@ class Config(C.Structure):
                 ('stem', C.c_int32), ('stage_c', C.c_int32 * 3), ('stage_n', C.c_int32 * 3), ('last', C.c_int32),
                 ('feat', C.c_int32), ('rnn_image', C.c_int32), ('rnn_small', C.c_int32), ('dyn', C.c_int32),
                 ('head', C.c_int32), ('exp_scale', C.c_float), ('compute', C.c_int32),
-                ('freeze_trunk', C.c_int32)]
+                ('freeze_trunk', C.c_int32), ('optimizer', C.c_int32), ('polyak', C.c_float)]
 
 
 COMPUTE_F32, COMPUTE_BF16_OPERANDS, COMPUTE_BF16_STORAGE = 0, 1, 2
+# cdrl_config.optimizer: CDRL_OPT_* in this order (include/cdrl.h); the reference's optimizer names (rl/utils.py:29-37)
+OPTIMIZERS = ('adam', 'sgd', 'rmsprop', 'adagrad', 'adadelta', 'adamax', 'nadam', 'ftrl')
+# Keras' slot names per optimizer: (slot kept in the adam_m arena, slot kept in the adam_v arena), None where unused
+OPTIMIZER_SLOTS = dict(adam=('m', 'v'), sgd=(None, None), rmsprop=(None, 'rms'), adagrad=(None, 'accumulator'),
+                       adadelta=('accum_var', 'accum_grad'), adamax=('m', 'v'), nadam=('m', 'v'), ftrl=('linear', 'accumulator'))
 
 
 class ParamInfo(C.Structure):
@@ -62,6 +67,7 @@ PROTOTYPES = {
     'cdrl_diag_active': (_i, []),
     'cdrl_crc32c': (C.c_uint32, [C.c_uint32, C.c_void_p, C.c_size_t]),
     'cdrl_config_default': (None, [C.POINTER(Config)]),
+    'cdrl_optimizer_slots': (_i, [_i, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     'cdrl_learner_create': (_i, [C.POINTER(Config), C.POINTER(_L)]),
     'cdrl_learner_destroy': (None, [_L]),
     'cdrl_learner_param_count': (_i, [_L, _i]),

@@ -101,7 +101,9 @@ class CARLAgent(PPOAgent):
         `compute='bf16'`: the engine's bf16-operand mode (not in the reference; CARLANetwork docstring).
         `update_dynamics=False`: frozen trunk -- every minibatch step runs the trunk forward in training mode (its BatchNorm moving
         statistics update) and trains the policy / value heads only; `dynamics_lr` is then accepted and unused, as in the
-        reference (core/carla_agent.py:351-373,430-463).  Typical use: load a trained trunk with `load_full=False`, fine-tune the heads."""
+        reference (core/carla_agent.py:351-373,430-463).  Typical use: load a trained trunk with `load_full=False`, fine-tune the heads.
+        `optimizer=name` (PPOAgent): one Keras optimizer class for the policy, value AND dynamics optimizers, as the reference builds
+        all three from the one name (core/carla_agent.py:123-124); `polyak < 1` averages the policy / value heads, not the trunk."""
         assert aug_intensity >= 0.0
         network_spec = dict(kwargs.pop('network', {}))
         network_spec.setdefault('network', CARLANetwork)

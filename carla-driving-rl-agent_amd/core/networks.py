@@ -62,7 +62,9 @@ class CARLANetwork(Network):
         (include/cdrl.h CDRL_COMPUTE_BF16_OPERANDS, BASELINE.json configs[2]; see DESIGN.md section 7 for what it costs numerically).
         update_dynamics=False: frozen trunk -- the learner engines train the policy / value heads only (cdrl_config.freeze_trunk);
         CARLAgent passes its own update_dynamics.  (The reference's keyword defaults to False but is never read there; here it
-        drives the engine, so the default is the agent's.)"""
+        drives the engine, so the default is the agent's.)
+        The agent's optimizer name and polyak coefficient (PPOAgent(optimizer=..., polyak=...)) configure every engine built here
+        (cdrl_config.optimizer / polyak)."""
         super().__init__(agent)
         env = agent.env
         T = env.time_horizon
@@ -85,7 +87,8 @@ class CARLANetwork(Network):
                         stem=img['stem'], stage_c=img['stage_c'], stage_n=img['stage_n'], last=img['last'],
                         feat=self.dynamics_spec['features']['road']['units'], rnn_image=self.dynamics_spec['rnn']['image'],
                         rnn_small=self.dynamics_spec['rnn']['road'], dyn=self.dynamics_spec['units'],
-                        head=p_branch['units'], exp_scale=self.exp_scale, compute=compute, freeze_trunk=not update_dynamics)
+                        head=p_branch['units'], exp_scale=self.exp_scale, compute=compute, freeze_trunk=not update_dynamics,
+                        optimizer=getattr(agent, 'optimizer_name', 'adam'), polyak=float(getattr(agent, 'polyak_coeff', 1.0)))
         self.device = agent.device
         self.engine = LearnerEngine(agent.batch_size, device=self.device, **self.cfg)          # learner minibatches
         self._rollouts = {}                # number of environments E -> inference engine over the same arenas

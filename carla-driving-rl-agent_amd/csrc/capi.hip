@@ -83,6 +83,29 @@ void cdrl_config_default(cdrl_config* c) {
     c->dyn = d.dyn; c->head = d.head; c->exp_scale = d.exp_scale;
     c->compute = d.compute;
     c->freeze_trunk = d.freeze_trunk;
+    c->optimizer = d.optimizer;
+    c->polyak = d.polyak;
+}
+
+int cdrl_optimizer_slots(int optimizer, int32_t* used, float* init) {
+    // {uses adam_m, uses adam_v, initial adam_m, initial adam_v} of every CDRL_OPT_* (include/cdrl.h table)
+    static const float tab[8][4] = {{1, 1, 0.0f, 0.0f},     // adam: m, v
+                                    {0, 0, 0.0f, 0.0f},     // sgd
+                                    {0, 1, 0.0f, 0.0f},     // rmsprop: -, rms
+                                    {0, 1, 0.0f, 0.1f},     // adagrad: -, accumulator (Keras initial_accumulator_value)
+                                    {1, 1, 0.0f, 0.0f},     // adadelta: accum_var, accum_grad
+                                    {1, 1, 0.0f, 0.0f},     // adamax: m, v
+                                    {1, 1, 0.0f, 0.0f},     // nadam: m, v
+                                    {1, 1, 0.0f, 0.1f}};    // ftrl: linear, accumulator (Keras initial_accumulator_value)
+    if (optimizer < CDRL_OPT_ADAM || optimizer > CDRL_OPT_FTRL) {
+        cdrl::set_error("cdrl_optimizer_slots: unknown optimizer %d", optimizer);
+        return -1;
+    }
+    for (int i = 0; i < 2; ++i) {
+        if (used) used[i] = (int32_t)tab[optimizer][i];
+        if (init) init[i] = tab[optimizer][2 + i];
+    }
+    return 0;
 }
 
 int cdrl_learner_create(const cdrl_config* c, cdrl_learner** out) {
@@ -116,6 +139,16 @@ int cdrl_learner_create(const cdrl_config* c, cdrl_learner** out) {
         return -1;
     }
     d.freeze_trunk = c->freeze_trunk;
+    if (c->optimizer < CDRL_OPT_ADAM || c->optimizer > CDRL_OPT_FTRL) {
+        cdrl::set_error("cdrl_learner_create: unknown optimizer %d (CDRL_OPT_ADAM .. CDRL_OPT_FTRL)", c->optimizer);
+        return -1;
+    }
+    d.optimizer = c->optimizer;
+    if (!(c->polyak > 0.0f && c->polyak <= 1.0f)) {      // (NaN fails too)
+        cdrl::set_error("cdrl_learner_create: polyak must be in (0, 1] (got %g)", (double)c->polyak);
+        return -1;
+    }
+    d.polyak = c->polyak;
     if (cdrl::diag_active()) {      // loud, every time: results of this learner are WRONG by request (timing diagnostics)
         char ov[2048];
         cdrl::env_overrides(ov, (int)sizeof(ov));
@@ -232,6 +265,12 @@ int cdrl_learner_share_hparams(cdrl_learner* l, const cdrl_learner* owner) {
     CHECK_L(l);
     if (!owner || !owner->impl || !owner->impl->dev_hp() || !l->impl->dev_hp()) {
         cdrl::set_error("cdrl_learner_share_hparams: both learners must be bound");
+        return -1;
+    }
+    const Config &a = l->impl->config(), &b = owner->impl->config();
+    if (a.optimizer != b.optimizer || a.polyak != b.polyak) {      // one optimizer: its state and step counters must agree
+        cdrl::set_error("cdrl_learner_share_hparams: optimizer / polyak differ (%d, %g vs the owner's %d, %g)", a.optimizer,
+                        (double)a.polyak, b.optimizer, (double)b.polyak);
         return -1;
     }
     l->impl->share_hp(*owner->impl);

@@ -430,8 +430,10 @@ struct DevHP {
     float clip_ratio, entropy_coef;
     float clip_norm_policy, clip_norm_value;   // <= 0 : no clipping
     float beta1, beta2, eps;
-    int t_policy, t_value, t_dynamics;         // Adam step counters (incremented on device)
-    int pad[3];
+    int t_policy, t_value, t_dynamics;         // optimizer step counters (incremented on device)
+    // Nadam's running product of the momentum schedule, one per optimizer (1 at the start; S_t of the last step).  Behind the
+    // counters, so that an upload of the float block (upload_hp: up to t_policy) never overwrites it
+    float m_cache_policy, m_cache_value, m_cache_dynamics;
 };
 struct TensorSeg {      // one parameter tensor inside a flat arena
     int64_t off;
@@ -443,13 +445,22 @@ struct TensorSeg {      // one parameter tensor inside a flat arena
 int tensor_sqnorms(const float* g, const TensorSeg* segs_dev, int ntensors, const int* chunk_tensor_dev,
                    const int64_t* chunk_off_dev, int nchunks, double* chunk_part, float* sqnorms, hipStream_t st,
                    DevHP* tick_hp = nullptr, int tick_mask = 0, bool fold_final = false);
-// tick_hp / tick_mask (1 policy, 2 value, 4 trunk): the chunk kernel also advances those Adam step counters; fold_final: no second
+// tick_hp / tick_mask (1 policy, 2 value, 4 trunk): the chunk kernel also advances those step counters (| 8: and, for Nadam, their
+// m_caches to S_t of the new count); fold_final: no second
 // stage -- the consumer folds the chunk partials (clip_adam with chunk_part)
 int clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev /*or null*/,
               const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms /*or null*/,
               DevHP* hp, int which, hipStream_t st, const double* chunk_part = nullptr, int ticked = 0);
 // chunk_part: per-tensor norms folded here from tensor_sqnorms' chunk partials; ticked: the step counter was advanced already
 int adam_tick(DevHP* hp, int which, hipStream_t st);
+// The other optimizers of cdrl_config.optimizer (include/cdrl.h table; opt = CDRL_OPT_*) and polyak averaging, same arguments and
+// clip as clip_adam; m / v are the optimizer's slots in the adam_m / adam_v arenas.  Adam with polyak 1 IS clip_adam.
+// polyak < 1 (heads only): p = a * p_new + c * p_old in the same pass.
+int clip_update(int opt, float polyak, float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev,
+                const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms, DevHP* hp, int which,
+                hipStream_t st, const double* chunk_part = nullptr, int ticked = 0);
+// counters to 0, Nadam m_caches to 1 (cdrl_learner_reset_optimizer_steps)
+int reset_steps(DevHP* hp, hipStream_t st);
 int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, hipStream_t st);
 
 // ---------------------------------------------------------------- GAE (gae.hip)

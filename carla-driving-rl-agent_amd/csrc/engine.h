@@ -32,6 +32,8 @@ struct Config {
                             //    is bf16 in HBM (statistics, partials, coefficients, weights, accumulators stay float32 / double)
     int freeze_trunk = 0;   // 1: the passes train the heads only on a fixed trunk (reference CARLAgent(update_dynamics=False)): train-mode
                             //    trunk forward (batch statistics, moving statistics updated), no trunk backward, no trunk Adam step
+    int optimizer = 0;      // CDRL_OPT_* of the policy, value and dynamics optimizers (include/cdrl.h table)
+    float polyak = 1.0f;    // < 1: polyak averaging of the heads after their optimizer step
 };
 
 enum Model : int { M_TRUNK = 0, M_POLICY = 1, M_VALUE = 2, M_OLD_POLICY = 3 };

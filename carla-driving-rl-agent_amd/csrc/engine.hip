@@ -14,6 +14,7 @@
 #include <cstdio>
 
 #include "engine.h"
+#include "../../include/cdrl.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -37,6 +38,7 @@ Learner::Learner(const Config& cfg) : cfg_(cfg) {
     hp_host_.beta1 = 0.9f;
     hp_host_.beta2 = 0.999f;
     hp_host_.eps = 1e-7f;
+    hp_host_.m_cache_policy = hp_host_.m_cache_value = hp_host_.m_cache_dynamics = 1.0f;
     at_ = cfg_.compute == 2 ? 1 : 0;
     guard_ = cdrl_getenv("CDRL_GUARD") && atoi(cdrl_getenv("CDRL_GUARD")) == 1;
     build(true);
@@ -1811,7 +1813,8 @@ void Learner::build(bool dry) {
     note_named("sample.du_dalpha", sample_da_, (size_t)cfg_.B * A * sizeof(float));
     note_named("sample.du_dbeta", sample_db_, (size_t)cfg_.B * A * sizeof(float));
     hp_dev_ = reinterpret_cast<DevHP*>(alloc(sizeof(DevHP) / sizeof(float) + 4));
-    note_named("hparams", hp_dev_, sizeof(DevHP));      // 10 floats (lr x3, clip, entropy, clip norms x2, beta1, beta2, eps), 3 int step counters
+    note_named("hparams", hp_dev_, sizeof(DevHP));      // 10 floats (lr x3, clip, entropy, clip norms x2, beta1, beta2, eps), 3 int step counters,
+                                                        // 3 Nadam m_caches
     // optimiser tables
     for (int m = 1; m <= 2; ++m) {
         SegTable& s = seg_[m];
@@ -2008,7 +2011,7 @@ int Learner::upload_hp(hipStream_t st) {
 }
 
 int Learner::reset_counters(hipStream_t st) {
-    CDRL_HIP(hipMemsetAsync(reinterpret_cast<char*>(hp_dev_) + offsetof(DevHP, t_policy), 0, 3 * sizeof(int), st));
+    CDRL_TRY(reset_steps(hp_dev_, st));      // counters 0, Nadam m_caches 1
     tail_invalidate(st);
     return 0;
 }
@@ -2180,18 +2183,20 @@ int Learner::policy_apply(hipStream_t caller) {
 int Learner::policy_apply_impl(hipStream_t st) {
     // order: trunk Adam (unclipped, F9) -> clip -> old_policy <- policy -> policy Adam
     // frozen trunk: no trunk Adam step, and the trunk's step counter stays where it is (reference ppo.py:238-252 on the heads only)
+    // (another cdrl_config.optimizer: its step in place of Adam's, same launches; polyak < 1: the policy is averaged in its update)
     const int64_t to = tr_offset(M_TRUNK), po = tr_offset(M_POLICY);
+    const int opt = cfg_.optimizer, nadam = opt == CDRL_OPT_NADAM ? 8 : 0;
     if (!frozen())
-        CDRL_TRY(clip_adam(buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK], nullptr,
-                           nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
+        CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK],
+                             nullptr, nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
     SegTable& s = seg_[M_POLICY];
     // four launches instead of seven (round 6): the chunk kernel of the norms also advances the trunk's step counter (its update ran in front)
     // and the policy's (its update runs behind and is told so); the per-tensor fold of the chunk partials happens inside clip_adam
     CDRL_TRY(tensor_sqnorms(buf_.grads + po, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part,
-                            s.sqnorms, st, hp_dev_, frozen() ? 1 : 4 | 1, true));
+                            s.sqnorms, st, hp_dev_, (frozen() ? 1 : 4 | 1) | nadam, true));
     CDRL_TRY(update_old_policy_impl(st));
-    return clip_adam(buf_.params + po, buf_.grads + po, buf_.adam_m + po, buf_.adam_v + po, tr_size_[M_POLICY], s.chunk_tensor,
-                     s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 0, st, s.chunk_part, 1);
+    return clip_update(opt, cfg_.polyak, buf_.params + po, buf_.grads + po, buf_.adam_m + po, buf_.adam_v + po, tr_size_[M_POLICY],
+                       s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 0, st, s.chunk_part, 1);
 }
 
 int Learner::value_apply(hipStream_t caller) {
@@ -2200,14 +2205,15 @@ int Learner::value_apply(hipStream_t caller) {
 
 int Learner::value_apply_impl(hipStream_t st) {
     const int64_t to = tr_offset(M_TRUNK), vo = tr_offset(M_VALUE);
+    const int opt = cfg_.optimizer, nadam = opt == CDRL_OPT_NADAM ? 8 : 0;
     if (!frozen())
-        CDRL_TRY(clip_adam(buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK], nullptr,
-                           nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
+        CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK],
+                             nullptr, nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
     SegTable& s = seg_[M_VALUE];
     CDRL_TRY(tensor_sqnorms(buf_.grads + vo, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part,
-                            s.sqnorms, st, hp_dev_, frozen() ? 2 : 4 | 2, true));       // (see policy_apply_impl)
-    return clip_adam(buf_.params + vo, buf_.grads + vo, buf_.adam_m + vo, buf_.adam_v + vo, tr_size_[M_VALUE], s.chunk_tensor,
-                     s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 1, st, s.chunk_part, 1);
+                            s.sqnorms, st, hp_dev_, (frozen() ? 2 : 4 | 2) | nadam, true));       // (see policy_apply_impl)
+    return clip_update(opt, cfg_.polyak, buf_.params + vo, buf_.grads + vo, buf_.adam_m + vo, buf_.adam_v + vo, tr_size_[M_VALUE],
+                       s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 1, st, s.chunk_part, 1);
 }
 
 int Learner::predict(const float* image, const float* road, const float* vehicle, const float* navigation,

@@ -9,11 +9,18 @@
 // hipGraph of the whole update step can be replayed while learning rates change between steps.
 // One workgroup handles one 1024-element chunk of one tensor: HBM-bound streaming, no atomics,
 // norms reduced in two deterministic stages.
+// The seven other Keras optimizers of cdrl_config.optimizer and polyak averaging: clip_update (table in include/cdrl.h).
 #include "cdrl_kernels.h"
+#include "../../include/cdrl.h"
 
 namespace cdrl {
 
 #define CHUNK 1024
+
+// Keras Nadam's momentum schedule (schedule decay 0.004), float32 as TensorFlow computes it: mu_t = beta1 (1 - 0.5 * 0.96^(0.004 t)).
+// S_t = m_cache * mu_t is formed by the trunk's update (ahead of its tick) and stored by the chunk kernel that ticks the counter:
+// one function, so both produce the same bits.
+__device__ __forceinline__ float nadam_mu(float b1, int t) { return b1 * (1.0f - 0.5f * powf(0.96f, 0.004f * (float)t)); }
 
 __global__ void __launch_bounds__(256) sqnorm_chunk_kernel(const float* __restrict__ g,
                                                            const TensorSeg* __restrict__ segs,
@@ -24,11 +31,16 @@ __global__ void __launch_bounds__(256) sqnorm_chunk_kernel(const float* __restri
     const int c = blockIdx.x;
     // Adam step counters advanced here instead of by launches of their own: the trunk's (its update ran in FRONT of this kernel) and the
     // head's, whose update runs BEHIND it and is told so (clip_adam's `ticked`)
-    // (bit mask: 1 policy, 2 value, 4 trunk)
+    // (bit mask: 1 policy, 2 value, 4 trunk; 8: Nadam -- each ticked optimizer's m_cache also becomes S_t of its new count)
     if (tick > 0 && c == 0 && threadIdx.x == 0) {
         if (tick & 1) hp->t_policy += 1;
         if (tick & 2) hp->t_value += 1;
         if (tick & 4) hp->t_dynamics += 1;
+        if (tick & 8) {
+            if (tick & 1) hp->m_cache_policy = hp->m_cache_policy * nadam_mu(hp->beta1, hp->t_policy);
+            if (tick & 2) hp->m_cache_value = hp->m_cache_value * nadam_mu(hp->beta1, hp->t_value);
+            if (tick & 4) hp->m_cache_dynamics = hp->m_cache_dynamics * nadam_mu(hp->beta1, hp->t_dynamics);
+        }
     }
     const TensorSeg s = segs[chunk_tensor[c]];
     const int64_t beg = chunk_off[c];
@@ -138,6 +150,172 @@ int clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const int
     const int grid = chunk_tensor_dev ? nchunks : (int)cdiv64(n, CHUNK);
     hipLaunchKernelGGL(clip_adam_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, chunk_tensor_dev, chunk_off_dev,
                        segs_dev, sqnorms, hp, which, chunk_part, ticked);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
+// clip + one step of the optimizer OPT (include/cdrl.h table) + optional polyak averaging.  The chunk / clip prologue is
+// clip_adam_kernel's, kept as a copy so that Adam's own kernel stays exactly as it was.  Per element one streaming pass over p, g
+// and the slots the optimizer uses (none for SGD; never the others).
+template <int OPT>
+__global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                          const int* __restrict__ chunk_tensor,
+                                                          const int64_t* __restrict__ chunk_off,
+                                                          const TensorSeg* __restrict__ segs,
+                                                          const float* __restrict__ sqnorms, const DevHP* __restrict__ hp,
+                                                          int which, const double* __restrict__ chunk_part, int ticked,
+                                                          int blend, float pa, float pc) {
+    int64_t beg, end;
+    float cn = 0.0f, denom = 1.0f;
+    const float clip_norm = which == 0 ? hp->clip_norm_policy : (which == 1 ? hp->clip_norm_value : 0.0f);
+    if (chunk_tensor) {
+        const int c = blockIdx.x;
+        const int t = chunk_tensor[c];
+        const TensorSeg s = segs[t];
+        beg = chunk_off[c];
+        end = beg + CHUNK;
+        if (end > s.off + s.n) end = s.off + s.n;
+        if ((sqnorms || chunk_part) && clip_norm > 0.0f) {
+            float l2;
+            if (chunk_part) {       // (clip_adam_kernel: same fold, same bits)
+                const int lane = threadIdx.x & 63;
+                double acc = 0.0;
+                for (int cc = lane; cc < s.nchunks; cc += 64) acc += chunk_part[s.first_chunk + cc];
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+                l2 = (float)__shfl(acc, 0, 64);
+            } else {
+                l2 = sqnorms[t];
+            }
+            const float norm = l2 > 0.0f ? sqrtf(l2) : l2;
+            cn = clip_norm;
+            denom = fmaxf(norm, clip_norm);
+        }
+    } else {
+        beg = (int64_t)blockIdx.x * CHUNK;
+        end = beg + CHUNK;
+        if (end > n) end = n;
+    }
+    const float lr = which == 0 ? hp->lr_policy : (which == 1 ? hp->lr_value : hp->lr_dynamics);
+    const int t1 = (which == 0 ? hp->t_policy : (which == 1 ? hp->t_value : hp->t_dynamics)) + (ticked ? 0 : 1);
+    const float b1 = hp->beta1, b2 = hp->beta2, eps = hp->eps;
+    // per-step scalars, float32 (Keras _prepare_local / the training ops' scalar operands)
+    float k0 = 0.0f, k1 = 0.0f, k2 = 0.0f, k3 = 0.0f, k4 = 0.0f;
+    if (OPT == CDRL_OPT_ADAM) {
+        k0 = lr * sqrtf(1.0f - powf(b2, (float)t1)) / (1.0f - powf(b1, (float)t1));
+    } else if (OPT == CDRL_OPT_RMSPROP) {
+        k0 = 0.9f;
+        k1 = 1.0f - k0;
+    } else if (OPT == CDRL_OPT_ADADELTA) {
+        k0 = 0.95f;
+        k1 = 1.0f - k0;
+    } else if (OPT == CDRL_OPT_ADAMAX) {
+        k0 = lr / (1.0f - powf(b1, (float)t1));
+    } else if (OPT == CDRL_OPT_NADAM) {
+        const float mc = which == 0 ? hp->m_cache_policy : (which == 1 ? hp->m_cache_value : hp->m_cache_dynamics);
+        const float mu = nadam_mu(b1, t1), mu1 = nadam_mu(b1, t1 + 1);
+        const float st = ticked ? mc : mc * mu;      // S_t (ticked: the chunk kernel stored it already)
+        k0 = 1.0f - mu;                              // one_minus_m_t
+        k1 = 1.0f - st;                              // one_minus_m_schedule_new
+        k2 = 1.0f - st * mu1;                        // one_minus_m_schedule_next
+        k3 = mu1;                                    // m_t_1
+        k4 = 1.0f - powf(b2, (float)t1);             // v_t_prime_denominator
+    }
+    for (int64_t i = beg + threadIdx.x; i < end; i += 256) {
+        float gi = g[i];
+        if (cn > 0.0f) gi = (gi * cn) / denom;
+        const float po = p[i];
+        float pn;
+        if (OPT == CDRL_OPT_ADAM) {
+            float mi = m[i], vi = v[i];
+            mi += (gi - mi) * (1.0f - b1);
+            vi += (gi * gi - vi) * (1.0f - b2);
+            m[i] = mi;
+            v[i] = vi;
+            pn = po - (mi * k0) / (sqrtf(vi) + eps);
+        } else if (OPT == CDRL_OPT_SGD) {
+            pn = po - gi * lr;
+        } else if (OPT == CDRL_OPT_RMSPROP) {
+            const float r = k0 * v[i] + k1 * (gi * gi);
+            v[i] = r;
+            pn = po - lr * gi / (sqrtf(r) + eps);
+        } else if (OPT == CDRL_OPT_ADAGRAD) {
+            const float a = v[i] + gi * gi;
+            v[i] = a;
+            pn = po - gi * lr / (sqrtf(a) + eps);
+        } else if (OPT == CDRL_OPT_ADADELTA) {
+            const float a = v[i] * k0 + (gi * gi) * k1;           // accum_grad
+            const float d = m[i];                                 // accum_var
+            const float u = sqrtf(d + eps) * (1.0f / sqrtf(a + eps)) * gi;
+            v[i] = a;
+            m[i] = d * k0 + (u * u) * k1;
+            pn = po - u * lr;
+        } else if (OPT == CDRL_OPT_ADAMAX) {
+            float mi = m[i];
+            mi += (gi - mi) * (1.0f - b1);
+            const float vi = fmaxf(b2 * v[i], fabsf(gi));
+            m[i] = mi;
+            v[i] = vi;
+            pn = po - k0 * (mi / (vi + eps));
+        } else if (OPT == CDRL_OPT_NADAM) {
+            const float gp = gi / k1;
+            const float mi = b1 * m[i] + (1.0f - b1) * gi;
+            const float vi = b2 * v[i] + (1.0f - b2) * (gi * gi);
+            m[i] = mi;
+            v[i] = vi;
+            const float mbar = k0 * gp + k3 * (mi / k2);
+            pn = po - lr * mbar / (sqrtf(vi / k4) + eps);
+        } else {      // CDRL_OPT_FTRL
+            const float nn = v[i], n1 = nn + gi * gi;
+            const float z = m[i] + (gi - (sqrtf(n1) - sqrtf(nn)) / lr * po);
+            m[i] = z;
+            v[i] = n1;
+            pn = fabsf(z) > 0.0f ? -z / (sqrtf(n1) / lr) : 0.0f;
+        }
+        if (blend) pn = pa * pn + pc * po;      // polyak: two float32 products, one float32 sum (numpy's order)
+        p[i] = pn;
+    }
+}
+
+int clip_update(int opt, float polyak, float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev,
+                const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms, DevHP* hp, int which,
+                hipStream_t st, const double* chunk_part, int ticked) {
+    const int blend = polyak < 1.0f;
+    if (opt == CDRL_OPT_ADAM && !blend)
+        return clip_adam(p, g, m, v, n, chunk_tensor_dev, chunk_off_dev, nchunks, segs_dev, sqnorms, hp, which, st, chunk_part, ticked);
+    const float pa = polyak, pc = (float)(1.0 - (double)polyak);
+    const int grid = chunk_tensor_dev ? nchunks : (int)cdiv64(n, CHUNK);
+#define CDRL_CLIP_UPDATE(O)                                                                                                      \
+    hipLaunchKernelGGL(clip_update_kernel<O>, dim3(grid), dim3(256), 0, st, p, g, m, v, n, chunk_tensor_dev, chunk_off_dev,       \
+                       segs_dev, sqnorms, hp, which, chunk_part, ticked, blend, pa, pc)
+    switch (opt) {
+        case CDRL_OPT_ADAM: CDRL_CLIP_UPDATE(CDRL_OPT_ADAM); break;
+        case CDRL_OPT_SGD: CDRL_CLIP_UPDATE(CDRL_OPT_SGD); break;
+        case CDRL_OPT_RMSPROP: CDRL_CLIP_UPDATE(CDRL_OPT_RMSPROP); break;
+        case CDRL_OPT_ADAGRAD: CDRL_CLIP_UPDATE(CDRL_OPT_ADAGRAD); break;
+        case CDRL_OPT_ADADELTA: CDRL_CLIP_UPDATE(CDRL_OPT_ADADELTA); break;
+        case CDRL_OPT_ADAMAX: CDRL_CLIP_UPDATE(CDRL_OPT_ADAMAX); break;
+        case CDRL_OPT_NADAM: CDRL_CLIP_UPDATE(CDRL_OPT_NADAM); break;
+        case CDRL_OPT_FTRL: CDRL_CLIP_UPDATE(CDRL_OPT_FTRL); break;
+        default: set_error("clip_update: unknown optimizer %d", opt); return -1;
+    }
+#undef CDRL_CLIP_UPDATE
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
+__global__ void reset_steps_kernel(DevHP* hp) {
+    hp->t_policy = 0;
+    hp->t_value = 0;
+    hp->t_dynamics = 0;
+    hp->m_cache_policy = 1.0f;
+    hp->m_cache_value = 1.0f;
+    hp->m_cache_dynamics = 1.0f;
+}
+
+int reset_steps(DevHP* hp, hipStream_t st) {
+    hipLaunchKernelGGL(reset_steps_kernel, dim3(1), dim3(1), 0, st, hp);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

@@ -29,6 +29,10 @@ def make_config(B, T=4, H=90, W=120, road=9, vehicle=4, navigation=5, A=2, **kw)
             v = {'f32': _lib.COMPUTE_F32, 'bf16': _lib.COMPUTE_BF16_OPERANDS, 'bf16s': _lib.COMPUTE_BF16_STORAGE}[v]
         if k == 'freeze_trunk' and isinstance(v, bool):
             v = int(v)
+        if k == 'optimizer' and isinstance(v, str):
+            if v.lower() not in _lib.OPTIMIZERS:
+                raise _lib.CdrlError(f'unknown optimizer {v!r}; select one of {_lib.OPTIMIZERS}')
+            v = _lib.OPTIMIZERS.index(v.lower())
         if k in ('stage_c', 'stage_n'):
             for i in range(3):
                 getattr(cfg, k)[i] = v[i]
@@ -58,16 +62,26 @@ class LearnerEngine:
     def __init__(self, B, device: Optional[str] = 'cuda:0', share_with: 'LearnerEngine' = None, **cfg):
         """device=None -> host-only inspection (parameter tables, workspace size; no HIP calls).
         share_with -> reuse another engine's parameter arenas (e.g. a B=1 rollout engine); the new engine inherits its
-        freeze_trunk unless one is given.
-        freeze_trunk=True -> the passes train the heads only on a fixed trunk (cdrl_config.freeze_trunk, include/cdrl.h)."""
+        freeze_trunk, optimizer and polyak unless they are given.
+        freeze_trunk=True -> the passes train the heads only on a fixed trunk (cdrl_config.freeze_trunk, include/cdrl.h).
+        optimizer -> one of _lib.OPTIMIZERS, any letter case (the reference's get_optimizer_by_name), for the policy, value and
+        dynamics optimizers; its slots live in the adam_m / adam_v arenas (optimizer_slots).  polyak in (0, 1]: < 1 averages the
+        heads after each optimizer step (cdrl_config.optimizer / polyak, include/cdrl.h)."""
         self.lib = _lib.load()
-        if share_with is not None and 'freeze_trunk' not in cfg:
-            cfg['freeze_trunk'] = share_with.frozen
+        if share_with is not None:
+            cfg.setdefault('freeze_trunk', share_with.frozen)
+            cfg.setdefault('optimizer', share_with.optimizer)
+            cfg.setdefault('polyak', share_with.polyak)
         self.cfg = make_config(B, **cfg)
         h = C.c_void_p()
         _lib.check(self.lib.cdrl_learner_create(C.byref(self.cfg), C.byref(h)), 'cdrl_learner_create')
         self.h = h
         self.frozen = bool(self.cfg.freeze_trunk)
+        self.optimizer = _lib.OPTIMIZERS[self.cfg.optimizer]
+        self.polyak = float(self.cfg.polyak)
+        used, init = (C.c_int32 * 2)(), (C.c_float * 2)()
+        _lib.check(self.lib.cdrl_optimizer_slots(self.cfg.optimizer, used, init), 'cdrl_optimizer_slots')
+        self.slot_init = (float(init[0]), float(init[1]))       # initial value of the adam_m / adam_v arena's slot
         self.tables = {m: ParamTable(self.lib, h, mid) for m, mid in (('trunk', TRUNK), ('policy', POLICY), ('value', VALUE))}
         self.params_total = int(self.lib.cdrl_learner_params_total(h))
         self.grads_total = int(self.lib.cdrl_learner_grads_total(h))
@@ -91,8 +105,8 @@ class LearnerEngine:
         else:
             self.params = torch.zeros(self.params_total, dtype=torch.float32, device=dev)
             self.grads = torch.zeros(self.grads_total, dtype=torch.float32, device=dev)
-            self.adam_m = torch.zeros(self.grads_total, dtype=torch.float32, device=dev)
-            self.adam_v = torch.zeros(self.grads_total, dtype=torch.float32, device=dev)
+            self.adam_m = torch.full((self.grads_total,), self.slot_init[0], dtype=torch.float32, device=dev)
+            self.adam_v = torch.full((self.grads_total,), self.slot_init[1], dtype=torch.float32, device=dev)
         self.workspace = torch.zeros(self.workspace_bytes, dtype=torch.uint8, device=dev)
         _lib.check(self.lib.cdrl_learner_bind(h, _lib.ptr(self.params), _lib.ptr(self.grads), _lib.ptr(self.adam_m),
                                               _lib.ptr(self.adam_v), _lib.ptr(self.workspace), self.workspace_bytes),
@@ -142,6 +156,15 @@ class LearnerEngine:
         return ({e['name']: self._view(self.adam_m, model, e) for e in t.entries if e['trainable']},
                 {e['name']: self._view(self.adam_v, model, e) for e in t.entries if e['trainable']})
 
+    def optimizer_slots(self, model: str) -> Dict[str, Dict[str, torch.Tensor]]:
+        """{Keras slot name: {tensor name: view}} of the optimizer's slots for `model`'s trainable tensors (e.g. rmsprop:
+        {'rms': ...}; sgd: {}).  The views alias adam_m / adam_v, as adam_views does."""
+        out = {}
+        for slot, flat in zip(_lib.OPTIMIZER_SLOTS[self.optimizer], (self.adam_m, self.adam_v)):
+            if slot is not None:
+                out[slot] = {e['name']: self._view(flat, model, e) for e in self.tables[model].entries if e['trainable']}
+        return out
+
     def load_params(self, model: str, values: Dict[str, np.ndarray]):
         views = self.param_views(model)
         for name, v in views.items():
@@ -175,8 +198,9 @@ class LearnerEngine:
         return off
 
     def reset_optimizer(self):
-        self.adam_m.zero_()
-        self.adam_v.zero_()
+        """A fresh optimizer: every slot at its initial value (0; adagrad / ftrl accumulators 0.1), step counters 0."""
+        self.adam_m.fill_(self.slot_init[0])
+        self.adam_v.fill_(self.slot_init[1])
         _lib.check(self.lib.cdrl_learner_reset_optimizer_steps(self.h, self._stream()), 'reset_optimizer_steps')
 
     def buffer(self, which: int, shape=None) -> torch.Tensor:

@@ -150,6 +150,8 @@ class DataParallelLearner:
             view.mul_(scale)
 
     def broadcast_parameters(self, src=0):
+        # adam_m / adam_v hold the slots of every optimizer (cdrl_config.optimizer); the step counters and Nadam's m_cache live in
+        # each rank's device block and advance identically on every rank
         if self.world > 1 or self.force:
             dist.broadcast(self.engine.params, src=src, group=self.group)
             dist.broadcast(self.engine.adam_m, src=src, group=self.group)

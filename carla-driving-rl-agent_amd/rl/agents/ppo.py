@@ -14,6 +14,7 @@ import torch
 from .. import utils
 from ..parameters import DynamicParameter
 from .agents import Agent
+from ..._lib import OPTIMIZERS
 
 
 class PPOAgent(Agent):
@@ -23,10 +24,11 @@ class PPOAgent(Agent):
                  polyak=1.0, repeat_action=1, advantage_scale=2.0, **kwargs):
         assert 0.0 < polyak <= 1.0
         assert repeat_action >= 1
-        if str(optimizer).lower() != 'adam':
-            raise ValueError("only optimizer='adam' is implemented natively (the reference stages all use it)")
-        if polyak < 1.0:
-            raise NotImplementedError('polyak averaging < 1.0 is off in every reference stage and not implemented')
+        # utils.get_optimizer_by_name (reference rl/utils.py:29-46): one Keras optimizer class, by name, for the policy and value
+        # optimizers (and CARLAgent's dynamics optimizer); it and polyak reach the learner engines through the network
+        if str(optimizer).lower() not in OPTIMIZERS:
+            raise ValueError(f'Cannot find optimizer {optimizer}. Select one of {OPTIMIZERS}.')
+        self.optimizer_name = str(optimizer).lower()
         super().__init__(*args, name=name, **kwargs)
         self.memory: PPOMemory = None
         self.gamma = gamma
@@ -48,7 +50,7 @@ class PPOAgent(Agent):
         self.policy_lr = DynamicParameter.create(value=policy_lr)
         self.value_lr = DynamicParameter.create(value=value_lr)
         self.optimization_steps = dict(policy=optimization_steps[0], value=optimization_steps[1])
-        self.should_polyak_average = False
+        self.should_polyak_average = polyak < 1.0
         self.polyak_coeff = polyak
         if not isinstance(network, dict) or 'network' not in network:
             raise ValueError("PPOAgent needs network=dict(network=<Network class>, ...)")

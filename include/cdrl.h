@@ -39,7 +39,40 @@ typedef struct cdrl_config {
     float exp_scale;                       /* 6.0 (core/networks.py:169)                        */
     int32_t compute;                       /* CDRL_COMPUTE_*: arithmetic of the tower's 1x1 convolutions (default float32) */
     int32_t freeze_trunk;                  /* 0 (default) or 1: frozen trunk, see below; other values fail at create       */
+    int32_t optimizer;                     /* CDRL_OPT_* (default CDRL_OPT_ADAM) of all three optimizers; see below         */
+    float polyak;                          /* (0, 1], default 1 (off): polyak averaging of the heads; see below            */
 } cdrl_config;
+
+/* optimizer -- PPOAgent(optimizer=name) (reference rl/utils.py:29-46, rl/agents/ppo.py:105-106, core/carla_agent.py:123-124): one
+ * Keras optimizer class for the policy, value and dynamics optimizers, built with the learning rate only, so every other
+ * constant is a Keras default.  Fixed at create; unknown values fail there.  Each optimizer keeps at most two per-element slots,
+ * in the adam_m / adam_v arenas (layouts unchanged); a slot an optimizer does not use is never written.  g is the gradient after
+ * the per-tensor clip (heads) or unclipped (trunk), t the optimizer's step count including this step, lr the step's learning
+ * rate, eps / beta1 / beta2 those of cdrl_hparams.  Scalar coefficients are float32, as in TensorFlow.
+ *   name      adam_m      adam_v       initial m, v   update
+ *   adam      m           v            0, 0           ResourceApplyAdam (unchanged)
+ *   sgd       -           -            -              p -= lr g
+ *   rmsprop   -           rms          -, 0           rho 0.9: r = rho r + (1 - rho) g^2; p -= lr g / (sqrt(r) + eps)
+ *   adagrad   -           accumulator  -, 0.1         a += g^2; p -= lr g / (sqrt(a) + eps)
+ *   adadelta  accum_var   accum_grad   0, 0           rho 0.95: a = rho a + (1 - rho) g^2; u = sqrt(d + eps) rsqrt(a + eps) g;
+ *                                                     p -= lr u; d = rho d + (1 - rho) u^2
+ *   adamax    m           v            0, 0           m += (g - m)(1 - beta1); v = max(beta2 v, |g|); p -= lr / (1 - beta1^t) m / (v + eps)
+ *   nadam     m           v            0, 0           schedule decay 0.004: mu_t = beta1 (1 - 0.5 * 0.96^(0.004 t)); S_t = m_cache mu_t
+ *                                                     (m_cache: one float per optimizer, starts at 1, becomes S_t every step);
+ *                                                     S' = S_t mu_(t+1); m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2;
+ *                                                     p -= lr [(1 - mu_t) g / (1 - S_t) + mu_(t+1) m / (1 - S')] / (sqrt(v / (1 - beta2^t)) + eps)
+ *   ftrl      linear      accumulator  0, 0.1         lr_power -0.5, l1 = l2 = 0: n' = n + g^2; z += g - (sqrt(n') - sqrt(n)) / lr p;
+ *                                                     p = |z| > 0 ? -z / (sqrt(n') / lr) : 0; n = n'
+ * The initial slot values are also reported by cdrl_optimizer_slots.  cdrl_learner_reset_optimizer_steps resets the step counters
+ * to 0 and the Nadam m_caches to 1; the slots are the caller's arenas.  A frozen trunk's slots, counter and m_cache are untouched.
+ *
+ * polyak < 1 -- PPOAgent(polyak=a) (reference rl/agents/ppo.py:242-247,268-271, rl/utils.py:105-117): after each head's optimizer
+ * step its trainable tensors become a * p_new + c * p_old with a = (float)polyak, c = (float)(1 - (double)polyak), two float32
+ * products and one float32 sum, in the same pass as the update.  The trunk is not averaged (the reference's dynamics optimizer
+ * has none).  The non-trainable BatchNorm moving statistics are not touched (the reference blends two identical arrays there, a
+ * difference of float32 rounding only).  old_policy still receives the pre-update policy.  polyak = 1 is the plain update. */
+enum { CDRL_OPT_ADAM = 0, CDRL_OPT_SGD = 1, CDRL_OPT_RMSPROP = 2, CDRL_OPT_ADAGRAD = 3, CDRL_OPT_ADADELTA = 4, CDRL_OPT_ADAMAX = 5,
+       CDRL_OPT_NADAM = 6, CDRL_OPT_FTRL = 7 };
 
 /* freeze_trunk = 1 -- CARLAgent(update_dynamics=False) (reference core/carla_agent.py:77-80,351-373,430-463): the learner trains the
  * policy and value heads on a fixed trunk.  Fixed at create (the planner then leaves out the trunk-backward scratch:
@@ -124,6 +157,9 @@ uint32_t cdrl_crc32c(uint32_t crc, const void* data, size_t n);
 int cdrl_learner_create(const cdrl_config* cfg, cdrl_learner** out);
 void cdrl_learner_destroy(cdrl_learner* l);
 void cdrl_config_default(cdrl_config* cfg);
+/* Slots of optimizer CDRL_OPT_* `optimizer` (table above): used[0] / used[1] whether it keeps a slot in the adam_m / adam_v arena,
+ * init[0] / init[1] the slot's initial value (0 for an unused slot).  -1 for an unknown optimizer.  Host only. */
+int cdrl_optimizer_slots(int optimizer, int32_t* used, float* init);
 
 /* variable inventory: Model.trainable_variables / get_weights ordering (core/networks.py:281-285) */
 int cdrl_learner_param_count(const cdrl_learner* l, int model);
@@ -141,7 +177,8 @@ int cdrl_learner_bind(cdrl_learner* l, float* params, float* grads, float* adam_
 int cdrl_learner_set_hparams(cdrl_learner* l, const cdrl_hparams* hp, void* stream);
 /* Makes `l` read its hyper-parameters and Adam step counters from `owner`'s device block (both bound, sharing the same
  * parameter / Adam arenas): a second learner built for the ragged LAST minibatch of an update (the reference's tf.data
- * pipeline keeps it unless drop_remainder is set, rl/utils.py:365-393) then advances the same optimizer. */
+ * pipeline keeps it unless drop_remainder is set, rl/utils.py:365-393) then advances the same optimizer.  Fails when the two
+ * were created with a different optimizer or polyak. */
 int cdrl_learner_share_hparams(cdrl_learner* l, const cdrl_learner* owner);
 /* Data-parallel overlap: `stream` (caller-owned, or NULL to switch off) is made to wait inside every
  * following *_forward_backward call for the point of the backward pass at which the gradients of the head and of the trunk
@@ -153,6 +190,7 @@ int cdrl_learner_set_comm_stream(cdrl_learner* l, void* stream);
  * pass's own stream is.  Equals the trunk size when the stream is never released mid-pass (hipGraph replay, CDRL_GRAPH=1; a learner
  * created with freeze_trunk = 1, which writes no trunk gradient at all). */
 int64_t cdrl_learner_tail_offset(const cdrl_learner* l);
+/* Step counters to 0 and the Nadam m_caches to 1 (a fresh optimizer; the slots in the arenas are the caller's to reset). */
 int cdrl_learner_reset_optimizer_steps(cdrl_learner* l, void* stream);
 
 /* CARLAgent.get_policy_gradients (core/carla_agent.py:351-373): train-mode trunk forward,
@@ -180,7 +218,8 @@ int cdrl_learner_policy_forward_backward_resample(cdrl_learner* l, const cdrl_po
 int cdrl_learner_sequence_begin(cdrl_learner* l, void* stream);
 int cdrl_learner_sequence_end(cdrl_learner* l, void* stream);
 /* CARLAgent.apply_policy_gradients (core/carla_agent.py:375-388) + PPOAgent.apply_policy_gradients
- * (rl/agents/ppo.py:238-252): trunk Adam, per-tensor clip, old_policy <- policy, policy Adam (freeze_trunk = 1: no trunk Adam). */
+ * (rl/agents/ppo.py:238-252): trunk Adam, per-tensor clip, old_policy <- policy, policy Adam (freeze_trunk = 1: no trunk Adam).
+ * With another cdrl_config.optimizer, that optimizer's step in place of Adam's; polyak < 1 averages the policy after its step. */
 int cdrl_learner_policy_apply(cdrl_learner* l, void* stream);
 /* CARLAgent.get_value_gradients / apply_value_gradients (core/carla_agent.py:430-463;
  * rl/agents/ppo.py:264-275). */
