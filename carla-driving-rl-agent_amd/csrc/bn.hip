@@ -86,11 +86,8 @@ __device__ __forceinline__ void strided_sum2(const double* __restrict__ p0, cons
 
 // partial lanes of the finalize blocks (x 8 channel lanes = threads per block).  A 1024-thread block needs 16 free wave
 // slots on one CU before it starts; in the backward pass the side stream keeps the CUs busy and the finalize kernels of the
-// critical stream then queue behind it (outliers of 74 us for a 5.6 us kernel).  CDRL_FIN_PY = 128 | 64 | 32.
-static int fin_py() {
-    static const int v = 64;
-    return v >= 128 ? 128 : (v >= 64 ? 64 : 32);
-}
+// critical stream then queue behind it (outliers of 74 us for a 5.6 us kernel).  64 of 128 | 64 | 32.
+static constexpr int FIN_LANES = 64;
 
 __device__ __forceinline__ int fin_group_slots(int G) { return G <= 1 ? 1 : (G <= 2 ? 2 : (G <= 4 ? 4 : 8)); }
 
@@ -183,11 +180,8 @@ __global__ void __launch_bounds__(FIN_CX * FIN_PY) bn_finalize_kernel(const doub
 
 int bn_finalize(const double* part, int nb, int G, int Mg, int C, const float* gamma, const float* beta,
                 float* mov_mean, float* mov_var, int bessel, int training, float* stats, hipStream_t st) {
-    // block = (8 channel lanes, fin_py() partial lanes)
-    const int py = fin_py();
-    if (py == 128) hipLaunchKernelGGL(bn_finalize_kernel<128>, dim3(cdiv(C, FIN_CX)), dim3(FIN_CX, 128), 0, st, part, nb, G, Mg, C, gamma, beta, mov_mean, mov_var, bessel, training, stats);
-    else if (py == 64) hipLaunchKernelGGL(bn_finalize_kernel<64>, dim3(cdiv(C, FIN_CX)), dim3(FIN_CX, 64), 0, st, part, nb, G, Mg, C, gamma, beta, mov_mean, mov_var, bessel, training, stats);
-    else hipLaunchKernelGGL(bn_finalize_kernel<32>, dim3(cdiv(C, FIN_CX)), dim3(FIN_CX, 32), 0, st, part, nb, G, Mg, C, gamma, beta, mov_mean, mov_var, bessel, training, stats);
+    // block = (8 channel lanes, FIN_LANES partial lanes)
+    hipLaunchKernelGGL(bn_finalize_kernel<FIN_LANES>, dim3(cdiv(C, FIN_CX)), dim3(FIN_CX, FIN_LANES), 0, st, part, nb, G, Mg, C, gamma, beta, mov_mean, mov_var, bessel, training, stats);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
@@ -502,14 +496,13 @@ template <class T>
 static int bn_apply_t(View y, int G, int Mg, int C, const float* stats, int act, View dst, int shuffle_ctot,
                       hipStream_t st, const View* pass_src, const View* pass_dst) {
     {
-        static const bool fast = true;
         const VColGeom g = vcol_geom(Mg, C, 2048);
         View ps{nullptr, 0, 0}, pd{nullptr, 0, 0};
         if (pass_src && pass_dst) {
             ps = *pass_src;
             pd = *pass_dst;
         }
-        if (fast && stats && shuffle_ctot && g.nloop == 1 && g.vec >= 2 && view_aligned(y, g.vec) && (!ps.p || view_aligned(ps, g.vec))) {
+        if (stats && shuffle_ctot && g.nloop == 1 && g.vec >= 2 && view_aligned(y, g.vec) && (!ps.p || view_aligned(ps, g.vec))) {
             dim3 grid(g.nb, G), block(g.cx, g.cy);
             if (g.vec == 4) {
                 if (ps.p) hipLaunchKernelGGL((bn_apply_shuf_kernel<4, true, T>), grid, block, 0, st, y, Mg, C, g.rb, G * C, stats, act, dst, shuffle_ctot, ps, pd);
@@ -548,7 +541,7 @@ int bn_apply(View y, int G, int Mg, int C, const float* stats, int act, View dst
 }
 
 // BatchNorm apply + activation + global average pool in one pass over the raw conv output (the head of the tower: the 12288 x 768
-// activated tensor is neither written nor read; same operation order as bn_apply followed by gap_fwd_kernel, so the same bits)
+// activated tensor is neither written nor read; same operation order as bn_apply followed by a separate per-frame mean, so the same bits)
 template <class T>
 __global__ void bn_act_gap_fwd_kernel(const T* __restrict__ y, const float* __restrict__ stats, float* __restrict__ out, int N,
                                       int P, int C, int GC, int frames_per_group, int act) {
@@ -769,7 +762,6 @@ static void launch_bbr_shuf(const VColGeom& g, int G, hipStream_t st, View da, i
 int bn_bwd_reduce(View da, int shuffle_ctot, View y, int G, int Mg, int C, const float* stats, int act,
                   double* part, hipStream_t st, const PoolSrc* pool, const View* pass_gsrc, const View* pass_gdst, int bcast_rows, int at) {
     {
-        static const bool fast = true;
         const VColGeom g = vcol_geom(Mg, C, NB_STATS);
         View pgs{nullptr, 0, 0}, pgd{nullptr, 0, 0};
         if (pass_gsrc && pass_gdst) {
@@ -778,7 +770,7 @@ int bn_bwd_reduce(View da, int shuffle_ctot, View y, int G, int Mg, int C, const
         }
         const bool ydense = y.ld == C && y.coff == 0 && view_aligned(y, g.vec);
         const bool pok = !pgs.p || (pgd.p && view_aligned(pgd, g.vec));
-        if (fast && !pool && !bcast_rows && shuffle_ctot && act == ACT_RELU6 && g.nloop == 1 && ydense && pok && g.vec >= 2) {
+        if (!pool && !bcast_rows && shuffle_ctot && act == ACT_RELU6 && g.nloop == 1 && ydense && pok && g.vec >= 2) {
             if (at) {
                 if (g.vec == 4) launch_bbr_shuf<4, bf16_t>(g, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
                 else launch_bbr_shuf<2, bf16_t>(g, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
@@ -993,16 +985,14 @@ __global__ void __launch_bounds__(256) pool_bn_bwd_reduce_v4_kernel(PoolSrc ps, 
 int pool_bn_bwd_reduce(const PoolSrc& ps, const float* y, int G, int frames_per_group, int C, const float* stats, double* part,
                        hipStream_t st, int at) {
     {
-        static const bool fast = true;
         const int Mg = frames_per_group * ps.Ho * ps.Wo;
         const VColGeom g = vcol_geom(Mg, C, NB_STATS);
-        if (fast && g.vec == 4 && g.nloop == 1) {
+        if (g.vec == 4 && g.nloop == 1) {
             dim3 grid(g.nb, G), block(g.cx, g.cy);
             const size_t smb = (size_t)g.cy * 4 * g.cx * sizeof(double);
-            static const bool pooled_env = true;
-            if (at && ps.pa && pooled_env) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<bf16_t, true>), grid, block, smb, st, ps, reinterpret_cast<const bf16_t*>(y), stats, G * C, C, Mg, g.rb, part);
+            if (at && ps.pa) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<bf16_t, true>), grid, block, smb, st, ps, reinterpret_cast<const bf16_t*>(y), stats, G * C, C, Mg, g.rb, part);
             else if (at) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<bf16_t, false>), grid, block, smb, st, ps, reinterpret_cast<const bf16_t*>(y), stats, G * C, C, Mg, g.rb, part);
-            else if (ps.pa && pooled_env) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<float, true>), grid, block, smb, st, ps, y, stats, G * C, C, Mg, g.rb, part);
+            else if (ps.pa) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<float, true>), grid, block, smb, st, ps, y, stats, G * C, C, Mg, g.rb, part);
             else hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<float, false>), grid, block, smb, st, ps, y, stats, G * C, C, Mg, g.rb, part);
             CDRL_LAUNCH_CHECK();
             return 0;
@@ -1059,10 +1049,7 @@ __global__ void __launch_bounds__(FIN_CX * FIN_PY) bn_bwd_finalize_kernel(const 
 
 int bn_bwd_finalize(const double* part, int nb, int G, int Mg, int C, const float* stats, float* dgamma,
                     float* dbeta, float* coef, hipStream_t st) {
-    const int py = fin_py();
-    if (py == 128) hipLaunchKernelGGL(bn_bwd_finalize_kernel<128>, dim3(cdiv(C, FIN_CX)), dim3(FIN_CX, 128), 0, st, part, nb, G, Mg, C, stats, dgamma, dbeta, coef);
-    else if (py == 64) hipLaunchKernelGGL(bn_bwd_finalize_kernel<64>, dim3(cdiv(C, FIN_CX)), dim3(FIN_CX, 64), 0, st, part, nb, G, Mg, C, stats, dgamma, dbeta, coef);
-    else hipLaunchKernelGGL(bn_bwd_finalize_kernel<32>, dim3(cdiv(C, FIN_CX)), dim3(FIN_CX, 32), 0, st, part, nb, G, Mg, C, stats, dgamma, dbeta, coef);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel<FIN_LANES>, dim3(cdiv(C, FIN_CX)), dim3(FIN_CX, FIN_LANES), 0, st, part, nb, G, Mg, C, stats, dgamma, dbeta, coef);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
@@ -1209,10 +1196,9 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_fast_kernel(View da, int cto
 int bn_bwd_apply(View da, int shuffle_ctot, View y, int G, int Mg, int C, const float* stats, const float* coef,
                  int act, float* dy, double* part2, hipStream_t st, const PoolSrc* pool, int bcast_rows, int at) {
     {
-        static const bool fast = true;
         const VColGeom g = vcol_geom(Mg, C, NB_STATS);
         const bool ydense = y.ld == C && y.coff == 0 && view_aligned(y, g.vec);
-        if (fast && !pool && g.nloop == 1 && g.vec >= 2 && ydense && (reinterpret_cast<uintptr_t>(dy) % (4 * g.vec)) == 0) {
+        if (!pool && g.nloop == 1 && g.vec >= 2 && ydense && (reinterpret_cast<uintptr_t>(dy) % (4 * g.vec)) == 0) {
             dim3 grid(g.nb, G), block(g.cx, g.cy);
             const size_t sm = (size_t)g.cy * g.vec * g.cx * sizeof(double);
             const bf16_t* yb = reinterpret_cast<const bf16_t*>(y.p);
@@ -1410,12 +1396,6 @@ __global__ void permute_bt_kernel(const float* __restrict__ src, float* __restri
 
 int permute_bt(const float* src, float* dst, int B, int T, int D, hipStream_t st) {
     hipLaunchKernelGGL(permute_bt_kernel, dim3(flat_grid((int64_t)B * T * D)), dim3(256), 0, st, src, dst, B, T, D, 0);
-    CDRL_LAUNCH_CHECK();
-    return 0;
-}
-
-int permute_tb_bwd(const float* src, float* dst, int B, int T, int D, hipStream_t st) {
-    hipLaunchKernelGGL(permute_bt_kernel, dim3(flat_grid((int64_t)B * T * D)), dim3(256), 0, st, src, dst, B, T, D, 1);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

@@ -77,7 +77,6 @@ int act_bwd(const float* z, const float* da, float* dz, int64_t n, int act, hipS
 int fill(float* p, int64_t n, float v, hipStream_t st);
 // (B,T,D) -> (T*B, D)
 int permute_bt(const float* src, float* dst, int B, int T, int D, hipStream_t st);
-int permute_tb_bwd(const float* src, float* dst, int B, int T, int D, hipStream_t st);
 // dst[i,:] = src[idx[i],:]
 int gather_rows(const float* src, const int* idx, float* dst, int nrows, int64_t row_elems, hipStream_t st);
 
@@ -109,7 +108,7 @@ int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int a
             const float* pro_stats = nullptr, const TnBnBwd* dpro = nullptr, bool bf16_operands = false, int at = 0);
 
 // LDS-staged form for the bf16 modes (gemm_tn_lds.hip): same contract as gemm_tn with bf16_operands = true; at: 0 float32 / 1 bf16
-// tensors.  gemm_tn dispatches to it (CDRL_TN_LDS=0 keeps the direct form).
+// tensors.  gemm_tn dispatches to it for the shapes it takes.
 bool gemm_tn_lds_supported(View A, View D, int N, int K, const TnBnBwd* dpro);
 int64_t gemm_tn_lds_part_elems(int M, int N, int K, int G = 1);
 // f32_mode (with at = 0): 1 = float32 operands on v_mfma_f32_32x32x2_f32 (the float32 engine's arithmetic); 2 = float32-accurate
@@ -220,12 +219,9 @@ int maxpool_bwd(const uint8_t* argmax, const float* dp, float* da, int N, int H,
 int maxpool_bn_fwd(const float* y, const float* stats, int G, int frames_per_group, float* p, uint8_t* argmax, int N,
                    int H, int W, int C, hipStream_t st, int at = 0);
 PoolSrc make_pool_src(const uint8_t* argmax, const float* dp, int H, int W);
-// mean over the P pixels of each frame: a [N][P][C] -> out [N][C]
-int gap_fwd(const float* a, float* out, int N, int P, int C, hipStream_t st);
 // out[n][c] = mean_p act(scale[g][c] * y[n*P + p][c] + shift[g][c]): BatchNorm apply + activation + global average pool fused
 int bn_act_gap_fwd(const float* y, const float* stats, float* out, int G, int frames_per_group, int P, int C, int act, hipStream_t st,
                    int at = 0);
-int gap_bwd(const float* dout, float* da, int N, int P, int C, hipStream_t st);
 
 // batched transposes W[cin][cout] -> WT[cout][cin] of many small matrices in one launch (gemm.hip)
 struct PwTranspose {
@@ -452,7 +448,6 @@ int clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const int
               const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms /*or null*/,
               DevHP* hp, int which, hipStream_t st, const double* chunk_part = nullptr, int ticked = 0);
 // chunk_part: per-tensor norms folded here from tensor_sqnorms' chunk partials; ticked: the step counter was advanced already
-int adam_tick(DevHP* hp, int which, hipStream_t st);
 // The other optimizers of cdrl_config.optimizer (include/cdrl.h table; opt = CDRL_OPT_*) and polyak averaging, same arguments and
 // clip as clip_adam; m / v are the optimizer's slots in the adam_m / adam_v arenas.  Adam with polyak 1 IS clip_adam.
 // polyak < 1 (heads only): p = a * p_new + c * p_old in the same pass.

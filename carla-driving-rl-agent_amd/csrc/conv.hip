@@ -1182,38 +1182,4 @@ PoolSrc make_pool_src(const uint8_t* argmax, const float* dp, int H, int W) {
     return ps;
 }
 
-// ------------------------------------------------------------------------------------------
-// GlobalAveragePooling2D (reference core/architectures.py:172)
-// ------------------------------------------------------------------------------------------
-__global__ void gap_fwd_kernel(const float* __restrict__ a, float* __restrict__ out, int N, int P, int C) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * C) return;
-    const int c = (int)(i % C);
-    const int64_t n = i / C;
-    float s = 0.0f;
-    for (int p = 0; p < P; ++p) s += a[(n * P + p) * C + c];
-    out[i] = s / (float)P;
-}
-
-int gap_fwd(const float* a, float* out, int N, int P, int C, hipStream_t st) {
-    hipLaunchKernelGGL(gap_fwd_kernel, dim3((unsigned)cdiv64((int64_t)N * C, 256)), dim3(256), 0, st, a, out, N, P, C);
-    CDRL_LAUNCH_CHECK();
-    return 0;
-}
-
-__global__ void gap_bwd_kernel(const float* __restrict__ dout, float* __restrict__ da, int N, int P, int C) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * P * C) return;
-    const int c = (int)(i % C);
-    const int64_t n = i / ((int64_t)P * C);
-    da[i] = dout[n * C + c] / (float)P;
-}
-
-int gap_bwd(const float* dout, float* da, int N, int P, int C, hipStream_t st) {
-    hipLaunchKernelGGL(gap_bwd_kernel, dim3((unsigned)cdiv64((int64_t)N * P * C, 256)), dim3(256), 0, st, dout, da, N, P,
-                       C);
-    CDRL_LAUNCH_CHECK();
-    return 0;
-}
-
 }  // namespace cdrl

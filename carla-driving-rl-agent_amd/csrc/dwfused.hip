@@ -127,8 +127,7 @@ DwfGeom dwf_geom(int B, int G, int H, int W, int C, int stride) {
     g.nb_bwd = g.nb;
     g.strip.ok = false;
     static const bool strips = !(cdrl_getenv("CDRL_DWS") && atoi(cdrl_getenv("CDRL_DWS")) == 0);
-    static const int want_env = 0;
-    const int want_wgs = want_env ? want_env : (H * W <= 16 ? 512 : 256);
+    const int want_wgs = H * W <= 16 ? 512 : 256;
     if (strips && (stride == 1 || stride == 2) && (int64_t)G * B * H * W * C * 8 < (int64_t)1 << 31) {
         // (the channel-chunk count of the plan does not depend on fpb: plan with 1 first)
         DwsGeom d = stride == 1 ? dws_geom(B, G, 1, H, W, C) : dws2_geom(B, G, 1, H, W, C);
@@ -329,7 +328,7 @@ __global__ void __launch_bounds__(DWF_T_BWD) dwf_bwd_kernel(const T* __restrict_
                                                       const float* __restrict__ post_coef, const float* __restrict__ w,
                                                       View dx, double* __restrict__ part_bn, double* __restrict__ part_w,
                                                       int Bf, int H, int W, int Ho, int Wo, int C, int GC, int pt, int pl,
-                                                      int fpb, int nb, int cchunk, bool dx_al, int nfb, bool reload_y1) {
+                                                      int fpb, int nb, int cchunk, bool dx_al, int nfb) {
     extern __shared__ __attribute__((aligned(16))) float tile[];     // A [H*W][cc] | D [Ho*Wo][cc]
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int CX = blockDim.x, CY = blockDim.y;
@@ -374,7 +373,7 @@ __global__ void __launch_bounds__(DWF_T_BWD) dwf_bwd_kernel(const T* __restrict_
     // xhat1 = (v - bt1) * rg1 with v = the activated value of tile A (bt1 = beta, rg1 = 1 / gamma) or, for a thread holding a channel
     // with (6 + |beta|) / |gamma| > 170, v = y1 re-read from memory (bt1 = mean, rg1 = invstd); see the input-gradient phase
     VecF<VEC> bt1, rg1;
-    bool slow1 = reload_y1;
+    bool slow1 = false;
     if (PRE && on) {
         // error of (a - beta) / gamma: ~ 2^-24 (|a| + |beta|) / |gamma| with a in (0, 6); held to ~1e-5 of xhat's unit scale
 #pragma unroll
@@ -646,7 +645,7 @@ __global__ void __launch_bounds__(DWS_LB) dws_bwd_kernel(const T* __restrict__ x
                                                       const T* __restrict__ y2, const float* __restrict__ post_stats,
                                                       const float* __restrict__ post_coef, const float* __restrict__ w, View dx,
                                                       double* __restrict__ part_bn, double* __restrict__ part_w, int Bf, int H, int W, int C,
-                                                      int GC, int fpb, int nb, int cchunk, bool dx_al, int nfb, bool reload_y1, int F, int S,
+                                                      int GC, int fpb, int nb, int cchunk, bool dx_al, int nfb, int F, int S,
                                                       int tile_floats) {
     // D: [F][H + 2][S * SW + 2][cchunk], zero border and right padding | coefficient table [16][cchunk]
     extern __shared__ __attribute__((aligned(16))) float tile[];
@@ -668,7 +667,7 @@ __global__ void __launch_bounds__(DWS_LB) dws_bwd_kernel(const T* __restrict__ x
     // the window phase the 9 filter taps -- read where they are used, they are not live across the other phase (~30 VGPRs)
     const int ctab = tile_floats + tx * 2;             // entry e of this lane's channel pair: tile[ctab + e * cchunk]
     VecF<2> bt1, rg1;
-    bool slow1 = PRE && reload_y1;
+    bool slow1 = false;
     {
         VecF<2> mean1, inv1, sc, sh;
 #pragma unroll
@@ -888,7 +887,7 @@ __global__ void __launch_bounds__(512) dws2_bwd_kernel(const T* __restrict__ x, 
                                                        const float* __restrict__ post_coef, const float* __restrict__ w, View dx,
                                                        double* __restrict__ part_bn, double* __restrict__ part_w, int Bf, int H, int W, int Ho,
                                                        int Wo, int C, int GC, int pt, int fpb, int nb, int cchunk, bool dx_al, int nfb,
-                                                       bool reload_y1, int F, int S, int Wdp, int tile_floats) {
+                                                       int F, int S, int Wdp, int tile_floats) {
     constexpr int SW = 8, ND = SW / 2 + 1 + PL;     // D columns a strip touches per row
     extern __shared__ __attribute__((aligned(16))) float tile[];     // D: [F][Ho + 2][Wdp][cchunk] (zero frame) | coefficient table [16][cchunk]
     const int tx = threadIdx.x, ty = threadIdx.y;
@@ -906,7 +905,7 @@ __global__ void __launch_bounds__(512) dws2_bwd_kernel(const T* __restrict__ x, 
     for (int i = (ty * CX + tx) * 2; i < tile_floats; i += CX * CY * 2) *reinterpret_cast<float2*>(&tile[i]) = make_float2(0.0f, 0.0f);
     const int ctab = tile_floats + tx * 2;
     VecF<2> bt1, rg1, sc, sh;
-    bool slow1 = reload_y1;
+    bool slow1 = false;
     if (PRE) {
         const VecF<2> mean1 = vload<2>(pre_stats + 0 * GC + g * C + c), inv1 = vload<2>(pre_stats + 1 * GC + g * C + c);
         sc = vload<2>(pre_stats + 2 * GC + g * C + c);
@@ -1245,12 +1244,11 @@ template <int PL, bool PRE, class T>
 static int launch_dws2_bwd(const DwfGeom& g, const DwsGeom& d, hipStream_t st, const float* x, const float* pre_stats, const float* dout,
                            const float* y2, const float* post_stats, const float* post_coef, const float* w, View dx, double* part_bn,
                            double* part_w, int G, int B, int H, int W, int C) {
-    static const bool reload_y1 = cdrl_getenv("CDRL_DWF_XHAT_RELOAD") && atoi(cdrl_getenv("CDRL_DWF_XHAT_RELOAD")) == 1;
     CDRL_TRY((allow_lds<dws2_bwd_kernel<PL, PRE, T>>(d.lds)));
     hipLaunchKernelGGL((dws2_bwd_kernel<PL, PRE, T>), dim3(cdiv(G * g.nb_bwd, 8) * 8 * d.nch), dim3(d.cx, d.cy), d.lds, st,
                        reinterpret_cast<const T*>(x), pre_stats, reinterpret_cast<const T*>(dout), reinterpret_cast<const T*>(y2), post_stats,
                        post_coef, w, dx, part_bn, part_w, B, H, W, same_out(H, 2), same_out(W, 2), C, G * C, same_pad_before(H, 2), g.fpb_bwd,
-                       g.nb_bwd, d.cchunk, view_aligned(dx, 2), G * g.nb_bwd, reload_y1, d.F, d.S, d.wdp, d.tile_floats);
+                       g.nb_bwd, d.cchunk, view_aligned(dx, 2), G * g.nb_bwd, d.F, d.S, d.wdp, d.tile_floats);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
@@ -1259,11 +1257,10 @@ template <int SW, int R, bool PRE, class T>
 static int launch_dws_bwd(const DwfGeom& g, const DwsGeom& d, hipStream_t st, const float* x, const float* pre_stats, const float* dout,
                           const float* y2, const float* post_stats, const float* post_coef, const float* w, View dx, double* part_bn,
                           double* part_w, int G, int B, int H, int W, int C) {
-    static const bool reload_y1 = cdrl_getenv("CDRL_DWF_XHAT_RELOAD") && atoi(cdrl_getenv("CDRL_DWF_XHAT_RELOAD")) == 1;
     CDRL_TRY((allow_lds<dws_bwd_kernel<SW, R, PRE, T>>(d.lds)));
     hipLaunchKernelGGL((dws_bwd_kernel<SW, R, PRE, T>), dim3(cdiv(G * g.nb_bwd, 8) * 8 * d.nch), dim3(d.cx, d.cy), d.lds, st,
                        reinterpret_cast<const T*>(x), pre_stats, reinterpret_cast<const T*>(dout), reinterpret_cast<const T*>(y2), post_stats,
-                       post_coef, w, dx, part_bn, part_w, B, H, W, C, G * C, g.fpb_bwd, g.nb_bwd, d.cchunk, view_aligned(dx, 2), G * g.nb_bwd, reload_y1,
+                       post_coef, w, dx, part_bn, part_w, B, H, W, C, G * C, g.fpb_bwd, g.nb_bwd, d.cchunk, view_aligned(dx, 2), G * g.nb_bwd,
                        d.F, d.S, d.tile_floats);
     CDRL_LAUNCH_CHECK();
     return 0;
@@ -1320,13 +1317,11 @@ static int launch_dwf_bwd(const DwfGeom& g, hipStream_t st, const float* x, cons
                           const float* y2, const float* post_stats, const float* post_coef, const float* w, View dx,
                           double* part_bn, double* part_w, int G, int B, int H, int W, int C) {
     const int Ho = same_out(H, S), Wo = same_out(W, S);
-    // CDRL_DWF_XHAT_RELOAD=1: xhat1 from a re-read of y1 for every channel (the form of rounds 1-3) instead of the activated tile
-    static const bool reload_y1 = cdrl_getenv("CDRL_DWF_XHAT_RELOAD") && atoi(cdrl_getenv("CDRL_DWF_XHAT_RELOAD")) == 1;
     CDRL_TRY((allow_lds<dwf_bwd_kernel<S, VEC, PRE, T>>(g.lds_bwd)));
     hipLaunchKernelGGL((dwf_bwd_kernel<S, VEC, PRE, T>), dim3(cdiv(G * g.nb, 8) * 8 * g.nch), dim3(g.cx_bwd, g.cy_bwd), g.lds_bwd, st,
                        reinterpret_cast<const T*>(x), pre_stats, reinterpret_cast<const T*>(dout), reinterpret_cast<const T*>(y2),
                        post_stats, post_coef, w, dx, part_bn, part_w, B, H, W, Ho, Wo, C, G * C, same_pad_before(H, S),
-                       same_pad_before(W, S), g.fpb, g.nb, g.cchunk, view_aligned(dx, g.vec_bwd), G * g.nb, reload_y1);
+                       same_pad_before(W, S), g.fpb, g.nb, g.cchunk, view_aligned(dx, g.vec_bwd), G * g.nb);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

@@ -1,12 +1,9 @@
 // Learner engine: owns the layer graph of CARLANetwork (trunk + policy / old-policy / value
 // heads), the flat parameter-arena layout and the workspace plan for one batch size.
 #pragma once
-#include <condition_variable>
 #include <functional>
 #include <map>
 #include <memory>
-#include <mutex>
-#include <thread>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -262,8 +259,8 @@ private:
                         int pre_stats_nb = 0, bool post_apply = true, int post_bwd_nb = 0, float* stats1_ext = nullptr,
                         float* coef1_ext = nullptr, bool pre_defer_apply = false, float** coef2_out = nullptr,
                         std::shared_ptr<bool> post_bwd_done = nullptr, std::shared_ptr<bool> pre_fin_done = nullptr);
-    bool fused_dw_ = true, fused_pw_ = true, fused_pw_wide_ = false;
-    int fused_bb_ = 1;
+    bool fused_dw_ = true, fused_pw_ = true;
+    bool fused_bb_ = true;
     bool fused_bwd_ = true;             // backward-data + filter gradient of the unit convs as one kernel (gemm_pw_bwd.hip)
     int pw_fwd_nbpg(int G, int Mg, int N, int K) const;    // statistics partial rows per group written by a unit conv's forward
     bool pw_bwd_x3_wide(int G, int Mg, int N, int K) const;               // backward-data on pw_x3_wide_bwd_kernel (N = conv inputs, K = conv outputs)
@@ -360,26 +357,6 @@ private:
     hipStream_t side_ = nullptr;
     hipStream_t aux_ = nullptr;          // feature nets + small GRUs (forward and backward)
     bool aux_pending_ = false;
-    // Optional second host thread that ENQUEUES the ~340 launches per update-step of the small-modality nets (opt-in,
-    // CDRL_AUX_THREAD=1): the single-threaded enqueue of an update-step costs 12.3 ms of host time (8 us per launch incl.
-    // the event traffic), which bounds the step for small images.
-    struct AuxWorker {
-        std::thread th;
-        std::mutex m;
-        std::condition_variable cv;
-        std::function<int()> task;
-        bool has_task = false, busy = false, stop = false;
-        int rc = 0, device = 0;
-        std::string err;
-        explicit AuxWorker(int dev);
-        ~AuxWorker();
-        void submit(std::function<int()> fn);
-        int wait();             // blocks until the submitted task has been enqueued; returns its status
-        void loop();
-    };
-    std::unique_ptr<AuxWorker> aux_worker_;
-    bool aux_inflight_ = false;
-    int aux_wait();
     hipEvent_t ev_in_sys_ = nullptr;                    // hand-over from the caller's stream with the fence (data-parallel use)
     hipEvent_t ev_out_sys_ = nullptr;                   // hand-back to the caller's stream WITH the system-scope fence (data-parallel use)
     bool dp_hint_ = false;                              // a pass ran with a gradient scale below 1 (world size > 1)
@@ -447,9 +424,8 @@ private:
     } seg_[3];
     void build_seg_tables();
     int upload_seg_tables();
-    // transposed copies of the pointwise-conv weights for the backward-data GEMMs: with W^T in memory the persistent GEMM
-    // loads its weight fragments coalesced (the strided fragment load of W cost ~7 us of TA time per CU and launch);
-    // refreshed by one batched transpose launch at the start of every trunk backward
+    // transposed copies of weights for backward GEMMs (the GRUs' recurrent kernels; the unit convs read packed W^T fragments instead):
+    // refreshed by the pack launch at the start of every training forward
     std::vector<PwTranspose> h_pwt_;
     std::map<std::string, float*> pwt_by_name_;
     PwTranspose* d_pwt_ = nullptr;

@@ -47,7 +47,6 @@ Learner::Learner(const Config& cfg) : cfg_(cfg) {
 }
 
 Learner::~Learner() {
-    aux_worker_.reset();
     if (hp_stage_) (void)hipHostFree(hp_stage_);
     for (int i = 0; i < NSLOT; ++i) {
         if (ev_main_[i]) (void)hipEventDestroy(ev_main_[i]);
@@ -74,62 +73,6 @@ Learner::~Learner() {
     if (ev_aux_done_) (void)hipEventDestroy(ev_aux_done_);
     if (side_) (void)hipStreamDestroy(side_);
     if (aux_) (void)hipStreamDestroy(aux_);
-}
-
-Learner::AuxWorker::AuxWorker(int dev) : device(dev) { th = std::thread([this] { loop(); }); }
-
-Learner::AuxWorker::~AuxWorker() {
-    {
-        std::lock_guard<std::mutex> lk(m);
-        stop = true;
-    }
-    cv.notify_all();
-    if (th.joinable()) th.join();
-}
-
-void Learner::AuxWorker::loop() {
-    (void)hipSetDevice(device);
-    for (;;) {
-        std::function<int()> fn;
-        {
-            std::unique_lock<std::mutex> lk(m);
-            cv.wait(lk, [this] { return has_task || stop; });
-            if (stop) return;
-            fn = std::move(task);
-            has_task = false;
-        }
-        const int r = fn();
-        {
-            std::lock_guard<std::mutex> lk(m);
-            rc = r;
-            err = r != 0 ? last_error() : "";
-            busy = false;
-        }
-        cv.notify_all();
-    }
-}
-
-void Learner::AuxWorker::submit(std::function<int()> fn) {
-    std::unique_lock<std::mutex> lk(m);
-    cv.wait(lk, [this] { return !busy; });
-    task = std::move(fn);
-    has_task = true;
-    busy = true;
-    lk.unlock();
-    cv.notify_all();
-}
-
-int Learner::AuxWorker::wait() {
-    std::unique_lock<std::mutex> lk(m);
-    cv.wait(lk, [this] { return !busy; });
-    if (rc != 0) set_error("%s", err.c_str());
-    return rc;
-}
-
-int Learner::aux_wait() {
-    if (!aux_inflight_) return 0;
-    aux_inflight_ = false;
-    return aux_worker_->wait();
 }
 
 void Learner::drop_graphs() {
@@ -317,8 +260,7 @@ void Learner::flush_deferred() {
 }
 
 int Learner::defer_side(hipStream_t st, std::function<int(hipStream_t)> fn) {
-    static const bool on = true;
-    if (!side_enabled_ || !on || (g_diag_noev & 2)) {
+    if (!side_enabled_ || (g_diag_noev & 2)) {
         hipStream_t side = fork_side(st);
         CDRL_TRY(fn(side));
         return done_side(side);
@@ -364,7 +306,6 @@ int Learner::join_side(hipStream_t st) {
     const uint64_t js = note_side_record(ev_join_);
     if (st == main_) main_waited_ = js;
     if (aux_pending_) {
-        CDRL_TRY(aux_wait());
         CDRL_HIP(hipStreamWaitEvent(st, ev_aux_done_, 0));
         aux_pending_ = false;
     }
@@ -567,8 +508,7 @@ int Learner::pw_fwd_nbpg(int G, int Mg, int N, int K) const {
 // M = 49152 (the stride-2 unit's first conv, on the 6x8 maps) the fragment traffic (3072 x 196 KB) outweighs what the persistent kernel
 // loses to its serial tiles -- measured in the step: 140 us against 100 us there, 36 against 53 us (BatchNorm-sum epilogue) at M = 12288.
 bool Learner::pw_bwd_x3_wide(int G, int Mg, int N, int K) const {
-    static const bool on = !(cdrl_getenv("CDRL_PW_X3_WIDE_BWD") && atoi(cdrl_getenv("CDRL_PW_X3_WIDE_BWD")) == 0);
-    return on && pw_fwd_x3_wide(G, Mg, N, K) && (int64_t)G * Mg <= 16384;
+    return pw_fwd_x3_wide(G, Mg, N, K) && (int64_t)G * Mg <= 16384;
 }
 
 int Learner::pw_bwd_nbpg(int G, int Mg, int N, int K) const {
@@ -578,10 +518,9 @@ int Learner::pw_bwd_nbpg(int G, int Mg, int N, int K) const {
 
 bool Learner::pw_fwd_x3_wide(int G, int Mg, int N, int K) const {
     static const bool x3_env = !(cdrl_getenv("CDRL_PW_X3") && atoi(cdrl_getenv("CDRL_PW_X3")) == 0);
-    static const bool wide_env = !(cdrl_getenv("CDRL_PW_X3_WIDE") && atoi(cdrl_getenv("CDRL_PW_X3_WIDE")) == 0);
     // (measured at M = 12288 and 49152 rows: 16-20 against 26-36 us, ~60 against 80 us; beyond that every 32-row tile would still stream
     //  its own copy of W -- 196 KB per tile and column block -- and the persistent kernel keeps the shape)
-    return cfg_.compute == 0 && x3_env && wide_env && (K > 128 || N > 128) && K <= 256 && N <= 256 && K % 4 == 0 && (int64_t)G * Mg <= 49152;
+    return cfg_.compute == 0 && x3_env && (K > 128 || N > 128) && K <= 256 && N <= 256 && K % 4 == 0 && (int64_t)G * Mg <= 49152;
 }
 
 const void* Learner::gemm_x3_packed(const float* w, int K, int N, int sbk, int sbn) {
@@ -667,8 +606,7 @@ Learner::BnRec Learner::add_bn(std::vector<Op>& ops, int model, const std::strin
     if (inf_batched) note_bn_inference(gamma.p, beta.p, mm.p, mv.p, stats, G, C);
     // single-group BatchNorm over a few hundred rows (dense BNs of the trunk tail and the control branches): one launch per
     // direction instead of three
-    static const bool small_env = true;
-    const bool small = small_env && G == 1 && Mg <= 2048 && !bessel && act == ACT_NONE && !out_shuffle && !dout_shuffle && dx &&
+    const bool small = G == 1 && Mg <= 2048 && !bessel && act == ACT_NONE && !out_shuffle && !dout_shuffle && dx &&
                        !stats_nb && !defer_apply && !pass.fsrc.p && !pass.gsrc.p && !pass.gap_out;
     const bool gap = pass.gap_out != nullptr;
     const int at = model == M_TRUNK && prefix.compare(0, 4, "img.") == 0 ? at_ : 0;     // tower tensors only
@@ -720,11 +658,6 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
     const int G = cfg_.T, Mg = rows / G;
     Scratch* sc = build_scr_;           // statistics / BatchNorm-sum partials: the scratch of the stream this op's forward runs on (the shortcut
                                         // branch of a stride-2 unit runs beside the main branch and has its own)
-    static const bool pack_env = true;
-    static const bool wt_env = true;
-    const float* wt = (wt_env && !pack_env && fuse.bwd_pw) ? pw_transposed(prefix, w.p, Cin, Cout) : nullptr;
-    const float* wb = wt ? wt : w.p;                    // backward-data operand B(k = cout, n = cin)
-    const int wb_sk = wt ? Cin : 1, wb_sn = wt ? 1 : Cout;
     // compute mode 1 (configuration 3): every 1x1 convolution of the tower multiplies bf16-rounded operands -- forward,
     // backward-data and filter gradient: the fused kernels in their BF variant, the plain wide ones through gemm_x3's
     // single-plane form, the filter gradients through tn_direct's BF variant
@@ -747,9 +680,8 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
     if (bfc && ((!fuse.fwd_pw && !use_g3f) || (!fuse.bwd_pw && !fuse.bb && !use_g3b) || (fuse.bb && !fuse.bwd_pw)))
         build_fail("bf16-operand mode: 1x1 convolution %s (%d -> %d, fwd %d bwd %d bb %d; input ld %d coff %d) has no bf16 kernel",
                    prefix.c_str(), Cin, Cout, (int)fuse.fwd_pw, (int)fuse.bwd_pw, (int)fuse.bb, in.ld, in.coff);
-    if (bfc && !pack_env) build_fail("bf16-operand mode needs the packed-weight path (CDRL_PW_PACK=0 is set)");
-    const float* wpf = (pack_env && fuse.fwd_pw && !w3f) ? pw_packed(w.p, Cin, Cout, Cout, 1, bfc) : nullptr;      // forward: B(k = cin, n = cout)
-    const float* wpb = (pack_env && fuse.bwd_pw && !frozen()) ? pw_packed(w.p, Cout, Cin, 1, Cout, bfc) : nullptr;      // backward-data: W^T
+    const float* wpf = (fuse.fwd_pw && !w3f) ? pw_packed(w.p, Cin, Cout, Cout, 1, bfc) : nullptr;      // forward: B(k = cin, n = cout)
+    const float* wpb = (fuse.bwd_pw && !frozen()) ? pw_packed(w.p, Cout, Cin, 1, Cout, bfc) : nullptr;      // backward-data: W^T
     const int tn_groups = (fuse.pro_stats || fuse.bb) ? G : 1;
     note_scratch(0, 0, (size_t)rows * Cout, (size_t)gemm_tn_part_elems(rows, Cout, Cin, tn_groups));
     if (fuse.epi_stats) note_scratch((size_t)G * nb_fwd * 2 * Cout, 0, 0, 0);
@@ -774,8 +706,8 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
     // 24 input channels -- the first unit, the last conv of the backward -- pad to 64: 158 us against 104 us for the backward-data kernel of
     // the two-kernel form, which is why rounds 4 kept it there; but that form's filter gradient (163 us on the side stream) then bounds the
     // tail of the pass and slows the BatchNorm reduction beside it (117 us instead of 29): fused 14.00 vs 14.06 ms per update-step, and one
-    // pass over (dz, y) = 0.3 GB per pass less.  CDRL_FBWD_MIN_CIN=32 -> the two-kernel form for that conv.
-    static const int fbwd_min_cin = 24;
+    // pass over (dz, y) = 0.3 GB per pass less.
+    static constexpr int fbwd_min_cin = 24;
     const bool fbwd = fused_bwd_ && fuse.bb && fuse.bwd_pw && (!bfc || at) && G <= 8 && Cin >= fbwd_min_cin && pw_bwd_fused_supported(dz_probe, in, din, Cout, Cin, at) &&
                       (!anorm || (fuse.bwd_ey == in.p && fuse.bwd_epi_stats == fuse.pro_stats && fuse.a_bn && in.ld == Cin && in.coff == 0)) &&
                       (anorm || !fuse.bwd_ey);
@@ -862,7 +794,7 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
                 CDRL_TRY(pw_x3_wide_bwd(dz, pb, wpx, din, din_acc, G, Mg, Cin, Cout, fuse.bwd_ey, fuse.bwd_epi_stats,
                                         fuse.bwd_ey ? sc->part : nullptr, st));
             else
-                CDRL_TRY(pw_nn(dz, nullptr, wb, wb_sk, wb_sn, nullptr, din, din_acc, G, Mg, Cin, Cout, fuse.bwd_ey ? 2 : 0, fuse.bwd_ey,
+                CDRL_TRY(pw_nn(dz, nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout, fuse.bwd_ey ? 2 : 0, fuse.bwd_ey,
                                fuse.bwd_epi_stats, sc->part, st, &pb, wpb, bfc, at));
             // bias gradient = column sums of the (virtual) dy, reduced from the GEMM's partials: rides on the next fork
             double* p2 = part2s_[slot_];
@@ -877,7 +809,7 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
         // main stream: the critical path to the previous layer
         if (din.p) {
             if (fuse.bwd_pw)
-                return pw_nn(make_view(dy, Cout), nullptr, wb, wb_sk, wb_sn, nullptr, din, din_acc, G, Mg, Cin, Cout,
+                return pw_nn(make_view(dy, Cout), nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout,
                              fuse.bwd_ey ? 2 : 0, fuse.bwd_ey, fuse.bwd_epi_stats, sc->part, st, nullptr, wpb, bfc, at);
             if (g3b) return gemm_x3(make_view(dy, Cout), g3b, nullptr, din, rows, Cin, Cout, din_acc, st, bfc, at);
             CDRL_TRY(gemm_nn(make_view(dy, Cout), w.p, 1, Cout, nullptr, din, rows, Cin, Cout, din_acc, st));
@@ -893,8 +825,7 @@ void Learner::add_dw(std::vector<Op>& ops, const std::string& prefix, View in, i
     PRef b = param(M_TRUNK, prefix + ".b", {C}, true);
     const int Ho = same_out_h(H, stride), Wo = same_out_h(W, stride);
     note_scratch(0, 0, (size_t)N * Ho * Wo * C, 0, (size_t)dw_bwd_part_elems(N, H, W, C, stride));
-    static const bool fuse_env = true;
-    const bool fuse = fuse_env && pre_bn && pre_bn->y && din_acc == 0 && pre_bn->C == C && pre_bn->Mg * pre_bn->G == N * H * W;
+    const bool fuse = pre_bn && pre_bn->y && din_acc == 0 && pre_bn->C == C && pre_bn->Mg * pre_bn->G == N * H * W;
     BnRec pre;
     if (fuse) {
         pre = *pre_bn;
@@ -1079,7 +1010,7 @@ void Learner::add_gru(std::vector<Op>& ops, const std::string& name, Tens& x, in
     float* dHb = alloc((size_t)B * u);
     if (!dry_) zero_once_.push_back(std::make_pair(Hs, (size_t)B * u * sizeof(float)));
     if (!gru_step_supported(u)) build_fail("GRU units %d unsupported by the fused step kernels", u);
-    const float* RT = frozen() ? nullptr : pw_transposed(name + ".recurrent", Rp.p, u, U3);        // [3u][u], refreshed with the conv W^T copies
+    const float* RT = frozen() ? nullptr : pw_transposed(name + ".recurrent", Rp.p, u, U3);        // [3u][u], refreshed by the pack launch
     note_scratch((size_t)vcol_geom(T * B, U3).nb * U3, (size_t)vcol_geom(T * B, U3).nb * U3, 0,
                  (size_t)std::max(gemm_tn_part_elems(T * B, U3, In), gemm_tn_part_elems(T * B, U3, u)));
     const int nbc = vcol_geom(T * B, U3).nb;
@@ -1148,17 +1079,6 @@ void Learner::add_aux_fork(std::vector<Op>& ops) {
         if (!side_enabled_) return run_fwd(aux_ops_, st, training);
         hipEvent_t evf = nullptr;
         CDRL_TRY(mark_stream(st, ev_aux_fork_, &evf));        // parameters / inputs produced on the main stream
-        if (aux_worker_ && !graphs_enabled_) {
-            CDRL_TRY(aux_wait());
-            aux_worker_->submit([this, training, evf]() -> int {
-                CDRL_HIP(hipStreamWaitEvent(aux_, evf, 0));
-                CDRL_TRY(run_fwd(aux_ops_, aux_, training));
-                CDRL_HIP(hipEventRecord(ev_aux_done_, aux_));
-                return 0;
-            });
-            aux_inflight_ = true;
-            return 0;
-        }
         CDRL_HIP(hipStreamWaitEvent(aux_, evf, 0));
         CDRL_TRY(run_fwd(aux_ops_, aux_, training));
         CDRL_HIP(hipEventRecord(ev_aux_done_, aux_));
@@ -1171,10 +1091,7 @@ void Learner::add_aux_fork(std::vector<Op>& ops) {
 void Learner::add_aux_join(std::vector<Op>& ops) {
     Op op;
     op.fwd = [=](hipStream_t st, int) -> int {
-        if (side_enabled_) {
-            CDRL_TRY(aux_wait());               // the worker has recorded ev_aux_done_
-            CDRL_HIP(hipStreamWaitEvent(st, ev_aux_done_, 0));
-        }
+        if (side_enabled_) CDRL_HIP(hipStreamWaitEvent(st, ev_aux_done_, 0));
         return 0;
     };
     static const int diag_skip_aux = cdrl_getenv("CDRL_DIAG_SKIP_AUX") ? atoi(cdrl_getenv("CDRL_DIAG_SKIP_AUX")) : 0;     // timing diagnostics only (wrong results)
@@ -1186,17 +1103,6 @@ void Learner::add_aux_join(std::vector<Op>& ops) {
         hipEvent_t evf = nullptr;
         CDRL_TRY(mark_stream(st, ev_aux_fork_, &evf));        // gradient of the concat is ready
         aux_pending_ = true;                                  // joined by join_side() at the end of the backward
-        if (aux_worker_ && !graphs_enabled_) {
-            CDRL_TRY(aux_wait());
-            aux_worker_->submit([this, evf]() -> int {
-                CDRL_HIP(hipStreamWaitEvent(aux_, evf, 0));
-                CDRL_TRY(run_bwd(aux_ops_, aux_));
-                CDRL_HIP(hipEventRecord(ev_aux_done_, aux_));
-                return 0;
-            });
-            aux_inflight_ = true;
-            return 0;
-        }
         CDRL_HIP(hipStreamWaitEvent(aux_, evf, 0));
         CDRL_TRY(run_bwd(aux_ops_, aux_));
         CDRL_HIP(hipEventRecord(ev_aux_done_, aux_));
@@ -1227,16 +1133,15 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         fused_dw_ = !(e && atoi(e) == 0);
         const char* e2 = cdrl_getenv("CDRL_FUSED_PW");       // 0 -> generic tiled GEMM + separate BN passes around the 1x1 convs
         fused_pw_ = !(e2 && atoi(e2) == 0);
-        fused_pw_wide_ = !(e2 && atoi(e2) == 1);        // K, N = 232 (stage-2 units) on the fused path too; 1 -> narrow layers only
-        // BN-backward apply as GEMM operand prologue: bit 0 -> for the unit's first 1x1 conv (bn1), bit 1 -> for the second
-        // (bn3, gathered through the shuffle map); 0 -> separate apply passes with a materialised dy
+        // BN-backward apply as GEMM operand prologue, for both 1x1 convs of a unit (bn1; bn3, gathered through the shuffle map) and the
+        // shortcut conv of the stride-2 units; 0 -> separate apply passes with a materialised dy
         const char* e3 = cdrl_getenv("CDRL_FUSED_BB");
-        // measured at v19: 1 -> 25.5, 0 -> 25.8, 3 -> 26.0, 2 -> 26.2 ms/update-step; re-measured at v29 (buffer-load filter
-        // gradient: the shuffle gather costs nothing there any more): 3 -> 20.66, 1 -> 20.80, 0 -> 21.0, 2 -> 21.3, and with
-        // the wide fused pointwise path 3 -> 20.21.  Bit 2: also for the first unit's conv with 24 input channels -- slower before
-        // the accumulate variant prefetched its old output tile (248 us against 165 us for apply + plain GEMM), now 15.91 vs 15.96
+        // measured at v19 (bit mask: 1 = bn1, 2 = bn3): 1 -> 25.5, 0 -> 25.8, 3 -> 26.0, 2 -> 26.2 ms/update-step; re-measured at v29
+        // (buffer-load filter gradient: the shuffle gather costs nothing there any more): 3 -> 20.66, 1 -> 20.80, 0 -> 21.0, 2 -> 21.3, and
+        // with the wide fused pointwise path 3 -> 20.21.  The first unit's conv with 24 input channels takes it too -- slower before the
+        // accumulate variant prefetched its old output tile (248 us against 165 us for apply + plain GEMM), now 15.91 vs 15.96
         // ms/update-step and one 164 MB tensor less
-        fused_bb_ = e3 ? atoi(e3) : 7;
+        fused_bb_ = !(e3 && atoi(e3) == 0);
         // (round 4's LDS-resident 64-row panel form of the 232-channel forward convs, gemm_pw_wide.hip, is gone: 18 vs 26 us per launch
         //  isolated but 14.43 vs 14.48 ms per update-step, and -- like any change of a float32 forward -- it re-drew the ReLU6 decisions
         //  and moved smoke()'s worst tensor from 6.9e-5 to 9.5e-5 of the 1e-4 gate, both times it was measured: DESIGN.md section 3)
@@ -1289,15 +1194,13 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         op.bwd = [=](hipStream_t st) -> int {
             if (stem_fused) {
                 CDRL_TRY(next_slot(st));
-                // the last kernel of the backward: nothing is left on the critical stream to run beside it, so the hand-over to the side
-                // stream and back only costs its two event bubbles (CDRL_STEM_BWD_MAIN=0 -> side stream as in rounds 1-4)
-                static const bool on_main = true;
-                hipStream_t side = on_main ? st : fork_side(st);
+                // the last kernel of the backward, on the critical stream: nothing is left there to run beside it, so a hand-over to the
+                // side stream and back would only cost its two event bubbles (rounds 1-4 ran it on the side stream)
                 PoolSrc ps = make_pool_src(argmax, pool.g, Hs, Ws);
                 static const bool diag_skip = cdrl_getenv("CDRL_DIAG_SKIP_STEMF") && atoi(cdrl_getenv("CDRL_DIAG_SKIP_STEMF")) == 1;    // timing diagnostics only (no stem filter gradient)
                 if (!diag_skip)
-                    CDRL_TRY(stem_bwd_filter_fused(in_image_, ps, y.p, stem_stats, stem_coef, w.g, b.g, B, T, H, W, Cs, fparts_[slot_], side, at));
-                return done_side(side);
+                    CDRL_TRY(stem_bwd_filter_fused(in_image_, ps, y.p, stem_stats, stem_coef, w.g, b.g, B, T, H, W, Cs, fparts_[slot_], st, at));
+                return 0;
             }
             hipStream_t side = fork_side(st);
             CDRL_TRY(stem_bwd_filter(in_image_, dys_[slot_], w.g, b.g, B, T, H, W, Cs, fparts_[slot_], side));
@@ -1365,8 +1268,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                 note_named(pre + ".out.g", out.g, (size_t)rows_out * C * esz());
                 // stride-2 units: the shortcut branch (dw3x3/s2 -> BN -> 1x1 -> BN+ReLU6) only depends on the unit input; in the
                 // FORWARD pass (where the side stream is idle) it runs on the side stream next to the main branch
-                static const bool sc_overlap_env = true;
-                const bool sc_overlap = sc_overlap_env && stride == 2;
+                const bool sc_overlap = stride == 2;
                 const int sc_ev = s;
                 if (sc_overlap) {
                     Op fk;
@@ -1401,21 +1303,19 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                 Tens y1 = tens_a(rows_in, mid, false);
                 Tens y2 = tens_a(rows_out, mid, false), a2 = tens_a(rows_out, mid);
                 Tens y3 = tens_a(rows_out, main_out, false);
-                // BatchNorm work folded into the 1x1-conv GEMMs (K, N <= 128: stages 0 and 1)
+                // BatchNorm work folded into the 1x1-conv GEMMs, every stage
                 // (the K, N = 232 variants of stage 2 run at one workgroup per CU -- 116 W-fragment VGPRs per wave; slower than the
-                //  tiled GEMM + separate BN passes at v19 (+0.15 ms), faster at v29 (-0.24 ms/update-step): CDRL_FUSED_PW=1 -> off)
-                const bool fpw = fused_dw_ && fused_pw_ && (fused_pw_wide_ || (mid <= 128 && main_in <= 128 && main_out <= 128)) &&
-                                 pw_nn_supported(X.v(main_off), mid, main_in) &&
+                //  tiled GEMM + separate BN passes at v19 (+0.15 ms), faster at v29 (-0.24 ms/update-step))
+                const bool fpw = fused_dw_ && fused_pw_ && pw_nn_supported(X.v(main_off), mid, main_in) &&
                                  pw_nn_supported(y2.v(), main_out, mid) && pw_nn_supported(y3.v(), mid, main_out) &&
                                  pw_nn_supported(y1.v(), main_in, mid);
                 if (fpw) {
                     // BN-backward apply as GEMM operand prologue (needs the filter-gradient GEMM's fixed column mapping)
-                    // (bit 2 of CDRL_FUSED_BB: also for N <= 32 outputs of the backward-data GEMM, i.e. the first unit's 24 input
-                    //  channels; see the default above)
+                    // (also for N <= 32 outputs of the backward-data GEMM, i.e. the first unit's 24 input channels; see CDRL_FUSED_BB above)
                     // (also for the wide stage-2 units: without the prologues there 19.55 vs 18.82 ms/update-step;
                     //  CU-masking the side stream re-measured at v33: 224 / 192 / 128 CUs -> 21.2 / 21.2 / 23.5 vs 18.7 ms)
-                    const bool bb1 = (fused_bb_ & 1) && gemm_tn_dpro_supported(mid) && (main_in > 32 || (fused_bb_ & 4));
-                    const bool bb3 = (fused_bb_ & 2) && gemm_tn_dpro_supported(main_out);
+                    const bool bb1 = fused_bb_ && gemm_tn_dpro_supported(mid);
+                    const bool bb3 = fused_bb_ && gemm_tn_dpro_supported(main_out);
                     float* stats1 = alloc((size_t)4 * T * mid);
                     float* coef1 = alloc((size_t)3 * T * mid);
                     PwFuse f1;
@@ -1516,9 +1416,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                     // conv's operand prologue, sc_bn1's backward sums out of the conv backward (fused conv backward: stages 0 / 1; the
                     // BatchNorm-sum epilogue of the wide kernel: stage 2).  Before: 3 more launches per stride-2 unit on the critical
                     // stream of every backward (apply of sc_bn2, reduce + finalize of sc_bn1) and two on the forward's side stream.
-                    static const bool sc_fused_env = !(cdrl_getenv("CDRL_FUSED_SC") && atoi(cdrl_getenv("CDRL_FUSED_SC")) == 0);
-                    const bool sc_fpw = sc_fused_env && fused_dw_ && fused_pw_ && (fused_pw_wide_ || sc_c <= 128) && (fused_bb_ & 2) &&
-                                        gemm_tn_dpro_supported(sc_c) && pw_nn_supported(ys1.v(), sc_c, sc_c);
+                    const bool sc_fpw = fused_dw_ && fused_pw_ && fused_bb_ && gemm_tn_dpro_supported(sc_c) && pw_nn_supported(ys1.v(), sc_c, sc_c);
                     if (sc_fpw) {
                         const int nbb_sc = pw_bwd_nbpg(T, Mg_out, sc_c, sc_c);      // conv backward-data epilogue rows (BatchNorm sums of sc_bn1)
                         float* coef_s1 = nullptr;
@@ -1607,27 +1505,14 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         Tens yh = tens_a(rows, c.last, false);
         add_pw(ops, "img.head.conv", X.v(), rows, curC, c.last, yh.p, X.gv(), 0, bnrec(T, B * P, c.last));
         feat_ = tens(N, c.last);
-        static const bool gap_fused = true;
-        if (gap_fused) {
-            // BatchNorm + ReLU6 + GlobalAveragePooling2D as one op: the 12288 x 768 activated tensor and its gradient are never
-            // written -- the forward pools on the fly, the backward reads the pooled gradient broadcast over the frame's pixels
-            Passthrough hp;
-            hp.gap_out = feat_.p;
-            hp.gap_dout = feat_.g;
-            hp.gap_rows = P;
-            add_bn(ops, M_TRUNK, "img.head.bn", yh.v(), T, B * P, c.last, true, ACT_RELU6, View{nullptr, 0, 0}, 0, View{nullptr, 0, 0}, 0,
-                   nullptr, 0, false, hp);
-        } else {
-            if (at) build_fail("bf16 activation storage needs the fused head pool (CDRL_FUSED_GAP=0 is set)");
-            Tens ah = tens(rows, c.last);
-            add_bn(ops, M_TRUNK, "img.head.bn", yh.v(), T, B * P, c.last, true, ACT_RELU6, ah.v(), 0, ah.gv(), 0, nullptr);
-            Tens feat = feat_;
-            const int Cl = c.last;
-            Op gp;
-            gp.fwd = [=](hipStream_t st, int) -> int { return gap_fwd(ah.p, feat.p, N, P, Cl, st); };
-            gp.bwd = [=](hipStream_t st) -> int { return gap_bwd(feat.g, ah.g, N, P, Cl, st); };
-            ops.push_back(gp);
-        }
+        // BatchNorm + ReLU6 + GlobalAveragePooling2D as one op: the 12288 x 768 activated tensor and its gradient are never
+        // written -- the forward pools on the fly, the backward reads the pooled gradient broadcast over the frame's pixels
+        Passthrough hp;
+        hp.gap_out = feat_.p;
+        hp.gap_dout = feat_.g;
+        hp.gap_rows = P;
+        add_bn(ops, M_TRUNK, "img.head.bn", yh.v(), T, B * P, c.last, true, ACT_RELU6, View{nullptr, 0, 0}, 0, View{nullptr, 0, 0}, 0,
+               nullptr, 0, false, hp);
     }
 
     // every trunk parameter registered from here on is a TAIL tensor (feature nets, GRUs, concat BN + Dense): their gradients
@@ -1673,7 +1558,6 @@ void Learner::build_trunk(std::vector<Op>& ops) {
             // under hipGraph capture the external communication stream must not be pulled into the capture (it would never be
             // joined, and a replay would never release it): the caller falls back to the single post-pass all-reduce
             if (!comm_ || graphs_enabled_) return 0;
-            CDRL_TRY(aux_wait());
             CDRL_HIP(hipEventRecord(ev_tail_main_, st));          // (recorded, with its system-scope fence: the collectives read these bytes)
             CDRL_HIP(hipStreamWaitEvent(comm_, ev_tail_main_, 0));
             if (side_enabled_) {
@@ -1711,8 +1595,7 @@ void Learner::build_head(std::vector<Op>& ops, int model, const std::string& pre
     int L = 0;
     for (int i = 0; i < nheads; ++i) L += head_dims[i];
     lin = tens(B, L);
-    static const bool fused_heads = true;
-    if (fused_heads && nheads <= HEADS_MAX && L <= HEADS_MAX_OUT) {
+    if (nheads <= HEADS_MAX && L <= HEADS_MAX_OUT) {
         // all linear heads of the branch in one launch per direction (heads.hip); same parameter names / order as add_dense
         HeadSet hs{};
         hs.nheads = nheads;
@@ -1987,15 +1870,6 @@ int Learner::bind(const Buffers& b) {
         CDRL_HIP(hipStreamCreateWithPriority(&aux_, hipStreamNonBlocking, prio_lo));
         CDRL_HIP(hipEventCreateWithFlags(&ev_aux_fork_, evf_int));
         CDRL_HIP(hipEventCreateWithFlags(&ev_aux_done_, evf_int));
-        const char* tenv = cdrl_getenv("CDRL_AUX_THREAD");
-        // opt-in (CDRL_AUX_THREAD=1): measured 20.76 vs 20.83 ms/update-step at B=256 -- the host is 8 ms per step ahead of
-        // the GPU in steady state, so the second enqueue thread only pays off for small images (host-bound below ~45x60)
-        if (side_enabled_ && !graphs_enabled_ && tenv && atoi(tenv) == 1) {
-            int dev = 0;
-            CDRL_HIP(hipGetDevice(&dev));
-            aux_worker_.reset(new AuxWorker(dev));
-            side_lag_ = -1;         // (two enqueue threads: the record bookkeeping is single-threaded)
-        }
     }
     if (!hp_stage_) CDRL_HIP(hipHostMalloc(reinterpret_cast<void**>(&hp_stage_), sizeof(DevHP), 0));
     CDRL_HIP(hipMemcpy(hp_dev_, &hp_host_, sizeof(DevHP), hipMemcpyHostToDevice));

@@ -157,171 +157,6 @@ __global__ void __launch_bounds__(256, 2) gemm_nn_kernel(View A, const float* __
 }
 
 // ------------------------------------------------------------------------------------------
-// Persistent "skinny" variant for K <= 128, N <= 128 (all stage-1/2 pointwise convs = most of the
-// GEMM time): the whole weight panel W[K x BN] is loaded into LDS ONCE per workgroup, which then
-// walks over 64-row tiles of A with a continuous register-prefetch pipeline across tile borders.
-// Per slice a thread issues 4 float2 loads instead of 4 + 16 (A + B) -> far fewer VMEM/LDS
-// instructions per MFMA, no per-tile prologue bubble, and the K tail (116 = 3*32 + 20) runs only
-// the k-steps that exist.
-// ------------------------------------------------------------------------------------------
-template <int NT, bool BT, bool VEC>
-__global__ void __launch_bounds__(256, 2) gemm_nn_persist_kernel(View A, const float* __restrict__ Bp, int sbk, int sbn,
-                                                                 const float* __restrict__ bias, View C, int M, int N,
-                                                                 int K, int accumulate, int ntiles) {
-    constexpr int BMp = 64;
-    constexpr int NTW = NT / 2;
-    constexpr int BN = 32 * NT;
-    constexpr int NA = (BMp * BK) / 256;      // 8
-    extern __shared__ float smem[];
-    const int Kp = (K + 1) & ~1;
-    float* Ws = smem;                          // [Kp][BN + 1]
-    float* As = smem + (size_t)Kp * (BN + 1);  // [2][64][33]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wr = wave & 1, wc = wave >> 1;
-    const int lrow = lane & 31, lk = lane >> 5;
-    for (int idx = tid; idx < Kp * BN; idx += 256) {
-        const int kk = BT ? (idx % Kp) : (idx / BN);
-        const int nn = BT ? (idx / Kp) : (idx % BN);
-        Ws[kk * (BN + 1) + nn] = (kk < K && nn < N) ? Bp[(int64_t)kk * sbk + (int64_t)nn * sbn] : 0.0f;
-    }
-    const int nchunk = (K + BK - 1) / BK;
-    const int my_tiles = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int nsteps = my_tiles * nchunk;
-    float ra[NA];
-
-    auto load_slice = [&](int step) {
-        const int tile = blockIdx.x + (step / nchunk) * gridDim.x;
-        const int k0 = (step % nchunk) * BK;
-        const int64_t m0 = (int64_t)tile * BMp;
-        if (VEC) {
-#pragma unroll
-            for (int i = 0; i < NA / 2; ++i) {
-                const int idx = tid + 256 * i;
-                const int r = idx >> 4, kk = (idx & 15) * 2;
-                const int64_t m = m0 + r;
-                float2 v = make_float2(0.0f, 0.0f);
-                if (m < M && (k0 + kk) < K) v = *reinterpret_cast<const float2*>(&A.p[m * A.ld + A.coff + k0 + kk]);
-                ra[2 * i] = v.x;
-                ra[2 * i + 1] = v.y;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                const int idx = tid + 256 * i;
-                const int r = idx >> 5, kk = idx & 31;
-                const int64_t m = m0 + r;
-                ra[i] = (m < M && (k0 + kk) < K) ? A.p[m * A.ld + A.coff + k0 + kk] : 0.0f;
-            }
-        }
-    };
-    auto store_slice = [&](int buf) {
-        float* Ab = As + buf * (BMp * (BK + 1));
-        if (VEC) {
-#pragma unroll
-            for (int i = 0; i < NA / 2; ++i) {
-                const int idx = tid + 256 * i;
-                const int r = idx >> 4, kk = (idx & 15) * 2;
-                Ab[r * (BK + 1) + kk] = ra[2 * i];
-                Ab[r * (BK + 1) + kk + 1] = ra[2 * i + 1];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                const int idx = tid + 256 * i;
-                Ab[(idx >> 5) * (BK + 1) + (idx & 31)] = ra[i];
-            }
-        }
-    };
-
-    f32x16 acc[NTW];
-#pragma unroll
-    for (int j = 0; j < NTW; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-    if (nsteps > 0) {
-        load_slice(0);
-        store_slice(0);
-    }
-    __syncthreads();
-    int buf = 0;
-    for (int step = 0; step < nsteps; ++step) {
-        const bool more = (step + 1) < nsteps;
-        if (more) load_slice(step + 1);
-        const int chunk = step % nchunk;
-        const int k0 = chunk * BK;
-        const int kmax = min(BK, Kp - k0);
-        const float* Ab = As + buf * (BMp * (BK + 1)) + (wr * 32 + lrow) * (BK + 1) + lk;
-        const float* Wb = Ws + (size_t)(k0 + lk) * (BN + 1) + wc * 32 + lrow;
-#pragma unroll 4
-        for (int kk = 0; kk < kmax; kk += 2) {
-            const float a = Ab[kk];
-#pragma unroll
-            for (int j = 0; j < NTW; ++j) {
-                const float b = Wb[kk * (BN + 1) + j * 64];
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[j], 0, 0, 0);
-            }
-        }
-        if (chunk == nchunk - 1) {      // tile finished: epilogue, then reset the accumulators
-            const int tile = blockIdx.x + (step / nchunk) * gridDim.x;
-            const int64_t m0 = (int64_t)tile * BMp;
-#pragma unroll
-            for (int j = 0; j < NTW; ++j) {
-                const int n = (wc + j * 2) * 32 + lrow;
-                if (n < N) {
-                    const float bv = bias ? bias[n] : 0.0f;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int64_t m = m0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                        if (m < M) {
-                            float* c = &C.p[m * C.ld + C.coff + n];
-                            float v = acc[j][r] + bv;
-                            if (accumulate) v += *c;
-                            *c = v;
-                        }
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-            }
-        }
-        if (more) store_slice(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-}
-
-template <int NT>
-static int launch_nn_persist(bool bt, bool vec, hipStream_t st, View A, const float* Bp, int sbk, int sbn, const float* bias,
-                             View C, int M, int N, int K, int acc) {
-    const int Kp = (K + 1) & ~1;
-    const size_t lds = ((size_t)Kp * (32 * NT + 1) + 2 * 64 * (BK + 1)) * sizeof(float);
-    const int ntiles = cdiv(M, 64);
-    int grid = 512;                 // 2 resident workgroups per CU
-    if (grid > ntiles) grid = ntiles;
-#define CDRL_PERSIST(BTv, VECv)                                                                                         \
-    do {                                                                                                                \
-        static LdsAttrOnce attr_done;                                                                                   \
-        if (attr_done.need()) {                                                                                               \
-            CDRL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nn_persist_kernel<NT, BTv, VECv>),           \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                       \
-            attr_done.mark();                                                                                             \
-        }                                                                                                               \
-        hipLaunchKernelGGL((gemm_nn_persist_kernel<NT, BTv, VECv>), dim3(grid), dim3(256), lds, st, A, Bp, sbk, sbn, bias, \
-                           C, M, N, K, acc, ntiles);                                                                    \
-    } while (0)
-    if (bt) {
-        if (vec) CDRL_PERSIST(true, true);
-        else CDRL_PERSIST(true, false);
-    } else {
-        if (vec) CDRL_PERSIST(false, true);
-        else CDRL_PERSIST(false, false);
-    }
-#undef CDRL_PERSIST
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
 // Row-stacked variant for the wide late layers (stage-3 units K = N = 232, head conv 464 -> 768): a (32*RT) x 128
 // tile, wave w owns column tile w and RT row tiles, so one B fragment feeds RT MFMAs (LDS reads per MFMA: (RT+1)/RT
 // instead of 3/2) and M = 12288 splits into exactly 256 workgroups at RT = 3 (the 64 x 128 tiling gave 384 = 1.5
@@ -567,31 +402,15 @@ int gemm_nn(View A, const float* Bp, int sbk, int sbn, const float* bias, View C
     const bool bt = sbn != 1;
     const bool vec = (K % 2 == 0) && (A.ld % 2 == 0) && (A.coff % 2 == 0) && ((reinterpret_cast<uintptr_t>(A.p) & 7) == 0);
     {   // row-stacked tiles for the wide late layers
-        static const int rt = 3;
-        static const int rt_minn = 129;
+        static constexpr int rt_minn = 129;
         const bool a16 = (K % 4 == 0) && (A.ld % 4 == 0) && (A.coff % 4 == 0) && ((reinterpret_cast<uintptr_t>(A.p) & 15) == 0);
         const bool b16 = ((reinterpret_cast<uintptr_t>(Bp) & 15) == 0) &&
                          (bt ? (sbk == 1 && sbn % 4 == 0) : (sbn == 1 && sbk % 4 == 0 && N % 4 == 0));
-        if (rt >= 2 && rt <= 4 && N >= rt_minn && K >= 64 && M >= 2048 && a16 && b16) {
-            if (rt == 2) launch_nn_rt<2>(bt, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate);
-            else if (rt == 3) launch_nn_rt<3>(bt, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate);
-            else launch_nn_rt<4>(bt, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate);
+        if (N >= rt_minn && K >= 64 && M >= 2048 && a16 && b16) {
+            launch_nn_rt<3>(bt, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate);
             CDRL_LAUNCH_CHECK();
             return 0;
         }
-    }
-    static int persist = -1;
-    if (persist < 0) {
-        // measured at B=256 (768 tiles of 64 rows over 512 resident workgroups): 40.8 us vs 26.7 us for the
-        // non-persistent 64-row kernel at M=49152, K=N=116 -- too few tiles per workgroup to amortise the
-        // weight panel, and 1.5 tiles/workgroup is badly balanced.  Off by default; worth re-testing at B>=1024.
-        persist = 0;
-    }
-    if (persist && gy == 1 && K <= 128 && (nt == 2 || nt == 4) && M >= 4096) {
-        if (nt == 2) CDRL_TRY(launch_nn_persist<2>(bt, vec, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate));
-        else CDRL_TRY(launch_nn_persist<4>(bt, vec, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate));
-        CDRL_LAUNCH_CHECK();
-        return 0;
     }
     const bool small = (nt % 2 == 0) && (cdiv(M, 128) * gy < g_nn_bm64_threshold);
     if (small) {
@@ -741,13 +560,13 @@ __global__ void __launch_bounds__(256) tn_reduce_few_kernel(const float* __restr
 
 int reduce_partials_f32(const float* part, int nparts, int64_t n, int64_t stride, float* out, int accumulate,
                         hipStream_t st) {
-    static const bool v4 = true;
-    if (v4 && n % 4 == 0 && stride % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0 && nparts < 16 && n >= 4096) {
+    const bool v4 = n % 4 == 0 && stride % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0;
+    if (v4 && nparts < 16 && n >= 4096) {
         hipLaunchKernelGGL(tn_reduce_few_kernel, dim3((unsigned)cdiv64(n, 1024)), dim3(256), 0, st, part, nparts, n, stride, out, accumulate);
         CDRL_LAUNCH_CHECK();
         return 0;
     }
-    if (v4 && n % 4 == 0 && stride % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0 && nparts >= 16) {
+    if (v4 && nparts >= 16) {
         if (cdiv64(n, 64) >= 160)
             hipLaunchKernelGGL(tn_reduce_v4_kernel<16>, dim3((unsigned)cdiv64(n, 64)), dim3(256), 0, st, part, nparts, n, stride, out, accumulate);
         else if (cdiv64(n, 16) >= 128 || nparts < 128)

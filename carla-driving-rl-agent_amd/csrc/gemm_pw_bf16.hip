@@ -195,12 +195,9 @@ static inline int pw_bf16_nt(int N) { return N <= 32 ? 1 : (N <= 64 ? 2 : 4); }
 
 bool pw_bf16_supported(int lda, int a_coff, int N, int K) { return K >= 4 && K <= 128 && N >= 1 && N <= 128 && lda % 4 == 0 && a_coff % 4 == 0 && K % 4 == 0; }
 
-static int pw_bf16_occ() {
-    static const int v = 2;
-    return v < 1 ? 1 : (v > 8 ? 8 : v);
-}
+static constexpr int PW_BF16_OCC = 2;   // workgroups per CU of the grid
 
-int pw_bf16_partial_rows(int G, int Mg, int N, int K) { return pw_bf16_nbpg(G, Mg, 32 * (4 / pw_bf16_nt(N)), pw_bf16_occ()); }
+int pw_bf16_partial_rows(int G, int Mg, int N, int K) { return pw_bf16_nbpg(G, Mg, 32 * (4 / pw_bf16_nt(N)), PW_BF16_OCC); }
 
 int64_t pw_bf16_packed_elems(int K) { return (int64_t)(pw_bf16_kp(K) / 16) * 2 * 128 * 8; }
 

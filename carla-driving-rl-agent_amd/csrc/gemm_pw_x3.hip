@@ -546,24 +546,20 @@ int pw_x3_pack_many(const PwX3Pack* tab_dev, int n, hipStream_t st) {
 bool pw_x3_supported(View A, int N, int K) {
     // K <= 128 (the persistent kernel): its A chunks are 16-byte BUFFER loads, which need dword alignment only, and columns beyond K
     // inside the last chunk are zeroed -- so the 58-channel rows of stage 0 (232-byte pitch, channel offset 58) qualify (round 6;
-    // CDRL_PW_X3_UNALIGNED=0 -> 16-byte aligned rows only, as before: those convs then stay on the float32 matrix pipe)
-    static const bool unal = !(cdrl_getenv("CDRL_PW_X3_UNALIGNED") && atoi(cdrl_getenv("CDRL_PW_X3_UNALIGNED")) == 0);
-    if (unal && K >= 4 && K <= 128 && N >= 1 && N <= 128 && K % 2 == 0 && A.ld % 2 == 0 && A.coff % 2 == 0 &&
+    // before, only 16-byte aligned rows did, and those convs stayed on the float32 matrix pipe)
+    if (K >= 4 && K <= 128 && N >= 1 && N <= 128 && K % 2 == 0 && A.ld % 2 == 0 && A.coff % 2 == 0 &&
         (reinterpret_cast<uintptr_t>(A.p) & 15) == 0)
         return true;
     return K >= 4 && K <= 256 && N >= 1 && N <= 256 && K % 4 == 0 && A.ld % 4 == 0 && A.coff % 4 == 0 &&
            (reinterpret_cast<uintptr_t>(A.p) & 15) == 0;
 }
 
-static int x3_occ() {
-    static const int v = 2;
-    return v < 1 ? 1 : (v > 8 ? 8 : v);
-}
+static constexpr int X3_OCC = 2;        // workgroups per CU of the grid: pw_x3_kernel's __launch_bounds__(256, 2)
 
 int pw_x3_partial_rows(int G, int Mg, int N, int K) {
     if (x3_wide(N, K)) return cdiv(Mg, 32);         // one partial row per 32-row tile
     const int bm = 32 * (4 / x3_nt(N)), tiles = cdiv(Mg, bm);
-    int nb = 256 * x3_occ() / G;
+    int nb = 256 * X3_OCC / G;
     if (nb < 1) nb = 1;
     return nb > tiles ? tiles : nb;
 }

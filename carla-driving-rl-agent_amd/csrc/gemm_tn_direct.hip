@@ -441,8 +441,7 @@ static TndPlan tnd_plan(int M, int N, int K, int G, bool dpro = false) {
     p.gy = cdiv(K, 128);
     p.gz = cdiv(N, 128);
     int KT = K >= 128 ? 4 : cdiv(K, 32), NT = N >= 128 ? 4 : cdiv(N, 32);   // tiles of the (first) 128-block
-    static const bool tr_on = true;
-    p.TR = (dpro && tr_on) ? 1 : 0;
+    p.TR = dpro ? 1 : 0;
     if (p.TR) {                                  // same mapping with the roles of k and n exchanged
         const int t = KT;
         KT = NT;
@@ -456,13 +455,12 @@ static TndPlan tnd_plan(int M, int N, int K, int G, bool dpro = false) {
     p.RS = left / p.NSPL;
     const int Mg = M / G;
     // enough workgroups to fill the chip a few times over, but >= 128 rows each so that the partial buffer stays small
-    static const int tn_target = 1024;     // 2048 doubles the split-M partial traffic (8.8 GB/update-step) for no measurable gain
+    static constexpr int tn_target = 1024;     // 2048 doubles the split-M partial traffic (8.8 GB/update-step) for no measurable gain
     int target = tn_target / (p.gy * p.gz * G * p.RS);
     if (target < 1) target = 1;
-    static const int tn_minrows = 128;
+    static constexpr int tn_minrows = 128;
     // in-workgroup row halves (8 waves): the same rows per wave, twice the rows per partial
-    static const int tn_rs2 = 2;
-    p.RS2 = (tn_rs2 == 2 && Mg >= 2 * tn_minrows) ? 2 : 1;
+    p.RS2 = Mg >= 2 * tn_minrows ? 2 : 1;
     int ns = Mg / (tn_minrows * p.RS2);
     if (ns > target) ns = target;
     if (ns < 1) ns = 1;
@@ -506,11 +504,8 @@ static void launch_tnd(bool apro, bool dpro, dim3 grid, hipStream_t st, const Tn
         launch_tnd_u<NJW, 8, 1>(apro, dpro, grid, st, a);
         return;
     }
-    static const int u = 4;
-    static const int ud = 8;      // D prologue (transposed mapping: 200 VGPRs at U = 8; 19.6 -> 19.2 ms/update-step over U = 4)
-    const int uu = dpro ? ud : u;
-    if (uu >= 16 && !dpro) launch_tnd_u<NJW, 16, 0>(apro, dpro, grid, st, a);
-    else if (uu >= 8) launch_tnd_u<NJW, 8, 0>(apro, dpro, grid, st, a);
+    // U = 8 with a D prologue (transposed mapping: 200 VGPRs at U = 8; 19.6 -> 19.2 ms/update-step over U = 4), else U = 4
+    if (dpro) launch_tnd_u<NJW, 8, 0>(apro, dpro, grid, st, a);
     else launch_tnd_u<NJW, 4, 0>(apro, dpro, grid, st, a);
 }
 
@@ -529,12 +524,10 @@ int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int a
         set_error("gemm_tn: operands of 2 GB or more are not supported (M=%d)", M);
         return -1;
     }
-    static const bool trace = false;      // shapes of the filter-gradient GEMMs
-    if (trace) fprintf(stderr, "gemm_tn M=%d K=%d N=%d G=%d apro=%d dpro=%d shuffle=%d bf16=%d at=%d\n", M, K, N, G, pro_stats != nullptr, dpro != nullptr, dpro ? dpro->shuffle_ctot : 0, (int)bf16_operands, at);
     static const bool diag_skip = cdrl_getenv("CDRL_DIAG_SKIP_TN") && atoi(cdrl_getenv("CDRL_DIAG_SKIP_TN")) == 1;   // timing diagnostics only
     if (diag_skip) return 0;
     // bf16 modes: operands staged once per workgroup through LDS (gemm_tn_lds.hip) -- the direct form is a stream of 2-byte loads
-    // there; CDRL_TN_LDS=0 keeps the direct form, CDRL_TN_LDS=1 restricts the LDS form to one column block (96 <= K, N <= 128).
+    // there.
     // Shapes: its 128 x 128 column block with one k tile per wave only pays for wide products -- measured isolated at B = 1024:
     // K = N = 116: 47.6 vs 64.2 us, 232: 40.9 vs 58.3 us, but K = N = 58: 82.9 vs 68.2 us and 24 x 58: 264 vs 126 us.
     // (A NARROW geometry of the LDS kernel for the K, N <= 64 convs of stage 0 -- one 64-column block, 64-row chunks, the <= 4 tile
@@ -544,9 +537,7 @@ int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int a
     // (Until the ReLU6 masks became single compares -- relu6_open(), cdrl_common.h -- the shapes with several column blocks were kept
     //  off this path: next to them the fused backward-data GEMM on the main stream lost its run-to-run reproducibility.  The cause
     //  was in that kernel's mask code, not here: DESIGN.md "What round 3 found", tools/det_co.py.)
-    static const int lds_mode = 2;
-    const bool lds_shape = K >= 96 && N >= 96 && (lds_mode == 2 || (K <= 128 && N <= 128));
-    if (bf16_operands && lds_mode != 0 && lds_shape && gemm_tn_lds_supported(A, D, N, K, dpro))
+    if (bf16_operands && K >= 96 && N >= 96 && gemm_tn_lds_supported(A, D, N, K, dpro))
         return gemm_tn_lds(A, D, Cout, M, N, K, part, accumulate, st, G, pro_stats, dpro, at);
     // float32 tensors through the same staging: three bf16 planes per operand + six plane products on the bf16 pipe (exact split, float32-
     // accurate).  Round 3 measured it at K = N = 116, M = 196608 (B = 1024), isolated: direct 87.6 us, float32-MFMA LDS form 104.1 us,
@@ -554,10 +545,10 @@ int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int a
     // then the stage-0 / stage-1 filter gradients ran next to it on the side stream.  Since the fused conv backward took those over, what is
     // left here are the 232-channel convs of stage 2, the head conv and the shortcut convs, and the faster kernel shortens the contention
     // with the critical stream: round 5, same box, 14.27 (direct) | 14.31 (float32-MFMA LDS form) | 14.01 ms (this form).  Default since
-    // round 5; CDRL_TN_LDS_F32=0 -> direct form, 1 -> float32 LDS columns + v_mfma_f32_32x32x2_f32.
-    static const int lds_f32 = cdrl_getenv("CDRL_TN_LDS_F32") ? atoi(cdrl_getenv("CDRL_TN_LDS_F32")) : 2;
-    if (!bf16_operands && lds_f32 && K >= 96 && N >= 96 && gemm_tn_lds_supported(A, D, N, K, dpro))
-        return gemm_tn_lds(A, D, Cout, M, N, K, part, accumulate, st, G, pro_stats, dpro, 0, lds_f32 == 2 ? 2 : 1);
+    // round 5; CDRL_TN_LDS_F32=1 -> float32 LDS columns + v_mfma_f32_32x32x2_f32.
+    static const bool f32_mfma = cdrl_getenv("CDRL_TN_LDS_F32") && atoi(cdrl_getenv("CDRL_TN_LDS_F32")) == 1;
+    if (!bf16_operands && K >= 96 && N >= 96 && gemm_tn_lds_supported(A, D, N, K, dpro))
+        return gemm_tn_lds(A, D, Cout, M, N, K, part, accumulate, st, G, pro_stats, dpro, 0, f32_mfma ? 1 : 2);
     const TndPlan p = tnd_plan(M, N, K, G, dpro != nullptr);
     TnDirectArgs a;
     a.A = A;

@@ -336,16 +336,4 @@ int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1,
     return 0;
 }
 
-__global__ void adam_tick_kernel(DevHP* hp, int which) {
-    if (which == 0) hp->t_policy += 1;
-    else if (which == 1) hp->t_value += 1;
-    else hp->t_dynamics += 1;
-}
-
-int adam_tick(DevHP* hp, int which, hipStream_t st) {
-    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, st, hp, which);
-    CDRL_LAUNCH_CHECK();
-    return 0;
-}
-
 }  // namespace cdrl

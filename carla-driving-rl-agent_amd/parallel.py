@@ -10,7 +10,6 @@ applies the identical clip + Adam update (parameters and Adam state stay replica
 BatchNorm statistics are local to a rank's minibatch (N independent reference agents sharing
 weights); the moving statistics are averaged with a second, tiny all-reduce.
 """
-import os
 
 import torch
 import torch.distributed as dist
@@ -62,8 +61,6 @@ class DataParallelLearner:
         self._policy_early = [(0, p_n), (t_off + tower_n, t_off + t_n)]
         self._value_early = [(t_off + tower_n, t_off + t_n + v_n)]
         self._comm = None
-        if os.environ.get('CDRL_DP_OVERLAP', '1') == '0':       # one fused all-reduce per pass after the backward (round 1 form)
-            overlap = False
         if not self.frozen and self.use_comm_stream(overlap, self.world, self.force, tower_n, t_n,
                                 bool(getattr(engine, 'device', None)) and hasattr(engine, 'set_comm_stream') and engine.grads.is_cuda):
             self._comm = torch.cuda.Stream(device=engine.grads.device)
@@ -193,7 +190,7 @@ class DataParallelLearner:
         """One PPO update-step = one policy minibatch step + one value minibatch step
         (reference rl/agents/ppo.py:199-224).  Frozen trunk: the moving statistics are averaged behind the update with the
         coalesced sync_moving_statistics() (the value pass has no early group to carry them)."""
-        if self.world == 1 and not self.force and os.environ.get('CDRL_SEQUENCE', '1') != '0':
+        if self.world == 1 and not self.force:
             # no collective between the four calls: one hand-over between the caller's stream and the engine's around all of them
             with self.engine.sequence():
                 self.policy_step(policy_batch, resample)

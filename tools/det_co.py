@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Co-execution determinism probe: the fused 1x1-conv backward (bf16 storage) on one stream while another stream runs
 (a) nothing, (b) the LDS filter-gradient GEMM with several column blocks, (c) a torch copy kernel.
-usage: CDRL_TN_LDS=2 tools/det_co.py [reps]"""
+usage: tools/det_co.py [reps]"""
 import ctypes as C, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

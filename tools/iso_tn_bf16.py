@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Isolated timing (HIP events, rotating buffer sets) of the filter-gradient GEMM of a stage-1 unit with the BatchNorm-backward
 operand prologue (cdrl_pwconv_bn_bwd_packed would add the backward-data conv; here only the TN product through cdrl_gemm_tn) at
-B = 1024 shapes: float32 direct, bf16-operand (float32 tensors) and bf16-storage forms.  CDRL_TN_LDS=0 selects the direct form."""
+B = 1024 shapes: float32 and bf16-storage tensors (gemm_tn picks the direct or the LDS-staged kernel per shape)."""
 import ctypes as C
 import os
 import sys
@@ -41,5 +41,4 @@ for (M, K, N) in [(196608, 116, 116), (675840, 58, 58), (49152, 232, 232), (2703
     t16 = timeit(lambda k: lib.cdrl_gemm_tn(P(ab[k]), K, 0, P(db[k]), N, 0, P(dw), M, N, K, P(ws), 0, S()), nsets)
     lib.cdrl_set_op_activation_type(0)
     by = M * (K + N)
-    print(f'M={M} K={K} N={N}: float32 direct {t32:.1f} us ({by * 4 / t32 / 1e3:.0f} GB/s) | bf16 storage {t16:.1f} us ({by * 2 / t16 / 1e3:.0f} GB/s)'
-          f'  [CDRL_TN_LDS={os.environ.get("CDRL_TN_LDS", "1")}]')
+    print(f'M={M} K={K} N={N}: float32 {t32:.1f} us ({by * 4 / t32 / 1e3:.0f} GB/s) | bf16 storage {t16:.1f} us ({by * 2 / t16 / 1e3:.0f} GB/s)')
