@@ -4,6 +4,7 @@ Sub-modules
   _lib      ctypes binding of libcdrl_hip.so (fails loudly when the library is missing)
   engine    LearnerEngine: parameter arenas + workspace as torch tensors, step functions
   synthetic deterministic synthetic rollout buffers
+  train_stats  host side of the update diagnostics: ring rows -> the reference's log keys
   core, rl  host-side mirror of the reference's CARLAgent / CARLANetwork / PPOMemory API
 """
 __version__ = '0.1.0'

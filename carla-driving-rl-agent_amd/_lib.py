@@ -19,7 +19,14 @@ class Config(C.Structure):
                 ('stem', C.c_int32), ('stage_c', C.c_int32 * 3), ('stage_n', C.c_int32 * 3), ('last', C.c_int32),
                 ('feat', C.c_int32), ('rnn_image', C.c_int32), ('rnn_small', C.c_int32), ('dyn', C.c_int32),
                 ('head', C.c_int32), ('exp_scale', C.c_float), ('compute', C.c_int32),
-                ('freeze_trunk', C.c_int32), ('optimizer', C.c_int32), ('polyak', C.c_float)]
+                ('freeze_trunk', C.c_int32), ('optimizer', C.c_int32), ('polyak', C.c_float), ('train_stats', C.c_int32)]
+
+
+class TrainStatsLayout(C.Structure):
+    """cdrl_train_stats_layout (include/cdrl.h): geometry of the train-stats ring and the offsets of a row's fields."""
+    _fields_ = [(n, C.c_int32) for n in ('rows', 'width', 'header', 'kind', 't_head', 't_dynamics', 'lr', 'lr_dynamics', 'clip_ratio',
+                                         'entropy_coef', 'speed', 'similarity', 'metrics', 'norms', 'trunk_norms', 'n_policy',
+                                         'n_value', 'n_trunk')]
 
 
 COMPUTE_F32, COMPUTE_BF16_OPERANDS, COMPUTE_BF16_STORAGE = 0, 1, 2
@@ -83,6 +90,9 @@ PROTOTYPES = {
     'cdrl_learner_set_comm_stream': (_i, [_L, _fp]),
     'cdrl_learner_tail_offset': (_i64, [_L]),
     'cdrl_learner_reset_optimizer_steps': (_i, [_L, _fp]),
+    'cdrl_learner_train_stats_layout': (_i, [_L, C.POINTER(TrainStatsLayout)]),
+    'cdrl_learner_train_stats_buffer': (_i, [_L, C.POINTER(C.c_void_p), C.POINTER(_i64)]),
+    'cdrl_learner_train_stats_reset': (_i, [_L, _fp]),
     'cdrl_learner_policy_forward_backward': (_i, [_L, C.POINTER(PolicyBatch), _f, _fp]),
     'cdrl_learner_policy_forward': (_i, [_L, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_learner_policy_backward': (_i, [_L, C.POINTER(PolicyBatch), _f, _fp]),

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .. import train_stats
 from ..parallel import DataParallelLearner
 from ..rl import utils, spaces
 from ..rl.agents.ppo import PPOAgent, PPOMemory
@@ -233,6 +234,12 @@ class CARLAgent(PPOAgent):
             self._reset_info()
             return
         super().update()
+        if self.statistics.mode is not None:        # (reference core/carla_agent.py:137-140)
+            kw = train_stats.action_entries(self.memory.actions)
+            if kw is None:
+                print('[update] unable to print actions')
+            else:
+                self.log(**kw)
         self._reset_info()
 
     def _reset_info(self):

@@ -64,7 +64,8 @@ class CARLANetwork(Network):
         CARLAgent passes its own update_dynamics.  (The reference's keyword defaults to False but is never read there; here it
         drives the engine, so the default is the agent's.)
         The agent's optimizer name and polyak coefficient (PPOAgent(optimizer=..., polyak=...)) configure every engine built here
-        (cdrl_config.optimizer / polyak)."""
+        (cdrl_config.optimizer / polyak).  When the agent logs (log_mode is not None) the learner engines keep a train-stats ring
+        of `agent.train_stats_rows` rows (cdrl_config.train_stats): `train_stats()` fetches one update()'s diagnostics."""
         super().__init__(agent)
         env = agent.env
         T = env.time_horizon
@@ -90,7 +91,9 @@ class CARLANetwork(Network):
                         head=p_branch['units'], exp_scale=self.exp_scale, compute=compute, freeze_trunk=not update_dynamics,
                         optimizer=getattr(agent, 'optimizer_name', 'adam'), polyak=float(getattr(agent, 'polyak_coeff', 1.0)))
         self.device = agent.device
-        self.engine = LearnerEngine(agent.batch_size, device=self.device, **self.cfg)          # learner minibatches
+        # update diagnostics: the learner engines only (main + ragged share one ring); off when the agent does not log
+        self.train_stats_rows = int(getattr(agent, 'train_stats_rows', 0)) if agent.statistics.mode is not None else 0
+        self.engine = LearnerEngine(agent.batch_size, device=self.device, train_stats=self.train_stats_rows, **self.cfg)   # learner minibatches
         self._rollouts = {}                # number of environments E -> inference engine over the same arenas
         self.rollout = self.rollout_for(1)                                                       # B = 1 inference
         self._ragged = {}                  # minibatch rows -> engine for a ragged last minibatch (shares arenas + optimizer)
@@ -114,8 +117,19 @@ class CARLANetwork(Network):
         if rows == self.engine.cfg.B:
             return self.engine
         if rows not in self._ragged:
-            self._ragged[rows] = LearnerEngine(rows, device=self.device, share_with=self.engine, **self.cfg)
+            self._ragged[rows] = LearnerEngine(rows, device=self.device, share_with=self.engine, train_stats=self.train_stats_rows,
+                                               **self.cfg)
         return self._ragged[rows]
+
+    def train_stats(self, fetch=True):
+        """The learner engines' update diagnostics since the last call (LearnerEngine.train_stats), or None when the ring is off.
+        fetch=False empties the ring without the device-to-host copy (data-parallel ranks that do not write summaries)."""
+        if self.train_stats_rows <= 0:
+            return None
+        if not fetch:
+            self.engine.train_stats_reset()
+            return None
+        return self.engine.train_stats()
 
     # -- hyper-parameters -----------------------------------------------------------------------
     def set_hparams(self, **kw):

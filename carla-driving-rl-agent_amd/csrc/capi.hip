@@ -85,6 +85,7 @@ void cdrl_config_default(cdrl_config* c) {
     c->freeze_trunk = d.freeze_trunk;
     c->optimizer = d.optimizer;
     c->polyak = d.polyak;
+    c->train_stats = d.train_stats;
 }
 
 int cdrl_optimizer_slots(int optimizer, int32_t* used, float* init) {
@@ -149,6 +150,11 @@ int cdrl_learner_create(const cdrl_config* c, cdrl_learner** out) {
         return -1;
     }
     d.polyak = c->polyak;
+    if (c->train_stats < 0 || c->train_stats > (1 << 20)) {
+        cdrl::set_error("cdrl_learner_create: train_stats must be 0 (off) or a row count up to 2^20 (got %d)", c->train_stats);
+        return -1;
+    }
+    d.train_stats = c->train_stats;
     if (cdrl::diag_active()) {      // loud, every time: results of this learner are WRONG by request (timing diagnostics)
         char ov[2048];
         cdrl::env_overrides(ov, (int)sizeof(ov));
@@ -273,8 +279,57 @@ int cdrl_learner_share_hparams(cdrl_learner* l, const cdrl_learner* owner) {
                         (double)a.polyak, b.optimizer, (double)b.polyak);
         return -1;
     }
+    if (a.train_stats > 0 && b.train_stats > 0 && (a.train_stats != b.train_stats || a.freeze_trunk != b.freeze_trunk)) {      // one ring: one layout
+        cdrl::set_error("cdrl_learner_share_hparams: train_stats / freeze_trunk differ (%d, %d vs the owner's %d, %d)", a.train_stats,
+                        a.freeze_trunk, b.train_stats, b.freeze_trunk);
+        return -1;
+    }
     l->impl->share_hp(*owner->impl);
     return 0;
+}
+
+int cdrl_learner_train_stats_layout(const cdrl_learner* l, cdrl_train_stats_layout* out) {
+    CHECK_L(l);
+    if (!out) return -1;
+    const Learner& e = *l->impl;
+    memset(out, 0, sizeof(*out));
+    out->rows = e.stats_rows();
+    if (out->rows <= 0) return 0;
+    out->width = e.stats_width();
+    out->header = Learner::STATS_HEADER;
+    out->kind = STATS_KIND;
+    out->t_head = STATS_T_HEAD;
+    out->t_dynamics = STATS_T_DYNAMICS;
+    out->lr = STATS_LR;
+    out->lr_dynamics = STATS_LR_DYNAMICS;
+    out->clip_ratio = STATS_CLIP_RATIO;
+    out->entropy_coef = STATS_ENTROPY_COEF;
+    out->speed = STATS_SPEED;
+    out->similarity = STATS_SIMILARITY;
+    out->metrics = Learner::STATS_SCALARS;
+    out->norms = e.stats_off_norms();
+    out->trunk_norms = e.stats_off_trunk();
+    out->n_policy = e.stats_tensors(cdrl::M_POLICY);
+    out->n_value = e.stats_tensors(cdrl::M_VALUE);
+    out->n_trunk = e.stats_tensors(cdrl::M_TRUNK);
+    return 0;
+}
+
+int cdrl_learner_train_stats_buffer(const cdrl_learner* l, void** ptr, int64_t* bytes) {
+    CHECK_L(l);
+    if (!ptr || !bytes) return -1;
+    if (!l->impl->stats_ring()) {
+        cdrl::set_error("cdrl_learner_train_stats_buffer: train stats are off (cdrl_config.train_stats = 0) or the learner is not bound");
+        return -1;
+    }
+    *ptr = l->impl->stats_ring();
+    *bytes = (int64_t)l->impl->stats_bytes();
+    return 0;
+}
+
+int cdrl_learner_train_stats_reset(cdrl_learner* l, void* stream) {
+    CHECK_L(l);
+    return l->impl->stats_reset(S(stream));
 }
 
 int cdrl_learner_set_comm_stream(cdrl_learner* l, void* stream) {

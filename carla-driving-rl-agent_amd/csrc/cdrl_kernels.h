@@ -458,6 +458,35 @@ int clip_update(int opt, float polyak, float* p, const float* g, float* m, float
 int reset_steps(DevHP* hp, hipStream_t st);
 int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, hipStream_t st);
 
+// ---------------------------------------------------------------- update diagnostics (train_stats.hip)
+// Chunk partials of a chunk table (sum of squares per 1024-element chunk, float64): one wave per chunk, no LDS.  Same partials
+// contract as sqnorm_chunk_kernel (which also ticks the optimizer counters and is the clip path's): deterministic, no atomics.
+int stats_chunk_sqnorms(const float* g, const TensorSeg* segs_dev, const int* chunk_tensor_dev, const int64_t* chunk_off_dev,
+                        int nchunks, double* chunk_part, hipStream_t st);
+// One ring row of an apply step (layout: include/cdrl.h, cdrl_train_stats_layout).  ring = [header int32 words | rows x width floats];
+// the row index is header[0] % rows, read on the device.  stats_fold_norms writes sqrt(per-tensor sum of chunk partials) of the head
+// (table a) at off_a and of the trunk (table b, nb may be 0) at off_b; stats_write_row, enqueued BEHIND it, writes everything else,
+// zeroes the unused norm slots and advances header[0] (and header[1] when it overwrote an unread row).
+enum StatsSlot : int {      // offsets inside a row's scalar block (KIND, T_HEAD, T_DYNAMICS hold int32 bit patterns)
+    STATS_KIND = 0, STATS_T_HEAD = 1, STATS_T_DYNAMICS = 2, STATS_LR = 3, STATS_LR_DYNAMICS = 4, STATS_CLIP_RATIO = 5,
+    STATS_ENTROPY_COEF = 6, STATS_SPEED = 7, STATS_SIMILARITY = 8, STATS_NSCALARS = 16
+};
+struct StatsRowArgs {
+    float* ring;
+    int header, rows, width;
+    int kind;                   // 0 policy, 1 value
+    const DevHP* hp;
+    const float* metrics;       // 16 floats, copied verbatim
+    const float* lin;           // [B][ld] linear head outputs
+    int B, ld, col_speed, col_similarity;
+    int off_scalars, off_metrics, off_norms, off_trunk;
+    int n_head, n_trunk;
+};
+int stats_fold_norms(float* ring, int header, int rows, int width, const TensorSeg* segs_a, int na, const double* part_a, int off_a,
+                     const TensorSeg* segs_b, int nb, const double* part_b, int off_b, hipStream_t st);
+int stats_write_row(const StatsRowArgs& a, hipStream_t st);
+int stats_reset_ring(float* ring, hipStream_t st);
+
 // ---------------------------------------------------------------- GAE (gae.hip)
 // rewards [N+1] (bootstrap appended), values_be [N+1][2] -> returns_be [N][2], returns [N], adv_raw [N], adv [N]
 int gae_returns(const float* rewards, const float* values_be, int N, double gamma, double lambda, float scale,

@@ -1,6 +1,7 @@
 // Learner engine: owns the layer graph of CARLANetwork (trunk + policy / old-policy / value
 // heads), the flat parameter-arena layout and the workspace plan for one batch size.
 #pragma once
+#include <algorithm>
 #include <functional>
 #include <map>
 #include <memory>
@@ -31,6 +32,7 @@ struct Config {
                             //    trunk forward (batch statistics, moving statistics updated), no trunk backward, no trunk Adam step
     int optimizer = 0;      // CDRL_OPT_* of the policy, value and dynamics optimizers (include/cdrl.h table)
     float polyak = 1.0f;    // < 1: polyak averaging of the heads after their optimizer step
+    int train_stats = 0;    // N > 0: device-resident ring of N update-diagnostics rows, one per apply step (include/cdrl.h)
 };
 
 enum Model : int { M_TRUNK = 0, M_POLICY = 1, M_VALUE = 2, M_OLD_POLICY = 3 };
@@ -171,7 +173,29 @@ public:
     DevHP* dev_hp() const { return hp_dev_; }
     // Use another (bound) learner's device hyper-parameter block -- learning rates, clip, AND the Adam step counters -- so
     // that engines built for different minibatch sizes over the same parameter arenas behave as one optimizer.
-    void share_hp(const Learner& owner) { hp_dev_ = owner.hp_dev_; }
+    // ... and, when both keep a train-stats ring, the owner's ring: the rows of all minibatch sizes land in one sequence.
+    void share_hp(const Learner& owner) {
+        hp_dev_ = owner.hp_dev_;
+        if (stats_ring_ && owner.stats_ring_) stats_ring_ = owner.stats_ring_;
+        drop_graphs();      // (captured kernel arguments name the block)
+    }
+    // Train-stats ring (cfg.train_stats rows; include/cdrl.h): STATS_HEADER int32 words -- [0] rows written since the last reset,
+    // [1] rows overwritten before they were read -- then the rows.
+    static constexpr int STATS_HEADER = 64, STATS_SCALARS = STATS_NSCALARS, STATS_METRICS = 16;
+    int stats_rows() const { return cfg_.train_stats; }
+    // tensors of `model` a row carries a norm for (counted from the parameter table: the planner asks before the chunk tables exist)
+    int stats_tensors(int model) const {
+        int n = 0;
+        if (cfg_.train_stats > 0 && !(model == M_TRUNK && frozen()))
+            for (const ParamInfo& pi : infos_[model]) n += pi.trainable ? 1 : 0;
+        return n;
+    }
+    int stats_off_norms() const { return STATS_SCALARS + STATS_METRICS; }
+    int stats_off_trunk() const { return stats_off_norms() + std::max(stats_tensors(M_POLICY), stats_tensors(M_VALUE)); }
+    int stats_width() const { return cfg_.train_stats > 0 ? (stats_off_trunk() + stats_tensors(M_TRUNK) + 3) / 4 * 4 : 0; }
+    size_t stats_bytes() const { return ((size_t)STATS_HEADER + (size_t)stats_rows() * stats_width()) * sizeof(float); }
+    float* stats_ring() const { return stats_ring_; }
+    int stats_reset(hipStream_t caller);
     // Data-parallel overlap: `s` (a caller-owned stream, or null) is made to wait, in the middle of every backward pass, for
     // the point where the gradients of the heads and of the trunk tail (GRUs, feature nets, concat BN + Dense) are final --
     // a collective enqueued on `s` after the pass has been enqueued then runs UNDER the tower's backward.
@@ -423,6 +447,8 @@ private:
         std::vector<int64_t> h_chunk_off;
     } seg_[3];
     void build_seg_tables();
+    float* stats_ring_ = nullptr;           // header + rows (this learner's, or the hyper-parameter owner's)
+    int stats_row(int kind, hipStream_t st);    // the tail of an apply step: trunk chunk norms, per-tensor fold, row writer
     int upload_seg_tables();
     // transposed copies of weights for backward GEMMs (the GRUs' recurrent kernels; the unit convs read packed W^T fragments instead):
     // refreshed by the pack launch at the start of every training forward

@@ -1699,7 +1699,8 @@ void Learner::build(bool dry) {
     note_named("hparams", hp_dev_, sizeof(DevHP));      // 10 floats (lr x3, clip, entropy, clip norms x2, beta1, beta2, eps), 3 int step counters,
                                                         // 3 Nadam m_caches
     // optimiser tables
-    for (int m = 1; m <= 2; ++m) {
+    // (train stats, unfrozen: the trunk gets a table too -- it is never clipped, its norms are diagnostics only)
+    for (int m = (cfg_.train_stats > 0 && !frozen()) ? 0 : 1; m <= 2; ++m) {
         SegTable& s = seg_[m];
         int nt = 0;
         int64_t nch = 0;
@@ -1713,6 +1714,10 @@ void Learner::build(bool dry) {
         s.chunk_off = reinterpret_cast<int64_t*>(alloc((size_t)nch * 2));
         s.chunk_part = alloc_d((size_t)nch);
         s.sqnorms = alloc((size_t)nt);
+    }
+    if (cfg_.train_stats > 0) {
+        stats_ring_ = alloc(stats_bytes() / sizeof(float));
+        if (!dry_) zero_once_.push_back(std::make_pair(stats_ring_, (size_t)STATS_HEADER * sizeof(float)));
     }
     if (guard_) {       // band table (device) behind everything else; no band behind it
         const bool g = guard_;
@@ -1737,7 +1742,7 @@ void Learner::build(bool dry) {
 }
 
 void Learner::build_seg_tables() {
-    for (int m = 1; m <= 2; ++m) {
+    for (int m = (cfg_.train_stats > 0 && !frozen()) ? 0 : 1; m <= 2; ++m) {
         SegTable& s = seg_[m];
         s.h_segs.clear();
         s.h_chunk_tensor.clear();
@@ -1771,7 +1776,7 @@ int Learner::upload_seg_tables() {
         CDRL_HIP(hipMemcpy(d_pack3_, h_pack3_.data(), h_pack3_.size() * sizeof(PwX3Pack), hipMemcpyHostToDevice));
     if (!h_gpack_.empty())
         CDRL_HIP(hipMemcpy(d_gpack_, h_gpack_.data(), h_gpack_.size() * sizeof(GemmX3Pack), hipMemcpyHostToDevice));
-    for (int m = 1; m <= 2; ++m) {
+    for (int m = (cfg_.train_stats > 0 && !frozen()) ? 0 : 1; m <= 2; ++m) {
         SegTable& s = seg_[m];
         CDRL_HIP(hipMemcpy(s.segs, s.h_segs.data(), s.h_segs.size() * sizeof(TensorSeg), hipMemcpyHostToDevice));
         CDRL_HIP(hipMemcpy(s.chunk_tensor, s.h_chunk_tensor.data(), s.h_chunk_tensor.size() * sizeof(int),
@@ -2069,8 +2074,50 @@ int Learner::policy_apply_impl(hipStream_t st) {
     CDRL_TRY(tensor_sqnorms(buf_.grads + po, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part,
                             s.sqnorms, st, hp_dev_, (frozen() ? 1 : 4 | 1) | nadam, true));
     CDRL_TRY(update_old_policy_impl(st));
-    return clip_update(opt, cfg_.polyak, buf_.params + po, buf_.grads + po, buf_.adam_m + po, buf_.adam_v + po, tr_size_[M_POLICY],
-                       s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 0, st, s.chunk_part, 1);
+    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + po, buf_.grads + po, buf_.adam_m + po, buf_.adam_v + po, tr_size_[M_POLICY],
+                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 0, st, s.chunk_part, 1));
+    return cfg_.train_stats > 0 ? stats_row(0, st) : 0;
+}
+
+// Tail of an apply step with cfg.train_stats > 0: one ring row.  The gradients are read-only during the apply and the head's chunk
+// partials (written by the clip path above, from the unclipped gradient) stay until the head's next apply, so this runs in order
+// behind the updates: one extra read of the trunk gradient, a fold per tensor, the row writer.
+int Learner::stats_row(int kind, hipStream_t st) {
+    const int head = kind == 0 ? M_POLICY : M_VALUE;
+    SegTable &h = seg_[head], &t = seg_[M_TRUNK];
+    const int nt = stats_tensors(M_TRUNK);
+    if (nt > 0)
+        CDRL_TRY(stats_chunk_sqnorms(buf_.grads + tr_offset(M_TRUNK), t.segs, t.chunk_tensor, t.chunk_off, t.nchunks, t.chunk_part, st));
+    CDRL_TRY(stats_fold_norms(stats_ring_, STATS_HEADER, stats_rows(), stats_width(), h.segs, h.ntensors, h.chunk_part, stats_off_norms(),
+                              t.segs, nt, t.chunk_part, stats_off_trunk(), st));
+    StatsRowArgs a;
+    a.ring = stats_ring_;
+    a.header = STATS_HEADER;
+    a.rows = stats_rows();
+    a.width = stats_width();
+    a.kind = kind;
+    a.hp = hp_dev_;
+    a.metrics = kind == 0 ? metrics_p_ : metrics_v_;
+    a.lin = kind == 0 ? lin_p_.p : lin_v_.p;
+    a.B = cfg_.B;
+    a.ld = kind == 0 ? 2 * cfg_.A + 2 : 4;                  // policy: alpha, beta, similarity, speed; value: base, exp, speed, similarity
+    a.col_speed = kind == 0 ? 2 * cfg_.A + 1 : 2;
+    a.col_similarity = kind == 0 ? 2 * cfg_.A : 3;
+    a.off_scalars = 0;
+    a.off_metrics = STATS_SCALARS;
+    a.off_norms = stats_off_norms();
+    a.off_trunk = stats_off_trunk();
+    a.n_head = h.ntensors;
+    a.n_trunk = nt;
+    return stats_write_row(a, st);
+}
+
+int Learner::stats_reset(hipStream_t caller) {
+    if (!stats_ring_) {
+        set_error("train stats are off (cdrl_config.train_stats = 0) or the learner is not bound");
+        return -1;
+    }
+    return launch(caller, {}, false, [&](hipStream_t st) -> int { return stats_reset_ring(stats_ring_, st); });
 }
 
 int Learner::value_apply(hipStream_t caller) {
@@ -2086,8 +2133,9 @@ int Learner::value_apply_impl(hipStream_t st) {
     SegTable& s = seg_[M_VALUE];
     CDRL_TRY(tensor_sqnorms(buf_.grads + vo, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part,
                             s.sqnorms, st, hp_dev_, (frozen() ? 2 : 4 | 2) | nadam, true));       // (see policy_apply_impl)
-    return clip_update(opt, cfg_.polyak, buf_.params + vo, buf_.grads + vo, buf_.adam_m + vo, buf_.adam_v + vo, tr_size_[M_VALUE],
-                       s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 1, st, s.chunk_part, 1);
+    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + vo, buf_.grads + vo, buf_.adam_m + vo, buf_.adam_v + vo, tr_size_[M_VALUE],
+                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 1, st, s.chunk_part, 1));
+    return cfg_.train_stats > 0 ? stats_row(1, st) : 0;
 }
 
 int Learner::predict(const float* image, const float* road, const float* vehicle, const float* navigation,

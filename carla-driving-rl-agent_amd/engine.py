@@ -66,7 +66,10 @@ class LearnerEngine:
         freeze_trunk=True -> the passes train the heads only on a fixed trunk (cdrl_config.freeze_trunk, include/cdrl.h).
         optimizer -> one of _lib.OPTIMIZERS, any letter case (the reference's get_optimizer_by_name), for the policy, value and
         dynamics optimizers; its slots live in the adam_m / adam_v arenas (optimizer_slots).  polyak in (0, 1]: < 1 averages the
-        heads after each optimizer step (cdrl_config.optimizer / polyak, include/cdrl.h)."""
+        heads after each optimizer step (cdrl_config.optimizer / polyak, include/cdrl.h).
+        train_stats=N > 0 -> every policy_apply / value_apply appends one row of update diagnostics to a device ring of N rows
+        (cdrl_config.train_stats); train_stats() fetches them.  Not inherited through share_with (rollout engines have no use for
+        it); an engine that is given it appends to the ring of the engine it shares with, when that one has a ring too."""
         self.lib = _lib.load()
         if share_with is not None:
             cfg.setdefault('freeze_trunk', share_with.frozen)
@@ -82,6 +85,9 @@ class LearnerEngine:
         used, init = (C.c_int32 * 2)(), (C.c_float * 2)()
         _lib.check(self.lib.cdrl_optimizer_slots(self.cfg.optimizer, used, init), 'cdrl_optimizer_slots')
         self.slot_init = (float(init[0]), float(init[1]))       # initial value of the adam_m / adam_v arena's slot
+        lay = _lib.TrainStatsLayout()
+        _lib.check(self.lib.cdrl_learner_train_stats_layout(h, C.byref(lay)), 'cdrl_learner_train_stats_layout')
+        self.train_stats_layout = {n: int(getattr(lay, n)) for n, _ in lay._fields_}      # rows == 0: the ring is off
         self.tables = {m: ParamTable(self.lib, h, mid) for m, mid in (('trunk', TRUNK), ('policy', POLICY), ('value', VALUE))}
         self.params_total = int(self.lib.cdrl_learner_params_total(h))
         self.grads_total = int(self.lib.cdrl_learner_grads_total(h))
@@ -202,6 +208,32 @@ class LearnerEngine:
         self.adam_m.fill_(self.slot_init[0])
         self.adam_v.fill_(self.slot_init[1])
         _lib.check(self.lib.cdrl_learner_reset_optimizer_steps(self.h, self._stream()), 'reset_optimizer_steps')
+
+    def _stats_owner(self):
+        owner = getattr(self, '_hp_owner', None)
+        return owner if owner is not None and owner.train_stats_layout['rows'] > 0 else self
+
+    def train_stats_reset(self):
+        """Empties the train-stats ring without reading it (enqueued on the current stream)."""
+        _lib.check(self.lib.cdrl_learner_train_stats_reset(self.h, self._stream()), 'train_stats_reset')
+
+    def train_stats(self):
+        """The update diagnostics written by the apply steps since the last call (this engine's and those of the engines sharing
+        its ring), oldest first: dict(rows=[...], dropped=rows lost to a full ring); see train_stats.decode for a row.  ONE
+        device-to-host copy, then the ring is reset.  None when the ring is off (train_stats=0)."""
+        if self.train_stats_layout['rows'] <= 0:
+            return None
+        from . import train_stats as ts
+        own = self._stats_owner()           # the ring lives in the workspace of the engine whose hyper-parameters are shared
+        p, n = C.c_void_p(), C.c_int64()
+        _lib.check(self.lib.cdrl_learner_train_stats_buffer(self.h, C.byref(p), C.byref(n)), 'train_stats_buffer')
+        off = p.value - own.workspace.data_ptr()
+        if off < 0 or off + n.value > own.workspace.numel():
+            raise _lib.CdrlError('train-stats ring outside the workspace')
+        block = own.workspace[off: off + n.value].view(torch.float32).cpu().numpy()
+        self.train_stats_reset()
+        names = {m: [e['name'] for e in self.tables[m].entries if e['trainable']] for m in ('policy', 'value', 'trunk')}
+        return ts.decode(block, self.train_stats_layout, names)
 
     def buffer(self, which: int, shape=None) -> torch.Tensor:
         """Zero-copy torch view of an engine-owned workspace buffer."""

@@ -15,13 +15,17 @@ from .. import utils
 from ..parameters import DynamicParameter
 from .agents import Agent
 from ..._lib import OPTIMIZERS
+from ... import train_stats
 
 
 class PPOAgent(Agent):
     def __init__(self, *args, policy_lr=1e-3, gamma=0.99, lambda_=0.95, value_lr=3e-4, load=False,
                  optimization_steps=(1, 1), name='ppo-agent', optimizer='adam', clip_norm=(1.0, 1.0), clip_ratio=0.2,
                  seed_regularization=False, entropy_regularization=0.0, network: dict = None, update_frequency=1,
-                 polyak=1.0, repeat_action=1, advantage_scale=2.0, **kwargs):
+                 polyak=1.0, repeat_action=1, advantage_scale=2.0, train_stats_rows=256, **kwargs):
+        """train_stats_rows: capacity, in minibatch steps, of the device ring the learner engines append their per-step diagnostics
+        to when the agent logs (log_mode is not None); update() reads it once.  An update() with more policy + value steps than
+        that keeps the newest rows and reports how many it lost."""
         assert 0.0 < polyak <= 1.0
         assert repeat_action >= 1
         # utils.get_optimizer_by_name (reference rl/utils.py:29-46): one Keras optimizer class, by name, for the policy and value
@@ -29,6 +33,7 @@ class PPOAgent(Agent):
         if str(optimizer).lower() not in OPTIMIZERS:
             raise ValueError(f'Cannot find optimizer {optimizer}. Select one of {OPTIMIZERS}.')
         self.optimizer_name = str(optimizer).lower()
+        self.train_stats_rows = int(train_stats_rows)
         super().__init__(*args, name=name, **kwargs)
         self.memory: PPOMemory = None
         self.gamma = gamma
@@ -119,6 +124,7 @@ class PPOAgent(Agent):
                 self.update_value(grads)
                 self.log(loss_value=value_loss, lr_value=self.value_lr.value)
         self.after_update()
+        self.log_train_stats()
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         print(f'Update took {round(time.time() - t0, 3)}s')
@@ -129,6 +135,23 @@ class PPOAgent(Agent):
 
     def after_update(self):
         """Hook for data-parallel agents (BatchNorm moving statistics are averaged once per update())."""
+
+    def log_train_stats(self):
+        """The reference's per-minibatch scalars of update() (ratio, entropy, loss terms, head means, gradients_norm_*; reference
+        rl/agents/ppo.py:209-225 and the objectives of the agent), read from the engines' train-stats ring in ONE copy after the
+        minibatch loops and logged under the reference's keys.  loss_total / loss_value / lr_* are logged by the loops above.
+        Only the rank that writes summaries fetches; the others empty their ring."""
+        fetch = getattr(self.network, 'train_stats', None)
+        if fetch is None:
+            return
+        stats = fetch(fetch=self.is_writer())
+        if stats is None:
+            return
+        if stats['dropped']:
+            print(f"[train stats] ring of {self.train_stats_rows} rows was full: {stats['dropped']} oldest minibatch steps not logged "
+                  f'(raise train_stats_rows)')
+        for kw in train_stats.log_entries(stats['rows'], skip=train_stats.LOGGED_BY_UPDATE):
+            self.log(**kw)
 
     def update_policy(self, gradients):
         return self.apply_policy_gradients(gradients), True

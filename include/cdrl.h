@@ -41,6 +41,7 @@ typedef struct cdrl_config {
     int32_t freeze_trunk;                  /* 0 (default) or 1: frozen trunk, see below; other values fail at create       */
     int32_t optimizer;                     /* CDRL_OPT_* (default CDRL_OPT_ADAM) of all three optimizers; see below         */
     float polyak;                          /* (0, 1], default 1 (off): polyak averaging of the heads; see below            */
+    int32_t train_stats;                   /* 0 (default, off) or N > 0: ring of N update-diagnostics rows; see cdrl_train_stats_layout */
 } cdrl_config;
 
 /* optimizer -- PPOAgent(optimizer=name) (reference rl/utils.py:29-46, rl/agents/ppo.py:105-106, core/carla_agent.py:123-124): one
@@ -193,6 +194,45 @@ int64_t cdrl_learner_tail_offset(const cdrl_learner* l);
 /* Step counters to 0 and the Nadam m_caches to 1 (a fresh optimizer; the slots in the arenas are the caller's to reset). */
 int cdrl_learner_reset_optimizer_steps(cdrl_learner* l, void* stream);
 
+/* ---- update diagnostics (train stats) --------------------------------------------------------
+ * The scalars PPOAgent.update / CARLAgent.update log per minibatch (reference rl/agents/ppo.py:209-225; core/carla_agent.py:382,
+ * 423-426,461,483-484), produced on the device.  A learner created with cdrl_config.train_stats = N > 0 keeps a ring of N rows in
+ * its workspace; every cdrl_learner_policy_apply / _value_apply appends ONE row behind its updates (three small launches; two on
+ * a frozen trunk).  The row index is a device-side counter, so a replayed hipGraph of the apply step writes successive rows, and
+ * nothing is read back per step: the host copies the ring once per update().  With train_stats = 0 nothing is allocated and the
+ * apply steps enqueue exactly the launches they enqueue without the feature.
+ * The buffer is `header` int32 words -- [0] rows written since the last reset, [1] rows overwritten before a reset (the ring is
+ * full: the oldest row goes) -- followed by `rows` rows of `width` float32; row r of the current sequence sits at index
+ * r % rows.  Fields of a row, as offsets in floats (kind, t_head, t_dynamics hold int32 bit patterns):
+ *   kind           0 policy_apply, 1 value_apply
+ *   t_head         step count of the head's optimizer INCLUDING this step; t_dynamics: the trunk's (frozen: unchanged)
+ *   lr             learning rate of the head in force (cdrl_hparams policy_lr / value_lr); lr_dynamics; clip_ratio; entropy_coef
+ *   speed          mean over the B rows of 2 * sigmoid(lin) of the head's speed output (CDRL_BUF_LIN_P column 2A + 1, _V column 2);
+ *   similarity     mean of tanh(lin) of its similarity output (column 2A, _V column 3) -- float64 sums, fixed order
+ *   metrics        the 16 floats of CDRL_BUF_METRICS_P (kind 0) or _V (kind 1) of the pass in front of the apply, verbatim
+ *   norms          n_policy (kind 0) or n_value (kind 1) floats: L2 norm of every trainable tensor's gradient of the head, in
+ *                  parameter-table order; trunk_norms: n_trunk floats, the trunk's (n_trunk = 0 with freeze_trunk = 1, as the
+ *                  reference logs no dynamics norms with update_dynamics=False).  Unused slots of a row are 0.
+ * The norms are those of the gradient arena at the apply: after grad_scale and any all-reduce the caller ran, BEFORE the per-tensor
+ * clip (the reference logs the lists get_*_gradients returned; tf.clip_by_norm runs on a copy).  Squared sums are accumulated in
+ * float64 in two deterministic stages (1024-element chunks, then per tensor; the heads reuse the clip path's chunk sums), then
+ * sqrt in float64 and one rounding to float32.
+ * cdrl_learner_share_hparams also makes `l` append to `owner`'s ring when both have one (same train_stats and freeze_trunk
+ * required), so that the rows of a ragged last minibatch land in order.
+ * cdrl_learner_train_stats_layout: host only, valid after create (rows = 0 and all fields 0 when off).  _buffer: device pointer
+ * and byte size of header + rows of a bound learner (the owner's after share_hparams).  _reset: both counters to 0, enqueued on
+ * `stream` like every other entry point (no host sync). */
+typedef struct cdrl_train_stats_layout {
+    int32_t rows, width, header;
+    int32_t kind, t_head, t_dynamics;
+    int32_t lr, lr_dynamics, clip_ratio, entropy_coef, speed, similarity;
+    int32_t metrics, norms, trunk_norms;
+    int32_t n_policy, n_value, n_trunk;
+} cdrl_train_stats_layout;
+int cdrl_learner_train_stats_layout(const cdrl_learner* l, cdrl_train_stats_layout* out);
+int cdrl_learner_train_stats_buffer(const cdrl_learner* l, void** ptr, int64_t* bytes);
+int cdrl_learner_train_stats_reset(cdrl_learner* l, void* stream);
+
 /* CARLAgent.get_policy_gradients (core/carla_agent.py:351-373): train-mode trunk forward,
  * policy_objective (:394-428), gradients w.r.t. policy and trunk variables.  grad_scale = 1 /
  * world_size for data-parallel averaging. */
@@ -238,7 +278,7 @@ int cdrl_learner_trunk_forward_train(cdrl_learner* l, const float* image, const 
 enum {
     CDRL_BUF_DYNAMICS = 0,   /* (B, dyn)  trunk output                       */
     CDRL_BUF_IMG_FEAT = 1,   /* (T*B, last) tower output, frame = t*B + b    */
-    CDRL_BUF_METRICS_P = 2,  /* 16 floats: total, policy, entropy, speed, sim, ratio, log_prob */
+    CDRL_BUF_METRICS_P = 2,  /* 16 floats: total, policy, entropy, speed, sim, ratio, log_prob (last pass only; per-step history: train stats) */
     CDRL_BUF_METRICS_V = 3,  /* 16 floats: total, value, speed, sim           */
     CDRL_BUF_AUX_P = 4,      /* (B, 4A) alpha, beta, log_prob, entropy        */
     CDRL_BUF_AUX_V = 5,      /* (B, 2) value (base, exp)                      */
