@@ -898,6 +898,10 @@ int64_t cdrl_dwconv_bn_workspace_doubles(int G, int B, int H, int W, int C, int 
     return dwf_stats_part_elems(B, G, H, W, C, stride) + dwf_filter_part_elems(B, G, H, W, C, stride) + (int64_t)G * nbm * 3 * C;
 }
 
+int cdrl_dwconv_bn_plan(int G, int B, int H, int W, int C, int stride, int32_t* out, int n_out) {
+    return dwf_plan(B, G, H, W, C, stride, out, n_out);
+}
+
 int cdrl_dwconv_bn_fwd(const float* x, const float* pre_stats, const float* w, const float* bias, float* y, int G, int B,
                        int H, int W, int C, int stride, const float* gamma, const float* beta, float* moving_mean,
                        float* moving_var, int bessel, float* post_stats, double* workspace, int act_type, void* stream) {

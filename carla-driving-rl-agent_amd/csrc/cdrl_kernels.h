@@ -199,6 +199,10 @@ struct DwfGeom {
     DwsGeom strip;
 };
 DwfGeom dwf_geom(int B, int G, int H, int W, int C, int stride);
+// dwf_fwd / the pixel-mapped dwf_bwd refuse a frame whose LDS tile (lds_fwd / lds_bwd) exceeds this even at the smallest channel chunk
+static constexpr size_t DWF_LDS_LIMIT = 150 * 1024;
+// dwf_geom's plan and the further inputs of the launch ladders as int32 fields (cdrl_dwconv_bn_plan); returns the field count
+int dwf_plan(int B, int G, int H, int W, int C, int stride, int32_t* out, int n_out);
 int64_t dwf_stats_part_elems(int B, int G, int H, int W, int C, int stride);      // doubles: [G][nb][2][C]
 int64_t dwf_filter_part_elems(int B, int G, int H, int W, int C, int stride);     // doubles: [G*nb][10][C]
 // y = dw3x3(pre_stats ? relu6(scale*x+shift) : x) + bias and the per-block (sum y, sum y^2) partials of the

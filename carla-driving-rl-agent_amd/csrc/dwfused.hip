@@ -1296,7 +1296,7 @@ int dwf_fwd(const float* x, const float* pre_stats, const float* w, const float*
         return -1;
     }
     const DwfGeom g = dwf_geom(B, G, H, W, C, stride);
-    if (g.lds_fwd > 150 * 1024) {
+    if (g.lds_fwd > DWF_LDS_LIMIT) {
         set_error("dwf_fwd: frame %dx%d does not fit LDS even at %d channels", H, W, g.cchunk);
         return -1;
     }
@@ -1388,7 +1388,7 @@ int dwf_bwd(const float* x, const float* pre_stats, const float* dout, const flo
         CDRL_DWS2(0, false);
 #undef CDRL_DWS2
     }
-    if (g.lds_bwd > 150 * 1024) {
+    if (g.lds_bwd > DWF_LDS_LIMIT) {
         set_error("dwf_bwd: frame %dx%d does not fit LDS even at %d channels", H, W, g.cchunk);
         return -1;
     }
@@ -1401,6 +1401,32 @@ int dwf_bwd(const float* x, const float* pre_stats, const float* dout, const flo
     if (g.vec_bwd == 2) CDRL_DWF_BWD(2, 2);
     CDRL_DWF_BWD(2, 1);
 #undef CDRL_DWF_BWD
+}
+
+// The plan the two launch ladders above dispatch on, as plain numbers (cdrl_dwconv_bn_plan, field order in include/cdrl.h): read-only,
+// nothing here decides anything -- dwf_geom does, and the ladders' own inputs (strip.ok, strip.sw, strip.R, same_pad_before(W, 2),
+// the LDS limit) are reported as they are read there.
+int dwf_plan(int B, int G, int H, int W, int C, int stride, int32_t* out, int n_out) {
+    if (stride != 1 && stride != 2) {
+        set_error("dwf_plan: stride must be 1 or 2");
+        return -1;
+    }
+    if (G < 1 || B < 1 || H < 1 || W < 1 || C < 1 || (!out && n_out > 0)) {
+        set_error("dwf_plan: bad shape %dx%dx%dx%dx%d or null output", G, B, H, W, C);
+        return -1;
+    }
+    const DwfGeom g = dwf_geom(B, G, H, W, C, stride);
+    const DwsGeom& d = g.strip;
+    const int32_t f[] = {g.vec, g.nch, g.cchunk, g.cy, g.fpb, g.nb, g.vec_bwd, g.fpb_bwd, g.nb_bwd,
+                         d.ok ? stride : 0,
+                         d.ok ? d.sw : 0, d.ok ? d.R : 0, d.ok ? d.F : 0, d.ok ? d.nch : 0, d.ok ? d.cy : 0,
+                         same_pad_before(W, 2),
+                         g.lds_bwd > DWF_LDS_LIMIT,
+                         g.lds_fwd > DWF_LDS_LIMIT,
+                         g.cx, g.cx_bwd, g.cy_bwd, d.ok ? d.cx : 0};
+    const int n = (int)(sizeof(f) / sizeof(f[0]));
+    for (int i = 0; i < n && i < n_out; ++i) out[i] = f[i];
+    return n;
 }
 
 }  // namespace cdrl

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from carla_driving_rl_agent_amd import _lib
+from tests import dw_ref
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -84,13 +85,8 @@ def test_bn_train_bf16_storage(lib, G, Mg, Cc, relu, shuffle):
 @pytest.mark.parametrize('T,B,H,W,Cc,stride,pre', [(4, 8, 6, 8, 116, 1, True), (2, 6, 11, 15, 58, 1, True), (2, 4, 22, 30, 24, 2, False),
                                                     (4, 4, 11, 15, 116, 2, True), (2, 8, 3, 4, 232, 1, True)])
 def test_dwconv_bn_bf16_storage(lib, T, B, H, W, Cc, stride, pre):
-    rng = np.random.default_rng(T * B + H * W + Cc)
-    N, Ho, Wo = T * B, -(-H // stride), -(-W // stride)
-    xb = dev(rng.standard_normal((N, H, W, Cc)) * 1.5 + 0.4, BF)
-    w, b = dev(rng.standard_normal((3, 3, Cc, 1))), dev(rng.standard_normal(Cc))
-    dob = dev(rng.standard_normal((N, Ho, Wo, Cc)), BF)
-    g1, b1 = dev(rng.uniform(0.5, 1.5, Cc)), dev(rng.uniform(1.0, 3.0, Cc))
-    g2, b2 = dev(rng.uniform(0.5, 1.5, Cc)), dev(rng.uniform(-0.5, 0.5, Cc))
+    c = dw_ref.bf16_inputs(np.random.default_rng(T * B + H * W + Cc), T, B, H, W, Cc, stride, DEV)
+    N, Ho, Wo, xb, w, b, dob, g1, b1, g2, b2 = c.N, c.Ho, c.Wo, c.xb, c.w, c.b, c.dob, c.g1, c.b1, c.g2, c.b2
     res = {}
     for at, X, DO, dt in ((0, xb.float(), dob.float(), torch.float32), (1, xb, dob, BF)):
         with storage(lib, at):
@@ -109,12 +105,7 @@ def test_dwconv_bn_bf16_storage(lib, T, B, H, W, Cc, stride, pre):
             _lib.check(lib.cdrl_dwconv_bn_fwd(P(X), P(pre_stats), P(w), P(b), P(y), T, B, H, W, Cc, stride, P(g2), P(b2), P(mm2), P(mv2), 1,
                                               P(post_stats), P(ws), S()))
             res[(at, 'y')], res[(at, 'st')] = y, post_stats.clone()
-    # forward: y = rounded float32 y; the following BatchNorm's statistics are those of the ROUNDED y
-    assert same_bits(res[(1, 'y')], res[(0, 'y')])
-    yr = res[(1, 'y')].double().view(T, -1, Cc)
-    st = res[(1, 'st')].double().view(4, T, Cc)
-    assert torch.allclose(st[0], yr.mean(1), rtol=1e-6, atol=1e-6)
-    assert torch.allclose(st[1], 1.0 / torch.sqrt(yr.var(1, unbiased=False) + 1e-3), rtol=1e-5)
+    dw_ref.check_bf16_forward(res[(0, 'y')], res[(1, 'y')], res[(1, 'st')], T, Cc)
     # backward from a COMMON state (the rounded y and its statistics): activations rounded, everything else identical
     yb2, post = res[(1, 'y')], res[(1, 'st')]
     out = {}
@@ -128,17 +119,7 @@ def test_dwconv_bn_bf16_storage(lib, T, B, H, W, Cc, stride, pre):
             _lib.check(lib.cdrl_dwconv_bn_bwd(P(X), P(pre_stats), P(DO), P(Y), P(post), P(w), T, B, H, W, Cc, stride, P(dx), P(dw), P(db),
                                               P(vecs[0]), P(vecs[1]), P(coefs[0]), P(vecs[2]), P(vecs[3]), P(coefs[1]), P(ws), S()))
             out[at] = (dx, dw, db, vecs, coefs)
-    o0, o1 = out[0], out[1]
-    assert torch.equal(o0[1], o1[1]) and torch.equal(o0[2], o1[2])                  # filter / bias gradients
-    assert torch.equal(o0[3][0], o1[3][0]) and torch.equal(o0[3][1], o1[3][1]) and torch.equal(o0[4][0], o1[4][0])
-    if pre:
-        # dz1 (the masked gradient at the pre-BN's output) is the kernel's activation output; the op wrapper then applies the
-        # pre-BN backward IN PLACE on it (reads the stored dz1): float32 vs bf16 storage differ by that one rounding
-        assert torch.equal(o0[3][2], o1[3][2]) and torch.equal(o0[3][3], o1[3][3])  # BN1 sums come from the unrounded registers
-        e = (o1[0].float() - o0[0]).abs().max().item() / o0[0].abs().max().item()
-        assert e < 2.0 ** -7, e
-    else:
-        assert same_bits(o1[0], o0[0])
+    dw_ref.check_bf16_backward(out[0], out[1], pre)
 
 
 @pytest.mark.parametrize('G,Mg,K,N,pro,epi,bt', [(4, 330, 58, 58, 1, 1, 0), (4, 1000, 116, 116, 1, 1, 0), (2, 515, 24, 58, 0, 1, 0),

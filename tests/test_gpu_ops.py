@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 from carla_driving_rl_agent_amd import _lib
 from oracle import model as OM
+from tests import dw_ref
 from tests.util import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -269,33 +270,9 @@ def test_dwconv_bn_fused(lib, T, B, H, W, Cc, stride, pre):
     against torch autograd of the unfused composition."""
     rng = np.random.default_rng(T * B + H * W + Cc + stride)
     N = T * B
-    x = (rng.standard_normal((T, B, H, W, Cc)) * 1.5 + 0.4).astype(np.float32)
-    w = rng.standard_normal((3, 3, Cc, 1)).astype(np.float32)
-    b = rng.standard_normal(Cc).astype(np.float32)
-    Ho, Wo = -(-H // stride), -(-W // stride)
-
-    def bnp(name):
-        return {f'{name}.gamma': torch.tensor(rng.uniform(0.5, 1.5, Cc), dtype=torch.float64).requires_grad_(True),
-                f'{name}.beta': torch.tensor(rng.uniform(1.0, 3.0, Cc), dtype=torch.float64).requires_grad_(True),
-                f'{name}.moving_mean': torch.tensor(rng.uniform(-0.2, 0.2, Cc), dtype=torch.float64),
-                f'{name}.moving_var': torch.tensor(rng.uniform(0.5, 1.5, Cc), dtype=torch.float64)}
-    p = {'c.w': torch.tensor(w, dtype=torch.float64).requires_grad_(True),
-         'c.b': torch.tensor(b, dtype=torch.float64).requires_grad_(True), **bnp('pre'), **bnp('post')}
-    if pre == 2:
-        # channels the backward must NOT take xhat1 = (a - beta) / gamma for (tiny |gamma|, large |beta| / |gamma|: it re-reads y1 there),
-        # mixed with ordinary ones inside a thread's channel pair
-        with torch.no_grad():
-            p['pre.gamma'][::5] = torch.tensor(rng.choice([-1.0, 1.0], len(p['pre.gamma'][::5])) * 0.01, dtype=torch.float64)
-            p['pre.beta'][::5] = torch.tensor(rng.uniform(0.5, 2.5, len(p['pre.beta'][::5])), dtype=torch.float64)
-            p['pre.gamma'][3::7] = 0.2
-            p['pre.beta'][3::7] = 3.0 + 0.0 * p['pre.beta'][3::7]
-    f32 = {k: v.detach().clone().float() for k, v in p.items()}
-    xt = torch.tensor(x, dtype=torch.float64).permute(0, 1, 4, 2, 3).requires_grad_(True)        # (T,B,C,H,W)
-    a = OM.relu6(OM.bn_slices(xt, p, 'pre', True, True)) if pre else xt
-    y2 = OM.conv_dw(a, p, 'c', stride)
-    out = OM.bn_slices(y2, p, 'post', True, True)
-    dout = rng.standard_normal((T, B, Ho, Wo, Cc)).astype(np.float32)
-    out.backward(torch.tensor(dout, dtype=torch.float64).permute(0, 1, 4, 2, 3))
+    inp = dw_ref.draw(rng, T, B, H, W, Cc, stride, pre)
+    ref = dw_ref.evaluate(inp)
+    x, w, b, dout, f32, p, Ho, Wo = inp.x, inp.w, inp.b, inp.dout, inp.f32, ref.p, inp.Ho, inp.Wo
 
     X, Wd, Bd, DO = dev(x), dev(w), dev(b), dev(dout)
     pre_stats = None
@@ -314,14 +291,12 @@ def test_dwconv_bn_fused(lib, T, B, H, W, Cc, stride, pre):
     mm2, mv2 = dev(f32['post.moving_mean']), dev(f32['post.moving_var'])
     _lib.check(lib.cdrl_dwconv_bn_fwd(P(X), P(pre_stats), P(Wd), P(Bd), P(y), T, B, H, W, Cc, stride, P(g2), P(b2), P(mm2), P(mv2),
                                       1, P(post_stats), P(ws), S()))
-    y2n = y2.detach().permute(0, 1, 3, 4, 2).reshape(N, Ho, Wo, Cc).numpy()
-    assert rel_err(y.cpu().numpy(), y2n) < 1e-5
+    assert rel_err(y.cpu().numpy(), ref.y) < 1e-5
     st = post_stats.cpu().numpy().reshape(4, T, Cc)
-    y2g = y2n.reshape(T, -1, Cc)
-    assert rel_err(st[0], y2g.mean(axis=1)) < 1e-5
-    assert rel_err(st[1], 1.0 / np.sqrt(y2g.var(axis=1) + 1e-3)) < 1e-5
-    assert rel_err(mm2.cpu().numpy(), p['post.moving_mean'].numpy()) < 1e-5
-    assert rel_err(mv2.cpu().numpy(), p['post.moving_var'].numpy()) < 1e-5
+    assert rel_err(st[0], ref.mean) < 1e-5
+    assert rel_err(st[1], ref.rstd) < 1e-5
+    assert rel_err(mm2.cpu().numpy(), ref.moving_mean) < 1e-5
+    assert rel_err(mv2.cpu().numpy(), ref.moving_var) < 1e-5
     # backward
     dx = torch.zeros((N, H, W, Cc), device=DEV)
     dw = torch.zeros((3, 3, Cc, 1), device=DEV)
@@ -330,17 +305,17 @@ def test_dwconv_bn_fused(lib, T, B, H, W, Cc, stride, pre):
     coefs = [torch.zeros(3 * T * Cc, device=DEV) for _ in range(2)]
     _lib.check(lib.cdrl_dwconv_bn_bwd(P(X), P(pre_stats), P(DO), P(y), P(post_stats), P(Wd), T, B, H, W, Cc, stride, P(dx), P(dw),
                                       P(db), P(vecs[0]), P(vecs[1]), P(coefs[0]), P(vecs[2]), P(vecs[3]), P(coefs[1]), P(ws), S()))
-    assert rel_err(dx.cpu().numpy(), xt.grad.permute(0, 1, 3, 4, 2).reshape(N, H, W, Cc).numpy()) < 2e-5
-    assert rel_err(dw.cpu().numpy(), p['c.w'].grad.numpy()) < 2e-5
+    assert rel_err(dx.cpu().numpy(), ref.dx) < 2e-5
+    assert rel_err(dw.cpu().numpy(), ref.dw) < 2e-5
     # the bias feeds a train-mode BN: its true gradient is 0, the computed one is rounding noise of the sums
     assert np.abs(db.cpu().numpy()).max() < 1e-4 * np.abs(dw.cpu().numpy()).max()
-    assert rel_err(vecs[0].cpu().numpy(), p['post.gamma'].grad.numpy()) < 2e-5
-    assert rel_err(vecs[1].cpu().numpy(), p['post.beta'].grad.numpy()) < 2e-5
+    assert rel_err(vecs[0].cpu().numpy(), ref.dgamma_post) < 2e-5
+    assert rel_err(vecs[1].cpu().numpy(), ref.dbeta_post) < 2e-5
     if pre:
-        eg = np.abs(vecs[2].cpu().numpy() - p['pre.gamma'].grad.numpy()) / np.abs(p['pre.gamma'].grad.numpy()).max()
+        eg = np.abs(vecs[2].cpu().numpy() - ref.dgamma_pre) / np.abs(ref.dgamma_pre).max()
         assert eg.max() < 2e-5, (eg.max(), int(eg.argmax()), p['pre.gamma'][int(eg.argmax())].item(), p['pre.beta'][int(eg.argmax())].item())
         # (pre == 2: 2.4e-5 measured on the stride-2 case, with and without the xhat shortcut -- the tiny-gamma channels put 1 / gamma = 100 in front of the float32 dz)
-        assert rel_err(vecs[3].cpu().numpy(), p['pre.beta'].grad.numpy()) < (5e-5 if pre == 2 else 2e-5)
+        assert rel_err(vecs[3].cpu().numpy(), ref.dbeta_pre) < (5e-5 if pre == 2 else 2e-5)
 
 
 @pytest.mark.parametrize('N,H,W', [(3, 44, 59), (2, 19, 27), (2, 20, 28)])
