@@ -82,42 +82,6 @@ struct Passthrough {
     int gap_rows = 0;                                   // P pixels per frame
 };
 
-// BatchNorm work folded into a pointwise conv (gemm_pw.hip); all optional
-struct PwFuse {
-    bool fwd_pw = false;                 // forward through the persistent skinny GEMM
-    const float* pro_stats = nullptr;    // input = BN-apply(in) with these statistics (in = raw previous conv output)
-    bool epi_stats = false;              // forward epilogue: statistics partials of the following BN -> scr_main_.part
-    bool bwd_pw = false;                 // backward-data through the persistent skinny GEMM
-    const float* bwd_ey = nullptr;       // backward epilogue: BN-backward sums of the BN whose raw input is bwd_ey
-    const float* bwd_epi_stats = nullptr;
-    // BatchNorm-backward apply of the BN that follows this conv, done as the operand prologue of the backward-data and
-    // filter-gradient GEMMs (the gradient w.r.t. the conv output is never materialised)
-    bool bb = false;
-    const float* bb_stats = nullptr;     // that BN's statistics / backward coefficients (filled by its own backward op)
-    const float* bb_coef = nullptr;
-    View bb_dz{nullptr, 0, 0};           // gradient w.r.t. the BN output; p == nullptr: the current scratch slot (dense)
-    int bb_shuffle = 0, bb_act = 0;
-    bool bb_claim_slot = false;          // this op claims the rotating scratch slot (nobody upstream did)
-    // fused backward (gemm_pw_bwd.hip): when the conv input is a BatchNorm output applied on load (pro_stats; bwd_ey = its raw
-    // input), that BatchNorm's parameters / gradient outputs / coefficient block -- its backward sums come out of the conv's
-    // reduce kernel, and its own backward op does nothing (`a_bn_done`)
-    bool a_bn = false;                   // the five pointers below are set (they are null in the dry build either way)
-    const float* a_gamma = nullptr;
-    const float* a_beta = nullptr;
-    float* a_dgamma = nullptr;
-    float* a_dbeta = nullptr;
-    float* a_coef = nullptr;
-    std::shared_ptr<bool> a_bn_done;
-    // finalize of the BatchNorm BEHIND the conv on load (gemm_pw_bwd.hip, float32): its backward sums sit in *bb_fin_part
-    // (bb_fin_nb rows per group); dgamma / dbeta come out of the conv's reduce kernel; `bb_fin_done` tells the BatchNorm's backward op
-    bool bb_fin = false;
-    double** bb_fin_part = nullptr;      // &scratch.part
-    int bb_fin_nb = 0;
-    float* bb_dgamma = nullptr;
-    float* bb_dbeta = nullptr;
-    std::shared_ptr<bool> bb_fin_done;
-};
-
 class Learner {
 public:
     const std::string& build_error() const { return build_err_; }
@@ -230,22 +194,94 @@ private:
         float* p = nullptr;
         float* g = nullptr;
     };
+    // reduction scratch of the ops on the main stream / of the auxiliary ops (feature nets + small GRUs) / of the shortcut branch of a
+    // stride-2 unit, which run concurrently on other streams and therefore need their own
+    struct Scratch {
+        double* part = nullptr;
+        double* part2 = nullptr;
+        float* tn = nullptr;
+    };
+    // One BatchNorm of the graph: its parameters and blocks (make_bn).  They exist before any op is emitted, so the conv in front of
+    // it, its own op and the ops behind it all refer to the same record.
     struct BnRec {
-        int G, Mg, C, nb;
+        std::string name;
+        int G = 0, Mg = 0, C = 0, nb = 0;  // nb: partial rows per group of its own reductions
+        View x{nullptr, 0, 0};             // its raw input
+        int act = 0;
+        int at = 0;                        // x is a bf16 tensor (tower BatchNorm of a bf16-storage build)
+        bool batched_inf = false;          // trunk: the inference-mode statistics block comes from the batched launch
+        PRef gamma, beta, mm, mv;
         float* stats = nullptr;            // [4][G][C] of this BatchNorm
         float* coef = nullptr;             // [3][G][C] backward coefficients
-        float* y = nullptr;                // its (dense) input
-        int act = 0;
-        // set by the op that produces this BN's incoming gradient when it also accumulates the BN-backward
-        // sums (sum dz, sum dz*xhat) in its own pass: the BN backward then skips its reduce kernel
-        std::shared_ptr<bool> reduce_fused;
-        // the fused backward of the conv in front (float32) folds this BatchNorm's backward sums itself (finalize on load): the
-        // BatchNorm backward then skips bn_bwd_finalize.  What that kernel needs: the scratch block the sums are left in, their row
-        // count, the gradient slots of gamma / beta.
-        std::shared_ptr<bool> fin_by_consumer;
-        double** part_ptr = nullptr;        // &scratch.part of the stream the BatchNorm runs on (filled at the end of the build)
-        float* dgamma = nullptr;
-        float* dbeta = nullptr;
+        Scratch* scr = nullptr;            // partials of the stream the BatchNorm runs on
+        int bwd_nb = 0;                    // partial rows per group its backward sums are left in (set by whoever plans their producer)
+        explicit operator bool() const { return C > 0; }
+    };
+    // Backward form of a unit 1x1 conv, decided from shapes, views and switches before any op of the unit is emitted (pw_bwd_form):
+    // the BatchNorm ops around the conv are built from the same answer.
+    enum class PwBwd {
+        Plain,      // dy materialised by the BatchNorm behind the conv; backward-data + filter gradient as two GEMMs
+        Prologue,   // BatchNorm-backward apply as operand prologue of those two GEMMs (persistent float32 / bf16 kernel)
+        Wide,       // the same with backward-data on the one-tile-per-workgroup split-precision kernel (stage 2, float32)
+        Fused,      // one kernel for backward-data + filter + bias gradient (gemm_pw_bwd.hip)
+        FusedFin    // ... which also finalizes the BatchNorm behind the conv on load (float32)
+    };
+    static bool pw_fused(PwBwd f) { return f == PwBwd::Fused || f == PwBwd::FusedFin; }
+    PwBwd pw_bwd_form(View in, View din, View dz, int Mg, int Cin, int Cout, bool bn_in) const;
+    // BatchNorm work folded into a pointwise conv (gemm_pw.hip); all optional
+    struct PwFuse {
+        bool fwd_pw = false;                 // forward through the persistent skinny GEMM
+        bool epi_stats = false;              // forward epilogue: statistics partials of the BatchNorm behind the conv -> scratch part
+        bool bwd_pw = false;                 // backward-data through the persistent skinny GEMM
+        // the BatchNorm in front, applied on load (the conv input is its raw input): its backward sums come out of the conv's
+        // backward -- the backward-data epilogue, or the reduce kernel of the fused form, which leaves nothing for its own op
+        BnRec bn_in;
+        // != Plain: BatchNorm-backward apply of the BatchNorm behind the conv as the operand prologue of the backward GEMMs (the
+        // gradient w.r.t. the conv output is never materialised)
+        PwBwd bwd = PwBwd::Plain;
+        View bb_dz{nullptr, 0, 0};           // gradient w.r.t. that BatchNorm's output; ld == 0: the current scratch slot (dense)
+        int bb_shuffle = 0, bb_act = 0;
+        bool bb_claim_slot = false;          // this op claims the rotating scratch slot (nobody upstream did)
+    };
+    // How a BatchNorm's op runs (add_bn)
+    struct BnOp {
+        bool bessel = true;
+        View out{nullptr, 0, 0}, dout{nullptr, 0, 0};
+        int out_shuffle = 0, dout_shuffle = 0;
+        float* dx = nullptr;                 // nullptr: tower mode, the gradient w.r.t. the input goes to the current scratch slot
+        int stats_nb = 0;                    // > 0: the statistics partials were written by the producing op (rows per group)
+        PwBwd conv = PwBwd::Plain;           // backward form of the conv in front: != Plain applies this BatchNorm's backward on load,
+                                             // FusedFin finalizes it too
+        bool sums_by_producer = false;       // the op that produces the incoming gradient accumulates the backward sums in its pass
+        Passthrough pass;
+    };
+    // Fused depthwise block (add_dw_block); the input side comes first, so that a call site spells it as one aggregate
+    struct DwBlock {
+        float* x = nullptr;                  // block input [N*H*W][C]: raw input of `pre`, or the activated tensor without one
+        int H = 0, W = 0, C = 0, stride = 1;
+        View din{nullptr, 0, 0};             // gradient target when there is no pre-BN
+        BnRec pre;                           // BatchNorm (+ReLU6) in front, or none
+        int pre_stats_nb = 0;                // > 0: its statistics partials were written by the producing conv's epilogue
+        PwBwd pre_conv = PwBwd::Plain;       // backward form of the conv in front of `pre` (as BnOp::conv)
+        std::string dw, bn_post;             // parameter prefixes of the depthwise conv and the BatchNorm behind it
+        float* y2 = nullptr;                 // raw depthwise output
+        View out{nullptr, 0, 0}, dout{nullptr, 0, 0};
+        // the conv behind applies the post-BN on load: its output is not materialised, and its backward sums come from that conv --
+        // post_bwd_nb rows per group from the backward-data epilogue, or everything from the fused form's reduce kernel
+        bool post_on_load = false;
+        int post_bwd_nb = 0;
+        PwBwd post_conv = PwBwd::Plain;
+    };
+    // Second half of a unit branch (add_half): `d` carries the input side of its depthwise block (x .. pre_conv)
+    struct Half {
+        std::string unit;
+        const char *dw, *bn_mid, *pw, *bn_out;      // layer names: dw / bn2 / pw2 / bn3 or sc_dw / sc_bn1 / sc_pw / sc_bn2
+        DwBlock d;
+        Tens out;                            // unit output
+        int out_off = 0;                     // channel offset of this half before the shuffle
+        int Cout = 0;
+        bool fused = false, bb = false;      // BatchNorm work folded into the 1x1 conv; BatchNorm-backward apply as its operand prologue
+        Passthrough pass;
     };
 
     // --- building
@@ -262,27 +298,25 @@ private:
     void build_trunk(std::vector<Op>& ops);
     void build_head(std::vector<Op>& ops, int model, const std::string& prefix, Tens& lin, int nheads,
                     const int* head_dims, const char* const* head_names);
-    // dx == nullptr: tower mode, the gradient w.r.t. the BN input goes to the current scratch slot
-    // stats_nb > 0: the statistics partials were already written by the producing op (that many rows per group)
-    BnRec add_bn(std::vector<Op>& ops, int model, const std::string& prefix, View x, int G, int Mg, int C, bool bessel,
-                 int act, View out, int out_shuffle, View dout, int dout_shuffle, float* dx, int stats_nb = 0,
-                 bool defer_apply = false, Passthrough pass = Passthrough());
+    // make_bn registers a BatchNorm's parameters and allocates its blocks; add_bn emits its op.  pw_bn: the BatchNorm behind the 1x1
+    // conv `conv`, whose own parameters are registered first (the parameter tables keep layer order wherever the blocks are created)
+    BnRec make_bn(int model, const std::string& prefix, View x, int G, int Mg, int C, int act);
+    BnRec pw_bn(const std::string& conv, int Cin, int Cout, const std::string& bn, float* y, int Mg, int act);
+    void add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o);
+    // dense BatchNorm between two tensors (feature nets, trunk tail, control branches): no Bessel correction, no activation
+    void add_dense_bn(std::vector<Op>& ops, int model, const std::string& prefix, const Tens& in, const Tens& out, int G);
     void add_pw(std::vector<Op>& ops, const std::string& prefix, View in, int rows, int Cin, int Cout, float* y,
-                View din, int din_acc, BnRec bn_after, PwFuse fuse = PwFuse());
+                View din, int din_acc, const BnRec& bn_out, const PwFuse& fuse);
+    // pre_bn: the op also accumulates the backward sums of that BatchNorm (the layer that produced `in`)
     void add_dw(std::vector<Op>& ops, const std::string& prefix, View in, int N, int H, int W, int C, int stride,
                 float* y, View din, int din_acc, const BnRec* pre_bn = nullptr);
-    // Fused depthwise block (dwfused.hip): [BN `bn_pre` (+ReLU6) of the raw 1x1-conv output x, or none] -> dw3x3 ->
-    // BN `bn_post` (no activation) -> out.  Emits three ops (pre-BN, depthwise, post-BN); the normalised depthwise
-    // input and the post-BN input gradient never touch HBM.  din: gradient target when there is no pre-BN.
-    // pre_stats_nb > 0: the pre-BN statistics partials were already written (by the producing GEMM's epilogue) with
-    // that many partial rows per group; post_apply = false: the post-BN output is not materialised (its consumer
-    // applies it on load); post_bwd_nb > 0: the post-BN backward sums were written by the GEMM that produced dout.
-    // Returns the post-BN statistics block.
-    float* add_dw_block(std::vector<Op>& ops, const std::string& unit, const char* bn_pre, const char* dw, const char* bn_post,
-                        float* x, int H, int W, int C, int stride, float* y2, View out, View dout, View din,
-                        int pre_stats_nb = 0, bool post_apply = true, int post_bwd_nb = 0, float* stats1_ext = nullptr,
-                        float* coef1_ext = nullptr, bool pre_defer_apply = false, float** coef2_out = nullptr,
-                        std::shared_ptr<bool> post_bwd_done = nullptr, std::shared_ptr<bool> pre_fin_done = nullptr);
+    // Fused depthwise block (dwfused.hip): [BN `pre` (+ReLU6) of the raw 1x1-conv output x, or none] -> dw3x3 -> BN `bn_post` (no
+    // activation) -> out.  Emits three ops (pre-BN, depthwise, post-BN); the normalised depthwise input and the post-BN input
+    // gradient never touch HBM.  Returns the post-BN.
+    BnRec add_dw_block(std::vector<Op>& ops, const DwBlock& d);
+    // Depthwise block, then 1x1 conv, then BN + ReLU6 into a shuffled half of the unit output: the second half of a main branch and the
+    // whole shortcut branch of a stride-2 unit (core/architectures.py:126-137)
+    void add_half(std::vector<Op>& ops, const Half& h);
     bool fused_dw_ = true, fused_pw_ = true;
     bool fused_bb_ = true;
     bool fused_bwd_ = true;             // backward-data + filter gradient of the unit convs as one kernel (gemm_pw_bwd.hip)
@@ -342,13 +376,7 @@ private:
     size_t head_part2_ = 0, head_tn_ = 0;
     struct SlotSizes { size_t dy, part2, tn, fpart, qpart, dbpart, fintot; };
     SlotSizes slot_sizes() const;
-    // reduction scratch of the ops on the main stream / of the auxiliary ops (feature nets + small GRUs),
-    // which run concurrently on the side stream and therefore need their own
-    struct Scratch {
-        double* part = nullptr;
-        double* part2 = nullptr;
-        float* tn = nullptr;
-    };
+    void alloc_scratch();               // main / aux / shortcut scratch, the NSLOT rotating slots, the NQ ring
     Scratch scr_main_, scr_aux_, scr_sc_;
     hipEvent_t ev_sc_fork_[3] = {}, ev_sc_done_[3] = {};   // shortcut branch of the stride-2 units on the side stream (forward)
     Scratch* build_scr_ = &scr_main_;

@@ -25,6 +25,8 @@ namespace cdrl {
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int same_out_h(int n, int s) { return (n + s - 1) / s; }
+// path switch: on unless the variable is set to 0
+static inline bool env_on(const char* name) { return !(cdrl_getenv(name) && atoi(cdrl_getenv(name)) == 0); }
 
 Learner::Learner(const Config& cfg) : cfg_(cfg) {
     memset(&hp_host_, 0, sizeof(hp_host_));
@@ -517,7 +519,7 @@ int Learner::pw_bwd_nbpg(int G, int Mg, int N, int K) const {
 }
 
 bool Learner::pw_fwd_x3_wide(int G, int Mg, int N, int K) const {
-    static const bool x3_env = !(cdrl_getenv("CDRL_PW_X3") && atoi(cdrl_getenv("CDRL_PW_X3")) == 0);
+    static const bool x3_env = env_on("CDRL_PW_X3");
     // (measured at M = 12288 and 49152 rows: 16-20 against 26-36 us, ~60 against 80 us; beyond that every 32-row tile would still stream
     //  its own copy of W -- 196 KB per tile and column block -- and the persistent kernel keeps the shape)
     return cfg_.compute == 0 && x3_env && (K > 128 || N > 128) && K <= 256 && N <= 256 && K % 4 == 0 && (int64_t)G * Mg <= 49152;
@@ -571,88 +573,123 @@ Learner::SlotSizes Learner::slot_sizes() const {
 // ------------------------------------------------------------------------------------------
 // op builders
 // ------------------------------------------------------------------------------------------
-Learner::BnRec Learner::add_bn(std::vector<Op>& ops, int model, const std::string& prefix, View x, int G, int Mg, int C,
-                               bool bessel, int act, View out, int out_shuffle, View dout, int dout_shuffle, float* dx,
-                               int stats_nb, bool defer_apply, Passthrough pass) {
-    PRef gamma = param(model, prefix + ".gamma", {C}, true);
-    PRef beta = param(model, prefix + ".beta", {C}, true);
-    PRef mm = param(model, prefix + ".moving_mean", {C}, false);
-    PRef mv = param(model, prefix + ".moving_var", {C}, false);
-    float* stats = alloc((size_t)4 * G * C);
-    float* coef = alloc((size_t)3 * G * C);
-    note_named(prefix + ".stats", stats, (size_t)4 * G * C * sizeof(float));
-    if (x.ld == C && x.coff == 0) note_named(prefix + ".x", x.p, (size_t)G * Mg * C * (model == M_TRUNK && prefix.compare(0, 4, "img.") == 0 ? esz() : 4));
-    const int nb = vcol_geom(Mg, C).nb;
-    note_scratch((size_t)G * std::max(nb, stats_nb) * 2 * C, (size_t)G * nb * C, 0, 0);
-    BnRec rec;
-    rec.G = G;
-    rec.Mg = Mg;
-    rec.C = C;
-    rec.nb = nb;
-    rec.stats = stats;
-    rec.coef = coef;
-    rec.y = (x.ld == C && x.coff == 0) ? x.p : nullptr;
-    rec.act = act;
-    rec.reduce_fused = std::make_shared<bool>(false);
-    rec.fin_by_consumer = std::make_shared<bool>(false);
-    rec.part_ptr = &build_scr_->part;
-    rec.dgamma = gamma.g;
-    rec.dbeta = beta.g;
-    std::shared_ptr<bool> fused = rec.reduce_fused, finc = rec.fin_by_consumer;
-    const int bes = bessel ? 1 : 0;
-    Scratch* sc = build_scr_;
+Learner::BnRec Learner::make_bn(int model, const std::string& prefix, View x, int G, int Mg, int C, int act) {
+    BnRec r;
+    r.name = prefix;
+    r.G = G;
+    r.Mg = Mg;
+    r.C = C;
+    r.nb = r.bwd_nb = vcol_geom(Mg, C).nb;
+    r.x = x;
+    r.act = act;
+    const bool tower = model == M_TRUNK && prefix.compare(0, 4, "img.") == 0;
+    r.at = tower ? at_ : 0;
+    r.gamma = param(model, prefix + ".gamma", {C}, true);
+    r.beta = param(model, prefix + ".beta", {C}, true);
+    r.mm = param(model, prefix + ".moving_mean", {C}, false);
+    r.mv = param(model, prefix + ".moving_var", {C}, false);
+    r.stats = alloc((size_t)4 * G * C);
+    r.coef = alloc((size_t)3 * G * C);
+    r.scr = build_scr_;
+    note_named(prefix + ".stats", r.stats, (size_t)4 * G * C * sizeof(float));
+    if (x.ld == C && x.coff == 0) note_named(prefix + ".x", x.p, (size_t)G * Mg * C * (tower ? esz() : 4));
     // trunk layers: the inference-mode statistics block comes from the batched launch at the start of the forward
-    const bool inf_batched = model == M_TRUNK;
-    if (inf_batched) note_bn_inference(gamma.p, beta.p, mm.p, mv.p, stats, G, C);
+    r.batched_inf = model == M_TRUNK;
+    if (r.batched_inf) note_bn_inference(r.gamma.p, r.beta.p, r.mm.p, r.mv.p, r.stats, G, C);
+    return r;
+}
+
+Learner::BnRec Learner::pw_bn(const std::string& conv, int Cin, int Cout, const std::string& bn, float* y, int Mg, int act) {
+    (void)param(M_TRUNK, conv + ".w", {1, 1, Cin, Cout}, true);
+    (void)param(M_TRUNK, conv + ".b", {Cout}, true);
+    return make_bn(M_TRUNK, bn, make_view(y, Cout), cfg_.T, Mg, Cout, act);
+}
+
+void Learner::add_dense_bn(std::vector<Op>& ops, int model, const std::string& prefix, const Tens& in, const Tens& out, int G) {
+    BnOp o;
+    o.bessel = false;
+    o.out = out.v();
+    o.dout = out.gv();
+    o.dx = in.g;
+    add_bn(ops, make_bn(model, prefix, in.v(), G, in.rows / G, in.C, ACT_NONE), o);
+}
+
+void Learner::add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o) {
+    const int G = bn.G, Mg = bn.Mg, C = bn.C, nb = bn.nb, act = bn.act, at = bn.at, stats_nb = o.stats_nb, bes = o.bessel ? 1 : 0;
+    const View x = bn.x;
+    const Passthrough pass = o.pass;
+    const bool apply_by_conv = o.conv != PwBwd::Plain, fin_by_conv = o.conv == PwBwd::FusedFin;
+    Scratch* sc = bn.scr;
+    note_scratch((size_t)G * std::max(nb, stats_nb) * 2 * C, (size_t)G * nb * C, 0, 0);
     // single-group BatchNorm over a few hundred rows (dense BNs of the trunk tail and the control branches): one launch per
     // direction instead of three
-    const bool small = G == 1 && Mg <= 2048 && !bessel && act == ACT_NONE && !out_shuffle && !dout_shuffle && dx &&
-                       !stats_nb && !defer_apply && !pass.fsrc.p && !pass.gsrc.p && !pass.gap_out;
+    const bool small = G == 1 && Mg <= 2048 && !o.bessel && act == ACT_NONE && !o.out_shuffle && !o.dout_shuffle && o.dx &&
+                       !stats_nb && !apply_by_conv && !pass.fsrc.p && !pass.gsrc.p && !pass.gap_out;
     const bool gap = pass.gap_out != nullptr;
-    const int at = model == M_TRUNK && prefix.compare(0, 4, "img.") == 0 ? at_ : 0;     // tower tensors only
     std::shared_ptr<int> diag_calls3 = std::make_shared<int>(0);
-    if (at && small) build_fail("%s: single-launch BatchNorm has no bf16-storage form", prefix.c_str());
-    if (gap && (pass.gap_rows <= 0 || Mg % pass.gap_rows != 0 || x.ld != C || x.coff != 0 || out_shuffle || dout_shuffle || pass.fsrc.p ||
+    if (at && small) build_fail("%s: single-launch BatchNorm has no bf16-storage form", bn.name.c_str());
+    if (gap && (pass.gap_rows <= 0 || Mg % pass.gap_rows != 0 || x.ld != C || x.coff != 0 || o.out_shuffle || o.dout_shuffle || pass.fsrc.p ||
                 pass.gsrc.p))
-        build_fail("%s: fused global average pool needs a dense input and whole frames per group", prefix.c_str());
+        build_fail("%s: fused global average pool needs a dense input and whole frames per group", bn.name.c_str());
     Op op;
     if (small) {
         op.fwd = [=](hipStream_t st, int training) -> int {
-            if (training) return bn_small_fwd(x, Mg, C, gamma.p, beta.p, mm.p, mv.p, stats, out, st);
-            if (!inf_batched) CDRL_TRY(bn_finalize(sc->part, nb, G, Mg, C, gamma.p, beta.p, mm.p, mv.p, bes, training, stats, st));
-            return bn_apply(x, G, Mg, C, stats, act, out, out_shuffle, st);
+            if (training) return bn_small_fwd(x, Mg, C, bn.gamma.p, bn.beta.p, bn.mm.p, bn.mv.p, bn.stats, o.out, st);
+            if (!bn.batched_inf) CDRL_TRY(bn_finalize(sc->part, nb, G, Mg, C, bn.gamma.p, bn.beta.p, bn.mm.p, bn.mv.p, bes, training, bn.stats, st));
+            return bn_apply(x, G, Mg, C, bn.stats, act, o.out, o.out_shuffle, st);
         };
-        op.bwd = [=](hipStream_t st) -> int { return bn_small_bwd(dout, x, Mg, C, stats, gamma.g, beta.g, coef, dx, st); };
+        op.bwd = [=](hipStream_t st) -> int { return bn_small_bwd(o.dout, x, Mg, C, bn.stats, bn.gamma.g, bn.beta.g, bn.coef, o.dx, st); };
         ops.push_back(op);
-        return rec;
+        return;
     }
     op.fwd = [=](hipStream_t st, int training) -> int {
         if (training && !stats_nb) CDRL_TRY(colstats(x, G, Mg, C, sc->part, st, at));
-        if ((training || !inf_batched) && !((g_diag_skip_fin & 4) && stats_nb && ++*diag_calls3 > 3))
-            CDRL_TRY(bn_finalize(sc->part, stats_nb ? stats_nb : nb, G, Mg, C, gamma.p, beta.p, mm.p, mv.p, bes, training, stats, st));
-        if (gap) return bn_act_gap_fwd(x.p, stats, pass.gap_out, G, Mg / pass.gap_rows, pass.gap_rows, C, act, st, at);
-        if (pass.fsrc.p) return bn_apply(x, G, Mg, C, stats, act, out, out_shuffle, st, &pass.fsrc, &pass.fdst, at);
-        return bn_apply(x, G, Mg, C, stats, act, out, out_shuffle, st, nullptr, nullptr, at);
+        if ((training || !bn.batched_inf) && !((g_diag_skip_fin & 4) && stats_nb && ++*diag_calls3 > 3))
+            CDRL_TRY(bn_finalize(sc->part, stats_nb ? stats_nb : nb, G, Mg, C, bn.gamma.p, bn.beta.p, bn.mm.p, bn.mv.p, bes, training, bn.stats, st));
+        if (gap) return bn_act_gap_fwd(x.p, bn.stats, pass.gap_out, G, Mg / pass.gap_rows, pass.gap_rows, C, act, st, at);
+        if (pass.fsrc.p) return bn_apply(x, G, Mg, C, bn.stats, act, o.out, o.out_shuffle, st, &pass.fsrc, &pass.fdst, at);
+        return bn_apply(x, G, Mg, C, bn.stats, act, o.out, o.out_shuffle, st, nullptr, nullptr, at);
     };
     op.bwd = [=](hipStream_t st) -> int {
         // fused global average pool: the gradient source is the pooled gradient, one row per gap_rows rows of x
-        const View dsrc = gap ? make_view(const_cast<float*>(pass.gap_dout), C) : dout;
-        const int bc = gap ? pass.gap_rows : 0;
-        if (pass.gsrc.p) CDRL_TRY(bn_bwd_reduce(dout, dout_shuffle, x, G, Mg, C, stats, act, sc->part, st, nullptr, &pass.gsrc, &pass.gdst, 0, at));
-        else if (!*fused) CDRL_TRY(bn_bwd_reduce(dsrc, dout_shuffle, x, G, Mg, C, stats, act, sc->part, st, nullptr, nullptr, nullptr, bc, at));
-        if (*finc) return 0;            // sums folded, applied and turned into dgamma / dbeta by the fused conv backward that follows
-        CDRL_TRY(bn_bwd_finalize(sc->part, nb, G, Mg, C, stats, gamma.g, beta.g, coef, st));
-        if (defer_apply) return 0;      // applied by the consumer GEMMs on load (PwFuse::bb)
-        if (dx) return bn_bwd_apply(dsrc, dout_shuffle, x, G, Mg, C, stats, coef, act, dx, sc->part2, st, nullptr, bc, at);
+        const View dsrc = gap ? make_view(const_cast<float*>(pass.gap_dout), C) : o.dout;
+        const int bc = gap ? pass.gap_rows : 0, dsh = o.dout_shuffle;
+        if (pass.gsrc.p) CDRL_TRY(bn_bwd_reduce(o.dout, dsh, x, G, Mg, C, bn.stats, act, sc->part, st, nullptr, &pass.gsrc, &pass.gdst, 0, at));
+        else if (!o.sums_by_producer) CDRL_TRY(bn_bwd_reduce(dsrc, dsh, x, G, Mg, C, bn.stats, act, sc->part, st, nullptr, nullptr, nullptr, bc, at));
+        if (fin_by_conv) return 0;      // sums folded, applied and turned into dgamma / dbeta by the fused conv backward that follows
+        CDRL_TRY(bn_bwd_finalize(sc->part, nb, G, Mg, C, bn.stats, bn.gamma.g, bn.beta.g, bn.coef, st));
+        if (apply_by_conv) return 0;    // applied by the backward GEMMs of the conv in front on load
+        if (o.dx) return bn_bwd_apply(dsrc, dsh, x, G, Mg, C, bn.stats, bn.coef, act, o.dx, sc->part2, st, nullptr, bc, at);
         CDRL_TRY(next_slot(st));       // tower: dy + db partials go to a rotating scratch slot
-        return bn_bwd_apply(dsrc, dout_shuffle, x, G, Mg, C, stats, coef, act, dys_[slot_], part2s_[slot_], st, nullptr, bc, at);
+        return bn_bwd_apply(dsrc, dsh, x, G, Mg, C, bn.stats, bn.coef, act, dys_[slot_], part2s_[slot_], st, nullptr, bc, at);
     };
     ops.push_back(op);
-    return rec;
+}
+
+// Backward form of a unit conv whose BatchNorm-backward apply rides on its operand loads (in / din: conv input and its gradient, dz: the
+// gradient w.r.t. the output of the BatchNorm behind the conv, bn_in: the input is a BatchNorm output applied on load)
+Learner::PwBwd Learner::pw_bwd_form(View in, View din, View dz, int Mg, int Cin, int Cout, bool bn_in) const {
+    const int G = cfg_.T;
+    const bool bfc = cfg_.compute >= 1;
+    // One kernel for backward-data + filter gradient + bias gradient (+ the backward sums of the BatchNorm in front of the conv):
+    // float32 engine and bf16 activation storage (not the operand-only mode), both channel counts padded alike (gemm_pw_bwd.hip)
+    // 24 input channels -- the first unit, the last conv of the backward -- pad to 64: 158 us against 104 us for the backward-data kernel of
+    // the two-kernel form, which is why rounds 4 kept it there; but that form's filter gradient (163 us on the side stream) then bounds the
+    // tail of the pass and slows the BatchNorm reduction beside it (117 us instead of 29): fused 14.00 vs 14.06 ms per update-step, and one
+    // pass over (dz, y) = 0.3 GB per pass less.
+    static constexpr int fbwd_min_cin = 24;
+    if (fused_bwd_ && (!bfc || at_) && G <= 8 && Cin >= fbwd_min_cin && pw_bwd_fused_supported(dz, in, din, Cout, Cin, at_) &&
+        (!bn_in || (in.ld == Cin && in.coff == 0)))
+        // float32: the finalize of the BatchNorm behind the conv inside the fused kernel (no bn_bwd_finalize launch in front of it)
+        return (!at_ && fin_on_load_) ? PwBwd::FusedFin : PwBwd::Fused;
+    // 232-channel convs (stage 2), float32: backward-data with the BatchNorm-backward prologue on the one-tile-per-workgroup
+    // split-precision kernel (round 6; the filter gradient stays on the side stream)
+    if (!bfc && !at_ && pw_bwd_x3_wide(G, Mg, Cin, Cout)) return PwBwd::Wide;
+    return PwBwd::Prologue;
 }
 
 void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, int rows, int Cin, int Cout, float* y,
-                     View din, int din_acc, BnRec bn_after, PwFuse fuse) {
+                     View din, int din_acc, const BnRec& bn_out, const PwFuse& fuse) {
     PRef w = param(M_TRUNK, prefix + ".w", {1, 1, Cin, Cout}, true);
     PRef b = param(M_TRUNK, prefix + ".b", {Cout}, true);
     const int G = cfg_.T, Mg = rows / G;
@@ -663,87 +700,80 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
     // single-plane form, the filter gradients through tn_direct's BF variant
     const bool bfc = cfg_.compute >= 1;
     const int at = at_;
+    const bool anorm = (bool)fuse.bn_in, bb = fuse.bwd != PwBwd::Plain, fbwd = pw_fused(fuse.bwd), wbw = fuse.bwd == PwBwd::Wide;
+    const bool fin = fuse.bwd == PwBwd::FusedFin;
+    const float *pro_stats = fuse.bn_in.stats, *bwd_ey = fuse.bn_in.x.p;      // (null without a BatchNorm in front)
     // forward on the bf16 matrix pipe (exact three-way operand split, gemm_pw_x3.hip) where the shape allows it
-    static const bool x3_env = !(cdrl_getenv("CDRL_PW_X3") && atoi(cdrl_getenv("CDRL_PW_X3")) == 0);
+    static const bool x3_env = env_on("CDRL_PW_X3");
     const bool x3_shape = (Cin <= 128 && Cout <= 128) || pw_fwd_x3_wide(G, Mg, Cout, Cin);
-    const void* w3f = (!bfc && x3_env && fuse.fwd_pw && x3_shape && pw_x3_supported(in, Cout, Cin)) ? pw_x3_packed(w.p, Cin, Cout, Cout, 1) : nullptr;
-    if (fuse.fwd_pw && pw_fwd_x3_wide(G, Mg, Cout, Cin) && !w3f && !dry_)
+    // (dry build: `in.p` is null, which counts as aligned -- as every tens_a tensor is, dense and 256-byte aligned)
+    const bool x3f = !bfc && x3_env && fuse.fwd_pw && x3_shape && pw_x3_supported(in, Cout, Cin);
+    const void* w3f = x3f ? pw_x3_packed(w.p, Cin, Cout, Cout, 1) : nullptr;
+    if (fuse.fwd_pw && pw_fwd_x3_wide(G, Mg, Cout, Cin) && !x3f)
         build_fail("%s: the wide split-precision forward needs 16-byte aligned input rows (ld %d, offset %d)", prefix.c_str(), in.ld, in.coff);
     const int nb_fwd = pw_fwd_nbpg(G, Mg, Cout, Cin);
     // plain (unfused) wide convs -- the 464 -> 768 head conv, the 232-wide shortcut conv -- on the bf16 matrix pipe too (gemm_x3.hip)
     const bool wide = Cin >= 128 || Cout > 128;
     const bool g3 = bfc || (x3_env && wide);
     const bool use_g3f = g3 && !fuse.fwd_pw && gemm_x3_supported(in, Cin);
-    const bool use_g3b = g3 && !fuse.bwd_pw && !fuse.bb && Cout % 4 == 0;
+    const bool use_g3b = g3 && !fuse.bwd_pw && !bb && Cout % 4 == 0;
     const void* g3f = use_g3f ? gemm_x3_packed(w.p, Cin, Cout, Cout, 1) : nullptr;
     const void* g3b = (use_g3b && !frozen()) ? gemm_x3_packed(w.p, Cout, Cin, 1, Cout) : nullptr;       // (frozen: no backward)
-    if (bfc && ((!fuse.fwd_pw && !use_g3f) || (!fuse.bwd_pw && !fuse.bb && !use_g3b) || (fuse.bb && !fuse.bwd_pw)))
+    if (bfc && ((!fuse.fwd_pw && !use_g3f) || (!fuse.bwd_pw && !bb && !use_g3b) || (bb && !fuse.bwd_pw)))
         build_fail("bf16-operand mode: 1x1 convolution %s (%d -> %d, fwd %d bwd %d bb %d; input ld %d coff %d) has no bf16 kernel",
-                   prefix.c_str(), Cin, Cout, (int)fuse.fwd_pw, (int)fuse.bwd_pw, (int)fuse.bb, in.ld, in.coff);
-    const float* wpf = (fuse.fwd_pw && !w3f) ? pw_packed(w.p, Cin, Cout, Cout, 1, bfc) : nullptr;      // forward: B(k = cin, n = cout)
-    const float* wpb = (fuse.bwd_pw && !frozen()) ? pw_packed(w.p, Cout, Cin, 1, Cout, bfc) : nullptr;      // backward-data: W^T
-    const int tn_groups = (fuse.pro_stats || fuse.bb) ? G : 1;
+                   prefix.c_str(), Cin, Cout, (int)fuse.fwd_pw, (int)fuse.bwd_pw, (int)bb, in.ld, in.coff);
+    const float* wpf = (fuse.fwd_pw && !x3f) ? pw_packed(w.p, Cin, Cout, Cout, 1, bfc) : nullptr;      // forward: B(k = cin, n = cout)
+    // backward operands: W^T in float32-MFMA fragment order for the persistent kernel, as three bf16 planes for the fused and the wide
+    // form (a frozen trunk has no backward and packs nothing)
+    const float* wpb = (fuse.bwd_pw && !fbwd && !wbw && !frozen()) ? pw_packed(w.p, Cout, Cin, 1, Cout, bfc) : nullptr;
+    const void* wpx = ((fbwd || wbw) && !frozen()) ? pw_x3_packed(w.p, Cout, Cin, 1, Cout) : nullptr;      // B(k = cout, n = cin)
+    const int tn_groups = (anorm || bb) ? G : 1;
     note_scratch(0, 0, (size_t)rows * Cout, (size_t)gemm_tn_part_elems(rows, Cout, Cin, tn_groups));
     if (fuse.epi_stats) note_scratch((size_t)G * nb_fwd * 2 * Cout, 0, 0, 0);
-    if (fuse.bwd_ey) note_scratch((size_t)G * pw_bwd_nbpg(G, Mg, Cin, Cout) * 2 * Cin, 0, 0, 0);
+    if (anorm && !fbwd) note_scratch((size_t)G * pw_bwd_nbpg(G, Mg, Cin, Cout) * 2 * Cin, 0, 0, 0);     // backward-data epilogue: its sums
     Op op;
     op.fwd = [=](hipStream_t st, int) -> int {
-        if (w3f)
-            return pw_x3(in, fuse.pro_stats, w3f, b.p, make_view(y, Cout), G, Mg, Cout, Cin, fuse.epi_stats ? sc->part : nullptr, st,
+        if (x3f)
+            return pw_x3(in, pro_stats, w3f, b.p, make_view(y, Cout), G, Mg, Cout, Cin, fuse.epi_stats ? sc->part : nullptr, st,
                          nb_fwd);
         if (fuse.fwd_pw)
-            return pw_nn(in, fuse.pro_stats, w.p, Cout, 1, b.p, make_view(y, Cout), 0, G, Mg, Cout, Cin, fuse.epi_stats ? 1 : 0,
+            return pw_nn(in, pro_stats, w.p, Cout, 1, b.p, make_view(y, Cout), 0, G, Mg, Cout, Cin, fuse.epi_stats ? 1 : 0,
                          nullptr, nullptr, sc->part, st, nullptr, wpf, bfc, at);
         if (g3f) return gemm_x3(in, g3f, b.p, make_view(y, Cout), rows, Cout, Cin, 0, st, bfc, at);
         return gemm_nn(in, w.p, Cout, 1, b.p, make_view(y, Cout), rows, Cout, Cin, 0, st);
     };
-    const int nbp_bwd = fuse.bb ? pw_bwd_nbpg(G, Mg, Cin, Cout) : 0;
-    if (fuse.bb) note_scratch(0, (size_t)G * nbp_bwd * Cout, 0, 0);
-    // One kernel for backward-data + filter gradient + bias gradient (+ the backward sums of the BatchNorm in front of the conv):
-    // float32 engine and bf16 activation storage (not the operand-only mode), both channel counts padded alike (gemm_pw_bwd.hip)
-    const View dz_probe = fuse.bb_dz.p ? fuse.bb_dz : make_view(reinterpret_cast<float*>(uintptr_t(16)), Cout);
-    const bool anorm = fuse.pro_stats != nullptr;
-    // 24 input channels -- the first unit, the last conv of the backward -- pad to 64: 158 us against 104 us for the backward-data kernel of
-    // the two-kernel form, which is why rounds 4 kept it there; but that form's filter gradient (163 us on the side stream) then bounds the
-    // tail of the pass and slows the BatchNorm reduction beside it (117 us instead of 29): fused 14.00 vs 14.06 ms per update-step, and one
-    // pass over (dz, y) = 0.3 GB per pass less.
-    static constexpr int fbwd_min_cin = 24;
-    const bool fbwd = fused_bwd_ && fuse.bb && fuse.bwd_pw && (!bfc || at) && G <= 8 && Cin >= fbwd_min_cin && pw_bwd_fused_supported(dz_probe, in, din, Cout, Cin, at) &&
-                      (!anorm || (fuse.bwd_ey == in.p && fuse.bwd_epi_stats == fuse.pro_stats && fuse.a_bn && in.ld == Cin && in.coff == 0)) &&
-                      (anorm || !fuse.bwd_ey);
-    // 232-channel convs (stage 2), float32: backward-data with the BatchNorm-backward prologue on the one-tile-per-workgroup
-    // split-precision kernel (round 6; the filter gradient stays on the side stream)
-    const bool wbw = !bfc && !at && fuse.bb && fuse.bwd_pw && !fbwd && pw_bwd_x3_wide(G, Mg, Cin, Cout);
-    if (wbw && !pw_x3_wide_bwd_supported(dz_probe, din, Cin, Cout, fuse.bb_shuffle))
+    const int nbp_bwd = bb ? pw_bwd_nbpg(G, Mg, Cin, Cout) : 0;
+    if (bb) note_scratch(0, (size_t)G * nbp_bwd * Cout, 0, 0);
+    const View dz_view = fuse.bb_dz.ld ? fuse.bb_dz : make_view(nullptr, Cout);
+    if (wbw && !pw_x3_wide_bwd_supported(dz_view, din, Cin, Cout, fuse.bb_shuffle))
         build_fail("%s: the wide split-precision backward needs even / 16-byte aligned gradient rows (ld %d, offset %d, shuffle %d)", prefix.c_str(),
-                   dz_probe.ld, dz_probe.coff, fuse.bb_shuffle);
-    const void* wpx = ((fbwd || wbw) && !frozen()) ? pw_x3_packed(w.p, Cout, Cin, 1, Cout) : nullptr;      // W^T planes: B(k = cout, n = cin)
+                   dz_view.ld, dz_view.coff, fuse.bb_shuffle);
     if (fbwd) {
         max_qpart_ = std::max(max_qpart_, (size_t)pw_bwd_fused_qpart_elems(G, Mg, Cout, Cin, at));
         max_dbpart_ = std::max(max_dbpart_, (size_t)pw_bwd_fused_dbpart_elems(G, Mg, Cout, Cin, at));
-        if (fuse.a_bn_done) *fuse.a_bn_done = true;
     }
-    // float32: the finalize of the BatchNorm behind the conv inside the fused kernel (no bn_bwd_finalize launch in front of it)
-    const bool fin = fbwd && !at && fin_on_load_ && fuse.bb_fin;
-    if (fin && fuse.bb_fin_done) *fuse.bb_fin_done = true;
-    if (fin && !dry_ && (!fuse.bb_fin_part || fuse.bb_fin_nb <= 0)) build_fail("%s: finalize on load without the BatchNorm's scratch block", prefix.c_str());
+    if (fin && bn_out.bwd_nb <= 0) build_fail("%s: finalize on load without the BatchNorm's scratch block", prefix.c_str());
+    const float *o_stats = bn_out.stats, *o_coef = bn_out.coef;
+    float *o_dgamma = bn_out.gamma.g, *o_dbeta = bn_out.beta.g;
+    Scratch* o_scr = bn_out.scr;
+    const int o_rows = bn_out.G * bn_out.nb, o_bwd_nb = bn_out.bwd_nb;
     op.bwd = [=](hipStream_t st) -> int {
         if (fbwd) {
             if (fuse.bb_claim_slot) CDRL_TRY(next_slot(st));
             PwBwdFused f;
-            f.dz = fuse.bb_dz.p ? fuse.bb_dz : make_view(dys_[slot_], Cout);
+            f.dz = fuse.bb_dz.ld ? fuse.bb_dz : make_view(dys_[slot_], Cout);
             f.dz_shuffle = fuse.bb_shuffle;
             f.act = fuse.bb_act;
             f.y = y;
-            f.stats = fuse.bb_stats;
-            f.coef = fuse.bb_coef;
+            f.stats = o_stats;
+            f.coef = o_coef;
             f.a = in;
-            f.a_stats = anorm ? fuse.pro_stats : nullptr;
-            f.a_gamma = fuse.a_gamma;
-            f.a_beta = fuse.a_beta;
-            f.a_dgamma = fuse.a_dgamma;
-            f.a_dbeta = fuse.a_dbeta;
-            f.a_coef = fuse.a_coef;
+            f.a_stats = pro_stats;
+            f.a_gamma = fuse.bn_in.gamma.p;
+            f.a_beta = fuse.bn_in.beta.p;
+            f.a_dgamma = fuse.bn_in.gamma.g;
+            f.a_dbeta = fuse.bn_in.beta.g;
+            f.a_coef = fuse.bn_in.coef;
             f.W = w.p;
             f.Wp = wpx;
             f.da = din;
@@ -755,11 +785,11 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
             f.qpart = qparts_[qi];
             f.dbpart = dbparts_[qi];
             if (fin) {
-                f.fin_part = *fuse.bb_fin_part;
-                f.fin_nb = fuse.bb_fin_nb;
+                f.fin_part = o_scr->part;
+                f.fin_nb = o_bwd_nb;
                 f.fin_tot = fintots_[qi];
-                f.o_dgamma = fuse.bb_dgamma;
-                f.o_dbeta = fuse.bb_dbeta;
+                f.o_dgamma = o_dgamma;
+                f.o_dbeta = o_dbeta;
             }
             f.G = G;
             f.Mg = Mg;
@@ -781,21 +811,20 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
             }));
             return flush_side(st);
         }
-        if (fuse.bb) {
+        if (bb) {
             // BN-backward apply fused into the operand loads: dz (+ raw y, statistics, coefficients) instead of dy
             if (fuse.bb_claim_slot) CDRL_TRY(next_slot(st));
-            const View dz = fuse.bb_dz.p ? fuse.bb_dz : make_view(dys_[slot_], Cout);
+            const View dz = fuse.bb_dz.ld ? fuse.bb_dz : make_view(dys_[slot_], Cout);
             hipStream_t side = fork_side(st);
-            TnBnBwd tb{y, fuse.bb_stats, fuse.bb_coef, fuse.bb_shuffle, fuse.bb_act};
-            CDRL_TRY(gemm_tn(in, dz, w.g, rows, Cout, Cin, tns_[slot_], 0, side, G, fuse.pro_stats, &tb, bfc, at));
+            TnBnBwd tb{y, o_stats, o_coef, fuse.bb_shuffle, fuse.bb_act};
+            CDRL_TRY(gemm_tn(in, dz, w.g, rows, Cout, Cin, tns_[slot_], 0, side, G, pro_stats, &tb, bfc, at));
             CDRL_TRY(done_side(side));
-            PwBnBwd pb{y, fuse.bb_stats, fuse.bb_coef, fuse.bb_shuffle, fuse.bb_act, part2s_[slot_]};
+            PwBnBwd pb{y, o_stats, o_coef, fuse.bb_shuffle, fuse.bb_act, part2s_[slot_]};
             if (wbw)
-                CDRL_TRY(pw_x3_wide_bwd(dz, pb, wpx, din, din_acc, G, Mg, Cin, Cout, fuse.bwd_ey, fuse.bwd_epi_stats,
-                                        fuse.bwd_ey ? sc->part : nullptr, st));
+                CDRL_TRY(pw_x3_wide_bwd(dz, pb, wpx, din, din_acc, G, Mg, Cin, Cout, bwd_ey, pro_stats, anorm ? sc->part : nullptr, st));
             else
-                CDRL_TRY(pw_nn(dz, nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout, fuse.bwd_ey ? 2 : 0, fuse.bwd_ey,
-                               fuse.bwd_epi_stats, sc->part, st, &pb, wpb, bfc, at));
+                CDRL_TRY(pw_nn(dz, nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout, anorm ? 2 : 0, bwd_ey, pro_stats, sc->part,
+                               st, &pb, wpb, bfc, at));
             // bias gradient = column sums of the (virtual) dy, reduced from the GEMM's partials: rides on the next fork
             double* p2 = part2s_[slot_];
             return defer_side(st, [=](hipStream_t sd) -> int { return reduce_partials(p2, G * nbp_bwd, Cout, Cout, b.g, 0, sd); });
@@ -803,14 +832,14 @@ void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, i
         float* dy = dys_[slot_];
         // side stream: bias gradient (column sums of dy, reduced per block by bn_bwd_apply) + filter gradient
         hipStream_t side = fork_side(st);
-        CDRL_TRY(reduce_partials(part2s_[slot_], bn_after.G * bn_after.nb, Cout, Cout, b.g, 0, side));
-        CDRL_TRY(gemm_tn(in, make_view(dy, Cout), w.g, rows, Cout, Cin, tns_[slot_], 0, side, tn_groups, fuse.pro_stats, nullptr, bfc, at));
+        CDRL_TRY(reduce_partials(part2s_[slot_], o_rows, Cout, Cout, b.g, 0, side));
+        CDRL_TRY(gemm_tn(in, make_view(dy, Cout), w.g, rows, Cout, Cin, tns_[slot_], 0, side, tn_groups, pro_stats, nullptr, bfc, at));
         CDRL_TRY(done_side(side));
         // main stream: the critical path to the previous layer
         if (din.p) {
             if (fuse.bwd_pw)
                 return pw_nn(make_view(dy, Cout), nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout,
-                             fuse.bwd_ey ? 2 : 0, fuse.bwd_ey, fuse.bwd_epi_stats, sc->part, st, nullptr, wpb, bfc, at);
+                             anorm ? 2 : 0, bwd_ey, pro_stats, sc->part, st, nullptr, wpb, bfc, at);
             if (g3b) return gemm_x3(make_view(dy, Cout), g3b, nullptr, din, rows, Cin, Cout, din_acc, st, bfc, at);
             CDRL_TRY(gemm_nn(make_view(dy, Cout), w.p, 1, Cout, nullptr, din, rows, Cin, Cout, din_acc, st));
         }
@@ -825,12 +854,11 @@ void Learner::add_dw(std::vector<Op>& ops, const std::string& prefix, View in, i
     PRef b = param(M_TRUNK, prefix + ".b", {C}, true);
     const int Ho = same_out_h(H, stride), Wo = same_out_h(W, stride);
     note_scratch(0, 0, (size_t)N * Ho * Wo * C, 0, (size_t)dw_bwd_part_elems(N, H, W, C, stride));
-    const bool fuse = pre_bn && pre_bn->y && din_acc == 0 && pre_bn->C == C && pre_bn->Mg * pre_bn->G == N * H * W;
-    BnRec pre;
-    if (fuse) {
-        pre = *pre_bn;
-        *pre.reduce_fused = true;
-    }
+    const bool fuse = pre_bn != nullptr;
+    if (fuse && (din_acc != 0 || pre_bn->C != C || pre_bn->Mg * pre_bn->G != N * H * W || pre_bn->x.ld != C || pre_bn->x.coff != 0))
+        build_fail("%s: the BatchNorm in front does not cover the depthwise input", prefix.c_str());
+    const int pre_G = fuse ? pre_bn->G : 0, pre_act = fuse ? pre_bn->act : 0;
+    const float *pre_y = fuse ? pre_bn->x.p : nullptr, *pre_stats = fuse ? pre_bn->stats : nullptr;
     if (at_) build_fail("%s: the unfused depthwise path has no bf16-storage form (CDRL_FUSED_DW=0 is set)", prefix.c_str());
     Op op;
     op.fwd = [=](hipStream_t st, int) -> int { return dw_fwd(in, w.p, b.p, y, N, H, W, C, stride, st); };
@@ -840,48 +868,28 @@ void Learner::add_dw(std::vector<Op>& ops, const std::string& prefix, View in, i
         CDRL_TRY(dw_bwd_filter(in, dy, w.g, b.g, N, H, W, C, stride, fparts_[slot_], side));
         CDRL_TRY(done_side(side));
         if (fuse)      // bwd-data + BN-backward sums of the layer that produced `in` in one pass over da
-            return dw_bwd_data_bnreduce(dy, w.p, din, N, H, W, C, stride, pre.G, pre.y, pre.stats, pre.act, scr_main_.part, st);
+            return dw_bwd_data_bnreduce(dy, w.p, din, N, H, W, C, stride, pre_G, pre_y, pre_stats, pre_act, scr_main_.part, st);
         return dw_bwd_data(dy, w.p, din, N, H, W, C, stride, din_acc, st);
     };
     ops.push_back(op);
 }
 
-float* Learner::add_dw_block(std::vector<Op>& ops, const std::string& unit, const char* bn_pre, const char* dw,
-                             const char* bn_post, float* x, int H, int W, int C, int stride, float* y2, View out, View dout,
-                             View din, int pre_stats_nb, bool post_apply, int post_bwd_nb, float* stats1_ext, float* coef1_ext,
-                             bool pre_defer_apply, float** coef2_out, std::shared_ptr<bool> post_bwd_done,
-                             std::shared_ptr<bool> pre_fin_done) {
+Learner::BnRec Learner::add_dw_block(std::vector<Op>& ops, const DwBlock& d) {
     const int B = cfg_.B, G = cfg_.T, N = B * G;
+    const int H = d.H, W = d.W, C = d.C, stride = d.stride;
     const int Ho = same_out_h(H, stride), Wo = same_out_h(W, stride);
     const int Mi = B * H * W, Mo = B * Ho * Wo;
-    const bool pre = bn_pre != nullptr;
+    const bool pre = (bool)d.pre;
     Scratch* sc = build_scr_;           // the shortcut branch of a stride-2 unit has its own partial buffers (it runs on the side stream)
-    PRef g1, b1, mm1, mv1;
-    float *stats1 = nullptr, *coef1 = nullptr;
-    if (pre) {
-        const std::string n1 = unit + "." + bn_pre;
-        g1 = param(M_TRUNK, n1 + ".gamma", {C}, true);
-        b1 = param(M_TRUNK, n1 + ".beta", {C}, true);
-        mm1 = param(M_TRUNK, n1 + ".moving_mean", {C}, false);
-        mv1 = param(M_TRUNK, n1 + ".moving_var", {C}, false);
-        stats1 = stats1_ext ? stats1_ext : alloc((size_t)4 * G * C);
-        note_bn_inference(g1.p, b1.p, mm1.p, mv1.p, stats1, G, C);
-        coef1 = coef1_ext ? coef1_ext : alloc((size_t)3 * G * C);
-        note_named(n1 + ".stats", stats1, (size_t)4 * G * C * sizeof(float));
-        note_named(n1 + ".x", x, (size_t)N * H * W * C * esz());
-    }
-    PRef w = param(M_TRUNK, unit + "." + dw + ".w", {3, 3, C, 1}, true);
-    PRef b = param(M_TRUNK, unit + "." + dw + ".b", {C}, true);
-    const std::string n2 = unit + "." + bn_post;
-    PRef g2 = param(M_TRUNK, n2 + ".gamma", {C}, true);
-    PRef b2 = param(M_TRUNK, n2 + ".beta", {C}, true);
-    PRef mm2 = param(M_TRUNK, n2 + ".moving_mean", {C}, false);
-    PRef mv2 = param(M_TRUNK, n2 + ".moving_var", {C}, false);
-    float* stats2 = alloc((size_t)4 * G * C);
-    note_bn_inference(g2.p, b2.p, mm2.p, mv2.p, stats2, G, C);
-    float* coef2 = alloc((size_t)3 * G * C);
-    if (coef2_out) *coef2_out = coef2;
-    const int nb_in = vcol_geom(Mi, C).nb, nb_out = vcol_geom(Mo, C).nb;
+    float *x = d.x, *y2 = d.y2;
+    PRef w = param(M_TRUNK, d.dw + ".w", {3, 3, C, 1}, true);
+    PRef b = param(M_TRUNK, d.dw + ".b", {C}, true);
+    const BnRec post = make_bn(M_TRUNK, d.bn_post, make_view(y2, C), G, Mo, C, ACT_NONE);
+    const View out = d.out, dout = d.dout, din = d.din;
+    const int pre_stats_nb = d.pre_stats_nb, post_bwd_nb = d.post_bwd_nb;
+    const bool pre_apply_by_conv = d.pre_conv != PwBwd::Plain, pre_fin_by_conv = d.pre_conv == PwBwd::FusedFin;
+    const bool post_on_load = d.post_on_load, post_bwd_by_conv = pw_fused(d.post_conv);
+    const int nb_in = vcol_geom(Mi, C).nb, nb_out = post.nb;
     const int nbf = dwf_geom(B, G, H, W, C, stride).nb;              // partial rows of the forward kernel (BN2 statistics) ...
     const int nbb = dwf_geom(B, G, H, W, C, stride).nb_bwd;          // ... and of the backward (BN1 sums, filter partials)
     const size_t nbmax = (size_t)std::max(std::max(std::max(nb_in, nb_out), std::max(nbf, nbb)), std::max(pre_stats_nb, post_bwd_nb));
@@ -897,16 +905,15 @@ float* Learner::add_dw_block(std::vector<Op>& ops, const std::string& unit, cons
             if (!training) return 0;                            // inference: statistics block from the batched launch
             if (!pre_stats_nb) CDRL_TRY(colstats(xv, G, Mi, C, sc->part, st, at));
             if ((g_diag_skip_fin & 1) && ++*diag_calls > 6) return 0;      // timing diagnostic: stale statistics of an earlier step
-            return bn_finalize(sc->part, pre_stats_nb ? pre_stats_nb : nb_in, G, Mi, C, g1.p, b1.p, mm1.p, mv1.p, 1, training,
-                               stats1, st);
+            return bn_finalize(sc->part, pre_stats_nb ? pre_stats_nb : nb_in, G, Mi, C, d.pre.gamma.p, d.pre.beta.p, d.pre.mm.p, d.pre.mv.p, 1, training, d.pre.stats, st);
         };
         op.bwd = [=](hipStream_t st) -> int {
-            if (pre_fin_done && *pre_fin_done) return 0;   // folded by the fused backward of the 1x1 conv in front (finalize on load)
-            CDRL_TRY(bn_bwd_finalize(sc->part, nbb, G, Mi, C, stats1, g1.g, b1.g, coef1, st));
-            if (pre_defer_apply) return 0;                 // the 1x1 conv in front applies it on load (PwFuse::bb)
+            if (pre_fin_by_conv) return 0;                 // folded by the fused backward of the 1x1 conv in front (finalize on load)
+            CDRL_TRY(bn_bwd_finalize(sc->part, nbb, G, Mi, C, d.pre.stats, d.pre.gamma.g, d.pre.beta.g, d.pre.coef, st));
+            if (pre_apply_by_conv) return 0;               // the 1x1 conv in front applies it on load
             const float* dz = dys_[slot_];                 // masked gradient left there by the depthwise op
             CDRL_TRY(next_slot(st));
-            return bn_bwd_apply(make_view(const_cast<float*>(dz), C), 0, xv, G, Mi, C, stats1, coef1, ACT_NONE, dys_[slot_],
+            return bn_bwd_apply(make_view(const_cast<float*>(dz), C), 0, xv, G, Mi, C, d.pre.stats, d.pre.coef, ACT_NONE, dys_[slot_],
                                 part2s_[slot_], st, nullptr, 0, at);
         };
         ops.push_back(op);
@@ -914,13 +921,13 @@ float* Learner::add_dw_block(std::vector<Op>& ops, const std::string& unit, cons
     {
         Op op;
         op.fwd = [=](hipStream_t st, int) -> int {
-            return dwf_fwd(x, stats1, w.p, b.p, y2, sc->part, G, B, H, W, C, stride, st, at);
+            return dwf_fwd(x, d.pre.stats, w.p, b.p, y2, sc->part, G, B, H, W, C, stride, st, at);
         };
         op.bwd = [=](hipStream_t st) -> int {
             CDRL_TRY(next_slot(st));
             double* pw = fparts_[slot_];
             const View dx = pre ? make_view(dys_[slot_], C) : din;
-            CDRL_TRY(dwf_bwd(x, stats1, dout.p, y2, stats2, coef2, w.p, dx, sc->part, pw, G, B, H, W, C, stride, st, at));
+            CDRL_TRY(dwf_bwd(x, d.pre.stats, dout.p, y2, post.stats, post.coef, w.p, dx, sc->part, pw, G, B, H, W, C, stride, st, at));
             return defer_side(st, [=](hipStream_t sd) -> int {
                 return reduce_partials2(pw, G * nbb, 9 * C, C, (int64_t)10 * C, w.g, b.g, 0, sd);
             });
@@ -931,18 +938,85 @@ float* Learner::add_dw_block(std::vector<Op>& ops, const std::string& unit, cons
         Op op;
         op.fwd = [=](hipStream_t st, int training) -> int {
             if (training && !((g_diag_skip_fin & 2) && ++*diag_calls > 6))
-                CDRL_TRY(bn_finalize(sc->part, nbf, G, Mo, C, g2.p, b2.p, mm2.p, mv2.p, 1, training, stats2, st));
-            if (!post_apply) return 0;
-            return bn_apply(y2v, G, Mo, C, stats2, ACT_NONE, out, 0, st, nullptr, nullptr, at);
+                CDRL_TRY(bn_finalize(sc->part, nbf, G, Mo, C, post.gamma.p, post.beta.p, post.mm.p, post.mv.p, 1, training, post.stats, st));
+            if (post_on_load) return 0;
+            return bn_apply(y2v, G, Mo, C, post.stats, ACT_NONE, out, 0, st, nullptr, nullptr, at);
         };
         op.bwd = [=](hipStream_t st) -> int {
-            if (post_bwd_done && *post_bwd_done) return 0;      // dgamma, dbeta, coefficients came out of the consumer conv's reduce kernel
-            if (!post_bwd_nb) CDRL_TRY(bn_bwd_reduce(dout, 0, y2v, G, Mo, C, stats2, ACT_NONE, sc->part, st, nullptr, nullptr, nullptr, 0, at));
-            return bn_bwd_finalize(sc->part, post_bwd_nb ? post_bwd_nb : nb_out, G, Mo, C, stats2, g2.g, b2.g, coef2, st);
+            if (post_bwd_by_conv) return 0;     // dgamma, dbeta, coefficients come out of the consumer conv's reduce kernel
+            if (!post_bwd_nb) CDRL_TRY(bn_bwd_reduce(dout, 0, y2v, G, Mo, C, post.stats, ACT_NONE, sc->part, st, nullptr, nullptr, nullptr, 0, at));
+            return bn_bwd_finalize(sc->part, post_bwd_nb ? post_bwd_nb : nb_out, G, Mo, C, post.stats, post.gamma.g, post.beta.g, post.coef, st);
         };
         ops.push_back(op);
     }
-    return stats2;
+    return post;
+}
+
+void Learner::add_half(std::vector<Op>& ops, const Half& h) {
+    const int B = cfg_.B, T = cfg_.T, N = B * T;
+    DwBlock d = h.d;
+    const int Ho = same_out_h(d.H, d.stride), Wo = same_out_h(d.W, d.stride);
+    const int rows_in = N * d.H * d.W, rows_out = N * Ho * Wo, Mg_out = B * Ho * Wo;
+    const int Cm = d.C, Co = h.Cout, Ct = h.out.C;
+    const std::string dw = h.unit + "." + h.dw, bn_mid = h.unit + "." + h.bn_mid, pw = h.unit + "." + h.pw, bn_out = h.unit + "." + h.bn_out;
+    Tens y2 = tens_a(rows_out, Cm, false), a2 = tens_a(rows_out, Cm), y3 = tens_a(rows_out, Co, false);
+    BnOp o3;
+    o3.out = h.out.v(h.out_off);
+    o3.dout = h.out.gv(h.out_off);
+    o3.out_shuffle = o3.dout_shuffle = Ct;
+    o3.pass = h.pass;
+    d.dw = dw;
+    d.bn_post = bn_mid;
+    d.y2 = y2.p;
+    d.out = a2.v();
+    d.dout = a2.gv();
+    if (h.fused) {
+        // BN-apply of the middle BatchNorm on the conv's operand load (its output is never written), statistics of the last one in
+        // the conv's epilogue; backward: the BatchNorm-backward of the last one as the conv's operand prologue (gathered through the
+        // shuffle map), the middle one's backward sums out of the conv backward -- the fused form's reduce kernel, else the
+        // backward-data epilogue
+        PwFuse f;
+        f.fwd_pw = f.epi_stats = f.bwd_pw = true;
+        if (h.bb) {
+            f.bwd = pw_bwd_form(y2.v(), a2.gv(), o3.dout, Mg_out, Cm, Co, true);
+            f.bb_dz = o3.dout;
+            f.bb_shuffle = Ct;
+            f.bb_act = ACT_RELU6;
+            f.bb_claim_slot = true;
+        }
+        d.post_on_load = true;
+        d.post_bwd_nb = pw_bwd_nbpg(T, Mg_out, Cm, Co);
+        d.post_conv = f.bwd;
+        f.bn_in = add_dw_block(ops, d);
+        const BnRec last = pw_bn(pw, Cm, Co, bn_out, y3.p, Mg_out, ACT_RELU6);
+        add_pw(ops, pw, y2.v(), rows_out, Cm, Co, y3.p, a2.gv(), 0, last, f);
+        o3.stats_nb = pw_fwd_nbpg(T, Mg_out, Co, Cm);
+        o3.conv = f.bwd;
+        add_bn(ops, last, o3);
+        return;
+    }
+    if (fused_dw_) {
+        add_dw_block(ops, d);
+    } else {
+        if (d.pre) {
+            Tens a1 = tens_a(rows_in, Cm);
+            BnOp o1;
+            o1.out = a1.v();
+            o1.dout = a1.gv();
+            o1.sums_by_producer = true;     // the depthwise backward-data kernel leaves them
+            add_bn(ops, d.pre, o1);
+            add_dw(ops, dw, a1.v(), N, d.H, d.W, Cm, d.stride, y2.p, a1.gv(), 0, &d.pre);
+        } else {
+            add_dw(ops, dw, make_view(d.x, Cm), N, d.H, d.W, Cm, d.stride, y2.p, d.din, 0);
+        }
+        BnOp o2;
+        o2.out = a2.v();
+        o2.dout = a2.gv();
+        add_bn(ops, make_bn(M_TRUNK, bn_mid, y2.v(), T, Mg_out, Cm, ACT_NONE), o2);
+    }
+    const BnRec last = pw_bn(pw, Cm, Co, bn_out, y3.p, Mg_out, ACT_RELU6);
+    add_pw(ops, pw, a2.v(), rows_out, Cm, Co, y3.p, a2.gv(), 0, last, PwFuse());
+    add_bn(ops, last, o3);
 }
 
 void Learner::add_dense(std::vector<Op>& ops, int model, const std::string& prefix, View in, int M, int K, int N,
@@ -1118,30 +1192,19 @@ void Learner::build_trunk(std::vector<Op>& ops) {
     const Config& c = cfg_;
     const int B = c.B, T = c.T, N = B * T;
     const int Hs = (c.H - 3) / 2 + 1, Ws = (c.W - 3) / 2 + 1;
-    auto bnrec = [](int G, int Mg, int C) {
-        BnRec r;
-        r.G = G;
-        r.Mg = Mg;
-        r.C = C;
-        r.nb = vcol_geom(Mg, C).nb;
-        return r;
-    };
     aux_ops_.clear();
     add_aux_fork(ops);
     {
-        const char* e = cdrl_getenv("CDRL_FUSED_DW");        // 0 -> unfused bn-apply / depthwise / stats kernels
-        fused_dw_ = !(e && atoi(e) == 0);
-        const char* e2 = cdrl_getenv("CDRL_FUSED_PW");       // 0 -> generic tiled GEMM + separate BN passes around the 1x1 convs
-        fused_pw_ = !(e2 && atoi(e2) == 0);
+        fused_dw_ = env_on("CDRL_FUSED_DW");        // 0 -> unfused bn-apply / depthwise / stats kernels
+        fused_pw_ = env_on("CDRL_FUSED_PW");        // 0 -> generic tiled GEMM + separate BN passes around the 1x1 convs
         // BN-backward apply as GEMM operand prologue, for both 1x1 convs of a unit (bn1; bn3, gathered through the shuffle map) and the
         // shortcut conv of the stride-2 units; 0 -> separate apply passes with a materialised dy
-        const char* e3 = cdrl_getenv("CDRL_FUSED_BB");
         // measured at v19 (bit mask: 1 = bn1, 2 = bn3): 1 -> 25.5, 0 -> 25.8, 3 -> 26.0, 2 -> 26.2 ms/update-step; re-measured at v29
         // (buffer-load filter gradient: the shuffle gather costs nothing there any more): 3 -> 20.66, 1 -> 20.80, 0 -> 21.0, 2 -> 21.3, and
         // with the wide fused pointwise path 3 -> 20.21.  The first unit's conv with 24 input channels takes it too -- slower before the
         // accumulate variant prefetched its old output tile (248 us against 165 us for apply + plain GEMM), now 15.91 vs 15.96
         // ms/update-step and one 164 MB tensor less
-        fused_bb_ = !(e3 && atoi(e3) == 0);
+        fused_bb_ = env_on("CDRL_FUSED_BB");
         // (round 4's LDS-resident 64-row panel form of the 232-channel forward convs, gemm_pw_wide.hip, is gone: 18 vs 26 us per launch
         //  isolated but 14.43 vs 14.48 ms per update-step, and -- like any change of a float32 forward -- it re-drew the ReLU6 decisions
         //  and moved smoke()'s worst tensor from 6.9e-5 to 9.5e-5 of the 1e-4 gate, both times it was measured: DESIGN.md section 3)
@@ -1151,10 +1214,9 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         // of them from L2 -- and kept it opt-in; with 64 rows from the strip-form depthwise backward and 128 from the BatchNorm reductions
         // (NB_STATS) it is worth 0.16 ms per update-step (14.15 vs 14.31 ms, same box) and is the default.  CDRL_FIN_ON_LOAD=0 -> stand-alone
         // finalize launches.
-        const char* e6 = cdrl_getenv("CDRL_FIN_ON_LOAD");
-        fin_on_load_ = !(e6 && atoi(e6) == 0);
+        fin_on_load_ = env_on("CDRL_FIN_ON_LOAD");
         const char* e4 = cdrl_getenv("CDRL_FUSED_BWD");     // 0 -> backward-data (critical stream) + filter gradient (side stream) as two kernels
-        fused_bwd_ = !(e4 && atoi(e4) == 0);
+        fused_bwd_ = env_on("CDRL_FUSED_BWD");
         // bf16 storage: its two-kernel form is cheap already (one plane, half the bytes); fused-on vs fused-off measured
         // 12.41 vs 12.20 ms per update-step at B = 256, 18.67 vs 18.74 at B = 512, 31.38 vs 32.62 at B = 1024 -> from B = 512
         if (at_ && !(e4 && atoi(e4) == 1) && B < 512) fused_bwd_ = false;
@@ -1170,7 +1232,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         Op op;
         const int H = c.H, W = c.W, Cs = c.stem;
         // forward: BN statistics in the conv's epilogue (training only; inference uses the moving statistics)
-        const bool stem_fstats = stem_fwd_stats_supported(Cs) && !(cdrl_getenv("CDRL_FUSED_STEM") && atoi(cdrl_getenv("CDRL_FUSED_STEM")) == 0);
+        const bool stem_fstats = stem_fwd_stats_supported(Cs) && env_on("CDRL_FUSED_STEM");
         const int nb_stem = stem_fstats ? stem_fwd_stats_nb(B, T, H, W, Cs) : 0;
         if (at && !stem_fstats) build_fail("bf16 activation storage needs the fused stem forward (stem channels %d, CDRL_FUSED_STEM)", Cs);
         op.fwd = [=](hipStream_t st, int training) -> int {
@@ -1178,7 +1240,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
             if (stem_fstats && (training || at)) return stem_fwd_stats(in_image_, w.p, b.p, y.p, scr_main_.part, B, T, H, W, Cs, st, at);
             return stem_fwd(in_image_, w.p, b.p, y.p, B, T, H, W, Cs, st);
         };
-        const bool stem_fused = stem_bwd_fused_supported(Cs) && !(cdrl_getenv("CDRL_FUSED_STEM") && atoi(cdrl_getenv("CDRL_FUSED_STEM")) == 0);
+        const bool stem_fused = stem_bwd_fused_supported(Cs) && env_on("CDRL_FUSED_STEM");
         // blocks of the stem BatchNorm (allocated here: the stem conv's backward consumes them in the fused form)
         float* stem_stats = alloc((size_t)4 * T * Cs);
         float* stem_coef = alloc((size_t)3 * T * Cs);
@@ -1261,7 +1323,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                 const int mid = C / 2, main_out = C - sc_c;
                 const int Ho = stride == 2 ? same_out_h(curH, 2) : curH, Wo = stride == 2 ? same_out_h(curW, 2) : curW;
                 const int rows_in = N * curH * curW, rows_out = N * Ho * Wo;
-                const int Mg_in = B * curH * curW, Mg_out = B * Ho * Wo;
+                const int Mg_in = B * curH * curW;
                 const std::string pre = "img.s" + std::to_string(s) + ".u" + std::to_string(u);
                 Tens out = tens_a(rows_out, C);
                 note_named(pre + ".out", out.p, (size_t)rows_out * C * esz());        // unit output / its gradient (per-unit parity tests)
@@ -1283,7 +1345,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                     ops.push_back(fk);
                 }
                 Passthrough pass;
-                static const bool fuse_pass = !(cdrl_getenv("CDRL_FUSED_PASS") && atoi(cdrl_getenv("CDRL_FUSED_PASS")) == 0);
+                static const bool fuse_pass = env_on("CDRL_FUSED_PASS");
                 if (stride == 1 && fuse_pass && sc_c == C - sc_c) {
                     // identity half: carried by the unit's last BatchNorm op (same channel count as the main half)
                     pass.fsrc = X.v(0);
@@ -1301,180 +1363,50 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                     ops.push_back(cp);
                 }
                 Tens y1 = tens_a(rows_in, mid, false);
-                Tens y2 = tens_a(rows_out, mid, false), a2 = tens_a(rows_out, mid);
-                Tens y3 = tens_a(rows_out, main_out, false);
+                const View xin = X.v(main_off), xg = X.gv(main_off);
                 // BatchNorm work folded into the 1x1-conv GEMMs, every stage
                 // (the K, N = 232 variants of stage 2 run at one workgroup per CU -- 116 W-fragment VGPRs per wave; slower than the
                 //  tiled GEMM + separate BN passes at v19 (+0.15 ms), faster at v29 (-0.24 ms/update-step))
-                const bool fpw = fused_dw_ && fused_pw_ && pw_nn_supported(X.v(main_off), mid, main_in) &&
-                                 pw_nn_supported(y2.v(), main_out, mid) && pw_nn_supported(y3.v(), mid, main_out) &&
-                                 pw_nn_supported(y1.v(), main_in, mid);
+                // (the views of y2 / y3 are probed as null pointers: every tens_a tensor is dense and 256-byte aligned, like them)
+                const bool fpw = fused_dw_ && fused_pw_ && pw_nn_supported(xin, mid, main_in) && pw_nn_supported(make_view(nullptr, mid), main_out, mid) &&
+                                 pw_nn_supported(make_view(nullptr, main_out), mid, main_out) && pw_nn_supported(y1.v(), main_in, mid);
+                // BN-backward apply as GEMM operand prologue (needs the filter-gradient GEMM's fixed column mapping)
+                // (also for N <= 32 outputs of the backward-data GEMM, i.e. the first unit's 24 input channels; see CDRL_FUSED_BB above)
+                // (also for the wide stage-2 units: without the prologues there 19.55 vs 18.82 ms/update-step;
+                //  CU-masking the side stream re-measured at v33: 224 / 192 / 128 CUs -> 21.2 / 21.2 / 23.5 vs 18.7 ms)
+                const bool bb1 = fpw && fused_bb_ && gemm_tn_dpro_supported(mid);
+                const bool bb3 = fpw && fused_bb_ && gemm_tn_dpro_supported(main_out);
+                // order: blocks of bn1, backward form of pw1, then the ops (pw1; bn1, dw, bn2, pw2, bn3 from add_half)
+                BnRec bn1 = pw_bn(pre + ".pw1", main_in, mid, pre + ".bn1", y1.p, Mg_in, ACT_RELU6);
+                PwFuse f1;
                 if (fpw) {
-                    // BN-backward apply as GEMM operand prologue (needs the filter-gradient GEMM's fixed column mapping)
-                    // (also for N <= 32 outputs of the backward-data GEMM, i.e. the first unit's 24 input channels; see CDRL_FUSED_BB above)
-                    // (also for the wide stage-2 units: without the prologues there 19.55 vs 18.82 ms/update-step;
-                    //  CU-masking the side stream re-measured at v33: 224 / 192 / 128 CUs -> 21.2 / 21.2 / 23.5 vs 18.7 ms)
-                    const bool bb1 = fused_bb_ && gemm_tn_dpro_supported(mid);
-                    const bool bb3 = fused_bb_ && gemm_tn_dpro_supported(main_out);
-                    float* stats1 = alloc((size_t)4 * T * mid);
-                    float* coef1 = alloc((size_t)3 * T * mid);
-                    PwFuse f1;
-                    f1.fwd_pw = true;
-                    f1.epi_stats = true;
-                    f1.bwd_pw = true;
-                    if (bb1) {
-                        f1.bb = true;
-                        f1.bb_stats = stats1;
-                        f1.bb_coef = coef1;          // dz = masked gradient in the current scratch slot (written by the dw op)
-                    }
-                    std::shared_ptr<bool> bn1_fin = std::make_shared<bool>(false);
-                    if (bb1 && fused_dw_) {     // BN1's backward sums come out of the depthwise backward: sc->part, dwf_geom rows
-                        // (parameter order = the reference's variable order: pw1's own parameters are registered first, as add_pw would)
-                        (void)param(M_TRUNK, pre + ".pw1.w", {1, 1, main_in, mid}, true);
-                        (void)param(M_TRUNK, pre + ".pw1.b", {mid}, true);
-                        PRef g1 = param(M_TRUNK, pre + ".bn1.gamma", {mid}, true), b1 = param(M_TRUNK, pre + ".bn1.beta", {mid}, true);
-                        f1.bb_fin = true;
-                        f1.bb_fin_part = &build_scr_->part;
-                        f1.bb_fin_nb = dwf_geom(B, T, curH, curW, mid, stride).nb_bwd;
-                        f1.bb_dgamma = g1.g;
-                        f1.bb_dbeta = b1.g;
-                        f1.bb_fin_done = bn1_fin;
-                    }
-                    add_pw(ops, pre + ".pw1", X.v(main_off), rows_in, main_in, mid, y1.p, X.gv(main_off), stride == 2 ? 1 : 0,
-                           bnrec(T, Mg_in, mid), f1);
-                    const int nb1 = pw_fwd_nbpg(T, Mg_in, mid, main_in);
-                    const int nbb = pw_bwd_nbpg(T, Mg_out, mid, main_out);        // pw2 backward-data epilogue rows
-                    float* coef2 = nullptr;
-                    std::shared_ptr<bool> bn2_done = std::make_shared<bool>(false);
-                    float* stats2 = add_dw_block(ops, pre, "bn1", "dw", "bn2", y1.p, curH, curW, mid, stride, y2.p, a2.v(), a2.gv(),
-                                                 View{nullptr, 0, 0}, nb1, false, nbb, stats1, coef1, bb1, &coef2, bn2_done, bn1_fin);
-                    // BN3's statistics / coefficient blocks are allocated by add_bn below; bump-allocate them here first so
-                    // that pw2 (which precedes bn3 in the op list) can reference them
-                    PwFuse f2;
-                    f2.fwd_pw = true;
-                    f2.pro_stats = stats2;
-                    f2.epi_stats = true;
-                    f2.bwd_pw = true;
-                    f2.bwd_ey = y2.p;
-                    f2.bwd_epi_stats = stats2;
-                    {   // BN2's blocks for the fused backward of pw2 (same arena slots as add_dw_block's lookups)
-                        PRef g2 = param(M_TRUNK, pre + ".bn2.gamma", {mid}, true), b2 = param(M_TRUNK, pre + ".bn2.beta", {mid}, true);
-                        f2.a_gamma = g2.p;
-                        f2.a_beta = b2.p;
-                        f2.a_dgamma = g2.g;
-                        f2.a_dbeta = b2.g;
-                        f2.a_coef = coef2;
-                        f2.a_bn = true;
-                    }
-                    const size_t pw2_at = ops.size();
-                    add_pw(ops, pre + ".pw2", y2.v(), rows_out, mid, main_out, y3.p, a2.gv(), 0, bnrec(T, Mg_out, main_out), f2);
-                    BnRec r3 = add_bn(ops, M_TRUNK, pre + ".bn3", y3.v(), T, Mg_out, main_out, true, ACT_RELU6, out.v(sc_c), C,
-                                      out.gv(sc_c), C, nullptr, pw_fwd_nbpg(T, Mg_out, main_out, mid), bb3, pass);
-                    if (bb3) {      // rebuild pw2 with the BN3 blocks known (same parameters -> same arena slots)
-                        f2.bb = true;
-                        f2.bb_stats = r3.stats;
-                        f2.bb_coef = r3.coef;
-                        f2.bb_dz = out.gv(sc_c);
-                        f2.bb_shuffle = C;
-                        f2.bb_act = ACT_RELU6;
-                        f2.bb_claim_slot = true;
-                        f2.a_bn_done = bn2_done;
-                        f2.bb_fin = true;               // BN3's sums: bn_bwd_reduce(_shuf) into *r3.part_ptr, r3.nb rows per group
-                        f2.bb_fin_part = r3.part_ptr;
-                        f2.bb_fin_nb = r3.nb;
-                        f2.bb_dgamma = r3.dgamma;
-                        f2.bb_dbeta = r3.dbeta;
-                        f2.bb_fin_done = r3.fin_by_consumer;
-                        std::vector<Op> tmp;
-                        add_pw(tmp, pre + ".pw2", y2.v(), rows_out, mid, main_out, y3.p, a2.gv(), 0, bnrec(T, Mg_out, main_out), f2);
-                        ops[pw2_at] = tmp[0];
-                    }
-                } else {
-                    add_pw(ops, pre + ".pw1", X.v(main_off), rows_in, main_in, mid, y1.p, X.gv(main_off), stride == 2 ? 1 : 0,
-                           bnrec(T, Mg_in, mid));
-                    if (fused_dw_) {
-                        add_dw_block(ops, pre, "bn1", "dw", "bn2", y1.p, curH, curW, mid, stride, y2.p, a2.v(), a2.gv(),
-                                     View{nullptr, 0, 0});
-                    } else {
-                        Tens a1 = tens_a(rows_in, mid);
-                        BnRec r1 = add_bn(ops, M_TRUNK, pre + ".bn1", y1.v(), T, Mg_in, mid, true, ACT_RELU6, a1.v(), 0, a1.gv(), 0,
-                                          nullptr);
-                        add_dw(ops, pre + ".dw", a1.v(), N, curH, curW, mid, stride, y2.p, a1.gv(), 0, &r1);
-                        add_bn(ops, M_TRUNK, pre + ".bn2", y2.v(), T, Mg_out, mid, true, ACT_NONE, a2.v(), 0, a2.gv(), 0, nullptr);
-                    }
-                    add_pw(ops, pre + ".pw2", a2.v(), rows_out, mid, main_out, y3.p, a2.gv(), 0, bnrec(T, Mg_out, main_out));
-                    add_bn(ops, M_TRUNK, pre + ".bn3", y3.v(), T, Mg_out, main_out, true, ACT_RELU6, out.v(sc_c), C, out.gv(sc_c), C,
-                           nullptr, 0, false, pass);
+                    f1.fwd_pw = f1.epi_stats = f1.bwd_pw = true;
+                    // dz = the masked gradient the depthwise op leaves in the current scratch slot; BN1's backward sums come out of the
+                    // depthwise backward too
+                    if (bb1) f1.bwd = pw_bwd_form(xin, xg, make_view(nullptr, mid), Mg_in, main_in, mid, false);
+                    bn1.bwd_nb = dwf_geom(B, T, curH, curW, mid, stride).nb_bwd;
                 }
+                add_pw(ops, pre + ".pw1", xin, rows_in, main_in, mid, y1.p, xg, stride == 2 ? 1 : 0, bn1, f1);
+                Half mh{pre, "dw", "bn2", "pw2", "bn3", DwBlock{y1.p, curH, curW, mid, stride}, out, sc_c};
+                mh.d.pre = bn1;
+                mh.d.pre_stats_nb = fpw ? pw_fwd_nbpg(T, Mg_in, mid, main_in) : 0;
+                mh.d.pre_conv = f1.bwd;
+                mh.Cout = main_out;
+                mh.fused = fpw;
+                mh.bb = bb3;
+                mh.pass = pass;
+                add_half(ops, mh);
                 if (stride == 2) {
+                    // Round 6: the shortcut branch dw3x3/s2 -> BN -> 1x1 -> BN+ReLU6 (core/architectures.py:133-137) is the second half of a
+                    // main branch and runs on the same fused ops (fused conv backward: stages 0 / 1; the BatchNorm-sum epilogue of the
+                    // wide kernel: stage 2).  Before: 3 more launches per stride-2 unit on the critical stream of every backward (apply
+                    // of sc_bn2, reduce + finalize of sc_bn1) and two on the forward's side stream.
                     const size_t sc_begin = ops.size();
                     if (sc_overlap) build_scr_ = &scr_sc_;
-                    Tens ys1 = tens_a(rows_out, sc_c, false), b1 = tens_a(rows_out, sc_c);
-                    // Round 6: the shortcut branch dw3x3/s2 -> BN -> 1x1 -> BN+ReLU6 (core/architectures.py:133-137) is the second half of a
-                    // main branch and runs on the same fused ops: BN-apply of sc_bn1 on the conv's operand load (its output is never
-                    // written), statistics of sc_bn2 in the conv's epilogue, and in the backward the BatchNorm-backward of sc_bn2 as the
-                    // conv's operand prologue, sc_bn1's backward sums out of the conv backward (fused conv backward: stages 0 / 1; the
-                    // BatchNorm-sum epilogue of the wide kernel: stage 2).  Before: 3 more launches per stride-2 unit on the critical
-                    // stream of every backward (apply of sc_bn2, reduce + finalize of sc_bn1) and two on the forward's side stream.
-                    const bool sc_fpw = fused_dw_ && fused_pw_ && fused_bb_ && gemm_tn_dpro_supported(sc_c) && pw_nn_supported(ys1.v(), sc_c, sc_c);
-                    if (sc_fpw) {
-                        const int nbb_sc = pw_bwd_nbpg(T, Mg_out, sc_c, sc_c);      // conv backward-data epilogue rows (BatchNorm sums of sc_bn1)
-                        float* coef_s1 = nullptr;
-                        std::shared_ptr<bool> s1_done = std::make_shared<bool>(false);
-                        float* stats_s1 = add_dw_block(ops, pre, nullptr, "sc_dw", "sc_bn1", X.p, curH, curW, sc_c, 2, ys1.p, b1.v(), b1.gv(),
-                                                       X.gv(0), 0, false, nbb_sc, nullptr, nullptr, false, &coef_s1, s1_done, nullptr);
-                        Tens ys2 = tens_a(rows_out, sc_c, false);
-                        PwFuse fs;
-                        fs.fwd_pw = true;
-                        fs.pro_stats = stats_s1;
-                        fs.epi_stats = true;
-                        fs.bwd_pw = true;
-                        fs.bwd_ey = ys1.p;
-                        fs.bwd_epi_stats = stats_s1;
-                        {
-                            PRef g1 = param(M_TRUNK, pre + ".sc_bn1.gamma", {sc_c}, true), bt1 = param(M_TRUNK, pre + ".sc_bn1.beta", {sc_c}, true);
-                            fs.a_gamma = g1.p;
-                            fs.a_beta = bt1.p;
-                            fs.a_dgamma = g1.g;
-                            fs.a_dbeta = bt1.g;
-                            fs.a_coef = coef_s1;
-                            fs.a_bn = true;
-                        }
-                        const size_t scpw_at = ops.size();
-                        add_pw(ops, pre + ".sc_pw", ys1.v(), rows_out, sc_c, sc_c, ys2.p, b1.gv(), 0, bnrec(T, Mg_out, sc_c), fs);
-                        BnRec rs = add_bn(ops, M_TRUNK, pre + ".sc_bn2", ys2.v(), T, Mg_out, sc_c, true, ACT_RELU6, out.v(0), C, out.gv(0), C,
-                                          nullptr, pw_fwd_nbpg(T, Mg_out, sc_c, sc_c), true);
-                        fs.bb = true;
-                        fs.bb_stats = rs.stats;
-                        fs.bb_coef = rs.coef;
-                        fs.bb_dz = out.gv(0);
-                        fs.bb_shuffle = C;
-                        fs.bb_act = ACT_RELU6;
-                        fs.bb_claim_slot = true;
-                        fs.a_bn_done = s1_done;
-                        fs.bb_fin = true;
-                        fs.bb_fin_part = rs.part_ptr;
-                        fs.bb_fin_nb = rs.nb;
-                        fs.bb_dgamma = rs.dgamma;
-                        fs.bb_dbeta = rs.dbeta;
-                        fs.bb_fin_done = rs.fin_by_consumer;
-                        std::vector<Op> tmp;
-                        add_pw(tmp, pre + ".sc_pw", ys1.v(), rows_out, sc_c, sc_c, ys2.p, b1.gv(), 0, bnrec(T, Mg_out, sc_c), fs);
-                        ops[scpw_at] = tmp[0];
-                    } else {
-                    if (fused_dw_) {
-                        add_dw_block(ops, pre, nullptr, "sc_dw", "sc_bn1", X.p, curH, curW, sc_c, 2, ys1.p, b1.v(), b1.gv(),
-                                     X.gv(0));
-                    } else {
-                        add_dw(ops, pre + ".sc_dw", X.v(0), N, curH, curW, sc_c, 2, ys1.p, X.gv(0), 0);
-                        add_bn(ops, M_TRUNK, pre + ".sc_bn1", ys1.v(), T, Mg_out, sc_c, true, ACT_NONE, b1.v(), 0, b1.gv(), 0,
-                               nullptr);
-                    }
-                    Tens ys2 = tens_a(rows_out, sc_c, false);
-                    add_pw(ops, pre + ".sc_pw", b1.v(), rows_out, sc_c, sc_c, ys2.p, b1.gv(), 0, bnrec(T, Mg_out, sc_c));
-                    add_bn(ops, M_TRUNK, pre + ".sc_bn2", ys2.v(), T, Mg_out, sc_c, true, ACT_RELU6, out.v(0), C, out.gv(0),
-                           C, nullptr);
-                    }
+                    Half sh{pre, "sc_dw", "sc_bn1", "sc_pw", "sc_bn2", DwBlock{X.p, curH, curW, sc_c, 2, X.gv(0)}, out, 0, sc_c};
+                    // (null probe view: every tens_a tensor is dense and 256-byte aligned, like the null pointer)
+                    sh.fused = sh.bb = fused_dw_ && fused_pw_ && fused_bb_ && gemm_tn_dpro_supported(sc_c) && pw_nn_supported(make_view(nullptr, sc_c), sc_c, sc_c);
+                    add_half(ops, sh);
                     if (sc_overlap) {
                         build_scr_ = &scr_main_;
                         for (size_t i = sc_begin; i < ops.size(); ++i) {        // forward of the shortcut ops -> side stream
@@ -1503,16 +1435,16 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         // ---- head conv + GAP (core/architectures.py:170-172)
         const int P = curH * curW, rows = N * P;
         Tens yh = tens_a(rows, c.last, false);
-        add_pw(ops, "img.head.conv", X.v(), rows, curC, c.last, yh.p, X.gv(), 0, bnrec(T, B * P, c.last));
+        const BnRec head_bn = pw_bn("img.head.conv", curC, c.last, "img.head.bn", yh.p, B * P, ACT_RELU6);
+        add_pw(ops, "img.head.conv", X.v(), rows, curC, c.last, yh.p, X.gv(), 0, head_bn, PwFuse());
         feat_ = tens(N, c.last);
         // BatchNorm + ReLU6 + GlobalAveragePooling2D as one op: the 12288 x 768 activated tensor and its gradient are never
         // written -- the forward pools on the fly, the backward reads the pooled gradient broadcast over the frame's pixels
-        Passthrough hp;
-        hp.gap_out = feat_.p;
-        hp.gap_dout = feat_.g;
-        hp.gap_rows = P;
-        add_bn(ops, M_TRUNK, "img.head.bn", yh.v(), T, B * P, c.last, true, ACT_RELU6, View{nullptr, 0, 0}, 0, View{nullptr, 0, 0}, 0,
-               nullptr, 0, false, hp);
+        BnOp hp;
+        hp.pass.gap_out = feat_.p;
+        hp.pass.gap_dout = feat_.g;
+        hp.pass.gap_rows = P;
+        add_bn(ops, head_bn, hp);
     }
 
     // every trunk parameter registered from here on is a TAIL tensor (feature nets, GRUs, concat BN + Dense): their gradients
@@ -1538,10 +1470,10 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         Tens a0 = tens(N, c.feat), n0 = tens(N, c.feat), a1 = tens(N, c.feat), n1 = tens(N, c.feat);
         add_dense(aux_ops_, M_TRUNK, nm + ".fc0", xin.v(), N, D, c.feat, ACT_RELU6, a0.v(), a0.gv(), View{nullptr, 0, 0}, 0,
                   false, "glorot");
-        add_bn(aux_ops_, M_TRUNK, nm + ".bn0", a0.v(), T, B, c.feat, false, ACT_NONE, n0.v(), 0, n0.gv(), 0, a0.g);
+        add_dense_bn(aux_ops_, M_TRUNK, nm + ".bn0", a0, n0, T);
         add_dense(aux_ops_, M_TRUNK, nm + ".fc1", n0.v(), N, c.feat, c.feat, ACT_RELU6, a1.v(), a1.gv(), n0.gv(), 0, true,
                   "glorot");
-        add_bn(aux_ops_, M_TRUNK, nm + ".bn1", a1.v(), T, B, c.feat, false, ACT_NONE, n1.v(), 0, n1.gv(), 0, a1.g);
+        add_dense_bn(aux_ops_, M_TRUNK, nm + ".bn1", a1, n1, T);
         build_scr_ = &scr_main_;
         fout[i] = n1;
     }
@@ -1578,7 +1510,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
     build_scr_ = &scr_main_;
     add_aux_join(ops);
     Tens ncat = tens(B, catC);
-    add_bn(ops, M_TRUNK, "dyn.bn", cat.v(), 1, B, catC, false, ACT_NONE, ncat.v(), 0, ncat.gv(), 0, cat.g);
+    add_dense_bn(ops, M_TRUNK, "dyn.bn", cat, ncat, 1);
     dyn_ = tens(B, c.dyn);
     add_dense(ops, M_TRUNK, "dyn.fc", ncat.v(), B, catC, c.dyn, ACT_NONE, dyn_.v(), dyn_.gv(), ncat.gv(), 0, true, "glorot");
 }
@@ -1588,9 +1520,9 @@ void Learner::build_head(std::vector<Op>& ops, int model, const std::string& pre
     const Config& c = cfg_;
     const int B = c.B;
     Tens n0 = tens(B, c.dyn), a0 = tens(B, c.head), n1 = tens(B, c.head), a1 = tens(B, c.head);
-    add_bn(ops, model, prefix + ".bn0", dyn_.v(), 1, B, c.dyn, false, ACT_NONE, n0.v(), 0, n0.gv(), 0, dyn_.g);
+    add_dense_bn(ops, model, prefix + ".bn0", dyn_, n0, 1);
     add_dense(ops, model, prefix + ".fc0", n0.v(), B, c.dyn, c.head, ACT_SWISH6, a0.v(), a0.gv(), n0.gv(), 0, true, "glorot");
-    add_bn(ops, model, prefix + ".bn1", a0.v(), 1, B, c.head, false, ACT_NONE, n1.v(), 0, n1.gv(), 0, a0.g);
+    add_dense_bn(ops, model, prefix + ".bn1", a0, n1, 1);
     add_dense(ops, model, prefix + ".fc1", n1.v(), B, c.head, c.head, ACT_SWISH6, a1.v(), a1.gv(), n1.gv(), 0, true, "glorot");
     int L = 0;
     for (int i = 0; i < nheads; ++i) L += head_dims[i];
@@ -1627,6 +1559,28 @@ void Learner::build_head(std::vector<Op>& ops, int model, const std::string& pre
     }
 }
 
+void Learner::alloc_scratch() {
+    const SlotSizes ss = slot_sizes();
+    for (Scratch* s : {&scr_main_, &scr_aux_, &scr_sc_}) {
+        s->part = alloc_d(max_part_);
+        s->part2 = alloc_d(max_part2_);
+    }
+    scr_main_.tn = alloc(max_tn_);
+    scr_aux_.tn = alloc(max_tn_);
+    scr_sc_.tn = scr_aux_.tn;           // (unused by the shortcut ops)
+    for (int i = 0; i < NSLOT; ++i) {
+        dys_[i] = alloc((ss.dy * esz() + 3) / 4);      // tower gradients: activation-typed
+        part2s_[i] = alloc_d(ss.part2);
+        tns_[i] = alloc(ss.tn);
+        fparts_[i] = alloc_d(ss.fpart);
+    }
+    for (int i = 0; i < NQ; ++i) {
+        qparts_[i] = alloc(ss.qpart);
+        dbparts_[i] = alloc_d(ss.dbpart);
+        fintots_[i] = alloc_d(ss.fintot);
+    }
+}
+
 void Learner::build(bool dry) {
     dry_ = dry;
     ws_off_ = 0;
@@ -1635,29 +1589,9 @@ void Learner::build(bool dry) {
     policy_ops_.clear();
     value_ops_.clear();
     old_policy_ops_.clear();
-    const SlotSizes ss = slot_sizes();
-    if (!dry) {
-        scr_main_.part = alloc_d(max_part_);
-        scr_main_.part2 = alloc_d(max_part2_);
-        scr_main_.tn = alloc(max_tn_);
-        scr_aux_.part = alloc_d(max_part_);
-        scr_aux_.part2 = alloc_d(max_part2_);
-        scr_aux_.tn = alloc(max_tn_);
-        scr_sc_.part = alloc_d(max_part_);
-        scr_sc_.part2 = alloc_d(max_part2_);
-        scr_sc_.tn = scr_aux_.tn;           // (unused by the shortcut ops)
-        for (int i = 0; i < NSLOT; ++i) {
-            dys_[i] = alloc((ss.dy * esz() + 3) / 4);      // tower gradients: activation-typed
-            part2s_[i] = alloc_d(ss.part2);
-            tns_[i] = alloc(ss.tn);
-            fparts_[i] = alloc_d(ss.fpart);
-        }
-        for (int i = 0; i < NQ; ++i) {
-            qparts_[i] = alloc(ss.qpart);
-            dbparts_[i] = alloc_d(ss.dbpart);
-            fintots_[i] = alloc_d(ss.fintot);
-        }
-    }
+    // the scratch blocks are sized by the maxima the dry build collects: the real layout starts with them, the dry build (where alloc
+    // only counts bytes and bands) adds them once its op lists are built
+    if (!dry) alloc_scratch();
     h_pwt_.clear();
     pwt_by_name_.clear();
     pwt_tiles_ = 0;
@@ -1719,6 +1653,7 @@ void Learner::build(bool dry) {
         stats_ring_ = alloc(stats_bytes() / sizeof(float));
         if (!dry_) zero_once_.push_back(std::make_pair(stats_ring_, (size_t)STATS_HEADER * sizeof(float)));
     }
+    if (dry) alloc_scratch();
     if (guard_) {       // band table (device) behind everything else; no band behind it
         const bool g = guard_;
         guard_ = false;
@@ -1726,19 +1661,7 @@ void Learner::build(bool dry) {
         guard_ = g;
         if (!dry && guard_off_.size() > GUARD_TABLE_MAX) build_fail("CDRL_GUARD: %zu bands exceed the table", guard_off_.size());
     }
-    if (dry) {
-        // scratch goes first in the real layout; account for it here (maxima of the whole dry build, hence a fresh slot_sizes())
-        const SlotSizes ss2 = slot_sizes();
-        ws_off_ += 512 + 2 * (align_up(max_part_ * sizeof(double), 256) + align_up(max_part2_ * sizeof(double), 256) +
-                        align_up(max_tn_ * sizeof(float), 256)) +
-                   align_up(max_part_ * sizeof(double), 256) + align_up(max_part2_ * sizeof(double), 256) +
-                   NSLOT * (align_up((ss2.dy * esz() + 3) / 4 * sizeof(float), 256) + align_up(ss2.part2 * sizeof(double), 256) +
-                            align_up(ss2.tn * sizeof(float), 256) + align_up(ss2.fpart * sizeof(double), 256)) +
-                   NQ * (align_up(ss2.qpart * sizeof(float), 256) + align_up(ss2.dbpart * sizeof(double), 256) +
-                         align_up(ss2.fintot * sizeof(double), 256));
-        if (guard_) ws_off_ += (size_t)(8 + 4 * NSLOT + 3 * NQ) * GUARD_BYTES;      // one band per scratch allocation above
-        ws_bytes_ = ws_off_ + 4096;
-    }
+    if (dry) ws_bytes_ = ws_off_ + 4096;
 }
 
 void Learner::build_seg_tables() {

@@ -30,6 +30,18 @@ def test_every_guard_band_is_intact_after_a_full_size_update_step(compute):
     assert ws > 5 * 2 ** 30 * (0.4 if compute == 'bf16s' else 1.0) * 0.5        # the full-size plan, bands included
 
 
+# every fusion and the side stream off (the switch set of tests/test_gpu_paths.py): the planner then hands other blocks to other kernels
+ALL_OFF = dict(CDRL_FUSED_DW=0, CDRL_FUSED_PW=0, CDRL_FUSED_STEM=0, CDRL_FUSED_PASS=0, CDRL_FUSED_BB=0, CDRL_SIDE_STREAM=0, CDRL_PW_X3=0)
+
+
+@pytest.mark.parametrize('compute,env', [('f32', ALL_OFF), ('bf16s', {})], ids=['f32-all-off', 'bf16s'])
+def test_every_guard_band_is_intact_at_the_small_shape(compute, env):
+    """B = 4, 48x64 (odd map sizes, partial tiles everywhere): a conv or BatchNorm op that reads or writes a block it was not given -- the
+    planner's allocation order decides the neighbours -- lands in a band."""
+    bad, first, _, _ = _run('check', compute, CDRL_GUARD=1, GB_B=4, GB_H=48, GB_W=64, **env)
+    assert (bad, first) == (0, -1), (bad, first)
+
+
 def test_a_written_band_is_reported_and_the_switch_is_needed():
     for which in (0, 5):        # the first band of the workspace and a later one
         bad, first, _, poked = _run('poke', 'f32', which, CDRL_GUARD=1, GB_B=4, GB_H=48, GB_W=64)
