@@ -60,11 +60,18 @@ class ValueBatch(C.Structure):
     _fields_ = [(n, _fp) for n in ('image', 'road', 'vehicle', 'navigation', 'returns', 'speed', 'similarity')]
 
 
+class View(C.Structure):
+    """cdrl_view (include/cdrl.h): element (r, c) at p[r * ld + coff + c], counted in elements of the tensor's type."""
+    _fields_ = [('p', C.c_void_p), ('ld', C.c_int32), ('coff', C.c_int32)]
+
+
 TRUNK, POLICY, VALUE, OLD_POLICY = 0, 1, 2, 3
 BUF_DYNAMICS, BUF_IMG_FEAT, BUF_METRICS_P, BUF_METRICS_V, BUF_AUX_P, BUF_AUX_V, BUF_LIN_P, BUF_LIN_V, BUF_SAMPLE = range(9)
 
 _i, _i64, _f, _d, _sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 _L = C.c_void_p
+_V = C.POINTER(View)
+_pp = C.POINTER(C.c_void_p)
 
 # name -> (restype, argtypes); must list every symbol declared in include/cdrl.h
 PROTOTYPES = {
@@ -174,6 +181,14 @@ PROTOTYPES = {
     'cdrl_bn_train_fwd': (_i, [_fp, _i, _i, _i, _fp, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _fp, _fp, _fp]),
     'cdrl_bn_train_bwd': (_i, [_fp, _i, _i, _i, _fp, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_maxpool_bn_fwd': (_i, [_fp, _fp, _i, _i, _fp, _fp, _i, _i, _i, _i, _fp]),
+    # (act_type listed explicitly: these are NOT in ACT_TYPE_BEFORE_STREAM, callers pass it)
+    'cdrl_bn_apply': (_i, [_V, _i, _i, _i, _fp, _i, _V, _i, _V, _V, _i, _fp]),
+    'cdrl_bn_bwd': (_i, [_V, _i, _V, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp, _fp, _V, _V, _i, _i, _fp]),
+    'cdrl_bn_plan': (_i, [_V, _V, _V, _i, _i, _i, _i, _i, _i, _V, _V, _V, _V, _fp, _i, _i, C.POINTER(C.c_int32), _i]),
+    'cdrl_bn_act_gap_fwd': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp]),
+    'cdrl_gather_view': (_i, [_V, _i, _i, _i, _V, _i, _fp]),
+    'cdrl_bn_inference_stats_table_bytes': (_i64, [_i]),
+    'cdrl_bn_inference_stats': (_i, [_i, _pp, _pp, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_i), _fp, _fp]),
     'cdrl_bn_train_bwd_pooled': (_i, [_fp, _fp, _i, _i, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_beta_ppo_loss': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _f, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_value_loss': (_i, [_fp, _fp, _fp, _fp, _i, _f, _f, _fp, _fp, _fp, _fp]),

@@ -492,44 +492,56 @@ __global__ void __launch_bounds__(256) bn_apply_shuf_kernel(View y, int Mg, int 
     }
 }
 
+static void plan_geom(BnPlan& p, const VColGeom& g) {
+    p.vec = g.vec;
+    p.cx = g.cx;
+    p.cy = g.cy;
+    p.nloop = g.nloop;
+    p.rb = g.rb;
+    p.nb = g.nb;
+}
+
+// The one place that decides between bn_apply_shuf_kernel (form 1) and bn_apply_kernel (form 0); bn_apply_t launches what it says.
+BnPlan bn_apply_plan(View y, int Mg, int C, bool has_stats, View dst, int shuffle_ctot, const View* pass_src, const View* pass_dst) {
+    BnPlan p{};
+    const VColGeom g = vcol_geom(Mg, C, 2048);
+    plan_geom(p, g);
+    const bool pass = pass_src && pass_dst && pass_src->p;
+    p.al0 = view_aligned(y, g.vec);
+    p.al1 = view_aligned(dst, g.vec);
+    p.al2 = pass && view_aligned(*pass_src, g.vec);
+    p.form = has_stats && shuffle_ctot && g.nloop == 1 && g.vec >= 2 && p.al0 && (!pass || p.al2);
+    return p;
+}
+
 template <class T>
 static int bn_apply_t(View y, int G, int Mg, int C, const float* stats, int act, View dst, int shuffle_ctot,
                       hipStream_t st, const View* pass_src, const View* pass_dst) {
-    {
-        const VColGeom g = vcol_geom(Mg, C, 2048);
-        View ps{nullptr, 0, 0}, pd{nullptr, 0, 0};
-        if (pass_src && pass_dst) {
-            ps = *pass_src;
-            pd = *pass_dst;
-        }
-        if (stats && shuffle_ctot && g.nloop == 1 && g.vec >= 2 && view_aligned(y, g.vec) && (!ps.p || view_aligned(ps, g.vec))) {
-            dim3 grid(g.nb, G), block(g.cx, g.cy);
-            if (g.vec == 4) {
-                if (ps.p) hipLaunchKernelGGL((bn_apply_shuf_kernel<4, true, T>), grid, block, 0, st, y, Mg, C, g.rb, G * C, stats, act, dst, shuffle_ctot, ps, pd);
-                else hipLaunchKernelGGL((bn_apply_shuf_kernel<4, false, T>), grid, block, 0, st, y, Mg, C, g.rb, G * C, stats, act, dst, shuffle_ctot, ps, pd);
-            } else {
-                if (ps.p) hipLaunchKernelGGL((bn_apply_shuf_kernel<2, true, T>), grid, block, 0, st, y, Mg, C, g.rb, G * C, stats, act, dst, shuffle_ctot, ps, pd);
-                else hipLaunchKernelGGL((bn_apply_shuf_kernel<2, false, T>), grid, block, 0, st, y, Mg, C, g.rb, G * C, stats, act, dst, shuffle_ctot, ps, pd);
-            }
-            CDRL_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    VColGeom g = vcol_geom(Mg, C, 2048);
-    const bool ai = view_aligned(y, g.vec), ao = view_aligned(dst, g.vec);
+    const BnPlan p = bn_apply_plan(y, Mg, C, stats != nullptr, dst, shuffle_ctot, pass_src, pass_dst);
     View ps{nullptr, 0, 0}, pd{nullptr, 0, 0};
     if (pass_src && pass_dst) {
         ps = *pass_src;
         pd = *pass_dst;
     }
-    const bool aps = ps.p && view_aligned(ps, g.vec);
-    dim3 grid(g.nb, G), block(g.cx, g.cy);
-    if (g.vec == 4)
-        hipLaunchKernelGGL((bn_apply_kernel<4, T>), grid, block, 0, st, y, Mg, C, g.rb, g.nloop, G * C, stats, act, dst, shuffle_ctot, ai, ao, ps, pd, aps);
-    else if (g.vec == 2)
-        hipLaunchKernelGGL((bn_apply_kernel<2, T>), grid, block, 0, st, y, Mg, C, g.rb, g.nloop, G * C, stats, act, dst, shuffle_ctot, ai, ao, ps, pd, aps);
+    dim3 grid(p.nb, G), block(p.cx, p.cy);
+    if (p.form == 1) {
+        if (p.vec == 4) {
+            if (ps.p) hipLaunchKernelGGL((bn_apply_shuf_kernel<4, true, T>), grid, block, 0, st, y, Mg, C, p.rb, G * C, stats, act, dst, shuffle_ctot, ps, pd);
+            else hipLaunchKernelGGL((bn_apply_shuf_kernel<4, false, T>), grid, block, 0, st, y, Mg, C, p.rb, G * C, stats, act, dst, shuffle_ctot, ps, pd);
+        } else {
+            if (ps.p) hipLaunchKernelGGL((bn_apply_shuf_kernel<2, true, T>), grid, block, 0, st, y, Mg, C, p.rb, G * C, stats, act, dst, shuffle_ctot, ps, pd);
+            else hipLaunchKernelGGL((bn_apply_shuf_kernel<2, false, T>), grid, block, 0, st, y, Mg, C, p.rb, G * C, stats, act, dst, shuffle_ctot, ps, pd);
+        }
+        CDRL_LAUNCH_CHECK();
+        return 0;
+    }
+    const bool ai = p.al0, ao = p.al1, aps = p.al2;
+    if (p.vec == 4)
+        hipLaunchKernelGGL((bn_apply_kernel<4, T>), grid, block, 0, st, y, Mg, C, p.rb, p.nloop, G * C, stats, act, dst, shuffle_ctot, ai, ao, ps, pd, aps);
+    else if (p.vec == 2)
+        hipLaunchKernelGGL((bn_apply_kernel<2, T>), grid, block, 0, st, y, Mg, C, p.rb, p.nloop, G * C, stats, act, dst, shuffle_ctot, ai, ao, ps, pd, aps);
     else
-        hipLaunchKernelGGL((bn_apply_kernel<1, T>), grid, block, 0, st, y, Mg, C, g.rb, g.nloop, G * C, stats, act, dst, shuffle_ctot, ai, ao, ps, pd, aps);
+        hipLaunchKernelGGL((bn_apply_kernel<1, T>), grid, block, 0, st, y, Mg, C, p.rb, p.nloop, G * C, stats, act, dst, shuffle_ctot, ai, ao, ps, pd, aps);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
@@ -747,7 +759,7 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_shuf_kernel(View da, int ct
 }
 
 template <int VEC, class T>
-static void launch_bbr_shuf(const VColGeom& g, int G, hipStream_t st, View da, int ctot, const float* y, const float* stats, int C,
+static void launch_bbr_shuf(const BnPlan& g, int G, hipStream_t st, View da, int ctot, const float* y, const float* stats, int C,
                             int Mg, View pgs, View pgd, double* part) {
     dim3 grid(g.nb, G), block(g.cx, g.cy);
     size_t sm = (size_t)g.cy * VEC * g.cx * sizeof(double);
@@ -759,44 +771,49 @@ static void launch_bbr_shuf(const VColGeom& g, int G, hipStream_t st, View da, i
         hipLaunchKernelGGL((bn_bwd_reduce_shuf_kernel<VEC, false, T>), grid, block, sm, st, da, ctot, yt, stats, G * C, C, Mg, g.rb, pgs, pgd, part);
 }
 
+// The one place that decides between bn_bwd_reduce_shuf_kernel (form 1) and the generic skeleton with BnBwdReduceF (form 0, which
+// takes its geometry from the same vcol_geom(Mg, C, NB_STATS)); bn_bwd_reduce launches what it says.
+BnPlan bn_bwd_reduce_plan(View da, int shuffle_ctot, View y, int Mg, int C, int act, bool pool, const View* pass_gsrc,
+                          const View* pass_gdst, int bcast_rows) {
+    BnPlan p{};
+    const VColGeom g = vcol_geom(Mg, C, NB_STATS);
+    plan_geom(p, g);
+    const bool pass = pass_gsrc && pass_gdst && pass_gsrc->p;
+    p.al0 = pool ? false : view_aligned(da, g.vec);
+    p.al1 = view_aligned(y, g.vec);
+    p.al2 = pass_gsrc && pass_gdst && pass_gdst->p && view_aligned(*pass_gdst, g.vec);
+    const bool ydense = y.ld == C && y.coff == 0 && p.al1;
+    const bool pok = !pass || p.al2;
+    p.form = !pool && !bcast_rows && shuffle_ctot && act == ACT_RELU6 && g.nloop == 1 && ydense && pok && g.vec >= 2;
+    return p;
+}
+
 int bn_bwd_reduce(View da, int shuffle_ctot, View y, int G, int Mg, int C, const float* stats, int act,
                   double* part, hipStream_t st, const PoolSrc* pool, const View* pass_gsrc, const View* pass_gdst, int bcast_rows, int at) {
-    {
-        const VColGeom g = vcol_geom(Mg, C, NB_STATS);
-        View pgs{nullptr, 0, 0}, pgd{nullptr, 0, 0};
-        if (pass_gsrc && pass_gdst) {
-            pgs = *pass_gsrc;
-            pgd = *pass_gdst;
-        }
-        const bool ydense = y.ld == C && y.coff == 0 && view_aligned(y, g.vec);
-        const bool pok = !pgs.p || (pgd.p && view_aligned(pgd, g.vec));
-        if (!pool && !bcast_rows && shuffle_ctot && act == ACT_RELU6 && g.nloop == 1 && ydense && pok && g.vec >= 2) {
-            if (at) {
-                if (g.vec == 4) launch_bbr_shuf<4, bf16_t>(g, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
-                else launch_bbr_shuf<2, bf16_t>(g, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
-            } else {
-                if (g.vec == 4) launch_bbr_shuf<4, float>(g, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
-                else launch_bbr_shuf<2, float>(g, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
-            }
-            CDRL_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    const int vec = vcol_geom(Mg, C).vec;
-    PoolSrc ps{};
-    if (pool) ps = *pool;
+    const BnPlan p = bn_bwd_reduce_plan(da, shuffle_ctot, y, Mg, C, act, pool != nullptr, pass_gsrc, pass_gdst, bcast_rows);
     View pgs{nullptr, 0, 0}, pgd{nullptr, 0, 0};
     if (pass_gsrc && pass_gdst) {
         pgs = *pass_gsrc;
         pgd = *pass_gdst;
     }
+    if (p.form == 1) {
+        if (at) {
+            if (p.vec == 4) launch_bbr_shuf<4, bf16_t>(p, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
+            else launch_bbr_shuf<2, bf16_t>(p, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
+        } else {
+            if (p.vec == 4) launch_bbr_shuf<4, float>(p, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
+            else launch_bbr_shuf<2, float>(p, G, st, da, shuffle_ctot, y.p, stats, C, Mg, pgs, pgd, part);
+        }
+        CDRL_LAUNCH_CHECK();
+        return 0;
+    }
+    PoolSrc ps{};
+    if (pool) ps = *pool;
     if (at)
         return launch_vcolreduce_t<2, BnBwdReduceF, bf16_t>(G, Mg, C, part, st, NB_STATS, da, shuffle_ctot, y, stats, G * C, C, act,
-                                                            pool ? false : view_aligned(da, vec), view_aligned(y, vec), pool != nullptr, ps,
-                                                            pgs, pgd, pgd.p && view_aligned(pgd, vec), bcast_rows);
+                                                            (bool)p.al0, (bool)p.al1, pool != nullptr, ps, pgs, pgd, (bool)p.al2, bcast_rows);
     return launch_vcolreduce_t<2, BnBwdReduceF, float>(G, Mg, C, part, st, NB_STATS, da, shuffle_ctot, y, stats, G * C, C, act,
-                                                       pool ? false : view_aligned(da, vec), view_aligned(y, vec), pool != nullptr, ps,
-                                                       pgs, pgd, pgd.p && view_aligned(pgd, vec), bcast_rows);
+                                                       (bool)p.al0, (bool)p.al1, pool != nullptr, ps, pgs, pgd, (bool)p.al2, bcast_rows);
 }
 
 // BN-backward sums of a BatchNorm+ReLU6 whose output feeds a 3x3/s2 max-pool, in SCATTER form: iterate over the POOLED
@@ -1193,40 +1210,50 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_fast_kernel(View da, int cto
     }
 }
 
+// The one place that decides between bn_bwd_apply_fast_kernel (form 1) and the generic skeleton with BnBwdApplyF (form 0, same
+// geometry); bn_bwd_apply launches what it says.  al2: dy is aligned for `vec` floats (form 0 refuses the call otherwise).
+BnPlan bn_bwd_apply_plan(View da, View y, int Mg, int C, const float* dy, bool pool) {
+    BnPlan p{};
+    const VColGeom g = vcol_geom(Mg, C, NB_STATS);
+    plan_geom(p, g);
+    p.al0 = pool ? false : view_aligned(da, g.vec);
+    p.al1 = view_aligned(y, g.vec);
+    p.al2 = (reinterpret_cast<uintptr_t>(dy) % (4 * g.vec)) == 0;
+    const bool ydense = y.ld == C && y.coff == 0 && p.al1;
+    p.form = !pool && g.nloop == 1 && g.vec >= 2 && ydense && p.al2;
+    return p;
+}
+
 int bn_bwd_apply(View da, int shuffle_ctot, View y, int G, int Mg, int C, const float* stats, const float* coef,
                  int act, float* dy, double* part2, hipStream_t st, const PoolSrc* pool, int bcast_rows, int at) {
-    {
-        const VColGeom g = vcol_geom(Mg, C, NB_STATS);
-        const bool ydense = y.ld == C && y.coff == 0 && view_aligned(y, g.vec);
-        if (!pool && g.nloop == 1 && g.vec >= 2 && ydense && (reinterpret_cast<uintptr_t>(dy) % (4 * g.vec)) == 0) {
-            dim3 grid(g.nb, G), block(g.cx, g.cy);
-            const size_t sm = (size_t)g.cy * g.vec * g.cx * sizeof(double);
-            const bf16_t* yb = reinterpret_cast<const bf16_t*>(y.p);
-            bf16_t* dyb = reinterpret_cast<bf16_t*>(dy);
-            if (at && g.vec == 4)
-                hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<4, bf16_t>), grid, block, sm, st, da, shuffle_ctot, yb, stats, coef, G * C, C, Mg, g.rb, act, dyb, part2, bcast_rows);
-            else if (at)
-                hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<2, bf16_t>), grid, block, sm, st, da, shuffle_ctot, yb, stats, coef, G * C, C, Mg, g.rb, act, dyb, part2, bcast_rows);
-            else if (g.vec == 4)
-                hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<4, float>), grid, block, sm, st, da, shuffle_ctot, y.p, stats, coef, G * C, C, Mg, g.rb, act, dy, part2, bcast_rows);
-            else
-                hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<2, float>), grid, block, sm, st, da, shuffle_ctot, y.p, stats, coef, G * C, C, Mg, g.rb, act, dy, part2, bcast_rows);
-            CDRL_LAUNCH_CHECK();
-            return 0;
-        }
+    const BnPlan p = bn_bwd_apply_plan(da, y, Mg, C, dy, pool != nullptr);
+    if (p.form == 1) {
+        dim3 grid(p.nb, G), block(p.cx, p.cy);
+        const size_t sm = (size_t)p.cy * p.vec * p.cx * sizeof(double);
+        const bf16_t* yb = reinterpret_cast<const bf16_t*>(y.p);
+        bf16_t* dyb = reinterpret_cast<bf16_t*>(dy);
+        if (at && p.vec == 4)
+            hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<4, bf16_t>), grid, block, sm, st, da, shuffle_ctot, yb, stats, coef, G * C, C, Mg, p.rb, act, dyb, part2, bcast_rows);
+        else if (at)
+            hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<2, bf16_t>), grid, block, sm, st, da, shuffle_ctot, yb, stats, coef, G * C, C, Mg, p.rb, act, dyb, part2, bcast_rows);
+        else if (p.vec == 4)
+            hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<4, float>), grid, block, sm, st, da, shuffle_ctot, y.p, stats, coef, G * C, C, Mg, p.rb, act, dy, part2, bcast_rows);
+        else
+            hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<2, float>), grid, block, sm, st, da, shuffle_ctot, y.p, stats, coef, G * C, C, Mg, p.rb, act, dy, part2, bcast_rows);
+        CDRL_LAUNCH_CHECK();
+        return 0;
     }
-    const int vec = vcol_geom(Mg, C).vec;
     PoolSrc ps{};
     if (pool) ps = *pool;
-    if ((reinterpret_cast<uintptr_t>(dy) % (4 * vec)) != 0) {
-        set_error("bn_bwd_apply: dy must be %d-byte aligned", 4 * vec);
+    if (!p.al2) {
+        set_error("bn_bwd_apply: dy must be %d-byte aligned", 4 * p.vec);
         return -1;
     }
     if (at)
         return launch_vcolreduce_t<1, BnBwdApplyF, bf16_t>(G, Mg, C, part2, st, NB_STATS, da, shuffle_ctot, y, stats, coef, G * C, C, act,
-                                                           dy, pool ? false : view_aligned(da, vec), view_aligned(y, vec), pool != nullptr, ps, bcast_rows);
+                                                           dy, (bool)p.al0, (bool)p.al1, pool != nullptr, ps, bcast_rows);
     return launch_vcolreduce_t<1, BnBwdApplyF, float>(G, Mg, C, part2, st, NB_STATS, da, shuffle_ctot, y, stats, coef, G * C, C, act,
-                                                      dy, pool ? false : view_aligned(da, vec), view_aligned(y, vec), pool != nullptr, ps, bcast_rows);
+                                                      dy, (bool)p.al0, (bool)p.al1, pool != nullptr, ps, bcast_rows);
 }
 
 // Block = (CX outputs, 1024/CX partial lanes).  CX = 16 gives 128-byte row segments; CX = 4 is used when there are few

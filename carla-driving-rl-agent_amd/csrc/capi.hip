@@ -967,6 +967,133 @@ int cdrl_bn_train_bwd(const float* dout, int dout_ld, int dout_coff, int shuffle
     return bn_bwd_apply(dv, shuffle_ctot, yv, G, Mg, C, stats, coef, act, dy, workspace, S(stream), nullptr, 0, act_type);
 }
 
+// ---- BatchNorm family at op level with the argument forms the engine uses (full views, identity pass-through, pooled gradient) ----
+static inline View view_of(const cdrl_view* v) {
+    View r{nullptr, 0, 0};
+    if (v) r = make_view(static_cast<float*>(v->p), v->ld, v->coff);
+    return r;
+}
+
+// columns [coff, coff + C) of a view, plain or through the shuffle map of a ctot-channel tensor, stay inside a row
+static bool view_ok(const char* fn, const char* name, const cdrl_view* v, int C, int shuffle_ctot) {
+    const bool ok = v && v->p && v->coff >= 0 &&
+                    (shuffle_ctot ? (shuffle_ctot % 2 == 0 && v->coff + C <= shuffle_ctot && shuffle_ctot <= v->ld) : v->coff + C <= v->ld);
+    if (!ok) cdrl::set_error("%s: view %s is null or its %d channels (shuffle %d) do not fit its rows", fn, name, C, shuffle_ctot);
+    return ok;
+}
+
+static bool bn_args_ok(const char* fn, int G, int Mg, int C, int shuffle_ctot, int bcast_rows, bool pass_a, bool pass_b, int at) {
+    if (bad_act_type(at)) return false;
+    if (G < 1 || Mg < 1 || C < 1 || shuffle_ctot < 0 || bcast_rows < 0 || pass_a != pass_b ||
+        (bcast_rows && (Mg % bcast_rows != 0 || shuffle_ctot || pass_a))) {
+        cdrl::set_error("%s: bad shape G %d Mg %d C %d, shuffle %d, bcast_rows %d, or half a pass-through pair", fn, G, Mg, C, shuffle_ctot, bcast_rows);
+        return false;
+    }
+    return true;
+}
+
+int cdrl_bn_apply(const cdrl_view* y, int G, int Mg, int C, const float* stats, int relu6, const cdrl_view* out, int shuffle_ctot,
+                  const cdrl_view* pass_src, const cdrl_view* pass_dst, int act_type, void* stream) {
+    if (!bn_args_ok("cdrl_bn_apply", G, Mg, C, shuffle_ctot, 0, pass_src != nullptr, pass_dst != nullptr, act_type)) return -1;
+    if (!view_ok("cdrl_bn_apply", "y", y, C, 0) || !view_ok("cdrl_bn_apply", "out", out, C, shuffle_ctot)) return -1;
+    if (pass_src && (!view_ok("cdrl_bn_apply", "pass_src", pass_src, C, 0) || !view_ok("cdrl_bn_apply", "pass_dst", pass_dst, C, shuffle_ctot)))
+        return -1;
+    if (!stats && (act_type || relu6)) {
+        cdrl::set_error("cdrl_bn_apply: the copy form (stats = NULL) is float32 without activation");
+        return -1;
+    }
+    const View ps = view_of(pass_src), pd = view_of(pass_dst);
+    return bn_apply(view_of(y), G, Mg, C, stats, relu6 ? ACT_RELU6 : ACT_NONE, view_of(out), shuffle_ctot, S(stream),
+                    pass_src ? &ps : nullptr, pass_dst ? &pd : nullptr, act_type);
+}
+
+int cdrl_bn_bwd(const cdrl_view* dout, int shuffle_ctot, const cdrl_view* y, int G, int Mg, int C, const float* stats, int relu6,
+                float* dgamma, float* dbeta, float* dy, float* coef, double* workspace, const cdrl_view* pass_gsrc,
+                const cdrl_view* pass_gdst, int bcast_rows, int act_type, void* stream) {
+    if (!bn_args_ok("cdrl_bn_bwd", G, Mg, C, shuffle_ctot, bcast_rows, pass_gsrc != nullptr, pass_gdst != nullptr, act_type)) return -1;
+    if (!view_ok("cdrl_bn_bwd", "dout", dout, C, shuffle_ctot) || !view_ok("cdrl_bn_bwd", "y", y, C, 0)) return -1;
+    if (pass_gsrc && (!view_ok("cdrl_bn_bwd", "pass_gsrc", pass_gsrc, C, shuffle_ctot) || !view_ok("cdrl_bn_bwd", "pass_gdst", pass_gdst, C, 0)))
+        return -1;
+    const View dv = view_of(dout), yv = view_of(y), pgs = view_of(pass_gsrc), pgd = view_of(pass_gdst);
+    const int nb = vcol_geom(Mg, C).nb;
+    const int act = relu6 ? ACT_RELU6 : ACT_NONE;
+    double* part2 = workspace + (int64_t)G * nb * 2 * C;
+    hipStream_t st = S(stream);
+    CDRL_TRY(bn_bwd_reduce(dv, shuffle_ctot, yv, G, Mg, C, stats, act, workspace, st, nullptr, pass_gsrc ? &pgs : nullptr,
+                           pass_gdst ? &pgd : nullptr, bcast_rows, act_type));
+    CDRL_TRY(bn_bwd_finalize(workspace, nb, G, Mg, C, stats, dgamma, dbeta, coef, st));
+    return bn_bwd_apply(dv, shuffle_ctot, yv, G, Mg, C, stats, coef, act, dy, part2, st, nullptr, bcast_rows, act_type);
+}
+
+int cdrl_bn_plan(const cdrl_view* y, const cdrl_view* out, const cdrl_view* dout, int shuffle_ctot, int G, int Mg, int C, int has_stats,
+                 int relu6, const cdrl_view* pass_src, const cdrl_view* pass_dst, const cdrl_view* pass_gsrc, const cdrl_view* pass_gdst,
+                 const float* dy, int bcast_rows, int act_type, int32_t* fields, int n_out) {
+    if (!bn_args_ok("cdrl_bn_plan", G, Mg, C, shuffle_ctot, bcast_rows, pass_src != nullptr, pass_dst != nullptr, act_type)) return -1;
+    if (!y || !out || !dout || (pass_gsrc != nullptr) != (pass_gdst != nullptr) || (!fields && n_out > 0)) {
+        cdrl::set_error("cdrl_bn_plan: y, out and dout views are required, pass-through views come in pairs");
+        return -1;
+    }
+    const View ps = view_of(pass_src), pd = view_of(pass_dst), pgs = view_of(pass_gsrc), pgd = view_of(pass_gdst);
+    const BnPlan plans[3] = {
+        bn_apply_plan(view_of(y), Mg, C, has_stats != 0, view_of(out), shuffle_ctot, pass_src ? &ps : nullptr, pass_dst ? &pd : nullptr),
+        bn_bwd_reduce_plan(view_of(dout), shuffle_ctot, view_of(y), Mg, C, relu6 ? ACT_RELU6 : ACT_NONE, false, pass_gsrc ? &pgs : nullptr,
+                           pass_gdst ? &pgd : nullptr, bcast_rows),
+        bn_bwd_apply_plan(view_of(dout), view_of(y), Mg, C, dy, false)};
+    int n = 0;
+    for (const BnPlan& p : plans) {
+        const int32_t f[] = {p.form, p.vec, p.cx, p.cy, p.nloop, p.rb, p.nb, p.al0, p.al1, p.al2};
+        for (int32_t v : f) {
+            if (n < n_out) fields[n] = v;
+            ++n;
+        }
+    }
+    return n;
+}
+
+int cdrl_bn_act_gap_fwd(const float* y, const float* stats, float* out, int G, int frames_per_group, int P, int C, int relu6,
+                        int act_type, void* stream) {
+    if (bad_act_type(act_type)) return -1;
+    if (!y || !stats || !out || G < 1 || frames_per_group < 1 || P < 1 || C < 1) {
+        cdrl::set_error("cdrl_bn_act_gap_fwd: null tensor or bad shape G %d frames %d P %d C %d", G, frames_per_group, P, C);
+        return -1;
+    }
+    return bn_act_gap_fwd(y, stats, out, G, frames_per_group, P, C, relu6 ? ACT_RELU6 : ACT_NONE, S(stream), act_type);
+}
+
+int cdrl_gather_view(const cdrl_view* src, int shuffle_ctot, int rows, int C, const cdrl_view* dst, int accumulate, void* stream) {
+    if (rows < 1 || C < 1 || shuffle_ctot < 0) {
+        cdrl::set_error("cdrl_gather_view: bad shape rows %d C %d shuffle %d", rows, C, shuffle_ctot);
+        return -1;
+    }
+    if (!view_ok("cdrl_gather_view", "src", src, C, shuffle_ctot) || !view_ok("cdrl_gather_view", "dst", dst, C, 0)) return -1;
+    return gather_view(view_of(src), shuffle_ctot, rows, C, view_of(dst), accumulate, S(stream));
+}
+
+int64_t cdrl_bn_inference_stats_table_bytes(int n) { return (int64_t)(n > 0 ? n : 0) * (int64_t)sizeof(BnInfEntry); }
+
+int cdrl_bn_inference_stats(int n, const float* const* gamma, const float* const* beta, const float* const* moving_mean,
+                            const float* const* moving_var, float* const* stats, const int* G, const int* C, void* table_dev,
+                            void* stream) {
+    if (n < 1 || n > 1024 || !gamma || !beta || !moving_mean || !moving_var || !stats || !G || !C || !table_dev) {
+        cdrl::set_error("cdrl_bn_inference_stats: 1..1024 layers, no null array");
+        return -1;
+    }
+    BnInfEntry tab[1024];
+    int max_c = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!gamma[i] || !beta[i] || !moving_mean[i] || !moving_var[i] || !stats[i] || G[i] < 1 || C[i] < 1) {
+            cdrl::set_error("cdrl_bn_inference_stats: layer %d has a null vector or a bad shape", i);
+            return -1;
+        }
+        tab[i] = BnInfEntry{gamma[i], beta[i], moving_mean[i], moving_var[i], stats[i], G[i], C[i]};
+        if (C[i] > max_c) max_c = C[i];
+    }
+    // the table lives on this frame: the copy goes through the stream, and the call waits for it before the frame goes away
+    CDRL_HIP(hipMemcpyAsync(table_dev, tab, (size_t)n * sizeof(BnInfEntry), hipMemcpyHostToDevice, S(stream)));
+    CDRL_HIP(hipStreamSynchronize(S(stream)));
+    return bn_inference_stats_many(static_cast<const BnInfEntry*>(table_dev), n, max_c, S(stream));
+}
+
 int cdrl_bn_small_fwd(const float* y, int M, int C, const float* gamma, const float* beta, float* moving_mean,
                       float* moving_var, float* stats, float* out, void* stream) {
     return bn_small_fwd(make_view(const_cast<float*>(y), C), M, C, gamma, beta, moving_mean, moving_var, stats, make_view(out, C),

@@ -71,6 +71,18 @@ int reduce_partials2(const double* part, int nparts, int n1, int n2, int64_t str
 int colsum(View x, int rows, int C, double* part, hipStream_t st);
 // dst(view) = src(view) gathered through the shuffle map on the *source* (backward of shuffle)
 int gather_view(View src, int shuffle_ctot, int rows, int C, View dst, int accumulate, hipStream_t st);
+// What the three launchers above dispatch on (they call these and launch what the plan says; cdrl_bn_plan reports the same structs).
+// form: 0 the generic vcolreduce-style kernel, 1 the fast kernel (bn_apply_shuf_kernel / bn_bwd_reduce_shuf_kernel /
+// bn_bwd_apply_fast_kernel); vec .. nb: the vcol_geom the launch uses; al0..al2: the alignment flags the generic kernel receives --
+// apply: y, dst, pass_src; reduce: da, y, pass_gdst; backward apply: da, y, dy (a misaligned dy is refused by form 0).
+struct BnPlan {
+    int form, vec, cx, cy, nloop, rb, nb;
+    int al0, al1, al2;
+};
+BnPlan bn_apply_plan(View y, int Mg, int C, bool has_stats, View dst, int shuffle_ctot, const View* pass_src, const View* pass_dst);
+BnPlan bn_bwd_reduce_plan(View da, int shuffle_ctot, View y, int Mg, int C, int act, bool pool, const View* pass_gsrc,
+                          const View* pass_gdst, int bcast_rows);
+BnPlan bn_bwd_apply_plan(View da, View y, int Mg, int C, const float* dy, bool pool);
 // elementwise activation on dense [n] arrays
 int act_fwd(const float* z, float* a, int64_t n, int act, hipStream_t st);
 int act_bwd(const float* z, const float* da, float* dz, int64_t n, int act, hipStream_t st);

@@ -559,6 +559,58 @@ int cdrl_linear_heads_bwd(const float* a, int nheads, const int* n, const float*
 int cdrl_bn_train_bwd(const float* dout, int dout_ld, int dout_coff, int shuffle_ctot, const float* y, int G, int Mg,
                       int C, const float* stats, int relu6, float* dgamma, float* dbeta, float* dy, float* coef,
                       double* workspace, int act_type, void* stream);
+/* ---- The BatchNorm family with the argument forms the engine runs it with (csrc/bn.hip: bn_apply, bn_bwd_reduce, bn_bwd_finalize,
+ * bn_bwd_apply, bn_act_gap_fwd, gather_view, bn_inference_stats_many).  Thin wrappers; every one takes `act_type` explicitly where the
+ * host function has one.
+ * A view: element (row r, channel c) of the tensor lives at p[r*ld + coff + c], ld and coff counted in elements of the tensor's type
+ * (float32, or bf16 with act_type = 1).  A view written or read "through the shuffle" of a ctot-channel tensor maps concat index
+ * i = coff + c to column (i & 1) * (ctot / 2) + (i >> 1) (channel_shuffle, core/architectures.py:109-118). */
+typedef struct cdrl_view {
+    void* p;
+    int32_t ld, coff;
+} cdrl_view;
+/* out = [relu6](scale * y + shift) of the stats block (4*G*C: mean, invstd, scale, shift), stored plain (shuffle_ctot = 0) or through the
+ * shuffle; pass_src / pass_dst (both or neither): a second tensor of the same C channels copied through the same store (the unit's
+ * identity half).  stats = NULL: copy only, float32, no activation. */
+int cdrl_bn_apply(const cdrl_view* y, int G, int Mg, int C, const float* stats, int relu6, const cdrl_view* out, int shuffle_ctot,
+                  const cdrl_view* pass_src, const cdrl_view* pass_dst, int act_type, void* stream);
+/* Backward of the same: sums -> dgamma, dbeta, coef (3*G*C) -> dy (dense [G*Mg][C]).  dout is read plain or through the shuffle;
+ * pass_gsrc (read through the same shuffle) -> pass_gdst (plain): the identity half's gradient, copied in the same pass.
+ * bcast_rows > 0: dout is a float32 tensor with ONE row per bcast_rows rows of y, divided by bcast_rows on load (the gradient of a
+ * global average pool; Mg % bcast_rows == 0, no shuffle, no pass-through).
+ * workspace: 3*G*nb*C doubles, nb = field 16 of cdrl_bn_plan (<= 128): [G][nb][2][C] partial (sum dz, sum dz*xhat), then [G][nb][C]
+ * partial column sums of dy. */
+int cdrl_bn_bwd(const cdrl_view* dout, int shuffle_ctot, const cdrl_view* y, int G, int Mg, int C, const float* stats, int relu6,
+                float* dgamma, float* dbeta, float* dy, float* coef, double* workspace, const cdrl_view* pass_gsrc,
+                const cdrl_view* pass_gdst, int bcast_rows, int act_type, void* stream);
+/* What the launchers of cdrl_bn_apply / cdrl_bn_bwd dispatch on for these arguments (they call the same host functions): launches
+ * nothing, reads no memory (the views' pointers only count for their alignment).  Writes min(n_out, 30) int32 fields and returns 30:
+ * three plans of 10 fields -- 0-9 forward apply, 10-19 backward reduce, 20-29 backward apply:
+ *   +0 form   0: generic kernel (vcolreduce skeleton), 1: fast kernel (bn_apply_shuf_kernel, bn_bwd_reduce_shuf_kernel,
+ *             bn_bwd_apply_fast_kernel)
+ *   +1 vec    channels per thread: 4 (C % 4 == 0), 2 (C even), 1
+ *   +2 cx     channel lanes per workgroup, min(C / vec, 256)
+ *   +3 cy     row lanes per workgroup, max(256 / cx, 1)
+ *   +4 nloop  channel-lane passes, > 1 when C / vec > 256 (generic kernel only)
+ *   +5 rb     rows per workgroup (a multiple of cy, at least 2 cy)
+ *   +6 nb     workgroups per group: the partial rows of the backward
+ *   +7..+9    alignment flags handed to the generic kernel -- apply: y, out, pass_src; reduce: dout, y, pass_gdst;
+ *             backward apply: dout, y, dy (form 0 refuses a dy that is not aligned) */
+int cdrl_bn_plan(const cdrl_view* y, const cdrl_view* out, const cdrl_view* dout, int shuffle_ctot, int G, int Mg, int C, int has_stats,
+                 int relu6, const cdrl_view* pass_src, const cdrl_view* pass_dst, const cdrl_view* pass_gsrc, const cdrl_view* pass_gdst,
+                 const float* dy, int bcast_rows, int act_type, int32_t* fields, int n_out);
+/* out[n][c] (float32) = mean over the P rows of frame n of [relu6](scale * y + shift); y dense [G*frames_per_group*P][C] */
+int cdrl_bn_act_gap_fwd(const float* y, const float* stats, float* out, int G, int frames_per_group, int P, int C, int relu6,
+                        int act_type, void* stream);
+/* dst (plain) = or += src read through the shuffle (shuffle_ctot = 0: plain); float32 */
+int cdrl_gather_view(const cdrl_view* src, int shuffle_ctot, int rows, int C, const cdrl_view* dst, int accumulate, void* stream);
+/* Inference-mode stats blocks (moving statistics, eps 1e-3) of n layers in one launch.  Host arrays of n device pointers / sizes;
+ * stats[i]: 4*G[i]*C[i] floats; table_dev: cdrl_bn_inference_stats_table_bytes(n) bytes of device memory, 8-byte aligned.  The call
+ * waits for the table copy (it synchronises the stream once). */
+int64_t cdrl_bn_inference_stats_table_bytes(int n);
+int cdrl_bn_inference_stats(int n, const float* const* gamma, const float* const* beta, const float* const* moving_mean,
+                            const float* const* moving_var, float* const* stats, const int* G, const int* C, void* table_dev,
+                            void* stream);
 /* Fused stem block (core/architectures.py:160-161): BatchNorm-apply + ReLU6 + MaxPooling2D(3,2,'same') on the
  * raw conv output (stats from cdrl_bn_train_fwd), and the BatchNorm backward that gathers its incoming
  * gradient from the pooled gradient `dp` through the saved argmax.  argmax codes: ky * 3 + kx of the winning window position in bits 0-3;
