@@ -185,6 +185,9 @@ PROTOTYPES = {
     'cdrl_bn_apply': (_i, [_V, _i, _i, _i, _fp, _i, _V, _i, _V, _V, _i, _fp]),
     'cdrl_bn_bwd': (_i, [_V, _i, _V, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _fp, _fp, _V, _V, _i, _i, _fp]),
     'cdrl_bn_plan': (_i, [_V, _V, _V, _i, _i, _i, _i, _i, _i, _V, _V, _V, _V, _fp, _i, _i, C.POINTER(C.c_int32), _i]),
+    'cdrl_pwconv_bwd_plan': (_i, [_V, _i, _V, _V] + [_i] * 5 + [_fp] * 7 + [_i] + [_fp] * 3 + [_i, C.POINTER(C.c_int32), _i]),
+    'cdrl_pwconv_bwd_fused_fin': (_i, [_V, _i, _i, _fp, _fp, _fp, _V] + [_fp] * 6 + [_fp, C.c_void_p, _V, _i] + [_fp] * 3 + [C.c_void_p, _fp, _i]
+                                  + [_fp] * 3 + [_i] * 4 + [_fp]),
     'cdrl_bn_act_gap_fwd': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp]),
     'cdrl_gather_view': (_i, [_V, _i, _i, _i, _V, _i, _fp]),
     'cdrl_bn_inference_stats_table_bytes': (_i64, [_i]),
@@ -201,7 +204,7 @@ _lib = None
 # `int act_type` argument (0 float32, 1 bf16) in front of the stream -- the library keeps no mode of its own (round 6; it had a
 # thread-local switch).  The prototypes above list the arguments WITHOUT it; it is spliced in here, and the binding object below offers
 # the tests a mode of its own (`lib.cdrl_set_op_activation_type(at)`, a Python attribute of the binding) that fills it in.
-ACT_TYPE_BEFORE_STREAM = ('cdrl_pwconv_bwd_fused', 'cdrl_gemm_tn', 'cdrl_gemm_x3', 'cdrl_stem_fwd_stats', 'cdrl_stem_block_bwd',
+ACT_TYPE_BEFORE_STREAM = ('cdrl_pwconv_bwd_fused', 'cdrl_pwconv_bwd_fused_fin', 'cdrl_gemm_tn', 'cdrl_gemm_x3', 'cdrl_stem_fwd_stats', 'cdrl_stem_block_bwd',
                           'cdrl_stem_block_bwd_pooled', 'cdrl_pwconv_fused_packed', 'cdrl_pwconv_bn_bwd', 'cdrl_pwconv_bn_bwd_packed',
                           'cdrl_dwconv_bn_fwd', 'cdrl_dwconv_bn_bwd', 'cdrl_bn_train_fwd', 'cdrl_bn_train_bwd', 'cdrl_maxpool_bn_fwd')
 ACT_TYPE_LAST = ('cdrl_pwconv_bwd_fused_workspace',)

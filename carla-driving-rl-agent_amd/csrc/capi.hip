@@ -1050,6 +1050,92 @@ int cdrl_bn_plan(const cdrl_view* y, const cdrl_view* out, const cdrl_view* dout
     return n;
 }
 
+// ---- fused 1x1-conv backward: the plan the launchers dispatch on, and the entry with the finalize-on-load arguments ----
+static void pwb_fill(PwBwdFused& f, const cdrl_view* dz, int dz_shuffle, const cdrl_view* a, const cdrl_view* da, int accumulate, int G, int Mg,
+                     int N, int K, const float* a_stats, const float* a_gamma, const float* a_beta, float* a_dgamma, float* a_dbeta,
+                     float* a_coef, const double* fin_part, int fin_nb, double* fin_tot, float* o_dgamma, float* o_dbeta, int act_type) {
+    f.dz = view_of(dz);
+    f.dz_shuffle = dz_shuffle;
+    f.a = view_of(a);
+    f.da = view_of(da);
+    f.accumulate = accumulate;
+    f.G = G;
+    f.Mg = Mg;
+    f.N = N;
+    f.K = K;
+    f.a_stats = a_stats;
+    f.a_gamma = a_gamma;
+    f.a_beta = a_beta;
+    f.a_dgamma = a_dgamma;
+    f.a_dbeta = a_dbeta;
+    f.a_coef = a_coef;
+    f.fin_part = fin_part;
+    f.fin_nb = fin_nb;
+    f.fin_tot = fin_tot;
+    f.o_dgamma = o_dgamma;
+    f.o_dbeta = o_dbeta;
+    f.at = act_type;
+}
+
+int cdrl_pwconv_bwd_plan(const cdrl_view* dz, int dz_shuffle, const cdrl_view* a, const cdrl_view* da, int accumulate, int G, int Mg, int N,
+                         int K, const float* a_stats, const float* a_gamma, const float* a_beta, const float* a_dgamma, const float* a_dbeta,
+                         const float* a_coef, const double* fin_part, int fin_nb, const double* fin_tot, const float* o_dgamma,
+                         const float* o_dbeta, int act_type, int32_t* fields, int n_out) {
+    if (bad_act_type(act_type)) return -1;
+    if (!dz || !a || !da || dz_shuffle < 0 || (!fields && n_out > 0)) {
+        cdrl::set_error("cdrl_pwconv_bwd_plan: the dz, a and da views are required (their pointers may be null), shuffle >= 0");
+        return -1;
+    }
+    PwBwdFused f;
+    pwb_fill(f, dz, dz_shuffle, a, da, accumulate, G, Mg, N, K, a_stats, a_gamma, a_beta, const_cast<float*>(a_dgamma), const_cast<float*>(a_dbeta),
+             const_cast<float*>(a_coef), fin_part, fin_nb, const_cast<double*>(fin_tot), const_cast<float*>(o_dgamma), const_cast<float*>(o_dbeta),
+             act_type);
+    const PwbPlan p = pw_bwd_fused_plan(f);
+    if (!p.ok) cdrl::set_error("%s", p.why);
+    const int32_t v[] = {p.ok, p.refusal, p.form, p.kp, p.np, p.bm, p.tiles, p.nbpg, p.wp_ks, p.shuf, p.anorm, p.acc, p.fin, p.coef_needed,
+                         p.lds_bytes, (int32_t)p.qpart_elems, (int32_t)p.dbpart_elems, (int32_t)p.spart_offset};
+    int n = 0;
+    for (int32_t x : v) {
+        if (n < n_out) fields[n] = x;
+        ++n;
+    }
+    return n;
+}
+
+int cdrl_pwconv_bwd_fused_fin(const cdrl_view* dz, int dz_shuffle, int act, const float* y, const float* stats, const float* coef,
+                              const cdrl_view* a, const float* a_stats, const float* a_gamma, const float* a_beta, float* a_dgamma,
+                              float* a_dbeta, float* a_coef, const float* W, const void* W_packed, const cdrl_view* da, int accumulate,
+                              float* dW, float* db, float* qpart, double* dbpart, const double* fin_part, int fin_nb, double* fin_tot,
+                              float* o_dgamma, float* o_dbeta, int G, int Mg, int N, int K, int act_type, void* stream) {
+    const char* fn = "cdrl_pwconv_bwd_fused_fin";
+    if (bad_act_type(act_type)) return -1;
+    if (G < 1 || Mg < 1 || N < 1 || K < 1 || dz_shuffle < 0) {
+        cdrl::set_error("%s: bad shape G %d Mg %d N %d K %d, shuffle %d", fn, G, Mg, N, K, dz_shuffle);
+        return -1;
+    }
+    if (!view_ok(fn, "dz", dz, N, dz_shuffle) || !view_ok(fn, "a", a, K, 0) || !view_ok(fn, "da", da, K, 0)) return -1;
+    // (coef: read only without finalize-on-load -- the plan's coef_needed)
+    if (!y || !stats || (!coef && !fin_part) || !W || !W_packed || !dW || !db || !qpart || !dbpart) {
+        cdrl::set_error("%s: null argument", fn);
+        return -1;
+    }
+    PwBwdFused f;
+    pwb_fill(f, dz, dz_shuffle, a, da, accumulate, G, Mg, N, K, a_stats, a_gamma, a_beta, a_dgamma, a_dbeta, a_coef, fin_part, fin_nb, fin_tot,
+             o_dgamma, o_dbeta, act_type);
+    f.act = act;
+    f.y = y;
+    f.stats = stats;
+    f.coef = coef;
+    f.W = W;
+    f.Wp = W_packed;
+    f.dW = dW;
+    f.db = db;
+    f.qpart = qpart;
+    f.dbpart = dbpart;
+    CDRL_TRY(pw_bwd_fused(f, S(stream)));
+    return pw_bwd_fused_reduce(f, S(stream));
+}
+
 int cdrl_bn_act_gap_fwd(const float* y, const float* stats, float* out, int G, int frames_per_group, int P, int C, int relu6,
                         int act_type, void* stream) {
     if (bad_act_type(act_type)) return -1;

@@ -309,6 +309,32 @@ struct PwBwdFused {
     float* o_dgamma = nullptr;
     float* o_dbeta = nullptr;
 };
+// What pw_bwd_fused / pw_bwd_fused_reduce launch for a call, and why they refuse one (pw_bwd_fused_plan: the launchers, the size queries
+// below and cdrl_pwconv_bwd_plan all take their numbers from it; nothing launches for a call it refuses).
+enum PwbRefusal {
+    PWB_OK = 0,
+    PWB_REFUSE_SHAPE = 1,       // K or N odd, outside 8..128, or padded 128 -> 64; G or Mg < 1
+    PWB_REFUSE_ALIGN = 2,       // odd leading dimension / channel offset, pointer not 8-byte aligned
+    PWB_REFUSE_PADDING = 3,     // bf16 storage: K and N padded differently
+    PWB_REFUSE_2GB = 4,         // an operand of 2 GB or more (32-bit buffer offsets)
+    PWB_REFUSE_GROUPS = 5,      // G > 8 (the reduce kernel's slots)
+    PWB_REFUSE_FIN = 6,         // finalize-on-load under bf16 storage, without fin_tot / fin_nb, or without o_dgamma / o_dbeta
+    PWB_REFUSE_ANORM = 7,       // a_stats without gamma / beta or the dgamma / dbeta / coef outputs
+};
+struct PwbPlan {
+    int ok, refusal;
+    int form;                   // 0: float32 tensors (pwb_kernel), 1: bf16 storage (pwb16_kernel)
+    int kp, np, bm;             // padded input / output channels, rows per tile
+    int tiles, nbpg;            // tiles per group, workgroups (= partial tiles) per group
+    int wp_ks;                  // K = 16 steps per plane of the packed W^T
+    int shuf, anorm, acc, fin;  // the instantiation's template flags; fin: finalize-on-load (a kernel argument)
+    int coef_needed;            // 0 with fin: k1 comes from the statistics block, k2 / k3 from fin_part -- `coef` is never read
+    int lds_bytes;              // dynamic LDS of the main kernel
+    int64_t qpart_elems, dbpart_elems;      // workspace sizes in floats / doubles
+    int64_t spart_offset;       // doubles into dbpart where the directly accumulated BatchNorm sums start (bf16 storage + a_stats), else 0
+    char why[192];              // the refusal in words
+};
+PwbPlan pw_bwd_fused_plan(const PwBwdFused& f);
 bool pw_bwd_fused_supported(View dz, View a, View da, int N, int K, int at = 0);
 int pw_bwd_fused_nbpg(int G, int Mg, int N, int K, int at = 0);
 int64_t pw_bwd_fused_qpart_elems(int G, int Mg, int N, int K, int at = 0);

@@ -19,6 +19,7 @@
 //     sum_r da[r, k] xhat = sum_n W[k, n] Q_g[k, n]                      the EPI_BNRED epilogue of gemm_pw.hip, for free)
 // Partials: one [KP][NP] float tile + [NP] doubles per workgroup, combined in fixed order by pwb_reduce_kernel (bit-wise
 // reproducible, no atomics).
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "colreduce.h"
@@ -1032,37 +1033,103 @@ __global__ void __launch_bounds__(128 * PWB_RS) pwb_reduce_kernel(PwbReduceArgs 
 // ------------------------------------------------------------------------------------------
 static inline int pwb_pad(int c) { return c <= 64 ? 64 : 128; }
 
-bool pw_bwd_fused_supported(View dz, View a, View da, int N, int K, int at) {
-    if (N > 128 || K > 128 || N < 8 || K < 8 || (N & 1) || (K & 1)) return false;
-    if (at && pwb_pad(N) != pwb_pad(K)) return false;          // bf16-storage form: equal paddings only
-    if (pwb_pad(N) != pwb_pad(K) && !(pwb_pad(K) == 64 && pwb_pad(N) == 128)) return false;      // 64/64, 128/128, 64 -> 128
-    auto ok = [](View v) { return (v.ld % 2 == 0) && (v.coff % 2 == 0) && ((reinterpret_cast<uintptr_t>(v.p) & 7) == 0); };
-    return ok(a) && ok(da) && (dz.ld % 2 == 0) && ((reinterpret_cast<uintptr_t>(dz.p) & 7) == 0);
-}
-
-int pw_bwd_fused_nbpg(int G, int Mg, int N, int K, int at) {
-    const int bm = (pwb_pad(K) == 128 || pwb_pad(N) == 128) ? 32 : 64;
-    const int tiles = cdiv(Mg, bm);
+// The ONE place the host decides anything about this family: padding, tile height, workgroups per group, the K steps of the weight
+// pack, LDS bytes, workspace sizes -- and every refusal.  pw_bwd_fused / pw_bwd_fused_reduce launch what it says, the size queries
+// return its numbers, cdrl_pwconv_bwd_plan reports it.  Looks at numbers and at whether pointers are null; reads no memory.
+PwbPlan pw_bwd_fused_plan(const PwBwdFused& f) {
+    PwbPlan p{};
+    const int N = f.N, K = f.K, G = f.G, Mg = f.Mg, at = f.at ? 1 : 0;
+    auto refuse = [&p](int code, const char* fmt, auto... args) -> PwbPlan {
+        p.ok = 0;
+        p.refusal = code;
+        snprintf(p.why, sizeof(p.why), fmt, args...);
+        return p;
+    };
+    p.form = at;
+    p.shuf = f.dz_shuffle != 0;
+    p.anorm = f.a_stats != nullptr;
+    p.acc = f.accumulate != 0;
+    p.fin = f.fin_part != nullptr;
+    p.coef_needed = !p.fin;
+    if (N > 128 || K > 128 || N < 8 || K < 8 || (N & 1) || (K & 1) || G < 1 || Mg < 1)
+        return refuse(PWB_REFUSE_SHAPE, "pw_bwd_fused: unsupported shape N=%d K=%d G=%d Mg=%d (even channel counts in 8..128)", N, K, G, Mg);
+    p.kp = pwb_pad(K);
+    p.np = pwb_pad(N);
+    p.bm = (p.kp == 128 || p.np == 128) ? 32 : 64;
+    p.tiles = cdiv(Mg, p.bm);
+    p.wp_ks = pw_x3_ksteps(N);
+    if (G > 8) return refuse(PWB_REFUSE_GROUPS, "pw_bwd_fused: more than 8 groups (G=%d)", G);
     // resident workgroups: one per CU (float32: 87 KB of LDS); bf16 storage (32 KB) fits two, taken while a workgroup still gets >= 6 tiles
     int nb = 256 / G;
-    if (at && tiles >= 6 * (512 / G)) nb = 512 / G;
+    if (at && p.tiles >= 6 * (512 / G)) nb = 512 / G;
     if (nb < 1) nb = 1;
-    return nb > tiles ? tiles : nb;
+    p.nbpg = nb > p.tiles ? p.tiles : nb;
+    p.qpart_elems = (int64_t)G * p.nbpg * p.kp * p.np;
+    // (bf16 storage: [column sums of dy | (sum da, sum da xhat)] -- three rows of NP == KP doubles per workgroup)
+    p.dbpart_elems = (int64_t)G * p.nbpg * p.np * (at ? 3 : 1);
+    p.spart_offset = (at && p.anorm) ? (int64_t)G * p.nbpg * p.np : 0;
+    if (at) p.lds_bytes = (p.bm * (p.np + 8) + 2 * p.np * (p.bm + 8)) * 2 + 7 * p.np * (int)sizeof(float) + (p.np / 16) * 2 * 128 * 8 * 2;
+    else p.lds_bytes = (3 * p.bm * (p.np + 8) + 3 * (p.np + p.kp) * (p.bm + 8)) * 2 + 7 * p.np * (int)sizeof(float);
+    if (at && p.np != p.kp)
+        return refuse(PWB_REFUSE_PADDING, "pw_bwd_fused: the bf16-storage form is instantiated for equal paddings only (N=%d K=%d)", N, K);
+    if (p.np != p.kp && !(p.kp == 64 && p.np == 128))
+        return refuse(PWB_REFUSE_SHAPE, "pw_bwd_fused: unsupported shape N=%d K=%d (paddings 64/64, 128/128, 64 -> 128)", N, K);
+    auto al = [](View v) { return (v.ld % 2 == 0) && (v.coff % 2 == 0) && ((reinterpret_cast<uintptr_t>(v.p) & 7) == 0); };
+    if (!al(f.a) || !al(f.da) || (f.dz.ld % 2 != 0) || (reinterpret_cast<uintptr_t>(f.dz.p) & 7) != 0 || (at && (f.dz.coff & 1)))
+        return refuse(PWB_REFUSE_ALIGN, "pw_bwd_fused: unsupported alignment N=%d K=%d (even leading dimensions / channel offsets, 8-byte aligned pointers)", N, K);
+    const int64_t Mtot = (int64_t)G * Mg, lim = (int64_t)1 << 31;
+    if (Mtot * f.dz.ld * 4 >= lim || Mtot * f.a.ld * 4 >= lim || Mtot * N * 4 >= lim || Mtot * f.da.ld * 4 >= lim)
+        return refuse(PWB_REFUSE_2GB, "pw_bwd_fused: operand of 2 GB or more (%lld rows)", (long long)Mtot);
+    if (p.fin && (at || !f.fin_tot || f.fin_nb <= 0))
+        return refuse(PWB_REFUSE_FIN, "pw_bwd_fused: finalize-on-load needs the float32 form, fin_tot and fin_nb (fin_nb=%d)", f.fin_nb);
+    if (p.fin && (!f.o_dgamma || !f.o_dbeta))
+        return refuse(PWB_REFUSE_FIN, "pw_bwd_fused: finalize-on-load needs the dgamma / dbeta outputs of the BatchNorm behind the conv (N=%d)", N);
+    if (p.anorm && (!f.a_gamma || !f.a_beta || !f.a_dgamma || !f.a_dbeta || !f.a_coef))
+        return refuse(PWB_REFUSE_ANORM, "pw_bwd_fused: normalised input needs gamma / beta and the dgamma / dbeta / coef outputs (K=%d)", K);
+    p.ok = 1;
+    return p;
 }
 
-int64_t pw_bwd_fused_qpart_elems(int G, int Mg, int N, int K, int at) {
-    return (int64_t)G * pw_bwd_fused_nbpg(G, Mg, N, K, at) * pwb_pad(K) * pwb_pad(N);
+// the queries the engine sizes its scratch with and picks its backward form by: the same plan, for dense views of this shape
+static PwbPlan pwb_shape_plan(View dz, View a, View da, int G, int Mg, int N, int K, int at) {
+    PwBwdFused f;
+    f.dz = dz;
+    f.a = a;
+    f.da = da;
+    f.G = G;
+    f.Mg = Mg;
+    f.N = N;
+    f.K = K;
+    f.at = at;
+    return pw_bwd_fused_plan(f);
 }
 
-// (bf16 storage: [column sums of dy | (sum da, sum da xhat)] -- three rows of NP == KP doubles per workgroup)
-int64_t pw_bwd_fused_dbpart_elems(int G, int Mg, int N, int K, int at) {
-    return (int64_t)G * pw_bwd_fused_nbpg(G, Mg, N, K, at) * pwb_pad(N) * (at ? 3 : 1);
+bool pw_bwd_fused_supported(View dz, View a, View da, int N, int K, int at) {
+    // (one row of one group: the shape, the paddings and the alignment decide; the caller bounds G, a 2 GB operand is refused at the launch)
+    return pwb_shape_plan(dz, a, da, 1, 1, N, K, at).ok != 0;
+}
+
+static PwbPlan pwb_dense_plan(int G, int Mg, int N, int K, int at) {
+    return pwb_shape_plan(make_view(nullptr, 2), make_view(nullptr, 2), make_view(nullptr, 2), G, Mg, N, K, at);
+}
+
+int pw_bwd_fused_nbpg(int G, int Mg, int N, int K, int at) { return pwb_dense_plan(G, Mg, N, K, at).nbpg; }
+
+int64_t pw_bwd_fused_qpart_elems(int G, int Mg, int N, int K, int at) { return pwb_dense_plan(G, Mg, N, K, at).qpart_elems; }
+
+int64_t pw_bwd_fused_dbpart_elems(int G, int Mg, int N, int K, int at) { return pwb_dense_plan(G, Mg, N, K, at).dbpart_elems; }
+
+// (the plan's LDS figure is the launch's: an instantiation whose layout disagrees with it is a host bug, refused instead of launched)
+static int pwb_lds_mismatch(const PwbPlan& p, size_t lds) {
+    set_error("pw_bwd_fused: the plan's %d bytes of LDS are not the kernel's %d (kp %d np %d form %d)", p.lds_bytes, (int)lds, p.kp, p.np, p.form);
+    return -1;
 }
 
 template <int KP, int NP, bool SHUF, bool ANORM, bool ACC>
-static int pwb_launch(const PwbArgs& a, hipStream_t st) {
+static int pwb_launch(const PwbArgs& a, const PwbPlan& p, hipStream_t st) {
     constexpr int BM = (KP == 128 || NP == 128) ? 32 : 64;
     constexpr size_t lds = (size_t)(3 * BM * (NP + 8) + 3 * (NP + KP) * (BM + 8)) * 2 + (size_t)7 * NP * sizeof(float);
+    if ((size_t)p.lds_bytes != lds || p.bm != BM) return pwb_lds_mismatch(p, lds);
     auto kern = pwb_kernel<KP, NP, SHUF, ANORM, ACC>;
     static LdsAttrOnce attr;
     if (attr.need()) {
@@ -1075,9 +1142,10 @@ static int pwb_launch(const PwbArgs& a, hipStream_t st) {
 }
 
 template <int P, bool SHUF, bool ANORM, bool ACC>
-static int pwb16_launch(const PwbArgs& a, hipStream_t st) {
+static int pwb16_launch(const PwbArgs& a, const PwbPlan& p, hipStream_t st) {
     constexpr int BM = P == 128 ? 32 : 64;
     constexpr size_t lds = (size_t)(BM * (P + 8) + 2 * P * (BM + 8)) * 2 + (size_t)7 * P * sizeof(float) + (size_t)(P / 16) * 2 * 128 * 8 * 2;
+    if ((size_t)p.lds_bytes != lds || p.bm != BM) return pwb_lds_mismatch(p, lds);
     auto kern = pwb16_kernel<P, P, SHUF, ANORM, ACC>;
     static LdsAttrOnce attr;
     if (attr.need() && lds >= 64 * 1024) {
@@ -1090,34 +1158,25 @@ static int pwb16_launch(const PwbArgs& a, hipStream_t st) {
 }
 
 template <int P, bool SHUF>
-static int pwb16_launch2(const PwbArgs& a, bool anorm, bool acc, hipStream_t st) {
-    if (anorm) return acc ? pwb16_launch<P, SHUF, true, true>(a, st) : pwb16_launch<P, SHUF, true, false>(a, st);
-    return acc ? pwb16_launch<P, SHUF, false, true>(a, st) : pwb16_launch<P, SHUF, false, false>(a, st);
+static int pwb16_launch2(const PwbArgs& a, const PwbPlan& p, hipStream_t st) {
+    if (p.anorm) return p.acc ? pwb16_launch<P, SHUF, true, true>(a, p, st) : pwb16_launch<P, SHUF, true, false>(a, p, st);
+    return p.acc ? pwb16_launch<P, SHUF, false, true>(a, p, st) : pwb16_launch<P, SHUF, false, false>(a, p, st);
 }
 
 template <int KP, int NP, bool SHUF>
-static int pwb_launch2(const PwbArgs& a, bool anorm, bool acc, hipStream_t st) {
-    if (anorm) return acc ? pwb_launch<KP, NP, SHUF, true, true>(a, st) : pwb_launch<KP, NP, SHUF, true, false>(a, st);
-    return acc ? pwb_launch<KP, NP, SHUF, false, true>(a, st) : pwb_launch<KP, NP, SHUF, false, false>(a, st);
+static int pwb_launch2(const PwbArgs& a, const PwbPlan& p, hipStream_t st) {
+    if (p.anorm) return p.acc ? pwb_launch<KP, NP, SHUF, true, true>(a, p, st) : pwb_launch<KP, NP, SHUF, true, false>(a, p, st);
+    return p.acc ? pwb_launch<KP, NP, SHUF, false, true>(a, p, st) : pwb_launch<KP, NP, SHUF, false, false>(a, p, st);
 }
 
 int pw_bwd_fused(const PwBwdFused& f, hipStream_t st) {
-    if (!pw_bwd_fused_supported(f.dz, f.a, f.da, f.N, f.K, f.at) || !f.Wp) {
-        set_error("pw_bwd_fused: unsupported shape / alignment N=%d K=%d", f.N, f.K);
+    const PwbPlan p = pw_bwd_fused_plan(f);
+    if (!p.ok) {
+        set_error("%s", p.why);
         return -1;
     }
-    const int64_t Mtot = (int64_t)f.G * f.Mg;
-    if (f.at && ((f.dz.coff | f.dz.ld | f.a.coff | f.a.ld | f.da.coff | f.da.ld) & 1)) {
-        set_error("pw_bwd_fused: bf16 storage needs even leading dimensions / channel offsets");
-        return -1;
-    }
-    if (Mtot * f.dz.ld * 4 >= ((int64_t)1 << 31) || Mtot * f.a.ld * 4 >= ((int64_t)1 << 31) || Mtot * f.N * 4 >= ((int64_t)1 << 31) ||
-        Mtot * f.da.ld * 4 >= ((int64_t)1 << 31)) {
-        set_error("pw_bwd_fused: operand of 2 GB or more");
-        return -1;
-    }
-    if (f.G > 8) {
-        set_error("pw_bwd_fused: more than 8 groups");
+    if (!f.Wp) {
+        set_error("pw_bwd_fused: no packed weights N=%d K=%d", f.N, f.K);
         return -1;
     }
     PwbArgs a;
@@ -1130,7 +1189,7 @@ int pw_bwd_fused(const PwBwdFused& f, hipStream_t st) {
     a.a = f.a;
     a.a_stats = f.a_stats;
     a.Wp = reinterpret_cast<const __bf16*>(f.Wp);
-    a.wp_ks = pw_x3_ksteps(f.N);
+    a.wp_ks = p.wp_ks;
     a.da = f.da;
     a.qpart = f.qpart;
     a.dbpart = f.dbpart;
@@ -1138,33 +1197,29 @@ int pw_bwd_fused(const PwBwdFused& f, hipStream_t st) {
     a.K = f.K;
     a.G = f.G;
     a.Mg = f.Mg;
-    a.nbpg = pw_bwd_fused_nbpg(f.G, f.Mg, f.N, f.K, f.at);
-    a.at = f.at;
-    a.fin_part = f.at ? nullptr : f.fin_part;
+    a.nbpg = p.nbpg;
+    a.at = p.form;
+    a.fin_part = p.fin ? f.fin_part : nullptr;
     a.fin_tot = f.fin_tot;
     a.fin_nb = f.fin_nb;
-    if (f.fin_part && (f.at || !f.fin_tot || f.fin_nb <= 0)) {
-        set_error("pw_bwd_fused: finalize-on-load needs the float32 form, fin_tot and fin_nb");
-        return -1;
-    }
-    a.spart = (f.at && f.a_stats) ? f.dbpart + (int64_t)f.G * a.nbpg * pwb_pad(f.N) : nullptr;
+    a.spart = p.spart_offset ? f.dbpart + p.spart_offset : nullptr;
     static const int dbg = cdrl_getenv("CDRL_DIAG_PWB") ? atoi(cdrl_getenv("CDRL_DIAG_PWB")) : 0;
     a.dbg = dbg;
-    const bool anorm = f.a_stats != nullptr, acc = f.accumulate != 0, shuf = f.dz_shuffle != 0;
-    if (f.at && pwb_pad(f.K) != pwb_pad(f.N)) {
-        set_error("pw_bwd_fused: the bf16-storage form is instantiated for equal paddings only (N=%d K=%d)", f.N, f.K);
-        return -1;
+    if (p.form == 1) {
+        if (p.kp == 128) return p.shuf ? pwb16_launch2<128, true>(a, p, st) : pwb16_launch2<128, false>(a, p, st);
+        return p.shuf ? pwb16_launch2<64, true>(a, p, st) : pwb16_launch2<64, false>(a, p, st);
     }
-    if (f.at) {
-        if (pwb_pad(f.K) == 128) return shuf ? pwb16_launch2<128, true>(a, anorm, acc, st) : pwb16_launch2<128, false>(a, anorm, acc, st);
-        return shuf ? pwb16_launch2<64, true>(a, anorm, acc, st) : pwb16_launch2<64, false>(a, anorm, acc, st);
-    }
-    if (pwb_pad(f.K) == 128) return shuf ? pwb_launch2<128, 128, true>(a, anorm, acc, st) : pwb_launch2<128, 128, false>(a, anorm, acc, st);
-    if (pwb_pad(f.N) == 128) return shuf ? pwb_launch2<64, 128, true>(a, anorm, acc, st) : pwb_launch2<64, 128, false>(a, anorm, acc, st);
-    return shuf ? pwb_launch2<64, 64, true>(a, anorm, acc, st) : pwb_launch2<64, 64, false>(a, anorm, acc, st);
+    if (p.kp == 128) return p.shuf ? pwb_launch2<128, 128, true>(a, p, st) : pwb_launch2<128, 128, false>(a, p, st);
+    if (p.np == 128) return p.shuf ? pwb_launch2<64, 128, true>(a, p, st) : pwb_launch2<64, 128, false>(a, p, st);
+    return p.shuf ? pwb_launch2<64, 64, true>(a, p, st) : pwb_launch2<64, 64, false>(a, p, st);
 }
 
 int pw_bwd_fused_reduce(const PwBwdFused& f, hipStream_t st) {
+    const PwbPlan p = pw_bwd_fused_plan(f);
+    if (!p.ok) {
+        set_error("%s", p.why);
+        return -1;
+    }
     PwbReduceArgs r;
     r.qpart = f.qpart;
     r.dbpart = f.dbpart;
@@ -1179,24 +1234,16 @@ int pw_bwd_fused_reduce(const PwBwdFused& f, hipStream_t st) {
     r.a_coef = f.a_coef;
     r.N = f.N;
     r.K = f.K;
-    r.KP = pwb_pad(f.K);
-    r.NP = pwb_pad(f.N);
+    r.KP = p.kp;
+    r.NP = p.np;
     r.G = f.G;
     r.Mg = f.Mg;
-    r.nbpg = pw_bwd_fused_nbpg(f.G, f.Mg, f.N, f.K, f.at);
-    r.wbf = f.at;
-    r.fin_tot = (f.fin_part && !f.at) ? f.fin_tot : nullptr;
+    r.nbpg = p.nbpg;
+    r.wbf = p.form;
+    r.fin_tot = p.fin ? f.fin_tot : nullptr;
     r.o_dgamma = f.o_dgamma;
     r.o_dbeta = f.o_dbeta;
-    if (r.fin_tot && (!f.o_dgamma || !f.o_dbeta)) {
-        set_error("pw_bwd_fused_reduce: finalize-on-load needs the dgamma / dbeta outputs of the BatchNorm behind the conv");
-        return -1;
-    }
-    r.spart = (f.at && f.a_stats) ? f.dbpart + (int64_t)f.G * r.nbpg * pwb_pad(f.N) : nullptr;
-    if (f.a_stats && (!f.a_gamma || !f.a_beta || !f.a_dgamma || !f.a_dbeta || !f.a_coef)) {
-        set_error("pw_bwd_fused_reduce: normalised input needs gamma / beta and the dgamma / dbeta / coef outputs");
-        return -1;
-    }
+    r.spart = p.spart_offset ? f.dbpart + p.spart_offset : nullptr;
     hipLaunchKernelGGL(pwb_reduce_kernel, dim3(f.K), dim3(128 * PWB_RS), 0, st, r);
     CDRL_LAUNCH_CHECK();
     return 0;

@@ -599,6 +599,35 @@ int cdrl_bn_bwd(const cdrl_view* dout, int shuffle_ctot, const cdrl_view* y, int
 int cdrl_bn_plan(const cdrl_view* y, const cdrl_view* out, const cdrl_view* dout, int shuffle_ctot, int G, int Mg, int C, int has_stats,
                  int relu6, const cdrl_view* pass_src, const cdrl_view* pass_dst, const cdrl_view* pass_gsrc, const cdrl_view* pass_gdst,
                  const float* dy, int bcast_rows, int act_type, int32_t* fields, int n_out);
+/* ---- The fused 1x1-conv backward (cdrl_pwconv_bwd_fused above) with the argument forms the engine runs it with.
+ * cdrl_pwconv_bwd_plan: what the launchers dispatch on for these arguments (they call the same host function) -- launches nothing, reads
+ * no memory: the views' pointers count for their alignment, the other pointers for being null or not (any non-null value probes).
+ * Writes min(n_out, 18) int32 fields and returns 18 (-1: no view struct, bad act_type):
+ *    0 ok       1: the call would run; 0: refused, field 1 says why and cdrl_last_error() holds the sentence
+ *    1 refusal  1 shape (K, N even in 8..128, not padded 128 -> 64; G, Mg >= 1), 2 parity / alignment (even ld / coff, 8-byte aligned
+ *               pointers), 3 bf16 storage with K and N padded differently, 4 an operand of 2 GB or more, 5 G > 8, 6 finalize-on-load
+ *               under bf16 storage / fin_nb < 1 / without fin_tot / without o_dgamma, o_dbeta, 7 a_stats without gamma, beta or an output
+ *    2 form     0 float32 tensors, 1 bf16 storage
+ *    3 kp  4 np padded input / output channels (64 | 128)     5 bm rows per tile (64 for 64/64, else 32)     6 tiles = ceil(Mg / bm)
+ *    7 nbpg     workgroups (partial tiles) per group: min(tiles, 256 / G), or 512 / G under bf16 storage once tiles >= 6 * (512 / G)
+ *    8 wp_ks    K = 16 steps per plane of W_packed (2 for N <= 32, 4 for N <= 64, 8)
+ *    9 shuf  10 anorm  11 acc  the kernel instantiation      12 fin finalize-on-load     13 coef_needed (0 with fin: coef may be NULL)
+ *   14 lds_bytes  15 qpart floats  16 dbpart doubles  17 spart_offset: doubles into dbpart where the directly accumulated BatchNorm sums
+ *               of the bf16-storage form with a_stats start (0 otherwise) */
+int cdrl_pwconv_bwd_plan(const cdrl_view* dz, int dz_shuffle, const cdrl_view* a, const cdrl_view* da, int accumulate, int G, int Mg, int N,
+                         int K, const float* a_stats, const float* a_gamma, const float* a_beta, const float* a_dgamma, const float* a_dbeta,
+                         const float* a_coef, const double* fin_part, int fin_nb, const double* fin_tot, const float* o_dgamma,
+                         const float* o_dbeta, int act_type, int32_t* fields, int n_out);
+/* cdrl_pwconv_bwd_fused with dz, a, da as views, plus FINALIZE-ON-LOAD (float32 tensors; the engine's default): fin_part != NULL holds the
+ * [G][fin_nb][2][N] backward sums (sum mask dz, sum mask dz xhat(y)) of the BatchNorm behind the conv; the kernel folds them into
+ * k2 = mean, k3 = mean itself, takes k1 from the scale row of `stats` (coef may be NULL), leaves the group totals in fin_tot [G][2][N]
+ * doubles, and the reduce writes that BatchNorm's o_dgamma / o_dbeta [N].  Every view must keep its channels inside its rows (dz: through
+ * the shuffle when dz_shuffle != 0); a refused call launches nothing. */
+int cdrl_pwconv_bwd_fused_fin(const cdrl_view* dz, int dz_shuffle, int act, const float* y, const float* stats, const float* coef,
+                              const cdrl_view* a, const float* a_stats, const float* a_gamma, const float* a_beta, float* a_dgamma,
+                              float* a_dbeta, float* a_coef, const float* W, const void* W_packed, const cdrl_view* da, int accumulate,
+                              float* dW, float* db, float* qpart, double* dbpart, const double* fin_part, int fin_nb, double* fin_tot,
+                              float* o_dgamma, float* o_dbeta, int G, int Mg, int N, int K, int act_type, void* stream);
 /* out[n][c] (float32) = mean over the P rows of frame n of [relu6](scale * y + shift); y dense [G*frames_per_group*P][C] */
 int cdrl_bn_act_gap_fwd(const float* y, const float* stats, float* out, int G, int frames_per_group, int P, int C, int relu6,
                         int act_type, void* stream);
