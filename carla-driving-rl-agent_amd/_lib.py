@@ -142,6 +142,8 @@ PROTOTYPES = {
     'cdrl_learner_named_buffer': (_i, [_L, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(_i64)]),
     'cdrl_learner_check_guards': (_i, [_L, _fp, C.POINTER(_i64), C.POINTER(_i64)]),
     'cdrl_gae_returns': (_i, [_fp, _fp, _i, _d, _d, _f, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'cdrl_gae_returns_segments': (_i, [_fp, _fp, _fp, _i, _i, _d, _d, _f, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'cdrl_gae_segments_scratch_doubles': (_i64, [_i, _i]),
     'cdrl_gather_rows': (_i, [_fp, _fp, _fp, _i, _i64, _fp]),
     'cdrl_gemm_nn': (_i, [_fp, _i, _i, _fp, _i, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp]),
     'cdrl_gemm_tn_workspace_elems': (_i64, [_i, _i, _i]),

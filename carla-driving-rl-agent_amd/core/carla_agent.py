@@ -251,10 +251,16 @@ class CARLAgent(PPOAgent):
         self._shard = shard
         return super().collect(shard, *args, **kwargs)
 
-    def trajectory_stored(self, env_index, rollout):
+    def trajectory_stored(self, env_index, rollout, segment=None):
         # several environments: remember which slice of WHICH environment's info buffer belongs to the rows just appended
         if len(self._shard) > 1:
             have = len(self._shard[env_index].info_buffer['speed'])
+            if segment is not None:
+                # auto-reset: one of several trajectories of the environment -- it starts `env_steps_at_start` entries (environment
+                # steps, repeated actions included) behind what the buffer held before this rollout
+                start, stop, _, env_steps_at_start = segment
+                self._info_segments.append((env_index, have - rollout.env_steps[env_index] + env_steps_at_start, stop - start))
+                return
             self._info_segments.append((env_index, have - rollout.env_steps[env_index], rollout.length[env_index]))
 
     def _info(self, n):

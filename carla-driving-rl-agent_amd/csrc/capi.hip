@@ -524,6 +524,34 @@ int cdrl_gae_returns(const float* rewards, const float* values_be, int N, double
     return gae_returns(rewards, values_be, N, gamma, lambda, scale, returns, returns_be, adv_raw, adv, scratch, S(stream));
 }
 
+int64_t cdrl_gae_segments_scratch_doubles(int N, int nseg) {
+    if (nseg < 1 || N < nseg) return 0;
+    return 2 * ((int64_t)N + nseg);
+}
+
+int cdrl_gae_returns_segments(const float* rewards, const float* values_be, const int32_t* seg_off, int nseg, int N, double gamma,
+                              double lambda, float scale, float* returns, float* returns_be, float* adv_raw, float* adv,
+                              double* scratch, void* stream) {
+    if (!rewards || !values_be || !seg_off || !returns || !returns_be || !adv_raw || !adv || !scratch) {
+        cdrl::set_error("cdrl_gae_returns_segments: null argument");
+        return -1;
+    }
+    if (nseg < 1) {
+        cdrl::set_error("cdrl_gae_returns_segments: S = %d segments (at least one)", nseg);
+        return -1;
+    }
+    if (N < nseg) {
+        cdrl::set_error("cdrl_gae_returns_segments: N = %d rows for S = %d segments (every segment holds at least one row)", N, nseg);
+        return -1;
+    }
+    if ((int64_t)N + nseg > INT32_MAX) {
+        cdrl::set_error("cdrl_gae_returns_segments: N + S = %lld padded entries exceed the 32-bit row offsets", (long long)N + nseg);
+        return -1;
+    }
+    return gae_returns_segments(rewards, values_be, seg_off, nseg, N, gamma, lambda, scale, returns, returns_be, adv_raw, adv, scratch,
+                                S(stream));
+}
+
 int64_t cdrl_pwconv_x3_packed_bytes(int K) { return pw_x3_packed_bytes(K); }
 int64_t cdrl_pwconv_x3_packed_bytes_n(int K, int N) { return pw_x3_packed_bytes_n(K, N); }
 int cdrl_pwconv_x3_partial_rows(int G, int Mg, int N, int K) { return pw_x3_partial_rows(G, Mg, N, K); }

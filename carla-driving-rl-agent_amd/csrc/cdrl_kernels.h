@@ -533,5 +533,10 @@ int stats_reset_ring(float* ring, hipStream_t st);
 // rewards [N+1] (bootstrap appended), values_be [N+1][2] -> returns_be [N][2], returns [N], adv_raw [N], adv [N]
 int gae_returns(const float* rewards, const float* values_be, int N, double gamma, double lambda, float scale,
                 float* returns, float* returns_be, float* adv_raw, float* adv, double* scratch, hipStream_t st);
+// S trajectories (N rows in all) in one launch, one workgroup each: seg_off [S+1] (device) row offsets; rewards [N+S] / values_be [N+S][2]
+// padded with every segment's bootstrap entry; packed outputs [N]; scratch 2*(N+S) doubles
+int gae_returns_segments(const float* rewards, const float* values_be, const int32_t* seg_off, int S, int N, double gamma,
+                         double lambda, float scale, float* returns, float* returns_be, float* adv_raw, float* adv, double* scratch,
+                         hipStream_t st);
 
 }  // namespace cdrl

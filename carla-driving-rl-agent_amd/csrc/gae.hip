@@ -36,11 +36,14 @@ __device__ __forceinline__ double gae_scan(double* a, int n, double d, double ac
     return acc;
 }
 
-__global__ void __launch_bounds__(256) gae_kernel(const float* __restrict__ rewards, const float* __restrict__ values_be,
-                                                  int N, double gamma, double lambda, float scale,
-                                                  float* __restrict__ returns, float* __restrict__ returns_be,
-                                                  float* __restrict__ adv_raw, float* __restrict__ adv,
-                                                  double* __restrict__ scratch) {
+// One trajectory of N steps by one 256-thread workgroup: rewards [N + 1] / values_be [N + 1][2] incl. the bootstrap entry, outputs [N],
+// scratch 2 * (N + 1) doubles.  The body of both kernels below, so that a trajectory gets the same arithmetic in the same order
+// whether it is launched alone or as one segment of many.  Every barrier is block-uniform: all loop bounds derive from N.
+__device__ __forceinline__ void gae_trajectory(const float* __restrict__ rewards, const float* __restrict__ values_be,
+                                               int N, double gamma, double lambda, float scale,
+                                               float* __restrict__ returns, float* __restrict__ returns_be,
+                                               float* __restrict__ adv_raw, float* __restrict__ adv,
+                                               double* __restrict__ scratch) {
     __shared__ float smax[256], smin[256];
     const int tid = threadIdx.x;
     double* delta = scratch;             // [N]
@@ -120,11 +123,48 @@ __global__ void __launch_bounds__(256) gae_kernel(const float* __restrict__ rewa
     }
 }
 
+__global__ void __launch_bounds__(256) gae_kernel(const float* __restrict__ rewards, const float* __restrict__ values_be,
+                                                  int N, double gamma, double lambda, float scale,
+                                                  float* __restrict__ returns, float* __restrict__ returns_be,
+                                                  float* __restrict__ adv_raw, float* __restrict__ adv,
+                                                  double* __restrict__ scratch) {
+    gae_trajectory(rewards, values_be, N, gamma, lambda, scale, returns, returns_be, adv_raw, adv, scratch);
+}
+
+// S trajectories in one launch, workgroup s = segment s: rows [seg_off[s], seg_off[s + 1]) of the packed outputs, entries
+// [seg_off[s] + s, seg_off[s + 1] + s] of the inputs (every segment carries its own bootstrap entry), 2 * (n_s + 1) doubles of scratch
+// from 2 * (seg_off[s] + s).  Scan carries and the sp-norm's max / min are per segment.  A malformed segment (empty, or outside
+// [0, N]) leaves before the first barrier -- the whole block takes the same branch -- and writes nothing; with 0 <= seg_off[s] <
+// seg_off[s + 1] <= N every access stays inside the N + S inputs, the N outputs and the 2 * (N + S) doubles of scratch.
+__global__ void __launch_bounds__(256) gae_segments_kernel(const float* __restrict__ rewards, const float* __restrict__ values_be,
+                                                           const int32_t* __restrict__ seg_off, int S, int N,
+                                                           double gamma, double lambda, float scale,
+                                                           float* __restrict__ returns, float* __restrict__ returns_be,
+                                                           float* __restrict__ adv_raw, float* __restrict__ adv,
+                                                           double* __restrict__ scratch) {
+    const int s = blockIdx.x;
+    if (s >= S) return;
+    const int lo = seg_off[s], hi = seg_off[s + 1];
+    if (lo < 0 || hi <= lo || hi > N) return;
+    const int64_t in = (int64_t)lo + s;         // first padded input entry of the segment
+    gae_trajectory(rewards + in, values_be + 2 * in, hi - lo, gamma, lambda, scale, returns + lo, returns_be + 2 * (int64_t)lo,
+                   adv_raw + lo, adv + lo, scratch + 2 * in);
+}
+
 int gae_returns(const float* rewards, const float* values_be, int N, double gamma, double lambda, float scale,
                 float* returns, float* returns_be, float* adv_raw, float* adv, double* scratch, hipStream_t st) {
     if (N <= 0) return 0;
     hipLaunchKernelGGL(gae_kernel, dim3(1), dim3(256), 0, st, rewards, values_be, N, gamma, lambda, scale, returns,
                        returns_be, adv_raw, adv, scratch);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
+int gae_returns_segments(const float* rewards, const float* values_be, const int32_t* seg_off, int S, int N, double gamma,
+                         double lambda, float scale, float* returns, float* returns_be, float* adv_raw, float* adv, double* scratch,
+                         hipStream_t st) {
+    hipLaunchKernelGGL(gae_segments_kernel, dim3(S), dim3(256), 0, st, rewards, values_be, seg_off, S, N, gamma, lambda, scale,
+                       returns, returns_be, adv_raw, adv, scratch);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

@@ -466,3 +466,34 @@ def gae_returns(rewards: torch.Tensor, values_be: torch.Tensor, gamma: float, la
                                     _lib.ptr(returns), _lib.ptr(returns_be), _lib.ptr(adv_raw), _lib.ptr(adv),
                                     _lib.ptr(scratch), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'gae_returns')
     return returns, returns_be, adv_raw, adv
+
+
+def gae_returns_segments(rewards: torch.Tensor, values_be: torch.Tensor, lengths, gamma: float, lambda_: float, scale: float = 2.0):
+    """Device GAE / returns for S trajectories in ONE launch (cdrl_gae_returns_segments), one workgroup per trajectory.
+    `lengths`: host list of the S row counts n_s >= 1 (N = their sum); rewards (N+S,), values_be (N+S, 2): the trajectories one after
+    the other, each followed by its own bootstrap entry.  -> packed returns (N,), returns_be (N, 2), adv_raw (N,), adv (N,), every
+    trajectory's rows bit-identical to `gae_returns` on that trajectory alone.  One host-to-device copy (the row offsets), no
+    device-to-host read."""
+    lengths = [int(n) for n in lengths]
+    S, n = len(lengths), sum(lengths)
+    if S < 1 or min(lengths) < 1:
+        raise ValueError(f'gae_returns_segments: every trajectory needs at least one row (lengths {lengths})')
+    if n + S != rewards.numel() or 2 * (n + S) != values_be.numel():
+        raise ValueError(f'gae_returns_segments: {S} trajectories of {n} rows in all need {n + S} rewards and ({n + S}, 2) values '
+                         f'(one bootstrap entry each), got {rewards.numel()} and {tuple(values_be.shape)}')
+    lib = _lib.load()
+    dev = rewards.device
+    offsets = [0] * (S + 1)
+    for s, k in enumerate(lengths):
+        offsets[s + 1] = offsets[s] + k
+    seg_off = torch.tensor(offsets, dtype=torch.int32, device=dev)
+    returns = torch.empty(n, dtype=torch.float32, device=dev)
+    returns_be = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    adv_raw = torch.empty(n, dtype=torch.float32, device=dev)
+    adv = torch.empty(n, dtype=torch.float32, device=dev)
+    scratch = torch.empty(int(lib.cdrl_gae_segments_scratch_doubles(n, S)), dtype=torch.float64, device=dev)
+    _lib.check(lib.cdrl_gae_returns_segments(_lib.ptr(rewards), _lib.ptr(values_be), _lib.ptr(seg_off), S, n, float(gamma),
+                                             float(lambda_), float(scale), _lib.ptr(returns), _lib.ptr(returns_be), _lib.ptr(adv_raw),
+                                             _lib.ptr(adv), _lib.ptr(scratch), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               'gae_returns_segments')
+    return returns, returns_be, adv_raw, adv

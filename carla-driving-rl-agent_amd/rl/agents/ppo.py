@@ -203,14 +203,18 @@ class PPOAgent(Agent):
         return int(every)
 
     def learn(self, episodes: int, timesteps: int, save_every: Union[bool, str, int] = False,
-              render_every: Union[bool, str, int] = False, close=True, envs: Optional[Sequence] = None):
+              render_every: Union[bool, str, int] = False, close=True, envs: Optional[Sequence] = None, auto_reset=False):
         """The reference's training loop (rl/agents/ppo.py:464-568: roll out up to `timesteps` steps per episode, close the
         trajectory with the bootstrap value, update() every `update_frequency` episodes, then the host side effects) built around
         an ENVIRONMENT SHARD: `envs` (default `[self.env]`, the reference's case) are stepped in lockstep, one batched
         `predict` per step for all of them, their rows stay on the device, and at the end of the episode every environment's
         trajectory is appended to the memory with its own bootstrap value and its own returns / GAE(lambda).  With one environment
-        the sequence of environment, sampler and memory operations is the reference's."""
+        the sequence of environment, sampler and memory operations is the reference's.
+        `auto_reset=True` (opt-in): an environment that reports `done` before `timesteps` is reset on the spot
+        and starts a new trajectory, so every environment records every step, and all trajectories of the rollout are closed by
+        ONE segmented returns / GAE launch (PPOMemory.extend_trajectories) instead of one end_episode each."""
         assert episodes % self.update_frequency == 0
+        mode = dict(auto_reset=True) if auto_reset else {}      # (not passed on otherwise: collect / store overrides keep their signature)
         save_period = self._period(save_every, episodes, end_keyword=True)
         render_period = self._period(render_every, episodes)
         shard = list(envs) if envs is not None else [self.env]
@@ -220,9 +224,9 @@ class PPOAgent(Agent):
                 self.seed_regularization()
                 self.on_episode_start()
                 self.reset()
-                rollout = self.collect(shard, timesteps, render=episode % render_period == 0, episode=episode)
+                rollout = self.collect(shard, timesteps, render=episode % render_period == 0, episode=episode, **mode)
                 updating = episode % self.update_frequency == 0
-                self.store(rollout, timesteps, keep_open=not updating)
+                self.store(rollout, timesteps, keep_open=not updating, **mode)
                 if updating:
                     self.update()
                     self.memory.delete()
@@ -283,9 +287,12 @@ class PPOAgent(Agent):
                 out[key] = torch.as_tensor(np.stack([np.asarray(v, dtype=np.float32) for v in vals], axis=0)).to(self.device)
         return out
 
-    def collect(self, shard: list, timesteps: int, render=False, episode=0) -> 'Rollout':
+    def collect(self, shard: list, timesteps: int, render=False, episode=0, auto_reset=False) -> 'Rollout':
         """One episode of every environment of the shard, in lockstep.  An environment that terminates early keeps its last
-        observation in the batch (its rows are not recorded any more), so the inference engine sees one shape throughout."""
+        observation in the batch (its rows are not recorded any more), so the inference engine sees one shape throughout.
+        `auto_reset`: it is reset instead and goes on recording (collect_auto_reset)."""
+        if auto_reset:
+            return self.collect_auto_reset(shard, timesteps, render=render, episode=episode)
         E = len(shard)
         preprocess_fn = self.preprocess()
         observations = [env.reset() for env in shard]
@@ -324,10 +331,58 @@ class PPOAgent(Agent):
         rollout.final = batch               # the observation behind every environment's last recorded step
         return rollout
 
-    def store(self, rollout: 'Rollout', timesteps: int, keep_open: bool):
+    def collect_auto_reset(self, shard: list, timesteps: int, render=False, episode=0) -> 'Rollout':
+        """`timesteps` steps of every environment of the shard, in lockstep, one batched `predict` per step.  An environment that
+        reports `done` at step t < timesteps has its trajectory closed as terminal, is reset, and starts a new trajectory with the
+        next step; at t == timesteps the open trajectory is closed as terminal (`done`, no reset) or as truncated.  Every
+        environment records every step; `rollout.segments[e]` lists its trajectories."""
+        E = len(shard)
+        preprocess_fn = self.preprocess()
+        observations = [env.reset() for env in shard]
+        rollout = Rollout(E, timesteps, self.device)
+        everyone = list(range(E))
+        trajectory_reward = [0.0] * E
+        t0 = time.time()
+        batch = self.observe(observations, preprocess_fn)
+        for t in range(1, timesteps + 1):
+            if render:
+                for env in shard:
+                    env.render()
+            action, mean, std, log_prob, value = self.predict(batch)
+            rollout.record(batch, action, log_prob, value, everyone)
+            env_actions = np.atleast_2d(self.convert_action(action))
+            rewards = []
+            for e in everyone:
+                reward, done = 0.0, False
+                for _ in range(self.repeat_action):
+                    observations[e], reward, done, _ = shard[e].step(env_actions[e])
+                    rollout.episode_reward[e] += reward
+                    trajectory_reward[e] += reward
+                    rollout.env_steps[e] += 1
+                    if done:
+                        break
+                rollout.rewards[e].append(float(reward))
+                rewards.append(reward)
+                if done or t == timesteps:
+                    start, stop = rollout.close_segment(e, terminal=done)[:2]
+                    print(f'Episode {episode}{f" [env {e}]" if E > 1 else ""} terminated after {stop - start} timesteps '
+                          f'(step {t} of the rollout) in {round(time.time() - t0, 3)}s with reward {round(trajectory_reward[e], 3)}.')
+                    self.log(timestep=stop - start)
+                    trajectory_reward[e] = 0.0
+                    if t < timesteps:
+                        observations[e] = shard[e].reset()
+            self.log(actions=action, rewards=rewards if E > 1 else rewards[0], distribution_mean=mean, distribution_std=std)
+            batch = self.observe(observations, preprocess_fn)
+        rollout.final = batch               # the observation behind every environment's last recorded step
+        return rollout
+
+    def store(self, rollout: 'Rollout', timesteps: int, keep_open: bool, auto_reset=False):
         """Appends every environment's trajectory to the memory: rows, bootstrap value (zero at a terminal state, the value
         head's estimate of the final observation otherwise), returns and GAE(lambda) of THAT trajectory (end_episode).
-        `keep_open`: more rows follow before the next update() (update_frequency > 1) -- the bootstrap entry is removed again."""
+        `keep_open`: more rows follow before the next update() (update_frequency > 1) -- the bootstrap entry is removed again.
+        `auto_reset`: the rollout holds several trajectories per environment; they are closed together (store_segments)."""
+        if auto_reset:
+            return self.store_segments(rollout, timesteps, keep_open)
         E = rollout.envs
         estimate = None
         if not all(rollout.terminal):
@@ -345,8 +400,33 @@ class PPOAgent(Agent):
                 self.memory.drop_bootstrap()
         rollout.blocks = None               # the trajectories were copied into the memory: release the timesteps-long staging blocks
 
-    def trajectory_stored(self, env_index: int, rollout: 'Rollout'):
-        """Hook: environment `env_index`'s trajectory of this rollout now sits at the end of the memory."""
+    def store_segments(self, rollout: 'Rollout', timesteps: int, keep_open: bool):
+        """Appends every trajectory of an auto-reset rollout to the memory, in memory order (Rollout.trajectories): one batched
+        value estimate for the truncated ones, zero bootstrap for the terminal ones, then ONE segmented returns / GAE(lambda) launch
+        for all of them (PPOMemory.extend_trajectories) and the logging of end_episode once per trajectory, in that order."""
+        estimate = None
+        if not all(rollout.terminal):
+            t_last = max(rollout.length)
+            estimate = self.network.predict_last_value(rollout.final, timestep=(t_last + 1) / timesteps, is_terminal=False)
+        pieces, rows, last_values = [], [], []
+        for e, segment, trajectory in rollout.trajectories():
+            pieces.append((e, segment))
+            rows.append(trajectory)
+            last_values.append(self.network.predict_last_value(None, is_terminal=True) if segment[2] else estimate[e:e + 1])
+        last_values = torch.cat([v.to(device=self.device, dtype=torch.float32).reshape(1, 2) for v in last_values], dim=0)
+        scale = self.adv_scale()
+        closed = self.memory.extend_trajectories(rows, last_values, self.gamma, self.lambda_, scale,
+                                                 append=self.update_frequency > 1 or len(rows) > 1)
+        for (e, segment), returns, values, advantages in zip(pieces, *closed):
+            self.log(returns=returns, advantages=advantages, values=values, advantage_scale=self.adv_scale.value)
+            self.trajectory_stored(e, rollout, segment)
+        if keep_open:
+            self.memory.drop_bootstrap()
+        rollout.blocks = None
+
+    def trajectory_stored(self, env_index: int, rollout: 'Rollout', segment=None):
+        """Hook: environment `env_index`'s trajectory of this rollout now sits at the end of the memory.  `segment`: which one of the
+        environment's trajectories (an entry of `rollout.segments[env_index]`) when the rollout was collected with auto-reset."""
 
     def get_memory(self):
         return PPOMemory(state_spec=self.state_spec, num_actions=self.num_actions, device=self.device)
@@ -393,7 +473,10 @@ class PPOAgent(Agent):
 class Rollout:
     """What an environment shard stepped in lockstep leaves behind: (steps, E, ...) device blocks written in place, one per
     state component / action / log-probability / value, plus the host-side bookkeeping per environment (rewards, number of
-    recorded steps, terminal flag).  `trajectory(e)` hands environment e's rows to the memory as contiguous blocks."""
+    recorded steps, terminal flag).  `trajectory(e)` hands environment e's rows to the memory as contiguous blocks.
+    With auto-reset an environment leaves several trajectories: `segments[e]` = [(start_step, stop_step, terminal,
+    env_steps_at_start), ...] in time order, `trajectories()` hands them out in MEMORY ORDER -- environment 0's in time order, then
+    environment 1's, and so on; `length[e]` / `terminal[e]` describe the environment's steps as a whole / its last trajectory."""
 
     def __init__(self, envs: int, timesteps: int, device):
         self.envs, self.timesteps, self.device = envs, timesteps, device
@@ -405,6 +488,8 @@ class Rollout:
         self.episode_reward = [0.0] * envs
         self.final = None
         self.step = 0
+        self.segments = [[] for _ in range(envs)]
+        self._open = [(0, 0)] * envs                        # (first step, environment steps taken before it) of the open trajectory
 
     def record(self, states: dict, action, log_prob, value, running):
         rows = dict(states)
@@ -417,6 +502,25 @@ class Rollout:
         self.step += 1
         for e in running:
             self.length[e] += 1
+
+    def close_segment(self, e: int, terminal: bool):
+        """Environment e's open trajectory ends with the step just recorded; the next recorded step starts a new one."""
+        start, env_steps = self._open[e]
+        segment = (start, self.length[e], bool(terminal), env_steps)
+        assert segment[1] > start, 'a trajectory holds at least one step'
+        self.segments[e].append(segment)
+        self._open[e] = (self.length[e], self.env_steps[e])
+        self.terminal[e] = bool(terminal)
+        return segment
+
+    def trajectories(self):
+        """-> (e, segment, (states, actions, rewards, values, log_probs)) per trajectory, in memory order."""
+        for e in range(self.envs):
+            for segment in self.segments[e]:
+                start, stop = segment[:2]
+                take = lambda k: self.blocks[k][start:stop, e].clone(memory_format=torch.contiguous_format)
+                states = {k: take(k) for k in self.blocks if not k.startswith('/')}
+                yield e, segment, (states, take('/action'), self.rewards[e][start:stop], take('/value'), take('/log_prob'))
 
     def trajectory(self, e: int):
         """-> (states, actions, rewards, values, log_probs) of environment e: its first `length[e]` steps."""
@@ -531,6 +635,47 @@ class PPOMemory:
         self._cache = {}
         self._rewards.append(float((lv[0, 0] * torch.pow(torch.tensor(10.0, device=lv.device), lv[0, 1])).item()))
         self._values.append(lv)
+
+    def extend_trajectories(self, trajectories, last_values, gamma: float, lambda_: float, scale=2.0, append=False):
+        """Appends S whole trajectories -- `trajectories`: [(states, actions, rewards, values, log_probs), ...] as `extend` takes them,
+        `last_values`: (S, 2) device tensor of their bootstrap values (zeros behind a terminal step) -- and closes ALL of them with one
+        segmented returns / GAE launch.  The memory ends up exactly as `extend` + end_trajectory + compute_returns +
+        compute_advantages + update_index(append=True) + drop_bootstrap per trajectory (all but the last drop) would leave it:
+        `_rewards` / `_values` keep the last trajectory's bootstrap entry only, `index` = number of rows.  The returns scan does not
+        depend on lambda, so `returns_be` of the (gamma, lambda_, scale) launch is what compute_returns' (gamma, 0, 1) launch gives.
+        One device-to-host read (the bootstrap reward `_rewards` keeps as a float).  No bootstrap entry may be open on entry.
+        -> (returns, values, raw advantages): three tuples of per-trajectory views, what end_episode logs."""
+        trajectories = list(trajectories)
+        S = len(trajectories)
+        lengths = [int(t[1].shape[0]) for t in trajectories]
+        if S < 1 or min(lengths) < 1:
+            raise ValueError(f'extend_trajectories: every trajectory needs at least one row (lengths {lengths})')
+        lv = last_values.to(device=self.device, dtype=torch.float32).reshape(-1, 2)
+        if lv.shape[0] != S:
+            raise ValueError(f'extend_trajectories: {S} trajectories, {lv.shape[0]} last values')
+        first = len(self._rewards)
+        for t in trajectories:
+            self.extend(*t)
+        # padded sequences: every trajectory followed by its bootstrap entry (the elementwise ops of end_trajectory, for all S at once)
+        boot = lv[:, 0] * torch.pow(torch.tensor(10.0, device=lv.device), lv[:, 1])
+        rows = torch.as_tensor(np.asarray(self._rewards[first:], dtype=np.float32), device=self.device)
+        r_parts, v_parts, off = [], [], 0
+        for s, n in enumerate(lengths):
+            r_parts += [rows[off:off + n], boot[s:s + 1]]
+            v_parts += [self._values[len(self._values) - S + s], lv[s:s + 1]]
+            off += n
+        rewards, values_be = torch.cat(r_parts), torch.cat(v_parts, dim=0)
+        out = utils.returns_and_advantages_segments(rewards, values_be, lengths, gamma, lambda_, scale, device=self.device)
+        keep = append and self.returns is not None
+        self.returns = torch.cat([self.returns, out['returns_be']], dim=0) if keep else out['returns_be']
+        self.advantages = torch.cat([self.advantages, out['advantages']], dim=0) if keep else out['advantages']
+        self._cache = {}
+        self._rewards.append(float(boot[S - 1].item()))
+        self._values.append(lv[S - 1:S])
+        self.index = len(self._rewards) - 1
+        values = values_be[:, 0] * torch.pow(torch.tensor(10.0, device=values_be.device), values_be[:, 1])
+        return (torch.split(out['returns'], lengths), torch.split(values, [n + 1 for n in lengths]),
+                torch.split(out['advantages_raw'], lengths))
 
     def drop_bootstrap(self):
         self._cache = {}

@@ -3,6 +3,7 @@ rl/utils.py that the hot path uses (names and argument meaning kept; TensorFlow 
 device kernels of libcdrl_hip.so, torch tensors as plain device memory).
 
   discount_cumsum / gae / rewards_to_go / decompose_number / tf_sp_norm  -> cdrl_gae_returns
+  (many trajectories at once: returns_and_advantages_segments)           -> cdrl_gae_returns_segments
   data_to_batches                                                         -> index pipeline +
                                                                              cdrl_gather_rows
   space_to_flat_spec, to_tensor, Summary, makedir                         -> host bookkeeping
@@ -49,6 +50,16 @@ def returns_and_advantages(rewards, values_be, gamma: float, lambda_: float, sca
     from ..engine import gae_returns
     r, v = _f32(rewards, device), _f32(values_be, device)
     ret, ret_be, adv_raw, adv = gae_returns(r, v, gamma, lambda_, scale)
+    return dict(returns=ret, returns_be=ret_be, advantages_raw=adv_raw, advantages=adv)
+
+
+def returns_and_advantages_segments(rewards, values_be, lengths, gamma: float, lambda_: float, scale: float = 2.0, device='cuda:0'):
+    """`returns_and_advantages` for S trajectories in ONE device launch: `lengths` (host list) are their row counts, N in all;
+    rewards (N+S,), values_be (N+S, 2) hold the trajectories one after the other, each followed by its own bootstrap entry.
+    -> the same dict, packed over the N rows; every trajectory's rows are those of `returns_and_advantages` on it alone."""
+    from ..engine import gae_returns_segments
+    r, v = _f32(rewards, device), _f32(values_be, device)
+    ret, ret_be, adv_raw, adv = gae_returns_segments(r, v, lengths, gamma, lambda_, scale)
     return dict(returns=ret, returns_be=ret_be, advantages_raw=adv_raw, advantages=adv)
 
 

@@ -307,6 +307,21 @@ int cdrl_learner_check_guards(cdrl_learner* l, void* stream, int64_t* bad_bands,
  * (rl/agents/ppo.py:692-697).  scratch: >= 2*(N+1)+2 doubles. */
 int cdrl_gae_returns(const float* rewards, const float* values_be, int N, double gamma, double lambda, float scale,
                      float* returns, float* returns_be, float* adv_raw, float* adv, double* scratch, void* stream);
+/* The same for S trajectories ("segments", N rows in all) in ONE launch, one 256-thread workgroup per segment -- an environment shard
+ * with auto-reset closes E x (resets + 1) trajectories per rollout.  seg_off: DEVICE array of S + 1 row offsets, seg_off[0] = 0,
+ * seg_off[S] = N, every n_s = seg_off[s+1] - seg_off[s] >= 1.  Inputs are padded with each segment's own bootstrap entry: segment s reads
+ * rewards[seg_off[s] + s .. + n_s] (n_s + 1 values) and the values_be rows of the same range, so rewards holds N + S values and values_be
+ * (N + S, 2).  Outputs are packed: segment s writes rows [seg_off[s], seg_off[s+1]) of returns (N), returns_be (N, 2), adv_raw (N) and
+ * adv (N).  Scratch of segment s: 2 * (n_s + 1) doubles from 2 * (seg_off[s] + s); in all 2 * (N + S) doubles, which
+ * cdrl_gae_segments_scratch_doubles returns.  Per-segment quantities stay per segment (scan carries start from 0, the sp-norm takes
+ * max / min over that segment's advantages): every output equals, bit for bit, what cdrl_gae_returns gives for the segment alone.
+ * A segment whose offsets are malformed (n_s <= 0, or outside [0, N]) is skipped and nothing of it is written.  Errors: null pointer,
+ * S < 1, N < S, N + S beyond 32 bits. */
+int cdrl_gae_returns_segments(const float* rewards, const float* values_be, const int32_t* seg_off, int S, int N,
+                              double gamma, double lambda, float scale,
+                              float* returns, float* returns_be, float* adv_raw, float* adv,
+                              double* scratch, void* stream);
+int64_t cdrl_gae_segments_scratch_doubles(int N, int S);
 
 /* tfp.distributions.Beta(alpha, beta).sample() with reparameterisation gradients (core/networks.py:
  * 136-137): u = g1/(g1+g2), g ~ Gamma via Marsaglia-Tsang on a Philox-4x32-10 stream, du/dalpha and
