@@ -94,7 +94,8 @@ class CARLAgent(PPOAgent):
                             dynamics=dict(units=512))
 
     def __init__(self, *args, aug_intensity=1.0, clip_norm=(1.0, 1.0, 1.0), name='carla', load_full=True, eta=0.0,
-                 dynamics_lr=1e-3, update_dynamics=True, delta=0.0, aux=1.0, resample_actions=True, compute='f32', **kwargs):
+                 dynamics_lr=1e-3, update_dynamics=True, delta=0.0, aux=1.0, resample_actions=True, compute='f32', batch_augment=False,
+                 **kwargs):
         """`resample_actions=True` (default, the reference's behaviour): the policy loss is evaluated on a fresh Beta sample of
         the NEW policy with pathwise gradients, as PolicyNetwork.call does (reference core/networks.py:96-110, SURVEY.md F8);
         the sample is drawn on the device.  `False` is the textbook-PPO variant on the stored rollout actions
@@ -104,7 +105,10 @@ class CARLAgent(PPOAgent):
         statistics update) and trains the policy / value heads only; `dynamics_lr` is then accepted and unused, as in the
         reference (core/carla_agent.py:351-373,430-463).  Typical use: load a trained trunk with `load_full=False`, fine-tune the heads.
         `optimizer=name` (PPOAgent): one Keras optimizer class for the policy, value AND dynamics optimizers, as the reference builds
-        all three from the one name (core/carla_agent.py:123-124); `polyak < 1` averages the policy / value heads, not the trunk."""
+        all three from the one name (core/carla_agent.py:123-124); `polyak < 1` averages the policy / value heads, not the trunk.
+        `batch_augment=True` (with `aug_intensity > 0` and an environment shard): the image stacks of all E environments are
+        augmented by ONE batched call per step (Augmenter.batch) instead of one call per environment; plans, Philox offsets and
+        the augmented images are those of the per-environment loop, bit for bit."""
         assert aug_intensity >= 0.0
         network_spec = dict(kwargs.pop('network', {}))
         network_spec.setdefault('network', CARLANetwork)
@@ -120,6 +124,7 @@ class CARLAgent(PPOAgent):
         super().__init__(*args, name=name, network=network_spec, clip_norm=head_clip, **kwargs)
         self.network: CARLANetwork = self.network
         self.aug_intensity = aug_intensity
+        self.batch_augment = bool(batch_augment)
         self.delta, self.eta, self.aux = delta, eta, aux                  # stored, unused (as in the reference)
         self.resample_actions = resample_actions
         self._sample_offset = 0
@@ -350,7 +355,7 @@ class CARLAgent(PPOAgent):
         if alpha <= 0.0:
             return prepare
 
-        from ..rl.augmentations import Augmenter, draw_plan
+        from ..rl.augmentations import Augmenter, draw_plan, draw_plans
 
         def augment_fn(state):
             """CARLAgent.augment (core/carla_agent.py:527-579): the image stack of every observation is augmented with
@@ -362,6 +367,27 @@ class CARLAgent(PPOAgent):
             plan = draw_plan(alpha, self._aug_rng, offset=self._aug_calls)
             state['state_image'] = self._augmenter(state['state_image'], plan)
             return state
+
+        def augment_shard(states):
+            """`augment_fn` for the E observations of an environment shard at once: one host array and one copy per key, the E plans
+            drawn in environment order from the same generator with the same offsets as E augment_fn calls, one batched
+            augmentation call."""
+            states = [prepare(s) for s in states]
+            if self._augmenter is None:
+                self._augmenter = Augmenter(self.device)
+            plans = draw_plans(alpha, self._aug_rng, len(states), first_offset=self._aug_calls + 1)
+            self._aug_calls += len(states)
+            out = {}
+            for k in states[0]:
+                vals = [np.asarray(s[k], dtype=np.float32) for s in states]
+                if k == 'state_image':
+                    out[k] = self._augmenter.batch(vals, plans)     # gathered into the augmenter's page-locked staging buffer
+                else:
+                    out[k] = torch.as_tensor(np.stack(vals, axis=0)).to(self.device)
+            return out
+
+        if self.batch_augment:
+            augment_fn.shard = augment_shard
         return augment_fn
 
     def evaluate(self, *args, **kwargs):

@@ -780,6 +780,13 @@ int cdrl_augment_images(const float* in, float* out, int T, int H, int W, const 
     return augment_images(in, out, T, H, W, p, workspace, S(stream));
 }
 
+int64_t cdrl_augment_batch_workspace_floats(int E, int T, int H, int W) { return augment_batch_workspace_floats(E, T, H, W); }
+
+int cdrl_augment_images_batch(const float* in, float* out, int E, int T, int H, int W, const cdrl_aug_plan* plans_dev,
+                              float* workspace, void* stream) {
+    return augment_images_batch(in, out, E, T, H, W, reinterpret_cast<const AugPlan*>(plans_dev), workspace, S(stream));
+}
+
 int64_t cdrl_stem_block_bwd_workspace_doubles(int B, int T, int H, int W, int Cout) {
     const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
     const int Hp = same_out(Ho, 2), Wp = same_out(Wo, 2);

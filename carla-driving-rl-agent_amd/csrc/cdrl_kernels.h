@@ -460,6 +460,13 @@ struct AugPlan {           // same layout as cdrl_aug_plan (include/cdrl.h)
 };
 // in/out: [T][H][W][3] floats; workspace: 2*T*H*W*3 + 5*T floats
 int augment_images(const float* in, float* out, int T, int H, int W, const AugPlan& plan, float* workspace, hipStream_t st);
+// E stacks at once: in/out [E][T][H][W][3]; plans_dev: E plans IN DEVICE MEMORY (a blur_size outside {0, 3, 5} is treated as 0: the
+// caller checks it before the upload); workspace: augment_batch_workspace_floats floats.  out[e] gets the bytes of
+// augment_images(in[e], ..., plans[e]); five launches for any E (the environment is the grid's y dimension).
+constexpr int AUG_BATCH_MAX_ENVS = 65535;
+int64_t augment_batch_workspace_floats(int E, int T, int H, int W);
+int augment_images_batch(const float* in, float* out, int E, int T, int H, int W, const AugPlan* plans_dev, float* workspace,
+                         hipStream_t st);
 
 // ---------------------------------------------------------------- optimiser (optim.hip)
 // Device hyper-parameter block, refreshed by the host before each step (graph-replay safe).

@@ -3,7 +3,9 @@ core/carla_agent.py:527-579) on the native kernels.
 
 `draw_plan(alpha, rng)` makes the same sequence of random decisions as the reference's `augment_fn` (one
 `tf_chance` per op compared with the op's probability times the intensity `alpha`, then the op's own random scalars);
-`augment_images(images, plan)` applies the plan on the device through `cdrl_augment_images`.  The random *fields*
+`Augmenter()(images, plan)` applies the plan to one stack on the device through `cdrl_augment_images`; `Augmenter().batch(images,
+plans)` applies E plans to the E stacks of an environment shard through `cdrl_augment_images_batch` (one copy of the images, one
+upload of the packed plans, five launches for any E; every stack gets the bytes the one-stack call gives it).  The random *fields*
 (salt & pepper masks, gaussian noise, dropout grid) are generated on the device from (plan seed, plan offset)."""
 import ctypes as C
 
@@ -54,6 +56,12 @@ def draw_plan(alpha: float, rng: np.random.Generator, offset=0) -> dict:
     return plan
 
 
+def draw_plans(alpha: float, rng: np.random.Generator, count: int, first_offset: int) -> list:
+    """`count` plans drawn one after the other from `rng`, with offsets first_offset, first_offset + 1, ...: what `count` successive
+    draw_plan calls give (the shard path of CARLAgent.preprocess draws its environments' plans here, in environment order)."""
+    return [draw_plan(alpha, rng, offset=first_offset + i) for i in range(count)]
+
+
 def to_struct(plan: dict) -> AugPlan:
     p = AugPlan()
     for k, v in plan.items():
@@ -65,6 +73,29 @@ def to_struct(plan: dict) -> AugPlan:
     return p
 
 
+# AugPlan's layout as a numpy record (align=True pads as the C compiler does: `seed` starts on an 8-byte boundary)
+PLAN_DTYPE = np.dtype([(n, np.float32, (75,)) if n == 'blur_kernel' else (n, np.dtype(t)) for n, t in AugPlan._fields_], align=True)
+assert PLAN_DTYPE.itemsize == C.sizeof(AugPlan) and all(PLAN_DTYPE.fields[n][1] == getattr(AugPlan, n).offset
+                                                        for n, _ in AugPlan._fields_)
+
+
+def pack_plans(plans: list) -> np.ndarray:
+    """The plans as one record array with AugPlan's byte layout (`.tobytes()` = the concatenated `to_struct` images), filled one
+    COLUMN at a time.  A blur size the kernels do not have is refused here: the device code cannot report it."""
+    out = np.zeros(len(plans), dtype=PLAN_DTYPE)
+    for name in PLAN_DTYPE.names:
+        if name == 'blur_kernel':
+            for row, plan in zip(out[name], plans):
+                kern = plan.get(name, ())
+                row[:len(kern)] = kern
+        else:
+            out[name] = [plan.get(name, 0) for plan in plans]
+    bad = ~np.isin(out['blur_size'], (0, 3, 5))
+    if bad.any():
+        raise ValueError(f'blur_size must be 0, 3 or 5, got {out["blur_size"][bad].tolist()} (plans {np.flatnonzero(bad).tolist()})')
+    return out
+
+
 class Augmenter:
     """Holds the workspace / output buffers for one observation-stack shape."""
 
@@ -73,6 +104,50 @@ class Augmenter:
         self.device = torch.device(device)
         self._ws = None
         self._shape = None
+        self._batch_ws = None
+        self._batch_shape = None
+        self._staging = None
+        self._staging_read = None
+
+    def _stage(self, stacks) -> torch.Tensor:
+        """E host stacks -> one (E, T, H, W, 3) device tensor: the stacks are gathered straight into a cached page-locked buffer
+        (one pass over the host data, no fresh 0.5 MB x E array per step) and cross PCIe as one asynchronous copy."""
+        shape = (len(stacks),) + tuple(np.shape(stacks[0]))
+        if self._staging is None or tuple(self._staging.shape) != shape:
+            self._staging = torch.empty(shape, dtype=torch.float32, pin_memory=True)
+            self._staging_read = None
+        if self._staging_read is not None:
+            self._staging_read.synchronize()                # the previous step's copy out of the buffer has finished
+        np.stack(stacks, axis=0, out=self._staging.numpy())
+        x = self._staging.to(self.device, non_blocking=True)
+        self._staging_read = torch.cuda.Event()
+        self._staging_read.record()
+        return x
+
+    def batch(self, images, plans: list) -> torch.Tensor:
+        """images: (E, T, H, W, 3), host or device, or a list of E host stacks (T, H, W, 3); plans: E dicts.  Stack e is augmented
+        with plans[e], as `self(images[e], plans[e])` would: one host-to-device copy of the images, one of the packed plans, one
+        library call."""
+        if isinstance(images, (list, tuple)) and not any(isinstance(v, torch.Tensor) for v in images):
+            x = self._stage(images)
+        else:
+            x = torch.as_tensor(images, dtype=torch.float32).to(self.device).contiguous()
+        if x.dim() != 5 or x.shape[-1] != 3:
+            raise ValueError(f'expected a shard of image stacks (E, T, H, W, 3), got {tuple(x.shape)}')
+        E, T, H, W, _ = x.shape
+        if len(plans) != E:
+            raise ValueError(f'{E} image stacks but {len(plans)} plans')
+        packed = pack_plans(plans)
+        if self._batch_shape != (E, T, H, W):
+            self._batch_ws = torch.empty(int(self.lib.cdrl_augment_batch_workspace_floats(E, T, H, W)), device=self.device)
+            self._batch_shape = (E, T, H, W)
+        plans_dev = torch.from_numpy(packed.view(np.uint8)).to(self.device)
+        out = torch.empty_like(x)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self.lib.cdrl_augment_images_batch(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), E, T, H, W,
+                                                      C.c_void_p(plans_dev.data_ptr()), C.c_void_p(self._batch_ws.data_ptr()), stream),
+                   'cdrl_augment_images_batch')
+        return out
 
     def __call__(self, images, plan: dict) -> torch.Tensor:
         x = torch.as_tensor(images, dtype=torch.float32).to(self.device).contiguous()

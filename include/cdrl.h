@@ -706,6 +706,15 @@ typedef struct {
 int64_t cdrl_augment_workspace_floats(int T, int H, int W);
 int cdrl_augment_images(const float* in, float* out, int T, int H, int W, const cdrl_aug_plan* plan, float* workspace,
                         void* stream);
+/* The same for a shard of E stacks in a fixed five launches: in/out [E][T][H][W][3] (may not alias; `in` is only read), plans_dev:
+ * E plans IN DEVICE MEMORY, one per stack -- ops may fire for some stacks and not for others.  out[e] receives exactly the bytes
+ * cdrl_augment_images(in + e * T*H*W*3, ..., &plans[e], ...) writes; the Philox streams stay keyed by stack e's own (seed, offset)
+ * and the element index within that stack.  The plans cannot be read by the host here: the caller validates blur_size before
+ * the upload, and the kernels treat a size outside {0, 3, 5} as 0.  E <= 65535.  workspace:
+ * cdrl_augment_batch_workspace_floats(E, T, H, W) floats (0 for a bad shape). */
+int64_t cdrl_augment_batch_workspace_floats(int E, int T, int H, int W);
+int cdrl_augment_images_batch(const float* in, float* out, int E, int T, int H, int W, const cdrl_aug_plan* plans_dev,
+                              float* workspace, void* stream);
 /* CARLAgent.policy_objective / value_objective on linear head outputs (core/carla_agent.py:394-428,
  * 469-486); writes d(loss)/d(lin) and 16 metric floats. */
 int cdrl_beta_ppo_loss(const float* lin, const float* adv, const float* old_logp, const float* speed,
