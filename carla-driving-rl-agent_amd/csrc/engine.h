@@ -217,8 +217,7 @@ private:
         int bwd_nb = 0;                    // partial rows per group its backward sums are left in (set by whoever plans their producer)
         explicit operator bool() const { return C > 0; }
     };
-    // Backward form of a unit 1x1 conv, decided from shapes, views and switches before any op of the unit is emitted (pw_bwd_form):
-    // the BatchNorm ops around the conv are built from the same answer.
+    // Backward form of a 1x1 conv of the tower
     enum class PwBwd {
         Plain,      // dy materialised by the BatchNorm behind the conv; backward-data + filter gradient as two GEMMs
         Prologue,   // BatchNorm-backward apply as operand prologue of those two GEMMs (persistent float32 / bf16 kernel)
@@ -227,31 +226,43 @@ private:
         FusedFin    // ... which also finalizes the BatchNorm behind the conv on load (float32)
     };
     static bool pw_fused(PwBwd f) { return f == PwBwd::Fused || f == PwBwd::FusedFin; }
-    PwBwd pw_bwd_form(View in, View din, View dz, int Mg, int Cin, int Cout, bool bn_in) const;
-    // BatchNorm work folded into a pointwise conv (gemm_pw.hip); all optional
-    struct PwFuse {
-        bool fwd_pw = false;                 // forward through the persistent skinny GEMM
-        bool epi_stats = false;              // forward epilogue: statistics partials of the BatchNorm behind the conv -> scratch part
-        bool bwd_pw = false;                 // backward-data through the persistent skinny GEMM
-        // the BatchNorm in front, applied on load (the conv input is its raw input): its backward sums come out of the conv's
-        // backward -- the backward-data epilogue, or the reduce kernel of the fused form, which leaves nothing for its own op
-        BnRec bn_in;
-        // != Plain: BatchNorm-backward apply of the BatchNorm behind the conv as the operand prologue of the backward GEMMs (the
-        // gradient w.r.t. the conv output is never materialised)
-        PwBwd bwd = PwBwd::Plain;
-        View bb_dz{nullptr, 0, 0};           // gradient w.r.t. that BatchNorm's output; ld == 0: the current scratch slot (dense)
-        int bb_shuffle = 0, bb_act = 0;
-        bool bb_claim_slot = false;          // this op claims the rotating scratch slot (nobody upstream did)
+    // GEMM entry of a 1x1 conv's forward / backward-data: split-precision pw_x3 (forward only), persistent pw_nn, gemm_x3, gemm_nn
+    enum class PwGemm { X3, PwNN, GemmX3, GemmNN };
+    // A 1x1 conv of the tower as its builder describes it (plan_pw, add_pw)
+    struct PwConv {
+        std::string name;                    // parameter prefix
+        View in{nullptr, 0, 0};
+        int rows = 0, Cin = 0, Cout = 0;
+        float* y = nullptr;                  // raw output [rows][Cout]
+        View din{nullptr, 0, 0};
+        int din_acc = 0;
+        // forms != Plain (dy is never materialised): the gradient w.r.t. the output of the BatchNorm behind the conv.  ld == 0: the current
+        // scratch slot (dense), left there by the op upstream; else the conv's backward claims the rotating slot itself (nobody upstream did)
+        View dz{nullptr, 0, 0};
+        int dz_shuffle = 0, dz_act = 0;
     };
+    // Every kernel choice of one 1x1 conv, decided before any op of its unit is emitted (plan_pw).  The unit builder asks once and hands
+    // the same value to add_pw and to the BatchNorm ops around the conv (BnOp::conv, DwBlock::pre_conv / post_conv).
+    struct ConvPlan {
+        PwGemm fwd = PwGemm::GemmNN;
+        PwBwd bwd = PwBwd::Plain;
+        PwGemm dgrad = PwGemm::GemmNN;       // backward-data GEMM of Plain (Prologue: pw_nn too; Wide, Fused*: the form's own kernel)
+        int stats_nb = 0;                    // > 0: rows per group of statistics partials (BatchNorm behind the conv) the forward epilogue writes
+        int bwd_nb = 0;                      // partial rows per group of the backward-data pass (bias sums, sums of the BatchNorm in front)
+        // the BatchNorm in front is applied on load (the conv input is its raw input): its backward sums come out of the conv's
+        // backward -- the backward-data epilogue, or the reduce kernel of the fused form, which leaves nothing for its own op
+        bool bn_in = false;
+    };
+    // fused: BatchNorm work folded into the unit's convs (persistent / split-precision kernels); bb: and BatchNorm-backward apply as prologue
+    ConvPlan plan_pw(const PwConv& c, bool fused, bool bb, bool bn_in);
     // How a BatchNorm's op runs (add_bn)
     struct BnOp {
         bool bessel = true;
         View out{nullptr, 0, 0}, dout{nullptr, 0, 0};
         int out_shuffle = 0, dout_shuffle = 0;
         float* dx = nullptr;                 // nullptr: tower mode, the gradient w.r.t. the input goes to the current scratch slot
-        int stats_nb = 0;                    // > 0: the statistics partials were written by the producing op (rows per group)
-        PwBwd conv = PwBwd::Plain;           // backward form of the conv in front: != Plain applies this BatchNorm's backward on load,
-                                             // FusedFin finalizes it too
+        ConvPlan conv;                       // the conv in front.  stats_nb > 0: it wrote the statistics partials; bwd != Plain: it applies this
+                                             // BatchNorm's backward on load, FusedFin finalizes it too
         bool sums_by_producer = false;       // the op that produces the incoming gradient accumulates the backward sums in its pass
         Passthrough pass;
     };
@@ -261,16 +272,13 @@ private:
         int H = 0, W = 0, C = 0, stride = 1;
         View din{nullptr, 0, 0};             // gradient target when there is no pre-BN
         BnRec pre;                           // BatchNorm (+ReLU6) in front, or none
-        int pre_stats_nb = 0;                // > 0: its statistics partials were written by the producing conv's epilogue
-        PwBwd pre_conv = PwBwd::Plain;       // backward form of the conv in front of `pre` (as BnOp::conv)
+        ConvPlan pre_conv;                   // the conv in front of `pre` (as BnOp::conv)
         std::string dw, bn_post;             // parameter prefixes of the depthwise conv and the BatchNorm behind it
         float* y2 = nullptr;                 // raw depthwise output
         View out{nullptr, 0, 0}, dout{nullptr, 0, 0};
-        // the conv behind applies the post-BN on load: its output is not materialised, and its backward sums come from that conv --
-        // post_bwd_nb rows per group from the backward-data epilogue, or everything from the fused form's reduce kernel
-        bool post_on_load = false;
-        int post_bwd_nb = 0;
-        PwBwd post_conv = PwBwd::Plain;
+        // the conv behind.  bn_in: it applies the post-BN on load: its output is not materialised, and its backward sums come from that
+        // conv -- bwd_nb rows per group from the backward-data epilogue, or everything from the fused form's reduce kernel
+        ConvPlan post_conv;
     };
     // Second half of a unit branch (add_half): `d` carries the input side of its depthwise block (x .. pre_conv)
     struct Half {
@@ -305,8 +313,19 @@ private:
     void add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o);
     // dense BatchNorm between two tensors (feature nets, trunk tail, control branches): no Bessel correction, no activation
     void add_dense_bn(std::vector<Op>& ops, int model, const std::string& prefix, const Tens& in, const Tens& out, int G);
-    void add_pw(std::vector<Op>& ops, const std::string& prefix, View in, int rows, int Cin, int Cout, float* y,
-                View din, int din_acc, const BnRec& bn_out, const PwFuse& fuse);
+    // emits what the plan says (bn_in: the record behind ConvPlan::bn_in, or none); the backward is one of three programs, chosen at build time
+    void add_pw(std::vector<Op>& ops, const PwConv& c, const ConvPlan& plan, const BnRec& bn_in, const BnRec& bn_out);
+    struct PwEmit {                          // what add_pw hands to the backward emitter of the plan's form
+        PwConv c;
+        ConvPlan plan;
+        BnRec bn_in, bn_out;
+        PRef w, b;
+        const float* wpb = nullptr;          // packed W^T: float32 / bf16 MFMA fragment order (persistent kernel),
+        const void *wpx = nullptr, *g3b = nullptr;      // three bf16 planes (fused and wide form), gemm_x3's
+    };
+    std::function<int(hipStream_t)> pw_bwd_fused_op(const PwEmit& e);
+    std::function<int(hipStream_t)> pw_bwd_prologue_op(const PwEmit& e);
+    std::function<int(hipStream_t)> pw_bwd_plain_op(const PwEmit& e);
     // pre_bn: the op also accumulates the backward sums of that BatchNorm (the layer that produced `in`)
     void add_dw(std::vector<Op>& ops, const std::string& prefix, View in, int N, int H, int W, int C, int stride,
                 float* y, View din, int din_acc, const BnRec* pre_bn = nullptr);
@@ -317,13 +336,8 @@ private:
     // Depthwise block, then 1x1 conv, then BN + ReLU6 into a shuffled half of the unit output: the second half of a main branch and the
     // whole shortcut branch of a stride-2 unit (core/architectures.py:126-137)
     void add_half(std::vector<Op>& ops, const Half& h);
-    bool fused_dw_ = true, fused_pw_ = true;
-    bool fused_bb_ = true;
+    bool fused_dw_ = true, fused_pw_ = true, fused_bb_ = true;
     bool fused_bwd_ = true;             // backward-data + filter gradient of the unit convs as one kernel (gemm_pw_bwd.hip)
-    int pw_fwd_nbpg(int G, int Mg, int N, int K) const;    // statistics partial rows per group written by a unit conv's forward
-    bool pw_bwd_x3_wide(int G, int Mg, int N, int K) const;               // backward-data on pw_x3_wide_bwd_kernel (N = conv inputs, K = conv outputs)
-    int pw_bwd_nbpg(int G, int Mg, int N, int K) const;    // partial rows per group of a unit conv's backward-data (bias sums, BatchNorm sums)
-    bool pw_fwd_x3_wide(int G, int Mg, int N, int K) const;               // that forward runs on pw_x3_wide_kernel (float32 engine, 128 < K or N <= 256)
     void add_dense(std::vector<Op>& ops, int model, const std::string& prefix, View in, int M, int K, int N, int act,
                    View out, View dout, View din, int din_acc, bool need_din, const char* bias_init);
     void add_gru(std::vector<Op>& ops, const std::string& name, Tens& x, int In, int u, View out, View dout,
@@ -430,7 +444,11 @@ private:
     uint64_t side_seq_ = 0, main_waited_ = 0;
     uint64_t slot_seq_[NSLOT] = {}, q_seq_[NQ] = {};
     int side_lag_ = 4;
-    uint64_t note_side_record(hipEvent_t ev);
+    // record `ev` on the side stream and number the record; seq / used: the scratch slot or ring entry that is free once it is covered
+    int record_side(hipEvent_t ev, uint64_t* seq = nullptr, bool* used = nullptr);
+    // `st` joins the side stream: `ev` recorded there (numbered) and waited for; the critical stream has then waited for that record
+    int join_side_at(hipStream_t st, hipEvent_t ev);
+    int release_q(int qi, hipStream_t sd);               // side job that read ring entry qi finished (fused conv backward's reduce)
     int wait_side_record(hipStream_t st, uint64_t need, hipEvent_t need_ev);
     int slot_ = 0;
     int next_slot(hipStream_t st);                       // main: claim a scratch slot (waits for its last side job)

@@ -190,10 +190,25 @@ static const int g_diag_noev = cdrl_getenv("CDRL_DIAG_NOEV") ? atoi(cdrl_getenv(
 // the record of its last user is covered -- so instead of one hipStreamWaitEvent (a barrier packet of its own on the critical stream,
 // 0.23 ms per update-step for ~100 of them by the no-waits diagnostic) per claim, the critical stream waits for a record `side_lag_`
 // behind the newest one whenever the record it needs is not covered yet, and skips the claims that wait covers (round 6).
-uint64_t Learner::note_side_record(hipEvent_t ev) {
+int Learner::record_side(hipEvent_t ev, uint64_t* seq, bool* used) {
+    CDRL_HIP(hipEventRecord(ev, side_));
     ++side_seq_;
     side_hist_[side_seq_ % SIDE_HIST] = SideRec{ev, side_seq_};
-    return side_seq_;
+    if (seq) *seq = side_seq_;
+    if (used) *used = true;
+    return 0;
+}
+
+int Learner::join_side_at(hipStream_t st, hipEvent_t ev) {
+    CDRL_TRY(record_side(ev));
+    CDRL_HIP(hipStreamWaitEvent(st, ev, 0));
+    if (st == main_) main_waited_ = side_seq_;
+    return 0;
+}
+
+int Learner::release_q(int qi, hipStream_t sd) {
+    if (!side_enabled_ || sd != side_) return 0;
+    return record_side(ev_q_[qi], &q_seq_[qi], &q_used_[qi]);      // the buffer pair is free again once the side job has run
 }
 
 int Learner::wait_side_record(hipStream_t st, uint64_t need, hipEvent_t need_ev) {
@@ -252,11 +267,8 @@ void Learner::flush_deferred() {
     for (Deferred& d : deferred_) {
         const int rc = d.fn(side_);
         if (rc != 0 && deferred_rc_ == 0) deferred_rc_ = rc;
-        if (d.slot != slot_) {      // (a job of the current slot is covered by the done_side() that follows)
-            if (hipEventRecord(ev_side_[d.slot], side_) != hipSuccess && deferred_rc_ == 0) deferred_rc_ = -3;
-            slot_seq_[d.slot] = note_side_record(ev_side_[d.slot]);
-            slot_used_[d.slot] = true;
-        }
+        // (a job of the current slot is covered by the done_side() that follows)
+        if (d.slot != slot_ && record_side(ev_side_[d.slot], &slot_seq_[d.slot], &slot_used_[d.slot]) != 0 && deferred_rc_ == 0) deferred_rc_ = -3;
     }
     deferred_.clear();
 }
@@ -291,10 +303,7 @@ int Learner::done_side(hipStream_t side) {
         return rc;
     }
     if (g_diag_noev & 4) return 0;
-    CDRL_HIP(hipEventRecord(ev_side_[slot_], side_));
-    slot_seq_[slot_] = note_side_record(ev_side_[slot_]);
-    slot_used_[slot_] = true;
-    return 0;
+    return record_side(ev_side_[slot_], &slot_seq_[slot_], &slot_used_[slot_]);
 }
 
 int Learner::join_side(hipStream_t st) {
@@ -303,10 +312,7 @@ int Learner::join_side(hipStream_t st) {
         hipStream_t side = fork_side(st);       // flushes the queue
         CDRL_TRY(done_side(side));
     }
-    CDRL_HIP(hipEventRecord(ev_join_, side_));
-    CDRL_HIP(hipStreamWaitEvent(st, ev_join_, 0));
-    const uint64_t js = note_side_record(ev_join_);
-    if (st == main_) main_waited_ = js;
+    CDRL_TRY(join_side_at(st, ev_join_));
     if (aux_pending_) {
         CDRL_HIP(hipStreamWaitEvent(st, ev_aux_done_, 0));
         aux_pending_ = false;
@@ -498,33 +504,6 @@ const void* Learner::pw_x3_packed(const float* w, int K, int N, int sbk, int sbn
     return wp;
 }
 
-int Learner::pw_fwd_nbpg(int G, int Mg, int N, int K) const {
-    // float32 engine, K or N above 128 (stage 2): the forward runs on the one-tile-per-workgroup split-precision kernel
-    // (gemm_pw_x3.hip pw_x3_wide_kernel), which writes one statistics row per 32-row tile
-    if (pw_fwd_x3_wide(G, Mg, N, K)) return pw_x3_partial_rows(G, Mg, N, K);
-    return pw_nn_plan(G, Mg, N, K).nbpg;
-}
-
-// backward-data of the same convs (N = conv input channels, K = conv output channels): pw_x3_wide_bwd_kernel, one part2 / part row per tile
-// Small products only (M = 12288 rows at B = 256: the 3x4-pixel maps of stage 2): every workgroup streams its block of W^T once, so at
-// M = 49152 (the stride-2 unit's first conv, on the 6x8 maps) the fragment traffic (3072 x 196 KB) outweighs what the persistent kernel
-// loses to its serial tiles -- measured in the step: 140 us against 100 us there, 36 against 53 us (BatchNorm-sum epilogue) at M = 12288.
-bool Learner::pw_bwd_x3_wide(int G, int Mg, int N, int K) const {
-    return pw_fwd_x3_wide(G, Mg, N, K) && (int64_t)G * Mg <= 16384;
-}
-
-int Learner::pw_bwd_nbpg(int G, int Mg, int N, int K) const {
-    if (pw_bwd_x3_wide(G, Mg, N, K)) return pw_x3_wide_bwd_rows(Mg);
-    return pw_nn_plan(G, Mg, N, K).nbpg;
-}
-
-bool Learner::pw_fwd_x3_wide(int G, int Mg, int N, int K) const {
-    static const bool x3_env = env_on("CDRL_PW_X3");
-    // (measured at M = 12288 and 49152 rows: 16-20 against 26-36 us, ~60 against 80 us; beyond that every 32-row tile would still stream
-    //  its own copy of W -- 196 KB per tile and column block -- and the persistent kernel keeps the shape)
-    return cfg_.compute == 0 && x3_env && (K > 128 || N > 128) && K <= 256 && N <= 256 && K % 4 == 0 && (int64_t)G * Mg <= 49152;
-}
-
 const void* Learner::gemm_x3_packed(const float* w, int K, int N, int sbk, int sbn) {
     void* wp = alloc((size_t)gemm_x3_packed_bytes(N, K) / sizeof(float));
     h_gpack_.push_back(gemm_x3_pack_entry(w, wp, K, N, sbk, sbn));
@@ -615,10 +594,10 @@ void Learner::add_dense_bn(std::vector<Op>& ops, int model, const std::string& p
 }
 
 void Learner::add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o) {
-    const int G = bn.G, Mg = bn.Mg, C = bn.C, nb = bn.nb, act = bn.act, at = bn.at, stats_nb = o.stats_nb, bes = o.bessel ? 1 : 0;
+    const int G = bn.G, Mg = bn.Mg, C = bn.C, nb = bn.nb, act = bn.act, at = bn.at, stats_nb = o.conv.stats_nb, bes = o.bessel ? 1 : 0;
     const View x = bn.x;
     const Passthrough pass = o.pass;
-    const bool apply_by_conv = o.conv != PwBwd::Plain, fin_by_conv = o.conv == PwBwd::FusedFin;
+    const bool apply_by_conv = o.conv.bwd != PwBwd::Plain, fin_by_conv = o.conv.bwd == PwBwd::FusedFin;
     Scratch* sc = bn.scr;
     note_scratch((size_t)G * std::max(nb, stats_nb) * 2 * C, (size_t)G * nb * C, 0, 0);
     // single-group BatchNorm over a few hundred rows (dense BNs of the trunk tail and the control branches): one launch per
@@ -666,11 +645,54 @@ void Learner::add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o) {
     ops.push_back(op);
 }
 
-// Backward form of a unit conv whose BatchNorm-backward apply rides on its operand loads (in / din: conv input and its gradient, dz: the
-// gradient w.r.t. the output of the BatchNorm behind the conv, bn_in: the input is a BatchNorm output applied on load)
-Learner::PwBwd Learner::pw_bwd_form(View in, View din, View dz, int Mg, int Cin, int Cout, bool bn_in) const {
-    const int G = cfg_.T;
+// One plan per 1x1 conv of the tower: forward kernel, backward form, backward-data GEMM and the partial-row counts its neighbours read.
+// The value is a pure function of the conv's views and shapes, cfg_, at_ and the switches; a conv that has no kernel is refused here
+// (build_fail), before anything of its unit is emitted.
+Learner::ConvPlan Learner::plan_pw(const PwConv& c, bool fused, bool bb, bool bn_in) {
+    static const bool x3_env = env_on("CDRL_PW_X3");
+    const int G = cfg_.T, Mg = c.rows / G, Cin = c.Cin, Cout = c.Cout;
+    // compute mode 1 (configuration 3): every 1x1 convolution of the tower multiplies bf16-rounded operands -- forward,
+    // backward-data and filter gradient: the fused kernels in their BF variant, the plain wide ones through gemm_x3's
+    // single-plane form, the filter gradients through tn_direct's BF variant
     const bool bfc = cfg_.compute >= 1;
+    ConvPlan p;
+    p.bn_in = bn_in;
+    if (!fused) {
+        // plain (unfused) wide convs -- the 464 -> 768 head conv, the 232-wide shortcut conv -- on the bf16 matrix pipe too (gemm_x3.hip)
+        const bool g3 = bfc || (x3_env && (Cin >= 128 || Cout > 128));
+        if (g3 && gemm_x3_supported(c.in, Cin)) p.fwd = PwGemm::GemmX3;
+        if (g3 && Cout % 4 == 0) p.dgrad = PwGemm::GemmX3;
+        if (bfc && (p.fwd != PwGemm::GemmX3 || p.dgrad != PwGemm::GemmX3))
+            build_fail("bf16-operand mode: 1x1 convolution %s (%d -> %d, fwd 0 bwd 0 bb 0; input ld %d coff %d) has no bf16 kernel",
+                       c.name.c_str(), Cin, Cout, c.in.ld, c.in.coff);
+        return p;
+    }
+    // float32 engine, K or N above 128 (stage 2): the forward runs on the one-tile-per-workgroup split-precision kernel (gemm_pw_x3.hip
+    // pw_x3_wide_kernel), which writes one statistics row per 32-row tile
+    // (measured at M = 12288 and 49152 rows: 16-20 against 26-36 us, ~60 against 80 us; beyond that every 32-row tile would still stream
+    //  its own copy of W -- 196 KB per tile and column block -- and the persistent kernel keeps the shape)
+    auto wide_shape = [&](int N, int K) {
+        return cfg_.compute == 0 && x3_env && (K > 128 || N > 128) && K <= 256 && N <= 256 && K % 4 == 0 && (int64_t)G * Mg <= 49152;
+    };
+    const bool wide = wide_shape(Cout, Cin);
+    // backward-data of the same convs (N = conv input channels, K = conv output channels): pw_x3_wide_bwd_kernel, one part2 / part row per tile
+    // Small products only (M = 12288 rows at B = 256: the 3x4-pixel maps of stage 2): every workgroup streams its block of W^T once, so at
+    // M = 49152 (the stride-2 unit's first conv, on the 6x8 maps) the fragment traffic (3072 x 196 KB) outweighs what the persistent kernel
+    // loses to its serial tiles -- measured in the step: 140 us against 100 us there, 36 against 53 us (BatchNorm-sum epilogue) at M = 12288.
+    const bool wide_bwd = wide_shape(Cin, Cout) && (int64_t)G * Mg <= 16384;
+    // forward on the bf16 matrix pipe (exact three-way operand split, gemm_pw_x3.hip) where the shape allows it
+    // (dry build: `in.p` is null, which counts as aligned -- as every tens_a tensor is, dense and 256-byte aligned)
+    const bool x3f = !bfc && x3_env && ((Cin <= 128 && Cout <= 128) || wide) && pw_x3_supported(c.in, Cout, Cin);
+    if (wide && !x3f)
+        build_fail("%s: the wide split-precision forward needs 16-byte aligned input rows (ld %d, offset %d)", c.name.c_str(), c.in.ld, c.in.coff);
+    p.fwd = x3f ? PwGemm::X3 : PwGemm::PwNN;
+    p.dgrad = PwGemm::PwNN;
+    p.stats_nb = wide ? pw_x3_partial_rows(G, Mg, Cout, Cin) : pw_nn_plan(G, Mg, Cout, Cin).nbpg;
+    p.bwd_nb = wide_bwd ? pw_x3_wide_bwd_rows(Mg) : pw_nn_plan(G, Mg, Cin, Cout).nbpg;
+    if (!bb) return p;
+    // Backward form of a unit conv whose BatchNorm-backward apply rides on its operand loads (dz: the gradient w.r.t. the output of the
+    // BatchNorm behind the conv, bn_in: the input is a BatchNorm output applied on load)
+    const View dz = c.dz.ld ? c.dz : make_view(nullptr, Cout);
     // One kernel for backward-data + filter gradient + bias gradient (+ the backward sums of the BatchNorm in front of the conv):
     // float32 engine and bf16 activation storage (not the operand-only mode), both channel counts padded alike (gemm_pw_bwd.hip)
     // 24 input channels -- the first unit, the last conv of the backward -- pad to 64: 158 us against 104 us for the backward-data kernel of
@@ -678,174 +700,158 @@ Learner::PwBwd Learner::pw_bwd_form(View in, View din, View dz, int Mg, int Cin,
     // tail of the pass and slows the BatchNorm reduction beside it (117 us instead of 29): fused 14.00 vs 14.06 ms per update-step, and one
     // pass over (dz, y) = 0.3 GB per pass less.
     static constexpr int fbwd_min_cin = 24;
-    if (fused_bwd_ && (!bfc || at_) && G <= 8 && Cin >= fbwd_min_cin && pw_bwd_fused_supported(dz, in, din, Cout, Cin, at_) &&
-        (!bn_in || (in.ld == Cin && in.coff == 0)))
+    if (fused_bwd_ && (!bfc || at_) && G <= 8 && Cin >= fbwd_min_cin && pw_bwd_fused_supported(dz, c.in, c.din, Cout, Cin, at_) &&
+        (!bn_in || (c.in.ld == Cin && c.in.coff == 0)))
         // float32: the finalize of the BatchNorm behind the conv inside the fused kernel (no bn_bwd_finalize launch in front of it)
-        return (!at_ && fin_on_load_) ? PwBwd::FusedFin : PwBwd::Fused;
+        p.bwd = (!at_ && fin_on_load_) ? PwBwd::FusedFin : PwBwd::Fused;
     // 232-channel convs (stage 2), float32: backward-data with the BatchNorm-backward prologue on the one-tile-per-workgroup
     // split-precision kernel (round 6; the filter gradient stays on the side stream)
-    if (!bfc && !at_ && pw_bwd_x3_wide(G, Mg, Cin, Cout)) return PwBwd::Wide;
-    return PwBwd::Prologue;
+    else if (!bfc && !at_ && wide_bwd) p.bwd = PwBwd::Wide;
+    else p.bwd = PwBwd::Prologue;
+    if (p.bwd == PwBwd::Wide && !pw_x3_wide_bwd_supported(dz, c.din, Cin, Cout, c.dz_shuffle))
+        build_fail("%s: the wide split-precision backward needs even / 16-byte aligned gradient rows (ld %d, offset %d, shuffle %d)", c.name.c_str(),
+                   dz.ld, dz.coff, c.dz_shuffle);
+    return p;
 }
 
-void Learner::add_pw(std::vector<Op>& ops, const std::string& prefix, View in, int rows, int Cin, int Cout, float* y,
-                     View din, int din_acc, const BnRec& bn_out, const PwFuse& fuse) {
-    PRef w = param(M_TRUNK, prefix + ".w", {1, 1, Cin, Cout}, true);
-    PRef b = param(M_TRUNK, prefix + ".b", {Cout}, true);
-    const int G = cfg_.T, Mg = rows / G;
+void Learner::add_pw(std::vector<Op>& ops, const PwConv& c, const ConvPlan& plan, const BnRec& bn_in, const BnRec& bn_out) {
+    PwEmit e{c, plan, bn_in, bn_out};
+    const PRef w = e.w = param(M_TRUNK, c.name + ".w", {1, 1, c.Cin, c.Cout}, true);
+    const PRef b = e.b = param(M_TRUNK, c.name + ".b", {c.Cout}, true);
+    const int G = cfg_.T, rows = c.rows, Mg = rows / G, Cin = c.Cin, Cout = c.Cout, at = at_, nb_fwd = plan.stats_nb;
     Scratch* sc = build_scr_;           // statistics / BatchNorm-sum partials: the scratch of the stream this op's forward runs on (the shortcut
                                         // branch of a stride-2 unit runs beside the main branch and has its own)
-    // compute mode 1 (configuration 3): every 1x1 convolution of the tower multiplies bf16-rounded operands -- forward,
-    // backward-data and filter gradient: the fused kernels in their BF variant, the plain wide ones through gemm_x3's
-    // single-plane form, the filter gradients through tn_direct's BF variant
     const bool bfc = cfg_.compute >= 1;
-    const int at = at_;
-    const bool anorm = (bool)fuse.bn_in, bb = fuse.bwd != PwBwd::Plain, fbwd = pw_fused(fuse.bwd), wbw = fuse.bwd == PwBwd::Wide;
-    const bool fin = fuse.bwd == PwBwd::FusedFin;
-    const float *pro_stats = fuse.bn_in.stats, *bwd_ey = fuse.bn_in.x.p;      // (null without a BatchNorm in front)
-    // forward on the bf16 matrix pipe (exact three-way operand split, gemm_pw_x3.hip) where the shape allows it
-    static const bool x3_env = env_on("CDRL_PW_X3");
-    const bool x3_shape = (Cin <= 128 && Cout <= 128) || pw_fwd_x3_wide(G, Mg, Cout, Cin);
-    // (dry build: `in.p` is null, which counts as aligned -- as every tens_a tensor is, dense and 256-byte aligned)
-    const bool x3f = !bfc && x3_env && fuse.fwd_pw && x3_shape && pw_x3_supported(in, Cout, Cin);
-    const void* w3f = x3f ? pw_x3_packed(w.p, Cin, Cout, Cout, 1) : nullptr;
-    if (fuse.fwd_pw && pw_fwd_x3_wide(G, Mg, Cout, Cin) && !x3f)
-        build_fail("%s: the wide split-precision forward needs 16-byte aligned input rows (ld %d, offset %d)", prefix.c_str(), in.ld, in.coff);
-    const int nb_fwd = pw_fwd_nbpg(G, Mg, Cout, Cin);
-    // plain (unfused) wide convs -- the 464 -> 768 head conv, the 232-wide shortcut conv -- on the bf16 matrix pipe too (gemm_x3.hip)
-    const bool wide = Cin >= 128 || Cout > 128;
-    const bool g3 = bfc || (x3_env && wide);
-    const bool use_g3f = g3 && !fuse.fwd_pw && gemm_x3_supported(in, Cin);
-    const bool use_g3b = g3 && !fuse.bwd_pw && !bb && Cout % 4 == 0;
-    const void* g3f = use_g3f ? gemm_x3_packed(w.p, Cin, Cout, Cout, 1) : nullptr;
-    const void* g3b = (use_g3b && !frozen()) ? gemm_x3_packed(w.p, Cout, Cin, 1, Cout) : nullptr;       // (frozen: no backward)
-    if (bfc && ((!fuse.fwd_pw && !use_g3f) || (!fuse.bwd_pw && !bb && !use_g3b) || (bb && !fuse.bwd_pw)))
-        build_fail("bf16-operand mode: 1x1 convolution %s (%d -> %d, fwd %d bwd %d bb %d; input ld %d coff %d) has no bf16 kernel",
-                   prefix.c_str(), Cin, Cout, (int)fuse.fwd_pw, (int)fuse.bwd_pw, (int)bb, in.ld, in.coff);
-    const float* wpf = (fuse.fwd_pw && !x3f) ? pw_packed(w.p, Cin, Cout, Cout, 1, bfc) : nullptr;      // forward: B(k = cin, n = cout)
-    // backward operands: W^T in float32-MFMA fragment order for the persistent kernel, as three bf16 planes for the fused and the wide
-    // form (a frozen trunk has no backward and packs nothing)
-    const float* wpb = (fuse.bwd_pw && !fbwd && !wbw && !frozen()) ? pw_packed(w.p, Cout, Cin, 1, Cout, bfc) : nullptr;
-    const void* wpx = ((fbwd || wbw) && !frozen()) ? pw_x3_packed(w.p, Cout, Cin, 1, Cout) : nullptr;      // B(k = cout, n = cin)
-    const int tn_groups = (anorm || bb) ? G : 1;
-    note_scratch(0, 0, (size_t)rows * Cout, (size_t)gemm_tn_part_elems(rows, Cout, Cin, tn_groups));
-    if (fuse.epi_stats) note_scratch((size_t)G * nb_fwd * 2 * Cout, 0, 0, 0);
-    if (anorm && !fbwd) note_scratch((size_t)G * pw_bwd_nbpg(G, Mg, Cin, Cout) * 2 * Cin, 0, 0, 0);     // backward-data epilogue: its sums
-    Op op;
-    op.fwd = [=](hipStream_t st, int) -> int {
-        if (x3f)
-            return pw_x3(in, pro_stats, w3f, b.p, make_view(y, Cout), G, Mg, Cout, Cin, fuse.epi_stats ? sc->part : nullptr, st,
-                         nb_fwd);
-        if (fuse.fwd_pw)
-            return pw_nn(in, pro_stats, w.p, Cout, 1, b.p, make_view(y, Cout), 0, G, Mg, Cout, Cin, fuse.epi_stats ? 1 : 0,
-                         nullptr, nullptr, sc->part, st, nullptr, wpf, bfc, at);
-        if (g3f) return gemm_x3(in, g3f, b.p, make_view(y, Cout), rows, Cout, Cin, 0, st, bfc, at);
-        return gemm_nn(in, w.p, Cout, 1, b.p, make_view(y, Cout), rows, Cout, Cin, 0, st);
-    };
-    const int nbp_bwd = bb ? pw_bwd_nbpg(G, Mg, Cin, Cout) : 0;
-    if (bb) note_scratch(0, (size_t)G * nbp_bwd * Cout, 0, 0);
-    const View dz_view = fuse.bb_dz.ld ? fuse.bb_dz : make_view(nullptr, Cout);
-    if (wbw && !pw_x3_wide_bwd_supported(dz_view, din, Cin, Cout, fuse.bb_shuffle))
-        build_fail("%s: the wide split-precision backward needs even / 16-byte aligned gradient rows (ld %d, offset %d, shuffle %d)", prefix.c_str(),
-                   dz_view.ld, dz_view.coff, fuse.bb_shuffle);
+    const bool fbwd = pw_fused(plan.bwd), two_kernel = plan.bwd == PwBwd::Plain || plan.bwd == PwBwd::Prologue;
+    const float* pro_stats = bn_in.stats;      // (null without a BatchNorm in front)
+    const View in = c.in, yv = make_view(c.y, Cout);
+    // operands in fragment order, only those the plan's kernels read.  Forward: B(k = cin, n = cout).  Backward, B(k = cout, n = cin): W^T in
+    // float32-MFMA fragment order for the persistent kernel, as three bf16 planes for the fused and the wide form (a frozen trunk has no
+    // backward and packs nothing)
+    const void* w3f = plan.fwd == PwGemm::X3 ? pw_x3_packed(w.p, Cin, Cout, Cout, 1) : nullptr;
+    const void* g3f = plan.fwd == PwGemm::GemmX3 ? gemm_x3_packed(w.p, Cin, Cout, Cout, 1) : nullptr;
+    if (plan.dgrad == PwGemm::GemmX3 && !frozen()) e.g3b = gemm_x3_packed(w.p, Cout, Cin, 1, Cout);
+    const float* wpf = plan.fwd == PwGemm::PwNN ? pw_packed(w.p, Cin, Cout, Cout, 1, bfc) : nullptr;
+    if (plan.dgrad == PwGemm::PwNN && two_kernel && !frozen()) e.wpb = pw_packed(w.p, Cout, Cin, 1, Cout, bfc);
+    if (!two_kernel && !frozen()) e.wpx = pw_x3_packed(w.p, Cout, Cin, 1, Cout);
+    note_scratch(0, 0, (size_t)rows * Cout, (size_t)gemm_tn_part_elems(rows, Cout, Cin, (plan.bn_in || plan.bwd != PwBwd::Plain) ? G : 1));
+    if (nb_fwd) note_scratch((size_t)G * nb_fwd * 2 * Cout, 0, 0, 0);
+    if (plan.bn_in && !fbwd) note_scratch((size_t)G * plan.bwd_nb * 2 * Cin, 0, 0, 0);     // backward-data epilogue: its sums
+    if (plan.bwd != PwBwd::Plain) note_scratch(0, (size_t)G * plan.bwd_nb * Cout, 0, 0);
     if (fbwd) {
         max_qpart_ = std::max(max_qpart_, (size_t)pw_bwd_fused_qpart_elems(G, Mg, Cout, Cin, at));
         max_dbpart_ = std::max(max_dbpart_, (size_t)pw_bwd_fused_dbpart_elems(G, Mg, Cout, Cin, at));
     }
-    if (fin && bn_out.bwd_nb <= 0) build_fail("%s: finalize on load without the BatchNorm's scratch block", prefix.c_str());
-    const float *o_stats = bn_out.stats, *o_coef = bn_out.coef;
-    float *o_dgamma = bn_out.gamma.g, *o_dbeta = bn_out.beta.g;
-    Scratch* o_scr = bn_out.scr;
-    const int o_rows = bn_out.G * bn_out.nb, o_bwd_nb = bn_out.bwd_nb;
-    op.bwd = [=](hipStream_t st) -> int {
-        if (fbwd) {
-            if (fuse.bb_claim_slot) CDRL_TRY(next_slot(st));
-            PwBwdFused f;
-            f.dz = fuse.bb_dz.ld ? fuse.bb_dz : make_view(dys_[slot_], Cout);
-            f.dz_shuffle = fuse.bb_shuffle;
-            f.act = fuse.bb_act;
-            f.y = y;
-            f.stats = o_stats;
-            f.coef = o_coef;
-            f.a = in;
-            f.a_stats = pro_stats;
-            f.a_gamma = fuse.bn_in.gamma.p;
-            f.a_beta = fuse.bn_in.beta.p;
-            f.a_dgamma = fuse.bn_in.gamma.g;
-            f.a_dbeta = fuse.bn_in.beta.g;
-            f.a_coef = fuse.bn_in.coef;
-            f.W = w.p;
-            f.Wp = wpx;
-            f.da = din;
-            f.accumulate = din_acc;
-            f.dW = w.g;
-            f.db = b.g;
-            CDRL_TRY(next_q(st));
-            const int qi = qi_;
-            f.qpart = qparts_[qi];
-            f.dbpart = dbparts_[qi];
-            if (fin) {
-                f.fin_part = o_scr->part;
-                f.fin_nb = o_bwd_nb;
-                f.fin_tot = fintots_[qi];
-                f.o_dgamma = o_dgamma;
-                f.o_dbeta = o_dbeta;
-            }
-            f.G = G;
-            f.Mg = Mg;
-            f.N = Cout;
-            f.K = Cin;
-            f.at = at;
-            CDRL_TRY(pw_bwd_fused(f, st));
-            // the reduce also finalizes the BatchNorm in front of the conv (its coefficients are the next kernel's input): critical
-            // stream; without one it only produces weight gradients -> side stream, flushed once per unit
-            if (anorm) return pw_bwd_fused_reduce(f, st);
-            CDRL_TRY(defer_side(st, [=](hipStream_t sd) -> int {
-                CDRL_TRY(pw_bwd_fused_reduce(f, sd));
-                if (side_enabled_ && sd == side_) {     // the buffer pair is free again once this reduce has run
-                    CDRL_HIP(hipEventRecord(ev_q_[qi], sd));
-                    q_seq_[qi] = note_side_record(ev_q_[qi]);
-                    q_used_[qi] = true;
-                }
-                return 0;
-            }));
-            return flush_side(st);
+    if (plan.bwd == PwBwd::FusedFin && bn_out.bwd_nb <= 0) build_fail("%s: finalize on load without the BatchNorm's scratch block", c.name.c_str());
+    Op op;
+    op.fwd = [=](hipStream_t st, int) -> int {
+        switch (plan.fwd) {
+            case PwGemm::X3: return pw_x3(in, pro_stats, w3f, b.p, yv, G, Mg, Cout, Cin, sc->part, st, nb_fwd);
+            case PwGemm::PwNN:
+                return pw_nn(in, pro_stats, w.p, Cout, 1, b.p, yv, 0, G, Mg, Cout, Cin, 1, nullptr, nullptr, sc->part, st, nullptr, wpf, bfc, at);
+            case PwGemm::GemmX3: return gemm_x3(in, g3f, b.p, yv, rows, Cout, Cin, 0, st, bfc, at);
+            default: return gemm_nn(in, w.p, Cout, 1, b.p, yv, rows, Cout, Cin, 0, st);
         }
-        if (bb) {
-            // BN-backward apply fused into the operand loads: dz (+ raw y, statistics, coefficients) instead of dy
-            if (fuse.bb_claim_slot) CDRL_TRY(next_slot(st));
-            const View dz = fuse.bb_dz.ld ? fuse.bb_dz : make_view(dys_[slot_], Cout);
-            hipStream_t side = fork_side(st);
-            TnBnBwd tb{y, o_stats, o_coef, fuse.bb_shuffle, fuse.bb_act};
-            CDRL_TRY(gemm_tn(in, dz, w.g, rows, Cout, Cin, tns_[slot_], 0, side, G, pro_stats, &tb, bfc, at));
-            CDRL_TRY(done_side(side));
-            PwBnBwd pb{y, o_stats, o_coef, fuse.bb_shuffle, fuse.bb_act, part2s_[slot_]};
-            if (wbw)
-                CDRL_TRY(pw_x3_wide_bwd(dz, pb, wpx, din, din_acc, G, Mg, Cin, Cout, bwd_ey, pro_stats, anorm ? sc->part : nullptr, st));
-            else
-                CDRL_TRY(pw_nn(dz, nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout, anorm ? 2 : 0, bwd_ey, pro_stats, sc->part,
-                               st, &pb, wpb, bfc, at));
-            // bias gradient = column sums of the (virtual) dy, reduced from the GEMM's partials: rides on the next fork
-            double* p2 = part2s_[slot_];
-            return defer_side(st, [=](hipStream_t sd) -> int { return reduce_partials(p2, G * nbp_bwd, Cout, Cout, b.g, 0, sd); });
+    };
+    op.bwd = fbwd ? pw_bwd_fused_op(e) : plan.bwd == PwBwd::Plain ? pw_bwd_plain_op(e) : pw_bwd_prologue_op(e);
+    ops.push_back(op);
+}
+
+// Fused / FusedFin: one kernel for backward-data, filter and bias gradient, then its reduce.  Everything but the scratch slot and the ring
+// entry is known when the op is built.
+std::function<int(hipStream_t)> Learner::pw_bwd_fused_op(const PwEmit& e) {
+    const PwConv& c = e.c;
+    const bool fin = e.plan.bwd == PwBwd::FusedFin, on_main = e.plan.bn_in;
+    PwBwdFused f0;
+    f0.dz = c.dz, f0.dz_shuffle = c.dz_shuffle, f0.act = c.dz_act;
+    f0.y = c.y, f0.stats = e.bn_out.stats, f0.coef = e.bn_out.coef;
+    f0.a = c.in, f0.a_stats = e.bn_in.stats, f0.a_coef = e.bn_in.coef;
+    f0.a_gamma = e.bn_in.gamma.p, f0.a_beta = e.bn_in.beta.p, f0.a_dgamma = e.bn_in.gamma.g, f0.a_dbeta = e.bn_in.beta.g;
+    f0.W = e.w.p, f0.Wp = e.wpx, f0.dW = e.w.g, f0.db = e.b.g;
+    f0.da = c.din, f0.accumulate = c.din_acc;
+    f0.G = cfg_.T, f0.Mg = c.rows / cfg_.T, f0.N = c.Cout, f0.K = c.Cin, f0.at = at_;
+    if (fin) f0.fin_nb = e.bn_out.bwd_nb, f0.o_dgamma = e.bn_out.gamma.g, f0.o_dbeta = e.bn_out.beta.g;
+    Scratch* o_scr = e.bn_out.scr;
+    return [=](hipStream_t st) -> int {
+        PwBwdFused f = f0;
+        if (f.dz.ld) CDRL_TRY(next_slot(st));
+        else f.dz = make_view(dys_[slot_], f.N);
+        CDRL_TRY(next_q(st));
+        const int qi = qi_;
+        f.qpart = qparts_[qi];
+        f.dbpart = dbparts_[qi];
+        if (fin) {
+            f.fin_part = o_scr->part;
+            f.fin_tot = fintots_[qi];
         }
-        float* dy = dys_[slot_];
+        CDRL_TRY(pw_bwd_fused(f, st));
+        // the reduce also finalizes the BatchNorm in front of the conv (its coefficients are the next kernel's input): critical
+        // stream; without one it only produces weight gradients -> side stream, flushed once per unit
+        if (on_main) return pw_bwd_fused_reduce(f, st);
+        CDRL_TRY(defer_side(st, [=](hipStream_t sd) -> int {
+            CDRL_TRY(pw_bwd_fused_reduce(f, sd));
+            return release_q(qi, sd);
+        }));
+        return flush_side(st);
+    };
+}
+
+// Prologue / Wide: BN-backward apply fused into the operand loads of two kernels, dz (+ raw y, statistics, coefficients) instead of dy;
+// filter gradient on the side stream, backward-data on the critical one
+std::function<int(hipStream_t)> Learner::pw_bwd_prologue_op(const PwEmit& e) {
+    const int G = cfg_.T, rows = e.c.rows, Mg = rows / G, Cin = e.c.Cin, Cout = e.c.Cout, at = at_, din_acc = e.c.din_acc, nb = e.plan.bwd_nb;
+    const bool bfc = cfg_.compute >= 1, wide = e.plan.bwd == PwBwd::Wide, bn_in = e.plan.bn_in;
+    Scratch* sc = build_scr_;
+    const View in = e.c.in, din = e.c.din, dz0 = e.c.dz;
+    const float *pro_stats = e.bn_in.stats, *bwd_ey = e.bn_in.x.p;      // (null without a BatchNorm in front)
+    const TnBnBwd tb{e.c.y, e.bn_out.stats, e.bn_out.coef, e.c.dz_shuffle, e.c.dz_act};
+    const PRef w = e.w, b = e.b;
+    const float* wpb = e.wpb;
+    const void* wpx = e.wpx;
+    return [=](hipStream_t st) -> int {
+        if (dz0.ld) CDRL_TRY(next_slot(st));
+        const View dz = dz0.ld ? dz0 : make_view(dys_[slot_], Cout);
+        hipStream_t side = fork_side(st);
+        CDRL_TRY(gemm_tn(in, dz, w.g, rows, Cout, Cin, tns_[slot_], 0, side, G, pro_stats, &tb, bfc, at));
+        CDRL_TRY(done_side(side));
+        PwBnBwd pb{tb.y, tb.stats, tb.coef, tb.shuffle_ctot, tb.act, part2s_[slot_]};
+        if (wide)
+            CDRL_TRY(pw_x3_wide_bwd(dz, pb, wpx, din, din_acc, G, Mg, Cin, Cout, bwd_ey, pro_stats, bn_in ? sc->part : nullptr, st));
+        else
+            CDRL_TRY(pw_nn(dz, nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout, bn_in ? 2 : 0, bwd_ey, pro_stats, sc->part, st, &pb,
+                           wpb, bfc, at));
+        // bias gradient = column sums of the (virtual) dy, reduced from the GEMM's partials: rides on the next fork
+        double* p2 = part2s_[slot_];
+        return defer_side(st, [=](hipStream_t sd) -> int { return reduce_partials(p2, G * nb, Cout, Cout, b.g, 0, sd); });
+    };
+}
+
+// Plain: dy is in the current scratch slot (left there by the BatchNorm behind the conv, with its column sums per block)
+std::function<int(hipStream_t)> Learner::pw_bwd_plain_op(const PwEmit& e) {
+    const int G = cfg_.T, rows = e.c.rows, Mg = rows / G, Cin = e.c.Cin, Cout = e.c.Cout, at = at_, din_acc = e.c.din_acc;
+    const int o_rows = e.bn_out.G * e.bn_out.nb, tn_groups = e.plan.bn_in ? G : 1, epi = e.plan.bn_in ? 2 : 0;
+    const bool bfc = cfg_.compute >= 1;
+    const PwGemm dgrad = e.plan.dgrad;
+    Scratch* sc = build_scr_;
+    const View in = e.c.in, din = e.c.din;
+    const float *pro_stats = e.bn_in.stats, *bwd_ey = e.bn_in.x.p;      // (null without a BatchNorm in front)
+    const PRef w = e.w, b = e.b;
+    const float* wpb = e.wpb;
+    const void* g3b = e.g3b;
+    return [=](hipStream_t st) -> int {
+        const View dy = make_view(dys_[slot_], Cout);
         // side stream: bias gradient (column sums of dy, reduced per block by bn_bwd_apply) + filter gradient
         hipStream_t side = fork_side(st);
         CDRL_TRY(reduce_partials(part2s_[slot_], o_rows, Cout, Cout, b.g, 0, side));
-        CDRL_TRY(gemm_tn(in, make_view(dy, Cout), w.g, rows, Cout, Cin, tns_[slot_], 0, side, tn_groups, pro_stats, nullptr, bfc, at));
+        CDRL_TRY(gemm_tn(in, dy, w.g, rows, Cout, Cin, tns_[slot_], 0, side, tn_groups, pro_stats, nullptr, bfc, at));
         CDRL_TRY(done_side(side));
         // main stream: the critical path to the previous layer
-        if (din.p) {
-            if (fuse.bwd_pw)
-                return pw_nn(make_view(dy, Cout), nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout,
-                             anorm ? 2 : 0, bwd_ey, pro_stats, sc->part, st, nullptr, wpb, bfc, at);
-            if (g3b) return gemm_x3(make_view(dy, Cout), g3b, nullptr, din, rows, Cin, Cout, din_acc, st, bfc, at);
-            CDRL_TRY(gemm_nn(make_view(dy, Cout), w.p, 1, Cout, nullptr, din, rows, Cin, Cout, din_acc, st));
-        }
-        return 0;
+        if (!din.p) return 0;
+        if (dgrad == PwGemm::PwNN)
+            return pw_nn(dy, nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout, epi, bwd_ey, pro_stats, sc->part, st, nullptr, wpb, bfc, at);
+        if (dgrad == PwGemm::GemmX3) return gemm_x3(dy, g3b, nullptr, din, rows, Cin, Cout, din_acc, st, bfc, at);
+        return gemm_nn(dy, w.p, 1, Cout, nullptr, din, rows, Cin, Cout, din_acc, st);
     };
-    ops.push_back(op);
 }
 
 void Learner::add_dw(std::vector<Op>& ops, const std::string& prefix, View in, int N, int H, int W, int C, int stride,
@@ -886,9 +892,9 @@ Learner::BnRec Learner::add_dw_block(std::vector<Op>& ops, const DwBlock& d) {
     PRef b = param(M_TRUNK, d.dw + ".b", {C}, true);
     const BnRec post = make_bn(M_TRUNK, d.bn_post, make_view(y2, C), G, Mo, C, ACT_NONE);
     const View out = d.out, dout = d.dout, din = d.din;
-    const int pre_stats_nb = d.pre_stats_nb, post_bwd_nb = d.post_bwd_nb;
-    const bool pre_apply_by_conv = d.pre_conv != PwBwd::Plain, pre_fin_by_conv = d.pre_conv == PwBwd::FusedFin;
-    const bool post_on_load = d.post_on_load, post_bwd_by_conv = pw_fused(d.post_conv);
+    const int pre_stats_nb = d.pre_conv.stats_nb, post_bwd_nb = d.post_conv.bwd_nb;
+    const bool pre_apply_by_conv = d.pre_conv.bwd != PwBwd::Plain, pre_fin_by_conv = d.pre_conv.bwd == PwBwd::FusedFin;
+    const bool post_on_load = d.post_conv.bn_in, post_bwd_by_conv = pw_fused(d.post_conv.bwd);
     const int nb_in = vcol_geom(Mi, C).nb, nb_out = post.nb;
     const int nbf = dwf_geom(B, G, H, W, C, stride).nb;              // partial rows of the forward kernel (BN2 statistics) ...
     const int nbb = dwf_geom(B, G, H, W, C, stride).nb_bwd;          // ... and of the backward (BN1 sums, filter partials)
@@ -975,23 +981,13 @@ void Learner::add_half(std::vector<Op>& ops, const Half& h) {
         // the conv's epilogue; backward: the BatchNorm-backward of the last one as the conv's operand prologue (gathered through the
         // shuffle map), the middle one's backward sums out of the conv backward -- the fused form's reduce kernel, else the
         // backward-data epilogue
-        PwFuse f;
-        f.fwd_pw = f.epi_stats = f.bwd_pw = true;
-        if (h.bb) {
-            f.bwd = pw_bwd_form(y2.v(), a2.gv(), o3.dout, Mg_out, Cm, Co, true);
-            f.bb_dz = o3.dout;
-            f.bb_shuffle = Ct;
-            f.bb_act = ACT_RELU6;
-            f.bb_claim_slot = true;
-        }
-        d.post_on_load = true;
-        d.post_bwd_nb = pw_bwd_nbpg(T, Mg_out, Cm, Co);
-        d.post_conv = f.bwd;
-        f.bn_in = add_dw_block(ops, d);
+        const PwConv conv{pw, y2.v(), rows_out, Cm, Co, y3.p, a2.gv(), 0, o3.dout, Ct, ACT_RELU6};
+        const ConvPlan plan = plan_pw(conv, true, h.bb, true);
+        d.post_conv = plan;
+        const BnRec mid = add_dw_block(ops, d);
         const BnRec last = pw_bn(pw, Cm, Co, bn_out, y3.p, Mg_out, ACT_RELU6);
-        add_pw(ops, pw, y2.v(), rows_out, Cm, Co, y3.p, a2.gv(), 0, last, f);
-        o3.stats_nb = pw_fwd_nbpg(T, Mg_out, Co, Cm);
-        o3.conv = f.bwd;
+        add_pw(ops, conv, plan, mid, last);
+        o3.conv = plan;
         add_bn(ops, last, o3);
         return;
     }
@@ -1015,7 +1011,8 @@ void Learner::add_half(std::vector<Op>& ops, const Half& h) {
         add_bn(ops, make_bn(M_TRUNK, bn_mid, y2.v(), T, Mg_out, Cm, ACT_NONE), o2);
     }
     const BnRec last = pw_bn(pw, Cm, Co, bn_out, y3.p, Mg_out, ACT_RELU6);
-    add_pw(ops, pw, a2.v(), rows_out, Cm, Co, y3.p, a2.gv(), 0, last, PwFuse());
+    const PwConv conv{pw, a2.v(), rows_out, Cm, Co, y3.p, a2.gv()};
+    add_pw(ops, conv, plan_pw(conv, false, false, false), BnRec(), last);
     add_bn(ops, last, o3);
 }
 
@@ -1241,15 +1238,13 @@ void Learner::build_trunk(std::vector<Op>& ops) {
             return stem_fwd(in_image_, w.p, b.p, y.p, B, T, H, W, Cs, st);
         };
         const bool stem_fused = stem_bwd_fused_supported(Cs) && env_on("CDRL_FUSED_STEM");
-        // blocks of the stem BatchNorm (allocated here: the stem conv's backward consumes them in the fused form)
-        float* stem_stats = alloc((size_t)4 * T * Cs);
-        float* stem_coef = alloc((size_t)3 * T * Cs);
+        // the stem BatchNorm (made here: the stem conv's backward consumes its blocks in the fused form)
+        const BnRec sbn = make_bn(M_TRUNK, "img.stem.bn", y.v(), T, B * Hs * Ws, Cs, ACT_RELU6);
+        float *stem_stats = sbn.stats, *stem_coef = sbn.coef;
         const int Hp0 = same_out_h(Hs, 2), Wp0 = same_out_h(Ws, 2);
         Tens pool = tens_a(N * Hp0 * Wp0, c.stem);
         if (at && !stem_fused) build_fail("bf16 activation storage needs the fused stem backward (stem channels %d, CDRL_FUSED_STEM)", Cs);
         uint8_t* argmax = reinterpret_cast<uint8_t*>(alloc(((size_t)N * Hp0 * Wp0 * c.stem + 3) / 4));
-        note_named("img.stem.bn.stats", stem_stats, (size_t)4 * T * Cs * sizeof(float));
-        note_named("img.stem.bn.x", y.p, (size_t)N * Hs * Ws * Cs * esz());
         note_named("img.stem.pool.argmax", argmax, (size_t)N * Hp0 * Wp0 * Cs);
         note_named("img.stem.pool.out", pool.p, (size_t)N * Hp0 * Wp0 * Cs * esz());
         note_named("img.stem.pool.out.g", pool.g, (size_t)N * Hp0 * Wp0 * Cs * esz());
@@ -1274,15 +1269,9 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         // BN backward gathers its incoming gradient straight from the pooled gradient through the argmax.
         const int Hp = Hp0, Wp = Wp0;
         {
-            const int G = T, Mg = B * Hs * Ws, C = c.stem;
-            PRef gamma = param(M_TRUNK, "img.stem.bn.gamma", {C}, true);
-            PRef beta = param(M_TRUNK, "img.stem.bn.beta", {C}, true);
-            PRef mm = param(M_TRUNK, "img.stem.bn.moving_mean", {C}, false);
-            PRef mv = param(M_TRUNK, "img.stem.bn.moving_var", {C}, false);
-            float* stats = stem_stats;
-            note_bn_inference(gamma.p, beta.p, mm.p, mv.p, stats, G, C);
-            float* coef = stem_coef;
-            const int nb = vcol_geom(Mg, C).nb;
+            const int G = sbn.G, Mg = sbn.Mg, C = sbn.C, nb = sbn.nb;
+            const PRef gamma = sbn.gamma, beta = sbn.beta, mm = sbn.mm, mv = sbn.mv;
+            float *stats = sbn.stats, *coef = sbn.coef;
             const int nb_pool = vcol_geom(B * Hp * Wp, C).nb;
             note_scratch((size_t)G * std::max(std::max(nb, nb_pool), nb_stem) * 2 * C, (size_t)G * nb * C, 0, 0);
             View yv = y.v();
@@ -1376,21 +1365,17 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                 //  CU-masking the side stream re-measured at v33: 224 / 192 / 128 CUs -> 21.2 / 21.2 / 23.5 vs 18.7 ms)
                 const bool bb1 = fpw && fused_bb_ && gemm_tn_dpro_supported(mid);
                 const bool bb3 = fpw && fused_bb_ && gemm_tn_dpro_supported(main_out);
-                // order: blocks of bn1, backward form of pw1, then the ops (pw1; bn1, dw, bn2, pw2, bn3 from add_half)
+                // order: blocks of bn1, plan of pw1, then the ops (pw1; bn1, dw, bn2, pw2, bn3 from add_half)
                 BnRec bn1 = pw_bn(pre + ".pw1", main_in, mid, pre + ".bn1", y1.p, Mg_in, ACT_RELU6);
-                PwFuse f1;
-                if (fpw) {
-                    f1.fwd_pw = f1.epi_stats = f1.bwd_pw = true;
-                    // dz = the masked gradient the depthwise op leaves in the current scratch slot; BN1's backward sums come out of the
-                    // depthwise backward too
-                    if (bb1) f1.bwd = pw_bwd_form(xin, xg, make_view(nullptr, mid), Mg_in, main_in, mid, false);
-                    bn1.bwd_nb = dwf_geom(B, T, curH, curW, mid, stride).nb_bwd;
-                }
-                add_pw(ops, pre + ".pw1", xin, rows_in, main_in, mid, y1.p, xg, stride == 2 ? 1 : 0, bn1, f1);
+                // dz (default view) = the masked gradient the depthwise op leaves in the current scratch slot; BN1's backward sums come out
+                // of the depthwise backward too
+                const PwConv pw1{pre + ".pw1", xin, rows_in, main_in, mid, y1.p, xg, stride == 2 ? 1 : 0};
+                const ConvPlan p1 = plan_pw(pw1, fpw, bb1, false);
+                if (fpw) bn1.bwd_nb = dwf_geom(B, T, curH, curW, mid, stride).nb_bwd;
+                add_pw(ops, pw1, p1, BnRec(), bn1);
                 Half mh{pre, "dw", "bn2", "pw2", "bn3", DwBlock{y1.p, curH, curW, mid, stride}, out, sc_c};
                 mh.d.pre = bn1;
-                mh.d.pre_stats_nb = fpw ? pw_fwd_nbpg(T, Mg_in, mid, main_in) : 0;
-                mh.d.pre_conv = f1.bwd;
+                mh.d.pre_conv = p1;
                 mh.Cout = main_out;
                 mh.fused = fpw;
                 mh.bb = bb3;
@@ -1416,11 +1401,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                         Op jn;
                         jn.fwd = [=](hipStream_t st, int) -> int {
                             if (!side_enabled_) return 0;
-                            CDRL_HIP(hipEventRecord(ev_sc_done_[sc_ev], side_));
-                            CDRL_HIP(hipStreamWaitEvent(st, ev_sc_done_[sc_ev], 0));
-                            const uint64_t js = note_side_record(ev_sc_done_[sc_ev]);
-                            if (st == main_) main_waited_ = js;
-                            return 0;
+                            return join_side_at(st, ev_sc_done_[sc_ev]);
                         };
                         jn.bwd = [](hipStream_t) -> int { return 0; };
                         ops.push_back(jn);
@@ -1436,7 +1417,8 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         const int P = curH * curW, rows = N * P;
         Tens yh = tens_a(rows, c.last, false);
         const BnRec head_bn = pw_bn("img.head.conv", curC, c.last, "img.head.bn", yh.p, B * P, ACT_RELU6);
-        add_pw(ops, "img.head.conv", X.v(), rows, curC, c.last, yh.p, X.gv(), 0, head_bn, PwFuse());
+        const PwConv head{"img.head.conv", X.v(), rows, curC, c.last, yh.p, X.gv()};
+        add_pw(ops, head, plan_pw(head, false, false, false), BnRec(), head_bn);
         feat_ = tens(N, c.last);
         // BatchNorm + ReLU6 + GlobalAveragePooling2D as one op: the 12288 x 768 activated tensor and its gradient are never
         // written -- the forward pools on the fly, the backward reads the pooled gradient broadcast over the frame's pixels
