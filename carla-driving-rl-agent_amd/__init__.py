@@ -5,6 +5,7 @@ Sub-modules
   engine    LearnerEngine: parameter arenas + workspace as torch tensors, step functions
   synthetic deterministic synthetic rollout buffers
   train_stats  host side of the update diagnostics: ring rows -> the reference's log keys
+  learner_state  on-disk container of the full learner state (arenas, optimizer scalars, counters, generators)
   core, rl  host-side mirror of the reference's CARLAgent / CARLANetwork / PPOMemory API
 """
 __version__ = '0.1.0'

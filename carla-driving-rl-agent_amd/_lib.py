@@ -48,6 +48,12 @@ class HParams(C.Structure):
                 ('clip_norm_value', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float)]
 
 
+class OptimizerState(C.Structure):
+    """cdrl_optimizer_state (include/cdrl.h): the optimizers' device-side step counters and Nadam m_caches."""
+    _fields_ = [('t_policy', C.c_int32), ('t_value', C.c_int32), ('t_dynamics', C.c_int32),
+                ('m_cache_policy', C.c_float), ('m_cache_value', C.c_float), ('m_cache_dynamics', C.c_float)]
+
+
 _fp = C.c_void_p   # device pointers travel as plain addresses
 
 
@@ -97,6 +103,8 @@ PROTOTYPES = {
     'cdrl_learner_set_comm_stream': (_i, [_L, _fp]),
     'cdrl_learner_tail_offset': (_i64, [_L]),
     'cdrl_learner_reset_optimizer_steps': (_i, [_L, _fp]),
+    'cdrl_learner_get_optimizer_state': (_i, [_L, C.POINTER(OptimizerState), _fp]),
+    'cdrl_learner_set_optimizer_state': (_i, [_L, C.POINTER(OptimizerState), _fp]),
     'cdrl_learner_train_stats_layout': (_i, [_L, C.POINTER(TrainStatsLayout)]),
     'cdrl_learner_train_stats_buffer': (_i, [_L, C.POINTER(C.c_void_p), C.POINTER(_i64)]),
     'cdrl_learner_train_stats_reset': (_i, [_L, _fp]),

@@ -84,6 +84,8 @@ class FakeCARLAEnvironment(spaces.Env):
 
 
 class CARLAgent(PPOAgent):
+    _constructed = False        # load=True runs inside PPOAgent.__init__, before this class's counters and generators exist
+    _pending_state_meta = None
     DEFAULT_CONTROL = dict(units=320, num_layers=2, activation=utils.swish6)
     DEFAULT_CONTROL_VALUE = dict(units=320, num_layers=2, activation=utils.swish6)
     DEFAULT_DYNAMICS = dict(road=dict(units=16, num_layers=2, activation=relu6),
@@ -108,7 +110,10 @@ class CARLAgent(PPOAgent):
         all three from the one name (core/carla_agent.py:123-124); `polyak < 1` averages the policy / value heads, not the trunk.
         `batch_augment=True` (with `aug_intensity > 0` and an environment shard): the image stacks of all E environments are
         augmented by ONE batched call per step (Augmenter.batch) instead of one call per environment; plans, Philox offsets and
-        the augmented images are those of the per-environment loop, bit for bit."""
+        the augmented images are those of the per-environment loop, bit for bit.
+        `full_state=True` (Agent): save() also writes the full learner state and load() restores it when it is there, so that an
+        interrupted run continues bit for bit (save_state / load_state; without the keyword both behave as in the reference:
+        weights and config.json, fresh optimizers)."""
         assert aug_intensity >= 0.0
         network_spec = dict(kwargs.pop('network', {}))
         network_spec.setdefault('network', CARLANetwork)
@@ -138,6 +143,10 @@ class CARLAgent(PPOAgent):
         self._aug_calls = 0
         self._shard, self._info_segments = [self.env], []
         self._init_data_parallel()
+        self._constructed = True
+        if self._pending_state_meta is not None:        # load=True with a full state: the host half waits for the fields above
+            meta, self._pending_state_meta = self._pending_state_meta, None
+            self.restore_host_state(meta)
 
     # -- data parallelism (reference loop rl/agents/ppo.py:190-226 inside :464-548) ------------------------------
     def _init_data_parallel(self):
@@ -223,6 +232,34 @@ class CARLAgent(PPOAgent):
         super().load()
         if getattr(self, 'data_parallel', False):       # (load=True in the constructor runs before _init_data_parallel, which broadcasts itself)
             self._dp_for(self.network.engine).broadcast_parameters()
+
+    # -- full state ----------------------------------------------------------------------------------------------------
+    def state_rank(self):
+        return self.rank if self.data_parallel else None
+
+    def host_state(self) -> dict:
+        """Agent.host_state plus this class's: the re-sampling Philox offset `_sample_offset`, the augmentation plan counter
+        `_aug_calls` and generator `_aug_rng`, and the rollout sampler's `action_index` / `sample_seed` (they live in the network
+        and differ per rank under data parallelism).  Generators saved in all: `rng`, `_aug_rng`, global `numpy.random`, global
+        `random`; the device samplers are counter-based (seed + offset) and have no other state."""
+        state = super().host_state()
+        state.update(sample_offset=int(self._sample_offset), aug_calls=int(self._aug_calls), aug_rng=self._aug_rng.bit_generator.state,
+                     action_index=int(self.network.action_index), sample_seed=int(self.network.sample_seed))
+        return state
+
+    def set_host_state(self, state: dict):
+        super().set_host_state(state)
+        self._sample_offset = int(state['sample_offset'])
+        self._aug_calls = int(state['aug_calls'])
+        self._aug_rng.bit_generator.state = state['aug_rng']
+        self.network.action_index = int(state['action_index'])
+        self.network.sample_seed = int(state['sample_seed'])
+
+    def restore_host_state(self, meta: dict):
+        if not self._constructed:
+            self._pending_state_meta = meta
+            return
+        super().restore_host_state(meta)
 
     def hyper_parameters(self) -> dict:
         hp = super().hyper_parameters()

@@ -233,6 +233,44 @@ class CARLANetwork(Network):
         if full:
             self.engine.update_old_policy()
 
+    def save_state(self, prefix: str, extra: dict = None):
+        """The full learner state under the directory `prefix` (learner_state.py: `learner_state.index` + data shards, then
+        `learner_state.json`): the engine's export_state() -- whole parameter arena with old_policy and the moving statistics, both
+        slot arenas, the six optimizer scalars, manifest -- plus the rollout sampler's Philox seed and offset (`sample_seed`,
+        `action_index`).  `extra`: JSON-able entries of the caller's that travel in the same JSON file (the agent's counters and
+        generators).  One host read of the device scalars and three arena copies; nothing on the step path changes."""
+        from .. import learner_state
+        state = self.engine.export_state()
+        opt = state['optimizer']
+        arrays = dict(params=state['params'], adam_m=state['adam_m'], adam_v=state['adam_v'],
+                      m_cache=np.asarray([opt['m_cache_policy'], opt['m_cache_value'], opt['m_cache_dynamics']], dtype=np.float32))
+        meta = dict(extra or {})
+        meta.update(manifest=state['manifest'], optimizer_steps=[opt['t_policy'], opt['t_value'], opt['t_dynamics']],
+                    action_index=int(self.action_index), sample_seed=int(self.sample_seed))
+        learner_state.save(prefix, arrays, meta)
+
+    def load_state(self, prefix: str) -> dict:
+        """Inverse of save_state; returns the JSON file's entries (the caller's `extra` among them).  Everything is read and
+        validated before anything is written (LearnerEngine.import_state).  old_policy comes back as it was saved -- after an
+        update() it is the policy BEFORE the last minibatch step, which is what the rollouts sample from -- so, unlike
+        load_weights, this does not end in update_old_policy()."""
+        from .. import learner_state
+        arrays, meta = learner_state.load(prefix)
+        for name in ('params', 'adam_m', 'adam_v', 'm_cache'):
+            if name not in arrays:
+                raise learner_state.LearnerStateError(f'{prefix}: array {name!r} is missing from the learner state')
+        t, mc = meta['optimizer_steps'], arrays['m_cache'].reshape(-1)
+        if len(t) != 3 or mc.shape[0] != 3:
+            raise learner_state.LearnerStateError(f'{prefix}: three step counters and three m_caches expected')
+        self.engine.import_state(dict(params=arrays['params'], adam_m=arrays['adam_m'], adam_v=arrays['adam_v'],
+                                      manifest=meta['manifest'],
+                                      optimizer=dict(t_policy=int(t[0]), t_value=int(t[1]), t_dynamics=int(t[2]),
+                                                     m_cache_policy=float(mc[0]), m_cache_value=float(mc[1]),
+                                                     m_cache_dynamics=float(mc[2]))))
+        self.action_index = int(meta['action_index'])
+        self.sample_seed = int(meta['sample_seed'])
+        return meta
+
     def summary(self):
         for model, title in (('policy', 'Policy Network'), ('value', 'Value Network'), ('trunk', 'Dynamics Model')):
             table = self.engine.tables[model]

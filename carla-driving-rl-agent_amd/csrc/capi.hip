@@ -350,6 +350,32 @@ int cdrl_learner_reset_optimizer_steps(cdrl_learner* l, void* stream) {
     return l->impl->reset_counters(S(stream));
 }
 
+int cdrl_learner_get_optimizer_state(const cdrl_learner* l, cdrl_optimizer_state* out, void* stream) {
+    CHECK_L(l);
+    if (!out) {
+        cdrl::set_error("cdrl_learner_get_optimizer_state: null output");
+        return -1;
+    }
+    int t[3];
+    float mc[3];
+    const int rc = l->impl->get_counters(t, mc, S(stream));
+    if (rc) return rc;
+    out->t_policy = t[0], out->t_value = t[1], out->t_dynamics = t[2];
+    out->m_cache_policy = mc[0], out->m_cache_value = mc[1], out->m_cache_dynamics = mc[2];
+    return 0;
+}
+
+int cdrl_learner_set_optimizer_state(cdrl_learner* l, const cdrl_optimizer_state* in, void* stream) {
+    CHECK_L(l);
+    if (!in) {
+        cdrl::set_error("cdrl_learner_set_optimizer_state: null state");
+        return -1;
+    }
+    const int t[3] = {in->t_policy, in->t_value, in->t_dynamics};
+    const float mc[3] = {in->m_cache_policy, in->m_cache_value, in->m_cache_dynamics};
+    return l->impl->set_counters(t, mc, S(stream));
+}
+
 int cdrl_learner_policy_forward_backward(cdrl_learner* l, const cdrl_policy_batch* b, float grad_scale, void* stream) {
     CHECK_L(l);
     if (!b) return -1;

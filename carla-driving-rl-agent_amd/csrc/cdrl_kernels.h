@@ -505,6 +505,9 @@ int clip_update(int opt, float polyak, float* p, const float* g, float* m, float
                 hipStream_t st, const double* chunk_part = nullptr, int ticked = 0);
 // counters to 0, Nadam m_caches to 1 (cdrl_learner_reset_optimizer_steps)
 int reset_steps(DevHP* hp, hipStream_t st);
+// counters to t[0..2] (policy, value, dynamics), Nadam m_caches to m_cache[0..2], passed to the kernel by value
+// (cdrl_learner_set_optimizer_state); the float block in front of t_policy is not written
+int set_steps(DevHP* hp, const int t[3], const float m_cache[3], hipStream_t st);
 int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, hipStream_t st);
 
 // ---------------------------------------------------------------- update diagnostics (train_stats.hip)

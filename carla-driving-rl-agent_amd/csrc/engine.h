@@ -103,6 +103,10 @@ public:
     DevHP* host_hp() { return &hp_host_; }
     int upload_hp(hipStream_t st);          // host hp block (lr, clip...) -> device, keeps device counters
     int reset_counters(hipStream_t st);
+    // the device block's three step counters and three Nadam m_caches (the owner's block after share_hp): get copies them behind
+    // everything on `st` and waits for the copy; set validates, then enqueues one one-thread kernel (no host sync)
+    int get_counters(int t[3], float m_cache[3], hipStream_t st);
+    int set_counters(const int t[3], const float m_cache[3], hipStream_t st);
 
     int policy_forward_backward(const PolicyBatch& b, float inv_world, hipStream_t st);
     // split form for the re-sampling loss (F8): forward -> (host samples u from alpha, beta) -> backward

@@ -10,7 +10,9 @@
 // Frames are ordered f = t*B + b, so each per-time-slice BatchNorm group is a contiguous row
 // range (F6); split / concat / channel_shuffle never materialise on their own: they are views
 // (ld, channel offset) plus a destination-index permutation in the BN-apply store (F7).
+#include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 
 #include "engine.h"
@@ -1796,6 +1798,45 @@ int Learner::upload_hp(hipStream_t st) {
 
 int Learner::reset_counters(hipStream_t st) {
     CDRL_TRY(reset_steps(hp_dev_, st));      // counters 0, Nadam m_caches 1
+    tail_invalidate(st);
+    return 0;
+}
+
+int Learner::get_counters(int t[3], float m_cache[3], hipStream_t st) {
+    if (!hp_dev_) {
+        set_error("get_optimizer_state: learner not bound");
+        return -1;
+    }
+    static_assert(offsetof(DevHP, m_cache_dynamics) + sizeof(float) == sizeof(DevHP) &&
+                      offsetof(DevHP, m_cache_policy) == offsetof(DevHP, t_policy) + 3 * sizeof(int),
+                  "DevHP ends in 3 int counters and 3 float m_caches");
+    unsigned char tail[sizeof(DevHP) - offsetof(DevHP, t_policy)];
+    CDRL_HIP(hipMemcpyAsync(tail, reinterpret_cast<const unsigned char*>(hp_dev_) + offsetof(DevHP, t_policy), sizeof(tail),
+                            hipMemcpyDeviceToHost, st));
+    tail_invalidate(st);
+    CDRL_HIP(hipStreamSynchronize(st));
+    memcpy(t, tail, 3 * sizeof(int));
+    memcpy(m_cache, tail + 3 * sizeof(int), 3 * sizeof(float));
+    return 0;
+}
+
+int Learner::set_counters(const int t[3], const float m_cache[3], hipStream_t st) {
+    if (!hp_dev_) {
+        set_error("set_optimizer_state: learner not bound");
+        return -1;
+    }
+    static const char* const names[3] = {"policy", "value", "dynamics"};
+    for (int i = 0; i < 3; ++i) {       // validate everything first: a refused state writes nothing
+        if (t[i] < 0) {
+            set_error("set_optimizer_state: t_%s = %d is negative", names[i], t[i]);
+            return -1;
+        }
+        if (!std::isfinite(m_cache[i]) || !(m_cache[i] > 0.0f)) {
+            set_error("set_optimizer_state: m_cache_%s = %g is not a finite positive number", names[i], (double)m_cache[i]);
+            return -1;
+        }
+    }
+    CDRL_TRY(set_steps(hp_dev_, t, m_cache, st));
     tail_invalidate(st);
     return 0;
 }

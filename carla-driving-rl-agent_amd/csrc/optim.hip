@@ -320,6 +320,23 @@ int reset_steps(DevHP* hp, hipStream_t st) {
     return 0;
 }
 
+// the six values travel by value (the caller's struct may be gone when the kernel runs); nothing in front of t_policy is written
+__global__ void set_steps_kernel(DevHP* hp, int t_policy, int t_value, int t_dynamics, float mc_policy, float mc_value,
+                                 float mc_dynamics) {
+    hp->t_policy = t_policy;
+    hp->t_value = t_value;
+    hp->t_dynamics = t_dynamics;
+    hp->m_cache_policy = mc_policy;
+    hp->m_cache_value = mc_value;
+    hp->m_cache_dynamics = mc_dynamics;
+}
+
+int set_steps(DevHP* hp, const int t[3], const float m_cache[3], hipStream_t st) {
+    hipLaunchKernelGGL(set_steps_kernel, dim3(1), dim3(1), 0, st, hp, t[0], t[1], t[2], m_cache[0], m_cache[1], m_cache[2]);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
 // two device-to-device copies as ONE launch of the library's own (old_policy <- policy: trainable and state slices): hipMemcpyAsync ran
 // two blit kernels of the runtime with their own fences in the middle of the apply
 __global__ void __launch_bounds__(256) copy_two_kernel(float* __restrict__ d0, const float* __restrict__ s0, int64_t n0,

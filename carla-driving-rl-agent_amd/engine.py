@@ -209,6 +209,85 @@ class LearnerEngine:
         self.adam_v.fill_(self.slot_init[1])
         _lib.check(self.lib.cdrl_learner_reset_optimizer_steps(self.h, self._stream()), 'reset_optimizer_steps')
 
+    # ------------------------------------------------------------------ full state (learner_state.py)
+    OPTIMIZER_SCALARS = ('t_policy', 't_value', 't_dynamics', 'm_cache_policy', 'm_cache_value', 'm_cache_dynamics')
+
+    def _need_device(self, what):
+        if self.device is None:
+            raise _lib.CdrlError(f'{what}: this engine was built with device=None (host-only inspection): it has no arenas and no '
+                                 f'device block to read or write')
+
+    def get_optimizer_state(self) -> dict:
+        """The three step counters (int) and the three Nadam m_caches (float32 values) of the device block this engine steps with
+        (the owner's under share_with): one small device-to-host copy behind everything on the current stream."""
+        self._need_device('get_optimizer_state')
+        st = _lib.OptimizerState()
+        _lib.check(self.lib.cdrl_learner_get_optimizer_state(self.h, C.byref(st), self._stream()), 'get_optimizer_state')
+        return {k: (int if k.startswith('t_') else float)(getattr(st, k)) for k in self.OPTIMIZER_SCALARS}
+
+    def set_optimizer_state(self, **values):
+        """Writes the six scalars (all of them: see OPTIMIZER_SCALARS), enqueued on the current stream with no host sync.  A
+        negative counter or an m_cache that is not finite and positive raises CdrlError and nothing is written."""
+        self._need_device('set_optimizer_state')
+        if set(values) != set(self.OPTIMIZER_SCALARS):
+            raise _lib.CdrlError(f'set_optimizer_state takes exactly {self.OPTIMIZER_SCALARS}, got {sorted(values)}')
+        st = _lib.OptimizerState()
+        for k in self.OPTIMIZER_SCALARS:
+            setattr(st, k, int(values[k]) if k.startswith('t_') else float(values[k]))
+        _lib.check(self.lib.cdrl_learner_set_optimizer_state(self.h, C.byref(st), self._stream()), 'set_optimizer_state')
+
+    def manifest(self) -> dict:
+        """What a saved state must agree with to fit this engine (learner_state.make_manifest): optimizer, polyak, parameter
+        tables.  Host only."""
+        from . import learner_state
+        return learner_state.make_manifest(self.optimizer, self.polyak, self.tables)
+
+    def export_state(self) -> dict:
+        """Everything the learner carries from one step to the next, as host copies: dict(params=, adam_m=, adam_v= flat float32
+        numpy arrays -- `params` is the whole arena: every model's trainable and state regions, old_policy and the BatchNorm moving
+        statistics included --, optimizer=the six scalars of get_optimizer_state, manifest=manifest()).  Three arena copies and
+        one small read; an engine built with share_with exports the owner's state (the same arenas and block)."""
+        self._need_device('export_state')
+        owner = getattr(self, '_hp_owner', None)
+        if owner is not None:
+            return owner.export_state()
+        opt = self.get_optimizer_state()            # (waits for the current stream: the arena copies below see finished steps)
+        return dict(params=self.params.detach().cpu().numpy().copy(), adam_m=self.adam_m.detach().cpu().numpy().copy(),
+                    adam_v=self.adam_v.detach().cpu().numpy().copy(), optimizer=opt, manifest=self.manifest())
+
+    def import_state(self, state: dict):
+        """Inverse of export_state.  Validates first and writes afterwards: a state whose optimizer or parameter tables differ
+        from this engine's, whose arenas have another size or type, or whose scalars the library would refuse raises CdrlError
+        naming the first difference, and no arena byte or counter has changed.  Batch size, compute mode, freeze_trunk and
+        train_stats of the exporting engine are free (the tables and region offsets do not depend on them)."""
+        self._need_device('import_state')
+        owner = getattr(self, '_hp_owner', None)
+        if owner is not None:
+            return owner.import_state(state)
+        from . import learner_state
+        diff = learner_state.manifest_difference(state.get('manifest', {}), self.manifest())
+        if diff is not None:
+            raise _lib.CdrlError(f'import_state: the state does not fit this engine -- {diff}')
+        arrays = {}
+        for name, dst in (('params', self.params), ('adam_m', self.adam_m), ('adam_v', self.adam_v)):
+            a = state.get(name)
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.shape != (dst.numel(),):
+                raise _lib.CdrlError(f'import_state: {name} must be a flat float32 array of {dst.numel()} elements, got '
+                                     f'{type(a).__name__} {getattr(a, "dtype", "")} {getattr(a, "shape", "")}')
+            arrays[name] = a
+        opt = state.get('optimizer', {})
+        if set(opt) != set(self.OPTIMIZER_SCALARS):
+            raise _lib.CdrlError(f'import_state: optimizer scalars {sorted(opt)} are not {sorted(self.OPTIMIZER_SCALARS)}')
+        for k in self.OPTIMIZER_SCALARS:            # the library's own rule, checked here so that the arenas are not written first
+            v = opt[k]
+            if k.startswith('t_') and not (isinstance(v, (int, np.integer)) and 0 <= int(v) < 2 ** 31):
+                raise _lib.CdrlError(f'import_state: {k} = {v!r} is not a step count')
+            if k.startswith('m_') and not (np.isfinite(np.float32(v)) and np.float32(v) > 0):
+                raise _lib.CdrlError(f'import_state: {k} = {v!r} is not a finite positive number')
+        for name, dst in (('params', self.params), ('adam_m', self.adam_m), ('adam_v', self.adam_v)):
+            dst.copy_(torch.from_numpy(arrays[name]))
+        self.set_optimizer_state(**opt)
+
     def _stats_owner(self):
         owner = getattr(self, '_hp_owner', None)
         return owner if owner is not None and owner.train_stats_layout['rows'] > 0 else self

@@ -15,7 +15,9 @@ class Agent:
     def __init__(self, env, batch_size: int, seed=None, weights_dir='weights', name='agent', log_mode='summary',
                  drop_batch_remainder=False, skip_data=0, consider_obs_every=1, evaluation_dir='evaluation',
                  shuffle_batches=False, shuffle=True, traces_dir: str = None, summary_keys: List[str] = None,
-                 device='cuda:0'):
+                 device='cuda:0', full_state=False):
+        """full_state=True: save() also writes, and load() also restores, the full learner state (save_state / load_state of the
+        subclass); the default writes and reads the weight checkpoints and config.json only."""
         if isinstance(env, str):
             raise ValueError('gym.make(env_id) is not supported: pass an environment object')
         self.env = env
@@ -41,6 +43,7 @@ class Agent:
                                  value=os.path.join(self.base_path, 'value_net'))
         self.config_path = os.path.join(self.base_path, 'config.json')
         self.config = dict()
+        self.full_state = bool(full_state)
         self.statistics = utils.Summary(mode=log_mode, name=name, keys=summary_keys)
 
     def set_random_seed(self, seed):
@@ -106,10 +109,37 @@ class Agent:
     def load(self):
         self.load_weights()
         self.load_config()
+        if self.full_state:
+            self.load_state(missing_ok=True)
 
     def save(self):
         self.save_weights()
         self.save_config()
+        if self.full_state:
+            self.save_state()
+
+    # -- full state (learner_state.py) ---------------------------------------------------------------
+    def host_state(self) -> dict:
+        """The host-side state of this class that a continued run needs, JSON-able: `seed` (set_random_seed and
+        seed_regularization change it; the device samplers' Philox seeds derive from it), the state of `rng` (minibatch shuffling)
+        and of the global `numpy.random` and `random` generators (seed_regularization draws from `numpy.random`).  Nothing in the
+        package draws from torch's generator."""
+        from ... import learner_state
+        return dict(seed=self.seed, rng=self.rng.bit_generator.state, numpy_random=learner_state.numpy_global_state(),
+                    python_random=learner_state.python_random_state(random))
+
+    def set_host_state(self, state: dict):
+        from ... import learner_state
+        self.seed = state['seed']
+        self.rng.bit_generator.state = state['rng']
+        learner_state.set_numpy_global_state(state['numpy_random'])
+        learner_state.set_python_random_state(random, state['python_random'])
+
+    def save_state(self):
+        raise NotImplementedError
+
+    def load_state(self, missing_ok=False):
+        raise NotImplementedError
 
     def load_weights(self):
         raise NotImplementedError

@@ -245,11 +245,13 @@ class PPOAgent(Agent):
                     # the writer's failure (disk full, permissions) must not leave the other ranks waiting in a bare barrier until the
                     # process-group timeout: the meeting point carries a status flag and every rank raises
                     failure = None
-                    if self.is_writer():
-                        try:
+                    try:
+                        if self.is_writer():
                             self.save()
-                        except Exception as exc:       # noqa: BLE001 -- re-raised below, on every rank
-                            failure = exc
+                        elif self.full_state:
+                            self.save_state()          # (a rank that is not the writer: its own counters and generators only)
+                    except Exception as exc:           # noqa: BLE001 -- re-raised below, on every rank
+                        failure = exc
                     self.rank_barrier(failed=failure is not None)
                     if failure is not None:
                         raise failure
@@ -450,6 +452,62 @@ class PPOAgent(Agent):
 
     def load_weights(self):
         self.network.load_weights()
+
+    # -- full state: bit-exact resume (learner_state.py) ----------------------------------
+    def state_rank(self) -> Optional[int]:
+        """Hook for data-parallel agents: this rank's number when every rank keeps host state of its own, else None."""
+        return None
+
+    def save_state(self):
+        """Writes the full learner state under `base_path` (save() does with full_state=True): the network's device state
+        (CARLANetwork.save_state: parameter arena with old_policy and the moving statistics, optimizer slots, step counters, Nadam
+        m_caches, rollout sampler offset) and this agent's host_state().  A later load_state() continues the run as if it had not
+        stopped: bit for bit, given an environment that is deterministic per episode or restores itself.
+        Not saved: the environment (the user's object), and rows pending in the rollout memory -- exact resume holds when the save
+        falls behind an update(), i.e. update_frequency=1 or save_every a multiple of update_frequency; otherwise the number of
+        rows left out is printed.  The DynamicParameter steps travel in config.json (save_config).
+        Data parallelism: the device state is identical on all ranks and written by the writer rank; every rank writes its own
+        `learner_state.rank<r>.json` (its counters and generators differ: rank-offset seeds, early episode ends)."""
+        from ... import learner_state
+        pending = len(self.memory) if self.memory is not None else 0
+        if pending:
+            print(f'[save_state] {pending} rollout rows pending in the memory are not saved: a run resumed from this state starts '
+                  f'the update period over')
+        host = self.host_state()
+        rank = self.state_rank()
+        if self.is_writer():
+            self.network.save_state(self.base_path, extra=dict(agent=host))
+        if rank is not None:
+            opt = self.network.engine.get_optimizer_state()
+            learner_state.save_rank(self.base_path, rank, dict(agent=host, optimizer_steps=[opt['t_policy'], opt['t_value'],
+                                                                                            opt['t_dynamics']]))
+
+    def load_state(self, missing_ok=False) -> bool:
+        """Restores what save_state wrote (load() does, after the weights, with full_state=True).  Without a state under
+        `base_path`: LearnerStateError, or with missing_ok one printed line and False -- the first stage of a curriculum loads
+        weights only.  Data parallelism: every rank reads the device state and its own rank file; a rank without one (the world size
+        changed) keeps its seed-derived counters and generators and says so."""
+        from ... import learner_state
+        if missing_ok and not learner_state.exists(self.base_path):
+            print(f'[load_state] no learner state under {self.base_path}: weights only, fresh optimizer')
+            return False
+        meta = self.network.load_state(self.base_path)
+        self.restore_host_state(meta)
+        return True
+
+    def restore_host_state(self, meta: dict):
+        """Second half of load_state: `meta` is the state's JSON file."""
+        from ... import learner_state
+        rank = self.state_rank()
+        if rank is None:
+            self.set_host_state(meta['agent'])
+            return
+        own = learner_state.load_rank(self.base_path, rank)
+        if own is None or own.get('optimizer_steps') != meta.get('optimizer_steps'):
+            print(f'[load_state] rank {rank}: no {os.path.basename(learner_state.rank_json_path(self.base_path, rank))} that belongs '
+                  f'to this state: keeping the seed-derived counters and generators')
+            return
+        self.set_host_state(own['agent'])
 
     def save_config(self):
         self.update_config(policy_lr=self.policy_lr.serialize(), value_lr=self.value_lr.serialize(),

@@ -121,7 +121,8 @@ def read_object_graph(prefix: str) -> Dict[str, str]:
 
 
 def read_index(path: str) -> List[dict]:
-    """[{key, shape, dtype, shard, offset, size}] for every float tensor of `<prefix>.index`."""
+    """[{key, shape, dtype, shard, offset, size, crc}] for every float tensor of `<prefix>.index` (crc: the entry's masked
+    crc32c of the tensor's bytes, None when the writer left it out)."""
     entries = _raw_entries(path)
     out = []
     for key, val in entries:
@@ -132,12 +133,14 @@ def read_index(path: str) -> List[dict]:
             continue
         shape = [_proto(d).get(1, [0])[0] for d in _proto(e[2][0]).get(2, [])] if 2 in e else []
         out.append(dict(key=key.decode().replace(_SUFFIX, ''), shape=tuple(shape), shard=e.get(3, [0])[0],
-                        offset=e.get(4, [0])[0], size=e.get(5, [0])[0]))
+                        offset=e.get(4, [0])[0], size=e.get(5, [0])[0],
+                        crc=struct.unpack('<I', e[6][0])[0] if 6 in e else None))
     return out
 
 
-def load_checkpoint(prefix: str) -> Dict[str, np.ndarray]:
-    """key -> float32 array for every tensor whose data shard is present."""
+def load_checkpoint(prefix: str, verify: bool = False) -> Dict[str, np.ndarray]:
+    """key -> float32 array for every tensor whose data shard is present.  verify=True: every tensor of the index must be
+    there in full and its bytes must match the index entry's crc32c; ValueError otherwise (nothing is skipped)."""
     entries = read_index(prefix + '.index')
     nshards = 1 + max(e['shard'] for e in entries)
     shards = {}
@@ -151,7 +154,11 @@ def load_checkpoint(prefix: str) -> Dict[str, np.ndarray]:
     for e in entries:
         raw = shards.get(e['shard'])
         if raw is None or e['offset'] + e['size'] > len(raw):
+            if verify:
+                raise ValueError(f"{prefix}: data shard {e['shard']} of {e['key']} is missing or too short")
             continue
+        if verify and (e['crc'] is None or _mask(_crc32c(raw[e['offset']:e['offset'] + e['size']])) != e['crc']):
+            raise ValueError(f"{prefix}: {e['key']} fails its crc32c check (corrupt data shard)")
         out[e['key']] = np.frombuffer(raw[e['offset']:e['offset'] + e['size']], dtype='<f4').reshape(e['shape']).copy()
     return out
 

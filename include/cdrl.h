@@ -193,6 +193,20 @@ int cdrl_learner_set_comm_stream(cdrl_learner* l, void* stream);
 int64_t cdrl_learner_tail_offset(const cdrl_learner* l);
 /* Step counters to 0 and the Nadam m_caches to 1 (a fresh optimizer; the slots in the arenas are the caller's to reset). */
 int cdrl_learner_reset_optimizer_steps(cdrl_learner* l, void* stream);
+/* The optimizer's device-side scalars: with the parameter arena and the two slot arenas (the caller's tensors) they are the whole
+ * state of the learner, so a caller that saves all four can continue a run bit for bit.  Both calls address the block the learner
+ * reads at its steps: the owner's after cdrl_learner_share_hparams.  A frozen trunk's counter and m_cache are read and written like
+ * the others (the frozen learner never advances them).
+ * _get: copies the six values behind everything enqueued on `stream` and waits for that copy (the one host read of a save).
+ * _set: enqueued on `stream` like cdrl_learner_reset_optimizer_steps, no host sync; `in` may be freed when the call returns.  The
+ * hyper-parameters of cdrl_learner_set_hparams are not touched.  A negative counter, or an m_cache that is not finite or not
+ * positive, is refused with -1 (cdrl_last_error) and nothing is written. */
+typedef struct cdrl_optimizer_state {
+    int32_t t_policy, t_value, t_dynamics;                        /* steps taken so far */
+    float   m_cache_policy, m_cache_value, m_cache_dynamics;      /* Nadam; 1 for a fresh optimizer */
+} cdrl_optimizer_state;
+int cdrl_learner_get_optimizer_state(const cdrl_learner* l, cdrl_optimizer_state* out, void* stream);
+int cdrl_learner_set_optimizer_state(cdrl_learner* l, const cdrl_optimizer_state* in, void* stream);
 
 /* ---- update diagnostics (train stats) --------------------------------------------------------
  * The scalars PPOAgent.update / CARLAgent.update log per minibatch (reference rl/agents/ppo.py:209-225; core/carla_agent.py:382,
