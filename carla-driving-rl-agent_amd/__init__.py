@@ -6,6 +6,7 @@ Sub-modules
   synthetic deterministic synthetic rollout buffers
   train_stats  host side of the update diagnostics: ring rows -> the reference's log keys
   learner_state  on-disk container of the full learner state (arenas, optimizer scalars, counters, generators)
+  evaluation  host side of CARLAgent.evaluate: driving metrics of an environment, per-trial seeds, the JSON record
   core, rl  host-side mirror of the reference's CARLAgent / CARLANetwork / PPOMemory API
 """
 __version__ = '0.1.0'

@@ -3,10 +3,12 @@
 Surface follows the reference core/carla_agent.py: constructor keywords (:70-72), class-level
 DEFAULT_* architectures (:61-68), update() guard (:129-145), policy / value batch tensors
 (:323-349), get_*_gradients / apply_*_gradients (:351-388, :430-463), CARLAMemory (:586-596) and
-the FakeCARLAEnvironment entry point (:26-52).  evaluate() / record() drive a CARLA simulator and
-are outside the learner hot path: they raise instead of pretending.
+the FakeCARLAEnvironment entry point (:26-52), evaluate() (:205-321, here over an environment shard).  record() needs the
+simulator's frame recorder and is outside what this package implements: it raises instead of pretending.
 """
+import json
 import os
+import time
 import warnings
 
 import numpy as np
@@ -14,6 +16,8 @@ import torch
 import torch.distributed as dist
 
 from .. import train_stats
+from ..engine import act_stats_width
+from ..evaluation import RESULT_KEYS, evaluation_info, summarize, trial_seed
 from ..parallel import DataParallelLearner
 from ..rl import utils, spaces
 from ..rl.agents.ppo import PPOAgent, PPOMemory
@@ -49,6 +53,19 @@ class FakeCARLAEnvironment(spaces.Env):
         self.info_buffer = dict(speed=[], similarity=[])
         self._rng = np.random.default_rng(seed)
         self._t = 0
+        self._speed, self._similarity = 0.0, 0.0        # what step() last drew (evaluation_info)
+        self.current_town = None
+
+    def set_town(self, town):
+        self.current_town = town
+
+    def evaluation_info(self):
+        """-> (similarity, speed, waypoint_distance, collided) after a step, for CARLAgent.evaluate: the similarity and speed
+        step() last drew, a waypoint distance derived from them (5 * (1 - |similarity|)), and `collided` exactly when
+        `episode_length` is reached.  Draws nothing from the generator: a seeded observation sequence is the same with and
+        without these calls."""
+        collided = self.episode_length is not None and self._t >= self.episode_length
+        return self._similarity, self._speed, 5.0 * (1.0 - abs(self._similarity)), collided
 
     def seed(self, seed=None):
         self._rng = np.random.default_rng(seed)
@@ -76,6 +93,7 @@ class FakeCARLAEnvironment(spaces.Env):
         similarity = float(self._rng.uniform(-1.0, 1.0))
         self.info_buffer['speed'].append(speed)
         self.info_buffer['similarity'].append(similarity)
+        self._speed, self._similarity = speed, similarity
         done = self.episode_length is not None and self._t >= self.episode_length
         return self._observation(), speed / 3.0 * abs(similarity), done, {}
 
@@ -427,9 +445,130 @@ class CARLAgent(PPOAgent):
             augment_fn.shard = augment_shard
         return augment_fn
 
-    def evaluate(self, *args, **kwargs):
-        raise NotImplementedError('CARLAgent.evaluate drives a CARLA simulator (collision / waypoint metrics); '
-                                  'it is outside the learner hot path this package implements')
+    def evaluate(self, name: str, timesteps: int, trials: int, seeds=None, town='Town03', initial_seed=None, close=False,
+                 envs=None, deterministic=False) -> dict:
+        """Scores the agent over `trials` trials of at most `timesteps` steps and writes the record -- per result key the list over
+        the trials, `<key>_mean` and `<key>_std` -- to `<evaluation_path>/<name>.json`; returns the result lists (collision_rate,
+        similarity, waypoint_distance, speed, total_reward, timesteps).  Semantics of the reference (core/carla_agent.py:205-321):
+        `initial_seed` goes to set_random_seed, `set_town(town)` is called on environments that have it, the augmentation is off
+        for the duration (`aug_intensity` is restored in any case), every trial has its own seed (evaluation.trial_seed), a step is
+        predict -> convert_action -> `repeat_action` environment steps (rewards summed, stopped at `done`), the driving metrics
+        are read after it (evaluation.evaluation_info), and a trial is recorded when `(done or t == timesteps) and t > 32` -- an
+        environment that reports `done` at t <= 32 is stepped on, as the reference does, and `timesteps <= 32`, where the
+        reference would never finish, raises ValueError.  `total_reward` is floored at -1000.  Per trial the `eval_*` scalars are
+        logged and write_summaries() runs.  `close=True` closes the environments.
+
+        What differs from the reference:
+          * `envs` (default `[self.env]`): trials run in WAVES of E = len(envs).  Wave w runs trials w*E .. min((w+1)*E, trials) - 1
+            on the first n <= E environments, stepped in lockstep: one observe() and one network.evaluate_step() -- one inference
+            forward of the n-environment engine plus one cdrl_beta_act launch -- per step.  An environment whose trial is recorded
+            becomes inactive: it keeps its last observation in the batch, is stepped no more and its `active` entry is cleared.
+          * seeds: with one environment the trial's seed goes through set_random_seed, as in the reference (which seeds `self.env`;
+            a single environment passed in `envs` that is another object gets `env.seed(seed)` as well); with several,
+            set_random_seed gets the wave's first seed and every trial's environment gets `env.seed(its seed)`.
+          * `deterministic=True` acts with the mode of the Beta policy instead of a sample, and consumes no sampler offset.
+          * nothing is appended to a memory (the reference fills one and deletes it); `data_for_dynamics` is a pass-through here.
+          * `eval_actions / eval_distribution_mean / eval_distribution_std` are logged once per trial, not once per step: each is
+            the mean over the trial's steps and action dimensions, taken from the running sums cdrl_beta_act keeps on the device
+            (read once per wave); `eval_values` (the mean value estimate, from the same block) is logged beside them, and
+            `eval_rewards` is the trial's mean step reward.  Per step ONE device-to-host copy is made: the actions.
+          * the environments' info buffers (`reset_info`, where an environment has it) are emptied at the end, so that the steps
+            taken here never reach the auxiliary targets of a following update().
+          * no collectives: under data parallelism every rank evaluates on its own and only `is_writer()` writes the JSON file
+            and the summaries.
+        Parameters, moving statistics, optimizer slots and step counters are not touched."""
+        assert trials > 0
+        if timesteps <= 32:
+            raise ValueError(f'evaluate: timesteps = {timesteps}: a trial is only recorded at t > 32, so this would never finish')
+        shard = list(envs) if envs is not None else [self.env]
+        E, A = len(shard), self.num_actions
+        if isinstance(initial_seed, int):
+            self.set_random_seed(seed=initial_seed)
+        if town is not None:
+            for env in shard:
+                if hasattr(env, 'set_town'):
+                    env.set_town(town)
+        results = {k: [] for k in RESULT_KEYS}
+        save_path = os.path.join(self.evaluation_path, f'{name}.json')
+        print(save_path)
+        aug_intensity = self.aug_intensity
+        self.aug_intensity = 0.0            # no data augmentation
+        try:
+            for first in range(0, trials, E):
+                n = min(E, trials - first)
+                wave = shard[:n]
+                wave_seeds = [trial_seed(seeds, trials, first + i) for i in range(n)]
+                if wave_seeds[0] is not None:
+                    self.set_random_seed(seed=wave_seeds[0])
+                for env, seed in zip(wave, wave_seeds):
+                    if seed is not None and (E > 1 or env is not self.env):      # (set_random_seed seeds self.env alone)
+                        env.seed(seed)
+                preprocess_fn = self.preprocess()
+                self.reset()
+                observations = [env.reset() for env in wave]
+                t0 = time.time()
+                stats = torch.zeros((n, act_stats_width(A)), dtype=torch.float64, device=self.device)
+                mask, active = [1] * n, None           # (null = every row active, until the first trial of the wave is recorded)
+                running = list(range(n))
+                total, step_rewards, steps, collided = [0.0] * n, [0.0] * n, [0] * n, [False] * n
+                metrics = [[0.0, 0.0, 0.0] for _ in range(n)]          # similarity, speed, waypoint distance: sums over the steps
+                batch = self.observe(observations, preprocess_fn)
+                for t in range(1, timesteps + 1):
+                    action, _ = self.network.evaluate_step(batch, deterministic, active=active, stats=stats)
+                    env_actions = np.atleast_2d(self.convert_action(action))
+                    recorded = False
+                    for e in list(running):
+                        reward, done = 0.0, False
+                        for _ in range(self.repeat_action):
+                            observations[e], reward, done, _ = wave[e].step(env_actions[e])
+                            total[e] += reward
+                            if done:
+                                break
+                        similarity, speed, distance, hit = evaluation_info(wave[e])
+                        for k, v in enumerate((similarity, speed, distance)):
+                            metrics[e][k] += v
+                        step_rewards[e] += float(reward)
+                        if (done or t == timesteps) and t > 32:        # (t > 32: skips accidental collisions right after the start)
+                            steps[e], collided[e], mask[e], recorded = t, hit, 0, True
+                            running.remove(e)
+                            print(f'Trial-{first + e} terminated after {t} timesteps in {round(time.time() - t0, 3)} '
+                                  f'with total reward of {round(total[e], 3)}.')
+                    if not running:
+                        break
+                    if recorded:
+                        active = torch.tensor(mask, dtype=torch.int32, device=self.device)
+                    batch = self.observe(observations, preprocess_fn)
+                sums = stats.cpu().numpy()              # the wave's ONE read of the device sums
+                for e in range(n):
+                    t = steps[e]
+                    assert int(sums[e, 3 * A + 1]) == t, (e, t, sums[e])
+                    results['total_reward'].append(-1000.0 if total[e] < -1000.0 else total[e])
+                    results['timesteps'].append(t)
+                    results['collision_rate'].append(1.0 if collided[e] else 0.0)
+                    results['similarity'].append(metrics[e][0] / t)
+                    results['speed'].append(metrics[e][1] / t)
+                    results['waypoint_distance'].append(metrics[e][2] / t)
+                    self.log(eval_actions=float(sums[e, :A].sum()) / (t * A), eval_rewards=step_rewards[e] / t,
+                             eval_distribution_mean=float(sums[e, A:2 * A].sum()) / (t * A),
+                             eval_distribution_std=float(sums[e, 2 * A:3 * A].sum()) / (t * A), eval_values=float(sums[e, 3 * A]) / t)
+                    self.log(**{f'eval_{k}': v[-1] for k, v in results.items()})
+                    if self.is_writer():
+                        self.write_summaries()
+                    else:
+                        self.statistics.stats = {}
+            if self.is_writer():
+                os.makedirs(self.evaluation_path, exist_ok=True)
+                with open(save_path, 'w') as f:
+                    json.dump(summarize(results), fp=f, indent=2)
+        finally:
+            self.aug_intensity = aug_intensity
+            for env in shard:
+                if hasattr(env, 'reset_info'):
+                    env.reset_info()
+            if close:
+                for env in shard:
+                    env.close()
+        return results
 
     def record(self, *args, **kwargs):
         raise NotImplementedError('CARLAgent.record drives a CARLA simulator; outside the learner hot path')

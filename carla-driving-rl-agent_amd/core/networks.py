@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine import LearnerEngine
+from ..engine import LearnerEngine, beta_act, ACT_SAMPLE, ACT_MODE
 from ..init import init_engine_parameters
 from ..rl.networks import Network
 from ..rl import utils
@@ -140,24 +140,46 @@ class CARLANetwork(Network):
         return {k: inputs[k].to(self.device, torch.float32).contiguous()
                 for k in ('state_image', 'state_road', 'state_vehicle', 'state_navigation')}
 
-    def predict(self, inputs: dict):
+    def predict(self, inputs: dict, deterministic=False):
         """-> (action sample, mean, std, log_prob of the clipped sample, value (base, exp)); uses old_policy and BatchNorm
         moving statistics, like the reference's rollout forward (core/networks.py:181-193).  The leading axis of the inputs
         is the number of environments E stepped together (1 in the reference's loop); the Beta sample and its log-density
         come from one cdrl_beta_sample_logp launch on the (alpha, beta) the forward left on the device -- no host round trip.
-        Returned tensors are fresh (not views of the engine's persistent output buffers)."""
+        Returned tensors are fresh (not views of the engine's persistent output buffers).
+        deterministic=True: the action is the mode of the Beta, (alpha - 1) / (alpha + beta - 2), and log_prob its log-density
+        (cdrl_beta_act, mode 1); nothing is drawn, so `action_index` does not advance and the sampler's stream is untouched."""
         st = self._pick(inputs)
         E = st['state_image'].shape[0]
-        out = self.rollout_for(E).predict(st)
+        eng = self.rollout_for(E)
+        out = eng.predict(st)
         A = out['alpha'].shape[1]
         action = torch.empty((E, A), dtype=torch.float32, device=self.device)
         log_prob = torch.empty((E, A), dtype=torch.float32, device=self.device)
+        if deterministic:
+            beta_act(eng._pred_out[0], None, ACT_MODE, action=action, log_prob=log_prob)
+            return action, out['mean'].clone(), out['std'].clone(), log_prob, out['value'].clone()
         self.action_index += 1
         alpha, beta = out['alpha'], out['beta']              # views of the persistent (E, 4, A) block: row stride 4A
         _lib.check(self.engine.lib.cdrl_beta_sample_logp(_lib.ptr(alpha), _lib.ptr(beta), E, A, 4 * A, int(self.sample_seed),
                                                          int(self.action_index * self.sample_stride + self.sample_rank), _lib.ptr(action), _lib.ptr(log_prob),
                                                          self.engine._stream()), 'cdrl_beta_sample_logp')
         return action, out['mean'].clone(), out['std'].clone(), log_prob, out['value'].clone()
+
+    def evaluate_step(self, inputs: dict, deterministic, active=None, stats=None):
+        """One evaluation step for E environments -> (action, log_prob): one inference forward plus ONE cdrl_beta_act launch that
+        also adds the step's action / mean / std / value to the device block `stats` (float64 (E, 3A + 2), engine.beta_act) for
+        the rows whose `active` entry (int32 (E,), None = all) is set -- mean, std and value are never copied.  In sample mode
+        the draw is the one predict() would make: `action_index` advances and selects the Philox offset in the same way."""
+        st = self._pick(inputs)
+        E = st['state_image'].shape[0]
+        eng = self.rollout_for(E)
+        eng.predict(st)
+        dist, value = eng._pred_out[0], eng._pred_out[1]
+        if deterministic:
+            return beta_act(dist, value, ACT_MODE, active=active, stats=stats)
+        self.action_index += 1
+        return beta_act(dist, value, ACT_SAMPLE, seed=int(self.sample_seed),
+                        offset=int(self.action_index * self.sample_stride + self.sample_rank), active=active, stats=stats)
 
     def dynamics_predict(self, inputs: dict):
         st = self._pick(inputs)

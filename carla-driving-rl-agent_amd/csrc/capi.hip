@@ -437,6 +437,11 @@ int cdrl_beta_sample(const float* alpha, const float* beta, int rows, int A, int
     return beta_sample(alpha, beta, rows, A, ld, seed, offset, u, du_dalpha, du_dbeta, S(stream));
 }
 
+int cdrl_beta_act(const float* dist, const float* value, int rows, int A, int mode, uint64_t seed, uint64_t offset,
+                  const int32_t* active, float* action, float* log_prob, double* stats, void* stream) {
+    return beta_act(dist, value, rows, A, mode, seed, offset, active, action, log_prob, stats, S(stream));
+}
+
 int cdrl_gamma_implicit_grad(const double* a, const double* g, int n, double* out, void* stream) {
     return gamma_implicit_grad(a, g, n, out, S(stream));
 }

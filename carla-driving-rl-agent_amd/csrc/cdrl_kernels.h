@@ -439,6 +439,10 @@ int value_act(const float* lin, float* out /*[B][4] base,exp,speed,sim*/, int B,
 // reparameterisation of the two Gamma samples).  Element (row, col): alpha[row*ld + col].
 int beta_sample(const float* alpha, const float* beta, int rows, int A, int ld, uint64_t seed, uint64_t offset, float* u,
                 float* du_da, float* du_db, hipStream_t st, float* logp = nullptr, double* gammas = nullptr);
+// evaluation-time action from the predict block dist [rows][4][A] (mode 0: the sample of beta_sample, 1: the mode of the Beta), its
+// log-density, and per-row running sums for the active rows (stats [rows][3A + 2] doubles, may be null); arguments checked here
+int beta_act(const float* dist, const float* value, int rows, int A, int mode, uint64_t seed, uint64_t offset, const int32_t* active,
+             float* action, float* logp, double* stats, hipStream_t st);
 int gamma_implicit_grad(const double* a, const double* g, int n, double* out, hipStream_t st);
 int philox_words(uint64_t seed, uint64_t offset, uint64_t idx0, int n, int nblocks, uint32_t* out, hipStream_t st);
 

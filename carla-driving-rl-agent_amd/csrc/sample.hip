@@ -96,6 +96,68 @@ int beta_sample(const float* alpha, const float* beta, int rows, int A, int ld, 
     return 0;
 }
 
+// Evaluation-time action (cdrl_beta_act): element i = (row, col) of the [rows][4][A] block cdrl_learner_predict writes (alpha, beta,
+// mean, std).  mode 0 draws the sample exactly as beta_sample_kernel does on the same (seed, offset, i) -- same helpers, same
+// log-density expression -- mode 1 takes the mode of the Beta, (a - 1) / (a + b - 2) (alpha, beta >= 1.01 from the head: the
+// denominator is >= 0.02).  action / log_prob are written for every row; an ACTIVE row also adds its action, mean and std to the
+// row's running sums, and its col-0 thread the value base * 10^exp and the step count: every stats slot has one owner thread.
+__global__ void beta_act_kernel(const float* __restrict__ dist, const float* __restrict__ value, int n, int A, int mode, uint64_t seed,
+                                uint64_t offset, const int32_t* __restrict__ active, float* __restrict__ action,
+                                float* __restrict__ logp, double* __restrict__ stats) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int row = i / A, col = i - row * A;
+    const float* d = dist + (int64_t)row * 4 * A;
+    const double a = (double)d[col], b = (double)d[A + col];
+    float u;
+    if (mode == 0) {
+        Philox rng(seed, offset, (uint64_t)i);
+        const double g1 = gamma_sample(a, rng), g2 = gamma_sample(b, rng);
+        const double s = g1 + g2;
+        u = (float)(g1 / s);
+    } else {
+        u = (float)((a - 1.0) / (a + b - 2.0));
+    }
+    action[i] = u;
+    const float eps = 1.1920929e-07f;
+    const double x = (double)fminf(fmaxf(u, eps), 1.0f - eps);
+    logp[i] = (float)((a - 1.0) * log(x) + (b - 1.0) * log1p(-x) - (lgamma(a) + lgamma(b) - lgamma(a + b)));
+    if (!stats || (active && active[row] == 0)) return;
+    double* s = stats + (int64_t)row * (3 * A + 2);
+    s[col] += (double)u;
+    s[A + col] += (double)d[2 * A + col];
+    s[2 * A + col] += (double)d[3 * A + col];
+    if (col == 0) {
+        s[3 * A] += (double)value[4 * (int64_t)row] * pow(10.0, (double)value[4 * (int64_t)row + 1]);
+        s[3 * A + 1] += 1.0;
+    }
+}
+
+int beta_act(const float* dist, const float* value, int rows, int A, int mode, uint64_t seed, uint64_t offset, const int32_t* active,
+             float* action, float* logp, double* stats, hipStream_t st) {
+    if (!dist || !action || !logp) {
+        set_error("beta_act: null dist, action or log_prob");
+        return -1;
+    }
+    if (rows < 1 || A < 1 || A > 8 || rows > (1 << 24)) {
+        set_error("beta_act: rows = %d (1 .. 2^24), A = %d (1 .. 8)", rows, A);
+        return -1;
+    }
+    if (mode != 0 && mode != 1) {
+        set_error("beta_act: mode %d (0: sample, 1: mode of the Beta)", mode);
+        return -1;
+    }
+    if (stats && !value) {
+        set_error("beta_act: stats need the value block");
+        return -1;
+    }
+    const int n = rows * A;
+    hipLaunchKernelGGL(beta_act_kernel, dim3(cdiv(n, 64)), dim3(64), 0, st, dist, value, n, A, mode, seed, offset, active, action, logp,
+                       stats);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
 // test hook: the first `nblocks` raw 128-bit blocks of the streams (seed, offset, idx0 + i), i < n -> out[i][nblocks][4]
 __global__ void philox_words_kernel(uint64_t seed, uint64_t offset, uint64_t idx0, int n, int nblocks, uint32_t* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -576,3 +576,37 @@ def gae_returns_segments(rewards: torch.Tensor, values_be: torch.Tensor, lengths
                                              _lib.ptr(adv), _lib.ptr(scratch), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                'gae_returns_segments')
     return returns, returns_be, adv_raw, adv
+
+
+ACT_SAMPLE, ACT_MODE = 0, 1
+
+
+def act_stats_width(A: int) -> int:
+    """CDRL_ACT_STATS(A) (include/cdrl.h): doubles per row of a cdrl_beta_act stats block."""
+    return 3 * int(A) + 2
+
+
+def beta_act(dist: torch.Tensor, value, mode: int, seed: int = 0, offset: int = 0, active=None, stats=None, action=None, log_prob=None):
+    """Evaluation-time action for the rows of a predict block (cdrl_beta_act, one launch).  dist (rows, 4, A): alpha, beta, mean,
+    std; value (rows, 4) or None; mode ACT_SAMPLE (the draw of cdrl_beta_sample_logp on (seed, offset), bit for bit) or ACT_MODE
+    (the mode of the Beta); active: int32 (rows,) device tensor or None = every row; stats: float64 (rows, 3A + 2) running sums
+    that the ACTIVE rows add to, or None.  -> (action, log_prob), (rows, A) each (written into `action` / `log_prob` when given)."""
+    lib = _lib.load()
+    rows, four, A = dist.shape
+    if four != 4 or dist.dtype != torch.float32 or not dist.is_contiguous():
+        raise ValueError(f'beta_act: dist must be a contiguous float32 (rows, 4, A) tensor, got {tuple(dist.shape)} {dist.dtype}')
+    if value is not None and (tuple(value.shape) != (rows, 4) or value.dtype != torch.float32 or not value.is_contiguous()):
+        raise ValueError(f'beta_act: value must be a contiguous float32 ({rows}, 4) tensor')
+    if active is not None and (tuple(active.shape) != (rows,) or active.dtype != torch.int32 or not active.is_contiguous()):
+        raise ValueError(f'beta_act: active must be a contiguous int32 ({rows},) tensor')
+    if stats is not None and (tuple(stats.shape) != (rows, act_stats_width(A)) or stats.dtype != torch.float64
+                              or not stats.is_contiguous()):
+        raise ValueError(f'beta_act: stats must be a contiguous float64 ({rows}, {act_stats_width(A)}) tensor')
+    if action is None:
+        action = torch.empty((rows, A), dtype=torch.float32, device=dist.device)
+    if log_prob is None:
+        log_prob = torch.empty((rows, A), dtype=torch.float32, device=dist.device)
+    _lib.check(lib.cdrl_beta_act(_lib.ptr(dist), _lib.ptr(value), rows, A, int(mode), int(seed), int(offset), _lib.ptr(active),
+                                 _lib.ptr(action), _lib.ptr(log_prob), _lib.ptr(stats),
+                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cdrl_beta_act')
+    return action, log_prob

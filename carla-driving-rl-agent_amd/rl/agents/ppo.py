@@ -91,10 +91,16 @@ class PPOAgent(Agent):
             if a.shape[0] == 1 else a.detach().cpu().numpy() * self.action_range + self.action_low
 
     # -- acting -----------------------------------------------------------------------------------
-    def predict(self, state, *args, **kwargs):
+    def predict(self, state, *args, deterministic=False, **kwargs):
+        """deterministic=True: the mode of the policy instead of a sample (no sampler offset is consumed); the keyword reaches
+        the network only then, so a network without it keeps serving the sampled path."""
+        if deterministic:
+            return self.network.predict(inputs=state, deterministic=True)
         return self.network.predict(inputs=state)
 
-    def act(self, state, *args, **kwargs):
+    def act(self, state, *args, deterministic=False, **kwargs):
+        if deterministic:
+            return self.convert_action(self.network.predict(inputs=state, deterministic=True)[0])
         return self.convert_action(self.network.predict(inputs=state)[0])
 
     # -- update -----------------------------------------------------------------------------------

@@ -346,6 +346,21 @@ int cdrl_beta_sample(const float* alpha, const float* beta, int rows, int A, int
  * log-density of the sample clipped to [eps, 1 - eps], no Jacobians. */
 int cdrl_beta_sample_logp(const float* alpha, const float* beta, int rows, int A, int ld, uint64_t seed, uint64_t offset,
                           float* u, float* log_prob, void* stream);
+/* Evaluation form (CARLAgent.evaluate, core/carla_agent.py:254-291): the action of every row of the block cdrl_learner_predict
+ * writes -- dist [rows][4][A]: alpha, beta, mean, std -- and its log-density, in one launch, one thread per (row, a), no atomics.
+ *   mode 0: the sample; action and log_prob are bit-identical to cdrl_beta_sample_logp on the same (alpha, beta, seed, offset)
+ *           (Philox element index row * A + a, sample clipped to [eps, 1 - eps] with eps = 1.1920929e-07f for the log-density).
+ *   mode 1: the mode of the Beta, action = (float)((alpha - 1) / (alpha + beta - 2)) evaluated in double (the policy head gives
+ *           alpha, beta >= 1.01); log_prob is the same expression at that action.  seed and offset are not used.
+ * action and log_prob (dense [rows][A]) are written for every row.  stats (may be null): [rows][CDRL_ACT_STATS(A)] doubles of
+ * running sums, read-modify-written for the rows with active[row] != 0 (active: [rows] on the device, null = every row) and left
+ * untouched for the others: slots a, A + a, 2A + a += action, mean, std of column a; slot 3A += base * 10^exp of value
+ * ([rows][4]: base, exp, speed, similarity; may be null when stats is null); slot 3A + 1 += 1 (the step count).
+ * Errors (-1, before any launch): null dist / action / log_prob, rows < 1 (or > 2^24), A < 1 or > 8, mode not 0 or 1, stats
+ * without value. */
+#define CDRL_ACT_STATS(A) (3 * (A) + 2)
+int cdrl_beta_act(const float* dist, const float* value, int rows, int A, int mode, uint64_t seed, uint64_t offset,
+                  const int32_t* active, float* action, float* log_prob, double* stats, void* stream);
 /* bf16 ACTIVATION STORAGE at op level (configuration 3): the op-level entry points that have a bf16-storage form -- cdrl_bn_train_fwd /
  * _bwd (y, out, dout, dy), cdrl_dwconv_bn_fwd / _bwd (x, y, dout, dx), cdrl_pwconv_fused_packed and cdrl_pwconv_bn_bwd(_packed) with
  * packed_bf16 = 1 (a, c, epi_y; dout, y, x, dx), cdrl_pwconv_bwd_fused (+ _workspace), cdrl_gemm_tn (A, D), cdrl_gemm_x3 (A, C),
