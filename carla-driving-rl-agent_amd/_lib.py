@@ -201,6 +201,11 @@ PROTOTYPES = {
     'cdrl_pwconv_bwd_plan': (_i, [_V, _i, _V, _V] + [_i] * 5 + [_fp] * 7 + [_i] + [_fp] * 3 + [_i, C.POINTER(C.c_int32), _i]),
     'cdrl_pwconv_bwd_fused_fin': (_i, [_V, _i, _i, _fp, _fp, _fp, _V] + [_fp] * 6 + [_fp, C.c_void_p, _V, _i] + [_fp] * 3 + [C.c_void_p, _fp, _i]
                                   + [_fp] * 3 + [_i] * 4 + [_fp]),
+    'cdrl_gemm_tn_plan': (_i, [_V, _V] + [_i] * 10 + [C.POINTER(C.c_int32), _i]),
+    'cdrl_gemm_tn_ex_workspace_elems': (_i64, [_i, _i, _i, _i]),
+    'cdrl_gemm_tn_ex': (_i, [_V, _fp, _V, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _fp, _i, _i, _i, _fp]),
+    'cdrl_reduce_partials_plan': (_i, [C.c_uint64, _i, _i64, _i64, C.POINTER(C.c_int32), _i]),
+    'cdrl_reduce_partials_f32': (_i, [_fp, _i, _i64, _i64, _fp, _i, _fp]),
     'cdrl_bn_act_gap_fwd': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp]),
     'cdrl_gather_view': (_i, [_V, _i, _i, _i, _V, _i, _fp]),
     'cdrl_bn_inference_stats_table_bytes': (_i64, [_i]),

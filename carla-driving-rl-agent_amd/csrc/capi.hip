@@ -1202,6 +1202,97 @@ int cdrl_pwconv_bwd_fused_fin(const cdrl_view* dz, int dz_shuffle, int act, cons
     return pw_bwd_fused_reduce(f, S(stream));
 }
 
+// ---- filter-gradient GEMM family: the plan gemm_tn dispatches on, the entry with its whole contract, and the partial reduce ----
+// the K / N columns of a view (D: through the shuffle map) stay inside a row; pointers are not looked at
+static const char* tn_views_fit(const cdrl_view* a, const cdrl_view* d, int N, int K, int has_dpro, int shuffle_ctot, int relu6) {
+    if (!a || !d) return "the a and d views are required (their pointers may be null in the plan query)";
+    if (shuffle_ctot < 0 || ((shuffle_ctot || relu6) && !has_dpro)) return "the shuffle gather and the ReLU6 mask belong to the D prologue";
+    if (a->coff < 0 || a->coff + K > a->ld) return "the K channels of view a do not fit its rows";
+    if (d->coff < 0 || (shuffle_ctot ? (shuffle_ctot % 2 != 0 || d->coff + N > shuffle_ctot || shuffle_ctot > d->ld) : d->coff + N > d->ld))
+        return "the N channels of view d (through its shuffle) do not fit its rows";
+    return nullptr;
+}
+
+int cdrl_gemm_tn_plan(const cdrl_view* a, const cdrl_view* d, int M, int N, int K, int G, int has_a_stats, int has_dpro, int shuffle_ctot,
+                      int relu6, int bf16_operands, int act_type, int32_t* fields, int n_out) {
+    if (bad_act_type(act_type)) return -1;
+    if (!fields && n_out > 0) {
+        cdrl::set_error("cdrl_gemm_tn_plan: no field array");
+        return -1;
+    }
+    TnPlan p{};
+    p.kernel = -1;
+    const char* bad = tn_views_fit(a, d, N, K, has_dpro, shuffle_ctot, relu6);
+    if (bad) {
+        p.refusal = 4;
+        p.why = bad;
+    } else {
+        p = gemm_tn_plan(view_of(a), view_of(d), M, N, K, G, has_a_stats != 0, has_dpro != 0, shuffle_ctot, bf16_operands != 0, act_type);
+    }
+    if (!p.ok) cdrl::set_error("cdrl_gemm_tn_plan: %s", p.why);
+    const int32_t v[] = {p.ok, p.refusal, p.kernel, p.mode, p.apro, p.dpro, p.NJW, p.WK, p.NSPL, p.RS, p.RS2, p.U, p.gy, p.gz, p.nspg, p.nsplit,
+                         p.rows_per, p.part_slots, (int32_t)p.part_elems, p.reduce_form, p.dhalf};
+    int n = 0;
+    for (int32_t x : v) {
+        if (n < n_out) fields[n] = x;
+        ++n;
+    }
+    return n;
+}
+
+int64_t cdrl_gemm_tn_ex_workspace_elems(int M, int N, int K, int G) {
+    if (G < 1 || M < 1 || N < 1 || K < 1 || M % G != 0) return 0;
+    return gemm_tn_part_elems(M, N, K, G);
+}
+
+int cdrl_gemm_tn_ex(const cdrl_view* a, const float* a_stats, const cdrl_view* d, const float* dpro_y, const float* dpro_stats,
+                    const float* dpro_coef, int shuffle_ctot, int relu6, float* out, int M, int N, int K, int G, float* workspace,
+                    int accumulate, int bf16_operands, int act_type, void* stream) {
+    if (bad_act_type(act_type)) return -1;
+    const char* bad = tn_views_fit(a, d, N, K, dpro_y != nullptr, shuffle_ctot, relu6);
+    if (bad) {
+        cdrl::set_error("cdrl_gemm_tn_ex: %s", bad);
+        return -1;
+    }
+    if (!a->p || !d->p || !out || !workspace || (dpro_y && (!dpro_stats || !dpro_coef))) {
+        cdrl::set_error("cdrl_gemm_tn_ex: null tensor, or a D prologue without its stats / coef");
+        return -1;
+    }
+    const TnBnBwd tb{dpro_y, dpro_stats, dpro_coef, shuffle_ctot, relu6 ? ACT_RELU6 : ACT_NONE};
+    return gemm_tn(view_of(a), view_of(d), out, M, N, K, workspace, accumulate, S(stream), G, a_stats, dpro_y ? &tb : nullptr,
+                   bf16_operands != 0, act_type);
+}
+
+static bool reduce_args_ok(const char* fn, int nparts, int64_t n, int64_t stride) {
+    if (nparts < 1 || n < 1 || stride < n) {
+        cdrl::set_error("%s: nparts %d, n %lld, stride %lld: at least one partial and one output, rows no shorter than n", fn, nparts,
+                        (long long)n, (long long)stride);
+        return false;
+    }
+    return true;
+}
+
+int cdrl_reduce_partials_plan(uint64_t part_addr, int nparts, int64_t n, int64_t stride, int32_t* fields, int n_out) {
+    if (!reduce_args_ok("cdrl_reduce_partials_plan", nparts, n, stride) || (!fields && n_out > 0)) return -1;
+    const ReduceF32Plan p = reduce_partials_f32_plan((uintptr_t)part_addr, nparts, n, stride);
+    const int32_t v[] = {p.form, (int32_t)p.grid, p.bx, p.by};
+    int k = 0;
+    for (int32_t x : v) {
+        if (k < n_out) fields[k] = x;
+        ++k;
+    }
+    return k;
+}
+
+int cdrl_reduce_partials_f32(const float* part, int nparts, int64_t n, int64_t stride, float* out, int accumulate, void* stream) {
+    if (!reduce_args_ok("cdrl_reduce_partials_f32", nparts, n, stride)) return -1;
+    if (!part || !out) {
+        cdrl::set_error("cdrl_reduce_partials_f32: null argument");
+        return -1;
+    }
+    return reduce_partials_f32(part, nparts, n, stride, out, accumulate, S(stream));
+}
+
 int cdrl_bn_act_gap_fwd(const float* y, const float* stats, float* out, int G, int frames_per_group, int P, int C, int relu6,
                         int act_type, void* stream) {
     if (bad_act_type(act_type)) return -1;

@@ -115,18 +115,36 @@ struct TnBnBwd {
 };
 bool gemm_tn_dpro_supported(int N);
 int64_t gemm_tn_part_elems(int M, int N, int K, int G = 1);
+// The one dispatch decision of gemm_tn: which kernel, which instantiation, which grid, how many partials, which reduce.  gemm_tn_plan
+// fills it from the shapes, the views' leading dimensions / offsets and CDRL_TN_LDS_F32 (reads no memory, launches nothing); gemm_tn
+// launches from it and cdrl_gemm_tn_plan reports it.
+struct TnPlan {
+    int ok, refusal;            // refusal (ok == 0): 1 G < 1 or M % G != 0, 2 bf16 storage without bf16 operands, 3 an operand of 2 GB or more
+    const char* why;
+    int kernel;                 // 0 tn_direct_kernel, 1 tn_direct_tr_kernel, 2 tn_lds_kernel; -1: an empty product, nothing is launched
+    int mode;                   // the kernel's MODE template argument
+    int apro, dpro;             // operand prologues (template arguments)
+    int NJW, WK, NSPL, RS, RS2, U;          // direct kernels: wave mapping and batch depth (0 for the LDS kernel)
+    int gy, gz, nspg, nsplit, rows_per;     // grid = (nsplit = G * nspg, gy, gz); rows per workgroup
+    int part_slots;             // partials [part_slots][K][N]: nsplit * RS (direct), nsplit (LDS)
+    int64_t part_elems;
+    int reduce_form;            // reduce_partials_f32_plan for a 16-byte aligned workspace
+    int dhalf;                  // LDS kernel: some thread gathers its last column pair as (s - 1, s) (shuffle, N = 2 mod 4)
+};
+TnPlan gemm_tn_plan(View A, View D, int M, int N, int K, int G, bool apro, bool dpro, int shuffle_ctot, bool bf16_operands, int at);
 // bf16_operands: both operands rounded to bf16 AFTER their prologues, v_mfma_f32_32x32x16_bf16 over 16-row steps (configuration 3)
 int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int accumulate, hipStream_t st, int G = 1,
             const float* pro_stats = nullptr, const TnBnBwd* dpro = nullptr, bool bf16_operands = false, int at = 0);
 
-// LDS-staged form for the bf16 modes (gemm_tn_lds.hip): same contract as gemm_tn with bf16_operands = true; at: 0 float32 / 1 bf16
-// tensors.  gemm_tn dispatches to it for the shapes it takes.
-bool gemm_tn_lds_supported(View A, View D, int N, int K, const TnBnBwd* dpro);
+// LDS-staged form (gemm_tn_lds.hip): same contract as gemm_tn; gemm_tn dispatches to it for the shapes it takes (K, N >= 96 and
+// gemm_tn_lds_supported).  mode: 2 bf16 tensors, 1 float32 tensors with bf16 operands, 0 float32 operands on v_mfma_f32_32x32x2_f32
+// (the float32 engine's arithmetic), 3 float32-accurate product from three bf16 planes per operand on v_mfma_f32_32x32x16_bf16 (six
+// plane products).  gemm_tn_lds_plan fills the grid fields, part_slots and dhalf of a plan; gemm_tn_lds launches from the plan.
+bool gemm_tn_lds_supported(View A, View D, int N, int K, int shuffle_ctot);
 int64_t gemm_tn_lds_part_elems(int M, int N, int K, int G = 1);
-// f32_mode (with at = 0): 1 = float32 operands on v_mfma_f32_32x32x2_f32 (the float32 engine's arithmetic); 2 = float32-accurate
-// product from three bf16 planes per operand on v_mfma_f32_32x32x16_bf16 (six plane products)
-int gemm_tn_lds(View A, View D, float* Cout, int M, int N, int K, float* part, int accumulate, hipStream_t st, int G,
-                const float* pro_stats, const TnBnBwd* dpro, int at, int f32_mode = 0);
+void gemm_tn_lds_plan(TnPlan& p, int M, int N, int K, int G, int shuffle_ctot);
+int gemm_tn_lds(const TnPlan& p, View A, View D, float* Cout, int M, int N, int K, float* part, int accumulate, hipStream_t st, int G,
+                const float* pro_stats, const TnBnBwd* dpro);
 
 // ---------------------------------------------------------------- fused pointwise conv (gemm_pw.hip)
 // Persistent skinny GEMM for K, N <= 128: C[m,n] (+)= sum_k pro(A[m,k]) W(k,n) + bias[n] over G groups of Mg rows.
@@ -164,6 +182,14 @@ int64_t pw_packed_elems(int N, int K);
 PwPack pw_pack_entry(const float* w, float* wp, int K, int N, int sbk, int sbn, bool bf16 = false);
 int pw_pack_many(const PwPack* tab_dev, int n, hipStream_t st);
 // out[i] (+)= sum_p part[p*stride + i] for float partials (double accumulation, fixed order)
+// The kernel is chosen by reduce_partials_f32_plan (address arithmetic only): form 0 tn_reduce_few_kernel, 1 / 2 / 3
+// tn_reduce_v4_kernel<16 / 4 / 1>, 4 / 5 tn_reduce_kernel<16 / 4> (any alignment, any n)
+struct ReduceF32Plan {
+    int form;
+    unsigned grid;
+    int bx, by;                 // block
+};
+ReduceF32Plan reduce_partials_f32_plan(uintptr_t part_addr, int nparts, int64_t n, int64_t stride);
 int reduce_partials_f32(const float* part, int nparts, int64_t n, int64_t stride, float* out, int accumulate,
                         hipStream_t st);
 

@@ -558,28 +558,30 @@ __global__ void __launch_bounds__(256) tn_reduce_few_kernel(const float* __restr
     out[i + 3] = o.w;
 }
 
+ReduceF32Plan reduce_partials_f32_plan(uintptr_t part_addr, int nparts, int64_t n, int64_t stride) {
+    const bool v4 = n % 4 == 0 && stride % 4 == 0 && (part_addr & 15) == 0;
+    if (v4 && nparts < 16 && n >= 4096) return {0, (unsigned)cdiv64(n, 1024), 256, 1};
+    if (v4 && nparts >= 16) {
+        if (cdiv64(n, 64) >= 160) return {1, (unsigned)cdiv64(n, 64), 256, 1};
+        if (cdiv64(n, 16) >= 128 || nparts < 128) return {2, (unsigned)cdiv64(n, 16), 256, 1};
+        return {3, (unsigned)cdiv64(n, 4), 256, 1};
+    }
+    if (cdiv64(n, 16) >= 128 || nparts <= 64) return {4, (unsigned)cdiv64(n, 16), 16, 64};
+    return {5, (unsigned)cdiv64(n, 4), 4, 256};
+}
+
 int reduce_partials_f32(const float* part, int nparts, int64_t n, int64_t stride, float* out, int accumulate,
                         hipStream_t st) {
-    const bool v4 = n % 4 == 0 && stride % 4 == 0 && (reinterpret_cast<uintptr_t>(part) & 15) == 0;
-    if (v4 && nparts < 16 && n >= 4096) {
-        hipLaunchKernelGGL(tn_reduce_few_kernel, dim3((unsigned)cdiv64(n, 1024)), dim3(256), 0, st, part, nparts, n, stride, out, accumulate);
-        CDRL_LAUNCH_CHECK();
-        return 0;
+    const ReduceF32Plan p = reduce_partials_f32_plan(reinterpret_cast<uintptr_t>(part), nparts, n, stride);
+    const dim3 grid(p.grid), blk(p.bx, p.by);
+    switch (p.form) {
+        case 0: hipLaunchKernelGGL(tn_reduce_few_kernel, grid, blk, 0, st, part, nparts, n, stride, out, accumulate); break;
+        case 1: hipLaunchKernelGGL(tn_reduce_v4_kernel<16>, grid, blk, 0, st, part, nparts, n, stride, out, accumulate); break;
+        case 2: hipLaunchKernelGGL(tn_reduce_v4_kernel<4>, grid, blk, 0, st, part, nparts, n, stride, out, accumulate); break;
+        case 3: hipLaunchKernelGGL(tn_reduce_v4_kernel<1>, grid, blk, 0, st, part, nparts, n, stride, out, accumulate); break;
+        case 4: hipLaunchKernelGGL(tn_reduce_kernel<16>, grid, blk, 0, st, part, nparts, n, stride, out, accumulate); break;
+        default: hipLaunchKernelGGL(tn_reduce_kernel<4>, grid, blk, 0, st, part, nparts, n, stride, out, accumulate); break;
     }
-    if (v4 && nparts >= 16) {
-        if (cdiv64(n, 64) >= 160)
-            hipLaunchKernelGGL(tn_reduce_v4_kernel<16>, dim3((unsigned)cdiv64(n, 64)), dim3(256), 0, st, part, nparts, n, stride, out, accumulate);
-        else if (cdiv64(n, 16) >= 128 || nparts < 128)
-            hipLaunchKernelGGL(tn_reduce_v4_kernel<4>, dim3((unsigned)cdiv64(n, 16)), dim3(256), 0, st, part, nparts, n, stride, out, accumulate);
-        else
-            hipLaunchKernelGGL(tn_reduce_v4_kernel<1>, dim3((unsigned)cdiv64(n, 4)), dim3(256), 0, st, part, nparts, n, stride, out, accumulate);
-        CDRL_LAUNCH_CHECK();
-        return 0;
-    }
-    if (cdiv64(n, 16) >= 128 || nparts <= 64)
-        hipLaunchKernelGGL(tn_reduce_kernel<16>, dim3((unsigned)cdiv64(n, 16)), dim3(16, 64), 0, st, part, nparts, n, stride, out, accumulate);
-    else
-        hipLaunchKernelGGL(tn_reduce_kernel<4>, dim3((unsigned)cdiv64(n, 4)), dim3(4, 256), 0, st, part, nparts, n, stride, out, accumulate);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

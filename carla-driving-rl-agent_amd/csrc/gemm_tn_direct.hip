@@ -479,53 +479,52 @@ int64_t gemm_tn_part_elems(int M, int N, int K, int G) {
 
 bool gemm_tn_dpro_supported(int) { return true; }
 
+// tn_direct_kernel is planned only WITHOUT a D prologue (tnd_plan: TR <=> dpro), so its DPRO = true instantiations are not built:
+// 3 widths x 2 A prologues x 3 (U, MODE) pairs per kernel, 18 + 18 in all.
 template <int NJW, int U, int BF>
-static void launch_tnd_u(bool apro, bool dpro, dim3 grid, hipStream_t st, const TnDirectArgs& a) {
+static void launch_tnd_u(bool apro, dim3 grid, hipStream_t st, const TnDirectArgs& a) {
     const dim3 blk(256 * a.RS2);
     const size_t lds = a.RS2 == 2 ? (size_t)4 * NJW * 16 * 64 * sizeof(float) : 0;     // <= 64 KB
-    if (a.TR) {         // (planned only with a D prologue)
+    if (a.TR) {         // with a D prologue
         if (apro) hipLaunchKernelGGL((tn_direct_tr_kernel<NJW, true, true, U, BF>), grid, blk, lds, st, a);
         else hipLaunchKernelGGL((tn_direct_tr_kernel<NJW, false, true, U, BF>), grid, blk, lds, st, a);
         return;
     }
-    if (apro && dpro) hipLaunchKernelGGL((tn_direct_kernel<NJW, true, true, U, BF>), grid, blk, lds, st, a);
-    else if (apro) hipLaunchKernelGGL((tn_direct_kernel<NJW, true, false, U, BF>), grid, blk, lds, st, a);
-    else if (dpro) hipLaunchKernelGGL((tn_direct_kernel<NJW, false, true, U, BF>), grid, blk, lds, st, a);
+    if (apro) hipLaunchKernelGGL((tn_direct_kernel<NJW, true, false, U, BF>), grid, blk, lds, st, a);
     else hipLaunchKernelGGL((tn_direct_kernel<NJW, false, false, U, BF>), grid, blk, lds, st, a);
 }
 
 template <int NJW>
-static void launch_tnd(bool apro, bool dpro, dim3 grid, hipStream_t st, const TnDirectArgs& a, bool bf, int at) {
-    if (at) {           // bf16 operands AND bf16 activation storage
-        launch_tnd_u<NJW, 8, 2>(apro, dpro, grid, st, a);
-        return;
-    }
-    if (bf) {           // bf16 operands: a batch is one 16-row MFMA step
-        launch_tnd_u<NJW, 8, 1>(apro, dpro, grid, st, a);
-        return;
-    }
-    // U = 8 with a D prologue (transposed mapping: 200 VGPRs at U = 8; 19.6 -> 19.2 ms/update-step over U = 4), else U = 4
-    if (dpro) launch_tnd_u<NJW, 8, 0>(apro, dpro, grid, st, a);
-    else launch_tnd_u<NJW, 4, 0>(apro, dpro, grid, st, a);
+static void launch_tnd(const TnPlan& p, dim3 grid, hipStream_t st, const TnDirectArgs& a) {
+    // MODE 2: bf16 operands AND bf16 activation storage; MODE 1: bf16 operands (a batch is one 16-row MFMA step); MODE 0: U = 8 with a
+    // D prologue (transposed mapping: 200 VGPRs at U = 8; 19.6 -> 19.2 ms/update-step over U = 4), else U = 4
+    if (p.mode == 2) launch_tnd_u<NJW, 8, 2>(p.apro != 0, grid, st, a);
+    else if (p.mode == 1) launch_tnd_u<NJW, 8, 1>(p.apro != 0, grid, st, a);
+    else if (p.U == 8) launch_tnd_u<NJW, 8, 0>(p.apro != 0, grid, st, a);
+    else launch_tnd_u<NJW, 4, 0>(p.apro != 0, grid, st, a);
 }
 
-int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int accumulate, hipStream_t st, int G,
-            const float* pro_stats, const TnBnBwd* dpro, bool bf16_operands, int at) {
-    if (G < 1 || M % G != 0) {
-        set_error("gemm_tn: M=%d is not a multiple of G=%d", M, G);
-        return -1;
-    }
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    if (at && !bf16_operands) {
-        set_error("gemm_tn: bf16 activation storage needs the bf16-operand variant");
-        return -1;
-    }
-    if ((int64_t)M * A.ld * 4 >= (1ll << 31) || (int64_t)M * D.ld * 4 >= (1ll << 31) || (int64_t)M * N * 4 >= (1ll << 31)) {
-        set_error("gemm_tn: operands of 2 GB or more are not supported (M=%d)", M);
-        return -1;
-    }
-    static const bool diag_skip = cdrl_getenv("CDRL_DIAG_SKIP_TN") && atoi(cdrl_getenv("CDRL_DIAG_SKIP_TN")) == 1;   // timing diagnostics only
-    if (diag_skip) return 0;
+static TnPlan tn_refuse(int code, const char* why) {
+    TnPlan p{};
+    p.refusal = code;
+    p.why = why;
+    p.kernel = -1;
+    return p;
+}
+
+TnPlan gemm_tn_plan(View A, View D, int M, int N, int K, int G, bool apro, bool dpro, int shuffle_ctot, bool bf16_operands, int at) {
+    if (G < 1 || M % G != 0) return tn_refuse(1, "gemm_tn: M is not a multiple of G (or G < 1)");
+    TnPlan p{};
+    p.ok = 1;
+    p.why = "";
+    p.kernel = -1;
+    p.apro = apro ? 1 : 0;
+    p.dpro = dpro ? 1 : 0;
+    if (M <= 0 || N <= 0 || K <= 0) return p;
+    if (at && !bf16_operands) return tn_refuse(2, "gemm_tn: bf16 activation storage needs the bf16-operand variant");
+    if ((int64_t)M * A.ld * 4 >= (1ll << 31) || (int64_t)M * D.ld * 4 >= (1ll << 31) || (int64_t)M * N * 4 >= (1ll << 31))
+        return tn_refuse(3, "gemm_tn: operands of 2 GB or more are not supported");
+    const int shuf = dpro ? shuffle_ctot : 0;
     // bf16 modes: operands staged once per workgroup through LDS (gemm_tn_lds.hip) -- the direct form is a stream of 2-byte loads
     // there.
     // Shapes: its 128 x 128 column block with one k tile per wave only pays for wide products -- measured isolated at B = 1024:
@@ -537,8 +536,6 @@ int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int a
     // (Until the ReLU6 masks became single compares -- relu6_open(), cdrl_common.h -- the shapes with several column blocks were kept
     //  off this path: next to them the fused backward-data GEMM on the main stream lost its run-to-run reproducibility.  The cause
     //  was in that kernel's mask code, not here: DESIGN.md "What round 3 found", tools/det_co.py.)
-    if (bf16_operands && K >= 96 && N >= 96 && gemm_tn_lds_supported(A, D, N, K, dpro))
-        return gemm_tn_lds(A, D, Cout, M, N, K, part, accumulate, st, G, pro_stats, dpro, at);
     // float32 tensors through the same staging: three bf16 planes per operand + six plane products on the bf16 pipe (exact split, float32-
     // accurate).  Round 3 measured it at K = N = 116, M = 196608 (B = 1024), isolated: direct 87.6 us, float32-MFMA LDS form 104.1 us,
     // this form 73.7 us; K = N = 232, M = 49152: 81.4 / 96.5 / 70.2 us -- and NO gain in the update-step (15.78 direct | 16.58 | 15.83 ms):
@@ -547,9 +544,43 @@ int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int a
     // with the critical stream: round 5, same box, 14.27 (direct) | 14.31 (float32-MFMA LDS form) | 14.01 ms (this form).  Default since
     // round 5; CDRL_TN_LDS_F32=1 -> float32 LDS columns + v_mfma_f32_32x32x2_f32.
     static const bool f32_mfma = cdrl_getenv("CDRL_TN_LDS_F32") && atoi(cdrl_getenv("CDRL_TN_LDS_F32")) == 1;
-    if (!bf16_operands && K >= 96 && N >= 96 && gemm_tn_lds_supported(A, D, N, K, dpro))
-        return gemm_tn_lds(A, D, Cout, M, N, K, part, accumulate, st, G, pro_stats, dpro, 0, f32_mfma ? 1 : 2);
-    const TndPlan p = tnd_plan(M, N, K, G, dpro != nullptr);
+    if (K >= 96 && N >= 96 && gemm_tn_lds_supported(A, D, N, K, shuf)) {
+        p.mode = at ? 2 : bf16_operands ? 1 : f32_mfma ? 0 : 3;
+        gemm_tn_lds_plan(p, M, N, K, G, shuf);
+    } else {
+        const TndPlan q = tnd_plan(M, N, K, G, dpro);
+        p.kernel = q.TR;
+        p.mode = at ? 2 : bf16_operands ? 1 : 0;
+        p.U = (p.mode || dpro) ? 8 : 4;
+        p.NJW = q.NJW;
+        p.WK = q.WK;
+        p.NSPL = q.NSPL;
+        p.RS = q.RS;
+        p.RS2 = q.RS2;
+        p.gy = q.gy;
+        p.gz = q.gz;
+        p.nspg = q.nspg;
+        p.nsplit = q.nsplit;
+        p.rows_per = q.rows_per;
+        p.part_slots = q.nsplit * q.RS;
+        p.dhalf = 0;
+    }
+    p.part_elems = (int64_t)p.part_slots * K * N;
+    p.reduce_form = reduce_partials_f32_plan(0, p.part_slots, (int64_t)K * N, (int64_t)K * N).form;
+    return p;
+}
+
+int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int accumulate, hipStream_t st, int G,
+            const float* pro_stats, const TnBnBwd* dpro, bool bf16_operands, int at) {
+    const TnPlan p = gemm_tn_plan(A, D, M, N, K, G, pro_stats != nullptr, dpro != nullptr, dpro ? dpro->shuffle_ctot : 0, bf16_operands, at);
+    if (!p.ok) {
+        set_error("%s (M=%d G=%d)", p.why, M, G);
+        return -1;
+    }
+    if (p.kernel < 0) return 0;
+    static const bool diag_skip = cdrl_getenv("CDRL_DIAG_SKIP_TN") && atoi(cdrl_getenv("CDRL_DIAG_SKIP_TN")) == 1;   // timing diagnostics only
+    if (diag_skip) return 0;
+    if (p.kernel == 2) return gemm_tn_lds(p, A, D, Cout, M, N, K, part, accumulate, st, G, pro_stats, dpro);
     TnDirectArgs a;
     a.A = A;
     a.D = D;
@@ -566,19 +597,19 @@ int gemm_tn(View A, View D, float* Cout, int M, int N, int K, float* part, int a
     a.NJW = p.NJW;
     a.RS = p.RS;
     a.RS2 = p.RS2;
-    a.TR = p.TR;
+    a.TR = p.kernel;
     a.a_stats = pro_stats;
     a.db = TnBnBwd{};
     if (dpro) a.db = *dpro;
     dim3 grid(p.nsplit, p.gy, p.gz);
     switch (p.NJW) {
-        case 1: launch_tnd<1>(pro_stats != nullptr, dpro != nullptr, grid, st, a, bf16_operands, at); break;
-        case 2: launch_tnd<2>(pro_stats != nullptr, dpro != nullptr, grid, st, a, bf16_operands, at); break;
-        default: launch_tnd<4>(pro_stats != nullptr, dpro != nullptr, grid, st, a, bf16_operands, at); break;
+        case 1: launch_tnd<1>(p, grid, st, a); break;
+        case 2: launch_tnd<2>(p, grid, st, a); break;
+        default: launch_tnd<4>(p, grid, st, a); break;
     }
     CDRL_LAUNCH_CHECK();
     const int64_t n = (int64_t)K * N;
-    return reduce_partials_f32(part, p.nsplit * p.RS, n, n, Cout, accumulate, st);
+    return reduce_partials_f32(part, p.part_slots, n, n, Cout, accumulate, st);
 }
 
 }  // namespace cdrl

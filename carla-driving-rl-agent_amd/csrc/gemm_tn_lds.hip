@@ -345,31 +345,34 @@ static TnlPlan tnl_plan(int M, int N, int K, int G) {
 
 int64_t gemm_tn_lds_part_elems(int M, int N, int K, int G) { return (int64_t)tnl_plan(M, N, K, G).nsplit * K * N; }
 
-bool gemm_tn_lds_supported(View A, View D, int N, int K, const TnBnBwd* dpro) {
+bool gemm_tn_lds_supported(View A, View D, int N, int K, int shuffle_ctot) {
     // adjacent-column pairs: even leading dimensions / offsets / widths (every tower tensor); the shuffle gather needs the two
     // halves of the concat to be even as well
     if ((A.ld & 1) || (A.coff & 1) || (D.ld & 1) || (D.coff & 1) || (K & 1) || (N & 1)) return false;
-    if (dpro && dpro->shuffle_ctot && ((dpro->shuffle_ctot >> 1) & 1)) return false;
+    if (shuffle_ctot && ((shuffle_ctot >> 1) & 1)) return false;
     return true;
 }
 
-int gemm_tn_lds(View A, View D, float* Cout, int M, int N, int K, float* part, int accumulate, hipStream_t st, int G, const float* pro_stats,
-                const TnBnBwd* dpro, int at, int f32_mode) {
-    if (G < 1 || M % G != 0) {
-        set_error("gemm_tn_lds: M=%d is not a multiple of G=%d", M, G);
+void gemm_tn_lds_plan(TnPlan& p, int M, int N, int K, int G, int shuffle_ctot) {
+    const TnlPlan q = tnl_plan(M, N, K, G);
+    p.kernel = 2;
+    p.NJW = p.WK = p.NSPL = p.RS = p.RS2 = p.U = 0;
+    p.gy = q.gy;
+    p.gz = q.gz;
+    p.nspg = q.nspg;
+    p.nsplit = q.nsplit;
+    p.rows_per = q.rows_per;
+    p.part_slots = q.nsplit;
+    // the thread whose micro-tile starts at column N - 2 of a width that is 2 mod 4 (N is even here), through the shuffle gather
+    p.dhalf = (p.dpro && shuffle_ctot && N % 4 == 2) ? 1 : 0;
+}
+
+int gemm_tn_lds(const TnPlan& p, View A, View D, float* Cout, int M, int N, int K, float* part, int accumulate, hipStream_t st, int G,
+                const float* pro_stats, const TnBnBwd* dpro) {
+    if (!p.ok || p.kernel != 2 || !gemm_tn_lds_supported(A, D, N, K, dpro ? dpro->shuffle_ctot : 0)) {
+        set_error("gemm_tn_lds: not planned for this call (K=%d N=%d)", K, N);
         return -1;
     }
-    if (M <= 0 || N <= 0 || K <= 0) return 0;
-    if (!gemm_tn_lds_supported(A, D, N, K, dpro)) {
-        set_error("gemm_tn_lds: odd leading dimension / offset / width (K=%d N=%d)", K, N);
-        return -1;
-    }
-    const int64_t esz = at ? 2 : 4;
-    if ((int64_t)M * A.ld * esz >= (1ll << 31) || (int64_t)M * D.ld * esz >= (1ll << 31) || (int64_t)M * N * esz >= (1ll << 31)) {
-        set_error("gemm_tn_lds: operands of 2 GB or more are not supported (M=%d)", M);
-        return -1;
-    }
-    const TnlPlan p = tnl_plan(M, N, K, G);
     TnLdsArgs a;
     a.A = A;
     a.D = D;
@@ -385,7 +388,7 @@ int gemm_tn_lds(View A, View D, float* Cout, int M, int N, int K, float* part, i
     a.db = TnBnBwd{};
     if (dpro) a.db = *dpro;
     const dim3 grid(p.nsplit, p.gy, p.gz), blk(256);
-    const bool ap = pro_stats != nullptr, dp = dpro != nullptr;
+    const bool ap = p.apro != 0, dp = p.dpro != 0;
 #define CDRL_TNL(BHV)                                                                               \
     do {                                                                                            \
         if (ap && dp) hipLaunchKernelGGL((tn_lds_kernel<BHV, true, true>), grid, blk, 0, st, a);    \
@@ -393,14 +396,16 @@ int gemm_tn_lds(View A, View D, float* Cout, int M, int N, int K, float* part, i
         else if (dp) hipLaunchKernelGGL((tn_lds_kernel<BHV, false, true>), grid, blk, 0, st, a);    \
         else hipLaunchKernelGGL((tn_lds_kernel<BHV, false, false>), grid, blk, 0, st, a);           \
     } while (0)
-    if (at) CDRL_TNL(2);
-    else if (f32_mode == 2) CDRL_TNL(3);
-    else if (f32_mode == 1) CDRL_TNL(0);
-    else CDRL_TNL(1);
+    switch (p.mode) {
+        case 2: CDRL_TNL(2); break;
+        case 3: CDRL_TNL(3); break;
+        case 0: CDRL_TNL(0); break;
+        default: CDRL_TNL(1); break;
+    }
 #undef CDRL_TNL
     CDRL_LAUNCH_CHECK();
     const int64_t n = (int64_t)K * N;
-    return reduce_partials_f32(part, p.nsplit, n, n, Cout, accumulate, st);
+    return reduce_partials_f32(part, p.part_slots, n, n, Cout, accumulate, st);
 }
 
 }  // namespace cdrl

@@ -672,6 +672,36 @@ int cdrl_pwconv_bwd_fused_fin(const cdrl_view* dz, int dz_shuffle, int act, cons
                               float* a_dbeta, float* a_coef, const float* W, const void* W_packed, const cdrl_view* da, int accumulate,
                               float* dW, float* db, float* qpart, double* dbpart, const double* fin_part, int fin_nb, double* fin_tot,
                               float* o_dgamma, float* o_dbeta, int G, int Mg, int N, int K, int act_type, void* stream);
+/* ---- The filter-gradient GEMM family  out[K][N] (+)= sum_m a'[m][K]^T d'[m][N]  (cdrl_gemm_tn above is its plain G = 1 form) with the
+ * whole contract of the engine's calls: rows in G equal groups; a' = scale[g][k] a + shift[g][k] from a_stats [4][G][K] (or a);
+ * d' = k1 (mask(dz) - k2 - xhat(y) k3) with dz = view d (gathered through the channel shuffle of a shuffle_ctot-channel tensor when
+ * shuffle_ctot != 0), y dense [M][N], mean / invstd / scale / shift from dpro_stats [4][G][N], k1..k3 from dpro_coef [3][G][N], the
+ * ReLU6 mask 0 < fmaf(scale, y, shift) < 6 with relu6 (or d' = d when dpro_y is NULL).  bf16_operands: a' and d' are rounded to bf16 after
+ * their float32 prologues; act_type 1 (a, d, y are bf16 tensors) needs it.
+ * cdrl_gemm_tn_plan: what gemm_tn dispatches on for these arguments (the launcher calls the same host function) -- launches nothing, reads
+ * no memory: only ld / coff of the views count.  Writes min(n_out, 21) int32 fields and returns 21 (-1: bad act_type, no field array):
+ *    0 ok       1: the call would run; 0: refused, field 1 says why and cdrl_last_error() holds the sentence
+ *    1 refusal  1 G < 1 or M not a multiple of G, 2 act_type 1 without bf16_operands, 3 an operand of 2 GB or more (M * ld * 4 bytes),
+ *               4 a view whose channels do not fit its rows, or shuffle / relu6 without the D prologue
+ *    2 kernel   0 tn_direct_kernel, 1 tn_direct_tr_kernel (exactly with the D prologue), 2 tn_lds_kernel (K, N >= 96, even ld / coff / K /
+ *               N, shuffle_ctot / 2 even); -1: M, N or K < 1, nothing to launch
+ *    3 mode     direct: 0 float32, 1 bf16 operands, 2 bf16 tensors; LDS: 0 float32 MFMA (CDRL_TN_LDS_F32=1), 1 bf16 operands, 2 bf16
+ *               tensors, 3 three bf16 planes per operand (float32 tensors, the default)
+ *    4 apro  5 dpro  6 NJW  7 WK  8 NSPL  9 RS  10 RS2  11 U   the instantiation and wave mapping of the direct kernels (6..11 are 0 for LDS)
+ *   12 gy  13 gz  14 nspg  15 nsplit = G * nspg (grid x)  16 rows_per workgroup  17 part_slots  18 part_elems = part_slots * K * N
+ *   19 reduce_form (cdrl_reduce_partials_plan, 16-byte aligned workspace)  20 dhalf: an LDS-kernel thread gathers the pair (s - 1, s) */
+int cdrl_gemm_tn_plan(const cdrl_view* a, const cdrl_view* d, int M, int N, int K, int G, int has_a_stats, int has_dpro, int shuffle_ctot,
+                      int relu6, int bf16_operands, int act_type, int32_t* fields, int n_out);
+/* floats of workspace cdrl_gemm_tn_ex needs for any prologue / operand type (0 for a shape it refuses) */
+int64_t cdrl_gemm_tn_ex_workspace_elems(int M, int N, int K, int G);
+int cdrl_gemm_tn_ex(const cdrl_view* a, const float* a_stats, const cdrl_view* d, const float* dpro_y, const float* dpro_stats,
+                    const float* dpro_coef, int shuffle_ctot, int relu6, float* out, int M, int N, int K, int G, float* workspace,
+                    int accumulate, int bf16_operands, int act_type, void* stream);
+/* out[i] (+)= float(sum_p part[p * stride + i]), i < n: the reduce behind every split-M float partial (double sums, fixed order).
+ * The plan writes min(n_out, 4) fields and returns 4: form (0 few partials, float4; 1 / 2 / 3 float4 with 16 / 4 / 1 column lanes;
+ * 4 / 5 scalar with 16 / 4 column lanes -- any alignment), grid, block x, block y.  -1: nparts < 1, n < 1 or stride < n. */
+int cdrl_reduce_partials_plan(uint64_t part_addr, int nparts, int64_t n, int64_t stride, int32_t* fields, int n_out);
+int cdrl_reduce_partials_f32(const float* part, int nparts, int64_t n, int64_t stride, float* out, int accumulate, void* stream);
 /* out[n][c] (float32) = mean over the P rows of frame n of [relu6](scale * y + shift); y dense [G*frames_per_group*P][C] */
 int cdrl_bn_act_gap_fwd(const float* y, const float* stats, float* out, int G, int frames_per_group, int P, int C, int relu6,
                         int act_type, void* stream);
