@@ -19,7 +19,8 @@ class Config(C.Structure):
                 ('stem', C.c_int32), ('stage_c', C.c_int32 * 3), ('stage_n', C.c_int32 * 3), ('last', C.c_int32),
                 ('feat', C.c_int32), ('rnn_image', C.c_int32), ('rnn_small', C.c_int32), ('dyn', C.c_int32),
                 ('head', C.c_int32), ('exp_scale', C.c_float), ('compute', C.c_int32),
-                ('freeze_trunk', C.c_int32), ('optimizer', C.c_int32), ('polyak', C.c_float), ('train_stats', C.c_int32)]
+                ('freeze_trunk', C.c_int32), ('optimizer', C.c_int32), ('polyak', C.c_float), ('train_stats', C.c_int32),
+                ('clip_mode', C.c_int32), ('skip_nonfinite', C.c_int32)]
 
 
 class TrainStatsLayout(C.Structure):
@@ -33,6 +34,9 @@ COMPUTE_F32, COMPUTE_BF16_OPERANDS, COMPUTE_BF16_STORAGE = 0, 1, 2
 # cdrl_config.optimizer: CDRL_OPT_* in this order (include/cdrl.h); the reference's optimizer names (rl/utils.py:29-37)
 OPTIMIZERS = ('adam', 'sgd', 'rmsprop', 'adagrad', 'adadelta', 'adamax', 'nadam', 'ftrl')
 # Keras' slot names per optimizer: (slot kept in the adam_m arena, slot kept in the adam_v arena), None where unused
+# cdrl_config.clip_mode: CDRL_CLIP_* in this order
+CLIP_TENSOR, CLIP_GLOBAL = 0, 1
+CLIP_MODES = ('tensor', 'global')
 OPTIMIZER_SLOTS = dict(adam=('m', 'v'), sgd=(None, None), rmsprop=(None, 'rms'), adagrad=(None, 'accumulator'),
                        adadelta=('accum_var', 'accum_grad'), adamax=('m', 'v'), nadam=('m', 'v'), ftrl=('linear', 'accumulator'))
 
@@ -45,13 +49,21 @@ class ParamInfo(C.Structure):
 class HParams(C.Structure):
     _fields_ = [('policy_lr', C.c_float), ('value_lr', C.c_float), ('dynamics_lr', C.c_float),
                 ('clip_ratio', C.c_float), ('entropy_coef', C.c_float), ('clip_norm_policy', C.c_float),
-                ('clip_norm_value', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float)]
+                ('clip_norm_value', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float),
+                ('clip_norm_dynamics', C.c_float)]
 
 
 class OptimizerState(C.Structure):
     """cdrl_optimizer_state (include/cdrl.h): the optimizers' device-side step counters and Nadam m_caches."""
     _fields_ = [('t_policy', C.c_int32), ('t_value', C.c_int32), ('t_dynamics', C.c_int32),
                 ('m_cache_policy', C.c_float), ('m_cache_value', C.c_float), ('m_cache_dynamics', C.c_float)]
+
+
+class GateStats(C.Structure):
+    """cdrl_gate_stats (include/cdrl.h): skip / apply counters and last norms and scales of the gradient gate; index 0 is
+    policy_apply, 1 value_apply."""
+    _fields_ = [('skipped', C.c_int32 * 2), ('applied', C.c_int32 * 2), ('norm', C.c_float * 2), ('scale', C.c_float * 2),
+                ('norm_dynamics', C.c_float * 2), ('scale_dynamics', C.c_float * 2)]
 
 
 _fp = C.c_void_p   # device pointers travel as plain addresses
@@ -105,6 +117,8 @@ PROTOTYPES = {
     'cdrl_learner_reset_optimizer_steps': (_i, [_L, _fp]),
     'cdrl_learner_get_optimizer_state': (_i, [_L, C.POINTER(OptimizerState), _fp]),
     'cdrl_learner_set_optimizer_state': (_i, [_L, C.POINTER(OptimizerState), _fp]),
+    'cdrl_learner_gate_stats': (_i, [_L, C.POINTER(GateStats), _fp]),
+    'cdrl_learner_gate_reset': (_i, [_L, _fp]),
     'cdrl_learner_train_stats_layout': (_i, [_L, C.POINTER(TrainStatsLayout)]),
     'cdrl_learner_train_stats_buffer': (_i, [_L, C.POINTER(C.c_void_p), C.POINTER(_i64)]),
     'cdrl_learner_train_stats_reset': (_i, [_L, _fp]),

@@ -126,6 +126,11 @@ class CARLAgent(PPOAgent):
         reference (core/carla_agent.py:351-373,430-463).  Typical use: load a trained trunk with `load_full=False`, fine-tune the heads.
         `optimizer=name` (PPOAgent): one Keras optimizer class for the policy, value AND dynamics optimizers, as the reference builds
         all three from the one name (core/carla_agent.py:123-124); `polyak < 1` averages the policy / value heads, not the trunk.
+        `clip_norm=(policy, value, dynamics)`: with `clip_mode='tensor'` (PPOAgent; the default) the first two are the per-tensor
+        tf.clip_by_norm thresholds of the heads and the third is parsed and unused -- the reference's trunk is never clipped (F9).
+        With `clip_mode='global'` each optimizer's gradient list is clipped by its global norm: the heads with the first two, the
+        trunk with the third (`clip_norm_dynamics` of hyper_parameters(): clip_norm[2] when it is a float, clip_norm itself when a
+        single float, else 0 = unclipped).  `skip_nonfinite=True` (PPOAgent) works in both modes.
         `batch_augment=True` (with `aug_intensity > 0` and an environment shard): the image stacks of all E environments are
         augmented by ONE batched call per step (Augmenter.batch) instead of one call per environment; plans, Philox offsets and
         the augmented images are those of the per-environment loop, bit for bit.
@@ -154,6 +159,8 @@ class CARLAgent(PPOAgent):
         # the reference computes should_clip_dynamics_grads but never reads it: trunk grads are unclipped (F9)
         self.should_clip_dynamics_grads = isinstance(clip_norm, float) or (clip_norm is not None and len(clip_norm) > 2
                                                                           and isinstance(clip_norm[2], float))
+        self.grad_norm_dynamics = float(clip_norm) if isinstance(clip_norm, float) else \
+            (float(clip_norm[2]) if self.should_clip_dynamics_grads else 0.0)
         self.dynamics_lr = DynamicParameter.create(value=dynamics_lr)
         self.dynamics_lr.load(config=self.config.get('dynamics_lr', {}))
         self._augmenter = None
@@ -282,6 +289,7 @@ class CARLAgent(PPOAgent):
     def hyper_parameters(self) -> dict:
         hp = super().hyper_parameters()
         hp['dynamics_lr'] = self.dynamics_lr()
+        hp['clip_norm_dynamics'] = self.grad_norm_dynamics       # read by the engines in clip_mode='global' only
         return hp
 
     # -- update -----------------------------------------------------------------------------------

@@ -64,7 +64,8 @@ class CARLANetwork(Network):
         CARLAgent passes its own update_dynamics.  (The reference's keyword defaults to False but is never read there; here it
         drives the engine, so the default is the agent's.)
         The agent's optimizer name and polyak coefficient (PPOAgent(optimizer=..., polyak=...)) configure every engine built here
-        (cdrl_config.optimizer / polyak).  When the agent logs (log_mode is not None) the learner engines keep a train-stats ring
+        (cdrl_config.optimizer / polyak), and so do its clip_mode and skip_nonfinite (PPOAgent(clip_mode=..., skip_nonfinite=...):
+        the gradient gate, cdrl_config.clip_mode / skip_nonfinite).  When the agent logs (log_mode is not None) the learner engines keep a train-stats ring
         of `agent.train_stats_rows` rows (cdrl_config.train_stats): `train_stats()` fetches one update()'s diagnostics."""
         super().__init__(agent)
         env = agent.env
@@ -89,7 +90,8 @@ class CARLANetwork(Network):
                         feat=self.dynamics_spec['features']['road']['units'], rnn_image=self.dynamics_spec['rnn']['image'],
                         rnn_small=self.dynamics_spec['rnn']['road'], dyn=self.dynamics_spec['units'],
                         head=p_branch['units'], exp_scale=self.exp_scale, compute=compute, freeze_trunk=not update_dynamics,
-                        optimizer=getattr(agent, 'optimizer_name', 'adam'), polyak=float(getattr(agent, 'polyak_coeff', 1.0)))
+                        optimizer=getattr(agent, 'optimizer_name', 'adam'), polyak=float(getattr(agent, 'polyak_coeff', 1.0)),
+                        clip_mode=getattr(agent, 'clip_mode', 'tensor'), skip_nonfinite=bool(getattr(agent, 'skip_nonfinite', False)))
         self.device = agent.device
         # update diagnostics: the learner engines only (main + ragged share one ring); off when the agent does not log
         self.train_stats_rows = int(getattr(agent, 'train_stats_rows', 0)) if agent.statistics.mode is not None else 0

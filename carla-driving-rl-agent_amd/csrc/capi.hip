@@ -86,6 +86,8 @@ void cdrl_config_default(cdrl_config* c) {
     c->optimizer = d.optimizer;
     c->polyak = d.polyak;
     c->train_stats = d.train_stats;
+    c->clip_mode = d.clip_mode;
+    c->skip_nonfinite = d.skip_nonfinite;
 }
 
 int cdrl_optimizer_slots(int optimizer, int32_t* used, float* init) {
@@ -155,6 +157,16 @@ int cdrl_learner_create(const cdrl_config* c, cdrl_learner** out) {
         return -1;
     }
     d.train_stats = c->train_stats;
+    if (c->clip_mode != CDRL_CLIP_TENSOR && c->clip_mode != CDRL_CLIP_GLOBAL) {
+        cdrl::set_error("cdrl_learner_create: clip_mode must be CDRL_CLIP_TENSOR (0) or CDRL_CLIP_GLOBAL (1) (got %d)", c->clip_mode);
+        return -1;
+    }
+    d.clip_mode = c->clip_mode;
+    if (c->skip_nonfinite != 0 && c->skip_nonfinite != 1) {
+        cdrl::set_error("cdrl_learner_create: skip_nonfinite must be 0 or 1 (got %d)", c->skip_nonfinite);
+        return -1;
+    }
+    d.skip_nonfinite = c->skip_nonfinite;
     if (cdrl::diag_active()) {      // loud, every time: results of this learner are WRONG by request (timing diagnostics)
         char ov[2048];
         cdrl::env_overrides(ov, (int)sizeof(ov));
@@ -264,6 +276,7 @@ int cdrl_learner_set_hparams(cdrl_learner* l, const cdrl_hparams* hp, void* stre
     h->beta1 = hp->beta1;
     h->beta2 = hp->beta2;
     h->eps = hp->eps;
+    l->impl->host_gate()->clip_norm_dynamics = hp->clip_norm_dynamics;
     return l->impl->upload_hp(S(stream));
 }
 
@@ -277,6 +290,11 @@ int cdrl_learner_share_hparams(cdrl_learner* l, const cdrl_learner* owner) {
     if (a.optimizer != b.optimizer || a.polyak != b.polyak) {      // one optimizer: its state and step counters must agree
         cdrl::set_error("cdrl_learner_share_hparams: optimizer / polyak differ (%d, %g vs the owner's %d, %g)", a.optimizer,
                         (double)a.polyak, b.optimizer, (double)b.polyak);
+        return -1;
+    }
+    if (a.clip_mode != b.clip_mode || a.skip_nonfinite != b.skip_nonfinite) {      // one gate block: one decision per step
+        cdrl::set_error("cdrl_learner_share_hparams: clip_mode / skip_nonfinite differ (%d, %d vs the owner's %d, %d)", a.clip_mode,
+                        a.skip_nonfinite, b.clip_mode, b.skip_nonfinite);
         return -1;
     }
     if (a.train_stats > 0 && b.train_stats > 0 && (a.train_stats != b.train_stats || a.freeze_trunk != b.freeze_trunk)) {      // one ring: one layout
@@ -330,6 +348,36 @@ int cdrl_learner_train_stats_buffer(const cdrl_learner* l, void** ptr, int64_t* 
 int cdrl_learner_train_stats_reset(cdrl_learner* l, void* stream) {
     CHECK_L(l);
     return l->impl->stats_reset(S(stream));
+}
+
+int cdrl_learner_gate_stats(const cdrl_learner* l, cdrl_gate_stats* out, void* stream) {
+    CHECK_L(l);
+    if (!out) {
+        cdrl::set_error("cdrl_learner_gate_stats: null output");
+        return -1;
+    }
+    if (!l->impl->gate_on()) {
+        cdrl::set_error("cdrl_learner_gate_stats: the learner has neither clip_mode = CDRL_CLIP_GLOBAL nor skip_nonfinite = 1");
+        return -1;
+    }
+    cdrl::GateBlock g;
+    const int rc = l->impl->gate_stats(&g, S(stream));
+    if (rc) return rc;
+    for (int h = 0; h < 2; ++h) {
+        out->skipped[h] = g.skipped[h], out->applied[h] = g.applied[h];
+        out->norm[h] = g.last_norm[h][0], out->scale[h] = g.last_scale[h][0];
+        out->norm_dynamics[h] = g.last_norm[h][1], out->scale_dynamics[h] = g.last_scale[h][1];
+    }
+    return 0;
+}
+
+int cdrl_learner_gate_reset(cdrl_learner* l, void* stream) {
+    CHECK_L(l);
+    if (!l->impl->gate_on()) {
+        cdrl::set_error("cdrl_learner_gate_reset: the learner has neither clip_mode = CDRL_CLIP_GLOBAL nor skip_nonfinite = 1");
+        return -1;
+    }
+    return l->impl->gate_reset(S(stream));
 }
 
 int cdrl_learner_set_comm_stream(cdrl_learner* l, void* stream) {

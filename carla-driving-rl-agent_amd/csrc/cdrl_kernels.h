@@ -530,15 +530,46 @@ int clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const int
 // The other optimizers of cdrl_config.optimizer (include/cdrl.h table; opt = CDRL_OPT_*) and polyak averaging, same arguments and
 // clip as clip_adam; m / v are the optimizer's slots in the adam_m / adam_v arenas.  Adam with polyak 1 IS clip_adam.
 // polyak < 1 (heads only): p = a * p_new + c * p_old in the same pass.
+// gate / gate_mode (GATE_MODE_*, below): the gated forms of the same kernels -- nothing is touched when the gate block says skip,
+// and in global mode the list's scale from the block replaces the per-tensor clip.  gate_mode 0 is the launch it always was.
+struct GateBlock;
 int clip_update(int opt, float polyak, float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev,
                 const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms, DevHP* hp, int which,
-                hipStream_t st, const double* chunk_part = nullptr, int ticked = 0);
+                hipStream_t st, const double* chunk_part = nullptr, int ticked = 0, const GateBlock* gate = nullptr,
+                int gate_mode = 0);
 // counters to 0, Nadam m_caches to 1 (cdrl_learner_reset_optimizer_steps)
 int reset_steps(DevHP* hp, hipStream_t st);
 // counters to t[0..2] (policy, value, dynamics), Nadam m_caches to m_cache[0..2], passed to the kernel by value
 // (cdrl_learner_set_optimizer_state); the float block in front of t_policy is not written
 int set_steps(DevHP* hp, const int t[3], const float m_cache[3], hipStream_t st);
 int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, hipStream_t st);
+
+// Gradient gate (cdrl_config.clip_mode = global and / or skip_nonfinite; include/cdrl.h): the norm of an optimizer's whole gradient
+// list, known on the device before any element of the list is applied.  One block per learner (shared like DevHP), written by
+// gate_decide in front of the updates of an apply step and read by the gated update / copy kernels behind it.
+struct GateBlock {
+    float clip_norm_dynamics;              // host-written (upload_hp), the only field the host writes; <= 0: trunk not clipped
+    float scale_head, scale_trunk;         // of the apply in flight (1 outside global mode)
+    int skip;                              // of the apply in flight
+    int skipped[2], applied[2];            // apply steps per head (0 policy, 1 value) since create / gate_reset
+    float last_norm[2][2], last_scale[2][2];      // [head][0: the head's list, 1: the trunk's] of that head's last apply
+};
+enum { GATE_GLOBAL = 1, GATE_GUARD = 2, GATE_TRUNK = 4 /* the apply consumes the trunk's gradient */, GATE_NADAM = 8,
+       GATE_HEAD_PARTS = 16 /* the head's chunk partials are wanted whatever the gate needs (train stats) */ };
+enum { GATE_MODE_OFF = 0, GATE_MODE_TENSOR = 1 /* skip only, per-tensor clip */, GATE_MODE_GLOBAL = 2 /* skip and list scale */ };
+// Chunk partials (as sqnorm_chunk_kernel forms them) of the head's table and, with nchunks_t > 0, of the trunk's, in one launch.  A
+// list whose norm neither the mode nor the guard needs (threshold <= 0 on the device, no guard) is not read.
+int gate_chunk_sqnorms(const float* g_head, const TensorSeg* segs_h, const int* chunk_tensor_h, const int64_t* chunk_off_h,
+                       int nchunks_h, double* part_h, const float* g_trunk, const TensorSeg* segs_t, const int* chunk_tensor_t,
+                       const int64_t* chunk_off_t, int nchunks_t, double* part_t, const DevHP* hp, const GateBlock* gate, int head,
+                       int flags, hipStream_t st);
+// One workgroup: folds the partials into the lists' squared norms (fixed order), writes scales, skip flag, last norms and the
+// skipped / applied counter, and -- unless the step is skipped -- ticks the step counters (head; trunk with GATE_TRUNK) and advances
+// the Nadam m_caches, as sqnorm_chunk_kernel does on the ungated path.
+int gate_decide(const double* part_h, int nchunks_h, const double* part_t, int nchunks_t, DevHP* hp, GateBlock* gate, int head,
+                int flags, hipStream_t st);
+int copy_two_gated(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, const GateBlock* gate,
+                   hipStream_t st);
 
 // ---------------------------------------------------------------- update diagnostics (train_stats.hip)
 // Chunk partials of a chunk table (sum of squares per 1024-element chunk, float64): one wave per chunk, no LDS.  Same partials

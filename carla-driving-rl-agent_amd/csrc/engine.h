@@ -33,6 +33,8 @@ struct Config {
     int optimizer = 0;      // CDRL_OPT_* of the policy, value and dynamics optimizers (include/cdrl.h table)
     float polyak = 1.0f;    // < 1: polyak averaging of the heads after their optimizer step
     int train_stats = 0;    // N > 0: device-resident ring of N update-diagnostics rows, one per apply step (include/cdrl.h)
+    int clip_mode = 0;      // CDRL_CLIP_TENSOR: per-tensor clip of the heads; CDRL_CLIP_GLOBAL: every optimizer's list by its global norm
+    int skip_nonfinite = 0; // 1: an apply step whose gradients hold a NaN / Inf writes nothing (include/cdrl.h, gradient gate)
 };
 
 enum Model : int { M_TRUNK = 0, M_POLICY = 1, M_VALUE = 2, M_OLD_POLICY = 3 };
@@ -145,6 +147,7 @@ public:
     void share_hp(const Learner& owner) {
         hp_dev_ = owner.hp_dev_;
         if (stats_ring_ && owner.stats_ring_) stats_ring_ = owner.stats_ring_;
+        if (gate_dev_ && owner.gate_dev_) gate_dev_ = owner.gate_dev_;      // one gate block: one set of counters
         drop_graphs();      // (captured kernel arguments name the block)
     }
     // Train-stats ring (cfg.train_stats rows; include/cdrl.h): STATS_HEADER int32 words -- [0] rows written since the last reset,
@@ -173,6 +176,12 @@ public:
     // Frozen trunk: no trunk gradient is ever written and the stream is never released; the whole trunk counts as "not final".
     int64_t tail_offset() const { return frozen() ? tr_size_[M_TRUNK] : tail_off_; }
     bool frozen() const { return cfg_.freeze_trunk != 0; }
+    // Gradient gate (clip_mode = global and / or skip_nonfinite): the apply steps take the gated launch sequence (gated_apply)
+    bool gate_on() const { return cfg_.clip_mode != 0 || cfg_.skip_nonfinite != 0; }
+    GateBlock* host_gate() { return &gate_host_; }
+    // one device-to-host copy of the block behind everything on `st` (waits for it); counters to zero, enqueued on `st`
+    int gate_stats(GateBlock* out, hipStream_t st);
+    int gate_reset(hipStream_t st);
     bool graphs_enabled() const { return graphs_enabled_; }
     // Named internal tensors (parity tests: the raw BatchNorm inputs, statistics blocks, max-pool argmax codes and dense
     // pre-activations from which the discrete ReLU6 / max-pool decisions of the last forward are reconstructed)
@@ -483,7 +492,12 @@ private:
     float *sample_u_ = nullptr, *sample_da_ = nullptr, *sample_db_ = nullptr;
     DevHP hp_host_;
     DevHP* hp_dev_ = nullptr;
-    DevHP* hp_stage_ = nullptr;     // pinned host staging
+    DevHP* hp_stage_ = nullptr;     // pinned host staging (DevHP, and one float behind it for the gate block's threshold)
+    GateBlock gate_host_;           // only clip_norm_dynamics is the host's
+    GateBlock* gate_dev_ = nullptr; // in the workspace of a learner with gate_on() (this learner's, or the hyper-parameter owner's)
+    int gated_apply(int head, hipStream_t st);
+    // the trunk has a chunk table: its norms are wanted by the train stats or by the gate
+    bool trunk_table() const { return !frozen() && (cfg_.train_stats > 0 || gate_on()); }
     // optimiser tables (device, inside workspace)
     struct SegTable {
         TensorSeg* segs = nullptr;

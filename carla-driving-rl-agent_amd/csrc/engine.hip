@@ -43,6 +43,9 @@ Learner::Learner(const Config& cfg) : cfg_(cfg) {
     hp_host_.beta2 = 0.999f;
     hp_host_.eps = 1e-7f;
     hp_host_.m_cache_policy = hp_host_.m_cache_value = hp_host_.m_cache_dynamics = 1.0f;
+    memset(&gate_host_, 0, sizeof(gate_host_));
+    gate_host_.scale_head = gate_host_.scale_trunk = 1.0f;
+    for (int h = 0; h < 2; ++h) gate_host_.last_scale[h][0] = gate_host_.last_scale[h][1] = 1.0f;
     at_ = cfg_.compute == 2 ? 1 : 0;
     guard_ = cdrl_getenv("CDRL_GUARD") && atoi(cdrl_getenv("CDRL_GUARD")) == 1;
     build(true);
@@ -1617,8 +1620,9 @@ void Learner::build(bool dry) {
     note_named("hparams", hp_dev_, sizeof(DevHP));      // 10 floats (lr x3, clip, entropy, clip norms x2, beta1, beta2, eps), 3 int step counters,
                                                         // 3 Nadam m_caches
     // optimiser tables
-    // (train stats, unfrozen: the trunk gets a table too -- it is never clipped, its norms are diagnostics only)
-    for (int m = (cfg_.train_stats > 0 && !frozen()) ? 0 : 1; m <= 2; ++m) {
+    // (train stats, unfrozen: the trunk gets a table too -- its norms are diagnostics there; the gradient gate folds them into the
+    // trunk list's norm)
+    for (int m = trunk_table() ? 0 : 1; m <= 2; ++m) {
         SegTable& s = seg_[m];
         int nt = 0;
         int64_t nch = 0;
@@ -1632,6 +1636,10 @@ void Learner::build(bool dry) {
         s.chunk_off = reinterpret_cast<int64_t*>(alloc((size_t)nch * 2));
         s.chunk_part = alloc_d((size_t)nch);
         s.sqnorms = alloc((size_t)nt);
+    }
+    if (gate_on()) {
+        gate_dev_ = reinterpret_cast<GateBlock*>(alloc(sizeof(GateBlock) / sizeof(float) + 4));
+        note_named("gate", gate_dev_, sizeof(GateBlock));
     }
     if (cfg_.train_stats > 0) {
         stats_ring_ = alloc(stats_bytes() / sizeof(float));
@@ -1649,7 +1657,7 @@ void Learner::build(bool dry) {
 }
 
 void Learner::build_seg_tables() {
-    for (int m = (cfg_.train_stats > 0 && !frozen()) ? 0 : 1; m <= 2; ++m) {
+    for (int m = trunk_table() ? 0 : 1; m <= 2; ++m) {
         SegTable& s = seg_[m];
         s.h_segs.clear();
         s.h_chunk_tensor.clear();
@@ -1683,7 +1691,7 @@ int Learner::upload_seg_tables() {
         CDRL_HIP(hipMemcpy(d_pack3_, h_pack3_.data(), h_pack3_.size() * sizeof(PwX3Pack), hipMemcpyHostToDevice));
     if (!h_gpack_.empty())
         CDRL_HIP(hipMemcpy(d_gpack_, h_gpack_.data(), h_gpack_.size() * sizeof(GemmX3Pack), hipMemcpyHostToDevice));
-    for (int m = (cfg_.train_stats > 0 && !frozen()) ? 0 : 1; m <= 2; ++m) {
+    for (int m = trunk_table() ? 0 : 1; m <= 2; ++m) {
         SegTable& s = seg_[m];
         CDRL_HIP(hipMemcpy(s.segs, s.h_segs.data(), s.h_segs.size() * sizeof(TensorSeg), hipMemcpyHostToDevice));
         CDRL_HIP(hipMemcpy(s.chunk_tensor, s.h_chunk_tensor.data(), s.h_chunk_tensor.size() * sizeof(int),
@@ -1783,8 +1791,9 @@ int Learner::bind(const Buffers& b) {
         CDRL_HIP(hipEventCreateWithFlags(&ev_aux_fork_, evf_int));
         CDRL_HIP(hipEventCreateWithFlags(&ev_aux_done_, evf_int));
     }
-    if (!hp_stage_) CDRL_HIP(hipHostMalloc(reinterpret_cast<void**>(&hp_stage_), sizeof(DevHP), 0));
+    if (!hp_stage_) CDRL_HIP(hipHostMalloc(reinterpret_cast<void**>(&hp_stage_), sizeof(DevHP) + sizeof(float), 0));
     CDRL_HIP(hipMemcpy(hp_dev_, &hp_host_, sizeof(DevHP), hipMemcpyHostToDevice));
+    if (gate_dev_) CDRL_HIP(hipMemcpy(gate_dev_, &gate_host_, sizeof(GateBlock), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1792,6 +1801,34 @@ int Learner::upload_hp(hipStream_t st) {
     // only the float block (lr / clip / entropy / betas); the Adam counters stay device-resident
     memcpy(hp_stage_, &hp_host_, sizeof(DevHP));
     CDRL_HIP(hipMemcpyAsync(hp_dev_, hp_stage_, offsetof(DevHP, t_policy), hipMemcpyHostToDevice, st));
+    if (gate_dev_) {        // the gate block's one host-written field; DevHP keeps its layout
+        static_assert(offsetof(GateBlock, clip_norm_dynamics) == 0, "the host writes the first float of the gate block");
+        float* stage = reinterpret_cast<float*>(hp_stage_ + 1);
+        *stage = gate_host_.clip_norm_dynamics;
+        CDRL_HIP(hipMemcpyAsync(gate_dev_, stage, sizeof(float), hipMemcpyHostToDevice, st));
+    }
+    tail_invalidate(st);
+    return 0;
+}
+
+int Learner::gate_stats(GateBlock* out, hipStream_t st) {
+    if (!gate_dev_) {
+        set_error("gate_stats: the learner has neither clip_mode = global nor skip_nonfinite, or is not bound");
+        return -1;
+    }
+    CDRL_HIP(hipMemcpyAsync(out, gate_dev_, sizeof(GateBlock), hipMemcpyDeviceToHost, st));
+    tail_invalidate(st);
+    CDRL_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int Learner::gate_reset(hipStream_t st) {
+    if (!gate_dev_) {
+        set_error("gate_reset: the learner has neither clip_mode = global nor skip_nonfinite, or is not bound");
+        return -1;
+    }
+    static_assert(offsetof(GateBlock, applied) == offsetof(GateBlock, skipped) + 2 * sizeof(int), "the four counters are contiguous");
+    CDRL_HIP(hipMemsetAsync(reinterpret_cast<unsigned char*>(gate_dev_) + offsetof(GateBlock, skipped), 0, 4 * sizeof(int), st));
     tail_invalidate(st);
     return 0;
 }
@@ -2005,7 +2042,35 @@ int Learner::policy_apply(hipStream_t caller) {
     return launch(caller, {3}, true, [&](hipStream_t st) -> int { return policy_apply_impl(st); });
 }
 
+// The apply step of a learner with the gradient gate: chunk norms of the lists the step consumes -> gate (scales,
+// skip flag, counter ticks) -> trunk update -> old_policy copy (policy) -> head update, the last three in their gated forms, which
+// return at once when the gate said skip.  Both updates run behind the tick.  No host read: the sequence is capturable.
+int Learner::gated_apply(int head, hipStream_t st) {
+    const int hm = head == 0 ? M_POLICY : M_VALUE;
+    const int64_t to = tr_offset(M_TRUNK), ho = tr_offset(hm);
+    const int opt = cfg_.optimizer;
+    const int flags = (cfg_.clip_mode == CDRL_CLIP_GLOBAL ? GATE_GLOBAL : 0) | (cfg_.skip_nonfinite ? GATE_GUARD : 0) |
+                      (frozen() ? 0 : GATE_TRUNK) | (opt == CDRL_OPT_NADAM ? GATE_NADAM : 0) |
+                      (cfg_.train_stats > 0 ? GATE_HEAD_PARTS : 0);
+    const int mode = cfg_.clip_mode == CDRL_CLIP_GLOBAL ? GATE_MODE_GLOBAL : GATE_MODE_TENSOR;
+    SegTable &s = seg_[hm], &t = seg_[M_TRUNK];
+    CDRL_TRY(gate_chunk_sqnorms(buf_.grads + ho, s.segs, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part, buf_.grads + to, t.segs,
+                                t.chunk_tensor, t.chunk_off, t.nchunks, t.chunk_part, hp_dev_, gate_dev_, head, flags, st));
+    CDRL_TRY(gate_decide(s.chunk_part, s.nchunks, t.chunk_part, t.nchunks, hp_dev_, gate_dev_, head, flags, st));
+    if (!frozen())
+        CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK],
+                             nullptr, nullptr, 0, nullptr, nullptr, hp_dev_, 2, st, nullptr, 1, gate_dev_, mode));
+    if (head == 0)
+        CDRL_TRY(copy_two_gated(buf_.params + tr_offset(M_OLD_POLICY), buf_.params + tr_offset(M_POLICY), tr_size_[M_POLICY],
+                                buf_.params + st_offset(M_OLD_POLICY), buf_.params + st_offset(M_POLICY), st_size_[M_POLICY], gate_dev_,
+                                st));
+    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + ho, buf_.grads + ho, buf_.adam_m + ho, buf_.adam_v + ho, tr_size_[hm],
+                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, head, st, s.chunk_part, 1, gate_dev_, mode));
+    return cfg_.train_stats > 0 ? stats_row(head, st) : 0;
+}
+
 int Learner::policy_apply_impl(hipStream_t st) {
+    if (gate_on()) return gated_apply(0, st);
     // order: trunk Adam (unclipped, F9) -> clip -> old_policy <- policy -> policy Adam
     // frozen trunk: no trunk Adam step, and the trunk's step counter stays where it is (reference ppo.py:238-252 on the heads only)
     // (another cdrl_config.optimizer: its step in place of Adam's, same launches; polyak < 1: the policy is averaged in its update)
@@ -2071,6 +2136,7 @@ int Learner::value_apply(hipStream_t caller) {
 }
 
 int Learner::value_apply_impl(hipStream_t st) {
+    if (gate_on()) return gated_apply(1, st);
     const int64_t to = tr_offset(M_TRUNK), vo = tr_offset(M_VALUE);
     const int opt = cfg_.optimizer, nadam = opt == CDRL_OPT_NADAM ? 8 : 0;
     if (!frozen())

@@ -157,7 +157,9 @@ int clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const int
 // clip + one step of the optimizer OPT (include/cdrl.h table) + optional polyak averaging.  The chunk / clip prologue is
 // clip_adam_kernel's, kept as a copy so that Adam's own kernel stays exactly as it was.  Per element one streaming pass over p, g
 // and the slots the optimizer uses (none for SGD; never the others).
-template <int OPT>
+// GATE (GATE_MODE_*): the gated forms.  Both return before touching anything when the gate block says skip; GATE_MODE_GLOBAL takes
+// the list's scale s from the block in place of the per-tensor clip (cn = s, denom = 1: the loop's g * cn / denom is g * s).
+template <int OPT, int GATE = GATE_MODE_OFF>
 __global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                           const int* __restrict__ chunk_tensor,
@@ -165,7 +167,8 @@ __global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p,
                                                           const TensorSeg* __restrict__ segs,
                                                           const float* __restrict__ sqnorms, const DevHP* __restrict__ hp,
                                                           int which, const double* __restrict__ chunk_part, int ticked,
-                                                          int blend, float pa, float pc) {
+                                                          int blend, float pa, float pc, const GateBlock* __restrict__ gate) {
+    if (GATE != GATE_MODE_OFF && gate->skip) return;
     int64_t beg, end;
     float cn = 0.0f, denom = 1.0f;
     const float clip_norm = which == 0 ? hp->clip_norm_policy : (which == 1 ? hp->clip_norm_value : 0.0f);
@@ -176,7 +179,7 @@ __global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p,
         beg = chunk_off[c];
         end = beg + CHUNK;
         if (end > s.off + s.n) end = s.off + s.n;
-        if ((sqnorms || chunk_part) && clip_norm > 0.0f) {
+        if (GATE != GATE_MODE_GLOBAL && (sqnorms || chunk_part) && clip_norm > 0.0f) {
             float l2;
             if (chunk_part) {       // (clip_adam_kernel: same fold, same bits)
                 const int lane = threadIdx.x & 63;
@@ -197,6 +200,7 @@ __global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p,
         end = beg + CHUNK;
         if (end > n) end = n;
     }
+    if (GATE == GATE_MODE_GLOBAL) cn = which == 2 ? gate->scale_trunk : gate->scale_head;
     const float lr = which == 0 ? hp->lr_policy : (which == 1 ? hp->lr_value : hp->lr_dynamics);
     const int t1 = (which == 0 ? hp->t_policy : (which == 1 ? hp->t_value : hp->t_dynamics)) + (ticked ? 0 : 1);
     const float b1 = hp->beta1, b2 = hp->beta2, eps = hp->eps;
@@ -280,15 +284,26 @@ __global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p,
 
 int clip_update(int opt, float polyak, float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev,
                 const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms, DevHP* hp, int which,
-                hipStream_t st, const double* chunk_part, int ticked) {
+                hipStream_t st, const double* chunk_part, int ticked, const GateBlock* gate, int gate_mode) {
     const int blend = polyak < 1.0f;
-    if (opt == CDRL_OPT_ADAM && !blend)
+    if (gate_mode != GATE_MODE_OFF && !gate) {
+        set_error("clip_update: gated form without a gate block");
+        return -1;
+    }
+    if (opt == CDRL_OPT_ADAM && !blend && gate_mode == GATE_MODE_OFF)
         return clip_adam(p, g, m, v, n, chunk_tensor_dev, chunk_off_dev, nchunks, segs_dev, sqnorms, hp, which, st, chunk_part, ticked);
     const float pa = polyak, pc = (float)(1.0 - (double)polyak);
     const int grid = chunk_tensor_dev ? nchunks : (int)cdiv64(n, CHUNK);
+#define CDRL_CLIP_UPDATE_G(O, G)                                                                                                 \
+    hipLaunchKernelGGL((clip_update_kernel<O, G>), dim3(grid), dim3(256), 0, st, p, g, m, v, n, chunk_tensor_dev, chunk_off_dev,  \
+                       segs_dev, sqnorms, hp, which, chunk_part, ticked, blend, pa, pc, gate)
+    // (a gated Adam step runs clip_update_kernel<CDRL_OPT_ADAM, ...>: the arithmetic of clip_adam_kernel, operation for operation)
 #define CDRL_CLIP_UPDATE(O)                                                                                                      \
-    hipLaunchKernelGGL(clip_update_kernel<O>, dim3(grid), dim3(256), 0, st, p, g, m, v, n, chunk_tensor_dev, chunk_off_dev,       \
-                       segs_dev, sqnorms, hp, which, chunk_part, ticked, blend, pa, pc)
+    do {                                                                                                                         \
+        if (gate_mode == GATE_MODE_OFF) CDRL_CLIP_UPDATE_G(O, GATE_MODE_OFF);                                                    \
+        else if (gate_mode == GATE_MODE_TENSOR) CDRL_CLIP_UPDATE_G(O, GATE_MODE_TENSOR);                                         \
+        else CDRL_CLIP_UPDATE_G(O, GATE_MODE_GLOBAL);                                                                            \
+    } while (0)
     switch (opt) {
         case CDRL_OPT_ADAM: CDRL_CLIP_UPDATE(CDRL_OPT_ADAM); break;
         case CDRL_OPT_SGD: CDRL_CLIP_UPDATE(CDRL_OPT_SGD); break;
@@ -301,6 +316,7 @@ int clip_update(int opt, float polyak, float* p, const float* g, float* m, float
         default: set_error("clip_update: unknown optimizer %d", opt); return -1;
     }
 #undef CDRL_CLIP_UPDATE
+#undef CDRL_CLIP_UPDATE_G
     CDRL_LAUNCH_CHECK();
     return 0;
 }
@@ -349,6 +365,153 @@ __global__ void __launch_bounds__(256) copy_two_kernel(float* __restrict__ d0, c
 int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, hipStream_t st) {
     if (n0 + n1 <= 0) return 0;
     hipLaunchKernelGGL(copy_two_kernel, dim3((unsigned)cdiv64(n0 + n1, 256)), dim3(256), 0, st, d0, s0, n0, d1, s1, n1);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- gradient gate (cdrl_config.clip_mode / skip_nonfinite; include/cdrl.h) ----------------------------------------------------
+// Whether the apply of `head` needs the squared norm of list 0 (the head's) or 1 (the trunk's): the guard needs every list the
+// step consumes, global mode the lists with a positive threshold.  One function for the chunk kernel and the gate.
+__device__ __forceinline__ bool gate_needs(const DevHP* hp, const GateBlock* gate, int head, int list, int flags) {
+    if (list == 1 && !(flags & GATE_TRUNK)) return false;
+    if (flags & GATE_GUARD) return true;
+    if (!(flags & GATE_GLOBAL)) return false;
+    return (list == 1 ? gate->clip_norm_dynamics : (head == 0 ? hp->clip_norm_policy : hp->clip_norm_value)) > 0.0f;
+}
+
+// blocks [0, nchunks_h): the head's chunk table, [nchunks_h, nchunks_h + nchunks_t): the trunk's.  The per-chunk sum is
+// sqnorm_chunk_kernel's (256 lanes striding the chunk, double, LDS tree): same partials, no tick.
+__global__ void __launch_bounds__(256) gate_chunk_kernel(const float* __restrict__ g_head, const TensorSeg* __restrict__ segs_h,
+                                                         const int* __restrict__ chunk_tensor_h,
+                                                         const int64_t* __restrict__ chunk_off_h, int nchunks_h,
+                                                         double* __restrict__ part_h, const float* __restrict__ g_trunk,
+                                                         const TensorSeg* __restrict__ segs_t,
+                                                         const int* __restrict__ chunk_tensor_t,
+                                                         const int64_t* __restrict__ chunk_off_t, double* __restrict__ part_t,
+                                                         const DevHP* __restrict__ hp, const GateBlock* __restrict__ gate, int head,
+                                                         int flags) {
+    __shared__ double sm[256];
+    const int list = (int)blockIdx.x < nchunks_h ? 0 : 1;
+    if (!gate_needs(hp, gate, head, list, flags) && !(list == 0 && (flags & GATE_HEAD_PARTS))) return;      // (uniform per block)
+    const int c = list == 0 ? (int)blockIdx.x : (int)blockIdx.x - nchunks_h;
+    const float* g = list == 0 ? g_head : g_trunk;
+    const TensorSeg s = list == 0 ? segs_h[chunk_tensor_h[c]] : segs_t[chunk_tensor_t[c]];
+    const int64_t beg = list == 0 ? chunk_off_h[c] : chunk_off_t[c];
+    int64_t end = beg + CHUNK;
+    if (end > s.off + s.n) end = s.off + s.n;
+    double acc = 0.0;
+    for (int64_t i = beg + threadIdx.x; i < end; i += 256) {
+        const double v = (double)g[i];
+        acc += v * v;
+    }
+    sm[threadIdx.x] = acc;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (threadIdx.x < k) sm[threadIdx.x] += sm[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) (list == 0 ? part_h : part_t)[c] = sm[0];
+}
+
+int gate_chunk_sqnorms(const float* g_head, const TensorSeg* segs_h, const int* chunk_tensor_h, const int64_t* chunk_off_h,
+                       int nchunks_h, double* part_h, const float* g_trunk, const TensorSeg* segs_t, const int* chunk_tensor_t,
+                       const int64_t* chunk_off_t, int nchunks_t, double* part_t, const DevHP* hp, const GateBlock* gate, int head,
+                       int flags, hipStream_t st) {
+    if (!(flags & GATE_TRUNK)) nchunks_t = 0;
+    if (nchunks_h + nchunks_t <= 0) return 0;
+    hipLaunchKernelGGL(gate_chunk_kernel, dim3(nchunks_h + nchunks_t), dim3(256), 0, st, g_head, segs_h, chunk_tensor_h, chunk_off_h,
+                       nchunks_h, part_h, g_trunk, segs_t, chunk_tensor_t, chunk_off_t, part_t, hp, gate, head, flags);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
+// sum of n chunk partials by one 256-thread workgroup: thread i adds the partials i, i + 256, ... in order, then a fixed LDS tree;
+// every thread returns the same bits
+__device__ __forceinline__ double gate_fold(const double* __restrict__ part, int n, double* sm) {
+    double acc = 0.0;
+    for (int c = threadIdx.x; c < n; c += 256) acc += part[c];
+    __syncthreads();        // (sm may still be read from the fold in front)
+    sm[threadIdx.x] = acc;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if (threadIdx.x < k) sm[threadIdx.x] += sm[threadIdx.x + k];
+        __syncthreads();
+    }
+    return sm[0];
+}
+
+// NaN and +-Inf elements are ordinary data: their squares make the double sum NaN or +Inf, which is all the guard asks about.  A
+// finite float32 squared is below 1.2e77, so no finite list overflows the sum.
+__device__ __forceinline__ bool gate_finite(double s) { return s <= 1.7976931348623157e308; }      // (false for NaN)
+
+__global__ void __launch_bounds__(256) gate_kernel(const double* __restrict__ part_h, int nchunks_h,
+                                                   const double* __restrict__ part_t, int nchunks_t, DevHP* hp, GateBlock* gate,
+                                                   int head, int flags) {
+    __shared__ double sm[256];
+    const bool need_h = gate_needs(hp, gate, head, 0, flags), need_t = gate_needs(hp, gate, head, 1, flags);
+    const double S_h = need_h ? gate_fold(part_h, nchunks_h, sm) : 0.0;
+    const double S_t = need_t ? gate_fold(part_t, nchunks_t, sm) : 0.0;
+    if (threadIdx.x != 0) return;
+    const int skip = (flags & GATE_GUARD) && !(gate_finite(S_h) && gate_finite(S_t)) ? 1 : 0;
+    const double n_h = sqrt(S_h), n_t = sqrt(S_t);
+    float s_h = 1.0f, s_t = 1.0f;
+    if (flags & GATE_GLOBAL) {      // s = (float)(c / max(sqrt(S), c)) in double, rounded once; at or below the threshold exactly 1
+        const double c_h = (double)(head == 0 ? hp->clip_norm_policy : hp->clip_norm_value), c_t = (double)gate->clip_norm_dynamics;
+        if (need_h && c_h > 0.0) s_h = (float)(c_h / fmax(n_h, c_h));
+        if (need_t && c_t > 0.0) s_t = (float)(c_t / fmax(n_t, c_t));
+    }
+    gate->scale_head = s_h;
+    gate->scale_trunk = s_t;
+    gate->skip = skip;
+    gate->last_norm[head][0] = (float)n_h;
+    gate->last_norm[head][1] = (float)n_t;
+    gate->last_scale[head][0] = s_h;
+    gate->last_scale[head][1] = s_t;
+    if (skip) {
+        gate->skipped[head] += 1;
+        return;
+    }
+    gate->applied[head] += 1;
+    // the ticks of sqnorm_chunk_kernel, in front of BOTH updates of the step (they run with ticked = 1)
+    const bool nadam = (flags & GATE_NADAM) != 0;
+    if (head == 0) {
+        hp->t_policy += 1;
+        if (nadam) hp->m_cache_policy = hp->m_cache_policy * nadam_mu(hp->beta1, hp->t_policy);
+    } else {
+        hp->t_value += 1;
+        if (nadam) hp->m_cache_value = hp->m_cache_value * nadam_mu(hp->beta1, hp->t_value);
+    }
+    if (flags & GATE_TRUNK) {
+        hp->t_dynamics += 1;
+        if (nadam) hp->m_cache_dynamics = hp->m_cache_dynamics * nadam_mu(hp->beta1, hp->t_dynamics);
+    }
+}
+
+int gate_decide(const double* part_h, int nchunks_h, const double* part_t, int nchunks_t, DevHP* hp, GateBlock* gate, int head,
+                int flags, hipStream_t st) {
+    if (head != 0 && head != 1) {
+        set_error("gate_decide: head %d", head);
+        return -1;
+    }
+    if (!(flags & GATE_TRUNK)) nchunks_t = 0;
+    hipLaunchKernelGGL(gate_kernel, dim3(1), dim3(256), 0, st, part_h, nchunks_h, part_t, nchunks_t, hp, gate, head, flags);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
+__global__ void __launch_bounds__(256) copy_two_gated_kernel(float* __restrict__ d0, const float* __restrict__ s0, int64_t n0,
+                                                             float* __restrict__ d1, const float* __restrict__ s1, int64_t n1,
+                                                             const GateBlock* __restrict__ gate) {
+    if (gate->skip) return;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n0) d0[i] = s0[i];
+    else if (i < n0 + n1) d1[i - n0] = s1[i - n0];
+}
+
+int copy_two_gated(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, const GateBlock* gate,
+                   hipStream_t st) {
+    if (n0 + n1 <= 0) return 0;
+    hipLaunchKernelGGL(copy_two_gated_kernel, dim3((unsigned)cdiv64(n0 + n1, 256)), dim3(256), 0, st, d0, s0, n0, d1, s1, n1, gate);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

@@ -33,6 +33,12 @@ def make_config(B, T=4, H=90, W=120, road=9, vehicle=4, navigation=5, A=2, **kw)
             if v.lower() not in _lib.OPTIMIZERS:
                 raise _lib.CdrlError(f'unknown optimizer {v!r}; select one of {_lib.OPTIMIZERS}')
             v = _lib.OPTIMIZERS.index(v.lower())
+        if k == 'clip_mode' and isinstance(v, str):
+            if v.lower() not in _lib.CLIP_MODES:
+                raise ValueError(f'unknown clip_mode {v!r}; select one of {_lib.CLIP_MODES}')
+            v = _lib.CLIP_MODES.index(v.lower())
+        if k == 'skip_nonfinite' and isinstance(v, bool):
+            v = int(v)
         if k in ('stage_c', 'stage_n'):
             for i in range(3):
                 getattr(cfg, k)[i] = v[i]
@@ -69,12 +75,19 @@ class LearnerEngine:
         heads after each optimizer step (cdrl_config.optimizer / polyak, include/cdrl.h).
         train_stats=N > 0 -> every policy_apply / value_apply appends one row of update diagnostics to a device ring of N rows
         (cdrl_config.train_stats); train_stats() fetches them.  Not inherited through share_with (rollout engines have no use for
-        it); an engine that is given it appends to the ring of the engine it shares with, when that one has a ring too."""
+        it); an engine that is given it appends to the ring of the engine it shares with, when that one has a ring too.
+        clip_mode -> 'tensor' (default: tf.clip_by_norm per tensor of the two heads, the trunk unclipped, as the reference does)
+        or 'global' (every optimizer's gradient list clipped by its global norm: the heads with clip_norm_policy / clip_norm_value,
+        the trunk with clip_norm_dynamics); an unknown name raises ValueError.  skip_nonfinite=True -> an apply step whose
+        gradients hold a NaN or an Inf writes nothing and is counted (gate_stats).  Both are cdrl_config fields (include/cdrl.h,
+        gradient gate), off by default, and inherited through share_with (a different value there is refused by the library)."""
         self.lib = _lib.load()
         if share_with is not None:
             cfg.setdefault('freeze_trunk', share_with.frozen)
             cfg.setdefault('optimizer', share_with.optimizer)
             cfg.setdefault('polyak', share_with.polyak)
+            cfg.setdefault('clip_mode', share_with.clip_mode)
+            cfg.setdefault('skip_nonfinite', share_with.skip_nonfinite)
         self.cfg = make_config(B, **cfg)
         h = C.c_void_p()
         _lib.check(self.lib.cdrl_learner_create(C.byref(self.cfg), C.byref(h)), 'cdrl_learner_create')
@@ -82,6 +95,9 @@ class LearnerEngine:
         self.frozen = bool(self.cfg.freeze_trunk)
         self.optimizer = _lib.OPTIMIZERS[self.cfg.optimizer]
         self.polyak = float(self.cfg.polyak)
+        self.clip_mode = _lib.CLIP_MODES[self.cfg.clip_mode]
+        self.skip_nonfinite = bool(self.cfg.skip_nonfinite)
+        self.gated = self.clip_mode == 'global' or self.skip_nonfinite     # the apply steps run the gated sequence
         used, init = (C.c_int32 * 2)(), (C.c_float * 2)()
         _lib.check(self.lib.cdrl_optimizer_slots(self.cfg.optimizer, used, init), 'cdrl_optimizer_slots')
         self.slot_init = (float(init[0]), float(init[1]))       # initial value of the adam_m / adam_v arena's slot
@@ -94,7 +110,7 @@ class LearnerEngine:
         self.workspace_bytes = int(self.lib.cdrl_learner_workspace_bytes(h))
         self.device = device
         self.hp = dict(policy_lr=3e-4, value_lr=3e-4, dynamics_lr=3e-4, clip_ratio=0.2, entropy_coef=1.0,
-                       clip_norm_policy=1.0, clip_norm_value=1.0, beta1=0.9, beta2=0.999, eps=1e-7)
+                       clip_norm_policy=1.0, clip_norm_value=1.0, beta1=0.9, beta2=0.999, eps=1e-7, clip_norm_dynamics=0.0)
         self._keep = []
         self._keep_stage = {}
         self._pred_out = None
@@ -180,6 +196,9 @@ class LearnerEngine:
         return {k: v.detach().cpu().numpy().copy() for k, v in self.param_views(model).items()}
 
     def set_hparams(self, **kw):
+        """Hyper-parameters of the following steps (cdrl_hparams).  clip_norm_* <= 0 or None: that clip is off.
+        clip_norm_dynamics is the trunk's threshold with clip_mode='global'; with 'tensor' it is accepted and ignored (the trunk
+        is never clipped there, as in the reference)."""
         if getattr(self, '_hp_owner', None) is not None:
             return self._hp_owner.set_hparams(**kw)
         self.hp.update(kw)
@@ -188,6 +207,7 @@ class LearnerEngine:
             setattr(hp, k, float(self.hp[k]))
         hp.clip_norm_policy = float(self.hp['clip_norm_policy'] or 0.0)
         hp.clip_norm_value = float(self.hp['clip_norm_value'] or 0.0)
+        hp.clip_norm_dynamics = float(self.hp.get('clip_norm_dynamics') or 0.0)
         _lib.check(self.lib.cdrl_learner_set_hparams(self.h, C.byref(hp), self._stream()), 'set_hparams')
 
     def set_comm_stream(self, stream: Optional['torch.cuda.Stream']):
@@ -287,6 +307,23 @@ class LearnerEngine:
         for name, dst in (('params', self.params), ('adam_m', self.adam_m), ('adam_v', self.adam_v)):
             dst.copy_(torch.from_numpy(arrays[name]))
         self.set_optimizer_state(**opt)
+
+    def gate_stats(self) -> dict:
+        """Counters and last norms / scales of the gradient gate (cdrl_gate_stats; the owner's block under share_with): per head
+        ('policy', 'value') dict(skipped=, applied= apply steps since create or gate_reset, norm=, scale= of the head's list and
+        norm_dynamics=, scale_dynamics= of the trunk's at that head's last apply; a norm that was not needed reads 0).  ONE
+        device-to-host copy behind everything on the current stream.  CdrlError when neither option is on."""
+        self._need_device('gate_stats')
+        gs = _lib.GateStats()
+        _lib.check(self.lib.cdrl_learner_gate_stats(self.h, C.byref(gs), self._stream()), 'gate_stats')
+        return {head: dict(skipped=int(gs.skipped[i]), applied=int(gs.applied[i]), norm=float(gs.norm[i]), scale=float(gs.scale[i]),
+                           norm_dynamics=float(gs.norm_dynamics[i]), scale_dynamics=float(gs.scale_dynamics[i]))
+                for i, head in enumerate(('policy', 'value'))}
+
+    def gate_reset(self):
+        """Skip / apply counters of the gradient gate to zero (enqueued on the current stream)."""
+        self._need_device('gate_reset')
+        _lib.check(self.lib.cdrl_learner_gate_reset(self.h, self._stream()), 'gate_reset')
 
     def _stats_owner(self):
         owner = getattr(self, '_hp_owner', None)

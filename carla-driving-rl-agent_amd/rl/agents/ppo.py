@@ -14,7 +14,7 @@ import torch
 from .. import utils
 from ..parameters import DynamicParameter
 from .agents import Agent
-from ..._lib import OPTIMIZERS
+from ..._lib import CLIP_MODES, OPTIMIZERS
 from ... import train_stats
 
 
@@ -22,8 +22,15 @@ class PPOAgent(Agent):
     def __init__(self, *args, policy_lr=1e-3, gamma=0.99, lambda_=0.95, value_lr=3e-4, load=False,
                  optimization_steps=(1, 1), name='ppo-agent', optimizer='adam', clip_norm=(1.0, 1.0), clip_ratio=0.2,
                  seed_regularization=False, entropy_regularization=0.0, network: dict = None, update_frequency=1,
-                 polyak=1.0, repeat_action=1, advantage_scale=2.0, train_stats_rows=256, **kwargs):
-        """train_stats_rows: capacity, in minibatch steps, of the device ring the learner engines append their per-step diagnostics
+                 polyak=1.0, repeat_action=1, advantage_scale=2.0, train_stats_rows=256, clip_mode='tensor', skip_nonfinite=False,
+                 **kwargs):
+        """clip_mode: 'tensor' (default; utils.clip_gradients of the reference: tf.clip_by_norm per tensor of each head) or 'global'
+        (tf.clip_by_global_norm of each optimizer's gradient list, the max_grad_norm of other PPO implementations; thresholds are
+        those of clip_norm).  skip_nonfinite=True: a minibatch step whose gradients hold a NaN or an Inf leaves parameters and
+        optimizer state untouched; update() logs how many were skipped (skipped_steps_policy / _value) and says so in one line.
+        With either option update() reads the gate statistics once, after the minibatch loops (one small copy); in global mode it
+        also logs the last gradients_global_norm_{policy,value,dynamics}.
+        train_stats_rows: capacity, in minibatch steps, of the device ring the learner engines append their per-step diagnostics
         to when the agent logs (log_mode is not None); update() reads it once.  An update() with more policy + value steps than
         that keeps the newest rows and reports how many it lost."""
         assert 0.0 < polyak <= 1.0
@@ -33,6 +40,11 @@ class PPOAgent(Agent):
         if str(optimizer).lower() not in OPTIMIZERS:
             raise ValueError(f'Cannot find optimizer {optimizer}. Select one of {OPTIMIZERS}.')
         self.optimizer_name = str(optimizer).lower()
+        if str(clip_mode).lower() not in CLIP_MODES:
+            raise ValueError(f'Unknown clip_mode {clip_mode}. Select one of {CLIP_MODES}.')
+        self.clip_mode = str(clip_mode).lower()
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._gate_seen = dict(policy=0, value=0)      # skip counts already reported by an earlier update()
         self.train_stats_rows = int(train_stats_rows)
         super().__init__(*args, name=name, **kwargs)
         self.memory: PPOMemory = None
@@ -131,6 +143,7 @@ class PPOAgent(Agent):
                 self.log(loss_value=value_loss, lr_value=self.value_lr.value)
         self.after_update()
         self.log_train_stats()
+        self.log_gate_stats()
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         print(f'Update took {round(time.time() - t0, 3)}s')
@@ -158,6 +171,22 @@ class PPOAgent(Agent):
                   f'(raise train_stats_rows)')
         for kw in train_stats.log_entries(stats['rows'], skip=train_stats.LOGGED_BY_UPDATE):
             self.log(**kw)
+
+    def log_gate_stats(self):
+        """Gradient-gate statistics of this update() (clip_mode='global' and / or skip_nonfinite): ONE copy after the minibatch
+        loops, by the rank that writes summaries only (every rank decides alike: the counters agree)."""
+        eng = getattr(self.network, 'engine', None)
+        if eng is None or not getattr(eng, 'gated', False) or not self.is_writer():
+            return
+        stats = eng.gate_stats()
+        new = {h: stats[h]['skipped'] - self._gate_seen[h] for h in ('policy', 'value')}
+        self._gate_seen = {h: stats[h]['skipped'] for h in ('policy', 'value')}
+        self.log(skipped_steps_policy=new['policy'], skipped_steps_value=new['value'])
+        if self.clip_mode == 'global':
+            self.log(gradients_global_norm_policy=stats['policy']['norm'], gradients_global_norm_value=stats['value']['norm'],
+                     gradients_global_norm_dynamics=stats['value']['norm_dynamics'])
+        if new['policy'] or new['value']:
+            print(f"[update] non-finite gradients: skipped {new['policy']} policy and {new['value']} value minibatch steps")
 
     def update_policy(self, gradients):
         return self.apply_policy_gradients(gradients), True

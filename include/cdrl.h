@@ -42,6 +42,8 @@ typedef struct cdrl_config {
     int32_t optimizer;                     /* CDRL_OPT_* (default CDRL_OPT_ADAM) of all three optimizers; see below         */
     float polyak;                          /* (0, 1], default 1 (off): polyak averaging of the heads; see below            */
     int32_t train_stats;                   /* 0 (default, off) or N > 0: ring of N update-diagnostics rows; see cdrl_train_stats_layout */
+    int32_t clip_mode;                     /* CDRL_CLIP_TENSOR (default) or CDRL_CLIP_GLOBAL; other values fail at create; see below   */
+    int32_t skip_nonfinite;                /* 0 (default) or 1: skip apply steps with a non-finite gradient; other values fail; see below */
 } cdrl_config;
 
 /* optimizer -- PPOAgent(optimizer=name) (reference rl/utils.py:29-46, rl/agents/ppo.py:105-106, core/carla_agent.py:123-124): one
@@ -74,6 +76,34 @@ typedef struct cdrl_config {
  * difference of float32 rounding only).  old_policy still receives the pre-update policy.  polyak = 1 is the plain update. */
 enum { CDRL_OPT_ADAM = 0, CDRL_OPT_SGD = 1, CDRL_OPT_RMSPROP = 2, CDRL_OPT_ADAGRAD = 3, CDRL_OPT_ADADELTA = 4, CDRL_OPT_ADAMAX = 5,
        CDRL_OPT_NADAM = 6, CDRL_OPT_FTRL = 7 };
+
+/* Gradient gate -- clip_mode and skip_nonfinite, both fixed at create and both off by default: a learner with neither enqueues in
+ * its apply steps exactly the launches it enqueues without the feature.  Both rest on the squared norm S of an optimizer's whole
+ * gradient LIST (policy head, value head, trunk), known on the device before any element of the list is applied: the sum in
+ * double of the squares of the float32 gradient elements of the list's trainable tensors (the padding between tensors is not part
+ * of it), as per-1024-element chunk sums folded in a fixed order.
+ *
+ * clip_mode = CDRL_CLIP_GLOBAL -- tf.clip_by_global_norm(gradients, norm) in place of utils.clip_gradients (per-tensor
+ * tf.clip_by_norm; reference rl/utils.py:120-121) in each apply_*_gradients: the policy head's list is clipped with
+ * cdrl_hparams.clip_norm_policy in policy_apply, the value head's with clip_norm_value in value_apply, and the trunk's with
+ * clip_norm_dynamics in both (not on a frozen trunk, which takes no step).  For a list with threshold c > 0 the scale is
+ * s = (float)(c / max(sqrt(S), c)), computed in double and rounded once, and every element becomes g * s, one float32 multiply;
+ * sqrt(S) <= c gives s == 1.0f exactly, an update identical bit for bit to the unclipped one.  A list with c <= 0 is not scaled
+ * (and its norm not computed unless the guard needs it).  With CDRL_CLIP_TENSOR clip_norm_dynamics is accepted and ignored: the
+ * trunk is never clipped, as in the reference.
+ *
+ * skip_nonfinite = 1 -- before anything is written, the apply step looks at the lists it is about to consume (the head's, and the
+ * trunk's unless frozen): if any S is not finite -- exactly when some element is NaN or +-Inf; finite float32 gradients cannot
+ * overflow the double sums, so a huge finite gradient is clipped or applied, never skipped -- the whole step is skipped.  A skipped
+ * step leaves bit-identical the whole parameter arena (old_policy included), both slot arenas, the three step counters and the
+ * Nadam m_caches, and increments the head's skip counter on the device.  Its train-stats row, when the ring is on, is still
+ * written and its norms show the non-finite values.  Works in both clip modes.  The decision is a pure function of the gradient
+ * arena: data-parallel ranks, whose arenas are identical after the all-reduce, decide alike with no collective.
+ *
+ * A gated apply enqueues: chunk sums (one launch for the lists involved), the gate (one workgroup: scales, skip flag, counter
+ * ticks), trunk update, old_policy copy (policy_apply), head update -- one launch more than the ungated step, no host read, no
+ * atomics; it can be captured in a hipGraph like the ungated one. */
+enum { CDRL_CLIP_TENSOR = 0, CDRL_CLIP_GLOBAL = 1 };
 
 /* freeze_trunk = 1 -- CARLAgent(update_dynamics=False) (reference core/carla_agent.py:77-80,351-373,430-463): the learner trains the
  * policy and value heads on a fixed trunk.  Fixed at create (the planner then leaves out the trunk-backward scratch:
@@ -116,6 +146,7 @@ typedef struct cdrl_hparams {
     float clip_ratio, entropy_coef;
     float clip_norm_policy, clip_norm_value;   /* <= 0 disables tf.clip_by_norm */
     float beta1, beta2, eps;
+    float clip_norm_dynamics;                  /* threshold of the trunk's list with CDRL_CLIP_GLOBAL (<= 0: off); ignored otherwise */
 } cdrl_hparams;
 
 /* One policy minibatch = what CARLAgent.policy_batch_tensors yields (core/carla_agent.py:323-331)
@@ -179,7 +210,8 @@ int cdrl_learner_set_hparams(cdrl_learner* l, const cdrl_hparams* hp, void* stre
 /* Makes `l` read its hyper-parameters and Adam step counters from `owner`'s device block (both bound, sharing the same
  * parameter / Adam arenas): a second learner built for the ragged LAST minibatch of an update (the reference's tf.data
  * pipeline keeps it unless drop_remainder is set, rl/utils.py:365-393) then advances the same optimizer.  Fails when the two
- * were created with a different optimizer or polyak. */
+ * were created with a different optimizer or polyak, or a different clip_mode or skip_nonfinite (`l` then also uses `owner`'s
+ * gate block: one set of skip counters). */
 int cdrl_learner_share_hparams(cdrl_learner* l, const cdrl_learner* owner);
 /* Data-parallel overlap: `stream` (caller-owned, or NULL to switch off) is made to wait inside every
  * following *_forward_backward call for the point of the backward pass at which the gradients of the head and of the trunk
@@ -207,6 +239,20 @@ typedef struct cdrl_optimizer_state {
 } cdrl_optimizer_state;
 int cdrl_learner_get_optimizer_state(const cdrl_learner* l, cdrl_optimizer_state* out, void* stream);
 int cdrl_learner_set_optimizer_state(cdrl_learner* l, const cdrl_optimizer_state* in, void* stream);
+/* Gradient-gate statistics (see clip_mode / skip_nonfinite above) of the block the learner gates with (the owner's after
+ * cdrl_learner_share_hparams).  Index 0 is policy_apply, 1 value_apply.  skipped / applied: apply steps since create or the last
+ * _reset.  norm / scale: sqrt(S) (rounded to float32) and s of the head's own list, norm_dynamics / scale_dynamics those of the
+ * trunk's list, at the LAST apply of that head; a norm that was not computed reads 0, a list that was not scaled has scale 1.
+ * The counters are diagnostics: they are neither part of cdrl_optimizer_state nor of a saved learner state.
+ * _stats: ONE device-to-host copy behind everything enqueued on `stream`, and waits for it.  _reset: the four counters to 0,
+ * enqueued on `stream`, no host sync.  Both fail with -1 on a learner that has neither option on. */
+typedef struct cdrl_gate_stats {
+    int32_t skipped[2], applied[2];
+    float norm[2], scale[2];
+    float norm_dynamics[2], scale_dynamics[2];
+} cdrl_gate_stats;
+int cdrl_learner_gate_stats(const cdrl_learner* l, cdrl_gate_stats* out, void* stream);
+int cdrl_learner_gate_reset(cdrl_learner* l, void* stream);
 
 /* ---- update diagnostics (train stats) --------------------------------------------------------
  * The scalars PPOAgent.update / CARLAgent.update log per minibatch (reference rl/agents/ppo.py:209-225; core/carla_agent.py:382,
@@ -273,7 +319,8 @@ int cdrl_learner_sequence_begin(cdrl_learner* l, void* stream);
 int cdrl_learner_sequence_end(cdrl_learner* l, void* stream);
 /* CARLAgent.apply_policy_gradients (core/carla_agent.py:375-388) + PPOAgent.apply_policy_gradients
  * (rl/agents/ppo.py:238-252): trunk Adam, per-tensor clip, old_policy <- policy, policy Adam (freeze_trunk = 1: no trunk Adam).
- * With another cdrl_config.optimizer, that optimizer's step in place of Adam's; polyak < 1 averages the policy after its step. */
+ * With another cdrl_config.optimizer, that optimizer's step in place of Adam's; polyak < 1 averages the policy after its step.
+ * With clip_mode = CDRL_CLIP_GLOBAL or skip_nonfinite = 1: the gated sequence (gradient gate, above). */
 int cdrl_learner_policy_apply(cdrl_learner* l, void* stream);
 /* CARLAgent.get_value_gradients / apply_value_gradients (core/carla_agent.py:430-463;
  * rl/agents/ppo.py:264-275). */

@@ -1,0 +1,425 @@
+"""Gradient gate on the GPU (cdrl_config.clip_mode = global, skip_nonfinite; include/cdrl.h): the gated apply kernels against the numpy
+restatement (tests/grad_gate_ref.py on top of tests/optim_ref.py) on injected gradients (no forward runs), the below-threshold path
+bit for bit against the ungated one, what a skipped step leaves untouched, huge finite gradients, graph replay, sharing, and a few
+agent updates.  NaN and Inf in a gradient arena are ordinary data here: nothing faults."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+from carla_driving_rl_agent_amd import _lib
+from carla_driving_rl_agent_amd.engine import LearnerEngine
+from tests.grad_gate_ref import F, clip_by_global_norm, list_sqnorm, should_skip
+from tests.optim_ref import SLOTS, OptState, polyak, step
+from tests.test_gpu_optimizers import H, SENTINEL, SEQ, W, _base_params, _engine, _grads, _hp, _segments
+from tests.test_optimizers_host import float64_bound
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADS = ('policy', 'value')
+
+
+def _segs(eng, model):
+    return [(s, c) for _, s, c in _segments(eng, model)]
+
+
+def _thresholds(eng, g, kind, above_head, above_trunk):
+    """float32 thresholds half (above: the list is clipped) or twice (below) the norm of the head's and the trunk's list of `g`."""
+    out = []
+    for model, above in ((kind, above_head), ('trunk', above_trunk)):
+        norm = np.sqrt(list_sqnorm(g, _segs(eng, model)))
+        out.append(float(F(norm * (0.5 if above else 2.0))))
+    return tuple(out)
+
+
+def _apply(eng, kind, g, lr, lr_t, c_head, c_trunk):
+    eng.set_hparams(policy_lr=lr, value_lr=lr, dynamics_lr=lr_t, clip_norm_policy=c_head, clip_norm_value=c_head,
+                    clip_norm_dynamics=c_trunk)
+    eng.grads.copy_(torch.as_tensor(g).to(eng.grads.device))
+    eng.policy_apply() if kind == 'policy' else eng.value_apply()
+
+
+def _restate(eng, p0, steps, opt, frozen, pk, dt):
+    """Expected trainable parameters, optimizer states and gate statistics after `steps` = [(kind, lr, lr_t, g, c_head, c_trunk)] in
+    global mode: every list the step consumes scaled by its own float32 scale, then tests/optim_ref.step."""
+    p = p0.astype(dt)
+    st = {m: OptState(opt, eng.grads_total, dt) for m in ('trunk', 'policy', 'value')}
+    stats = []
+    for kind, lr, lr_t, g, c_head, c_trunk in steps:
+        row = dict(norm_dynamics=0.0, scale_dynamics=1.0)
+        for model, c, rate, pol in (('trunk', c_trunk, lr_t, 1.0), (kind, c_head, lr, pk)):
+            if model == 'trunk' and frozen:
+                continue
+            gs, norm, s = clip_by_global_norm(g, _segs(eng, model), c, dt)
+            row.update(dict(norm_dynamics=norm, scale_dynamics=float(s)) if model == 'trunk' else dict(norm=norm, scale=float(s)))
+            o, n = eng.region(model, True)
+            sub = OptState(opt, n, dt)
+            sub.m, sub.v, sub.t, sub.m_cache = st[model].m[o:o + n], st[model].v[o:o + n], st[model].t, st[model].m_cache
+            new = step(sub, p[o:o + n], gs[o:o + n], rate)
+            if pol < 1.0:
+                new = polyak(new.astype(dt), p[o:o + n], pol, dt)
+            p[o:o + n] = new
+            st[model].t, st[model].m_cache = sub.t, sub.m_cache
+        stats.append(row)
+    return p, st, stats
+
+
+def _compare(eng, opt, frozen, ref32, ref64, tag):
+    params = eng.params.cpu().numpy()
+    arenas = (eng.adam_m.cpu().numpy(), eng.adam_v.cpu().numpy())
+    for model in HEADS if frozen else ('trunk',) + HEADS:
+        for name, s, c in _segments(eng, model):
+            for (p_ref, st, _), bound in ((ref32, 1e-6), (ref64, None)):
+                b = bound if bound is not None else float64_bound(opt, 'params')
+                got, exp = params[s:s + c], p_ref[s:s + c]
+                e = np.abs(got - exp).max() / (np.abs(exp).max() + 1e-30)
+                assert e < b, (tag, model, name, 'params', e)
+                for arena, slot, flat in zip(arenas, SLOTS[opt], (st[model].m, st[model].v)):
+                    if slot is None:
+                        continue
+                    b = bound if bound is not None else float64_bound(opt, slot)
+                    got, exp = arena[s:s + c], flat[s:s + c]
+                    e = np.abs(got - exp).max() / (np.abs(exp).max() + 1e-30)
+                    assert e < b, (tag, model, name, slot, e)
+    return params, arenas
+
+
+def _close(got, exp, what):
+    assert abs(got - exp) <= 1e-6 * abs(exp), (what, got, exp)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1. global clip
+# per step: (head list above its threshold, trunk list above its threshold)
+ABOVE = ((True, False), (False, True), (True, True))
+
+
+@pytest.mark.parametrize('opt,frozen,pk', [(o, f, 1.0) for o in ('adam', 'nadam', 'sgd', 'adadelta') for f in (False, True)]
+                         + [('nadam', False, 0.9)])
+def test_global_clip_matches_restatement(opt, frozen, pk):
+    p0 = _base_params().cpu().numpy()
+    eng = _engine(optimizer=opt, polyak=pk, freeze_trunk=frozen, clip_mode='global')
+    for arena, slot in zip((eng.adam_m, eng.adam_v), SLOTS[opt]):
+        if slot is None:
+            arena.fill_(SENTINEL)
+    steps, got_stats, before = [], [], None
+    for k, (kind, lr, lr_t, scale) in enumerate(SEQ):
+        g = _grads(eng, k, scale).numpy()
+        c_head, c_trunk = _thresholds(eng, g, kind, *ABOVE[k])
+        steps.append((kind, lr, lr_t, g, c_head, c_trunk))
+        if kind == 'policy':
+            before = eng.params.clone()
+        _apply(eng, kind, g, lr, lr_t, c_head, c_trunk)
+        got_stats.append(eng.gate_stats()[kind])
+    ref32 = _restate(eng, p0, steps, opt, frozen, pk, np.float32)
+    ref64 = _restate(eng, p0, steps, opt, frozen, pk, np.float64)
+    params, arenas = _compare(eng, opt, frozen, ref32, ref64, (opt, frozen, pk))
+    for arena, slot in zip(arenas, SLOTS[opt]):
+        if slot is None:
+            assert (arena[:eng.grads_total] == SENTINEL).all(), (opt, 'unused slot written')
+    if frozen:
+        o, n = eng.region('trunk', True)
+        assert np.array_equal(params[o:o + n], p0[o:o + n])
+    # the scales did what the plan says, and the gate reports the restatement's norms and scales
+    for k, (got, exp) in enumerate(zip(got_stats, ref32[2])):
+        assert (exp['scale'] < 1.0) == ABOVE[k][0] and (frozen or (exp['scale_dynamics'] < 1.0) == ABOVE[k][1])
+        for key in ('norm', 'scale', 'norm_dynamics', 'scale_dynamics'):
+            _close(got[key], exp[key], (k, key))
+        assert got['skipped'] == 0
+    assert [got_stats[-1]['applied'], got_stats[1]['applied']] == [2, 1]
+    # counters and Nadam's m_cache, as in the ungated path
+    counters, caches = _hp(eng)
+    assert counters == [2, 1, 0 if frozen else 3], counters
+    exp_cache = [ref32[1][m].m_cache if opt == 'nadam' else 1.0 for m in ('policy', 'value', 'trunk')]
+    if frozen:
+        exp_cache[2] = 1.0
+    np.testing.assert_allclose(caches, exp_cache, rtol=1e-6)
+    # old_policy is the pre-update policy; the heads' BatchNorm moving statistics are not touched
+    po, pn = eng.region('policy', True)
+    oo, on = eng.region('old_policy', True)
+    assert on == pn and np.array_equal(params[oo:oo + on], before.cpu().numpy()[po:po + pn])
+    for model in HEADS:
+        o, n = eng.region(model, False)
+        assert np.array_equal(params[o:o + n], p0[o:o + n]), model
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2. below threshold
+@pytest.mark.parametrize('kw', [dict(), dict(optimizer='nadam', polyak=0.9), dict(freeze_trunk=True)])
+def test_below_threshold_global_mode_is_the_unclipped_path(kw):
+    a, b = _engine(clip_mode='global', **kw), _engine(**kw)
+    for k, (kind, lr, lr_t, scale) in enumerate(SEQ):
+        g = _grads(a, k, scale).numpy()
+        _apply(a, kind, g, lr, lr_t, 1e30, 1e30)
+        _apply(b, kind, g, lr, lr_t, 0.0, 0.0)
+    torch.cuda.synchronize()
+    for name in ('params', 'adam_m', 'adam_v'):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    assert _hp(a) == _hp(b)
+    st = a.gate_stats()
+    assert all(st[h]['scale'] == 1.0 and st[h]['scale_dynamics'] == 1.0 and st[h]['skipped'] == 0 for h in HEADS)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3. skip
+def _state(eng):
+    torch.cuda.synchronize()
+    return (eng.params.clone(), eng.adam_m.clone(), eng.adam_v.clone(), eng.named_buffer('hparams', dtype=torch.int32)[:16].cpu().clone())
+
+
+def _same(a, b, what):
+    for x, y, name in zip(a[:3], b[:3], ('params', 'adam_m', 'adam_v')):
+        assert torch.equal(x, y), (what, name)
+    assert torch.equal(a[3][10:16], b[3][10:16]), (what, 'counters / m_caches')
+
+
+def _poison(eng, case, g):
+    """Writes the case's non-finite value into the flat gradient `g`; returns the kind of apply that consumes it."""
+    if case == 'head_nan':                    # last element of the largest policy tensor whose size is no multiple of 1024
+        s, c = max((sc for sc in _segs(eng, 'policy') if sc[1] % 1024), key=lambda sc: sc[1])
+        g[s + c - 1] = np.nan
+        return 'policy'
+    segs = _segs(eng, 'trunk')
+    if case == 'trunk_pinf_first':
+        g[segs[0][0]] = np.inf
+        return 'policy'
+    if case == 'trunk_ninf_last':
+        g[segs[-1][0] + segs[-1][1] - 1] = -np.inf
+        return 'value'
+    raise ValueError(case)
+
+
+def _padding(eng, model):
+    segs = _segs(eng, model)
+    return [i for (s, c), (s1, _) in zip(segs, segs[1:]) for i in range(s + c, s1)]
+
+
+@pytest.mark.parametrize('case', ['head_nan', 'trunk_pinf_first', 'trunk_ninf_last'])
+@pytest.mark.parametrize('mode', ['tensor', 'global'])
+def test_skip_leaves_everything_untouched(mode, case):
+    kw = dict(optimizer='nadam', polyak=0.9, clip_mode=mode, skip_nonfinite=True)
+    eng, twin = _engine(**kw), _engine(**kw)
+    for e in (eng, twin):                     # two clean steps first: slots, counters and m_caches are not at their initial values
+        for k, (kind, lr, lr_t, scale) in enumerate(SEQ[:2]):
+            _apply(e, kind, _grads(e, k, scale).numpy(), lr, lr_t, 1.0, 1.0)
+    snap = _state(eng)
+    g = _grads(eng, 2, 50.0).numpy()
+    kind = _poison(eng, case, g)
+    other = 'value' if kind == 'policy' else 'policy'
+    assert should_skip([list_sqnorm(g, _segs(eng, m)) for m in (kind, 'trunk')])
+    _apply(eng, kind, g, 5e-4, 2e-3, 1.0, 1.0)
+    _same(_state(eng), snap, (mode, case, 'skipped step'))                    # old_policy and every counter included
+    st = eng.gate_stats()
+    assert (st[kind]['skipped'], st[other]['skipped']) == (1, 0) and (st[kind]['applied'], st[other]['applied']) == (1, 1)
+    if case == 'head_nan':
+        assert np.isnan(st[kind]['norm'])
+    else:
+        assert np.isinf(st[kind]['norm_dynamics']) and np.isfinite(st[kind]['norm'])
+    # the next step is clean: bit-equal to a twin that never saw the poisoned one.  A NaN in the padding between the head's tensors
+    # (the head's list does not contain it) does not skip.
+    clean = _grads(eng, 3, 50.0).numpy()
+    dirty = clean.copy()
+    pad = _padding(eng, kind)
+    assert pad, 'the head arenas have padding between tensors (16-byte aligned tensor starts)'
+    dirty[pad] = np.nan
+    _apply(eng, kind, dirty, 5e-4, 2e-3, 1.0, 1.0)
+    _apply(twin, kind, clean, 5e-4, 2e-3, 1.0, 1.0)
+    _same(_state(eng), _state(twin), (mode, case, 'clean step'))
+    assert eng.gate_stats()[kind]['skipped'] == 1 and eng.gate_stats()[kind]['applied'] == 2
+    assert twin.gate_stats()[kind]['skipped'] == 0
+    assert torch.isfinite(eng.params).all()
+    eng.gate_reset()
+    st = eng.gate_stats()
+    assert all(st[h]['skipped'] == 0 and st[h]['applied'] == 0 for h in HEADS)
+
+
+@pytest.mark.parametrize('mode', ['tensor', 'global'])
+def test_frozen_trunk_ignores_a_poisoned_trunk_gradient(mode):
+    kw = dict(optimizer='nadam', clip_mode=mode, skip_nonfinite=True, freeze_trunk=True)
+    eng, twin = _engine(**kw), _engine(**kw)
+    clean = _grads(eng, 0, 50.0).numpy()
+    g = clean.copy()
+    segs = _segs(eng, 'trunk')
+    g[segs[0][0]], g[segs[-1][0] + segs[-1][1] - 1] = np.inf, -np.inf          # not consumed: the frozen step reads the head's list only
+    for kind in HEADS:
+        _apply(eng, kind, g, 3e-4, 1e-3, 1.0, 1.0)
+        _apply(twin, kind, clean, 3e-4, 1e-3, 1.0, 1.0)
+    _same(_state(eng), _state(twin), (mode, 'frozen'))
+    st = eng.gate_stats()
+    assert all(st[h]['skipped'] == 0 and st[h]['applied'] == 1 and st[h]['norm_dynamics'] == 0.0 for h in HEADS)
+    assert _hp(eng)[0] == [1, 1, 0] and torch.isfinite(eng.params).all()
+
+
+@pytest.mark.parametrize('mode', ['tensor', 'global'])
+def test_skipped_step_still_writes_its_train_stats_row(mode):
+    eng = _engine(clip_mode=mode, skip_nonfinite=True, train_stats=4)
+    clean = _grads(eng, 0, 1.0).numpy()
+    _apply(eng, 'policy', clean, 3e-4, 1e-3, 1.0, 1.0)
+    g = clean.copy()
+    assert _poison(eng, 'head_nan', g) == 'policy'
+    poisoned = max((e for e in eng.tables['policy'].entries if e['trainable'] and e['numel'] % 1024), key=lambda e: e['numel'])['name']
+    _apply(eng, 'policy', g, 3e-4, 1e-3, 1.0, 1.0)
+    rows = eng.train_stats()['rows']
+    assert [r['kind'] for r in rows] == ['policy', 'policy']
+    assert [r['t_head'] for r in rows] == [1, 1] and [r['t_dynamics'] for r in rows] == [1, 1]       # the skipped step took no step
+    assert all(np.isfinite(v) for v in rows[0]['norms'].values())
+    assert np.isnan(rows[1]['norms'][poisoned])
+    assert all(np.isfinite(v) for n, v in rows[1]['norms'].items() if n != poisoned)
+    want = {n: np.sqrt(list_sqnorm(clean, [(s, c)])) for n, s, c in _segments(eng, 'trunk')}
+    for n, v in rows[1]['trunk_norms'].items():
+        _close(v, want[n], n)
+    assert eng.gate_stats()['policy']['skipped'] == 1
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4. huge, finite
+def test_huge_finite_gradients_are_clipped_not_skipped():
+    p0 = _base_params().cpu().numpy()
+    eng = _engine(clip_mode='global', skip_nonfinite=True)
+    g = _grads(eng, 0, 1.0).numpy()
+    s, c = _segs(eng, 'policy')[0]
+    g[[s, s + c // 2, s + c - 1]] = 1e30                  # each square overflows float32; the double sum holds them
+    steps = [('policy', 3e-4, 1e-3, g, 1.0, 1.0)]
+    _apply(eng, 'policy', g, 3e-4, 1e-3, 1.0, 1.0)
+    ref32 = _restate(eng, p0, steps, 'adam', False, 1.0, np.float32)
+    ref64 = _restate(eng, p0, steps, 'adam', False, 1.0, np.float64)
+    _compare(eng, 'adam', False, ref32, ref64, 'huge')
+    st = eng.gate_stats()['policy']
+    assert st['skipped'] == 0 and st['applied'] == 1
+    _close(st['norm'], np.sqrt(3.0) * 1e30, 'norm')
+    _close(st['scale'], ref32[2][0]['scale'], 'scale')
+    assert 0.0 < st['scale'] < 1e-29
+    assert torch.isfinite(eng.params).all() and torch.isfinite(eng.adam_m).all() and torch.isfinite(eng.adam_v).all()
+    o, n = eng.region('policy', True)
+    assert not torch.equal(eng.params[o:o + n].cpu(), torch.as_tensor(p0[o:o + n]))
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5. graph replay
+# policy / value alternating; the first apply of each kind is captured, the others are replays: a poisoned replay of each kind
+# (steps 3 and 4), clean replays behind them
+GRAPH_SEQ = tuple(SEQ[k % 2][:3] + (1.0 + 20.0 * (k == 5),) for k in range(7))
+GRAPH_POISON = {3: 'trunk_ninf_last', 4: 'head_nan'}
+
+
+def _graph_run(eng):
+    skipped = []
+    for k, (kind, lr, lr_t, scale) in enumerate(GRAPH_SEQ):
+        g = _grads(eng, k, scale).numpy()
+        if k in GRAPH_POISON:
+            assert _poison(eng, GRAPH_POISON[k], g) == kind
+        _apply(eng, kind, g, lr, lr_t, 0.05, 0.5)
+        skipped.append(eng.gate_stats()[kind]['skipped'])
+    return dict(params=eng.params.cpu(), m=eng.adam_m.cpu(), v=eng.adam_v.cpu(), hp=_hp(eng), skipped=skipped, gate=eng.gate_stats())
+
+
+def _graph_worker(rank, out):
+    sys.path.insert(0, ROOT)
+    os.environ['CDRL_GRAPH'] = '1'
+    torch.cuda.set_device(0)
+    eng = _engine(optimizer='nadam', polyak=0.9, clip_mode='global', skip_nonfinite=True)
+    assert eng.lib.cdrl_learner_tail_offset(eng.h) == eng.region('trunk', True)[1]     # graphs are on in this process
+    torch.save(_graph_run(eng), os.path.join(out, 'gate.pt'))
+
+
+def test_gated_apply_replays_from_a_graph(tmp_path):
+    mp.spawn(_graph_worker, args=(str(tmp_path),), nprocs=1, join=True)
+    g = torch.load(tmp_path / 'gate.pt')
+    e = _graph_run(_engine(optimizer='nadam', polyak=0.9, clip_mode='global', skip_nonfinite=True))
+    assert e['skipped'] == [0, 0, 0, 1, 1, 1, 1] == g['skipped']
+    assert torch.equal(g['params'], e['params']) and torch.equal(g['m'], e['m']) and torch.equal(g['v'], e['v'])
+    assert g['hp'] == e['hp'] and e['hp'][0] == [3, 2, 5]
+    assert g['gate'] == e['gate']
+
+
+# ---------------------------------------------------------------------------------------------------------------- 6. sharing
+def test_shared_engines_inherit_and_share_the_gate():
+    owner = _engine(clip_mode='global', skip_nonfinite=True)
+    shared = LearnerEngine(2, device='cuda:0', share_with=owner, H=H, W=W)
+    assert shared.clip_mode == 'global' and shared.skip_nonfinite and shared.gated
+    for kw in (dict(clip_mode='tensor'), dict(skip_nonfinite=False)):
+        with pytest.raises(_lib.CdrlError, match='clip_mode / skip_nonfinite differ'):
+            LearnerEngine(2, device='cuda:0', share_with=owner, H=H, W=W, **kw)
+    with pytest.raises(_lib.CdrlError, match='clip_mode / skip_nonfinite differ'):
+        LearnerEngine(2, device='cuda:0', share_with=_engine(), H=H, W=W, skip_nonfinite=True)
+    # one block: a step of the shared engine is counted where the owner reads, and sees the owner's thresholds
+    snap = _state(owner)
+    g = _grads(owner, 0, 1.0).numpy()
+    _poison(owner, 'head_nan', g)
+    _apply(shared, 'policy', g, 3e-4, 1e-3, 1.0, 1.0)
+    _same(_state(owner), snap, 'shared skip')
+    np.testing.assert_equal(owner.gate_stats(), shared.gate_stats())          # (the skipped step's norm is NaN on both sides)
+    assert owner.gate_stats()['policy']['skipped'] == 1 and np.isnan(owner.gate_stats()['policy']['norm'])
+    with pytest.raises(_lib.CdrlError, match='neither'):
+        _engine().gate_stats()
+    with pytest.raises(_lib.CdrlError, match='neither'):
+        _engine().gate_reset()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7. agents
+def _agent(tmp_path, cls=None, **kw):
+    from carla_driving_rl_agent_amd.core import CARLAgent, FakeCARLAEnvironment
+    env = FakeCARLAEnvironment(image_shape=(48, 64, 3), time_horizon=2, num_waypoints=5, vehicle_features=4, num_actions=2)
+    cfg = dict(batch_size=8, seed=3, skip_data=1, drop_batch_remainder=True, shuffle=True, policy_lr=3e-4, value_lr=3e-4,
+               dynamics_lr=3e-4, aug_intensity=0.0, weights_dir=str(tmp_path), name='t', optimization_steps=(2, 1), log_mode='summary',
+               clip_norm=(1.0, 1.0, 0.5))
+    cfg.update(kw)
+    return (cls or CARLAgent)(env, **cfg)
+
+
+def _summary(tmp_path):
+    return {l['key']: l for l in map(json.loads, open(tmp_path / 'logs' / 't' / 'summary.jsonl'))}
+
+
+def test_agent_learns_in_global_mode_and_logs_the_gate(tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)
+    agent = _agent(tmp_path, clip_mode='global', skip_nonfinite=True)
+    eng = agent.network.engine
+    assert eng.clip_mode == 'global' and eng.skip_nonfinite and eng.hp['clip_norm_dynamics'] == 0.0
+    p0 = eng.params.clone()
+    agent.learn(episodes=1, timesteps=17, close=False)
+    assert eng.hp['clip_norm_dynamics'] == 0.5 and (eng.hp['clip_norm_policy'], eng.hp['clip_norm_value']) == (1.0, 1.0)
+    assert torch.isfinite(eng.params).all()
+    for m in ('trunk', 'policy', 'value'):
+        o, n = eng.region(m, True)
+        assert not torch.equal(p0[o:o + n], eng.params[o:o + n]), m
+    got = _summary(tmp_path)
+    keys = {'skipped_steps_policy', 'skipped_steps_value', 'gradients_global_norm_policy', 'gradients_global_norm_value',
+            'gradients_global_norm_dynamics'}
+    assert keys <= set(got), keys - set(got)
+    assert got['skipped_steps_policy']['mean'] == 0 and got['skipped_steps_value']['mean'] == 0
+    assert all(np.isfinite(got[k]['mean']) and got[k]['mean'] > 0 and got[k]['n'] == 1 for k in keys if k.startswith('gradients'))
+    st = eng.gate_stats()
+    assert (st['policy']['applied'], st['value']['applied']) == (4, 2)
+
+
+@pytest.mark.parametrize('guard', [True, False])
+def test_agent_survives_a_poisoned_minibatch_only_with_the_guard(tmp_path, monkeypatch, guard):
+    from carla_driving_rl_agent_amd.core import CARLAgent
+    monkeypatch.chdir(tmp_path)
+
+    class Poisoned(CARLAgent):
+        calls = 0
+
+        def apply_policy_gradients(self, gradients):
+            self.calls += 1
+            if self.calls == 2:
+                o, _ = self._step_engine.region('policy', True)
+                self._step_engine.grads[o] = float('nan')
+            return super().apply_policy_gradients(gradients)
+
+    agent = _agent(tmp_path, cls=Poisoned, skip_nonfinite=guard)
+    eng = agent.network.engine
+    agent.learn(episodes=1, timesteps=17, close=False)
+    assert agent.calls == 4
+    if not guard:            # the same poison without the guard: the guard, not luck, makes the difference
+        assert not torch.isfinite(eng.params).all()
+        assert 'skipped_steps_policy' not in _summary(tmp_path)
+        return
+    assert torch.isfinite(eng.params).all() and torch.isfinite(eng.adam_m).all() and torch.isfinite(eng.adam_v).all()
+    got = _summary(tmp_path)
+    assert got['skipped_steps_policy']['mean'] == 1 and got['skipped_steps_value']['mean'] == 0
+    assert 'gradients_global_norm_policy' not in got           # tensor mode: the per-tensor norms are the train stats'
+    st = eng.gate_stats()
+    assert (st['policy']['skipped'], st['policy']['applied'], st['value']['applied']) == (1, 3, 2)
+    counters, _ = _hp(eng)
+    assert counters == [3, 2, 5]                               # the run went on: three policy and two value steps were taken
