@@ -191,6 +191,7 @@ PROTOTYPES = {
     'cdrl_stem_block_bwd_workspace_doubles': (_i64, [_i] * 5),
     'cdrl_stem_block_bwd': (_i, [_fp] * 5 + [_i] * 5 + [_fp] * 7),
     'cdrl_stem_block_bwd_pooled': (_i, [_fp] * 6 + [_i] * 5 + [_fp] * 7),
+    'cdrl_stem_plan': (_i, [_i] * 9 + [C.POINTER(C.c_int32), _i]),
     'cdrl_pwconv_fused_partial_rows': (_i, [_i, _i, _i, _i]),
     'cdrl_pwconv_fused': (_i, [_fp, _i, _i, _fp, _fp, _i, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp]),
     'cdrl_pwconv_pack_elems': (_i64, [_i, _i]),

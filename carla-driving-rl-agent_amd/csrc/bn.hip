@@ -1003,13 +1003,14 @@ int pool_bn_bwd_reduce(const PoolSrc& ps, const float* y, int G, int frames_per_
                        hipStream_t st, int at) {
     {
         const int Mg = frames_per_group * ps.Ho * ps.Wo;
-        const VColGeom g = vcol_geom(Mg, C, NB_STATS);
-        if (g.vec == 4 && g.nloop == 1) {
+        const PoolReducePlan pr = pool_bn_reduce_plan(Mg, C, ps.pa != nullptr);       // (StemPlan::pr)
+        const VColGeom& g = pr.g;
+        if (pr.form == 1) {
             dim3 grid(g.nb, G), block(g.cx, g.cy);
             const size_t smb = (size_t)g.cy * 4 * g.cx * sizeof(double);
-            if (at && ps.pa) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<bf16_t, true>), grid, block, smb, st, ps, reinterpret_cast<const bf16_t*>(y), stats, G * C, C, Mg, g.rb, part);
+            if (at && pr.pooled) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<bf16_t, true>), grid, block, smb, st, ps, reinterpret_cast<const bf16_t*>(y), stats, G * C, C, Mg, g.rb, part);
             else if (at) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<bf16_t, false>), grid, block, smb, st, ps, reinterpret_cast<const bf16_t*>(y), stats, G * C, C, Mg, g.rb, part);
-            else if (ps.pa) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<float, true>), grid, block, smb, st, ps, y, stats, G * C, C, Mg, g.rb, part);
+            else if (pr.pooled) hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<float, true>), grid, block, smb, st, ps, y, stats, G * C, C, Mg, g.rb, part);
             else hipLaunchKernelGGL((pool_bn_bwd_reduce_v4_kernel<float, false>), grid, block, smb, st, ps, y, stats, G * C, C, Mg, g.rb, part);
             CDRL_LAUNCH_CHECK();
             return 0;

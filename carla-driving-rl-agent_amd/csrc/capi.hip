@@ -867,9 +867,31 @@ int cdrl_augment_images_batch(const float* in, float* out, int E, int T, int H, 
 }
 
 int64_t cdrl_stem_block_bwd_workspace_doubles(int B, int T, int H, int W, int Cout) {
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
-    const int Hp = same_out(Ho, 2), Wp = same_out(Wo, 2);
-    return (int64_t)T * vcol_geom(B * Hp * Wp, Cout).nb * 2 * Cout + stem_bwd_part_elems(B, T, H, W, Cout);
+    const StemPlan sp = stem_plan(B, T, H, W, Cout, 0, false, false, true);
+    return sp.pr_part_doubles + sp.ws_doubles;
+}
+
+int cdrl_stem_plan(int B, int T, int H, int W, int Cout, int act_type, int pooled, int db_adjacent, int y_aligned, int32_t* out, int n_out) {
+    if (bad_act_type(act_type)) return -1;
+    if (!out && n_out > 0) {
+        cdrl::set_error("cdrl_stem_plan: no field array");
+        return -1;
+    }
+    if (B < 1 || T < 1 || H < 3 || W < 3 || Cout < 1) {
+        cdrl::set_error("cdrl_stem_plan: B %d, T %d, H %d, W %d, Cout %d: at least one frame of 3 x 3 pixels and one channel", B, T, H, W, Cout);
+        return -1;
+    }
+    const StemPlan p = stem_plan(B, T, H, W, Cout, act_type, pooled != 0, db_adjacent != 0, y_aligned != 0);
+    const int32_t v[] = {p.Ho, p.Wo, p.Hp, p.Wp, p.fwd_vec, p.st_refusal, p.st_form, p.R, p.NB, p.nbpg, p.px, p.NP, p.lds, p.units_max, p.part_rows,
+                         p.pf.vec, p.pf.cx, p.pf.cy, p.pf.nloop, p.pf.rb, p.pf.nb, p.pr.form, p.pr.pooled, p.pr.g.nb, p.fg_form, p.ff_refusal, p.ff_form,
+                         p.NCH, p.ff_rowstats, p.rows_per, p.nblk, p.slices_max, p.single_reduce, (int32_t)p.part_doubles, (int32_t)p.ws_doubles,
+                         (int32_t)p.pr_part_doubles};
+    int n = 0;
+    for (int32_t x : v) {
+        if (n < n_out) out[n] = x;
+        ++n;
+    }
+    return n;
 }
 
 int cdrl_stem_block_bwd(const float* x, const float* y, const float* stats, const uint8_t* argmax, const float* dp, int B, int T,
@@ -881,14 +903,14 @@ int cdrl_stem_block_bwd(const float* x, const float* y, const float* stats, cons
 int cdrl_stem_block_bwd_pooled(const float* x, const float* y, const float* stats, const uint8_t* argmax, const float* dp,
                                const float* pooled, int B, int T, int H, int W, int Cout, float* dgamma, float* dbeta, float* coef,
                                float* dw, float* db, double* workspace, int act_type, void* stream) {
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
-    const int Hp = same_out(Ho, 2), Wp = same_out(Wo, 2);
+    const StemPlan sp = stem_plan(B, T, H, W, Cout, act_type, pooled != nullptr, db == dw + 27 * Cout, true);
+    const int Ho = sp.Ho, Wo = sp.Wo;
     hipStream_t st = S(stream);
     PoolSrc ps = make_pool_src(argmax, dp, Ho, Wo);
     ps.pa = pooled;
-    const int nb = vcol_geom(B * Hp * Wp, Cout).nb;
+    const int nb = sp.pr.g.nb;
     double* part = workspace;
-    double* fpart = workspace + (int64_t)T * nb * 2 * Cout;
+    double* fpart = workspace + sp.pr_part_doubles;
     CDRL_TRY(pool_bn_bwd_reduce(ps, y, T, B, Cout, stats, part, st, act_type));
     CDRL_TRY(bn_bwd_finalize(part, nb, T, B * Ho * Wo, Cout, stats, dgamma, dbeta, coef, st));
     return stem_bwd_filter_fused(x, ps, y, stats, coef, dw, db, B, T, H, W, Cout, fpart, st, act_type);

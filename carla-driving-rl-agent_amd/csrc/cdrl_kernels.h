@@ -203,6 +203,55 @@ int stem_fwd_stats_nb(int B, int T, int H, int W, int Cout);
 int stem_fwd_stats(const float* x, const float* w, const float* bias, float* y, double* part, int B, int T, int H, int W, int Cout,
                    hipStream_t st, int at = 0);
 int64_t stem_bwd_part_elems(int B, int T, int H, int W, int Cout);
+// Geometry of the band form of stem_fwd_stats (conv.hip: stem_fwd_band_kernel takes it by value)
+struct StemFwdGeom {
+    int R, NB, nbpg, xs_floats, px;     // band rows, bands per frame, workgroups per time slice, LDS floats of a band, 16-byte chunks per thread
+    size_t lds;
+    bool ok;
+};
+// Pool forward / scatter-form BatchNorm sums of the stem block: the geometry their launchers (maxpool_bn_fwd in conv.hip,
+// pool_bn_bwd_reduce in bn.hip) dispatch on, as functions of (rows, C) only
+inline VColGeom stem_pool_fwd_geom(int rows, int C) { return vcol_geom(rows, C, 4096); }
+struct PoolReducePlan {
+    int form;       // 1: pool_bn_bwd_reduce_v4_kernel (4 channels per thread, one channel-lane pass), 0: the generic vcolreduce skeleton
+    int pooled;     // the v4 kernel takes mask and xhat from the pooled activated output (ps.pa given)
+    VColGeom g;
+};
+inline PoolReducePlan pool_bn_reduce_plan(int Mg, int C, bool has_pooled) {
+    PoolReducePlan p;
+    p.g = vcol_geom(Mg, C, NB_STATS);
+    p.form = p.g.vec == 4 && p.g.nloop == 1;
+    p.pooled = p.form && has_pooled;
+    return p;
+}
+// Every host decision of the stem block conv 3x3/s2 'valid' -> BatchNorm + ReLU6 -> max-pool 3x3/s2 'same' in one place: stem_fwd,
+// stem_fwd_stats(_nb), maxpool_bn_fwd, pool_bn_bwd_reduce, stem_bwd_filter(_fused) and the workspace queries take theirs from here, and
+// cdrl_stem_plan reports the struct.  A function of the shape, the storage type and three facts about the pointers; reads no memory.
+enum { STEM_REFUSE_COUT = 1, STEM_REFUSE_2GB = 2, STEM_REFUSE_ALIGN = 3 };
+struct StemPlan {
+    int Ho, Wo, Hp, Wp;                 // conv output, pooled output
+    int fwd_vec;                        // stem_fwd: 1 four channels per thread, 0 stem_fwd_scalar_kernel (Cout % 4 or y not 16-byte aligned)
+    int st_refusal;                     // stem_fwd_stats: 0, STEM_REFUSE_COUT (Cout % 4 or > 64), STEM_REFUSE_ALIGN
+    int st_form;                        // 0 stem_fwd_band_kernel, 1 stem_fwd_stats_kernel (window form)
+    int R, NB, nbpg, px, NP, lds;       // band: rows, bands per frame, workgroups per slice, 16-byte chunks per thread; pixels per thread; LDS bytes
+    int units_max;                      // (frame, band) units the busiest workgroup walks (window form: 1 row range)
+    int st_rb;                          // window form: rows per workgroup
+    int part_rows;                      // rows of the [T][part_rows][2][Cout] partials
+    StemFwdGeom geom;
+    VColGeom pf;                        // maxpool_bn_fwd
+    PoolReducePlan pr;                  // pool_bn_bwd_reduce
+    int64_t pr_part_doubles;            // T * pr.g.nb * 2 * Cout
+    int fg_form;                        // stem_bwd_filter: 0 stem_bwd_mfma_kernel<false>, 2 column reduce (Cout > 32)
+    int ff_refusal;                     // stem_bwd_filter_fused: 0, STEM_REFUSE_COUT (Cout % 4 or > 32), STEM_REFUSE_2GB
+    int ff_form;                        // 1 stem_bwd_mfma_kernel<true>, -1 refused
+    int NCH;                            // 16-byte channel chunks per half-wave lane of the fused kernel (unfused: 1)
+    int ff_rowstats;                    // fused: 1 the form that reads its slice's seven values per row (slices_max > 2), 0 two staged slices
+    int rows_per, nblk;                 // rows per workgroup, workgroups (column reduce: rb, nb of col_geom)
+    int slices_max;                     // time slices the rows of one workgroup can come from
+    int single_reduce;                  // fused: db == dw + 27 * Cout, one reduce over the 28 * Cout columns
+    int64_t part_doubles, ws_doubles;   // workspace doubles the filter gradient writes / stem_bwd_part_elems
+};
+StemPlan stem_plan(int B, int T, int H, int W, int Cout, int at, bool pooled, bool db_adjacent, bool y_aligned);
 // stem filter gradient with the stem BatchNorm's backward apply + max-pool gather fused into the operand load (dy is
 // never materialised); y: raw stem conv output, stats/coef: the stem BN's [4|3][T][Cout] blocks
 bool stem_bwd_fused_supported(int Cout);

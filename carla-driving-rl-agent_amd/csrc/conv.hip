@@ -184,11 +184,7 @@ __global__ void __launch_bounds__(256) stem_fwd_stats_kernel(const float* __rest
 #ifndef STEM_FWD_NP
 #define STEM_FWD_NP 2        // pixels per thread and iteration (4: 256 VGPRs, one wave per SIMD)
 #endif
-struct StemFwdGeom {
-    int R, NB, nbpg, xs_floats, px;     // band rows, bands per frame, workgroups per time slice, LDS floats of a band, 16-byte chunks per thread
-    size_t lds;
-    bool ok;
-};
+// (StemFwdGeom: cdrl_kernels.h)
 
 template <int NP, int PX, class AT>
 __global__ void __launch_bounds__(256) stem_fwd_band_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
@@ -345,25 +341,112 @@ static StemFwdGeom stem_fwd_geom(int B, int T, int H, int W, int Cout) {
 }
 
 bool stem_fwd_stats_supported(int Cout) { return (Cout % 4) == 0 && Cout <= 64; }
+bool stem_bwd_fused_supported(int Cout) { return Cout <= 32 && (Cout % 4) == 0; }
 
-int stem_fwd_stats_nb(int B, int T, int H, int W, int Cout) {
-    const StemFwdGeom bg = stem_fwd_geom(B, T, H, W, Cout);
-    if (bg.ok) return bg.nbpg;
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
-    const int Mg = B * Ho * Wo;
-    const int rb = cdiv(Mg, NB_STATS);
-    return cdiv(Mg, rb);
+#define STEM_NBLK_MAX 2048                          // capacity of the partial buffer of the MFMA filter gradient
+static int stem_nblk() {
+    static const int n = 1024;
+    return n < 64 ? 64 : (n > STEM_NBLK_MAX ? STEM_NBLK_MAX : n);
 }
+
+// time slices (Mg rows each) that the rows [k * rows_per, (k + 1) * rows_per) of one workgroup can come from, the largest over k
+static int stem_slices_max(int rows, int rows_per, int Mg, int T) {
+    if (rows <= 0 || Mg <= 0 || rows_per <= 0) return 0;
+    int m = 1;
+    if (rows_per <= Mg) {                           // at most one slice boundary per workgroup: is one of them inside a workgroup?
+        for (int g = 1; g < T && m == 1; ++g)
+            if (((int64_t)g * Mg) % rows_per) m = 2;
+        return m;
+    }
+    for (int r0 = 0; r0 < rows; r0 += rows_per) {
+        const int r1 = std::min(r0 + rows_per, rows);
+        m = std::max(m, (r1 - 1) / Mg - r0 / Mg + 1);
+    }
+    return m;
+}
+
+StemPlan stem_plan(int B, int T, int H, int W, int Cout, int at, bool pooled, bool db_adjacent, bool y_aligned) {
+    StemPlan p{};
+    p.Ho = (H - 3) / 2 + 1;
+    p.Wo = (W - 3) / 2 + 1;
+    p.Hp = same_out(p.Ho, 2);
+    p.Wp = same_out(p.Wo, 2);
+    const int Mg = B * p.Ho * p.Wo;
+    // plain forward
+    p.fwd_vec = (Cout % 4 == 0) && y_aligned;
+    // forward with statistics
+    p.st_refusal = !stem_fwd_stats_supported(Cout) ? STEM_REFUSE_COUT : !y_aligned ? STEM_REFUSE_ALIGN : 0;
+    p.geom = stem_fwd_geom(B, T, H, W, Cout);
+    if (p.geom.ok) {
+        static const int npx = STEM_FWD_NP;
+        p.st_form = 0;
+        p.R = p.geom.R;
+        p.NB = p.geom.NB;
+        p.nbpg = p.geom.nbpg;
+        p.px = p.geom.px;
+        p.NP = npx >= 4 ? 4 : npx == 3 ? 3 : 2;
+        p.lds = (int)p.geom.lds;
+        p.units_max = cdiv(B * p.geom.NB, p.geom.nbpg);
+        p.part_rows = p.geom.nbpg;
+    } else {
+        p.st_form = 1;
+        p.st_rb = std::max(1, cdiv(Mg, NB_STATS));
+        p.part_rows = cdiv(Mg, p.st_rb);
+        p.nbpg = p.part_rows;
+        p.NP = 4;
+        p.units_max = 1;
+        if (Cout >= 4 && Cout % 4 == 0 && Cout <= 1024) {
+            const int cx = Cout / 4, cy = 256 / cx;
+            p.lds = (int)std::max((size_t)(27 * Cout + Cout) * sizeof(float), (size_t)8 * cy * cx * sizeof(double));
+        }
+    }
+    // pool forward, scatter-form BatchNorm sums over the pooled gradient
+    p.pf = stem_pool_fwd_geom(B * T * p.Hp * p.Wp, Cout);
+    p.pr = pool_bn_reduce_plan(B * p.Hp * p.Wp, Cout, pooled);
+    p.pr_part_doubles = (int64_t)T * p.pr.g.nb * 2 * Cout;
+    // filter gradient
+    const int64_t rows64 = (int64_t)B * T * p.Ho * p.Wo;
+    const int rows = (int)rows64;
+    p.NCH = 1;
+    if (Cout <= 32) {
+        p.fg_form = 0;
+        p.rows_per = std::max(128, cdiv(cdiv(rows, stem_nblk()), 128) * 128);
+        p.nblk = cdiv(rows, p.rows_per);
+        p.slices_max = stem_slices_max(rows, p.rows_per, Mg, T);
+        p.part_doubles = ((int64_t)p.nblk * 28 * Cout + 1) / 2;                 // float partials inside a double buffer
+        p.ws_doubles = ((int64_t)STEM_NBLK_MAX * 28 * Cout + 1) / 2;
+    } else {
+        const ColGeom g = col_geom(rows, Cout, NB_FILTER);
+        p.fg_form = 2;
+        p.rows_per = g.rb;
+        p.nblk = g.nb;
+        p.slices_max = stem_slices_max(rows, g.rb, Mg, T);
+        p.part_doubles = p.ws_doubles = (int64_t)g.nb * 28 * Cout;
+    }
+    p.ff_refusal = !stem_bwd_fused_supported(Cout) ? STEM_REFUSE_COUT : rows64 * Cout * 4 >= (1ll << 31) ? STEM_REFUSE_2GB : 0;
+    p.ff_form = p.ff_refusal ? -1 : 1;
+    if (!p.ff_refusal) {
+        p.NCH = ((Cout >> 2) + 1) / 2 <= 3 ? 3 : 4;
+        // the kernel stages the statistics of two time slices; a workgroup whose rows come from more reads them row by row
+        p.ff_rowstats = p.slices_max > 2;
+        p.single_reduce = db_adjacent;
+    }
+    (void)at;                                       // both storage types take the same decisions; the launchers pick the element type
+    return p;
+}
+
+int stem_fwd_stats_nb(int B, int T, int H, int W, int Cout) { return stem_plan(B, T, H, W, Cout, 0, false, false, true).part_rows; }
 
 int stem_fwd_stats(const float* x, const float* w, const float* bias, float* y, double* part, int B, int T, int H, int W, int Cout,
                    hipStream_t st, int at) {
-    if (!stem_fwd_stats_supported(Cout) || (reinterpret_cast<uintptr_t>(y) & 15) != 0) {
+    const StemPlan sp = stem_plan(B, T, H, W, Cout, at, false, false, (reinterpret_cast<uintptr_t>(y) & 15) == 0);
+    if (sp.st_refusal) {
         set_error("stem_fwd_stats: Cout=%d / alignment not supported", Cout);
         return -1;
     }
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
-    const StemFwdGeom bg = stem_fwd_geom(B, T, H, W, Cout);
-    if (bg.ok) {
+    const int Ho = sp.Ho, Wo = sp.Wo;
+    if (sp.st_form == 0) {
+        const StemFwdGeom& bg = sp.geom;
 #define CDRL_STEM_FWD_BAND_LAUNCH(NPN, PXN)                                                                                                 \
     do {                                                                                                                                    \
         if (at) hipLaunchKernelGGL((stem_fwd_band_kernel<NPN, PXN, bf16_t>), dim3(T * bg.nbpg), dim3(256), bg.lds, st, x, w, bias,          \
@@ -371,12 +454,11 @@ int stem_fwd_stats(const float* x, const float* w, const float* bias, float* y, 
         else hipLaunchKernelGGL((stem_fwd_band_kernel<NPN, PXN, float>), dim3(T * bg.nbpg), dim3(256), bg.lds, st, x, w, bias, y, part, B,  \
                                 T, H, W, Ho, Wo, Cout, bg);                                                                                 \
     } while (0)
-        static const int npx = STEM_FWD_NP;
-        if (npx >= 4) {
+        if (sp.NP == 4) {
             if (bg.px == 2) CDRL_STEM_FWD_BAND_LAUNCH(4, 2);
             else if (bg.px == 4) CDRL_STEM_FWD_BAND_LAUNCH(4, 4);
             else CDRL_STEM_FWD_BAND_LAUNCH(4, 6);
-        } else if (npx == 3) {
+        } else if (sp.NP == 3) {
             if (bg.px == 2) CDRL_STEM_FWD_BAND_LAUNCH(3, 2);
             else if (bg.px == 4) CDRL_STEM_FWD_BAND_LAUNCH(3, 4);
             else CDRL_STEM_FWD_BAND_LAUNCH(3, 6);
@@ -389,26 +471,20 @@ int stem_fwd_stats(const float* x, const float* w, const float* bias, float* y, 
         CDRL_LAUNCH_CHECK();
         return 0;
     }
-    const int Mg = B * Ho * Wo;
-    const int rb = cdiv(Mg, NB_STATS);
-    const int nb = cdiv(Mg, rb);
+    const int rb = sp.st_rb, nb = sp.part_rows;
     const int cx = Cout / 4, cy = 256 / cx;
-    size_t lds = (size_t)(27 * Cout + Cout) * sizeof(float);
-    const size_t red = (size_t)8 * cy * cx * sizeof(double);
-    if (lds < red) lds = red;
-    static const int np = 4;
+    const size_t lds = (size_t)sp.lds;
     if (at) hipLaunchKernelGGL((stem_fwd_stats_kernel<4, bf16_t>), dim3(nb, T), dim3(cx, cy), lds, st, x, w, bias, reinterpret_cast<bf16_t*>(y), part, B, T, H, W, Ho, Wo, Cout, rb);
-    else if (np >= 4) hipLaunchKernelGGL((stem_fwd_stats_kernel<4, float>), dim3(nb, T), dim3(cx, cy), lds, st, x, w, bias, y, part, B, T, H, W, Ho, Wo, Cout, rb);
-    else if (np >= 2) hipLaunchKernelGGL((stem_fwd_stats_kernel<2, float>), dim3(nb, T), dim3(cx, cy), lds, st, x, w, bias, y, part, B, T, H, W, Ho, Wo, Cout, rb);
-    else hipLaunchKernelGGL((stem_fwd_stats_kernel<1, float>), dim3(nb, T), dim3(cx, cy), lds, st, x, w, bias, y, part, B, T, H, W, Ho, Wo, Cout, rb);
+    else hipLaunchKernelGGL((stem_fwd_stats_kernel<4, float>), dim3(nb, T), dim3(cx, cy), lds, st, x, w, bias, y, part, B, T, H, W, Ho, Wo, Cout, rb);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
 
 int stem_fwd(const float* x, const float* w, const float* bias, float* y, int B, int T, int H, int W, int Cout,
              hipStream_t st) {
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
-    const bool v4 = (Cout % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
+    const StemPlan sp = stem_plan(B, T, H, W, Cout, 0, false, false, (reinterpret_cast<uintptr_t>(y) & 15) == 0);
+    const int Ho = sp.Ho, Wo = sp.Wo;
+    const bool v4 = sp.fwd_vec != 0;
     const int64_t total = (int64_t)B * T * Ho * Wo * (v4 ? Cout / 4 : Cout);
     int64_t nb = cdiv64(total, 256 * 2);
     if (nb > 16384) nb = 16384;
@@ -452,11 +528,7 @@ struct StemBwdF {
 // 32x32 accumulator; the 4 accumulators are summed through LDS at the end and written as one
 // float partial per workgroup (deterministic two-stage reduction, no atomics).
 typedef float f32x16_c __attribute__((ext_vector_type(16)));
-#define STEM_NBLK_MAX 2048                          // capacity of the partial buffer
-static int stem_nblk() {
-    static const int n = 1024;
-    return n < 64 ? 64 : (n > STEM_NBLK_MAX ? STEM_NBLK_MAX : n);
-}
+// (STEM_NBLK_MAX, stem_nblk: next to stem_plan above)
 
 // FUSED: dy is not read but computed on the fly, dy = k1*(dz - k2 - xhat*k3) with dz gathered from the pooled gradient
 // through the max-pool argmax (pool_gather) and masked by ReLU6: the stem BatchNorm's backward "apply" and the 255 MB
@@ -479,7 +551,10 @@ __device__ __forceinline__ void stem_wave_sync() {
 #define STEM_BWD_WGS 3      // waves per SIMD the register allocation aims at (153 + 16 registers sat one above the three-wave step: 180 -> 173 us)
 #endif
 // AT: element type of the pooled gradient and of the raw conv output y in the FUSED form (bf16 activation storage)
-template <bool FUSED, int NCH, class AT = float>
+// ROWSTATS (FUSED only): a workgroup's rows may come from more than the two time slices CF holds (few rows per slice: B * Ho * Wo below
+// rows_per / 2), so every row reads the seven values of ITS slice from global memory -- slow, and only selected at such tiny shapes
+// (StemPlan::ff_rowstats); the other instantiations are what they were.
+template <bool FUSED, int NCH, class AT = float, bool ROWSTATS = false>
 __global__ void __launch_bounds__(256, STEM_BWD_WGS) stem_bwd_mfma_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                             float* __restrict__ part, int B, int T, int H, int W, int Ho,
                                                             int Wo, int Cout, int rows, int rows_per, StemBnBwd bb) {
@@ -499,7 +574,7 @@ __global__ void __launch_bounds__(256, STEM_BWD_WGS) stem_bwd_mfma_kernel(const 
         (&P[wave][0][0])[i] = 0.0f;
         (&D[wave][0][0])[i] = 0.0f;
     }
-    if (FUSED) {
+    if (FUSED && !ROWSTATS) {
         const int GC = T * Cout;
         for (int i = tid; i < 2 * 7 * 32; i += 256) {
             const int gg = i / (7 * 32), q = (i / 32) % 7, c = i % 32;
@@ -622,8 +697,15 @@ __global__ void __launch_bounds__(256, STEM_BWD_WGS) stem_bwd_mfma_kernel(const 
                     for (int w4 = 0; w4 < 4; ++w4)
                         if (((ga[j][w4] >> (8 * i)) & 0x7fu) == wk[w4]) d += __uint_as_float(gd[j][w4][i]);
                     const float v = __uint_as_float(gy[j][i]);
-                    const float mean = CF[gs][0][c0 + i], inv = CF[gs][1][c0 + i], sc = CF[gs][2][c0 + i], sh = CF[gs][3][c0 + i];
-                    const float k1 = CF[gs][4][c0 + i], k2 = CF[gs][5][c0 + i], k3 = CF[gs][6][c0 + i];
+                    float mean, inv, sc, sh, k1, k2, k3;
+                    if (ROWSTATS) {         // t is the row's own slice (0 for a row that does not exist: its result is dropped)
+                        const int GC = T * Cout, o = t * Cout + c0 + i;
+                        mean = bb.stats[o]; inv = bb.stats[GC + o]; sc = bb.stats[2 * GC + o]; sh = bb.stats[3 * GC + o];
+                        k1 = bb.coef[o]; k2 = bb.coef[GC + o]; k3 = bb.coef[2 * GC + o];
+                    } else {
+                        mean = CF[gs][0][c0 + i]; inv = CF[gs][1][c0 + i]; sc = CF[gs][2][c0 + i]; sh = CF[gs][3][c0 + i];
+                        k1 = CF[gs][4][c0 + i]; k2 = CF[gs][5][c0 + i]; k3 = CF[gs][6][c0 + i];
+                    }
                     const float z = fmaf(sc, v, sh);
                     if (!relu6_open(z)) d = 0.0f;
                     const float xh = (v - mean) * inv;
@@ -659,21 +741,16 @@ __global__ void __launch_bounds__(256, STEM_BWD_WGS) stem_bwd_mfma_kernel(const 
     }
 }
 
-int64_t stem_bwd_part_elems(int B, int T, int H, int W, int Cout) {
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
-    if (Cout <= 32) return ((int64_t)STEM_NBLK_MAX * 28 * Cout + 1) / 2;      // float partials inside a double buffer
-    ColGeom g = col_geom(B * T * Ho * Wo, Cout, NB_FILTER);
-    return (int64_t)g.nb * 28 * Cout;
-}
+int64_t stem_bwd_part_elems(int B, int T, int H, int W, int Cout) { return stem_plan(B, T, H, W, Cout, 0, false, false, true).ws_doubles; }
 
 int stem_bwd_filter(const float* x, const float* dy, float* dw, float* db, int B, int T, int H, int W, int Cout,
                     double* part, hipStream_t st) {
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
+    const StemPlan sp = stem_plan(B, T, H, W, Cout, 0, false, false, true);
+    const int Ho = sp.Ho, Wo = sp.Wo;
     const int rows = B * T * Ho * Wo;
-    if (Cout <= 32) {
+    if (sp.fg_form == 0) {
         float* pf = reinterpret_cast<float*>(part);
-        int rows_per = cdiv(cdiv(rows, stem_nblk()), 128) * 128;
-        const int nblk = cdiv(rows, rows_per);
+        const int rows_per = sp.rows_per, nblk = sp.nblk;
         hipLaunchKernelGGL((stem_bwd_mfma_kernel<false, 1>), dim3(nblk), dim3(256), 0, st, x, dy, pf, B, T, H, W, Ho, Wo, Cout, rows,
                            rows_per, StemBnBwd{});
         CDRL_LAUNCH_CHECK();
@@ -682,32 +759,43 @@ int stem_bwd_filter(const float* x, const float* dy, float* dw, float* db, int B
     }
     StemBwdF f{x, dy, B, T, H, W, Ho, Wo, Cout};
     CDRL_TRY(launch_colreduce<28>(f, 1, rows, Cout, part, st, NB_FILTER));
-    ColGeom g = col_geom(rows, Cout, NB_FILTER);
-    CDRL_TRY(reduce_partials(part, g.nb, 27 * Cout, (int64_t)28 * Cout, dw, 0, st));
-    CDRL_TRY(reduce_partials(part + 27 * Cout, g.nb, Cout, (int64_t)28 * Cout, db, 0, st));
+    CDRL_TRY(reduce_partials(part, sp.nblk, 27 * Cout, (int64_t)28 * Cout, dw, 0, st));
+    CDRL_TRY(reduce_partials(part + 27 * Cout, sp.nblk, Cout, (int64_t)28 * Cout, db, 0, st));
     return 0;
 }
 
-bool stem_bwd_fused_supported(int Cout) { return Cout <= 32 && (Cout % 4) == 0; }
-
 int stem_bwd_filter_fused(const float* x, const PoolSrc& ps, const float* y, const float* stats, const float* coef, float* dw,
                           float* db, int B, int T, int H, int W, int Cout, double* part, hipStream_t st, int at) {
-    if (!stem_bwd_fused_supported(Cout)) {
+    const StemPlan sp = stem_plan(B, T, H, W, Cout, at, ps.pa != nullptr, db == dw + 27 * Cout, true);
+    if (sp.ff_refusal == STEM_REFUSE_COUT) {
         set_error("stem_bwd_filter_fused: Cout=%d not supported", Cout);
         return -1;
     }
-    const int Ho = (H - 3) / 2 + 1, Wo = (W - 3) / 2 + 1;
+    const int Ho = sp.Ho, Wo = sp.Wo;
     const int rows = B * T * Ho * Wo;
-    if ((int64_t)rows * Cout * 4 >= (1ll << 31)) {       // 32-bit buffer-descriptor offsets
+    if (sp.ff_refusal) {                                 // 32-bit buffer-descriptor offsets
         set_error("stem_bwd_filter_fused: conv output of 2 GB or more is not supported (rows=%d)", rows);
         return -1;
     }
     float* pf = reinterpret_cast<float*>(part);
-    int rows_per = cdiv(cdiv(rows, stem_nblk()), 128) * 128;
-    const int nblk = cdiv(rows, rows_per);
+    const int rows_per = sp.rows_per, nblk = sp.nblk;
     StemBnBwd bb{ps, y, stats, coef};
-    const bool n3 = ((Cout >> 2) + 1) / 2 <= 3;
-    if (at && n3)
+    const bool n3 = sp.NCH == 3;
+    if (sp.ff_rowstats) {
+        // rows of more than two time slices in one workgroup (a few rows per slice): the per-row form
+        if (at && n3)
+            hipLaunchKernelGGL((stem_bwd_mfma_kernel<true, 3, bf16_t, true>), dim3(nblk), dim3(256), 0, st, x, nullptr, pf, B, T, H, W, Ho, Wo, Cout,
+                               rows, rows_per, bb);
+        else if (at)
+            hipLaunchKernelGGL((stem_bwd_mfma_kernel<true, 4, bf16_t, true>), dim3(nblk), dim3(256), 0, st, x, nullptr, pf, B, T, H, W, Ho, Wo, Cout,
+                               rows, rows_per, bb);
+        else if (n3)
+            hipLaunchKernelGGL((stem_bwd_mfma_kernel<true, 3, float, true>), dim3(nblk), dim3(256), 0, st, x, nullptr, pf, B, T, H, W, Ho, Wo, Cout,
+                               rows, rows_per, bb);
+        else
+            hipLaunchKernelGGL((stem_bwd_mfma_kernel<true, 4, float, true>), dim3(nblk), dim3(256), 0, st, x, nullptr, pf, B, T, H, W, Ho, Wo, Cout,
+                               rows, rows_per, bb);
+    } else if (at && n3)
         hipLaunchKernelGGL((stem_bwd_mfma_kernel<true, 3, bf16_t>), dim3(nblk), dim3(256), 0, st, x, nullptr, pf, B, T, H, W, Ho, Wo, Cout, rows,
                            rows_per, bb);
     else if (at)
@@ -721,7 +809,7 @@ int stem_bwd_filter_fused(const float* x, const PoolSrc& ps, const float* y, con
                            rows_per, bb);
     CDRL_LAUNCH_CHECK();
     // (the engine's arena holds the bias gradient right behind the filter gradient: one reduce over the 28 * Cout columns of a partial)
-    if (db == dw + 27 * Cout) return reduce_partials_f32(pf, nblk, (int64_t)28 * Cout, (int64_t)28 * Cout, dw, 0, st);
+    if (sp.single_reduce) return reduce_partials_f32(pf, nblk, (int64_t)28 * Cout, (int64_t)28 * Cout, dw, 0, st);
     CDRL_TRY(reduce_partials_f32(pf, nblk, (int64_t)27 * Cout, (int64_t)28 * Cout, dw, 0, st));
     return reduce_partials_f32(pf + 27 * Cout, nblk, Cout, (int64_t)28 * Cout, db, 0, st);
 }
@@ -1153,7 +1241,7 @@ int maxpool_bn_fwd(const float* y, const float* stats, int G, int frames_per_gro
                    int H, int W, int C, hipStream_t st, int at) {
     const int Ho = same_out(H, 2), Wo = same_out(W, 2);
     const int rows = N * Ho * Wo;
-    VColGeom g = vcol_geom(rows, C, 4096);
+    const VColGeom g = stem_pool_fwd_geom(rows, C);
     dim3 grid(g.nb), block(g.cx, g.cy);
     const int pt = same_pad_before(H, 2), pl = same_pad_before(W, 2);
     if (at) {

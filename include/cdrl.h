@@ -775,7 +775,10 @@ int cdrl_bn_train_bwd_pooled(const uint8_t* argmax, const float* dp, int H, int 
  * are taken in scatter form over dp (one gathered y per pooled element), the BN-backward apply and the pool gather run
  * inside the operand load of the filter-gradient GEMM.  x: observations (B,T,H,W,3); y: raw conv output
  * [(t*B+b)][Ho][Wo][Cout]; stats: the BN's 4*T*Cout block; argmax/dp: [T*B][Hp][Wp][Cout].  Outputs dgamma, dbeta, coef
- * (3*T*Cout scratch), dw (3,3,3,Cout), db.  workspace: cdrl_stem_block_bwd_workspace_doubles().  Cout % 4 == 0, <= 32. */
+ * (3*T*Cout scratch), dw (3,3,3,Cout), db.  workspace: cdrl_stem_block_bwd_workspace_doubles().  Cout % 4 == 0, <= 32.
+ * Any number of rows per time slice is handled: a filter-gradient workgroup owns rows_per >= 128 consecutive rows and stages the
+ * statistics of two time slices; where B * Ho * Wo is so small that its rows come from three or more slices (field 31 of cdrl_stem_plan
+ * above 2), the host selects a form of the kernel that reads each row's own slice (field 28). */
 int64_t cdrl_stem_block_bwd_workspace_doubles(int B, int T, int H, int W, int Cout);
 int cdrl_stem_block_bwd(const float* x, const float* y, const float* stats, const uint8_t* argmax, const float* dp, int B, int T,
                         int H, int W, int Cout, float* dgamma, float* dbeta, float* coef, float* dw, float* db,
@@ -787,6 +790,27 @@ int cdrl_stem_block_bwd(const float* x, const float* y, const float* stats, cons
 int cdrl_stem_block_bwd_pooled(const float* x, const float* y, const float* stats, const uint8_t* argmax, const float* dp,
                                const float* pooled, int B, int T, int H, int W, int Cout, float* dgamma, float* dbeta, float* coef,
                                float* dw, float* db, double* workspace, int act_type, void* stream);
+/* cdrl_stem_plan: what the launchers of the stem block dispatch on for this shape (they call the same host function) -- launches nothing,
+ * reads no memory.  pooled: a pooled activated output is given (cdrl_stem_block_bwd_pooled); db_adjacent: db == dw + 27 * Cout;
+ * y_aligned: y is 16-byte aligned.  Writes min(n_out, 36) int32 fields and returns 36 (-1: bad act_type, no field array, B, T or Cout < 1,
+ * H or W < 3):
+ *    0 Ho  1 Wo (conv output)  2 Hp  3 Wp (pooled output)
+ *    4 cdrl_stem_fwd: 1 four channels per thread, 0 the scalar kernel (Cout % 4 != 0 or y unaligned)
+ *    5 cdrl_stem_fwd_stats refusal: 0 runs, 1 Cout (% 4 != 0 or > 64), 3 alignment of y
+ *    6 form: 0 band (a workgroup walks (frame, band of R rows) units staged in LDS), 1 window (image of 2 GB or more, a band of one row
+ *      wider than 6144 floats -- W > 682 --, Cout < 4, or CDRL_STEM_FWD_BAND=0)
+ *    7 R  8 NB bands per frame  9 nbpg workgroups per time slice  10 px 16-byte chunks per thread of a band (2, 4, 6)  11 NP pixels per
+ *      thread and iteration  12 LDS bytes  13 units the busiest workgroup walks  14 rows of the [T][rows][2][Cout] partials
+ *   15 vec  16 cx  17 cy  18 nloop  19 rb  20 nb   of cdrl_maxpool_bn_fwd
+ *   21 BatchNorm sums over the pooled gradient: 1 the four-channel kernel, 0 the generic column reduce   22 1: it reads the pooled
+ *      activated output   23 nb partial rows per time slice
+ *   24 cdrl_stem_bwd_filter: 0 MFMA kernel, 2 column reduce (Cout > 32)
+ *   25 fused filter gradient refusal: 0 runs, 1 Cout (% 4 != 0 or > 32), 2 conv output of 2 GB or more   26 1 fused MFMA kernel, -1 refused
+ *   27 NCH 16-byte channel chunks per lane (3: Cout <= 24, 4; 1 unfused)  28 1: the form that reads each row's own time slice
+ *   29 rows_per workgroup  30 workgroups  31 the most time slices the rows of one workgroup come from  32 1: one reduce over dw and db
+ *   33 workspace doubles the filter gradient writes  34 cdrl_stem_bwd_workspace_doubles  35 doubles of the BatchNorm partials in front */
+int cdrl_stem_plan(int B, int T, int H, int W, int Cout, int act_type, int pooled, int db_adjacent, int y_aligned, int32_t* fields,
+                   int n_out);
 
 /* Rollout-time image augmentation of one observation stack (CARLAgent.augment, core/carla_agent.py:545-577; ops of
  * rl/augmentations/augmentations.py and simclr.color_jitter): color jitter (brightness -> contrast -> saturation -> hue ->
