@@ -154,6 +154,9 @@ PROTOTYPES = {
     'cdrl_beta_sample_gammas': (_i, [_fp, _fp, _i, _i, _i, C.c_uint64, C.c_uint64, _fp, _fp]),
     'cdrl_philox_words': (_i, [C.c_uint64, C.c_uint64, C.c_uint64, _i, _i, _fp, _fp]),
     'cdrl_learner_policy_apply': (_i, [_L, _fp]),
+    'cdrl_learner_joint_forward_backward': (_i, [_L, C.POINTER(PolicyBatch), _fp, _f, _fp]),
+    'cdrl_learner_joint_forward_backward_resample': (_i, [_L, C.POINTER(PolicyBatch), _fp, C.c_uint64, C.c_uint64, _f, _fp]),
+    'cdrl_learner_joint_apply': (_i, [_L, _fp]),
     'cdrl_learner_sequence_begin': (_i, [_L, _fp]),
     'cdrl_learner_sequence_end': (_i, [_L, _fp]),
     'cdrl_learner_value_forward_backward': (_i, [_L, C.POINTER(ValueBatch), _f, _fp]),
@@ -173,6 +176,7 @@ PROTOTYPES = {
     'cdrl_gemm_tn': (_i, [_fp, _i, _i, _fp, _i, _i, _fp, _i, _i, _i, _fp, _i, _fp]),
     'cdrl_bn_small_fwd': (_i, [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_bn_small_bwd': (_i, [_fp, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'cdrl_bn_small_bwd_pair': (_i, [_fp, _fp, _fp, _i, _i] + [_fp] * 10),
     'cdrl_linear_heads_fwd': (_i, [_fp, _i, _fp, _fp, _fp, _fp, _i, _i, _fp]),
     'cdrl_linear_heads_bwd': (_i, [_fp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _fp]),
     'cdrl_stem_fwd': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp]),

@@ -136,7 +136,12 @@ class CARLAgent(PPOAgent):
         the augmented images are those of the per-environment loop, bit for bit.
         `full_state=True` (Agent): save() also writes the full learner state and load() restores it when it is there, so that an
         interrupted run continues bit for bit (save_state / load_state; without the keyword both behave as in the reference:
-        weights and config.json, fresh optimizers)."""
+        weights and config.json, fresh optimizers).
+        `joint_update=True` (PPOAgent; not in the reference): every minibatch step takes the policy loss and the value loss on ONE
+        train-mode trunk forward and back-propagates their sum once (engine.joint_forward_backward / joint_apply) instead of running
+        the trunk twice.  `dynamics_lr` then acts ONCE per minibatch -- the trunk's optimizer takes one step on the summed gradient
+        where the default takes two -- and the trunk's moving statistics update once.  update() runs one minibatch loop of
+        optimization_steps[0] passes over the policy batch pipeline (optimization_steps must be equal, else ValueError)."""
         assert aug_intensity >= 0.0
         network_spec = dict(kwargs.pop('network', {}))
         network_spec.setdefault('network', CARLANetwork)
@@ -398,6 +403,28 @@ class CARLAgent(PPOAgent):
 
     def apply_value_gradients(self, gradients):
         self._step_engine.value_apply()
+        return gradients
+
+    def get_joint_gradients(self, batch):
+        states, advantages, actions, log_probabilities, speed, similarity, returns = batch
+        eng = self._step_engine = self.network.engine_for(advantages.shape[0])
+        b = dict(states={k: states[k] for k in ('state_image', 'state_road', 'state_vehicle', 'state_navigation')},
+                 advantages=advantages, old_log_prob=log_probabilities, speed=speed, similarity=similarity, u=actions, returns=returns)
+        b = eng.stage(b, 'joint')
+        b.update(du_da=None, du_db=None)
+        scale = 1.0 / self.world
+        if self.resample_actions:       # (as get_policy_gradients)
+            self._sample_offset += 1
+            eng.joint_forward_backward_resample(b, seed=self.seed if self.seed is not None else 0,
+                                                offset=self._sample_offset * self.world + self.rank, grad_scale=scale)
+        else:
+            eng.joint_forward_backward(b, grad_scale=scale)
+        if self.data_parallel:
+            self._dp_for(eng).reduce_joint_gradients()
+        return (eng.buffer(2)[0].clone(), eng.buffer(3)[0].clone()), 'joint'
+
+    def apply_joint_gradients(self, gradients):
+        self._step_engine.joint_apply()     # trunk step ONCE (not when frozen) -> old_policy <- policy -> policy head -> value head
         return gradients
 
     # -- rollout helpers ------------------------------------------------------------------------------

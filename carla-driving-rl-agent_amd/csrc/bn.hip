@@ -365,6 +365,106 @@ int bn_small_bwd(View dout, View x, int M, int C, const float* stats, float* dga
     return 0;
 }
 
+// backward of TWO single-group BatchNorms A and B over the same raw input x (the joint update's pi.bn0 and v.bn0, both over the trunk
+// output): dx = dxA + dxB, each term k1 * (dz - k2 - xhat * k3) exactly as bn_small_bwd_kernel forms it (xhat from the raw input and
+// that BatchNorm's own mean / invstd), joined by one float32 addition.  Geometry and reduction order are bn_small_bwd_kernel's, so the
+// dgamma / dbeta / coef of either are bit-identical to a bn_small_bwd call on it alone; x is read once per phase.
+__global__ void __launch_bounds__(256) bn_small_bwd_pair_kernel(View doutA, View doutB, View x, int M, int C,
+                                                                const float* __restrict__ statsA, const float* __restrict__ statsB,
+                                                                float* __restrict__ dgammaA, float* __restrict__ dbetaA,
+                                                                float* __restrict__ coefA, float* __restrict__ dgammaB,
+                                                                float* __restrict__ dbetaB, float* __restrict__ coefB,
+                                                                float* __restrict__ dx) {
+    __shared__ double sm[4][16][16];
+    __shared__ float cf[6][16];
+    const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const int c = blockIdx.x * 16 + cl;
+    const bool ok = c < C;
+    const float* xp = x.p + x.coff + (ok ? c : 0);
+    const float* dpa = doutA.p + doutA.coff + (ok ? c : 0);
+    const float* dpb = doutB.p + doutB.coff + (ok ? c : 0);
+    const float meanA = ok ? statsA[0 * C + c] : 0.0f, invA = ok ? statsA[1 * C + c] : 0.0f;
+    const float meanB = ok ? statsB[0 * C + c] : 0.0f, invB = ok ? statsB[1 * C + c] : 0.0f;
+    double sa = 0.0, qa = 0.0, sb = 0.0, qb = 0.0;
+    for (int r0 = rl; r0 < M; r0 += 16 * 8) {
+        float v[8], da[8], db[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int64_t r = min(r0 + 16 * u, M - 1);
+            v[u] = xp[r * x.ld];
+            da[u] = dpa[r * doutA.ld];
+            db[u] = dpb[r * doutB.ld];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (r0 + 16 * u < M) {
+                const float xha = (v[u] - meanA) * invA, xhb = (v[u] - meanB) * invB;
+                sa += (double)da[u];
+                qa += (double)da[u] * (double)xha;
+                sb += (double)db[u];
+                qb += (double)db[u] * (double)xhb;
+            }
+    }
+    sm[0][rl][cl] = sa;
+    sm[1][rl][cl] = qa;
+    sm[2][rl][cl] = sb;
+    sm[3][rl][cl] = qb;
+    __syncthreads();
+    if (rl < 2 && ok) {         // row lane 0 folds A, row lane 1 folds B, each in bn_small_bwd_kernel's order
+        const double* s0 = &sm[2 * rl][0][cl];
+        const double* s1 = &sm[2 * rl + 1][0][cl];
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int y = 0; y < 16; ++y) {
+            a += s0[y * 16];
+            b += s1[y * 16];
+        }
+        const double n = (double)M;
+        const float* stats = rl ? statsB : statsA;
+        float* dgamma = rl ? dgammaB : dgammaA;
+        float* dbeta = rl ? dbetaB : dbetaA;
+        float* coef = rl ? coefB : coefA;
+        const float k1 = stats[2 * C + c], k2 = (float)(a / n), k3 = (float)(b / n);
+        dbeta[c] = (float)a;
+        dgamma[c] = (float)b;
+        coef[0 * C + c] = k1;
+        coef[1 * C + c] = k2;
+        coef[2 * C + c] = k3;
+        cf[3 * rl + 0][cl] = k1;
+        cf[3 * rl + 1][cl] = k2;
+        cf[3 * rl + 2][cl] = k3;
+    }
+    __syncthreads();
+    if (!ok) return;
+    const float k1a = cf[0][cl], k2a = cf[1][cl], k3a = cf[2][cl];
+    const float k1b = cf[3][cl], k2b = cf[4][cl], k3b = cf[5][cl];
+    for (int r0 = rl; r0 < M; r0 += 16 * 8) {
+        float v[8], da[8], db[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int64_t r = min(r0 + 16 * u, M - 1);
+            v[u] = xp[r * x.ld];
+            da[u] = dpa[r * doutA.ld];
+            db[u] = dpb[r * doutB.ld];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (r0 + 16 * u < M) {
+                const float xha = (v[u] - meanA) * invA, xhb = (v[u] - meanB) * invB;
+                const float ta = k1a * (da[u] - k2a - xha * k3a), tb = k1b * (db[u] - k2b - xhb * k3b);
+                dx[(int64_t)(r0 + 16 * u) * C + c] = ta + tb;
+            }
+    }
+}
+
+int bn_small_bwd_pair(View doutA, View doutB, View x, int M, int C, const float* statsA, const float* statsB, float* dgammaA,
+                      float* dbetaA, float* coefA, float* dgammaB, float* dbetaB, float* coefB, float* dx, hipStream_t st) {
+    hipLaunchKernelGGL(bn_small_bwd_pair_kernel, dim3(cdiv(C, 16)), dim3(256), 0, st, doutA, doutB, x, M, C, statsA, statsB, dgammaA,
+                       dbetaA, coefA, dgammaB, dbetaB, coefB, dx);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // forward apply
 // ------------------------------------------------------------------------------------------

@@ -542,6 +542,37 @@ int cdrl_learner_value_apply(cdrl_learner* l, void* stream) {
     return l->impl->value_apply(S(stream));
 }
 
+int cdrl_learner_joint_forward_backward(cdrl_learner* l, const cdrl_policy_batch* b, const float* returns, float grad_scale,
+                                       void* stream) {
+    CHECK_L(l);
+    if (!b) return -1;
+    PolicyBatch pb{b->image, b->road, b->vehicle, b->navigation, b->advantages, b->old_log_prob,
+                   b->speed, b->similarity, b->u, b->du_dalpha, b->du_dbeta};
+    if (!pb.adv || !pb.old_logp || !pb.speed || !pb.similarity || !pb.u || !returns) {
+        cdrl::set_error("joint batch: null tensor");
+        return -1;
+    }
+    return l->impl->joint_forward_backward(pb, returns, grad_scale, S(stream));
+}
+
+int cdrl_learner_joint_forward_backward_resample(cdrl_learner* l, const cdrl_policy_batch* b, const float* returns, uint64_t seed,
+                                                uint64_t offset, float grad_scale, void* stream) {
+    CHECK_L(l);
+    if (!b) return -1;
+    PolicyBatch pb{b->image, b->road, b->vehicle, b->navigation, b->advantages, b->old_log_prob,
+                   b->speed, b->similarity, nullptr, nullptr, nullptr};
+    if (!pb.adv || !pb.old_logp || !pb.speed || !pb.similarity || !returns) {
+        cdrl::set_error("joint batch: null tensor");
+        return -1;
+    }
+    return l->impl->joint_forward_backward_resample(pb, returns, seed, offset, grad_scale, S(stream));
+}
+
+int cdrl_learner_joint_apply(cdrl_learner* l, void* stream) {
+    CHECK_L(l);
+    return l->impl->joint_apply(S(stream));
+}
+
 int cdrl_learner_update_old_policy(cdrl_learner* l, void* stream) {
     CHECK_L(l);
     return l->impl->update_old_policy(S(stream));
@@ -1417,6 +1448,22 @@ int cdrl_bn_small_bwd(const float* dout, const float* y, int M, int C, const flo
                       float* coef, float* dx, void* stream) {
     return bn_small_bwd(make_view(const_cast<float*>(dout), C), make_view(const_cast<float*>(y), C), M, C, stats, dgamma, dbeta,
                         coef, dx, S(stream));
+}
+
+int cdrl_bn_small_bwd_pair(const float* doutA, const float* doutB, const float* y, int M, int C, const float* statsA,
+                           const float* statsB, float* dgammaA, float* dbetaA, float* coefA, float* dgammaB, float* dbetaB,
+                           float* coefB, float* dx, void* stream) {
+    if (!doutA || !doutB || !y || !statsA || !statsB || !dgammaA || !dbetaA || !coefA || !dgammaB || !dbetaB || !coefB || !dx) {
+        set_error("cdrl_bn_small_bwd_pair: null argument");
+        return -1;
+    }
+    if (M < 1 || C < 1) {
+        set_error("cdrl_bn_small_bwd_pair: M = %d, C = %d", M, C);
+        return -1;
+    }
+    return bn_small_bwd_pair(make_view(const_cast<float*>(doutA), C), make_view(const_cast<float*>(doutB), C),
+                             make_view(const_cast<float*>(y), C), M, C, statsA, statsB, dgammaA, dbetaA, coefA, dgammaB, dbetaB, coefB,
+                             dx, S(stream));
 }
 
 static int make_head_set(HeadSet& hs, int nheads, const int* n, const float* const* w, const float* const* b, float* const* dw,

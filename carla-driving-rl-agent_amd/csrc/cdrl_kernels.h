@@ -34,6 +34,10 @@ int bn_small_fwd(View x, int M, int C, const float* gamma, const float* beta, fl
                  View out, hipStream_t st);
 int bn_small_bwd(View dout, View x, int M, int C, const float* stats, float* dgamma, float* dbeta, float* coef, float* dx,
                  hipStream_t st);
+// backward of two such BatchNorms A and B over the SAME input x in one launch: per-BatchNorm outputs bit-identical to bn_small_bwd on
+// each alone, dx = dxA + dxB (one float32 addition per element)
+int bn_small_bwd_pair(View doutA, View doutB, View x, int M, int C, const float* statsA, const float* statsB, float* dgammaA,
+                      float* dbetaA, float* coefA, float* dgammaB, float* dbetaB, float* coefB, float* dx, hipStream_t st);
 // Gradient source "through a 3x3/s2 SAME max-pool": d(a)[n,iy,ix,c] = sum of dp over the windows whose
 // saved argmax points at (iy,ix).  Lets the stem BatchNorm backward read the pooled gradient directly
 // (the 255 MB pre-pool gradient tensor is never written or re-read).

@@ -124,6 +124,19 @@ public:
     int sequence_end(hipStream_t caller);
     int value_forward_backward(const ValueBatch& b, float inv_world, hipStream_t st);
     int value_apply(hipStream_t st);
+    // Joint policy + value update (opt-in): ONE train-mode trunk forward (moving statistics updated once), both heads'
+    // forwards, policy loss + policy head backward and value loss + value head backward each without the head's bn0, then one launch
+    // (bn_small_bwd_pair) that finishes both bn0 and leaves d(policy loss + value loss)/d(dynamics) in the trunk output gradient, then
+    // ONE trunk backward.  The value loss takes the policy batch's speed / similarity.  Frozen trunk: no trunk backward.
+    // Both refuse (-1) a learner whose heads' bn0 is not in the single-launch form (B > 2048): there is no joint form above it.
+    int joint_forward_backward(const PolicyBatch& b, const float* returns, float inv_world, hipStream_t st);
+    int joint_forward_backward_resample(const PolicyBatch& b, const float* returns, uint64_t seed, uint64_t offset, float inv_world,
+                                        hipStream_t st);
+    // The apply of a joint pass: the trunk steps ONCE (its counter advances once), then the policy head (old_policy <- policy in
+    // front), then the value head.  Gated: trunk + policy head are decided together from the trunk's and the policy's list, the value
+    // head from its own list; CDRL_CLIP_GLOBAL clips each of the three lists once, by its own threshold.  Train stats: the policy
+    // row, then the value row, both with the norms of the one joint trunk gradient.
+    int joint_apply(hipStream_t st);
     int update_old_policy(hipStream_t st);
     // inference: trunk (moving stats) + old_policy + value heads
     int predict(const float* image, const float* road, const float* vehicle, const float* navigation,
@@ -323,7 +336,8 @@ private:
     // conv `conv`, whose own parameters are registered first (the parameter tables keep layer order wherever the blocks are created)
     BnRec make_bn(int model, const std::string& prefix, View x, int G, int Mg, int C, int act);
     BnRec pw_bn(const std::string& conv, int Cin, int Cout, const std::string& bn, float* y, int Mg, int act);
-    void add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o);
+    // (returns whether the op took the single-launch form: bn_small_fwd / bn_small_bwd)
+    bool add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o);
     // dense BatchNorm between two tensors (feature nets, trunk tail, control branches): no Bessel correction, no activation
     void add_dense_bn(std::vector<Op>& ops, int model, const std::string& prefix, const Tens& in, const Tens& out, int G);
     // emits what the plan says (bn_in: the record behind ConvPlan::bn_in, or none); the backward is one of three programs, chosen at build time
@@ -375,10 +389,14 @@ private:
     int update_old_policy_impl(hipStream_t st);
     int policy_apply_impl(hipStream_t st);
     int value_apply_impl(hipStream_t st);
+    int joint_apply_impl(hipStream_t st);
+    int joint_refused();
+    // forward of the trunk and both heads (sample != null: policy_dist + Beta draw behind the policy head), losses, backward
+    int joint_impl(const PolicyBatch& b, const float* returns, const uint64_t* sample, float inv_world, hipStream_t st);
     int predict_impl(const float* image, const float* road, const float* vehicle, const float* navigation, float* dist_out,
                      float* value_out, float* dyn_out, hipStream_t st);
     int run_fwd(std::vector<Op>& ops, hipStream_t st, int training);
-    int run_bwd(std::vector<Op>& ops, hipStream_t st);
+    int run_bwd(std::vector<Op>& ops, hipStream_t st, size_t first = 0);      // ops [first, size) in reverse order
     int set_inputs(const float* image, const float* road, const float* vehicle, const float* navigation);
 
     Config cfg_;
@@ -488,6 +506,14 @@ private:
     const float* in_navigation_ = nullptr;
 
     Tens dyn_, feat_, lin_p_, lin_v_, lin_old_;
+    // The first BatchNorm of the policy ([0]) and value ([1]) head, both over dyn_: the joint pass runs the rest of a head's backward
+    // (ops behind `op`) and then both of these in one launch
+    struct HeadBn0 {
+        BnRec bn;
+        View dout{nullptr, 0, 0};
+        size_t op = 0;              // index of its op in the head's list
+        bool small = false;         // single-launch form
+    } bn0_[2];
     float *metrics_p_ = nullptr, *metrics_v_ = nullptr, *aux_p_ = nullptr, *aux_v_ = nullptr;
     float *sample_u_ = nullptr, *sample_da_ = nullptr, *sample_db_ = nullptr;
     DevHP hp_host_;
@@ -495,7 +521,9 @@ private:
     DevHP* hp_stage_ = nullptr;     // pinned host staging (DevHP, and one float behind it for the gate block's threshold)
     GateBlock gate_host_;           // only clip_norm_dynamics is the host's
     GateBlock* gate_dev_ = nullptr; // in the workspace of a learner with gate_on() (this learner's, or the hyper-parameter owner's)
-    int gated_apply(int head, hipStream_t st);
+    // with_trunk = false (the value head of a joint apply, whose trunk step the policy head's gated apply took): the head alone --
+    // no trunk norm in the decision, no trunk update, no trunk tick
+    int gated_apply(int head, hipStream_t st, bool with_trunk = true);
     // the trunk has a chunk table: its norms are wanted by the train stats or by the gate
     bool trunk_table() const { return !frozen() && (cfg_.train_stats > 0 || gate_on()); }
     // optimiser tables (device, inside workspace)

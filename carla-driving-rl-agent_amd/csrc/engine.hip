@@ -598,7 +598,7 @@ void Learner::add_dense_bn(std::vector<Op>& ops, int model, const std::string& p
     add_bn(ops, make_bn(model, prefix, in.v(), G, in.rows / G, in.C, ACT_NONE), o);
 }
 
-void Learner::add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o) {
+bool Learner::add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o) {
     const int G = bn.G, Mg = bn.Mg, C = bn.C, nb = bn.nb, act = bn.act, at = bn.at, stats_nb = o.conv.stats_nb, bes = o.bessel ? 1 : 0;
     const View x = bn.x;
     const Passthrough pass = o.pass;
@@ -624,7 +624,7 @@ void Learner::add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o) {
         };
         op.bwd = [=](hipStream_t st) -> int { return bn_small_bwd(o.dout, x, Mg, C, bn.stats, bn.gamma.g, bn.beta.g, bn.coef, o.dx, st); };
         ops.push_back(op);
-        return;
+        return true;
     }
     op.fwd = [=](hipStream_t st, int training) -> int {
         if (training && !stats_nb) CDRL_TRY(colstats(x, G, Mg, C, sc->part, st, at));
@@ -648,6 +648,7 @@ void Learner::add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o) {
         return bn_bwd_apply(dsrc, dsh, x, G, Mg, C, bn.stats, bn.coef, act, dys_[slot_], part2s_[slot_], st, nullptr, bc, at);
     };
     ops.push_back(op);
+    return false;
 }
 
 // One plan per 1x1 conv of the tower: forward kernel, backward form, backward-data GEMM and the partial-row counts its neighbours read.
@@ -1507,7 +1508,23 @@ void Learner::build_head(std::vector<Op>& ops, int model, const std::string& pre
     const Config& c = cfg_;
     const int B = c.B;
     Tens n0 = tens(B, c.dyn), a0 = tens(B, c.head), n1 = tens(B, c.head), a1 = tens(B, c.head);
-    add_dense_bn(ops, model, prefix + ".bn0", dyn_, n0, 1);
+    {   // bn0 as add_dense_bn emits it; the policy and value heads keep its record for the joint pass
+        BnOp o;
+        o.bessel = false;
+        o.out = n0.v();
+        o.dout = n0.gv();
+        o.dx = dyn_.g;
+        const BnRec bn = make_bn(model, prefix + ".bn0", dyn_.v(), 1, dyn_.rows, dyn_.C, ACT_NONE);
+        const size_t at_op = ops.size();
+        const bool small = add_bn(ops, bn, o);
+        if (model == M_POLICY || model == M_VALUE) {
+            HeadBn0& h = bn0_[model == M_POLICY ? 0 : 1];
+            h.bn = bn;
+            h.dout = o.dout;
+            h.op = at_op;
+            h.small = small;
+        }
+    }
     add_dense(ops, model, prefix + ".fc0", n0.v(), B, c.dyn, c.head, ACT_SWISH6, a0.v(), a0.gv(), n0.gv(), 0, true, "glorot");
     add_dense_bn(ops, model, prefix + ".bn1", a0, n1, 1);
     add_dense(ops, model, prefix + ".fc1", n1.v(), B, c.head, c.head, ACT_SWISH6, a1.v(), a1.gv(), n1.gv(), 0, true, "glorot");
@@ -1886,8 +1903,8 @@ int Learner::run_fwd(std::vector<Op>& ops, hipStream_t st, int training) {
     return 0;
 }
 
-int Learner::run_bwd(std::vector<Op>& ops, hipStream_t st) {
-    for (size_t i = ops.size(); i-- > 0;) CDRL_TRY(ops[i].bwd(st));
+int Learner::run_bwd(std::vector<Op>& ops, hipStream_t st, size_t first) {
+    for (size_t i = ops.size(); i-- > first;) CDRL_TRY(ops[i].bwd(st));
     return 0;
 }
 
@@ -2027,6 +2044,108 @@ int Learner::value_forward_backward_impl(const ValueBatch& b, float inv_world, h
     return join_side(st);
 }
 
+// ------------------------------------------------------------------------------------------
+// Joint policy + value update: one trunk forward and one trunk backward per minibatch
+// ------------------------------------------------------------------------------------------
+int Learner::joint_refused() {
+    if (bn0_[0].small && bn0_[1].small && bn0_[0].op == 0 && bn0_[1].op == 0) return 0;
+    set_error("joint update: the heads' first BatchNorm is not in the single-launch form (B = %d > 2048 rows); use the separate passes",
+              cfg_.B);
+    return -1;
+}
+
+int Learner::joint_impl(const PolicyBatch& b, const float* returns, const uint64_t* sample, float inv_world, hipStream_t st) {
+    CDRL_TRY(set_inputs(b.image, b.road, b.vehicle, b.navigation));
+    CDRL_TRY(run_trunk_fwd(st, 1));
+    CDRL_TRY(run_fwd(policy_ops_, st, 1));
+    PolicyLossArgs a;
+    a.u = b.u;
+    a.du_da = b.du_da;
+    a.du_db = b.du_db;
+    if (sample) {       // as policy_forward_backward_resample: u ~ Beta(alpha, beta) of the new policy, with its pathwise Jacobians
+        const int A = cfg_.A;
+        CDRL_TRY(policy_dist(lin_p_.p, aux_p_, cfg_.B, A, st));
+        CDRL_TRY(beta_sample(aux_p_, aux_p_ + A, cfg_.B, A, 4 * A, sample[0], sample[1], sample_u_, sample_da_, sample_db_, st));
+        a.u = sample_u_;
+        a.du_da = sample_da_;
+        a.du_db = sample_db_;
+    }
+    CDRL_TRY(run_fwd(value_ops_, st, 1));
+    a.lin = lin_p_.p;
+    a.adv = b.adv;
+    a.old_logp = b.old_logp;
+    a.speed = b.speed;
+    a.similarity = b.similarity;
+    a.hp = reinterpret_cast<const float*>(hp_dev_);
+    a.dlin = lin_p_.g;
+    a.metrics = metrics_p_;
+    a.aux = aux_p_;
+    a.B = cfg_.B;
+    a.A = cfg_.A;
+    a.inv_world = inv_world;
+    CDRL_TRY(policy_loss(a, st));
+    CDRL_TRY(run_bwd(policy_ops_, st, bn0_[0].op + 1));
+    ValueLossArgs v;
+    v.lin = lin_v_.p;
+    v.returns = returns;
+    v.speed = b.speed;
+    v.similarity = b.similarity;
+    v.dlin = lin_v_.g;
+    v.metrics = metrics_v_;
+    v.values = aux_v_;
+    v.B = cfg_.B;
+    v.exp_scale = cfg_.exp_scale;
+    v.inv_world = inv_world;
+    CDRL_TRY(value_loss(v, st));
+    CDRL_TRY(run_bwd(value_ops_, st, bn0_[1].op + 1));
+    // both bn0 over the trunk output: their own gradients, and dyn_.g = d(policy loss)/d(dynamics) + d(value loss)/d(dynamics)
+    const HeadBn0 &p0 = bn0_[0], &v0 = bn0_[1];
+    CDRL_TRY(bn_small_bwd_pair(p0.dout, v0.dout, p0.bn.x, p0.bn.Mg, p0.bn.C, p0.bn.stats, v0.bn.stats, p0.bn.gamma.g, p0.bn.beta.g,
+                               p0.bn.coef, v0.bn.gamma.g, v0.bn.beta.g, v0.bn.coef, dyn_.g, st));
+    if (frozen()) return join_side(st);        // (see policy_backward_impl; the summed dyn_.g has no consumer)
+    if (!packs_have_wt_) CDRL_TRY(transpose_many(d_pwt_, (int)h_pwt_.size(), pwt_tiles_, st));
+    CDRL_TRY(run_bwd(trunk_ops_, st));
+    return join_side(st);
+}
+
+int Learner::joint_forward_backward(const PolicyBatch& b, const float* returns, float inv_world, hipStream_t caller) {
+    CDRL_TRY(joint_refused());
+    if (inv_world != 1.0f) dp_hint_ = true;
+    std::vector<uint64_t> key = {6, K(b.image), K(b.road), K(b.vehicle), K(b.navigation), K(b.adv), K(b.old_logp), K(b.speed),
+                                 K(b.similarity), K(b.u), K(b.du_da), K(b.du_db), K(returns), Kf(inv_world)};
+    return launch(caller, key, true, [&](hipStream_t st) -> int { return joint_impl(b, returns, nullptr, inv_world, st); });
+}
+
+int Learner::joint_forward_backward_resample(const PolicyBatch& b, const float* returns, uint64_t seed, uint64_t offset, float inv_world,
+                                             hipStream_t caller) {
+    CDRL_TRY(joint_refused());
+    if (inv_world != 1.0f) dp_hint_ = true;
+    const uint64_t sample[2] = {seed, offset};      // kernel arguments that change every call -> eager, not graph-replayed
+    return launch(caller, {}, false, [&](hipStream_t st) -> int { return joint_impl(b, returns, sample, inv_world, st); });
+}
+
+int Learner::joint_apply(hipStream_t caller) {
+    return launch(caller, {7}, true, [&](hipStream_t st) -> int { return joint_apply_impl(st); });
+}
+
+int Learner::joint_apply_impl(hipStream_t st) {
+    // gated: trunk + policy head decided together (trunk list, policy list), then the value head from its own list, without the trunk
+    if (gate_on()) {
+        CDRL_TRY(gated_apply(0, st));
+        return gated_apply(1, st, false);
+    }
+    // policy_apply_impl, then value_apply_impl without its trunk step and trunk tick: the trunk's optimizer steps once per joint step
+    CDRL_TRY(policy_apply_impl(st));
+    const int64_t vo = tr_offset(M_VALUE);
+    const int opt = cfg_.optimizer, nadam = opt == CDRL_OPT_NADAM ? 8 : 0;
+    SegTable& s = seg_[M_VALUE];
+    CDRL_TRY(tensor_sqnorms(buf_.grads + vo, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part, s.sqnorms, st,
+                            hp_dev_, 2 | nadam, true));
+    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + vo, buf_.grads + vo, buf_.adam_m + vo, buf_.adam_v + vo, tr_size_[M_VALUE],
+                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 1, st, s.chunk_part, 1));
+    return cfg_.train_stats > 0 ? stats_row(1, st) : 0;
+}
+
 int Learner::update_old_policy(hipStream_t caller) {
     return launch(caller, {}, false, [&](hipStream_t st) -> int { return update_old_policy_impl(st); });
 }
@@ -2045,19 +2164,19 @@ int Learner::policy_apply(hipStream_t caller) {
 // The apply step of a learner with the gradient gate: chunk norms of the lists the step consumes -> gate (scales,
 // skip flag, counter ticks) -> trunk update -> old_policy copy (policy) -> head update, the last three in their gated forms, which
 // return at once when the gate said skip.  Both updates run behind the tick.  No host read: the sequence is capturable.
-int Learner::gated_apply(int head, hipStream_t st) {
+int Learner::gated_apply(int head, hipStream_t st, bool with_trunk) {
     const int hm = head == 0 ? M_POLICY : M_VALUE;
     const int64_t to = tr_offset(M_TRUNK), ho = tr_offset(hm);
     const int opt = cfg_.optimizer;
     const int flags = (cfg_.clip_mode == CDRL_CLIP_GLOBAL ? GATE_GLOBAL : 0) | (cfg_.skip_nonfinite ? GATE_GUARD : 0) |
-                      (frozen() ? 0 : GATE_TRUNK) | (opt == CDRL_OPT_NADAM ? GATE_NADAM : 0) |
+                      (frozen() || !with_trunk ? 0 : GATE_TRUNK) | (opt == CDRL_OPT_NADAM ? GATE_NADAM : 0) |
                       (cfg_.train_stats > 0 ? GATE_HEAD_PARTS : 0);
     const int mode = cfg_.clip_mode == CDRL_CLIP_GLOBAL ? GATE_MODE_GLOBAL : GATE_MODE_TENSOR;
     SegTable &s = seg_[hm], &t = seg_[M_TRUNK];
     CDRL_TRY(gate_chunk_sqnorms(buf_.grads + ho, s.segs, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part, buf_.grads + to, t.segs,
                                 t.chunk_tensor, t.chunk_off, t.nchunks, t.chunk_part, hp_dev_, gate_dev_, head, flags, st));
     CDRL_TRY(gate_decide(s.chunk_part, s.nchunks, t.chunk_part, t.nchunks, hp_dev_, gate_dev_, head, flags, st));
-    if (!frozen())
+    if (!frozen() && with_trunk)
         CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK],
                              nullptr, nullptr, 0, nullptr, nullptr, hp_dev_, 2, st, nullptr, 1, gate_dev_, mode));
     if (head == 0)

@@ -501,6 +501,40 @@ class LearnerEngine:
     def value_apply(self):
         _lib.check(self.lib.cdrl_learner_value_apply(self.h, self._stream()), 'value_apply')
 
+    # Joint policy + value update (opt-in, include/cdrl.h): one trunk forward and one trunk backward per minibatch.  `batch` is the
+    # policy batch dict plus 'returns' (B, 2); the value loss takes the batch's speed / similarity.
+    def _joint_batch(self, batch):
+        c = self.cfg
+        self._chk(batch['returns'], (c.B, 2), 'returns')
+        for k in ('speed', 'similarity'):
+            if batch[k].numel() != c.B:
+                raise ValueError(f'{k}: expected {c.B} elements')
+        return self._policy_batch(batch)
+
+    def joint_forward_backward(self, batch, grad_scale=1.0):
+        """Stored-action / injected-Jacobian policy loss + value loss on ONE train-mode trunk forward, one trunk backward."""
+        pb = self._joint_batch(batch)
+        _lib.check(self.lib.cdrl_learner_joint_forward_backward(self.h, C.byref(pb), _lib.ptr(batch['returns']), float(grad_scale),
+                                                                self._stream()), 'joint_forward_backward')
+
+    def joint_forward_backward_resample(self, batch, seed: int, offset: int, grad_scale=1.0):
+        """The joint pass with the Beta re-sampling done on the device (as policy_forward_backward_resample)."""
+        b = dict(batch)
+        b.setdefault('u', batch['old_log_prob'])       # placeholder; ignored by the entry point
+        pb = self._joint_batch(b)
+        _lib.check(self.lib.cdrl_learner_joint_forward_backward_resample(self.h, C.byref(pb), _lib.ptr(batch['returns']), int(seed),
+                                                                         int(offset), float(grad_scale), self._stream()),
+                   'joint_forward_backward_resample')
+
+    def joint_apply(self):
+        """Trunk step ONCE, then the policy head (old_policy <- policy in front), then the value head."""
+        _lib.check(self.lib.cdrl_learner_joint_apply(self.h, self._stream()), 'joint_apply')
+
+    def joint_step(self, batch):
+        with self.sequence():
+            self.joint_forward_backward(batch)
+            self.joint_apply()
+
     def sequence(self):
         """Context manager around a run of learner calls on the current stream with nothing of the caller's own between them (one
         minibatch on one GPU: policy pass, apply, value pass, apply): the hand-overs between the caller's stream and the engine's

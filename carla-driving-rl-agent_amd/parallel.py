@@ -60,6 +60,10 @@ class DataParallelLearner:
         self._tower = (t_off, t_off + tower_n)
         self._policy_early = [(0, p_n), (t_off + tower_n, t_off + t_n)]
         self._value_early = [(t_off + tower_n, t_off + t_n + v_n)]
+        # joint step (one pass writes all three lists): with the tower slice the early group covers the arena exactly once; without a
+        # communication stream the whole arena goes out as one slice -- frozen trunk: the two head slices, nothing of the trunk's
+        self._joint_early = [(0, p_n), (t_off + tower_n, t_off + t_n + v_n)]
+        self._joint_slices = [(0, p_n), (t_off + t_n, t_off + t_n + v_n)] if self.frozen else [(0, p_n + t_n + v_n)]
         self._comm = None
         if not self.frozen and self.use_comm_stream(overlap, self.world, self.force, tower_n, t_n,
                                 bool(getattr(engine, 'device', None)) and hasattr(engine, 'set_comm_stream') and engine.grads.is_cuda):
@@ -89,6 +93,10 @@ class DataParallelLearner:
     def reduce_value_gradients(self):
         self._reduce_gradients(self._value_early, self._value_slice)
 
+    def reduce_joint_gradients(self):
+        """All-reduce of a joint pass's gradients (all three lists); call after joint_forward_backward has been enqueued."""
+        self._reduce_gradients(self._joint_early, self._joint_slices)
+
     def _reduce_gradients(self, early, full, with_stats=False):
         """Gradient all-reduce of one pass, issued after the pass has been ENQUEUED: early buckets on the communication
         stream (released by the engine in the middle of the backward), the tower slice on the current stream.
@@ -99,6 +107,10 @@ class DataParallelLearner:
             return False
         g = self.engine.grads
         if self._comm is None:
+            if isinstance(full, list):      # several slices (joint step on a frozen trunk): one coalesced group
+                for w in self._all_reduce_many(g, full, dist.ReduceOp.SUM):
+                    w.wait()
+                return False
             dist.all_reduce(g[full[0]:full[1]], op=dist.ReduceOp.SUM, group=self.group)
             return False
         works = []
@@ -173,6 +185,30 @@ class DataParallelLearner:
         done = self._reduce_gradients(self._value_early, self._value_slice, with_stats=with_stats)
         e.value_apply()
         return done
+
+    def joint_step(self, batch, resample=None, with_stats=True):
+        """One joint policy + value minibatch step (engine.joint_forward_backward: one trunk forward and backward, one trunk optimizer
+        step): the pass with grad_scale = 1 / world, ONE gradient reduce over all three lists, joint_apply.  `batch`: the policy batch
+        plus 'returns'; resample as in policy_step.  The moving statistics ride in the early group (with_stats) or are averaged by
+        sync_moving_statistics() behind the step."""
+        e = self.engine
+        if self.world == 1 and not self.force:
+            with e.sequence():      # no collective between the two calls
+                self._joint_pass(batch, resample)
+                e.joint_apply()
+            return
+        self._joint_pass(batch, resample)
+        done = self._reduce_gradients(self._joint_early, self._joint_slices, with_stats=with_stats)
+        e.joint_apply()
+        if with_stats and not done:
+            self.sync_moving_statistics()
+
+    def _joint_pass(self, batch, resample):
+        e = self.engine
+        if resample is not None:
+            e.joint_forward_backward_resample(batch, seed=resample[0], offset=resample[1], grad_scale=1.0 / self.world)
+        else:
+            e.joint_forward_backward(batch, grad_scale=1.0 / self.world)
 
     def sync_moving_statistics(self):
         """Average of the BatchNorm moving statistics over the ranks: both state slices in ONE collective.  RCCL: a coalesced AVG

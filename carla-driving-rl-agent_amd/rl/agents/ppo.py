@@ -23,7 +23,7 @@ class PPOAgent(Agent):
                  optimization_steps=(1, 1), name='ppo-agent', optimizer='adam', clip_norm=(1.0, 1.0), clip_ratio=0.2,
                  seed_regularization=False, entropy_regularization=0.0, network: dict = None, update_frequency=1,
                  polyak=1.0, repeat_action=1, advantage_scale=2.0, train_stats_rows=256, clip_mode='tensor', skip_nonfinite=False,
-                 **kwargs):
+                 joint_update=False, **kwargs):
         """clip_mode: 'tensor' (default; utils.clip_gradients of the reference: tf.clip_by_norm per tensor of each head) or 'global'
         (tf.clip_by_global_norm of each optimizer's gradient list, the max_grad_norm of other PPO implementations; thresholds are
         those of clip_norm).  skip_nonfinite=True: a minibatch step whose gradients hold a NaN or an Inf leaves parameters and
@@ -32,8 +32,14 @@ class PPOAgent(Agent):
         also logs the last gradients_global_norm_{policy,value,dynamics}.
         train_stats_rows: capacity, in minibatch steps, of the device ring the learner engines append their per-step diagnostics
         to when the agent logs (log_mode is not None); update() reads it once.  An update() with more policy + value steps than
-        that keeps the newest rows and reports how many it lost."""
+        that keeps the newest rows and reports how many it lost.
+        joint_update=True: update() runs ONE minibatch loop whose steps take the policy and the value loss together (agents that
+        implement get_joint_gradients / apply_joint_gradients: CARLAgent); needs optimization_steps[0] == optimization_steps[1]."""
         assert 0.0 < polyak <= 1.0
+        self.joint_update = bool(joint_update)
+        if self.joint_update and optimization_steps[0] != optimization_steps[1]:
+            raise ValueError(f'joint_update=True runs one minibatch loop for both losses: optimization_steps must be equal, got '
+                             f'{tuple(optimization_steps)}')
         assert repeat_action >= 1
         # utils.get_optimizer_by_name (reference rl/utils.py:29-46): one Keras optimizer class, by name, for the policy and value
         # optimizers (and CARLAgent's dynamics optimizer); it and polyak reach the learner engines through the network
@@ -126,6 +132,8 @@ class PPOAgent(Agent):
         t0 = time.time()
         self.seed_regularization()
         self.network.set_hparams(**self.hyper_parameters())
+        if self.joint_update:
+            return self._update_joint(t0)
         value_batches = list(self.get_value_batches())
         policy_batches = list(self.get_policy_batches())
         policy_batches, value_batches = self.agree_on_batches(policy_batches, value_batches)
@@ -141,6 +149,24 @@ class PPOAgent(Agent):
                 value_loss, grads = self.get_value_gradients(batch)
                 self.update_value(grads)
                 self.log(loss_value=value_loss, lr_value=self.value_lr.value)
+        self.after_update()
+        self.log_train_stats()
+        self.log_gate_stats()
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        print(f'Update took {round(time.time() - t0, 3)}s')
+
+    def _update_joint(self, t0):
+        """update() with joint_update=True: one loop of optimization_steps['policy'] passes over the policy batch pipeline (the
+        policy's shuffle settings, one generator draw), every minibatch carrying the returns as well; each step is one joint pass
+        (one trunk forward and backward for both losses) and one joint apply (one trunk optimizer step)."""
+        batches, _ = self.agree_on_batches(list(self.get_joint_batches()), [])
+        for _ in range(self.optimization_steps['policy']):
+            for batch in batches:
+                self.seed_regularization()
+                (total_loss, value_loss), grads = self.get_joint_gradients(batch)
+                self.apply_joint_gradients(grads)
+                self.log(loss_total=total_loss, loss_value=value_loss, lr_policy=self.policy_lr.value, lr_value=self.value_lr.value)
         self.after_update()
         self.log_train_stats()
         self.log_gate_stats()
@@ -206,6 +232,12 @@ class PPOAgent(Agent):
     def apply_value_gradients(self, gradients):
         raise NotImplementedError
 
+    def get_joint_gradients(self, batch):
+        raise NotImplementedError
+
+    def apply_joint_gradients(self, gradients):
+        raise NotImplementedError
+
     def value_batch_tensors(self):
         return self.memory.states, self.memory.returns
 
@@ -222,6 +254,12 @@ class PPOAgent(Agent):
 
     def get_policy_batches(self):
         return self._batches(self.policy_batch_tensors(), self.shuffle, self.shuffle_batches)
+
+    def joint_batch_tensors(self):
+        return tuple(self.policy_batch_tensors()) + (self.memory.returns,)
+
+    def get_joint_batches(self):
+        return self._batches(self.joint_batch_tensors(), self.shuffle, self.shuffle_batches)
 
     # -- learning loop ------------------------------------------------------------------------------
     @staticmethod

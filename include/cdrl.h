@@ -326,6 +326,47 @@ int cdrl_learner_policy_apply(cdrl_learner* l, void* stream);
  * rl/agents/ppo.py:264-275). */
 int cdrl_learner_value_forward_backward(cdrl_learner* l, const cdrl_value_batch* b, float grad_scale, void* stream);
 int cdrl_learner_value_apply(cdrl_learner* l, void* stream);
+/* ---- joint policy + value update (opt-in; no reference counterpart) ---------------------------
+ * The reference (and the four calls above) runs the whole trunk twice per minibatch: a train-mode forward and a full backward for
+ * the policy loss, and again for the value loss, with a trunk optimizer step behind each.  The joint step sums the two losses on ONE
+ * shared-trunk forward and back-propagates once.  What differs from the reference:
+ *   - ONE trunk optimizer step per minibatch with dynamics_lr, where the reference takes two (t_dynamics advances once);
+ *   - the trunk's BatchNorm moving statistics are updated once per minibatch, not twice;
+ *   - the loss is policy total loss + value total loss, each exactly as policy_forward_backward / value_forward_backward form it
+ *     (no extra weight); the value head sees the trunk BEFORE the policy's step of the same minibatch, not after it.
+ * Nothing is configured at create: a learner may mix joint and separate steps, and learners sharing hyper-parameters
+ * (cdrl_learner_share_hparams) work unchanged.
+ *
+ * cdrl_learner_joint_forward_backward: the stored-action / injected-Jacobian loss (b->u, b->du_dalpha, b->du_dbeta as in
+ * cdrl_learner_policy_forward_backward) plus the value loss on `returns` (B, 2: base, exponent); the value loss takes b->speed and
+ * b->similarity (the agent gives both heads the same targets).  Order: train-mode trunk forward once, policy head forward, value
+ * head forward, policy loss, policy head backward, value loss, value head backward, then ONE launch (cdrl_bn_small_bwd_pair) that
+ * finishes the first BatchNorm of both heads and writes d(policy loss)/d(dynamics) + d(value loss)/d(dynamics), then the trunk
+ * backward once.  The gradients of both heads, CDRL_BUF_METRICS_P / _V and CDRL_BUF_AUX_P / _V are bit-identical to those of the
+ * separate passes on the same parameters; the trunk's gradient is the sum of theirs up to float32 rounding.  The communication
+ * stream (cdrl_learner_set_comm_stream) is released where the separate passes release it: both heads' gradients and the trunk
+ * tail's are final there, and cdrl_learner_tail_offset is unchanged.  freeze_trunk = 1: no trunk backward, the trunk's gradient
+ * slice is not written.  Captured and replayed as a hipGraph like policy_forward_backward.
+ * _resample: the same with u ~ Beta(alpha, beta) of the new policy drawn on the device behind the policy head's forward, as
+ * cdrl_learner_policy_forward_backward_resample (sample left in CDRL_BUF_SAMPLE; eager, not replayed).
+ * LIMIT (deliberate): both fail with -1 (cdrl_last_error names the limit) on a learner with B > 2048, where the heads' first
+ * BatchNorm is not in the single-launch form; there is no joint form above it.
+ *
+ * cdrl_learner_joint_apply: the optimizer steps of a joint pass.  Ungated: trunk update ONCE (not with freeze_trunk = 1), per-tensor
+ * norms of the policy head (they tick t_policy and t_dynamics), old_policy <- policy, policy head update, per-tensor norms of the
+ * value head (they tick t_value only), value head update.  Nadam m_caches advance with the counters they belong to.
+ * Gradient gate (clip_mode / skip_nonfinite): the gated policy_apply as it is, trunk included, then the gated value_apply WITHOUT
+ * the trunk.  Skip rule: the trunk and the policy head (and old_policy) are decided together, from the trunk's and the policy's
+ * list -- a non-finite element in either skips both, and counts as skipped[0]; the value head is decided from its own list alone
+ * (skipped[1]).  Clip rule with CDRL_CLIP_GLOBAL: each of the three lists is clipped once, by its own threshold (clip_norm_policy,
+ * clip_norm_dynamics, clip_norm_value); norm_dynamics[1] reads 0 and scale_dynamics[1] reads 1 after a joint apply.
+ * Train stats: two rows per joint apply, the policy's (kind 0), then the value's (kind 1); both carry the norms of the one joint
+ * trunk gradient and the same t_dynamics. */
+int cdrl_learner_joint_forward_backward(cdrl_learner* l, const cdrl_policy_batch* b, const float* returns, float grad_scale,
+                                       void* stream);
+int cdrl_learner_joint_forward_backward_resample(cdrl_learner* l, const cdrl_policy_batch* b, const float* returns, uint64_t seed,
+                                                uint64_t offset, float grad_scale, void* stream);
+int cdrl_learner_joint_apply(cdrl_learner* l, void* stream);
 /* CARLANetwork.update_old_policy (core/networks.py:281-285). */
 int cdrl_learner_update_old_policy(cdrl_learner* l, void* stream);
 /* CARLANetwork.predict deterministic part (core/networks.py:181-193): inference-mode trunk,
@@ -640,6 +681,13 @@ int cdrl_bn_small_fwd(const float* y, int M, int C, const float* gamma, const fl
                       float* moving_var, float* stats, float* out, void* stream);
 int cdrl_bn_small_bwd(const float* dout, const float* y, int M, int C, const float* stats, float* dgamma, float* dbeta,
                       float* coef, float* dx, void* stream);
+/* Backward of TWO such BatchNorms A and B that normalise the same input y (pi.bn0 and v.bn0 of the joint update, both over the
+ * trunk output) as one launch: dgamma / dbeta / coef of either are bit-identical to a cdrl_bn_small_bwd call on it alone (same
+ * geometry, same fixed reduction order, no atomics), and dx[r][c] = dxA + dxB, each term formed exactly as cdrl_bn_small_bwd
+ * forms it and the two joined by one float32 addition.  All tensors dense; statsA / statsB as cdrl_bn_small_fwd leaves them. */
+int cdrl_bn_small_bwd_pair(const float* doutA, const float* doutB, const float* y, int M, int C, const float* statsA,
+                           const float* statsB, float* dgammaA, float* dbetaA, float* coefA, float* dgammaB, float* dbetaB,
+                           float* coefB, float* dx, void* stream);
 /* The linear output heads of a control branch (core/networks.py:128-137, :267-275: up to 4 Dense(K -> n_h) layers on the
  * same [B][K] activation, 8 outputs in total) as one launch per direction.  w[h]: [K][n[h]], b[h]: [n[h]];
  * lin / dlin: [B][sum n]; backward: da [B][K] (overwritten), dw[h], db[h]. */
