@@ -368,21 +368,26 @@ class CARLAgent(PPOAgent):
         speed, similarity = self._info(returns.shape[0])
         return states, returns, speed, similarity
 
-    def get_policy_gradients(self, batch):
+    def _policy_pass(self, kind, batch, **extra):
+        """The `kind` ('policy' / 'joint') pass on a policy batch (+ extra tensors), staged under that name; returns the engine."""
         states, advantages, actions, log_probabilities, speed, similarity = batch
         eng = self._step_engine = self.network.engine_for(advantages.shape[0])
         b = dict(states={k: states[k] for k in ('state_image', 'state_road', 'state_vehicle', 'state_navigation')},
-                 advantages=advantages, old_log_prob=log_probabilities, speed=speed, similarity=similarity, u=actions)
-        b = eng.stage(b, 'policy')           # fixed addresses -> the captured hipGraph of the step is replayed
+                 advantages=advantages, old_log_prob=log_probabilities, speed=speed, similarity=similarity, u=actions, **extra)
+        b = eng.stage(b, kind)               # fixed addresses -> the captured hipGraph of the step is replayed
         b.update(du_da=None, du_db=None)
         scale = 1.0 / self.world
         if self.resample_actions:
             # Beta(alpha, beta) of the NEW policy is sampled on the device with pathwise Jacobians (rank-disjoint Philox offsets)
             self._sample_offset += 1
-            eng.policy_forward_backward_resample(b, seed=self.seed if self.seed is not None else 0,
-                                                 offset=self._sample_offset * self.world + self.rank, grad_scale=scale)
+            getattr(eng, f'{kind}_forward_backward_resample')(b, seed=self.seed if self.seed is not None else 0,
+                                                              offset=self._sample_offset * self.world + self.rank, grad_scale=scale)
         else:
-            eng.policy_forward_backward(b, grad_scale=scale)
+            getattr(eng, f'{kind}_forward_backward')(b, grad_scale=scale)
+        return eng
+
+    def get_policy_gradients(self, batch):
+        eng = self._policy_pass('policy', batch)
         if self.data_parallel:
             self._dp_for(eng).reduce_policy_gradients()
         return eng.buffer(2)[0].clone(), 'policy'  # device scalar (copy of CDRL_BUF_METRICS_P[0]); gradients stay in the arena
@@ -406,19 +411,8 @@ class CARLAgent(PPOAgent):
         return gradients
 
     def get_joint_gradients(self, batch):
-        states, advantages, actions, log_probabilities, speed, similarity, returns = batch
-        eng = self._step_engine = self.network.engine_for(advantages.shape[0])
-        b = dict(states={k: states[k] for k in ('state_image', 'state_road', 'state_vehicle', 'state_navigation')},
-                 advantages=advantages, old_log_prob=log_probabilities, speed=speed, similarity=similarity, u=actions, returns=returns)
-        b = eng.stage(b, 'joint')
-        b.update(du_da=None, du_db=None)
-        scale = 1.0 / self.world
-        if self.resample_actions:       # (as get_policy_gradients)
-            self._sample_offset += 1
-            eng.joint_forward_backward_resample(b, seed=self.seed if self.seed is not None else 0,
-                                                offset=self._sample_offset * self.world + self.rank, grad_scale=scale)
-        else:
-            eng.joint_forward_backward(b, grad_scale=scale)
+        *policy_batch, returns = batch
+        eng = self._policy_pass('joint', policy_batch, returns=returns)
         if self.data_parallel:
             self._dp_for(eng).reduce_joint_gradients()
         return (eng.buffer(2)[0].clone(), eng.buffer(3)[0].clone()), 'joint'

@@ -28,6 +28,29 @@ static inline bool bad_act_type(int at) {
     return true;
 }
 
+// cdrl_policy_batch -> PolicyBatch.  need_u: the stored-action forms; the re-sampling forms ignore u / du_* (passed on as null)
+static int policy_batch(const cdrl_policy_batch* b, bool need_u, const char* what, PolicyBatch* out) {
+    if (!b) {
+        cdrl::set_error("%s: null batch", what);
+        return -1;
+    }
+    *out = PolicyBatch{b->image, b->road, b->vehicle, b->navigation, b->advantages, b->old_log_prob, b->speed, b->similarity,
+                       need_u ? b->u : nullptr, need_u ? b->du_dalpha : nullptr, need_u ? b->du_dbeta : nullptr};
+    if (!out->adv || !out->old_logp || !out->speed || !out->similarity || (need_u && !out->u)) {
+        cdrl::set_error("%s: null tensor", what);
+        return -1;
+    }
+    return 0;
+}
+
+// ... plus the returns of a joint pass
+static int joint_batch(const cdrl_policy_batch* b, bool need_u, const float* returns, PolicyBatch* out) {
+    CDRL_TRY(policy_batch(b, need_u, "joint batch", out));
+    if (returns) return 0;
+    cdrl::set_error("joint batch: null tensor");
+    return -1;
+}
+
 extern "C" {
 
 const char* cdrl_last_error(void) { return cdrl::last_error(); }
@@ -426,13 +449,8 @@ int cdrl_learner_set_optimizer_state(cdrl_learner* l, const cdrl_optimizer_state
 
 int cdrl_learner_policy_forward_backward(cdrl_learner* l, const cdrl_policy_batch* b, float grad_scale, void* stream) {
     CHECK_L(l);
-    if (!b) return -1;
-    PolicyBatch pb{b->image, b->road, b->vehicle, b->navigation, b->advantages, b->old_log_prob,
-                   b->speed, b->similarity, b->u, b->du_dalpha, b->du_dbeta};
-    if (!pb.adv || !pb.old_logp || !pb.speed || !pb.similarity || !pb.u) {
-        cdrl::set_error("policy batch: null tensor");
-        return -1;
-    }
+    PolicyBatch pb;
+    CDRL_TRY(policy_batch(b, true, "policy batch", &pb));
     return l->impl->policy_forward_backward(pb, grad_scale, S(stream));
 }
 
@@ -444,26 +462,16 @@ int cdrl_learner_policy_forward(cdrl_learner* l, const float* image, const float
 
 int cdrl_learner_policy_backward(cdrl_learner* l, const cdrl_policy_batch* b, float grad_scale, void* stream) {
     CHECK_L(l);
-    if (!b) return -1;
-    PolicyBatch pb{b->image, b->road, b->vehicle, b->navigation, b->advantages, b->old_log_prob,
-                   b->speed, b->similarity, b->u, b->du_dalpha, b->du_dbeta};
-    if (!pb.adv || !pb.old_logp || !pb.speed || !pb.similarity || !pb.u) {
-        cdrl::set_error("policy batch: null tensor");
-        return -1;
-    }
+    PolicyBatch pb;
+    CDRL_TRY(policy_batch(b, true, "policy batch", &pb));
     return l->impl->policy_backward(pb, grad_scale, S(stream));
 }
 
 int cdrl_learner_policy_forward_backward_resample(cdrl_learner* l, const cdrl_policy_batch* b, uint64_t seed,
                                                  uint64_t offset, float grad_scale, void* stream) {
     CHECK_L(l);
-    if (!b) return -1;
-    PolicyBatch pb{b->image, b->road, b->vehicle, b->navigation, b->advantages, b->old_log_prob,
-                   b->speed, b->similarity, nullptr, nullptr, nullptr};
-    if (!pb.adv || !pb.old_logp || !pb.speed || !pb.similarity) {
-        cdrl::set_error("policy batch: null tensor");
-        return -1;
-    }
+    PolicyBatch pb;
+    CDRL_TRY(policy_batch(b, false, "policy batch", &pb));
     return l->impl->policy_forward_backward_resample(pb, seed, offset, grad_scale, S(stream));
 }
 
@@ -545,26 +553,16 @@ int cdrl_learner_value_apply(cdrl_learner* l, void* stream) {
 int cdrl_learner_joint_forward_backward(cdrl_learner* l, const cdrl_policy_batch* b, const float* returns, float grad_scale,
                                        void* stream) {
     CHECK_L(l);
-    if (!b) return -1;
-    PolicyBatch pb{b->image, b->road, b->vehicle, b->navigation, b->advantages, b->old_log_prob,
-                   b->speed, b->similarity, b->u, b->du_dalpha, b->du_dbeta};
-    if (!pb.adv || !pb.old_logp || !pb.speed || !pb.similarity || !pb.u || !returns) {
-        cdrl::set_error("joint batch: null tensor");
-        return -1;
-    }
+    PolicyBatch pb;
+    CDRL_TRY(joint_batch(b, true, returns, &pb));
     return l->impl->joint_forward_backward(pb, returns, grad_scale, S(stream));
 }
 
 int cdrl_learner_joint_forward_backward_resample(cdrl_learner* l, const cdrl_policy_batch* b, const float* returns, uint64_t seed,
                                                 uint64_t offset, float grad_scale, void* stream) {
     CHECK_L(l);
-    if (!b) return -1;
-    PolicyBatch pb{b->image, b->road, b->vehicle, b->navigation, b->advantages, b->old_log_prob,
-                   b->speed, b->similarity, nullptr, nullptr, nullptr};
-    if (!pb.adv || !pb.old_logp || !pb.speed || !pb.similarity || !returns) {
-        cdrl::set_error("joint batch: null tensor");
-        return -1;
-    }
+    PolicyBatch pb;
+    CDRL_TRY(joint_batch(b, false, returns, &pb));
     return l->impl->joint_forward_backward_resample(pb, returns, seed, offset, grad_scale, S(stream));
 }
 

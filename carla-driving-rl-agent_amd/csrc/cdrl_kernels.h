@@ -573,9 +573,10 @@ struct TensorSeg {      // one parameter tensor inside a flat arena
 int tensor_sqnorms(const float* g, const TensorSeg* segs_dev, int ntensors, const int* chunk_tensor_dev,
                    const int64_t* chunk_off_dev, int nchunks, double* chunk_part, float* sqnorms, hipStream_t st,
                    DevHP* tick_hp = nullptr, int tick_mask = 0, bool fold_final = false);
-// tick_hp / tick_mask (1 policy, 2 value, 4 trunk): the chunk kernel also advances those step counters (| 8: and, for Nadam, their
+// tick_hp / tick_mask (TICK_*): the chunk kernel also advances those step counters (| TICK_NADAM: and, for Nadam, their
 // m_caches to S_t of the new count); fold_final: no second
 // stage -- the consumer folds the chunk partials (clip_adam with chunk_part)
+enum TickMask : int { TICK_POLICY = 1, TICK_VALUE = 2, TICK_TRUNK = 4, TICK_NADAM = 8 };
 int clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev /*or null*/,
               const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms /*or null*/,
               DevHP* hp, int which, hipStream_t st, const double* chunk_part = nullptr, int ticked = 0);

@@ -382,17 +382,37 @@ private:
     hipEvent_t ev_in_ = nullptr, ev_out_ = nullptr;
     bool graphs_enabled_ = true;
     std::map<std::vector<uint64_t>, hipGraphExec_t> graphs_;
-    int policy_backward_impl(const PolicyBatch& b, float inv_world, hipStream_t st);
-    int policy_forward_impl(const float* image, const float* road, const float* vehicle, const float* navigation,
-                            hipStream_t st);
-    int value_forward_backward_impl(const ValueBatch& b, float inv_world, hipStream_t st);
+    // One training pass as its entry point describes it: the state pointers, the policy part (adv .. du_db) and / or the value part
+    // (returns; both: the joint pass), the one speed / similarity pair, the device re-sampling and the gradient scale
+    struct PassSpec {
+        const float *image, *road, *vehicle, *navigation, *speed, *similarity;
+        const PolicyBatch* policy;          // its adv, old_logp, u, du_da, du_db; or null
+        const float* returns;               // or null
+        float inv_world;
+        bool resample = false;              // u, du_da, du_db: drawn on the device from the new policy with (seed, offset), not the batch's
+        uint64_t seed = 0, offset = 0;
+        bool joint() const { return policy && returns; }
+    };
+    static PassSpec policy_pass(const PolicyBatch& b, const float* returns, float inv_world, bool resample = false, uint64_t seed = 0,
+                                uint64_t offset = 0) {
+        return {b.image, b.road, b.vehicle, b.navigation, b.speed, b.similarity, &b, returns, inv_world, resample, seed, offset};
+    }
+    PolicyLossArgs policy_loss_args(const PassSpec& s) const;
+    ValueLossArgs value_loss_args(const PassSpec& s) const;
+    // forward half: trunk, the heads present (dist: policy_dist behind the policy head; re-sampling: and the Beta draw, both in
+    // front of the value head); backward half: per head its loss and backward, joint: bn_small_bwd_pair, then the trunk
+    int pass_forward(const PassSpec& s, bool dist, hipStream_t st);
+    int pass_backward(const PassSpec& s, hipStream_t st);
+    int trunk_backward_tail(hipStream_t st);
+    // entry of every pass (fwd / bwd: the halves to run): gradient-scale hint, graph key, graph replay or eager launch
+    int run_pass(const PassSpec& s, hipStream_t caller, bool fwd = true, bool bwd = true);
     int update_old_policy_impl(hipStream_t st);
+    // the ungated apply of one head (0 policy, 1 value); with_trunk = false: as gated_apply's
+    int head_apply(int head, bool with_trunk, hipStream_t st);
     int policy_apply_impl(hipStream_t st);
     int value_apply_impl(hipStream_t st);
     int joint_apply_impl(hipStream_t st);
     int joint_refused();
-    // forward of the trunk and both heads (sample != null: policy_dist + Beta draw behind the policy head), losses, backward
-    int joint_impl(const PolicyBatch& b, const float* returns, const uint64_t* sample, float inv_world, hipStream_t st);
     int predict_impl(const float* image, const float* road, const float* vehicle, const float* navigation, float* dist_out,
                      float* value_out, float* dyn_out, hipStream_t st);
     int run_fwd(std::vector<Op>& ops, hipStream_t st, int training);

@@ -1932,121 +1932,97 @@ int Learner::trunk_forward_train(const float* image, const float* road, const fl
     });
 }
 
-int Learner::policy_forward(const float* image, const float* road, const float* vehicle, const float* navigation,
-                            hipStream_t caller) {
-    return launch(caller, {}, false, [&](hipStream_t st) -> int { return policy_forward_impl(image, road, vehicle, navigation, st); });
-}
-
-int Learner::policy_forward_impl(const float* image, const float* road, const float* vehicle, const float* navigation,
-                                 hipStream_t st) {
-    CDRL_TRY(set_inputs(image, road, vehicle, navigation));
-    CDRL_TRY(run_trunk_fwd(st, 1));
-    CDRL_TRY(run_fwd(policy_ops_, st, 1));
-    // alpha, beta (+ mean, std) of the CURRENT policy for the Beta re-sampling
-    return policy_dist(lin_p_.p, aux_p_, cfg_.B, cfg_.A, st);
-}
-
-int Learner::policy_backward(const PolicyBatch& b, float inv_world, hipStream_t caller) {
-    if (inv_world != 1.0f) dp_hint_ = true;
-    return launch(caller, {}, false, [&](hipStream_t st) -> int { return policy_backward_impl(b, inv_world, st); });
-}
-
-int Learner::policy_backward_impl(const PolicyBatch& b, float inv_world, hipStream_t st) {
-    PolicyLossArgs a;
-    a.lin = lin_p_.p;
-    a.adv = b.adv;
-    a.old_logp = b.old_logp;
-    a.speed = b.speed;
-    a.similarity = b.similarity;
-    a.u = b.u;
-    a.du_da = b.du_da;
-    a.du_db = b.du_db;
-    a.hp = reinterpret_cast<const float*>(hp_dev_);
-    a.dlin = lin_p_.g;
-    a.metrics = metrics_p_;
-    a.aux = aux_p_;
-    a.B = cfg_.B;
-    a.A = cfg_.A;
-    a.inv_world = inv_world;
-    CDRL_TRY(policy_loss(a, st));
-    CDRL_TRY(run_bwd(policy_ops_, st));
-    // Frozen trunk: the heads' backward ends in the BatchNorm of pi.bn0, which also writes d(loss)/d(dynamics) into the trunk's
-    // output gradient.  That write has no consumer here, but up to 2048 rows it comes out of the same launch that produces the
-    // BatchNorm's dgamma / dbeta (bn_small_bwd, one launch per direction): it stays, and the head gradients are those of a full pass.
-    if (frozen()) return join_side(st);
-    if (!packs_have_wt_) CDRL_TRY(transpose_many(d_pwt_, (int)h_pwt_.size(), pwt_tiles_, st));      // W^T of the pointwise convs (normally packed with the forward's operands)
-    CDRL_TRY(run_bwd(trunk_ops_, st));
-    return join_side(st);
-}
-
-int Learner::policy_forward_backward_resample(const PolicyBatch& b, uint64_t seed, uint64_t offset, float inv_world,
-                                              hipStream_t caller) {
-    if (inv_world != 1.0f) dp_hint_ = true;
-    // (seed, offset) are kernel arguments that change every call -> eager, not graph-replayed
-    return launch(caller, {}, false, [&](hipStream_t st) -> int {
-        CDRL_TRY(policy_forward_impl(b.image, b.road, b.vehicle, b.navigation, st));
-        const int A = cfg_.A;
-        CDRL_TRY(beta_sample(aux_p_, aux_p_ + A, cfg_.B, A, 4 * A, seed, offset, sample_u_, sample_da_, sample_db_, st));
-        PolicyBatch r = b;
-        r.u = sample_u_;
-        r.du_da = sample_da_;
-        r.du_db = sample_db_;
-        return policy_backward_impl(r, inv_world, st);
-    });
-}
-
+// ------------------------------------------------------------------------------------------
+// Training passes.  Every entry describes its pass as a PassSpec and goes through run_pass; both heads present: the joint
+// policy + value update, one trunk forward and one trunk backward per minibatch
+// ------------------------------------------------------------------------------------------
 static inline uint64_t K(const void* p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); }
 static inline uint64_t Kf(float f) {
     uint32_t u;
     memcpy(&u, &f, 4);
     return u;
 }
+// step kind: the first word of a graph key
+enum KeyKind : uint64_t {
+    KEY_POLICY_PASS = 1, KEY_VALUE_PASS = 2, KEY_POLICY_APPLY = 3, KEY_VALUE_APPLY = 4, KEY_PREDICT = 5, KEY_JOINT_PASS = 6, KEY_JOINT_APPLY = 7
+};
 
-int Learner::policy_forward_backward(const PolicyBatch& b, float inv_world, hipStream_t caller) {
-    if (inv_world != 1.0f) dp_hint_ = true;
-    std::vector<uint64_t> key = {1, K(b.image), K(b.road), K(b.vehicle), K(b.navigation), K(b.adv), K(b.old_logp), K(b.speed),
-                                 K(b.similarity), K(b.u), K(b.du_da), K(b.du_db), Kf(inv_world)};
-    return launch(caller, key, true, [&](hipStream_t st) -> int {
-        CDRL_TRY(set_inputs(b.image, b.road, b.vehicle, b.navigation));
-        CDRL_TRY(run_trunk_fwd(st, 1));
-        CDRL_TRY(run_fwd(policy_ops_, st, 1));
-        return policy_backward_impl(b, inv_world, st);
-    });
+PolicyLossArgs Learner::policy_loss_args(const PassSpec& s) const {
+    PolicyLossArgs a;
+    a.lin = lin_p_.p;
+    a.adv = s.policy->adv;
+    a.old_logp = s.policy->old_logp;
+    a.speed = s.speed;
+    a.similarity = s.similarity;
+    a.u = s.resample ? sample_u_ : s.policy->u;
+    a.du_da = s.resample ? sample_da_ : s.policy->du_da;
+    a.du_db = s.resample ? sample_db_ : s.policy->du_db;
+    a.hp = reinterpret_cast<const float*>(hp_dev_);
+    a.dlin = lin_p_.g;
+    a.metrics = metrics_p_;
+    a.aux = aux_p_;
+    a.B = cfg_.B;
+    a.A = cfg_.A;
+    a.inv_world = s.inv_world;
+    return a;
 }
 
-int Learner::value_forward_backward(const ValueBatch& b, float inv_world, hipStream_t caller) {
-    if (inv_world != 1.0f) dp_hint_ = true;
-    std::vector<uint64_t> key = {2, K(b.image), K(b.road), K(b.vehicle), K(b.navigation), K(b.returns), K(b.speed),
-                                 K(b.similarity), Kf(inv_world)};
-    return launch(caller, key, true, [&](hipStream_t st) -> int { return value_forward_backward_impl(b, inv_world, st); });
-}
-
-int Learner::value_forward_backward_impl(const ValueBatch& b, float inv_world, hipStream_t st) {
-    CDRL_TRY(set_inputs(b.image, b.road, b.vehicle, b.navigation));
-    CDRL_TRY(run_trunk_fwd(st, 1));
-    CDRL_TRY(run_fwd(value_ops_, st, 1));
+ValueLossArgs Learner::value_loss_args(const PassSpec& s) const {
     ValueLossArgs a;
     a.lin = lin_v_.p;
-    a.returns = b.returns;
-    a.speed = b.speed;
-    a.similarity = b.similarity;
+    a.returns = s.returns;
+    a.speed = s.speed;
+    a.similarity = s.similarity;
     a.dlin = lin_v_.g;
     a.metrics = metrics_v_;
     a.values = aux_v_;
     a.B = cfg_.B;
     a.exp_scale = cfg_.exp_scale;
-    a.inv_world = inv_world;
-    CDRL_TRY(value_loss(a, st));
-    CDRL_TRY(run_bwd(value_ops_, st));
-    if (frozen()) return join_side(st);        // (see policy_backward_impl)
-    if (!packs_have_wt_) CDRL_TRY(transpose_many(d_pwt_, (int)h_pwt_.size(), pwt_tiles_, st));
+    a.inv_world = s.inv_world;
+    return a;
+}
+
+int Learner::pass_forward(const PassSpec& s, bool dist, hipStream_t st) {
+    CDRL_TRY(set_inputs(s.image, s.road, s.vehicle, s.navigation));
+    CDRL_TRY(run_trunk_fwd(st, 1));
+    if (s.policy) CDRL_TRY(run_fwd(policy_ops_, st, 1));
+    const int A = cfg_.A;
+    // alpha, beta (+ mean, std) of the CURRENT policy for the Beta re-sampling
+    if (dist || s.resample) CDRL_TRY(policy_dist(lin_p_.p, aux_p_, cfg_.B, A, st));
+    if (s.resample)     // u ~ Beta(alpha, beta) of the new policy, with its pathwise Jacobians
+        CDRL_TRY(beta_sample(aux_p_, aux_p_ + A, cfg_.B, A, 4 * A, s.seed, s.offset, sample_u_, sample_da_, sample_db_, st));
+    return s.returns ? run_fwd(value_ops_, st, 1) : 0;
+}
+
+int Learner::pass_backward(const PassSpec& s, hipStream_t st) {
+    // joint: each head's backward stops in front of its bn0; one launch then finishes both bn0 over the trunk output -- their own
+    // gradients, and dyn_.g = d(policy loss)/d(dynamics) + d(value loss)/d(dynamics)
+    const HeadBn0 &p0 = bn0_[0], &v0 = bn0_[1];
+    if (s.policy) {
+        CDRL_TRY(policy_loss(policy_loss_args(s), st));
+        CDRL_TRY(run_bwd(policy_ops_, st, s.joint() ? p0.op + 1 : 0));
+    }
+    if (s.returns) {
+        CDRL_TRY(value_loss(value_loss_args(s), st));
+        CDRL_TRY(run_bwd(value_ops_, st, s.joint() ? v0.op + 1 : 0));
+    }
+    if (s.joint())
+        CDRL_TRY(bn_small_bwd_pair(p0.dout, v0.dout, p0.bn.x, p0.bn.Mg, p0.bn.C, p0.bn.stats, v0.bn.stats, p0.bn.gamma.g, p0.bn.beta.g,
+                                   p0.bn.coef, v0.bn.gamma.g, v0.bn.beta.g, v0.bn.coef, dyn_.g, st));
+    return trunk_backward_tail(st);
+}
+
+int Learner::trunk_backward_tail(hipStream_t st) {
+    // Frozen trunk: the heads' backward ends in the BatchNorm of bn0 (joint: the pair launch), which also writes d(loss)/d(dynamics)
+    // into the trunk's output gradient.  That write has no consumer here, but up to 2048 rows it comes out of the same launch that
+    // produces the BatchNorm's dgamma / dbeta (bn_small_bwd, one launch per direction): it stays, and the head gradients are those of
+    // a full pass.
+    if (frozen()) return join_side(st);
+    if (!packs_have_wt_) CDRL_TRY(transpose_many(d_pwt_, (int)h_pwt_.size(), pwt_tiles_, st));      // W^T of the pointwise convs (normally packed with the forward's operands)
     CDRL_TRY(run_bwd(trunk_ops_, st));
     return join_side(st);
 }
 
-// ------------------------------------------------------------------------------------------
-// Joint policy + value update: one trunk forward and one trunk backward per minibatch
-// ------------------------------------------------------------------------------------------
 int Learner::joint_refused() {
     if (bn0_[0].small && bn0_[1].small && bn0_[0].op == 0 && bn0_[1].op == 0) return 0;
     set_error("joint update: the heads' first BatchNorm is not in the single-launch form (B = %d > 2048 rows); use the separate passes",
@@ -2054,78 +2030,57 @@ int Learner::joint_refused() {
     return -1;
 }
 
-int Learner::joint_impl(const PolicyBatch& b, const float* returns, const uint64_t* sample, float inv_world, hipStream_t st) {
-    CDRL_TRY(set_inputs(b.image, b.road, b.vehicle, b.navigation));
-    CDRL_TRY(run_trunk_fwd(st, 1));
-    CDRL_TRY(run_fwd(policy_ops_, st, 1));
-    PolicyLossArgs a;
-    a.u = b.u;
-    a.du_da = b.du_da;
-    a.du_db = b.du_db;
-    if (sample) {       // as policy_forward_backward_resample: u ~ Beta(alpha, beta) of the new policy, with its pathwise Jacobians
-        const int A = cfg_.A;
-        CDRL_TRY(policy_dist(lin_p_.p, aux_p_, cfg_.B, A, st));
-        CDRL_TRY(beta_sample(aux_p_, aux_p_ + A, cfg_.B, A, 4 * A, sample[0], sample[1], sample_u_, sample_da_, sample_db_, st));
-        a.u = sample_u_;
-        a.du_da = sample_da_;
-        a.du_db = sample_db_;
+int Learner::run_pass(const PassSpec& s, hipStream_t caller, bool fwd, bool bwd) {
+    if (s.joint()) CDRL_TRY(joint_refused());
+    if (s.inv_world != 1.0f) dp_hint_ = true;
+    // one half alone (the split form) is eager; so is re-sampling: (seed, offset) are kernel arguments that change every call
+    const bool graphable = fwd && bwd && !s.resample;
+    std::vector<uint64_t> key;
+    if (graphable) {
+        key = {s.joint() ? KEY_JOINT_PASS : s.policy ? KEY_POLICY_PASS : KEY_VALUE_PASS,
+               K(s.image), K(s.road), K(s.vehicle), K(s.navigation), K(s.speed), K(s.similarity), K(s.returns), Kf(s.inv_world)};
+        if (const PolicyBatch* b = s.policy) key.insert(key.end(), {K(b->adv), K(b->old_logp), K(b->u), K(b->du_da), K(b->du_db)});
     }
-    CDRL_TRY(run_fwd(value_ops_, st, 1));
-    a.lin = lin_p_.p;
-    a.adv = b.adv;
-    a.old_logp = b.old_logp;
-    a.speed = b.speed;
-    a.similarity = b.similarity;
-    a.hp = reinterpret_cast<const float*>(hp_dev_);
-    a.dlin = lin_p_.g;
-    a.metrics = metrics_p_;
-    a.aux = aux_p_;
-    a.B = cfg_.B;
-    a.A = cfg_.A;
-    a.inv_world = inv_world;
-    CDRL_TRY(policy_loss(a, st));
-    CDRL_TRY(run_bwd(policy_ops_, st, bn0_[0].op + 1));
-    ValueLossArgs v;
-    v.lin = lin_v_.p;
-    v.returns = returns;
-    v.speed = b.speed;
-    v.similarity = b.similarity;
-    v.dlin = lin_v_.g;
-    v.metrics = metrics_v_;
-    v.values = aux_v_;
-    v.B = cfg_.B;
-    v.exp_scale = cfg_.exp_scale;
-    v.inv_world = inv_world;
-    CDRL_TRY(value_loss(v, st));
-    CDRL_TRY(run_bwd(value_ops_, st, bn0_[1].op + 1));
-    // both bn0 over the trunk output: their own gradients, and dyn_.g = d(policy loss)/d(dynamics) + d(value loss)/d(dynamics)
-    const HeadBn0 &p0 = bn0_[0], &v0 = bn0_[1];
-    CDRL_TRY(bn_small_bwd_pair(p0.dout, v0.dout, p0.bn.x, p0.bn.Mg, p0.bn.C, p0.bn.stats, v0.bn.stats, p0.bn.gamma.g, p0.bn.beta.g,
-                               p0.bn.coef, v0.bn.gamma.g, v0.bn.beta.g, v0.bn.coef, dyn_.g, st));
-    if (frozen()) return join_side(st);        // (see policy_backward_impl; the summed dyn_.g has no consumer)
-    if (!packs_have_wt_) CDRL_TRY(transpose_many(d_pwt_, (int)h_pwt_.size(), pwt_tiles_, st));
-    CDRL_TRY(run_bwd(trunk_ops_, st));
-    return join_side(st);
+    return launch(caller, key, graphable, [&](hipStream_t st) -> int {
+        if (fwd) CDRL_TRY(pass_forward(s, !bwd, st));       // (the forward alone: its caller samples from alpha, beta)
+        return bwd ? pass_backward(s, st) : 0;
+    });
+}
+
+int Learner::policy_forward_backward(const PolicyBatch& b, float inv_world, hipStream_t caller) {
+    return run_pass(policy_pass(b, nullptr, inv_world), caller);
+}
+
+int Learner::policy_forward(const float* image, const float* road, const float* vehicle, const float* navigation,
+                            hipStream_t caller) {
+    const PolicyBatch b{image, road, vehicle, navigation};
+    return run_pass(policy_pass(b, nullptr, 1.0f), caller, true, false);
+}
+
+int Learner::policy_backward(const PolicyBatch& b, float inv_world, hipStream_t caller) {
+    return run_pass(policy_pass(b, nullptr, inv_world), caller, false, true);
+}
+
+int Learner::policy_forward_backward_resample(const PolicyBatch& b, uint64_t seed, uint64_t offset, float inv_world,
+                                              hipStream_t caller) {
+    return run_pass(policy_pass(b, nullptr, inv_world, true, seed, offset), caller);
+}
+
+int Learner::value_forward_backward(const ValueBatch& b, float inv_world, hipStream_t caller) {
+    return run_pass({b.image, b.road, b.vehicle, b.navigation, b.speed, b.similarity, nullptr, b.returns, inv_world}, caller);
 }
 
 int Learner::joint_forward_backward(const PolicyBatch& b, const float* returns, float inv_world, hipStream_t caller) {
-    CDRL_TRY(joint_refused());
-    if (inv_world != 1.0f) dp_hint_ = true;
-    std::vector<uint64_t> key = {6, K(b.image), K(b.road), K(b.vehicle), K(b.navigation), K(b.adv), K(b.old_logp), K(b.speed),
-                                 K(b.similarity), K(b.u), K(b.du_da), K(b.du_db), K(returns), Kf(inv_world)};
-    return launch(caller, key, true, [&](hipStream_t st) -> int { return joint_impl(b, returns, nullptr, inv_world, st); });
+    return run_pass(policy_pass(b, returns, inv_world), caller);
 }
 
 int Learner::joint_forward_backward_resample(const PolicyBatch& b, const float* returns, uint64_t seed, uint64_t offset, float inv_world,
                                              hipStream_t caller) {
-    CDRL_TRY(joint_refused());
-    if (inv_world != 1.0f) dp_hint_ = true;
-    const uint64_t sample[2] = {seed, offset};      // kernel arguments that change every call -> eager, not graph-replayed
-    return launch(caller, {}, false, [&](hipStream_t st) -> int { return joint_impl(b, returns, sample, inv_world, st); });
+    return run_pass(policy_pass(b, returns, inv_world, true, seed, offset), caller);
 }
 
 int Learner::joint_apply(hipStream_t caller) {
-    return launch(caller, {7}, true, [&](hipStream_t st) -> int { return joint_apply_impl(st); });
+    return launch(caller, {KEY_JOINT_APPLY}, true, [&](hipStream_t st) -> int { return joint_apply_impl(st); });
 }
 
 int Learner::joint_apply_impl(hipStream_t st) {
@@ -2134,16 +2089,9 @@ int Learner::joint_apply_impl(hipStream_t st) {
         CDRL_TRY(gated_apply(0, st));
         return gated_apply(1, st, false);
     }
-    // policy_apply_impl, then value_apply_impl without its trunk step and trunk tick: the trunk's optimizer steps once per joint step
-    CDRL_TRY(policy_apply_impl(st));
-    const int64_t vo = tr_offset(M_VALUE);
-    const int opt = cfg_.optimizer, nadam = opt == CDRL_OPT_NADAM ? 8 : 0;
-    SegTable& s = seg_[M_VALUE];
-    CDRL_TRY(tensor_sqnorms(buf_.grads + vo, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part, s.sqnorms, st,
-                            hp_dev_, 2 | nadam, true));
-    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + vo, buf_.grads + vo, buf_.adam_m + vo, buf_.adam_v + vo, tr_size_[M_VALUE],
-                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 1, st, s.chunk_part, 1));
-    return cfg_.train_stats > 0 ? stats_row(1, st) : 0;
+    // the value head without the trunk step and trunk tick: the trunk's optimizer steps once per joint step
+    CDRL_TRY(head_apply(0, true, st));
+    return head_apply(1, false, st);
 }
 
 int Learner::update_old_policy(hipStream_t caller) {
@@ -2158,7 +2106,7 @@ int Learner::update_old_policy_impl(hipStream_t st) {
 }
 
 int Learner::policy_apply(hipStream_t caller) {
-    return launch(caller, {3}, true, [&](hipStream_t st) -> int { return policy_apply_impl(st); });
+    return launch(caller, {KEY_POLICY_APPLY}, true, [&](hipStream_t st) -> int { return policy_apply_impl(st); });
 }
 
 // The apply step of a learner with the gradient gate: chunk norms of the lists the step consumes -> gate (scales,
@@ -2188,26 +2136,32 @@ int Learner::gated_apply(int head, hipStream_t st, bool with_trunk) {
     return cfg_.train_stats > 0 ? stats_row(head, st) : 0;
 }
 
-int Learner::policy_apply_impl(hipStream_t st) {
-    if (gate_on()) return gated_apply(0, st);
-    // order: trunk Adam (unclipped, F9) -> clip -> old_policy <- policy -> policy Adam
-    // frozen trunk: no trunk Adam step, and the trunk's step counter stays where it is (reference ppo.py:238-252 on the heads only)
-    // (another cdrl_config.optimizer: its step in place of Adam's, same launches; polyak < 1: the policy is averaged in its update)
-    const int64_t to = tr_offset(M_TRUNK), po = tr_offset(M_POLICY);
-    const int opt = cfg_.optimizer, nadam = opt == CDRL_OPT_NADAM ? 8 : 0;
-    if (!frozen())
+// The ungated apply of one head (0 policy, 1 value).  with_trunk = false (the value head of a joint apply): no trunk step, no trunk tick.
+// order: trunk Adam (unclipped, F9) -> clip -> old_policy <- policy -> policy Adam
+// frozen trunk: no trunk Adam step, and the trunk's step counter stays where it is (reference ppo.py:238-252 on the heads only)
+// (another cdrl_config.optimizer: its step in place of Adam's, same launches; polyak < 1: the head is averaged in its update)
+int Learner::head_apply(int head, bool with_trunk, hipStream_t st) {
+    const int hm = head == 0 ? M_POLICY : M_VALUE;
+    const int64_t to = tr_offset(M_TRUNK), ho = tr_offset(hm);
+    const int opt = cfg_.optimizer;
+    const bool trunk = with_trunk && !frozen();
+    if (trunk)
         CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK],
                              nullptr, nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
-    SegTable& s = seg_[M_POLICY];
+    SegTable& s = seg_[hm];
     // four launches instead of seven (round 6): the chunk kernel of the norms also advances the trunk's step counter (its update ran in front)
-    // and the policy's (its update runs behind and is told so); the per-tensor fold of the chunk partials happens inside clip_adam
-    CDRL_TRY(tensor_sqnorms(buf_.grads + po, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part,
-                            s.sqnorms, st, hp_dev_, (frozen() ? 1 : 4 | 1) | nadam, true));
-    CDRL_TRY(update_old_policy_impl(st));
-    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + po, buf_.grads + po, buf_.adam_m + po, buf_.adam_v + po, tr_size_[M_POLICY],
-                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 0, st, s.chunk_part, 1));
-    return cfg_.train_stats > 0 ? stats_row(0, st) : 0;
+    // and the head's (its update runs behind and is told so); the per-tensor fold of the chunk partials happens inside clip_adam
+    const int tick = (head == 0 ? TICK_POLICY : TICK_VALUE) | (trunk ? TICK_TRUNK : 0) | (opt == CDRL_OPT_NADAM ? TICK_NADAM : 0);
+    CDRL_TRY(tensor_sqnorms(buf_.grads + ho, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part, s.sqnorms, st,
+                            hp_dev_, tick, true));
+    if (head == 0) CDRL_TRY(update_old_policy_impl(st));
+    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + ho, buf_.grads + ho, buf_.adam_m + ho, buf_.adam_v + ho, tr_size_[hm],
+                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, head, st, s.chunk_part, 1));
+    return cfg_.train_stats > 0 ? stats_row(head, st) : 0;
 }
+
+int Learner::policy_apply_impl(hipStream_t st) { return gate_on() ? gated_apply(0, st) : head_apply(0, true, st); }
+int Learner::value_apply_impl(hipStream_t st) { return gate_on() ? gated_apply(1, st) : head_apply(1, true, st); }
 
 // Tail of an apply step with cfg.train_stats > 0: one ring row.  The gradients are read-only during the apply and the head's chunk
 // partials (written by the clip path above, from the unclipped gradient) stay until the head's next apply, so this runs in order
@@ -2251,27 +2205,12 @@ int Learner::stats_reset(hipStream_t caller) {
 }
 
 int Learner::value_apply(hipStream_t caller) {
-    return launch(caller, {4}, true, [&](hipStream_t st) -> int { return value_apply_impl(st); });
-}
-
-int Learner::value_apply_impl(hipStream_t st) {
-    if (gate_on()) return gated_apply(1, st);
-    const int64_t to = tr_offset(M_TRUNK), vo = tr_offset(M_VALUE);
-    const int opt = cfg_.optimizer, nadam = opt == CDRL_OPT_NADAM ? 8 : 0;
-    if (!frozen())
-        CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK],
-                             nullptr, nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
-    SegTable& s = seg_[M_VALUE];
-    CDRL_TRY(tensor_sqnorms(buf_.grads + vo, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part,
-                            s.sqnorms, st, hp_dev_, (frozen() ? 2 : 4 | 2) | nadam, true));       // (see policy_apply_impl)
-    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + vo, buf_.grads + vo, buf_.adam_m + vo, buf_.adam_v + vo, tr_size_[M_VALUE],
-                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, 1, st, s.chunk_part, 1));
-    return cfg_.train_stats > 0 ? stats_row(1, st) : 0;
+    return launch(caller, {KEY_VALUE_APPLY}, true, [&](hipStream_t st) -> int { return value_apply_impl(st); });
 }
 
 int Learner::predict(const float* image, const float* road, const float* vehicle, const float* navigation,
                      float* dist_out, float* value_out, float* dyn_out, hipStream_t caller) {
-    std::vector<uint64_t> key = {5, K(image), K(road), K(vehicle), K(navigation), K(dist_out), K(value_out), K(dyn_out)};
+    std::vector<uint64_t> key = {KEY_PREDICT, K(image), K(road), K(vehicle), K(navigation), K(dist_out), K(value_out), K(dyn_out)};
     return launch(caller, key, true, [&](hipStream_t st) -> int {
         return predict_impl(image, road, vehicle, navigation, dist_out, value_out, dyn_out, st);
     });

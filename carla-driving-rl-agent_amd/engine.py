@@ -425,35 +425,24 @@ class LearnerEngine:
         self._chk(nav, (c.B, c.T, c.navigation), 'state_navigation')
 
     def policy_forward_backward(self, batch, grad_scale=1.0):
-        c = self.cfg
-        img, road, veh, nav = self._states(batch)
-        self._check_states(img, road, veh, nav)
-        self._chk(batch['advantages'], (c.B,), 'advantages')
-        self._chk(batch['old_log_prob'], (c.B, c.A), 'old_log_prob')
-        self._chk(batch['u'], (c.B, c.A), 'u')
-        for k in ('speed', 'similarity'):
-            if batch[k].numel() != c.B:
-                raise ValueError(f'{k}: expected {c.B} elements')
-        pb = _lib.PolicyBatch(image=img.data_ptr(), road=road.data_ptr(), vehicle=veh.data_ptr(),
-                              navigation=nav.data_ptr(), advantages=batch['advantages'].data_ptr(),
-                              old_log_prob=batch['old_log_prob'].data_ptr(), speed=batch['speed'].data_ptr(),
-                              similarity=batch['similarity'].data_ptr(), u=batch['u'].data_ptr(),
-                              du_dalpha=batch['du_da'].data_ptr() if batch.get('du_da') is not None else None,
-                              du_dbeta=batch['du_db'].data_ptr() if batch.get('du_db') is not None else None)
+        pb = self._policy_batch(batch)
         _lib.check(self.lib.cdrl_learner_policy_forward_backward(self.h, C.byref(pb), float(grad_scale), self._stream()),
                    'policy_forward_backward')
 
-    def _policy_batch(self, batch, with_states=True):
+    def _policy_batch(self, batch, resample=False):
+        """The checked cdrl_policy_batch of a batch dict.  resample: the entry point draws u on the device and ignores the batch's,
+        so a batch without one gets a placeholder."""
         c = self.cfg
+        if resample and 'u' not in batch:
+            batch = dict(batch, u=batch['old_log_prob'])
         img, road, veh, nav = self._states(batch)
-        if with_states:
-            self._check_states(img, road, veh, nav)
+        self._check_states(img, road, veh, nav)
         self._chk(batch['advantages'], (c.B,), 'advantages')
-        self._chk(batch['old_log_prob'], (c.B, c.A), 'old_log_prob')
-        self._chk(batch['u'], (c.B, c.A), 'u')
-        for k in ('du_da', 'du_db'):
-            if batch.get(k) is not None:
-                self._chk(batch[k], (c.B, c.A), k)
+        for k in ('old_log_prob', 'u', 'du_da', 'du_db'):
+            self._chk(batch.get(k), (c.B, c.A), k)
+        for k in ('speed', 'similarity'):
+            if batch[k].numel() != c.B:
+                raise ValueError(f'{k}: expected {c.B} elements')
         return _lib.PolicyBatch(image=img.data_ptr(), road=road.data_ptr(), vehicle=veh.data_ptr(),
                                 navigation=nav.data_ptr(), advantages=batch['advantages'].data_ptr(),
                                 old_log_prob=batch['old_log_prob'].data_ptr(), speed=batch['speed'].data_ptr(),
@@ -477,9 +466,7 @@ class LearnerEngine:
 
     def policy_forward_backward_resample(self, batch, seed: int, offset: int, grad_scale=1.0):
         """F8-faithful step with the Beta re-sampling done on the device (no torch.distributions)."""
-        b = dict(batch)
-        b.setdefault('u', batch['old_log_prob'])       # placeholder; ignored by the entry point
-        pb = self._policy_batch(b)
+        pb = self._policy_batch(batch, resample=True)
         _lib.check(self.lib.cdrl_learner_policy_forward_backward_resample(self.h, C.byref(pb), int(seed), int(offset),
                                                                          float(grad_scale), self._stream()),
                    'policy_forward_backward_resample')
@@ -503,13 +490,9 @@ class LearnerEngine:
 
     # Joint policy + value update (opt-in, include/cdrl.h): one trunk forward and one trunk backward per minibatch.  `batch` is the
     # policy batch dict plus 'returns' (B, 2); the value loss takes the batch's speed / similarity.
-    def _joint_batch(self, batch):
-        c = self.cfg
-        self._chk(batch['returns'], (c.B, 2), 'returns')
-        for k in ('speed', 'similarity'):
-            if batch[k].numel() != c.B:
-                raise ValueError(f'{k}: expected {c.B} elements')
-        return self._policy_batch(batch)
+    def _joint_batch(self, batch, resample=False):
+        self._chk(batch['returns'], (self.cfg.B, 2), 'returns')
+        return self._policy_batch(batch, resample)
 
     def joint_forward_backward(self, batch, grad_scale=1.0):
         """Stored-action / injected-Jacobian policy loss + value loss on ONE train-mode trunk forward, one trunk backward."""
@@ -519,9 +502,7 @@ class LearnerEngine:
 
     def joint_forward_backward_resample(self, batch, seed: int, offset: int, grad_scale=1.0):
         """The joint pass with the Beta re-sampling done on the device (as policy_forward_backward_resample)."""
-        b = dict(batch)
-        b.setdefault('u', batch['old_log_prob'])       # placeholder; ignored by the entry point
-        pb = self._joint_batch(b)
+        pb = self._joint_batch(batch, resample=True)
         _lib.check(self.lib.cdrl_learner_joint_forward_backward_resample(self.h, C.byref(pb), _lib.ptr(batch['returns']), int(seed),
                                                                          int(offset), float(grad_scale), self._stream()),
                    'joint_forward_backward_resample')

@@ -39,8 +39,8 @@ class DataParallelLearner:
         t_off, t_n = engine.region('trunk', True)
         v_off, v_n = engine.region('value', True)
         assert p_off == 0 and t_off == p_n and v_off == p_n + t_n, 'gradient arena must be [policy|trunk|value]'
-        self._policy_slice = (0, p_n) if self.frozen else (0, p_n + t_n)
-        self._value_slice = (t_off + t_n, t_off + t_n + v_n) if self.frozen else (t_off, t_off + t_n + v_n)
+        self._policy_slices = [(0, p_n) if self.frozen else (0, p_n + t_n)]
+        self._value_slices = [(t_off + t_n, t_off + t_n + v_n) if self.frozen else (t_off, t_off + t_n + v_n)]
         # Overlap: the trunk's tail tensors (everything behind the image tower: feature nets, GRUs, concat
         # BN + Dense) sit at the END of the trunk region and are final ~1 ms into the backward, like the head's; they go out
         # as early buckets on a communication stream that the engine releases at that point, and only the tower's slice
@@ -64,6 +64,9 @@ class DataParallelLearner:
         # communication stream the whole arena goes out as one slice -- frozen trunk: the two head slices, nothing of the trunk's
         self._joint_early = [(0, p_n), (t_off + tower_n, t_off + t_n + v_n)]
         self._joint_slices = [(0, p_n), (t_off + t_n, t_off + t_n + v_n)] if self.frozen else [(0, p_n + t_n + v_n)]
+        # per pass kind: (early group on the communication stream, slices of the whole pass without one)
+        self._buckets = dict(policy=(self._policy_early, self._policy_slices), value=(self._value_early, self._value_slices),
+                             joint=(self._joint_early, self._joint_slices))
         self._comm = None
         if not self.frozen and self.use_comm_stream(overlap, self.world, self.force, tower_n, t_n,
                                 bool(getattr(engine, 'device', None)) and hasattr(engine, 'set_comm_stream') and engine.grads.is_cuda):
@@ -88,16 +91,16 @@ class DataParallelLearner:
 
     def reduce_policy_gradients(self):
         """All-reduce of the policy pass's gradients [policy | trunk]; call after policy_forward_backward has been enqueued."""
-        self._reduce_gradients(self._policy_early, self._policy_slice)
+        self._reduce_gradients('policy')
 
     def reduce_value_gradients(self):
-        self._reduce_gradients(self._value_early, self._value_slice)
+        self._reduce_gradients('value')
 
     def reduce_joint_gradients(self):
         """All-reduce of a joint pass's gradients (all three lists); call after joint_forward_backward has been enqueued."""
-        self._reduce_gradients(self._joint_early, self._joint_slices)
+        self._reduce_gradients('joint')
 
-    def _reduce_gradients(self, early, full, with_stats=False):
+    def _reduce_gradients(self, kind, with_stats=False):
         """Gradient all-reduce of one pass, issued after the pass has been ENQUEUED: early buckets on the communication
         stream (released by the engine in the middle of the backward), the tower slice on the current stream.
         with_stats: the BatchNorm moving statistics ride in the same early group (they are final once the pass's FORWARD has run,
@@ -106,12 +109,13 @@ class DataParallelLearner:
         if self.world == 1 and not self.force:
             return False
         g = self.engine.grads
+        early, full = self._buckets[kind]
         if self._comm is None:
-            if isinstance(full, list):      # several slices (joint step on a frozen trunk): one coalesced group
-                for w in self._all_reduce_many(g, full, dist.ReduceOp.SUM):
-                    w.wait()
+            if len(full) == 1:
+                dist.all_reduce(g[full[0][0]:full[0][1]], op=dist.ReduceOp.SUM, group=self.group)
                 return False
-            dist.all_reduce(g[full[0]:full[1]], op=dist.ReduceOp.SUM, group=self.group)
+            for w in self._all_reduce_many(g, full, dist.ReduceOp.SUM):     # (joint step on a frozen trunk): one coalesced group
+                w.wait()
             return False
         works = []
         stats = with_stats and self.sync_bn_stats and self._nccl()
@@ -166,49 +170,46 @@ class DataParallelLearner:
             dist.broadcast(self.engine.adam_m, src=src, group=self.group)
             dist.broadcast(self.engine.adam_v, src=src, group=self.group)
 
-    def policy_step(self, batch, resample=None):
-        """resample=(seed, offset): the reference-faithful loss on a fresh Beta sample of the new policy drawn on the device
-        (each rank passes its own Philox offset); None: stored-action loss (batch['u'])."""
-        e = self.engine
-        if resample is not None:
-            e.policy_forward_backward_resample(batch, seed=resample[0], offset=resample[1], grad_scale=1.0 / self.world)
+    def _pass(self, kind, batch, resample=None):
+        """The `kind` ('policy', 'value', 'joint') pass with grad_scale = 1 / world.  resample=(seed, offset): the reference-faithful
+        policy loss on a fresh Beta sample of the new policy drawn on the device (each rank passes its own Philox offset); None:
+        stored-action loss (batch['u'])."""
+        if resample is None:
+            getattr(self.engine, f'{kind}_forward_backward')(batch, grad_scale=1.0 / self.world)
         else:
-            e.policy_forward_backward(batch, grad_scale=1.0 / self.world)
-        self._reduce_gradients(self._policy_early, self._policy_slice)
-        e.policy_apply()
+            getattr(self.engine, f'{kind}_forward_backward_resample')(batch, seed=resample[0], offset=resample[1],
+                                                                      grad_scale=1.0 / self.world)
+
+    def policy_step(self, batch, resample=None):
+        """resample: as _pass."""
+        self._pass('policy', batch, resample)
+        self._reduce_gradients('policy')
+        self.engine.policy_apply()
 
     def value_step(self, batch, with_stats=False):
         """with_stats: average the BatchNorm moving statistics in this pass's early group (update_step: the value pass is the last
         forward of an update-step).  Returns True when that happened (no separate sync_moving_statistics() needed)."""
-        e = self.engine
-        e.value_forward_backward(batch, grad_scale=1.0 / self.world)
-        done = self._reduce_gradients(self._value_early, self._value_slice, with_stats=with_stats)
-        e.value_apply()
+        self._pass('value', batch)
+        done = self._reduce_gradients('value', with_stats=with_stats)
+        self.engine.value_apply()
         return done
 
     def joint_step(self, batch, resample=None, with_stats=True):
         """One joint policy + value minibatch step (engine.joint_forward_backward: one trunk forward and backward, one trunk optimizer
         step): the pass with grad_scale = 1 / world, ONE gradient reduce over all three lists, joint_apply.  `batch`: the policy batch
-        plus 'returns'; resample as in policy_step.  The moving statistics ride in the early group (with_stats) or are averaged by
+        plus 'returns'; resample as in _pass.  The moving statistics ride in the early group (with_stats) or are averaged by
         sync_moving_statistics() behind the step."""
         e = self.engine
         if self.world == 1 and not self.force:
             with e.sequence():      # no collective between the two calls
-                self._joint_pass(batch, resample)
+                self._pass('joint', batch, resample)
                 e.joint_apply()
             return
-        self._joint_pass(batch, resample)
-        done = self._reduce_gradients(self._joint_early, self._joint_slices, with_stats=with_stats)
+        self._pass('joint', batch, resample)
+        done = self._reduce_gradients('joint', with_stats=with_stats)
         e.joint_apply()
         if with_stats and not done:
             self.sync_moving_statistics()
-
-    def _joint_pass(self, batch, resample):
-        e = self.engine
-        if resample is not None:
-            e.joint_forward_backward_resample(batch, seed=resample[0], offset=resample[1], grad_scale=1.0 / self.world)
-        else:
-            e.joint_forward_backward(batch, grad_scale=1.0 / self.world)
 
     def sync_moving_statistics(self):
         """Average of the BatchNorm moving statistics over the ranks: both state slices in ONE collective.  RCCL: a coalesced AVG

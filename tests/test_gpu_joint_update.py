@@ -153,6 +153,23 @@ def test_joint_heads_match_separate_passes(compute, stored):
     assert torch.equal(a.params[st], v.params[st])
 
 
+def test_policy_split_form_matches_the_one_call_pass():
+    """policy_forward then policy_backward (the split form of the C ABI) against policy_forward_backward on the stored-action batch:
+    the same ops in the same order, so gradients, metrics and moving statistics are equal bit for bit."""
+    x, y = _engines(2, batch=4)
+    dpol, _, _ = _batches(batch=4)
+    batch = dict(dpol, du_da=None, du_db=None)
+    x.policy_forward_backward(batch)
+    y.policy_forward(batch['states'])
+    y.policy_backward(batch)
+    torch.cuda.synchronize()
+    for model in ('policy', 'trunk'):
+        assert torch.equal(x.grads[_slice(x, model)], y.grads[_slice(y, model)]), model
+        assert torch.equal(x.params[_slice(x, model, False)], y.params[_slice(y, model, False)]), f'{model} moving statistics'
+    assert torch.equal(x.buffer(_lib.BUF_METRICS_P), y.buffer(_lib.BUF_METRICS_P))
+    assert float(x.grads[_slice(x, 'trunk')].abs().max()) > 0.0
+
+
 # ---------------------------------------------------------------------------------------------- 3. trunk gradient is the sum
 def test_joint_trunk_gradient_is_the_sum():
     """Per trainable trunk tensor max|g_A - (g_P + g_V)| / (max|g_P| + max|g_V|), the sum formed in float64.  Bound: twice the
