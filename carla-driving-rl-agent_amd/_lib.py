@@ -78,6 +78,11 @@ class ValueBatch(C.Structure):
     _fields_ = [(n, _fp) for n in ('image', 'road', 'vehicle', 'navigation', 'returns', 'speed', 'similarity')]
 
 
+class CloneBatch(C.Structure):
+    """cdrl_clone_batch (include/cdrl.h): states, expert actions, optional weights / targets / returns."""
+    _fields_ = [(n, _fp) for n in ('image', 'road', 'vehicle', 'navigation', 'u', 'weight', 'speed', 'similarity', 'returns')]
+
+
 class View(C.Structure):
     """cdrl_view (include/cdrl.h): element (r, c) at p[r * ld + coff + c], counted in elements of the tensor's type."""
     _fields_ = [('p', C.c_void_p), ('ld', C.c_int32), ('coff', C.c_int32)]
@@ -157,6 +162,7 @@ PROTOTYPES = {
     'cdrl_learner_joint_forward_backward': (_i, [_L, C.POINTER(PolicyBatch), _fp, _f, _fp]),
     'cdrl_learner_joint_forward_backward_resample': (_i, [_L, C.POINTER(PolicyBatch), _fp, C.c_uint64, C.c_uint64, _f, _fp]),
     'cdrl_learner_joint_apply': (_i, [_L, _fp]),
+    'cdrl_learner_clone_forward_backward': (_i, [_L, C.POINTER(CloneBatch), _f, _f, _f, _f, _fp]),
     'cdrl_learner_sequence_begin': (_i, [_L, _fp]),
     'cdrl_learner_sequence_end': (_i, [_L, _fp]),
     'cdrl_learner_value_forward_backward': (_i, [_L, C.POINTER(ValueBatch), _f, _fp]),
@@ -230,6 +236,7 @@ PROTOTYPES = {
     'cdrl_bn_inference_stats_table_bytes': (_i64, [_i]),
     'cdrl_bn_inference_stats': (_i, [_i, _pp, _pp, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_i), _fp, _fp]),
     'cdrl_bn_train_bwd_pooled': (_i, [_fp, _fp, _i, _i, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'cdrl_beta_clone_loss': (_i, [_fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _f, _fp, _fp, _fp, _fp]),
     'cdrl_beta_ppo_loss': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _f, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_value_loss': (_i, [_fp, _fp, _fp, _fp, _i, _f, _f, _fp, _fp, _fp, _fp]),
 }

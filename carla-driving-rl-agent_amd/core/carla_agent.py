@@ -421,6 +421,33 @@ class CARLAgent(PPOAgent):
         self._step_engine.joint_apply()     # trunk step ONCE (not when frozen) -> old_policy <- policy -> policy head -> value head
         return gradients
 
+    # -- imitation (PPOAgent.imitate) ----------------------------------------------------
+    STATE_KEYS = ('state_image', 'state_road', 'state_vehicle', 'state_navigation')
+
+    def imitation_state_keys(self) -> list:
+        return list(self.STATE_KEYS)
+
+    def stacks_time(self) -> bool:
+        return True
+
+    def clone_minibatch(self, batch, policy_weight, value_weight, aux_weight):
+        eng = self.network.engine_for(batch['u'].shape[0])          # (a ragged last minibatch: its own engine, as in update())
+        b = dict(batch, states={k: batch['states'][k] for k in self.STATE_KEYS})
+        eng.clone_step(eng.stage(b, 'clone'), policy_weight, value_weight, aux_weight)
+        return eng
+
+    def imitation_learning(self, alpha=0.5, beta=0.5, clip_grad=1.0, lr=1e-3, polyak=None, epochs=1, shuffle_data=True,
+                           traces_dir=None, **kw):
+        """The supervised stage of the reference's curriculum (Stage.imitation_learning, core/learning.py:180-181, calls this name
+        with these keywords; the reference never defines it): imitate() with alpha as the policy weight, beta as the value weight,
+        clip_grad as every optimizer's clip threshold and lr as every optimizer's learning rate.  polyak: fixed when the learner
+        engines are created (CARLAgent(polyak=...)), so any other value is refused."""
+        if polyak is not None and float(polyak) != float(self.polyak_coeff):
+            raise ValueError(f'imitation_learning(polyak={polyak}): the agent was created with polyak={self.polyak_coeff}, which its '
+                             f'learner engines are built with; create the agent with CARLAgent(polyak={polyak}) instead')
+        return self.imitate(epochs=epochs, shuffle_data=shuffle_data, traces_dir=traces_dir, policy_weight=alpha, value_weight=beta,
+                            clip_norm=clip_grad, lr=lr, **kw)
+
     # -- rollout helpers ------------------------------------------------------------------------------
     def get_memory(self):
         return CARLAMemory(state_spec=self.state_spec, num_actions=self.num_actions, time_horizon=self.env.time_horizon,

@@ -571,6 +571,29 @@ int cdrl_learner_joint_apply(cdrl_learner* l, void* stream) {
     return l->impl->joint_apply(S(stream));
 }
 
+int cdrl_learner_clone_forward_backward(cdrl_learner* l, const cdrl_clone_batch* b, float policy_weight, float value_weight,
+                                        float aux_weight, float grad_scale, void* stream) {
+    CHECK_L(l);
+    if (!b) {
+        cdrl::set_error("clone batch: null batch");
+        return -1;
+    }
+    if (!b->u) {
+        cdrl::set_error("clone batch: null tensor (u)");
+        return -1;
+    }
+    if (!b->speed != !b->similarity) {
+        cdrl::set_error("clone batch: speed and similarity come together (both, or both null)");
+        return -1;
+    }
+    if (b->returns && !b->speed) {
+        cdrl::set_error("clone batch: returns need the speed and similarity targets (the value loss reads them)");
+        return -1;
+    }
+    const CloneBatch cb{b->image, b->road, b->vehicle, b->navigation, b->u, b->weight, b->speed, b->similarity, b->returns};
+    return l->impl->clone_forward_backward(cb, policy_weight, value_weight, aux_weight, grad_scale, S(stream));
+}
+
 int cdrl_learner_update_old_policy(cdrl_learner* l, void* stream) {
     CHECK_L(l);
     return l->impl->update_old_policy(S(stream));
@@ -1532,6 +1555,16 @@ int cdrl_beta_ppo_loss(const float* lin, const float* adv, const float* old_logp
     a.u = u; a.du_da = du_da; a.du_db = du_db; a.hp = hp_scratch16; a.dlin = dlin; a.metrics = metrics; a.aux = aux;
     a.B = B; a.A = A; a.inv_world = grad_scale;
     return policy_loss(a, S(stream));
+}
+
+int cdrl_beta_clone_loss(const float* lin, const float* u, const float* weight, const float* speed, const float* similarity,
+                         float entropy_coef, float aux_weight, int B, int A, float grad_scale, float* dlin, float* metrics, float* aux,
+                         void* stream) {
+    CloneLossArgs a;
+    a.lin = lin; a.u = u; a.weight = weight; a.speed = speed; a.similarity = similarity; a.hp = nullptr;
+    a.entropy_coef = entropy_coef; a.aux_weight = aux_weight; a.dlin = dlin; a.metrics = metrics; a.aux = aux;
+    a.B = B; a.A = A; a.grad_scale = grad_scale;
+    return clone_loss(a, S(stream));
 }
 
 int cdrl_value_loss(const float* lin, const float* returns, const float* speed, const float* similarity, int B,

@@ -496,6 +496,21 @@ struct PolicyLossArgs {
     float inv_world;         // gradient scale for data-parallel averaging (1/world_size)
 };
 int policy_loss(const PolicyLossArgs& a, hipStream_t st);
+struct CloneLossArgs {       // behaviour cloning: weighted Beta negative log-likelihood of expert actions
+    const float* lin;        // [B][2A+2] as PolicyLossArgs::lin
+    const float* u;          // [B][A] expert action in the unit interval
+    const float* weight;     // [B] or nullptr (= 1)
+    const float* speed;      // [B] or nullptr; speed and similarity come together
+    const float* similarity; // [B] or nullptr
+    const float* hp;         // device hyper-parameter block (DevHP) whose entropy_coef is read, or nullptr: entropy_coef below
+    float entropy_coef, aux_weight;
+    float* dlin;             // [B][2A+2]
+    float* metrics;          // [16]; 0..7 written: total, clone, entropy, speed, similarity, mean weight, mean logp, mode error
+    float* aux;              // optional [B][4A]: alpha, beta, log_prob, entropy
+    int B, A;
+    float grad_scale;
+};
+int clone_loss(const CloneLossArgs& a, hipStream_t st);
 struct ValueLossArgs {
     const float* lin;        // [B][4]: base_pre, exp_pre, speed_pre, similarity_pre
     const float* returns;    // [B][2]

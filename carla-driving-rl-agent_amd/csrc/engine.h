@@ -66,6 +66,10 @@ struct ValueBatch {
     const float *image, *road, *vehicle, *navigation;
     const float *returns, *speed, *similarity;
 };
+struct CloneBatch {                                         // behaviour cloning: expert actions in place of adv / old_logp
+    const float *image, *road, *vehicle, *navigation;
+    const float *u, *weight, *speed, *similarity, *returns; // weight, (speed, similarity), returns: optional
+};
 
 struct Op {
     std::function<int(hipStream_t, int)> fwd;
@@ -137,6 +141,11 @@ public:
     // head from its own list; CDRL_CLIP_GLOBAL clips each of the three lists once, by its own threshold.  Train stats: the policy
     // row, then the value row, both with the norms of the one joint trunk gradient.
     int joint_apply(hipStream_t st);
+    // Behaviour-cloning pass: pass_forward as it is, then the clone loss in the place of the policy loss; with
+    // returns the value loss and the joint tail as in a joint pass (and its B <= 2048 limit).  policy_weight / value_weight scale the
+    // two losses' dlin (through their grad_scale, next to inv_world), nothing else.  Followed by policy_apply, or joint_apply with returns.
+    int clone_forward_backward(const CloneBatch& b, float policy_weight, float value_weight, float aux_weight, float inv_world,
+                               hipStream_t st);
     int update_old_policy(hipStream_t st);
     // inference: trunk (moving stats) + old_policy + value heads
     int predict(const float* image, const float* road, const float* vehicle, const float* navigation,
@@ -391,13 +400,18 @@ private:
         float inv_world;
         bool resample = false;              // u, du_da, du_db: drawn on the device from the new policy with (seed, offset), not the batch's
         uint64_t seed = 0, offset = 0;
-        bool joint() const { return policy && returns; }
+        // clone mode (policy is null): the clone loss on (clone_u, clone_w) stands where the policy loss stands
+        const float *clone_u = nullptr, *clone_w = nullptr;
+        float policy_weight = 1.0f, value_weight = 1.0f, aux_weight = 1.0f;
+        bool head() const { return policy || clone_u; }      // the policy head takes part
+        bool joint() const { return head() && returns; }
     };
     static PassSpec policy_pass(const PolicyBatch& b, const float* returns, float inv_world, bool resample = false, uint64_t seed = 0,
                                 uint64_t offset = 0) {
         return {b.image, b.road, b.vehicle, b.navigation, b.speed, b.similarity, &b, returns, inv_world, resample, seed, offset};
     }
     PolicyLossArgs policy_loss_args(const PassSpec& s) const;
+    CloneLossArgs clone_loss_args(const PassSpec& s) const;
     ValueLossArgs value_loss_args(const PassSpec& s) const;
     // forward half: trunk, the heads present (dist: policy_dist behind the policy head; re-sampling: and the Beta draw, both in
     // front of the value head); backward half: per head its loss and backward, joint: bn_small_bwd_pair, then the trunk

@@ -1944,7 +1944,8 @@ static inline uint64_t Kf(float f) {
 }
 // step kind: the first word of a graph key
 enum KeyKind : uint64_t {
-    KEY_POLICY_PASS = 1, KEY_VALUE_PASS = 2, KEY_POLICY_APPLY = 3, KEY_VALUE_APPLY = 4, KEY_PREDICT = 5, KEY_JOINT_PASS = 6, KEY_JOINT_APPLY = 7
+    KEY_POLICY_PASS = 1, KEY_VALUE_PASS = 2, KEY_POLICY_APPLY = 3, KEY_VALUE_APPLY = 4, KEY_PREDICT = 5, KEY_JOINT_PASS = 6, KEY_JOINT_APPLY = 7,
+    KEY_CLONE_PASS = 8
 };
 
 PolicyLossArgs Learner::policy_loss_args(const PassSpec& s) const {
@@ -1967,6 +1968,25 @@ PolicyLossArgs Learner::policy_loss_args(const PassSpec& s) const {
     return a;
 }
 
+CloneLossArgs Learner::clone_loss_args(const PassSpec& s) const {
+    CloneLossArgs a;
+    a.lin = lin_p_.p;
+    a.u = s.clone_u;
+    a.weight = s.clone_w;
+    a.speed = s.speed;
+    a.similarity = s.similarity;
+    a.hp = reinterpret_cast<const float*>(hp_dev_);
+    a.entropy_coef = 0.0f;
+    a.aux_weight = s.aux_weight;
+    a.dlin = lin_p_.g;
+    a.metrics = metrics_p_;
+    a.aux = aux_p_;
+    a.B = cfg_.B;
+    a.A = cfg_.A;
+    a.grad_scale = s.inv_world * s.policy_weight;
+    return a;
+}
+
 ValueLossArgs Learner::value_loss_args(const PassSpec& s) const {
     ValueLossArgs a;
     a.lin = lin_v_.p;
@@ -1978,14 +1998,14 @@ ValueLossArgs Learner::value_loss_args(const PassSpec& s) const {
     a.values = aux_v_;
     a.B = cfg_.B;
     a.exp_scale = cfg_.exp_scale;
-    a.inv_world = s.inv_world;
+    a.inv_world = s.inv_world * s.value_weight;         // (1 outside a clone pass: the product is exact)
     return a;
 }
 
 int Learner::pass_forward(const PassSpec& s, bool dist, hipStream_t st) {
     CDRL_TRY(set_inputs(s.image, s.road, s.vehicle, s.navigation));
     CDRL_TRY(run_trunk_fwd(st, 1));
-    if (s.policy) CDRL_TRY(run_fwd(policy_ops_, st, 1));
+    if (s.head()) CDRL_TRY(run_fwd(policy_ops_, st, 1));
     const int A = cfg_.A;
     // alpha, beta (+ mean, std) of the CURRENT policy for the Beta re-sampling
     if (dist || s.resample) CDRL_TRY(policy_dist(lin_p_.p, aux_p_, cfg_.B, A, st));
@@ -1998,8 +2018,8 @@ int Learner::pass_backward(const PassSpec& s, hipStream_t st) {
     // joint: each head's backward stops in front of its bn0; one launch then finishes both bn0 over the trunk output -- their own
     // gradients, and dyn_.g = d(policy loss)/d(dynamics) + d(value loss)/d(dynamics)
     const HeadBn0 &p0 = bn0_[0], &v0 = bn0_[1];
-    if (s.policy) {
-        CDRL_TRY(policy_loss(policy_loss_args(s), st));
+    if (s.head()) {
+        CDRL_TRY(s.policy ? policy_loss(policy_loss_args(s), st) : clone_loss(clone_loss_args(s), st));
         CDRL_TRY(run_bwd(policy_ops_, st, s.joint() ? p0.op + 1 : 0));
     }
     if (s.returns) {
@@ -2037,9 +2057,10 @@ int Learner::run_pass(const PassSpec& s, hipStream_t caller, bool fwd, bool bwd)
     const bool graphable = fwd && bwd && !s.resample;
     std::vector<uint64_t> key;
     if (graphable) {
-        key = {s.joint() ? KEY_JOINT_PASS : s.policy ? KEY_POLICY_PASS : KEY_VALUE_PASS,
+        key = {s.clone_u ? KEY_CLONE_PASS : s.joint() ? KEY_JOINT_PASS : s.policy ? KEY_POLICY_PASS : KEY_VALUE_PASS,
                K(s.image), K(s.road), K(s.vehicle), K(s.navigation), K(s.speed), K(s.similarity), K(s.returns), Kf(s.inv_world)};
         if (const PolicyBatch* b = s.policy) key.insert(key.end(), {K(b->adv), K(b->old_logp), K(b->u), K(b->du_da), K(b->du_db)});
+        if (s.clone_u) key.insert(key.end(), {K(s.clone_u), K(s.clone_w), Kf(s.policy_weight), Kf(s.value_weight), Kf(s.aux_weight)});
     }
     return launch(caller, key, graphable, [&](hipStream_t st) -> int {
         if (fwd) CDRL_TRY(pass_forward(s, !bwd, st));       // (the forward alone: its caller samples from alpha, beta)
@@ -2077,6 +2098,17 @@ int Learner::joint_forward_backward(const PolicyBatch& b, const float* returns, 
 int Learner::joint_forward_backward_resample(const PolicyBatch& b, const float* returns, uint64_t seed, uint64_t offset, float inv_world,
                                              hipStream_t caller) {
     return run_pass(policy_pass(b, returns, inv_world, true, seed, offset), caller);
+}
+
+int Learner::clone_forward_backward(const CloneBatch& b, float policy_weight, float value_weight, float aux_weight, float inv_world,
+                                    hipStream_t caller) {
+    PassSpec s{b.image, b.road, b.vehicle, b.navigation, b.speed, b.similarity, nullptr, b.returns, inv_world};
+    s.clone_u = b.u;
+    s.clone_w = b.weight;
+    s.policy_weight = policy_weight;
+    s.value_weight = value_weight;
+    s.aux_weight = aux_weight;
+    return run_pass(s, caller);
 }
 
 int Learner::joint_apply(hipStream_t caller) {

@@ -6,6 +6,8 @@
 //                0.5*MSE aux speed / similarity heads.  The Beta sample u and (optionally) its
 //                pathwise Jacobians are inputs (F8 / Appendix C-1).
 //  value_loss  : CARLAgent.value_objective (core/carla_agent.py:469-486).
+//  clone_loss  : behaviour cloning (no reference counterpart): weighted negative Beta log-likelihood of an expert
+//                action, with the entropy and auxiliary terms of policy_loss.
 // One workgroup, wavefront/LDS reductions in double: B is a few hundred rows, the kernels are
 // latency-bound, so everything transcendental (lgamma / digamma / trigamma) runs in double.
 #include "cdrl_kernels.h"
@@ -149,6 +151,100 @@ int policy_loss(const PolicyLossArgs& a, hipStream_t st) {
         return -1;
     }
     hipLaunchKernelGGL(policy_loss_kernel, dim3(1), dim3(256), 0, st, a);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
+// Behaviour cloning: weighted negative log-likelihood of the expert action under Beta(alpha, beta), the entropy
+// bonus and the auxiliary heads of the policy objective.  Same structure as policy_loss_kernel: one workgroup, row loop, double
+// transcendentals, one double block reduction, one float rounding per output.  No gradient flows through the clipped action.
+__global__ void __launch_bounds__(256) clone_loss_kernel(CloneLossArgs p) {
+    __shared__ double sm[7 * 256];
+    const double cent = p.hp ? (double)reinterpret_cast<const DevHP*>(p.hp)->entropy_coef : (double)p.entropy_coef;
+    const double aw = (double)p.aux_weight;
+    const int B = p.B, A = p.A, L = 2 * A + 2;
+    const double invB = 1.0 / (double)B, invA = 1.0 / (double)A;
+    const double gs = (double)p.grad_scale;
+    const bool targets = p.speed && p.similarity;
+    double acc[7] = {0, 0, 0, 0, 0, 0, 0};   // weighted nll, entropy, speed sq, sim sq, weight, logp, mode error
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        const float* lin = p.lin + (int64_t)b * L;
+        float* dlin = p.dlin + (int64_t)b * L;
+        const double w = p.weight ? (double)p.weight[b] : 1.0;
+        const double dL_dlogp = -invB * w * invA, dL_dH = -cent * invB * invA;
+        double nll = 0.0;
+        for (int a = 0; a < A; ++a) {
+            const double la = (double)lin[a], lb = (double)lin[A + a];
+            const double al = softplus_d(la) + 1.01, be = softplus_d(lb) + 1.01;
+            const float uf = p.u[(int64_t)b * A + a];
+            const double x = (double)fminf(fmaxf(uf, F32_EPS), 1.0f - F32_EPS);      // _clip_actions
+            const double lx = log(x), l1x = log1p(-x);
+            const double lnB = lgamma(al) + lgamma(be) - lgamma(al + be);
+            const double pa = digamma_d(al), pb = digamma_d(be), pab = digamma_d(al + be);
+            const double logp = (al - 1.0) * lx + (be - 1.0) * l1x - lnB;
+            const double ent = lnB - (al - 1.0) * pa - (be - 1.0) * pb + (al + be - 2.0) * pab;
+            const double tab = trigamma_d(al + be);
+            const double dH_da = -(al - 1.0) * trigamma_d(al) + (al + be - 2.0) * tab;
+            const double dH_db = -(be - 1.0) * trigamma_d(be) + (al + be - 2.0) * tab;
+            dlin[a] = (float)(gs * (dL_dlogp * (lx - pa + pab) + dL_dH * dH_da) * sigmoid_d(la));
+            dlin[A + a] = (float)(gs * (dL_dlogp * (l1x - pb + pab) + dL_dH * dH_db) * sigmoid_d(lb));
+            nll -= logp;
+            acc[1] += ent;
+            acc[5] += logp;
+            acc[6] += fabs((al - 1.0) / (al + be - 2.0) - x);       // alpha, beta >= 1.01: the mode exists
+            if (p.aux) {
+                float* ax = p.aux + (int64_t)b * 4 * A;
+                ax[a] = (float)al;
+                ax[A + a] = (float)be;
+                ax[2 * A + a] = (float)logp;
+                ax[3 * A + a] = (float)ent;
+            }
+        }
+        acc[0] += w * nll * invA;
+        acc[4] += w;
+        if (targets) {
+            const double sim = tanh((double)lin[2 * A]);
+            const double sgs = sigmoid_d((double)lin[2 * A + 1]);
+            const double dsim = sim - (double)p.similarity[b], dspd = 2.0 * sgs - (double)p.speed[b];
+            acc[3] += dsim * dsim;
+            acc[2] += dspd * dspd;
+            dlin[2 * A] = (float)(gs * aw * invB * dsim * (1.0 - sim * sim));
+            dlin[2 * A + 1] = (float)(gs * aw * invB * dspd * 2.0 * sgs * (1.0 - sgs));
+        } else {
+            dlin[2 * A] = 0.0f;
+            dlin[2 * A + 1] = 0.0f;
+        }
+    }
+    block_reduce<7>(acc, sm);
+    if (threadIdx.x == 0) {
+        const double clone = acc[0] * invB;
+        const double entropy = acc[1] * invB * invA;
+        const double speed_loss = 0.5 * acc[2] * invB, sim_loss = 0.5 * acc[3] * invB;
+        p.metrics[0] = (float)(clone - cent * entropy + aw * (speed_loss + sim_loss));
+        p.metrics[1] = (float)clone;
+        p.metrics[2] = (float)entropy;
+        p.metrics[3] = (float)speed_loss;
+        p.metrics[4] = (float)sim_loss;
+        p.metrics[5] = (float)(acc[4] * invB);
+        p.metrics[6] = (float)(acc[5] * invB * invA);
+        p.metrics[7] = (float)(acc[6] * invB * invA);
+    }
+}
+
+int clone_loss(const CloneLossArgs& a, hipStream_t st) {
+    if (a.A < 1 || a.A > 8) {
+        set_error("clone_loss: num_actions %d outside 1..8 unsupported", a.A);
+        return -1;
+    }
+    if (a.B < 1 || !a.lin || !a.u || !a.dlin || !a.metrics) {
+        set_error("clone_loss: B = %d rows or a null lin / u / dlin / metrics", a.B);
+        return -1;
+    }
+    if (!a.speed != !a.similarity) {
+        set_error("clone_loss: speed and similarity targets come together (both, or both null)");
+        return -1;
+    }
+    hipLaunchKernelGGL(clone_loss_kernel, dim3(1), dim3(256), 0, st, a);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

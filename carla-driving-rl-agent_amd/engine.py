@@ -516,6 +516,46 @@ class LearnerEngine:
             self.joint_forward_backward(batch)
             self.joint_apply()
 
+    # Behaviour cloning (include/cdrl.h).  `batch`: states, 'u' (B, A) expert actions in the unit interval, optional
+    # 'weight' (B), optional 'speed' / 'similarity' (B each, together), optional 'returns' (B, 2; needs the two targets).
+    def _clone_batch(self, batch):
+        c = self.cfg
+        img, road, veh, nav = self._states(batch)
+        self._check_states(img, road, veh, nav)
+        if batch.get('u') is None:
+            raise ValueError('u: a clone batch needs the expert actions, shape (B, A) in the unit interval')
+        self._chk(batch['u'], (c.B, c.A), 'u')
+        self._chk(batch.get('weight'), (c.B,), 'weight')
+        self._chk(batch.get('returns'), (c.B, 2), 'returns')
+        targets = [batch.get(k) for k in ('speed', 'similarity')]
+        if (targets[0] is None) != (targets[1] is None):
+            raise ValueError('speed and similarity targets come together: give both, or neither')
+        if batch.get('returns') is not None and targets[0] is None:
+            raise ValueError('returns: the value loss needs the speed and similarity targets as well')
+        for k, t in zip(('speed', 'similarity'), targets):
+            self._chk(t, (c.B,), k)
+        p = lambda t: t.data_ptr() if t is not None else None
+        return _lib.CloneBatch(image=img.data_ptr(), road=road.data_ptr(), vehicle=veh.data_ptr(), navigation=nav.data_ptr(),
+                               u=batch['u'].data_ptr(), weight=p(batch.get('weight')), speed=p(targets[0]), similarity=p(targets[1]),
+                               returns=p(batch.get('returns')))
+
+    def clone_forward_backward(self, batch, policy_weight=1.0, value_weight=0.0, aux_weight=1.0, grad_scale=1.0):
+        """Behaviour-cloning pass: the clone loss in the place of the policy loss; with batch['returns'] also the value loss, on one
+        trunk forward and backward like the joint pass.  The weights scale gradients only (metrics stay unscaled)."""
+        cb = self._clone_batch(batch)
+        _lib.check(self.lib.cdrl_learner_clone_forward_backward(self.h, C.byref(cb), float(policy_weight), float(value_weight),
+                                                                float(aux_weight), float(grad_scale), self._stream()),
+                   'clone_forward_backward')
+
+    def clone_step(self, batch, policy_weight=1.0, value_weight=0.0, aux_weight=1.0):
+        """Clone pass, then the matching apply: policy_apply, or joint_apply when the batch carries returns."""
+        with self.sequence():
+            self.clone_forward_backward(batch, policy_weight, value_weight, aux_weight)
+            if batch.get('returns') is not None:
+                self.joint_apply()
+            else:
+                self.policy_apply()
+
     def sequence(self):
         """Context manager around a run of learner calls on the current stream with nothing of the caller's own between them (one
         minibatch on one GPU: policy pass, apply, value pass, apply): the hand-overs between the caller's stream and the engine's
@@ -575,12 +615,18 @@ class LearnerEngine:
                     speed=value[:, 2], similarity=value[:, 3], dynamics=dyn)
 
     def metrics(self, which='policy'):
-        m = self.buffer(_lib.BUF_METRICS_P if which == 'policy' else _lib.BUF_METRICS_V).cpu().numpy()
+        m = self.buffer(_lib.BUF_METRICS_P if which in ('policy', 'clone') else _lib.BUF_METRICS_V).cpu().numpy()
         if which == 'policy':
             keys = ('loss', 'policy_loss', 'entropy', 'speed_loss', 'similarity_loss', 'ratio', 'log_prob')
+        elif which == 'clone':      # the policy block as a clone pass leaves it
+            keys = CLONE_METRICS
         else:
             keys = ('loss', 'value_loss', 'speed_loss', 'similarity_loss')
         return {k: float(m[i]) for i, k in enumerate(keys)}
+
+
+# slots 0..7 of CDRL_BUF_METRICS_P after a clone pass (cdrl_beta_clone_loss, include/cdrl.h)
+CLONE_METRICS = ('loss', 'clone_loss', 'entropy', 'speed_loss', 'similarity_loss', 'weight', 'log_prob', 'mode_error')
 
 
 def gae_returns(rewards: torch.Tensor, values_be: torch.Tensor, gamma: float, lambda_: float, scale: float = 2.0):

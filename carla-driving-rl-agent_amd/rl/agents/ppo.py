@@ -15,7 +15,7 @@ from .. import utils
 from ..parameters import DynamicParameter
 from .agents import Agent
 from ..._lib import CLIP_MODES, OPTIMIZERS
-from ... import train_stats
+from ... import traces, train_stats
 
 
 class PPOAgent(Agent):
@@ -332,6 +332,203 @@ class PPOAgent(Agent):
             if close:
                 for env in shard:
                     env.close()
+
+    # -- imitation: behaviour cloning on expert traces ------------------------------------------------
+    def _traces_dir(self, traces_dir):
+        path = traces_dir if traces_dir is not None else getattr(self, 'traces_dir', None)
+        if path is None:
+            raise ValueError('no traces directory: pass traces_dir=..., or create the agent with traces_dir=...')
+        return path
+
+    def clone_minibatch(self, batch: dict, policy_weight: float, value_weight: float, aux_weight: float):
+        """Hook: one behaviour-cloning minibatch step (pass + apply) on `batch` -- dict(states, u, and optionally weight, speed,
+        similarity, returns) of device tensors.  -> the learner engine that ran it (imitate reads its metric buffers)."""
+        raise NotImplementedError
+
+    def _check_trace(self, trace: dict, need_info: bool, value_weight: float) -> int:
+        """Refuses a trace that does not fit the agent or the options, before anything is uploaded.  -> its number of rows."""
+        keys = self.imitation_state_keys()
+        missing = [k for k in keys if k not in trace]
+        if missing or 'action' not in trace:
+            raise ValueError(f"trace lacks {missing or ['action']}: it was recorded from another observation space; the agent needs "
+                             f'{list(keys)} and action (traces.write_trace layout)')
+        actions = np.asarray(trace['action'])
+        n = actions.shape[0]
+        if actions.reshape(n, -1).shape[1] != self.num_actions:
+            raise ValueError(f'trace actions have width {actions.reshape(n, -1).shape[1]}, the agent has {self.num_actions} actions: '
+                             f'collect the traces with the same action space')
+        T = int(getattr(self.env, 'time_horizon', 1))
+        for k in keys:
+            shape, want = tuple(np.shape(trace[k])), tuple(self.state_spec[k])
+            if shape[:1] != (n,) or shape[1:] not in (want, (T,) + want):
+                raise ValueError(f'trace {k} has shape {shape}; the agent needs ({n},) + {want} per step, or ({n}, {T}) + {want} '
+                                 f'with the time_horizon axis')
+        if need_info and ('info_speed' not in trace or 'info_similarity' not in trace):
+            raise ValueError('trace has no info_speed / info_similarity: the auxiliary and value losses need them -- set '
+                             'value_weight=0 and aux_weight=0 to clone the actions alone')
+        if value_weight > 0.0 and np.size(trace.get('reward', ())) != n + 1:
+            raise ValueError(f"trace reward has {np.size(trace.get('reward', ()))} entries; {n} steps need {n + 1} (the trailing one "
+                             f'included)')
+        return n
+
+    def _trace_tensors(self, trace: dict, weights, need_info: bool, value_weight: float) -> dict:
+        """One trace on the device, uploaded once: states (stacked over time_horizon when the rows come without that axis, one
+        windowing gather per key), unit actions, and what the options ask for (weight, speed / similarity, returns)."""
+        n = self._check_trace(trace, need_info, value_weight)
+        T = int(getattr(self.env, 'time_horizon', 1))
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+        index, states = None, {}
+        for k in self.imitation_state_keys():
+            want = tuple(self.state_spec[k])
+            dev = up(trace[k])
+            if tuple(dev.shape[1:]) == want and self.stacks_time():
+                if index is None:
+                    index = torch.as_tensor(traces.window_index(n, T)).to(self.device)
+                dev = utils.gather_rows(dev, index).view((n, T) + want)
+            states[k] = dev
+        out = dict(states=states, u=up(traces.unit_actions(np.asarray(trace['action']).reshape(n, -1), self.action_low, self.action_high)))
+        if weights is not None:
+            w = np.asarray(weights(trace), dtype=np.float32).reshape(-1)
+            if w.shape[0] != n:
+                raise ValueError(f'weights(trace) returned {w.shape[0]} values for a trace of {n} rows')
+            out['weight'] = up(w)
+        if need_info:
+            out['speed'] = up(np.reshape(trace['info_speed'], -1)) / 100.0
+            out['similarity'] = up(np.reshape(trace['info_similarity'], -1))
+        if value_weight > 0.0:
+            # returns of the whole trace in one launch: zero values, the trace's own trailing reward as the bootstrap entry
+            zeros = torch.zeros((n + 1, 2), dtype=torch.float32, device=self.device)
+            out['returns'] = utils.returns_and_advantages(np.reshape(trace['reward'], -1), zeros, self.gamma, 0.0, 1.0,
+                                                          self.device)['returns_be']
+        return out
+
+    def imitation_state_keys(self) -> list:
+        """The state entries a trace must carry (those the network reads)."""
+        return list(self.state_spec)
+
+    def stacks_time(self) -> bool:
+        """Whether the learner's state rows carry a time_horizon axis in front of the per-step shape (CARLAgent: yes)."""
+        return False
+
+    def imitate(self, epochs=1, batch_size: Union[None, int] = None, shuffle_batches=False, shuffle_data=False, close=True, seed=None,
+                *, traces_dir=None, policy_weight=1.0, value_weight=0.0, aux_weight=1.0, lr=None, clip_norm=None, weights=None,
+                max_traces=None):
+        """Supervised pre-training on `trace-*.npz` files (traces.py): maximum likelihood of the recorded action under the policy's
+        Beta (behaviour cloning), plus -- value_weight > 0 -- the value loss on the traces' discounted returns, one minibatch step
+        per batch through the clone pass (one trunk forward and backward).  The first six parameters are the reference's
+        PPOAgent.imitate (rl/agents/ppo.py:415-462); its body is PPO on self-collected traces, which has no meaning for traces of
+        another expert, so the objective is this project's own.
+        Per epoch the files are read in an order drawn from `self.rng`; each trace is uploaded once and cut into minibatches by the
+        update()'s pipeline (skip_data, consider_obs_every, drop_batch_remainder; shuffle_data / shuffle_batches as given).
+        policy_weight / value_weight scale the two losses' gradients, aux_weight the speed / similarity terms of the clone loss.
+        lr / clip_norm: one learning rate / clip threshold for all optimizers during the run (the agent's own come back afterwards,
+        also after an error).  weights: callable(trace dict) -> (N,) per-row weights.  max_traces: read at most that many files.
+        No augmentation; the rollout sampler and the re-sampling offsets are not touched.  Ends with update_old_policy()."""
+        if getattr(self, 'data_parallel', False):
+            raise RuntimeError('imitate() runs on one GPU: pre-train in a single process, save(), and load the weights in the '
+                               'data-parallel run')
+        path = self._traces_dir(traces_dir)
+        batch_size = self.batch_size if batch_size is None else int(batch_size)
+        if seed is not None:
+            self.set_random_seed(seed)
+        policy_weight, value_weight, aux_weight = float(policy_weight), float(value_weight), float(aux_weight)
+        need_info = value_weight > 0.0 or aux_weight > 0.0
+        base = self.hyper_parameters()
+        run = dict(base)
+        if lr is not None:
+            run.update({k: float(lr) for k in base if k.endswith('_lr')})
+        if clip_norm is not None:
+            run.update({k: float(clip_norm) for k in base if k.startswith('clip_norm_')})
+        names = ('total', 'clone', 'entropy', 'speed', 'similarity')
+        try:
+            self.network.set_hparams(**run)
+            for epoch in range(1, epochs + 1):
+                for i, trace in enumerate(traces.load_traces(path, max_amount=max_traces, shuffle=True, rng=self.rng)):
+                    t0 = time.time()
+                    data = self._trace_tensors(trace, weights, need_info, value_weight)
+                    order = [k for k in ('u', 'weight', 'speed', 'similarity', 'returns') if k in data]
+                    batches = utils.data_to_batches((data['states'],) + tuple(data[k] for k in order), batch_size=batch_size,
+                                                    shuffle_batches=shuffle_batches, shuffle=shuffle_data,
+                                                    seed=int(self.rng.integers(2 ** 31)), skip=self.skip_count,
+                                                    num_shards=self.obs_skipping, drop_remainder=self.drop_batch_remainder)
+                    kept = []
+                    for states, *rest in batches:
+                        eng = self.clone_minibatch(dict(zip(order, rest), states=states), policy_weight, value_weight, aux_weight)
+                        row = [eng.buffer(2)[:8].clone()]       # CDRL_BUF_METRICS_P as the clone loss left it; copies stay on the device
+                        if 'returns' in data:
+                            row.append(eng.buffer(3)[:1].clone())
+                        kept.append(torch.cat(row))
+                    if kept:        # ONE device-to-host copy per trace
+                        for m in torch.stack(kept).cpu().numpy():
+                            entry = {f'imitation_loss_{k}': float(m[j]) for j, k in enumerate(names)}
+                            entry['imitation_entropy'] = entry.pop('imitation_loss_entropy')
+                            entry['imitation_mode_error'] = float(m[7])
+                            if 'returns' in data:
+                                entry['imitation_loss_value'] = float(m[8])
+                            self.log(**entry)
+                    self.write_summaries()
+                    print(f'[{epoch}] Trace-{i} took {round(time.time() - t0, 3)}s.')
+            self.network.update_old_policy()
+        finally:
+            self.network.set_hparams(**base)
+            fetch = getattr(self.network, 'train_stats', None)
+            if fetch is not None:
+                fetch(fetch=False)          # the imitation steps' rows never reach the next update()'s log
+            if close:
+                self.env.close()
+
+    def collect_traces(self, episodes: int, timesteps: int, envs: Optional[Sequence] = None, record_threshold=0.0, seeds=None,
+                       deterministic=False, traces_dir=None, close=False) -> list:
+        """The reference's PPOAgent.collect (rl/agents/ppo.py:360-413) on an environment shard: `episodes` rollouts of up to
+        `timesteps` steps with the CURRENT policy (deterministic=True: its mode), every environment's episode whose reward reaches
+        `record_threshold` written as one trace (traces.write_trace: states as observed, actions in environment units, the info
+        buffer's speed / similarity).  Nothing is appended to self.memory.  seeds: an int seeds the agent once, a list draws one
+        seed per episode.  -> the paths written.  A trained agent's traces are what another agent -- another compute mode, another
+        head size -- is distilled from with imitate()."""
+        path = self._traces_dir(traces_dir)
+        shard = list(envs) if envs is not None else [self.env]
+        if isinstance(seeds, int):
+            self.set_random_seed(seeds)
+        written = []
+        sampled = self.predict
+        try:
+            if deterministic:
+                self.predict = lambda state, *a, **kw: sampled(state, deterministic=True)
+            for episode in range(1, episodes + 1):
+                if isinstance(seeds, (list, tuple)):
+                    self.set_random_seed(int(seeds[int(self.rng.integers(len(seeds)))]))
+                self.reset()
+                before = [len(env.info_buffer['speed']) if hasattr(env, 'info_buffer') else 0 for env in shard]
+                rollout = self.collect(shard, timesteps, episode=episode)
+                for e, env in enumerate(shard):
+                    self.log(evaluation_reward=rollout.episode_reward[e])
+                    if rollout.episode_reward[e] < record_threshold:
+                        print(f'Trace-{episode} [env {e}] discarded: reward {round(rollout.episode_reward[e], 2)} below the threshold')
+                        continue
+                    states, actions, rewards, _, _ = rollout.trajectory(e)
+                    n = rollout.length[e]
+                    info = None
+                    if hasattr(env, 'info_buffer'):     # one entry per environment step: the last of each repeated action
+                        info = {}
+                        for k in ('speed', 'similarity'):
+                            piece = np.asarray(env.info_buffer[k][before[e]:], dtype=np.float32)[self.repeat_action - 1::self.repeat_action][:n]
+                            info[k] = np.pad(piece, (0, n - piece.shape[0]))
+                    done = np.zeros(n, np.float32)
+                    done[-1] = float(rollout.terminal[e])
+                    written.append(traces.write_trace(path, episode, {k: v.cpu().numpy() for k, v in states.items()},
+                                                      np.atleast_2d(self.convert_action(actions)), rewards, done, info))
+                self.write_summaries()
+            if self.memory is None or len(self.memory) == 0:     # the info buffers hold these rollouts' entries, not an update()'s
+                for env in shard:
+                    if hasattr(env, 'reset_info'):
+                        env.reset_info()
+        finally:
+            if deterministic:
+                del self.predict
+            if close:
+                for env in shard:
+                    env.close()
+        return written
 
     def is_writer(self) -> bool:
         """Hook for data-parallel agents: the rank that writes checkpoints, summaries and traces."""

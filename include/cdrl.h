@@ -367,6 +367,32 @@ int cdrl_learner_joint_forward_backward(cdrl_learner* l, const cdrl_policy_batch
 int cdrl_learner_joint_forward_backward_resample(cdrl_learner* l, const cdrl_policy_batch* b, const float* returns, uint64_t seed,
                                                 uint64_t offset, float grad_scale, void* stream);
 int cdrl_learner_joint_apply(cdrl_learner* l, void* stream);
+/* ---- behaviour cloning (supervised pre-training on expert traces) --------------
+ * The reference's curriculum calls agent.imitation_learning in front of the reinforcement stage but never defines it for CARLAgent;
+ * the definition here is the project's own: maximum likelihood of the expert's action under the policy's Beta(alpha, beta).
+ *
+ * cdrl_learner_clone_forward_backward: train-mode trunk forward, policy head forward (and value head forward with b->returns), then
+ * the loss of cdrl_beta_clone_loss (below) in the place of the policy loss, with entropy_coef read from the device hyper-parameters
+ * like the policy loss reads it; policy head backward; with b->returns the value loss and the joint tail exactly as in
+ * cdrl_learner_joint_forward_backward (same order, same B <= 2048 limit), otherwise the policy pass's tail.  Writes
+ * CDRL_BUF_METRICS_P (slots 0..7, table at cdrl_beta_clone_loss) and CDRL_BUF_AUX_P; with returns also CDRL_BUF_METRICS_V / _AUX_V.
+ * policy_weight and value_weight scale GRADIENTS only: the d(loss)/d(lin) of the clone loss is multiplied by grad_scale *
+ * policy_weight, that of the value loss by grad_scale * value_weight; every metric stays unscaled.  aux_weight multiplies the
+ * speed / similarity terms of the clone loss (total and gradient).  freeze_trunk = 1: no trunk backward, the trunk's gradient slice
+ * is not written.  Captured and replayed as a hipGraph like the stored-action policy pass; the three weights are part of the key.
+ * There is no apply of its own: a pass without returns is followed by cdrl_learner_policy_apply, one with returns by
+ * cdrl_learner_joint_apply, so optimizers, polyak, the gradient gate and the train-stats rows work as they are.  Both applies copy
+ * old_policy <- policy BEFORE the step: end a cloning run with cdrl_learner_update_old_policy, or the policy that acts lags one
+ * step behind the one that was trained. */
+typedef struct cdrl_clone_batch {
+    const float *image, *road, *vehicle, *navigation;
+    const float *u;            /* (B, A) expert action, unit interval */
+    const float *weight;       /* (B) or NULL */
+    const float *speed, *similarity;   /* (B) each; both NULL = no auxiliary targets (then returns must be NULL too) */
+    const float *returns;      /* (B, 2) (base, exponent) or NULL = policy only */
+} cdrl_clone_batch;
+int cdrl_learner_clone_forward_backward(cdrl_learner* l, const cdrl_clone_batch* b, float policy_weight, float value_weight,
+                                        float aux_weight, float grad_scale, void* stream);
 /* CARLANetwork.update_old_policy (core/networks.py:281-285). */
 int cdrl_learner_update_old_policy(cdrl_learner* l, void* stream);
 /* CARLANetwork.predict deterministic part (core/networks.py:181-193): inference-mode trunk,
@@ -901,6 +927,19 @@ int cdrl_beta_ppo_loss(const float* lin, const float* adv, const float* old_logp
                        float* hp_scratch16, void* stream);
 int cdrl_value_loss(const float* lin, const float* returns, const float* speed, const float* similarity, int B,
                     float exp_scale, float grad_scale, float* dlin, float* metrics, float* values, void* stream);
+/* Behaviour-cloning loss of the Beta head on linear head outputs lin (B, 2A+2: A alpha, A beta, similarity, speed columns) and
+ * expert actions u (B, A) in the unit interval.  alpha = softplus(lin) + 1.01 (beta likewise); x = clip(u, eps, 1 - eps) with the
+ * float32 machine epsilon, no gradient through x; clone = mean_b w_b * (-mean_a log Beta(x; alpha, beta)), weight (B) or NULL = 1;
+ * entropy = mean over B*A; speed_loss = 0.5 * mean (2 sigmoid(lin_speed) - speed)^2, sim_loss = 0.5 * mean (tanh(lin_sim) -
+ * similarity)^2 (speed and similarity both NULL: the two terms and their dlin columns are 0);
+ * total = clone - entropy_coef * entropy + aux_weight * (speed_loss + sim_loss); dlin (B, 2A+2) = grad_scale * d total / d lin,
+ * every entry written.  metrics: [0] total [1] clone [2] entropy [3] speed_loss [4] sim_loss [5] sum(w) / B [6] unweighted mean
+ * log-probability [7] unweighted mean over B*A of |mode - x|, mode = (alpha - 1) / (alpha + beta - 2): the error of the action a
+ * deterministic evaluation takes.  aux (B, 4A) or NULL: alpha, beta, log-probability, entropy, as cdrl_beta_ppo_loss writes them.
+ * One workgroup; transcendentals and sums in double, one rounding per output.  A <= 8 (-1 and cdrl_last_error above). */
+int cdrl_beta_clone_loss(const float* lin, const float* u, const float* weight, const float* speed, const float* similarity,
+                         float entropy_coef, float aux_weight, int B, int A, float grad_scale, float* dlin, float* metrics, float* aux,
+                         void* stream);
 
 #ifdef __cplusplus
 }
