@@ -89,7 +89,7 @@ class View(C.Structure):
 
 
 TRUNK, POLICY, VALUE, OLD_POLICY = 0, 1, 2, 3
-BUF_DYNAMICS, BUF_IMG_FEAT, BUF_METRICS_P, BUF_METRICS_V, BUF_AUX_P, BUF_AUX_V, BUF_LIN_P, BUF_LIN_V, BUF_SAMPLE = range(9)
+BUF_DYNAMICS, BUF_IMG_FEAT, BUF_METRICS_P, BUF_METRICS_V, BUF_AUX_P, BUF_AUX_V, BUF_LIN_P, BUF_LIN_V, BUF_SAMPLE, BUF_METRICS_R = range(10)
 
 _i, _i64, _f, _d, _sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 _L = C.c_void_p
@@ -163,6 +163,8 @@ PROTOTYPES = {
     'cdrl_learner_joint_forward_backward_resample': (_i, [_L, C.POINTER(PolicyBatch), _fp, C.c_uint64, C.c_uint64, _f, _fp]),
     'cdrl_learner_joint_apply': (_i, [_L, _fp]),
     'cdrl_learner_clone_forward_backward': (_i, [_L, C.POINTER(CloneBatch), _f, _f, _f, _f, _fp]),
+    'cdrl_learner_repr_forward_backward': (_i, [_L, _fp, _fp, _fp, _fp, _f, _f, _fp]),
+    'cdrl_learner_trunk_apply': (_i, [_L, _fp]),
     'cdrl_learner_sequence_begin': (_i, [_L, _fp]),
     'cdrl_learner_sequence_end': (_i, [_L, _fp]),
     'cdrl_learner_value_forward_backward': (_i, [_L, C.POINTER(ValueBatch), _f, _fp]),
@@ -237,6 +239,8 @@ PROTOTYPES = {
     'cdrl_bn_inference_stats': (_i, [_i, _pp, _pp, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_i), _fp, _fp]),
     'cdrl_bn_train_bwd_pooled': (_i, [_fp, _fp, _i, _i, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_beta_clone_loss': (_i, [_fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _f, _fp, _fp, _fp, _fp]),
+    'cdrl_ntxent_workspace_floats': (_i64, [_i, _i]),
+    'cdrl_ntxent_loss': (_i, [_fp, _i, _i, _f, _f, _fp, _fp, _fp, _fp]),
     'cdrl_beta_ppo_loss': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _f, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_value_loss': (_i, [_fp, _fp, _fp, _fp, _i, _f, _f, _fp, _fp, _fp, _fp]),
 }

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .. import train_stats
+from .. import _lib, traces, train_stats
 from ..engine import act_stats_width
 from ..evaluation import RESULT_KEYS, evaluation_info, summarize, trial_seed
 from ..parallel import DataParallelLearner
@@ -447,6 +447,103 @@ class CARLAgent(PPOAgent):
                              f'learner engines are built with; create the agent with CARLAgent(polyak={polyak}) instead')
         return self.imitate(epochs=epochs, shuffle_data=shuffle_data, traces_dir=traces_dir, policy_weight=alpha, value_weight=beta,
                             clip_norm=clip_grad, lr=lr, **kw)
+
+    # -- contrastive pre-training of the trunk ----------------------------------------------------------
+    VECTOR_KEYS = ('state_road', 'state_vehicle', 'state_navigation')
+    REPRESENTATION_LOG = ('representation_loss', 'representation_accuracy', 'representation_similarity_pos',
+                          'representation_similarity_neg', 'representation_embedding_norm')
+
+    def representation_views(self, rows: dict, plans: list, vector_inputs='zero') -> dict:
+        """The two views of N observation rows as one batch of 2N: the rows stacked twice, all 2N image stacks augmented by ONE
+        Augmenter.batch call with `plans` (2N of them; empty = no augmentation, as preprocess() at intensity 0), the vector inputs
+        zeroed ('zero') or passed through ('keep')."""
+        if vector_inputs not in ('zero', 'keep'):
+            raise ValueError(f"vector_inputs must be 'zero' or 'keep', got {vector_inputs!r}")
+        views = {k: torch.cat([rows[k], rows[k]], dim=0) for k in self.STATE_KEYS}
+        if plans:
+            if self._augmenter is None:
+                from ..rl.augmentations import Augmenter
+                self._augmenter = Augmenter(self.device)
+            views['state_image'] = self._augmenter.batch(views['state_image'], plans)
+        if vector_inputs == 'zero':
+            for k in self.VECTOR_KEYS:
+                views[k] = torch.zeros_like(views[k])
+        return views
+
+    def representation_plans(self, intensity: float, rng: np.random.Generator, count: int, first_offset: int) -> list:
+        """The augmentation plans of one minibatch's views: `count` draws from the call's own generator with consecutive Philox
+        offsets (draw_plans, as the shard path of preprocess()); none at intensity 0."""
+        if intensity <= 0.0:
+            return []
+        from ..rl.augmentations import draw_plans
+        return draw_plans(float(intensity), rng, count, first_offset=first_offset)
+
+    def representation_minibatch(self, views: dict, temperature: float):
+        """One representation step (pass + trunk apply) on a batch of views.  -> the learner engine that ran it."""
+        eng = self.network.engine_for(views['state_image'].shape[0])
+        eng.repr_step(eng.stage(views, 'representation'), temperature)
+        return eng
+
+    def learn_representation(self, epochs=1, batch_size=None, *, traces_dir=None, temperature=0.1, intensity=1.0,
+                             vector_inputs='zero', lr=None, shuffle_data=True, max_traces=None, seed=None, close=False):
+        """The representation stage of the reference's curriculum (Stage.representation_learning calls this name with its
+        `representation` keywords; the reference never defines it): contrastive pre-training of the shared trunk on the states of
+        `trace-*.npz` files (imitate()'s data source; actions, rewards and infos are not read).  Objective: NT-Xent (SimCLR, the
+        loss rl/augmentations/simclr.py of the reference points to) on the trunk's output, no projection head.
+        Each minibatch takes batch_size / 2 rows of one trace, stacks them twice, augments all image stacks with independently drawn
+        plans of `intensity`, and takes one trunk-only step (engine.repr_step); a remainder is dropped, a trace with fewer usable
+        rows is skipped.  vector_inputs='zero' feeds zeros for road / vehicle / navigation -- they are bit-identical in both views
+        and would give the pair away -- 'keep' passes them through.  lr: dynamics_lr during the run (the agent's own comes back
+        afterwards, also after an error).  seed: seeds the call's plan / shuffle generator; None: one draw from self.rng.
+        Only self.rng advances (that draw and the trace order): the rollout sampler, the re-sampling offset and the rollout
+        augmentation's generator and counter stay where they are.  No head changes, so old_policy is not touched."""
+        if getattr(self, 'data_parallel', False):
+            raise RuntimeError('learn_representation() runs on one GPU: pre-train in a single process, save(), and load the weights '
+                               'in the data-parallel run')
+        if not self.should_update_dynamics:
+            raise ValueError('learn_representation() trains the trunk: the agent was created with update_dynamics=False')
+        if self.clip_mode == 'global' or self.skip_nonfinite:
+            raise ValueError("learn_representation(): the gradient gate (clip_mode='global' / skip_nonfinite=True) is per head and has "
+                             'no trunk-only step; pre-train with an agent created without it')
+        if vector_inputs not in ('zero', 'keep'):
+            raise ValueError(f"vector_inputs must be 'zero' or 'keep', got {vector_inputs!r}")
+        batch_size = self.batch_size if batch_size is None else int(batch_size)
+        if batch_size < 2 or batch_size % 2:
+            raise ValueError(f'learn_representation(batch_size={batch_size}): a batch is two views of batch_size / 2 rows, so it '
+                             f'must be even')
+        if not float(temperature) > 0.0:
+            raise ValueError(f'learn_representation(temperature={temperature}) must be positive')
+        path = self._traces_dir(traces_dir)
+        rng_local = np.random.default_rng(int(self.rng.integers(2 ** 63 - 1)) if seed is None else int(seed))
+        half, calls = batch_size // 2, 0
+        base = self.hyper_parameters()
+        run = dict(base) if lr is None else dict(base, dynamics_lr=float(lr))
+        try:
+            self.network.set_hparams(**run)
+            for epoch in range(1, epochs + 1):
+                for i, trace in enumerate(traces.load_traces(path, max_amount=max_traces, shuffle=True, rng=self.rng)):
+                    t0 = time.time()
+                    n = self._check_trace_states(trace)
+                    states = self._trace_states(trace, n)
+                    batches = utils.data_to_batches((states,), batch_size=half, shuffle=shuffle_data, seed=int(rng_local.integers(2 ** 31)),
+                                                    skip=self.skip_count, num_shards=self.obs_skipping, drop_remainder=True)
+                    kept = []
+                    for (rows,) in batches:
+                        plans = self.representation_plans(intensity, rng_local, 2 * half, calls + 1)
+                        calls += 2 * half
+                        eng = self.representation_minibatch(self.representation_views(rows, plans, vector_inputs), float(temperature))
+                        kept.append(eng.buffer(_lib.BUF_METRICS_R)[:5].clone())      # copies stay on the device
+                    if not kept:
+                        print(f'[{epoch}] Trace-{i} skipped: {n} rows give no full minibatch of {half}.')
+                        continue
+                    for m in torch.stack(kept).cpu().numpy():       # ONE device-to-host copy per trace
+                        self.log(**{k: float(m[j]) for j, k in enumerate(self.REPRESENTATION_LOG)})
+                    self.write_summaries()
+                    print(f'[{epoch}] Trace-{i} took {round(time.time() - t0, 3)}s.')
+        finally:
+            self.network.set_hparams(**base)
+            if close:
+                self.env.close()
 
     # -- rollout helpers ------------------------------------------------------------------------------
     def get_memory(self):

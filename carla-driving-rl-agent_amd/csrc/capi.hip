@@ -594,6 +594,21 @@ int cdrl_learner_clone_forward_backward(cdrl_learner* l, const cdrl_clone_batch*
     return l->impl->clone_forward_backward(cb, policy_weight, value_weight, aux_weight, grad_scale, S(stream));
 }
 
+int cdrl_learner_repr_forward_backward(cdrl_learner* l, const float* image, const float* road, const float* vehicle,
+                                       const float* navigation, float temperature, float grad_scale, void* stream) {
+    CHECK_L(l);
+    if (!(temperature > 0.0f)) {
+        cdrl::set_error("representation pass: temperature = %g must be positive", (double)temperature);
+        return -1;
+    }
+    return l->impl->repr_forward_backward(image, road, vehicle, navigation, temperature, grad_scale, S(stream));
+}
+
+int cdrl_learner_trunk_apply(cdrl_learner* l, void* stream) {
+    CHECK_L(l);
+    return l->impl->trunk_apply(S(stream));
+}
+
 int cdrl_learner_update_old_policy(cdrl_learner* l, void* stream) {
     CHECK_L(l);
     return l->impl->update_old_policy(S(stream));
@@ -626,6 +641,7 @@ int cdrl_learner_get_buffer(const cdrl_learner* l, int which, float** ptr, int64
         case CDRL_BUF_LIN_P: *ptr = l->impl->policy_lin(); *elems = (int64_t)c.B * (2 * c.A + 2); break;
         case CDRL_BUF_LIN_V: *ptr = l->impl->value_lin(); *elems = (int64_t)c.B * 4; break;
         case CDRL_BUF_SAMPLE: *ptr = l->impl->sample_buffer(); *elems = (int64_t)c.B * c.A; break;
+        case CDRL_BUF_METRICS_R: *ptr = l->impl->metrics_repr(); *elems = 16; break;
         default: cdrl::set_error("unknown buffer id %d", which); return -1;
     }
     return 0;
@@ -1565,6 +1581,16 @@ int cdrl_beta_clone_loss(const float* lin, const float* u, const float* weight, 
     a.entropy_coef = entropy_coef; a.aux_weight = aux_weight; a.dlin = dlin; a.metrics = metrics; a.aux = aux;
     a.B = B; a.A = A; a.grad_scale = grad_scale;
     return clone_loss(a, S(stream));
+}
+
+int64_t cdrl_ntxent_workspace_floats(int B, int D) { return ntxent_workspace_floats(B, D); }
+
+int cdrl_ntxent_loss(const float* z, int B, int D, float temperature, float grad_scale, float* dz, float* metrics, float* workspace,
+                     void* stream) {
+    NtxentArgs a;
+    a.z = z; a.dz = dz; a.metrics = metrics; a.workspace = workspace;
+    a.B = B; a.D = D; a.temperature = temperature; a.grad_scale = grad_scale;
+    return ntxent_loss(a, S(stream));
 }
 
 int cdrl_value_loss(const float* lin, const float* returns, const float* speed, const float* similarity, int B,

@@ -524,6 +524,18 @@ struct ValueLossArgs {
     float inv_world;
 };
 int value_loss(const ValueLossArgs& a, hipStream_t st);
+// NT-Xent over pairs of views (ntxent.hip; no reference counterpart): rows i and (i + B/2) mod B of z are the two
+// views of one observation.  B even, 2 .. 2048; D >= 1; temperature > 0 (-1 and cdrl_last_error otherwise).
+struct NtxentArgs {
+    const float* z;          // [B][D] embeddings
+    float* dz;               // [B][D] grad_scale * dL/dz, every entry written; not z
+    float* metrics;          // [16]; 0..5 written (loss, top-1 accuracy, pair cosine, negatives' cosine, mean norm, temperature), 6..15 zero
+    float* workspace;        // ntxent_workspace_floats(B, D) floats, 16-byte aligned
+    int B, D;
+    float temperature, grad_scale;
+};
+int64_t ntxent_workspace_floats(int B, int D);      // -1: B or D refused
+int ntxent_loss(const NtxentArgs& a, hipStream_t st);
 // inference heads: alpha,beta,(mean,std) and value(base,exp) from linear outputs
 int policy_dist(const float* lin, float* out /*[B][4A]: alpha,beta,mean,std*/, int B, int A, hipStream_t st);
 int value_act(const float* lin, float* out /*[B][4] base,exp,speed,sim*/, int B, float exp_scale, hipStream_t st);
@@ -592,6 +604,8 @@ int tensor_sqnorms(const float* g, const TensorSeg* segs_dev, int ntensors, cons
 // m_caches to S_t of the new count); fold_final: no second
 // stage -- the consumer folds the chunk partials (clip_adam with chunk_part)
 enum TickMask : int { TICK_POLICY = 1, TICK_VALUE = 2, TICK_TRUNK = 4, TICK_NADAM = 8 };
+// the chunk kernel's tick alone, one thread (the trunk-only apply: no norm is wanted there)
+int tick_steps(DevHP* hp, int tick_mask, hipStream_t st);
 int clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev /*or null*/,
               const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms /*or null*/,
               DevHP* hp, int which, hipStream_t st, const double* chunk_part = nullptr, int ticked = 0);

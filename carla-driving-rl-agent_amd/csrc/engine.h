@@ -146,6 +146,15 @@ public:
     // two losses' dlin (through their grad_scale, next to inv_world), nothing else.  Followed by policy_apply, or joint_apply with returns.
     int clone_forward_backward(const CloneBatch& b, float policy_weight, float value_weight, float aux_weight, float inv_world,
                                hipStream_t st);
+    // Representation pass: train-mode trunk forward, the NT-Xent loss on the trunk's output (rows i and i + B/2: two
+    // views of one observation), the trunk's backward.  No head op runs; the heads' gradient slices, lin_*, metrics_p / metrics_v and
+    // the aux buffers are not written.  Refuses a frozen learner, an odd B and B > 2048.  Followed by trunk_apply.
+    int repr_forward_backward(const float* image, const float* road, const float* vehicle, const float* navigation, float temperature,
+                              float inv_world, hipStream_t st);
+    // The trunk's optimizer step alone (lr_dynamics, unclipped), then one tick of t_dynamics (Nadam: and of m_cache_dynamics) by a
+    // one-thread launch of the chunk-norm kernel's tick (tick_steps).  Nothing of either head, old_policy, the gate block or the
+    // train-stats ring is touched.  Refuses a frozen learner and one with the gradient gate (clip_mode = global / skip_nonfinite).
+    int trunk_apply(hipStream_t st);
     int update_old_policy(hipStream_t st);
     // inference: trunk (moving stats) + old_policy + value heads
     int predict(const float* image, const float* road, const float* vehicle, const float* navigation,
@@ -158,6 +167,7 @@ public:
     float* img_feat() const { return feat_.p; }
     float* metrics_policy() const { return metrics_p_; }
     float* metrics_value() const { return metrics_v_; }
+    float* metrics_repr() const { return metrics_r_; }
     float* policy_aux() const { return aux_p_; }
     float* value_aux() const { return aux_v_; }
     float* policy_lin() const { return lin_p_.p; }
@@ -403,6 +413,9 @@ private:
         // clone mode (policy is null): the clone loss on (clone_u, clone_w) stands where the policy loss stands
         const float *clone_u = nullptr, *clone_w = nullptr;
         float policy_weight = 1.0f, value_weight = 1.0f, aux_weight = 1.0f;
+        // representation mode (policy, returns, clone_u all null): the NT-Xent loss on the trunk's output, no head at all
+        bool repr = false;
+        float temperature = 0.0f;
         bool head() const { return policy || clone_u; }      // the policy head takes part
         bool joint() const { return head() && returns; }
     };
@@ -413,6 +426,7 @@ private:
     PolicyLossArgs policy_loss_args(const PassSpec& s) const;
     CloneLossArgs clone_loss_args(const PassSpec& s) const;
     ValueLossArgs value_loss_args(const PassSpec& s) const;
+    NtxentArgs ntxent_args(const PassSpec& s) const;
     // forward half: trunk, the heads present (dist: policy_dist behind the policy head; re-sampling: and the Beta draw, both in
     // front of the value head); backward half: per head its loss and backward, joint: bn_small_bwd_pair, then the trunk
     int pass_forward(const PassSpec& s, bool dist, hipStream_t st);
@@ -426,6 +440,8 @@ private:
     int policy_apply_impl(hipStream_t st);
     int value_apply_impl(hipStream_t st);
     int joint_apply_impl(hipStream_t st);
+    int trunk_apply_impl(hipStream_t st);
+    int repr_refused();
     int joint_refused();
     int predict_impl(const float* image, const float* road, const float* vehicle, const float* navigation, float* dist_out,
                      float* value_out, float* dyn_out, hipStream_t st);
@@ -549,6 +565,10 @@ private:
         bool small = false;         // single-launch form
     } bn0_[2];
     float *metrics_p_ = nullptr, *metrics_v_ = nullptr, *aux_p_ = nullptr, *aux_v_ = nullptr;
+    // representation pass: its 16 metrics sit behind the policy's in one allocation unit; the loss's scratch is backward slot 0's
+    // tower-gradient block, idle between the end of the trunk forward and the first backward op (its own block only where that one
+    // is too small).  Neither adds a byte to the workspace of a learner that never runs the pass.
+    float *metrics_r_ = nullptr, *ntxent_ws_ = nullptr;
     float *sample_u_ = nullptr, *sample_da_ = nullptr, *sample_db_ = nullptr;
     DevHP hp_host_;
     DevHP* hp_dev_ = nullptr;

@@ -1623,8 +1623,17 @@ void Learner::build(bool dry) {
     d_pack3_ = reinterpret_cast<PwX3Pack*>(alloc((h_pack3_.size() + 1) * sizeof(PwX3Pack) / sizeof(float) + 4));
     d_gpack_ = reinterpret_cast<GemmX3Pack*>(alloc((h_gpack_.size() + 1) * sizeof(GemmX3Pack) / sizeof(float) + 4));
     d_pwt_ = reinterpret_cast<PwTranspose*>(alloc((h_pwt_.size() + 1) * sizeof(PwTranspose) / sizeof(float) + 4));
-    metrics_p_ = alloc(16);
+    metrics_p_ = alloc(32);                                 // policy metrics, then the representation pass's (one 256-byte unit)
+    metrics_r_ = dry_ ? nullptr : metrics_p_ + 16;
     metrics_v_ = alloc(16);
+    ntxent_ws_ = nullptr;
+    if (!frozen() && cfg_.B % 2 == 0 && cfg_.B <= 2048) {   // (the learners the representation pass accepts)
+        const size_t need = (size_t)ntxent_workspace_floats(cfg_.B, cfg_.dyn);
+        const size_t have = (slot_sizes().dy * esz() + 3) / 4;      // floats of a backward slot's tower-gradient block
+        // dry build: the slots are sized behind the op lists, from the same maxima; the real build has them already
+        if (need > have) ntxent_ws_ = alloc(need);
+        else if (!dry_) ntxent_ws_ = dys_[0];
+    }
     aux_p_ = alloc((size_t)cfg_.B * 4 * A);
     aux_v_ = alloc((size_t)cfg_.B * 2);
     sample_u_ = alloc((size_t)cfg_.B * A);
@@ -1945,7 +1954,7 @@ static inline uint64_t Kf(float f) {
 // step kind: the first word of a graph key
 enum KeyKind : uint64_t {
     KEY_POLICY_PASS = 1, KEY_VALUE_PASS = 2, KEY_POLICY_APPLY = 3, KEY_VALUE_APPLY = 4, KEY_PREDICT = 5, KEY_JOINT_PASS = 6, KEY_JOINT_APPLY = 7,
-    KEY_CLONE_PASS = 8
+    KEY_CLONE_PASS = 8, KEY_REPR_PASS = 9, KEY_TRUNK_APPLY = 10
 };
 
 PolicyLossArgs Learner::policy_loss_args(const PassSpec& s) const {
@@ -2014,10 +2023,24 @@ int Learner::pass_forward(const PassSpec& s, bool dist, hipStream_t st) {
     return s.returns ? run_fwd(value_ops_, st, 1) : 0;
 }
 
+NtxentArgs Learner::ntxent_args(const PassSpec& s) const {
+    NtxentArgs a;
+    a.z = dyn_.p;
+    a.dz = dyn_.g;
+    a.metrics = metrics_r_;
+    a.workspace = ntxent_ws_;
+    a.B = cfg_.B;
+    a.D = cfg_.dyn;
+    a.temperature = s.temperature;
+    a.grad_scale = s.inv_world;
+    return a;
+}
+
 int Learner::pass_backward(const PassSpec& s, hipStream_t st) {
     // joint: each head's backward stops in front of its bn0; one launch then finishes both bn0 over the trunk output -- their own
     // gradients, and dyn_.g = d(policy loss)/d(dynamics) + d(value loss)/d(dynamics)
     const HeadBn0 &p0 = bn0_[0], &v0 = bn0_[1];
+    if (s.repr) CDRL_TRY(ntxent_loss(ntxent_args(s), st));   // writes dyn_.g, where a head's bn0 backward would
     if (s.head()) {
         CDRL_TRY(s.policy ? policy_loss(policy_loss_args(s), st) : clone_loss(clone_loss_args(s), st));
         CDRL_TRY(run_bwd(policy_ops_, st, s.joint() ? p0.op + 1 : 0));
@@ -2050,17 +2073,31 @@ int Learner::joint_refused() {
     return -1;
 }
 
+int Learner::repr_refused() {
+    if (frozen()) {
+        set_error("representation pass: freeze_trunk = 1: the pass trains the trunk and nothing else");
+        return -1;
+    }
+    if (cfg_.B % 2 != 0 || cfg_.B > 2048) {
+        set_error("representation pass: B = %d must be even (rows i and i + B/2 are two views) and at most 2048", cfg_.B);
+        return -1;
+    }
+    return 0;
+}
+
 int Learner::run_pass(const PassSpec& s, hipStream_t caller, bool fwd, bool bwd) {
     if (s.joint()) CDRL_TRY(joint_refused());
+    if (s.repr) CDRL_TRY(repr_refused());
     if (s.inv_world != 1.0f) dp_hint_ = true;
     // one half alone (the split form) is eager; so is re-sampling: (seed, offset) are kernel arguments that change every call
     const bool graphable = fwd && bwd && !s.resample;
     std::vector<uint64_t> key;
     if (graphable) {
-        key = {s.clone_u ? KEY_CLONE_PASS : s.joint() ? KEY_JOINT_PASS : s.policy ? KEY_POLICY_PASS : KEY_VALUE_PASS,
+        key = {s.repr ? KEY_REPR_PASS : s.clone_u ? KEY_CLONE_PASS : s.joint() ? KEY_JOINT_PASS : s.policy ? KEY_POLICY_PASS : KEY_VALUE_PASS,
                K(s.image), K(s.road), K(s.vehicle), K(s.navigation), K(s.speed), K(s.similarity), K(s.returns), Kf(s.inv_world)};
         if (const PolicyBatch* b = s.policy) key.insert(key.end(), {K(b->adv), K(b->old_logp), K(b->u), K(b->du_da), K(b->du_db)});
         if (s.clone_u) key.insert(key.end(), {K(s.clone_u), K(s.clone_w), Kf(s.policy_weight), Kf(s.value_weight), Kf(s.aux_weight)});
+        if (s.repr) key.push_back(Kf(s.temperature));
     }
     return launch(caller, key, graphable, [&](hipStream_t st) -> int {
         if (fwd) CDRL_TRY(pass_forward(s, !bwd, st));       // (the forward alone: its caller samples from alpha, beta)
@@ -2109,6 +2146,37 @@ int Learner::clone_forward_backward(const CloneBatch& b, float policy_weight, fl
     s.value_weight = value_weight;
     s.aux_weight = aux_weight;
     return run_pass(s, caller);
+}
+
+int Learner::repr_forward_backward(const float* image, const float* road, const float* vehicle, const float* navigation,
+                                   float temperature, float inv_world, hipStream_t caller) {
+    PassSpec s{image, road, vehicle, navigation, nullptr, nullptr, nullptr, nullptr, inv_world};
+    s.repr = true;
+    s.temperature = temperature;
+    return run_pass(s, caller);
+}
+
+int Learner::trunk_apply(hipStream_t caller) {
+    if (frozen()) {
+        set_error("trunk_apply: freeze_trunk = 1: the trunk has no optimizer step");
+        return -1;
+    }
+    if (gate_on()) {
+        set_error("trunk_apply: clip_mode = global / skip_nonfinite = 1: the gradient gate's decisions and counters are per head, a "
+                  "trunk-only step has no place in them");
+        return -1;
+    }
+    return launch(caller, {KEY_TRUNK_APPLY}, true, [&](hipStream_t st) -> int { return trunk_apply_impl(st); });
+}
+
+// order as in head_apply: the trunk's update (unclipped, which = 2, not yet ticked), the tick behind it -- the chunk-norm kernel's
+// tick on its own: a learner without train stats has no trunk chunk table, and this step needs no norm
+int Learner::trunk_apply_impl(hipStream_t st) {
+    const int64_t to = tr_offset(M_TRUNK);
+    const int opt = cfg_.optimizer;
+    CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK], nullptr,
+                         nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
+    return tick_steps(hp_dev_, TICK_TRUNK | (opt == CDRL_OPT_NADAM ? TICK_NADAM : 0), st);
 }
 
 int Learner::joint_apply(hipStream_t caller) {

@@ -22,6 +22,34 @@ namespace cdrl {
 // one function, so both produce the same bits.
 __device__ __forceinline__ float nadam_mu(float b1, int t) { return b1 * (1.0f - 0.5f * powf(0.96f, 0.004f * (float)t)); }
 
+// Step counters advanced by `tick` (TickMask bits: 1 policy, 2 value, 4 trunk; 8: Nadam -- each ticked optimizer's m_cache also
+// becomes S_t of its new count).  One thread.
+__device__ __forceinline__ void tick_counters(DevHP* hp, int tick) {
+    if (tick & 1) hp->t_policy += 1;
+    if (tick & 2) hp->t_value += 1;
+    if (tick & 4) hp->t_dynamics += 1;
+    if (tick & 8) {
+        if (tick & 1) hp->m_cache_policy = hp->m_cache_policy * nadam_mu(hp->beta1, hp->t_policy);
+        if (tick & 2) hp->m_cache_value = hp->m_cache_value * nadam_mu(hp->beta1, hp->t_value);
+        if (tick & 4) hp->m_cache_dynamics = hp->m_cache_dynamics * nadam_mu(hp->beta1, hp->t_dynamics);
+    }
+}
+
+// the tick without a norm (the trunk-only apply: its update ran in front, nothing runs behind)
+__global__ void tick_kernel(DevHP* hp, int tick) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) tick_counters(hp, tick);
+}
+
+int tick_steps(DevHP* hp, int tick_mask, hipStream_t st) {
+    if (!hp || tick_mask <= 0) {
+        set_error("tick_steps: null hyper-parameter block or empty mask");
+        return -1;
+    }
+    hipLaunchKernelGGL(tick_kernel, dim3(1), dim3(64), 0, st, hp, tick_mask);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
 __global__ void __launch_bounds__(256) sqnorm_chunk_kernel(const float* __restrict__ g,
                                                            const TensorSeg* __restrict__ segs,
                                                            const int* __restrict__ chunk_tensor,
@@ -31,17 +59,7 @@ __global__ void __launch_bounds__(256) sqnorm_chunk_kernel(const float* __restri
     const int c = blockIdx.x;
     // Adam step counters advanced here instead of by launches of their own: the trunk's (its update ran in FRONT of this kernel) and the
     // head's, whose update runs BEHIND it and is told so (clip_adam's `ticked`)
-    // (bit mask: 1 policy, 2 value, 4 trunk; 8: Nadam -- each ticked optimizer's m_cache also becomes S_t of its new count)
-    if (tick > 0 && c == 0 && threadIdx.x == 0) {
-        if (tick & 1) hp->t_policy += 1;
-        if (tick & 2) hp->t_value += 1;
-        if (tick & 4) hp->t_dynamics += 1;
-        if (tick & 8) {
-            if (tick & 1) hp->m_cache_policy = hp->m_cache_policy * nadam_mu(hp->beta1, hp->t_policy);
-            if (tick & 2) hp->m_cache_value = hp->m_cache_value * nadam_mu(hp->beta1, hp->t_value);
-            if (tick & 4) hp->m_cache_dynamics = hp->m_cache_dynamics * nadam_mu(hp->beta1, hp->t_dynamics);
-        }
-    }
+    if (tick > 0 && c == 0 && threadIdx.x == 0) tick_counters(hp, tick);
     const TensorSeg s = segs[chunk_tensor[c]];
     const int64_t beg = chunk_off[c];
     int64_t end = beg + CHUNK;

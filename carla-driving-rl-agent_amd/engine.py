@@ -556,6 +556,25 @@ class LearnerEngine:
             else:
                 self.policy_apply()
 
+    # Contrastive pre-training of the trunk (include/cdrl.h).  `states`: the four state tensors of B = 2N rows, rows
+    # i and i + N being two views of one observation.
+    def repr_forward_backward(self, states, temperature=0.1, grad_scale=1.0):
+        """Representation pass: train-mode trunk forward, NT-Xent on the trunk's output, trunk backward.  No head runs."""
+        img, road, veh, nav = self._states(states)
+        self._check_states(img, road, veh, nav)
+        _lib.check(self.lib.cdrl_learner_repr_forward_backward(self.h, _lib.ptr(img), _lib.ptr(road), _lib.ptr(veh), _lib.ptr(nav),
+                                                               float(temperature), float(grad_scale), self._stream()),
+                   'repr_forward_backward')
+
+    def trunk_apply(self):
+        """The trunk's optimizer step alone (dynamics_lr, unclipped) and one tick of its step counter."""
+        _lib.check(self.lib.cdrl_learner_trunk_apply(self.h, self._stream()), 'trunk_apply')
+
+    def repr_step(self, states, temperature=0.1):
+        with self.sequence():
+            self.repr_forward_backward(states, temperature)
+            self.trunk_apply()
+
     def sequence(self):
         """Context manager around a run of learner calls on the current stream with nothing of the caller's own between them (one
         minibatch on one GPU: policy pass, apply, value pass, apply): the hand-overs between the caller's stream and the engine's
@@ -615,6 +634,9 @@ class LearnerEngine:
                     speed=value[:, 2], similarity=value[:, 3], dynamics=dyn)
 
     def metrics(self, which='policy'):
+        if which == 'representation':
+            m = self.buffer(_lib.BUF_METRICS_R).cpu().numpy()
+            return {k: float(m[i]) for i, k in enumerate(REPRESENTATION_METRICS)}
         m = self.buffer(_lib.BUF_METRICS_P if which in ('policy', 'clone') else _lib.BUF_METRICS_V).cpu().numpy()
         if which == 'policy':
             keys = ('loss', 'policy_loss', 'entropy', 'speed_loss', 'similarity_loss', 'ratio', 'log_prob')
@@ -627,6 +649,29 @@ class LearnerEngine:
 
 # slots 0..7 of CDRL_BUF_METRICS_P after a clone pass (cdrl_beta_clone_loss, include/cdrl.h)
 CLONE_METRICS = ('loss', 'clone_loss', 'entropy', 'speed_loss', 'similarity_loss', 'weight', 'log_prob', 'mode_error')
+
+
+# slots 0..5 of CDRL_BUF_METRICS_R after a representation pass (cdrl_ntxent_loss, include/cdrl.h)
+REPRESENTATION_METRICS = ('loss', 'accuracy', 'similarity_pos', 'similarity_neg', 'embedding_norm', 'temperature')
+
+
+def ntxent_loss(z: torch.Tensor, temperature: float, grad_scale: float = 1.0):
+    """NT-Xent over pairs of views (cdrl_ntxent_loss): z (B, D) float32 on the device, B = 2N, rows i and i + N the two views of one
+    observation.  -> (dz (B, D) = grad_scale * dL/dz, metrics (16,): loss, top-1 accuracy, pair cosine, negatives' cosine, mean
+    norm, temperature).  Owns its workspace."""
+    lib = _lib.load()
+    if z.dim() != 2 or z.dtype != torch.float32 or not z.is_contiguous() or not z.is_cuda:
+        raise ValueError(f'ntxent_loss: z must be a contiguous float32 (B, D) device tensor, got {tuple(z.shape)} {z.dtype}')
+    B, D = z.shape
+    n = int(lib.cdrl_ntxent_workspace_floats(B, D))
+    if n < 0:
+        raise _lib.CdrlError('cdrl_ntxent_workspace_floats: ' + lib.cdrl_last_error().decode())
+    ws = torch.empty(n, dtype=torch.float32, device=z.device)
+    dz = torch.empty_like(z)
+    metrics = torch.empty(16, dtype=torch.float32, device=z.device)
+    _lib.check(lib.cdrl_ntxent_loss(_lib.ptr(z), B, D, float(temperature), float(grad_scale), _lib.ptr(dz), _lib.ptr(metrics),
+                                    _lib.ptr(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cdrl_ntxent_loss')
+    return dz, metrics
 
 
 def gae_returns(rewards: torch.Tensor, values_be: torch.Tensor, gamma: float, lambda_: float, scale: float = 2.0):

@@ -357,12 +357,7 @@ class PPOAgent(Agent):
         if actions.reshape(n, -1).shape[1] != self.num_actions:
             raise ValueError(f'trace actions have width {actions.reshape(n, -1).shape[1]}, the agent has {self.num_actions} actions: '
                              f'collect the traces with the same action space')
-        T = int(getattr(self.env, 'time_horizon', 1))
-        for k in keys:
-            shape, want = tuple(np.shape(trace[k])), tuple(self.state_spec[k])
-            if shape[:1] != (n,) or shape[1:] not in (want, (T,) + want):
-                raise ValueError(f'trace {k} has shape {shape}; the agent needs ({n},) + {want} per step, or ({n}, {T}) + {want} '
-                                 f'with the time_horizon axis')
+        self._check_trace_states(trace, n)
         if need_info and ('info_speed' not in trace or 'info_similarity' not in trace):
             raise ValueError('trace has no info_speed / info_similarity: the auxiliary and value losses need them -- set '
                              'value_weight=0 and aux_weight=0 to clone the actions alone')
@@ -371,10 +366,27 @@ class PPOAgent(Agent):
                              f'included)')
         return n
 
-    def _trace_tensors(self, trace: dict, weights, need_info: bool, value_weight: float) -> dict:
-        """One trace on the device, uploaded once: states (stacked over time_horizon when the rows come without that axis, one
-        windowing gather per key), unit actions, and what the options ask for (weight, speed / similarity, returns)."""
-        n = self._check_trace(trace, need_info, value_weight)
+    def _check_trace_states(self, trace: dict, n=None) -> int:
+        """The state entries of a trace against the agent's state_spec.  n: the row count they must have (None: that of the first
+        state entry; a trace without actions).  -> the row count."""
+        keys = self.imitation_state_keys()
+        missing = [k for k in keys if k not in trace]
+        if missing:
+            raise ValueError(f'trace lacks {missing}: it was recorded from another observation space; the agent needs {list(keys)} '
+                             f'(traces.write_trace layout)')
+        if n is None:
+            n = int(np.shape(trace[keys[0]])[0])
+        T = int(getattr(self.env, 'time_horizon', 1))
+        for k in keys:
+            shape, want = tuple(np.shape(trace[k])), tuple(self.state_spec[k])
+            if shape[:1] != (n,) or shape[1:] not in (want, (T,) + want):
+                raise ValueError(f'trace {k} has shape {shape}; the agent needs ({n},) + {want} per step, or ({n}, {T}) + {want} '
+                                 f'with the time_horizon axis')
+        return n
+
+    def _trace_states(self, trace: dict, n: int) -> dict:
+        """The state entries of a checked trace on the device, uploaded once: stacked over time_horizon when the rows come without
+        that axis (one windowing gather per key)."""
         T = int(getattr(self.env, 'time_horizon', 1))
         up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
         index, states = None, {}
@@ -386,7 +398,14 @@ class PPOAgent(Agent):
                     index = torch.as_tensor(traces.window_index(n, T)).to(self.device)
                 dev = utils.gather_rows(dev, index).view((n, T) + want)
             states[k] = dev
-        out = dict(states=states, u=up(traces.unit_actions(np.asarray(trace['action']).reshape(n, -1), self.action_low, self.action_high)))
+        return states
+
+    def _trace_tensors(self, trace: dict, weights, need_info: bool, value_weight: float) -> dict:
+        """One trace on the device, uploaded once: states (stacked over time_horizon when the rows come without that axis, one
+        windowing gather per key), unit actions, and what the options ask for (weight, speed / similarity, returns)."""
+        n = self._check_trace(trace, need_info, value_weight)
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+        out = dict(states=self._trace_states(trace, n), u=up(traces.unit_actions(np.asarray(trace['action']).reshape(n, -1), self.action_low, self.action_high)))
         if weights is not None:
             w = np.asarray(weights(trace), dtype=np.float32).reshape(-1)
             if w.shape[0] != n:
@@ -476,6 +495,14 @@ class PPOAgent(Agent):
                 fetch(fetch=False)          # the imitation steps' rows never reach the next update()'s log
             if close:
                 self.env.close()
+
+    def learn_representation(self, epochs=1, batch_size: Union[None, int] = None, *, traces_dir=None, temperature=0.1, intensity=1.0,
+                             vector_inputs='zero', lr=None, shuffle_data=True, max_traces=None, seed=None, close=False):
+        """Hook: the representation stage of the reference's curriculum (Stage.representation_learning, core/learning.py, calls
+        agent.learn_representation(**repr_args); the reference defines it on no agent).  An agent with a shared trunk implements it
+        (CARLAgent: contrastive pre-training of the trunk on trace files); this class has no trunk of its own."""
+        raise NotImplementedError(f'{type(self).__name__} has no shared trunk to pre-train: learn_representation is implemented by '
+                                  f'CARLAgent')
 
     def collect_traces(self, episodes: int, timesteps: int, envs: Optional[Sequence] = None, record_threshold=0.0, seeds=None,
                        deterministic=False, traces_dir=None, close=False) -> list:

@@ -393,6 +393,23 @@ typedef struct cdrl_clone_batch {
 } cdrl_clone_batch;
 int cdrl_learner_clone_forward_backward(cdrl_learner* l, const cdrl_clone_batch* b, float policy_weight, float value_weight,
                                         float aux_weight, float grad_scale, void* stream);
+/* ---- contrastive pre-training of the trunk ------------------------------------
+ * The reference's curriculum calls agent.learn_representation and never defines it; rl/augmentations/simclr.py names the objective.
+ * The definition here is the project's own: NT-Xent (table at the loss entry, below) on the trunk's output, B = 2N rows, rows i and
+ * i + N being two views of one observation.  No projection head: no parameter is added.
+ *
+ * The pass: train-mode trunk forward (moving statistics move once), the loss on CDRL_BUF_DYNAMICS, the trunk's backward.  No head op
+ * runs: the heads' gradient slices, CDRL_BUF_LIN_*, _METRICS_P / _V and _AUX_* are not written.  Writes the trunk's gradient slice
+ * and CDRL_BUF_METRICS_R.  grad_scale multiplies the gradient only.  Captured and replayed as a hipGraph; the four pointers,
+ * temperature and grad_scale are the key.  -1: freeze_trunk = 1, B odd, B > 2048, temperature <= 0.
+ *
+ * The apply: the trunk's optimizer step alone (cdrl_config.optimizer, learning rate lr_dynamics, unclipped), one tick of the trunk's
+ * step counter (Nadam: and of its m_cache).  The parameters, slots and counters of both heads, old_policy, the gate block and the
+ * train-stats ring stay as they are.  -1: freeze_trunk = 1; clip_mode = global or skip_nonfinite = 1 (the gate's decisions and
+ * counters are per head). */
+int cdrl_learner_repr_forward_backward(cdrl_learner* l, const float* image, const float* road, const float* vehicle,
+                                       const float* navigation, float temperature, float grad_scale, void* stream);
+int cdrl_learner_trunk_apply(cdrl_learner* l, void* stream);
 /* CARLANetwork.update_old_policy (core/networks.py:281-285). */
 int cdrl_learner_update_old_policy(cdrl_learner* l, void* stream);
 /* CARLANetwork.predict deterministic part (core/networks.py:181-193): inference-mode trunk,
@@ -412,7 +429,8 @@ enum {
     CDRL_BUF_AUX_V = 5,      /* (B, 2) value (base, exp)                      */
     CDRL_BUF_LIN_P = 6,      /* (B, 2A+2) linear head outputs                 */
     CDRL_BUF_LIN_V = 7,      /* (B, 4)                                        */
-    CDRL_BUF_SAMPLE = 8      /* (B, A) Beta sample drawn by ..._resample       */
+    CDRL_BUF_SAMPLE = 8,     /* (B, A) Beta sample drawn by ..._resample       */
+    CDRL_BUF_METRICS_R = 9   /* 16 floats of the last representation pass: loss, top-1 accuracy, pair cosine, negatives' cosine, mean norm, temperature */
 };
 int cdrl_learner_get_buffer(const cdrl_learner* l, int which, float** ptr, int64_t* elems);
 /* Named internal tensors of a bound learner, for parity tests: "<bn>.x" (raw BatchNorm input, dense NHWC rows with frames
@@ -940,6 +958,19 @@ int cdrl_value_loss(const float* lin, const float* returns, const float* speed, 
 int cdrl_beta_clone_loss(const float* lin, const float* u, const float* weight, const float* speed, const float* similarity,
                          float entropy_coef, float aux_weight, int B, int A, float grad_scale, float* dlin, float* metrics, float* aux,
                          void* stream);
+/* NT-Xent, the normalised-temperature cross-entropy over pairs of views, on embeddings z (B, D), B = 2N: rows i and
+ * pair(i) = (i + N) mod B are the two views of one observation.
+ *   zn_i = z_i / max(||z_i||, 1e-12);  s_ij = zn_i . zn_j / temperature;  l_i = log sum_{j != i} exp(s_ij) - s_{i,pair(i)};
+ *   L = mean_i l_i;  dz (B, D) = grad_scale * dL/dz, through both roles of every s_ij and through the normalisation; every entry
+ * written; dz may not be z.  metrics (16 floats, unscaled by grad_scale): [0] L  [1] share of rows whose positive logit is strictly
+ * above that of every other j != i (1 for B = 2)  [2] mean cosine of the pairs  [3] mean cosine over j != i, pair(i) (0 for B = 2)
+ * [4] mean ||z_i||  [5] temperature  [6..15] 0.
+ * workspace: the number of floats the first entry returns (16-byte aligned); all scratch lives there.  Deterministic (no atomics,
+ * fixed reduction order), no host read, no allocation: capturable.  The similarity matrix is never stored; row sums in double.
+ * -1 (and cdrl_last_error, naming the argument): B odd, B < 2, B > 2048, D < 1, temperature <= 0. */
+int64_t cdrl_ntxent_workspace_floats(int B, int D);
+int cdrl_ntxent_loss(const float* z, int B, int D, float temperature, float grad_scale, float* dz, float* metrics, float* workspace,
+                     void* stream);
 
 #ifdef __cplusplus
 }
