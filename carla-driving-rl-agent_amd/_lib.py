@@ -200,6 +200,8 @@ PROTOTYPES = {
     'cdrl_augment_images': (_i, [_fp, _fp, _i, _i, _i, _fp, _fp, _fp]),
     'cdrl_augment_batch_workspace_floats': (_i64, [_i, _i, _i, _i]),
     'cdrl_augment_images_batch': (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp]),
+    'cdrl_views_workspace_floats': (_i64, [_i, _i, _i, _i]),
+    'cdrl_views_batch': (_i, [_fp, _i, _fp, _i, _i, _i, _i, _fp, _fp, _fp]),
     'cdrl_stem_block_bwd_workspace_doubles': (_i64, [_i] * 5),
     'cdrl_stem_block_bwd': (_i, [_fp] * 5 + [_i] * 5 + [_fp] * 7),
     'cdrl_stem_block_bwd_pooled': (_i, [_fp] * 6 + [_i] * 5 + [_fp] * 7),

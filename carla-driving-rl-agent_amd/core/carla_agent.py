@@ -115,7 +115,7 @@ class CARLAgent(PPOAgent):
 
     def __init__(self, *args, aug_intensity=1.0, clip_norm=(1.0, 1.0, 1.0), name='carla', load_full=True, eta=0.0,
                  dynamics_lr=1e-3, update_dynamics=True, delta=0.0, aux=1.0, resample_actions=True, compute='f32', batch_augment=False,
-                 **kwargs):
+                 view_pipeline='agent', **kwargs):
         """`resample_actions=True` (default, the reference's behaviour): the policy loss is evaluated on a fresh Beta sample of
         the NEW policy with pathwise gradients, as PolicyNetwork.call does (reference core/networks.py:96-110, SURVEY.md F8);
         the sample is drawn on the device.  `False` is the textbook-PPO variant on the stored rollout actions
@@ -141,8 +141,14 @@ class CARLAgent(PPOAgent):
         train-mode trunk forward and back-propagates their sum once (engine.joint_forward_backward / joint_apply) instead of running
         the trunk twice.  `dynamics_lr` then acts ONCE per minibatch -- the trunk's optimizer takes one step on the summed gradient
         where the default takes two -- and the trunk's moving statistics update once.  update() runs one minibatch loop of
-        optimization_steps[0] passes over the policy batch pipeline (optimization_steps must be equal, else ValueError)."""
+        optimization_steps[0] passes over the policy batch pipeline (optimization_steps must be equal, else ValueError).
+        `view_pipeline` (not in config.json): how learn_representation() makes its two views of a row.  'agent' (default): the
+        rollout augmentation (draw_plans -> Augmenter.batch), pixel-aligned views.  'simclr': the SimCLR view pipeline -- random
+        crop resized back, flip, colour jitter, colour drop, Gaussian blur (draw_view_plans -> Augmenter.views).
+        A dict of draw_view_plans options (crop_scale, flip_prob, jitter_prob, drop_prob, blur_prob, blur_sigma) implies 'simclr'.
+        An unknown name or option: ValueError."""
         assert aug_intensity >= 0.0
+        self.view_pipeline, self.view_options = self.parse_view_pipeline(view_pipeline)
         network_spec = dict(kwargs.pop('network', {}))
         network_spec.setdefault('network', CARLANetwork)
         network_spec.setdefault('control_policy', self.DEFAULT_CONTROL)
@@ -453,18 +459,36 @@ class CARLAgent(PPOAgent):
     REPRESENTATION_LOG = ('representation_loss', 'representation_accuracy', 'representation_similarity_pos',
                           'representation_similarity_neg', 'representation_embedding_norm')
 
-    def representation_views(self, rows: dict, plans: list, vector_inputs='zero') -> dict:
-        """The two views of N observation rows as one batch of 2N: the rows stacked twice, all 2N image stacks augmented by ONE
-        Augmenter.batch call with `plans` (2N of them; empty = no augmentation, as preprocess() at intensity 0), the vector inputs
-        zeroed ('zero') or passed through ('keep')."""
+    view_pipeline, view_options = 'agent', {}       # class-level defaults: an agent that never ran __init__ has the old views
+
+    @staticmethod
+    def parse_view_pipeline(value) -> tuple:
+        """CARLAgent(view_pipeline=...) -> (name, options of draw_view_plans)."""
+        from ..rl.augmentations import check_view_options
+        if isinstance(value, dict):
+            check_view_options(**value)
+            return 'simclr', dict(value)
+        if value in ('agent', 'simclr'):
+            return value, {}
+        raise ValueError(f"view_pipeline must be 'agent', 'simclr' or a dict of draw_view_plans options, got {value!r}")
+
+    def representation_views(self, rows: dict, plans, vector_inputs='zero') -> dict:
+        """The two views of N observation rows as one batch of 2N, the vector inputs zeroed ('zero') or passed through ('keep').
+        plans, a list (view_pipeline 'agent'): the rows stacked twice, all 2N image stacks augmented by ONE Augmenter.batch call with
+        `plans` (2N of them; empty = no augmentation, as preprocess() at intensity 0).  plans, a record array of view plans
+        ('simclr'): ONE Augmenter.views call makes the 2N image stacks from the N rows, which are not stacked twice."""
         if vector_inputs not in ('zero', 'keep'):
             raise ValueError(f"vector_inputs must be 'zero' or 'keep', got {vector_inputs!r}")
-        views = {k: torch.cat([rows[k], rows[k]], dim=0) for k in self.STATE_KEYS}
-        if plans:
-            if self._augmenter is None:
-                from ..rl.augmentations import Augmenter
-                self._augmenter = Augmenter(self.device)
-            views['state_image'] = self._augmenter.batch(views['state_image'], plans)
+        if (isinstance(plans, np.ndarray) or plans) and self._augmenter is None:
+            from ..rl.augmentations import Augmenter
+            self._augmenter = Augmenter(self.device)
+        twice = lambda k: torch.cat([rows[k], rows[k]], dim=0)
+        if isinstance(plans, np.ndarray):
+            views = {k: self._augmenter.views(rows[k], plans) if k == 'state_image' else twice(k) for k in self.STATE_KEYS}
+        else:
+            views = {k: twice(k) for k in self.STATE_KEYS}
+            if plans:
+                views['state_image'] = self._augmenter.batch(views['state_image'], plans)
         if vector_inputs == 'zero':
             for k in self.VECTOR_KEYS:
                 views[k] = torch.zeros_like(views[k])
@@ -472,9 +496,15 @@ class CARLAgent(PPOAgent):
 
     def representation_plans(self, intensity: float, rng: np.random.Generator, count: int, first_offset: int) -> list:
         """The augmentation plans of one minibatch's views: `count` draws from the call's own generator with consecutive Philox
-        offsets (draw_plans, as the shard path of preprocess()); none at intensity 0."""
+        offsets (draw_plans, as the shard path of preprocess()); none at intensity 0.  With view_pipeline 'simclr': `count` view
+        plans as one record array (draw_view_plans with strength = intensity and the agent's view options; first_offset is unused,
+        view plans carry no random stream)."""
         if intensity <= 0.0:
             return []
+        if self.view_pipeline == 'simclr':
+            from ..rl.augmentations import draw_view_plans
+            H, W = self.state_spec['state_image'][-3:-1]
+            return draw_view_plans(float(intensity), rng, count, H, W, **self.view_options)
         from ..rl.augmentations import draw_plans
         return draw_plans(float(intensity), rng, count, first_offset=first_offset)
 

@@ -10,6 +10,7 @@
 // the rollout path, once per environment step: augment_images serves one stack with up to six launches and a copy, and
 // augment_images_batch serves a whole environment shard (E stacks, E plans in device memory) with five launches whatever E is,
 // writing for every environment the bytes augment_images writes (both are built from the __device__ bodies below).
+#include "aug_bodies.h"
 #include "cdrl_kernels.h"
 #include "philox.h"
 
@@ -17,78 +18,19 @@ namespace cdrl {
 
 enum { AUG_SP_SELECT = 1, AUG_SP_NOISE = 2, AUG_GN_SELECT = 3, AUG_GN_NOISE = 4, AUG_DROPOUT = 5 };
 
-__device__ __forceinline__ void rgb_to_hsv(float r, float g, float b, float& h, float& s, float& v) {
-    v = fmaxf(fmaxf(r, g), b);
-    const float mn = fminf(fminf(r, g), b);
-    const float d = v - mn;
-    s = v > 0.0f ? d / v : 0.0f;
-    if (d > 0.0f) {
-        float hh;
-        if (v == r) hh = (g - b) / d;
-        else if (v == g) hh = 2.0f + (b - r) / d;
-        else hh = 4.0f + (r - g) / d;
-        hh /= 6.0f;
-        h = hh - floorf(hh);
-    } else {
-        h = 0.0f;
-    }
-}
-
-__device__ __forceinline__ float hsv_f(float n, float h6, float s, float v) {
-    const float k = fmodf(n + h6, 6.0f);
-    return v - v * s * fmaxf(0.0f, fminf(fminf(k, 4.0f - k), 1.0f));
-}
-
-__device__ __forceinline__ void hsv_to_rgb(float h, float s, float v, float& r, float& g, float& b) {
-    const float h6 = h * 6.0f;
-    r = hsv_f(5.0f, h6, s, v);
-    g = hsv_f(3.0f, h6, s, v);
-    b = hsv_f(1.0f, h6, s, v);
-}
-
 // ---- per-pixel / per-image bodies, shared by the single-stack and the batched kernels so that both are compiled from the same
-// expressions (the batched form must write the single-stack form's bytes)
-
-// per-(image, channel) mean over H*W of x + add: the whole 1024-thread workgroup, strided partial sums in double, then a tree
-__device__ __forceinline__ void channel_mean_body(const float* __restrict__ xp, int P, float add, float* __restrict__ mean3) {
-    __shared__ double sm[3][1024];
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int p = threadIdx.x; p < P; p += blockDim.x)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s[c] += (double)(xp[p * 3 + c] + add);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) sm[c][threadIdx.x] = s[c];
-    __syncthreads();
-    for (int st = blockDim.x / 2; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) sm[c][threadIdx.x] += sm[c][threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) mean3[threadIdx.x] = (float)(sm[threadIdx.x][0] / (double)P);
-}
+// expressions (the batched form must write the single-stack form's bytes); the HSV conversions, the jitter of one pixel and the
+// channel mean live in aug_bodies.h, which views.hip shares
 
 // color jitter of pixel i of a stack (x, y: the stack's base; mean: its [T][3] channel means)
 __device__ __forceinline__ void jitter_pixel(const float* __restrict__ x, float* __restrict__ y, int64_t i, int P,
                                              const float* __restrict__ mean, float brightness, float contrast, float saturation,
                                              float hue) {
     const int t = (int)(i / P);
-    float c[3];
+    float c[3] = {x[i * 3], x[i * 3 + 1], x[i * 3 + 2]};
+    jitter_rgb(c, mean + t * 3, brightness, contrast, saturation, hue);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float m = mean[t * 3 + k];
-        c[k] = (x[i * 3 + k] + brightness - m) * contrast + m;
-    }
-    float h, s, v;
-    rgb_to_hsv(c[0], c[1], c[2], h, s, v);
-    s = fminf(fmaxf(s * saturation, 0.0f), 1.0f);
-    hsv_to_rgb(h, s, v, c[0], c[1], c[2]);
-    rgb_to_hsv(c[0], c[1], c[2], h, s, v);
-    h = h + hue;
-    h = h - floorf(h);
-    hsv_to_rgb(h, s, v, c[0], c[1], c[2]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) y[i * 3 + k] = fminf(fmaxf(c[k], 0.0f), 1.0f);
+    for (int k = 0; k < 3; ++k) y[i * 3 + k] = c[k];
 }
 
 // k x k cross-correlation of channel c at (t, yy, xx), zero padding; w: [k][k][3]

@@ -934,6 +934,14 @@ int cdrl_augment_images_batch(const float* in, float* out, int E, int T, int H, 
     return augment_images_batch(in, out, E, T, H, W, reinterpret_cast<const AugPlan*>(plans_dev), workspace, S(stream));
 }
 
+int64_t cdrl_views_workspace_floats(int V, int T, int H, int W) { return views_workspace_floats(V, T, H, W); }
+
+int cdrl_views_batch(const float* rows, int N, float* out, int V, int T, int H, int W, const cdrl_view_plan* plans_dev,
+                     float* workspace, void* stream) {
+    static_assert(sizeof(cdrl_view_plan) == sizeof(ViewPlan), "cdrl_view_plan / ViewPlan layout mismatch");
+    return views_batch(rows, N, out, V, T, H, W, reinterpret_cast<const ViewPlan*>(plans_dev), workspace, S(stream));
+}
+
 int64_t cdrl_stem_block_bwd_workspace_doubles(int B, int T, int H, int W, int Cout) {
     const StemPlan sp = stem_plan(B, T, H, W, Cout, 0, false, false, true);
     return sp.pr_part_doubles + sp.ws_doubles;

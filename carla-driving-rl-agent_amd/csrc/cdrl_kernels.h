@@ -578,6 +578,24 @@ int64_t augment_batch_workspace_floats(int E, int T, int H, int W);
 int augment_images_batch(const float* in, float* out, int E, int T, int H, int W, const AugPlan* plans_dev, float* workspace,
                          hipStream_t st);
 
+// ---------------------------------------------------------------- contrastive views (views.hip)
+constexpr int VIEW_MAX_TAPS = 15;
+struct ViewPlan {          // same layout as cdrl_view_plan (include/cdrl.h)
+    int32_t crop_y, crop_x, crop_h, crop_w;
+    int32_t flip;
+    int32_t jitter;
+    float brightness, contrast, saturation, hue;
+    int32_t drop;
+    int32_t blur_taps;
+    float blur_w[16];
+};
+// rows [N][T][H][W][3] -> out [V][T][H][W][3], view v from row v % N with plans_dev[v] (DEVICE memory; contents validated by the
+// caller before the upload: the kernels clamp a crop window into the frame and treat a tap count that is even or outside 3..15
+// as 0); workspace: views_workspace_floats floats, may not overlap rows or out.  Four launches for any V.
+int64_t views_workspace_floats(int V, int T, int H, int W);
+int views_batch(const float* rows, int N, float* out, int V, int T, int H, int W, const ViewPlan* plans_dev, float* workspace,
+                hipStream_t st);
+
 // ---------------------------------------------------------------- optimiser (optim.hip)
 // Device hyper-parameter block, refreshed by the host before each step (graph-replay safe).
 struct DevHP {

@@ -6,7 +6,12 @@ core/carla_agent.py:527-579) on the native kernels.
 `Augmenter()(images, plan)` applies the plan to one stack on the device through `cdrl_augment_images`; `Augmenter().batch(images,
 plans)` applies E plans to the E stacks of an environment shard through `cdrl_augment_images_batch` (one copy of the images, one
 upload of the packed plans, five launches for any E; every stack gets the bytes the one-stack call gives it).  The random *fields*
-(salt & pepper masks, gaussian noise, dropout grid) are generated on the device from (plan seed, plan offset)."""
+(salt & pepper masks, gaussian noise, dropout grid) are generated on the device from (plan seed, plan offset).
+
+Contrastive views (the reference's rl/augmentations/simclr.py:pipeline): `draw_view_plans` draws one plan per view --
+crop window, flip, colour jitter, colour drop, Gaussian blur -- as one numpy record array, vectorised over the views;
+`Augmenter().views(rows, plans)` turns N rows into copies * N views through `cdrl_views_batch` (one upload of the plans, one library
+call, four launches for any number of views, no doubled copy of the rows)."""
 import ctypes as C
 
 import numpy as np
@@ -96,6 +101,133 @@ def pack_plans(plans: list) -> np.ndarray:
     return out
 
 
+# ---- contrastive views (csrc/views.hip)
+VIEW_MAX_TAPS = 15
+
+
+class ViewPlan(C.Structure):
+    _fields_ = [('crop_y', C.c_int32), ('crop_x', C.c_int32), ('crop_h', C.c_int32), ('crop_w', C.c_int32), ('flip', C.c_int32),
+                ('jitter', C.c_int32), ('brightness', C.c_float), ('contrast', C.c_float), ('saturation', C.c_float),
+                ('hue', C.c_float), ('drop', C.c_int32), ('blur_taps', C.c_int32), ('blur_w', C.c_float * 16)]
+
+
+VIEW_PLAN_DTYPE = np.dtype([(n, np.float32, (16,)) if n == 'blur_w' else (n, np.dtype(t)) for n, t in ViewPlan._fields_], align=True)
+assert VIEW_PLAN_DTYPE.itemsize == C.sizeof(ViewPlan) and all(VIEW_PLAN_DTYPE.fields[n][1] == getattr(ViewPlan, n).offset
+                                                              for n, _ in ViewPlan._fields_)
+
+VIEW_OPTIONS = dict(crop_scale=(0.6, 1.0), flip_prob=0.0, jitter_prob=0.8, drop_prob=0.2, blur_prob=0.5, blur_sigma=(0.1, 2.0))
+
+
+def empty_view_plans(count: int, H: int, W: int) -> np.ndarray:
+    """`count` plans that change nothing: full-size crop, no flip, no colour op, no blur."""
+    out = np.zeros(count, dtype=VIEW_PLAN_DTYPE)
+    out['crop_h'], out['crop_w'], out['contrast'], out['saturation'] = H, W, 1.0, 1.0
+    return out
+
+
+def check_view_options(**options) -> dict:
+    """The keyword options of draw_view_plans, completed with their defaults; an unknown name or a value out of range: ValueError."""
+    unknown = sorted(set(options) - set(VIEW_OPTIONS))
+    if unknown:
+        raise ValueError(f'unknown view option(s) {unknown}: the options are {sorted(VIEW_OPTIONS)}')
+    opt = dict(VIEW_OPTIONS, **options)
+    for name in ('flip_prob', 'jitter_prob', 'drop_prob', 'blur_prob'):
+        if not 0.0 <= float(opt[name]) <= 1.0:
+            raise ValueError(f'{name}={opt[name]!r} is a probability: it must lie in [0, 1]')
+    for name in ('crop_scale', 'blur_sigma'):
+        if np.ndim(opt[name]) != 1 or len(opt[name]) != 2:
+            raise ValueError(f'{name}={opt[name]!r} must be a (low, high) pair')
+    lo, hi = (float(v) for v in opt['crop_scale'])
+    if not 0.0 < lo <= hi <= 1.0:
+        raise ValueError(f'crop_scale={opt["crop_scale"]!r} must satisfy 0 < low <= high <= 1')
+    lo, hi = (float(v) for v in opt['blur_sigma'])
+    if not 0.0 < lo <= hi:
+        raise ValueError(f'blur_sigma={opt["blur_sigma"]!r} must satisfy 0 < low <= high')
+    return opt
+
+
+def view_blur_taps(H: int, W: int) -> int:
+    """The blur's tap count for H x W frames: a tenth of the shorter side made odd, within 3..15 (9 at 90 x 120)."""
+    return int(np.clip(int(0.1 * min(H, W)) | 1, 3, VIEW_MAX_TAPS))
+
+
+def draw_view_plans(strength: float, rng: np.random.Generator, count: int, H: int, W: int, *, crop_scale=(0.6, 1.0), flip_prob=0.0,
+                    jitter_prob=0.8, drop_prob=0.2, blur_prob=0.5, blur_sigma=(0.1, 2.0)) -> np.ndarray:
+    """`count` view plans for H x W frames as a VIEW_PLAN_DTYPE record array: ONE generator call per field for all the plans, in a
+    fixed order, so the plans are a pure function of the generator's state.
+    crop: a side fraction s ~ U(crop_scale) per view, window round(s H) x round(s W) (at least 2, aspect ratio kept -- a panoramic
+    90 x 360 frame is not squeezed) at an integer-uniform offset.  The default crop_scale is a choice nobody has tuned.
+    flip: with flip_prob; 0 by default -- invariance to mirroring would give a left bend and a right bend one embedding.
+    jitter: with jitter_prob, the ranges of draw_plan at alpha = strength (brightness and hue +-0.2 s, contrast and saturation
+    1 +- 0.8 s).  drop: colour drop with drop_prob.  blur: with blur_prob, a normalised Gaussian of view_blur_taps(H, W) taps with
+    sigma ~ U(blur_sigma); the weights are normalised in float64 and stored as float32."""
+    opt = check_view_options(crop_scale=crop_scale, flip_prob=flip_prob, jitter_prob=jitter_prob, drop_prob=drop_prob,
+                             blur_prob=blur_prob, blur_sigma=blur_sigma)
+    count, H, W, s = int(count), int(H), int(W), float(strength)
+    if count < 0 or H < 2 or W < 2 or s < 0.0:
+        raise ValueError(f'draw_view_plans: count {count}, frames {H} x {W}, strength {strength}: need count >= 0, frames of at '
+                         f'least 2 x 2 and strength >= 0')
+    out = empty_view_plans(count, H, W)
+    scale = rng.uniform(*opt['crop_scale'], size=count)
+    out['crop_h'] = np.clip(np.rint(scale * H), 2, H)
+    out['crop_w'] = np.clip(np.rint(scale * W), 2, W)
+    out['crop_y'] = rng.integers(0, H - out['crop_h'] + 1)
+    out['crop_x'] = rng.integers(0, W - out['crop_w'] + 1)
+    out['flip'] = rng.random(count) < opt['flip_prob']
+    jitter = rng.random(count) < opt['jitter_prob']
+    out['jitter'] = jitter
+    out['brightness'] = np.where(jitter, rng.uniform(-0.2 * s, 0.2 * s, size=count), 0.0)
+    out['contrast'] = np.where(jitter, rng.uniform(1.0 - 0.8 * s, 1.0 + 0.8 * s, size=count), 1.0)
+    out['saturation'] = np.where(jitter, rng.uniform(1.0 - 0.8 * s, 1.0 + 0.8 * s, size=count), 1.0)
+    out['hue'] = np.where(jitter, rng.uniform(-0.2 * s, 0.2 * s, size=count), 0.0)
+    out['drop'] = rng.random(count) < opt['drop_prob']
+    blur = rng.random(count) < opt['blur_prob']
+    sigma = rng.uniform(*opt['blur_sigma'], size=count)
+    taps = view_blur_taps(H, W)
+    x = np.arange(taps, dtype=np.float64) - taps // 2
+    w = np.exp(-(x[None, :] ** 2) / (2.0 * sigma[:, None] ** 2))
+    w /= w.sum(axis=1, keepdims=True)
+    out['blur_taps'] = np.where(blur, taps, 0)
+    out['blur_w'][:, :taps] = np.where(blur[:, None], w, 0.0)
+    return out
+
+
+def pack_view_plans(plans, H: int, W: int) -> np.ndarray:
+    """The plans (a VIEW_PLAN_DTYPE record array, or a list of dicts over empty_view_plans' fields) as one contiguous record array
+    with cdrl_view_plan's byte layout, validated for H x W frames: the device cannot report a bad plan.  ValueError names the plans
+    whose crop window leaves the frame or is smaller than 2, whose tap count is not 0 or odd within 3..15, or whose weights do not
+    sum to 1 within 1e-5."""
+    if isinstance(plans, np.ndarray):
+        if plans.dtype != VIEW_PLAN_DTYPE or plans.ndim != 1:
+            raise ValueError(f'view plans must be a 1-D array of VIEW_PLAN_DTYPE, got {plans.dtype} with {plans.ndim} dimensions')
+        out = np.ascontiguousarray(plans)
+    else:
+        out = empty_view_plans(len(plans), H, W)
+        for i, plan in enumerate(plans):
+            for name, value in plan.items():
+                if name == 'blur_w':
+                    out[i][name][:len(value)] = value
+                else:
+                    out[i][name] = value
+    problems = []
+
+    def refuse(bad, what):
+        if bad.any():
+            problems.append(f'{what} (plans {np.flatnonzero(bad).tolist()})')
+
+    ch, cw, cy, cx = (out[n].astype(np.int64) for n in ('crop_h', 'crop_w', 'crop_y', 'crop_x'))
+    refuse((ch < 2) | (cw < 2), 'crop window smaller than 2')
+    refuse((cy < 0) | (cx < 0) | (cy + ch > H) | (cx + cw > W), f'crop window outside the {H} x {W} frame')
+    taps = out['blur_taps']
+    refuse((taps != 0) & ((taps < 3) | (taps > VIEW_MAX_TAPS) | (taps % 2 == 0)), f'blur_taps must be 0 or odd within 3..{VIEW_MAX_TAPS}')
+    used = np.arange(16)[None, :] < taps[:, None]
+    total = np.where(used, out['blur_w'].astype(np.float64), 0.0).sum(axis=1)
+    refuse((taps != 0) & ~(np.abs(total - 1.0) <= 1e-5), 'blur weights do not sum to 1 within 1e-5')
+    if problems:
+        raise ValueError('bad view plans: ' + '; '.join(problems))
+    return out
+
+
 class Augmenter:
     """Holds the workspace / output buffers for one observation-stack shape."""
 
@@ -108,6 +240,8 @@ class Augmenter:
         self._batch_shape = None
         self._staging = None
         self._staging_read = None
+        self._views_ws = None
+        self._views_shape = None
 
     def _stage(self, stacks) -> torch.Tensor:
         """E host stacks -> one (E, T, H, W, 3) device tensor: the stacks are gathered straight into a cached page-locked buffer
@@ -147,6 +281,28 @@ class Augmenter:
         _lib.check(self.lib.cdrl_augment_images_batch(C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), E, T, H, W,
                                                       C.c_void_p(plans_dev.data_ptr()), C.c_void_p(self._batch_ws.data_ptr()), stream),
                    'cdrl_augment_images_batch')
+        return out
+
+    def views(self, rows, plans, copies=2) -> torch.Tensor:
+        """rows: (N, T, H, W, 3), kept on the device; plans: copies * N view plans (pack_view_plans).  -> (copies * N, T, H, W, 3):
+        view v is row v % N under plans[v].  One upload of the packed plans and one library call; the rows are not copied."""
+        x = torch.as_tensor(rows, dtype=torch.float32).to(self.device).contiguous()
+        if x.dim() != 5 or x.shape[-1] != 3:
+            raise ValueError(f'expected image stacks (N, T, H, W, 3), got {tuple(x.shape)}')
+        N, T, H, W, _ = x.shape
+        V = int(copies) * N
+        if V < 1 or len(plans) != V:
+            raise ValueError(f'{copies} views of each of {N} rows need {V} plans (at least one), got {len(plans)}')
+        packed = pack_view_plans(plans, H, W)
+        if self._views_shape != (V, T, H, W):
+            self._views_ws = torch.empty(int(self.lib.cdrl_views_workspace_floats(V, T, H, W)), device=self.device)
+            self._views_shape = (V, T, H, W)
+        plans_dev = torch.from_numpy(packed.view(np.uint8)).to(self.device)
+        out = torch.empty((V, T, H, W, 3), dtype=torch.float32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(self.lib.cdrl_views_batch(C.c_void_p(x.data_ptr()), N, C.c_void_p(out.data_ptr()), V, T, H, W,
+                                             C.c_void_p(plans_dev.data_ptr()), C.c_void_p(self._views_ws.data_ptr()), stream),
+                   'cdrl_views_batch')
         return out
 
     def __call__(self, images, plan: dict) -> torch.Tensor:

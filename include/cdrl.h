@@ -937,6 +937,31 @@ int cdrl_augment_images(const float* in, float* out, int T, int H, int W, const 
 int64_t cdrl_augment_batch_workspace_floats(int E, int T, int H, int W);
 int cdrl_augment_images_batch(const float* in, float* out, int E, int T, int H, int W, const cdrl_aug_plan* plans_dev,
                               float* workspace, void* stream);
+/* Contrastive views (the SimCLR view pipeline the reference's rl/augmentations/simclr.py:pipeline states: crop + resize + flip ->
+ * colour jitter -> colour drop -> blur), one plan per view, shared by the T frames of its stack; scalars only, drawn by the host.
+ * rows [N][T][H][W][3] -> out [V][T][H][W][3]; view v reads row v % N (no doubled copy of the rows); any V >= 1, 1 <= N <= V.
+ *   1 crop window -> bilinear resize to H x W (tf.image.resize: half-pixel centres, no antialias; source (d + 0.5) * crop / full
+ *     - 0.5 clamped to [0, crop - 1], taps floor and min(floor + 1, crop - 1), x first, then y) -> horizontal flip; a full-size
+ *     crop without flip returns the input's bits
+ *   2 colour jitter as cdrl_augment_images (the contrast mean is that of the resized, brightness-shifted frame; fixed-order sums)
+ *   3 colour drop: 0.2989 r + 0.5870 g + 0.1140 b on all three channels
+ *   4 separable blur with blur_w, horizontal then vertical, replicate edge
+ * Four launches for any V; the same plans give the same bytes.  plans_dev: V plans IN DEVICE MEMORY; their contents are validated
+ * by the caller before the upload (the kernels clamp a crop window into the frame and treat a tap count that is even or outside
+ * 3..15 as 0).  Refused: null pointers, H or W < 2, V < 1, N outside [1, V], a workspace that overlaps rows or out.  workspace:
+ * cdrl_views_workspace_floats(V, T, H, W) floats (0 for a bad shape). */
+typedef struct cdrl_view_plan {
+    int32_t crop_y, crop_x, crop_h, crop_w;     /* crop window inside H x W; crop_h == H && crop_w == W: no crop */
+    int32_t flip;                               /* horizontal */
+    int32_t jitter;
+    float brightness, contrast, saturation, hue;
+    int32_t drop;                               /* colour drop */
+    int32_t blur_taps;                          /* 0, or odd, 3..15 */
+    float blur_w[16];                           /* 1-D weights, sum 1, drawn up by the host */
+} cdrl_view_plan;
+int64_t cdrl_views_workspace_floats(int V, int T, int H, int W);
+int cdrl_views_batch(const float* rows, int N, float* out, int V, int T, int H, int W, const cdrl_view_plan* plans_dev,
+                     float* workspace, void* stream);
 /* CARLAgent.policy_objective / value_objective on linear head outputs (core/carla_agent.py:394-428,
  * 469-486); writes d(loss)/d(lin) and 16 metric floats. */
 int cdrl_beta_ppo_loss(const float* lin, const float* adv, const float* old_logp, const float* speed,
