@@ -614,36 +614,50 @@ struct TensorSeg {      // one parameter tensor inside a flat arena
     int first_chunk;    // index of its first 1024-element chunk in the chunk table
     int nchunks;
 };
-// sq-norm per tensor -> norms[ntensors]; deterministic two-stage reduction
-int tensor_sqnorms(const float* g, const TensorSeg* segs_dev, int ntensors, const int* chunk_tensor_dev,
-                   const int64_t* chunk_off_dev, int nchunks, double* chunk_part, float* sqnorms, hipStream_t st,
-                   DevHP* tick_hp = nullptr, int tick_mask = 0, bool fold_final = false);
-// tick_hp / tick_mask (TICK_*): the chunk kernel also advances those step counters (| TICK_NADAM: and, for Nadam, their
-// m_caches to S_t of the new count); fold_final: no second
-// stage -- the consumer folds the chunk partials (clip_adam with chunk_part)
+// Device half of a chunk table: the trainable tensors of one model cut into 1024-element chunks, one workgroup each.  An empty
+// table (no list: the trunk's update, a learner without a trunk table) is ChunkTable{}.
+struct ChunkTable {
+    TensorSeg* segs = nullptr;
+    int* chunk_tensor = nullptr;        // [nchunks] tensor of the chunk
+    int64_t* chunk_off = nullptr;       // [nchunks] first element of the chunk, in the model's arena slice
+    int ntensors = 0, nchunks = 0;
+    double* chunk_part = nullptr;       // [nchunks] sum of squares of the chunk's gradient elements
+};
+// One model's trainable slice of the four flat arenas (weights, gradients, the optimizer's two slots), n elements.
+struct ArenaSlice {
+    float* p = nullptr;
+    const float* g = nullptr;
+    float* m = nullptr;
+    float* v = nullptr;
+    int64_t n = 0;
+};
+enum { WHICH_POLICY = 0, WHICH_VALUE = 1, WHICH_TRUNK = 2 };      // the optimizer whose DevHP fields a kernel reads
 enum TickMask : int { TICK_POLICY = 1, TICK_VALUE = 2, TICK_TRUNK = 4, TICK_NADAM = 8 };
-// the chunk kernel's tick alone, one thread (the trunk-only apply: no norm is wanted there)
+enum { NOT_TICKED = 0, TICKED = 1 };      // whether the optimizer's step counter was advanced before its update runs
+// First stage of the deterministic two-stage norm: tab.chunk_part[c] = float64 sum of squares of chunk c of g (one launch).  Its
+// block 0 also advances the step counters of tick_mask (TICK_*; | TICK_NADAM: and their m_caches to S_t of the new count).  The
+// second stage, the per-tensor fold, runs inside the consumers (clip_update, stats_fold_norms).
+int chunk_sqnorms_tick(const float* g, const ChunkTable& tab, DevHP* hp, int tick_mask, hipStream_t st);
+// the tick alone, one thread (the trunk-only apply: no norm is wanted there)
 int tick_steps(DevHP* hp, int tick_mask, hipStream_t st);
-int clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev /*or null*/,
-              const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms /*or null*/,
-              DevHP* hp, int which, hipStream_t st, const double* chunk_part = nullptr, int ticked = 0);
-// chunk_part: per-tensor norms folded here from tensor_sqnorms' chunk partials; ticked: the step counter was advanced already
-// The other optimizers of cdrl_config.optimizer (include/cdrl.h table; opt = CDRL_OPT_*) and polyak averaging, same arguments and
-// clip as clip_adam; m / v are the optimizer's slots in the adam_m / adam_v arenas.  Adam with polyak 1 IS clip_adam.
-// polyak < 1 (heads only): p = a * p_new + c * p_old in the same pass.
-// gate / gate_mode (GATE_MODE_*, below): the gated forms of the same kernels -- nothing is touched when the gate block says skip,
-// and in global mode the list's scale from the block replaces the per-tensor clip.  gate_mode 0 is the launch it always was.
+// One step of optimizer `opt` (CDRL_OPT_*, include/cdrl.h table) over the slice `a`, with the DevHP fields of `which` (WHICH_*); m / v
+// are the optimizer's slots in the adam_m / adam_v arenas.  One kernel for every optimizer, Keras Adam included.
+// tab: the slice's chunk table, whose chunk_part holds the gradient's partials -- every tensor is clipped by its norm (tf.clip_by_norm)
+// when the threshold of `which` is positive; ChunkTable{}: plain 1024-element chunks of the slice, no clip.
+// polyak < 1 (heads only): p = a * p_new + c * p_old in the same pass.  ticked: TICKED / NOT_TICKED.
+// gate / gate_mode (GATE_MODE_*, below): the gated forms -- nothing is touched when the gate block says skip, and in global mode the
+// list's scale from the block replaces the per-tensor clip.
 struct GateBlock;
-int clip_update(int opt, float polyak, float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev,
-                const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms, DevHP* hp, int which,
-                hipStream_t st, const double* chunk_part = nullptr, int ticked = 0, const GateBlock* gate = nullptr,
-                int gate_mode = 0);
+int clip_update(int opt, float polyak, const ArenaSlice& a, const ChunkTable& tab, DevHP* hp, int which, hipStream_t st,
+                int ticked = NOT_TICKED, const GateBlock* gate = nullptr, int gate_mode = 0);
 // counters to 0, Nadam m_caches to 1 (cdrl_learner_reset_optimizer_steps)
 int reset_steps(DevHP* hp, hipStream_t st);
 // counters to t[0..2] (policy, value, dynamics), Nadam m_caches to m_cache[0..2], passed to the kernel by value
 // (cdrl_learner_set_optimizer_state); the float block in front of t_policy is not written
 int set_steps(DevHP* hp, const int t[3], const float m_cache[3], hipStream_t st);
-int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, hipStream_t st);
+// two device-to-device copies in one launch; gate (or null): nothing is copied when the gate block says skip
+int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, hipStream_t st,
+             const GateBlock* gate = nullptr);
 
 // Gradient gate (cdrl_config.clip_mode = global and / or skip_nonfinite; include/cdrl.h): the norm of an optimizer's whole gradient
 // list, known on the device before any element of the list is applied.  One block per learner (shared like DevHP), written by
@@ -658,28 +672,22 @@ struct GateBlock {
 enum { GATE_GLOBAL = 1, GATE_GUARD = 2, GATE_TRUNK = 4 /* the apply consumes the trunk's gradient */, GATE_NADAM = 8,
        GATE_HEAD_PARTS = 16 /* the head's chunk partials are wanted whatever the gate needs (train stats) */ };
 enum { GATE_MODE_OFF = 0, GATE_MODE_TENSOR = 1 /* skip only, per-tensor clip */, GATE_MODE_GLOBAL = 2 /* skip and list scale */ };
-// Chunk partials (as sqnorm_chunk_kernel forms them) of the head's table and, with nchunks_t > 0, of the trunk's, in one launch.  A
+// Chunk partials (chunk_sqnorms_tick's, without the tick) of the head's table and, with GATE_TRUNK, of the trunk's, in one launch.  A
 // list whose norm neither the mode nor the guard needs (threshold <= 0 on the device, no guard) is not read.
-int gate_chunk_sqnorms(const float* g_head, const TensorSeg* segs_h, const int* chunk_tensor_h, const int64_t* chunk_off_h,
-                       int nchunks_h, double* part_h, const float* g_trunk, const TensorSeg* segs_t, const int* chunk_tensor_t,
-                       const int64_t* chunk_off_t, int nchunks_t, double* part_t, const DevHP* hp, const GateBlock* gate, int head,
-                       int flags, hipStream_t st);
+int gate_chunk_sqnorms(const float* g_head, const ChunkTable& tab_h, const float* g_trunk, const ChunkTable& tab_t, const DevHP* hp,
+                       const GateBlock* gate, int head, int flags, hipStream_t st);
 // One workgroup: folds the partials into the lists' squared norms (fixed order), writes scales, skip flag, last norms and the
 // skipped / applied counter, and -- unless the step is skipped -- ticks the step counters (head; trunk with GATE_TRUNK) and advances
-// the Nadam m_caches, as sqnorm_chunk_kernel does on the ungated path.
-int gate_decide(const double* part_h, int nchunks_h, const double* part_t, int nchunks_t, DevHP* hp, GateBlock* gate, int head,
-                int flags, hipStream_t st);
-int copy_two_gated(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, const GateBlock* gate,
-                   hipStream_t st);
+// the Nadam m_caches, as chunk_sqnorms_tick does on the ungated path.
+int gate_decide(const ChunkTable& tab_h, const ChunkTable& tab_t, DevHP* hp, GateBlock* gate, int head, int flags, hipStream_t st);
 
 // ---------------------------------------------------------------- update diagnostics (train_stats.hip)
 // Chunk partials of a chunk table (sum of squares per 1024-element chunk, float64): one wave per chunk, no LDS.  Same partials
-// contract as sqnorm_chunk_kernel (which also ticks the optimizer counters and is the clip path's): deterministic, no atomics.
-int stats_chunk_sqnorms(const float* g, const TensorSeg* segs_dev, const int* chunk_tensor_dev, const int64_t* chunk_off_dev,
-                        int nchunks, double* chunk_part, hipStream_t st);
+// contract as chunk_sqnorms_tick (which also ticks the optimizer counters and is the clip path's): deterministic, no atomics.
+int stats_chunk_sqnorms(const float* g, const ChunkTable& tab, hipStream_t st);
 // One ring row of an apply step (layout: include/cdrl.h, cdrl_train_stats_layout).  ring = [header int32 words | rows x width floats];
 // the row index is header[0] % rows, read on the device.  stats_fold_norms writes sqrt(per-tensor sum of chunk partials) of the head
-// (table a) at off_a and of the trunk (table b, nb may be 0) at off_b; stats_write_row, enqueued BEHIND it, writes everything else,
+// (table a) at off_a and of the trunk (table b, may be empty) at off_b; stats_write_row, enqueued BEHIND it, writes everything else,
 // zeroes the unused norm slots and advances header[0] (and header[1] when it overwrote an unread row).
 enum StatsSlot : int {      // offsets inside a row's scalar block (KIND, T_HEAD, T_DYNAMICS hold int32 bit patterns)
     STATS_KIND = 0, STATS_T_HEAD = 1, STATS_T_DYNAMICS = 2, STATS_LR = 3, STATS_LR_DYNAMICS = 4, STATS_CLIP_RATIO = 5,
@@ -696,8 +704,8 @@ struct StatsRowArgs {
     int off_scalars, off_metrics, off_norms, off_trunk;
     int n_head, n_trunk;
 };
-int stats_fold_norms(float* ring, int header, int rows, int width, const TensorSeg* segs_a, int na, const double* part_a, int off_a,
-                     const TensorSeg* segs_b, int nb, const double* part_b, int off_b, hipStream_t st);
+int stats_fold_norms(float* ring, int header, int rows, int width, const ChunkTable& tab_a, int off_a, const ChunkTable& tab_b,
+                     int off_b, hipStream_t st);
 int stats_write_row(const StatsRowArgs& a, hipStream_t st);
 int stats_reset_ring(float* ring, hipStream_t st);
 

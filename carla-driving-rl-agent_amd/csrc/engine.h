@@ -434,7 +434,8 @@ private:
     int trunk_backward_tail(hipStream_t st);
     // entry of every pass (fwd / bwd: the halves to run): gradient-scale hint, graph key, graph replay or eager launch
     int run_pass(const PassSpec& s, hipStream_t caller, bool fwd = true, bool bwd = true);
-    int update_old_policy_impl(hipStream_t st);
+    int update_old_policy_impl(hipStream_t st, const GateBlock* gate = nullptr);
+    ArenaSlice arena_slice(int model) const;      // the trainable slice of a model in params / grads / adam_m / adam_v
     // the ungated apply of one head (0 policy, 1 value); with_trunk = false: as gated_apply's
     int head_apply(int head, bool with_trunk, hipStream_t st);
     int policy_apply_impl(hipStream_t st);
@@ -582,12 +583,7 @@ private:
     bool trunk_table() const { return !frozen() && (cfg_.train_stats > 0 || gate_on()); }
     // optimiser tables (device, inside workspace)
     struct SegTable {
-        TensorSeg* segs = nullptr;
-        int* chunk_tensor = nullptr;
-        int64_t* chunk_off = nullptr;
-        int ntensors = 0, nchunks = 0;
-        double* chunk_part = nullptr;
-        float* sqnorms = nullptr;
+        ChunkTable dev;
         std::vector<TensorSeg> h_segs;
         std::vector<int> h_chunk_tensor;
         std::vector<int64_t> h_chunk_off;

@@ -1657,11 +1657,11 @@ void Learner::build(bool dry) {
                 ++nt;
                 nch += (pi.numel + 1023) / 1024;
             }
-        s.segs = reinterpret_cast<TensorSeg*>(alloc((size_t)nt * sizeof(TensorSeg) / sizeof(float)));
-        s.chunk_tensor = reinterpret_cast<int*>(alloc((size_t)nch));
-        s.chunk_off = reinterpret_cast<int64_t*>(alloc((size_t)nch * 2));
-        s.chunk_part = alloc_d((size_t)nch);
-        s.sqnorms = alloc((size_t)nt);
+        s.dev.segs = reinterpret_cast<TensorSeg*>(alloc((size_t)nt * sizeof(TensorSeg) / sizeof(float)));
+        s.dev.chunk_tensor = reinterpret_cast<int*>(alloc((size_t)nch));
+        s.dev.chunk_off = reinterpret_cast<int64_t*>(alloc((size_t)nch * 2));
+        s.dev.chunk_part = alloc_d((size_t)nch);
+        alloc((size_t)nt);      // unnamed padding: every offset behind the tables, and so the workspace size, is pinned by the planner's tests
     }
     if (gate_on()) {
         gate_dev_ = reinterpret_cast<GateBlock*>(alloc(sizeof(GateBlock) / sizeof(float) + 4));
@@ -1701,8 +1701,8 @@ void Learner::build_seg_tables() {
             }
             s.h_segs.push_back(seg);
         }
-        s.ntensors = (int)s.h_segs.size();
-        s.nchunks = (int)s.h_chunk_tensor.size();
+        s.dev.ntensors = (int)s.h_segs.size();
+        s.dev.nchunks = (int)s.h_chunk_tensor.size();
     }
 }
 
@@ -1719,10 +1719,10 @@ int Learner::upload_seg_tables() {
         CDRL_HIP(hipMemcpy(d_gpack_, h_gpack_.data(), h_gpack_.size() * sizeof(GemmX3Pack), hipMemcpyHostToDevice));
     for (int m = trunk_table() ? 0 : 1; m <= 2; ++m) {
         SegTable& s = seg_[m];
-        CDRL_HIP(hipMemcpy(s.segs, s.h_segs.data(), s.h_segs.size() * sizeof(TensorSeg), hipMemcpyHostToDevice));
-        CDRL_HIP(hipMemcpy(s.chunk_tensor, s.h_chunk_tensor.data(), s.h_chunk_tensor.size() * sizeof(int),
+        CDRL_HIP(hipMemcpy(s.dev.segs, s.h_segs.data(), s.h_segs.size() * sizeof(TensorSeg), hipMemcpyHostToDevice));
+        CDRL_HIP(hipMemcpy(s.dev.chunk_tensor, s.h_chunk_tensor.data(), s.h_chunk_tensor.size() * sizeof(int),
                            hipMemcpyHostToDevice));
-        CDRL_HIP(hipMemcpy(s.chunk_off, s.h_chunk_off.data(), s.h_chunk_off.size() * sizeof(int64_t),
+        CDRL_HIP(hipMemcpy(s.dev.chunk_off, s.h_chunk_off.data(), s.h_chunk_off.size() * sizeof(int64_t),
                            hipMemcpyHostToDevice));
     }
     return 0;
@@ -2169,14 +2169,18 @@ int Learner::trunk_apply(hipStream_t caller) {
     return launch(caller, {KEY_TRUNK_APPLY}, true, [&](hipStream_t st) -> int { return trunk_apply_impl(st); });
 }
 
-// order as in head_apply: the trunk's update (unclipped, which = 2, not yet ticked), the tick behind it -- the chunk-norm kernel's
+// order as in head_apply: the trunk's update (unclipped, not yet ticked), the tick behind it -- the chunk-norm kernel's
 // tick on its own: a learner without train stats has no trunk chunk table, and this step needs no norm
 int Learner::trunk_apply_impl(hipStream_t st) {
-    const int64_t to = tr_offset(M_TRUNK);
     const int opt = cfg_.optimizer;
-    CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK], nullptr,
-                         nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
+    CDRL_TRY(clip_update(opt, 1.0f, arena_slice(M_TRUNK), ChunkTable{}, hp_dev_, WHICH_TRUNK, st));
     return tick_steps(hp_dev_, TICK_TRUNK | (opt == CDRL_OPT_NADAM ? TICK_NADAM : 0), st);
+}
+
+// the trainable slice of `model` in the four arenas
+ArenaSlice Learner::arena_slice(int model) const {
+    const int64_t o = tr_offset(model);
+    return ArenaSlice{buf_.params + o, buf_.grads + o, buf_.adam_m + o, buf_.adam_v + o, tr_size_[model]};
 }
 
 int Learner::joint_apply(hipStream_t caller) {
@@ -2198,11 +2202,11 @@ int Learner::update_old_policy(hipStream_t caller) {
     return launch(caller, {}, false, [&](hipStream_t st) -> int { return update_old_policy_impl(st); });
 }
 
-int Learner::update_old_policy_impl(hipStream_t st) {
+int Learner::update_old_policy_impl(hipStream_t st, const GateBlock* gate) {
     // old_policy.set_weights(policy.get_weights()): all weights incl. BN moving statistics
-    // (reference core/networks.py:281-285)
+    // (reference core/networks.py:281-285); gate: the copy of a gated apply, which a skipped step does not make
     return copy_two(buf_.params + tr_offset(M_OLD_POLICY), buf_.params + tr_offset(M_POLICY), tr_size_[M_POLICY],
-                    buf_.params + st_offset(M_OLD_POLICY), buf_.params + st_offset(M_POLICY), st_size_[M_POLICY], st);
+                    buf_.params + st_offset(M_OLD_POLICY), buf_.params + st_offset(M_POLICY), st_size_[M_POLICY], st, gate);
 }
 
 int Learner::policy_apply(hipStream_t caller) {
@@ -2214,25 +2218,18 @@ int Learner::policy_apply(hipStream_t caller) {
 // return at once when the gate said skip.  Both updates run behind the tick.  No host read: the sequence is capturable.
 int Learner::gated_apply(int head, hipStream_t st, bool with_trunk) {
     const int hm = head == 0 ? M_POLICY : M_VALUE;
-    const int64_t to = tr_offset(M_TRUNK), ho = tr_offset(hm);
     const int opt = cfg_.optimizer;
     const int flags = (cfg_.clip_mode == CDRL_CLIP_GLOBAL ? GATE_GLOBAL : 0) | (cfg_.skip_nonfinite ? GATE_GUARD : 0) |
                       (frozen() || !with_trunk ? 0 : GATE_TRUNK) | (opt == CDRL_OPT_NADAM ? GATE_NADAM : 0) |
                       (cfg_.train_stats > 0 ? GATE_HEAD_PARTS : 0);
     const int mode = cfg_.clip_mode == CDRL_CLIP_GLOBAL ? GATE_MODE_GLOBAL : GATE_MODE_TENSOR;
-    SegTable &s = seg_[hm], &t = seg_[M_TRUNK];
-    CDRL_TRY(gate_chunk_sqnorms(buf_.grads + ho, s.segs, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part, buf_.grads + to, t.segs,
-                                t.chunk_tensor, t.chunk_off, t.nchunks, t.chunk_part, hp_dev_, gate_dev_, head, flags, st));
-    CDRL_TRY(gate_decide(s.chunk_part, s.nchunks, t.chunk_part, t.nchunks, hp_dev_, gate_dev_, head, flags, st));
-    if (!frozen() && with_trunk)
-        CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK],
-                             nullptr, nullptr, 0, nullptr, nullptr, hp_dev_, 2, st, nullptr, 1, gate_dev_, mode));
-    if (head == 0)
-        CDRL_TRY(copy_two_gated(buf_.params + tr_offset(M_OLD_POLICY), buf_.params + tr_offset(M_POLICY), tr_size_[M_POLICY],
-                                buf_.params + st_offset(M_OLD_POLICY), buf_.params + st_offset(M_POLICY), st_size_[M_POLICY], gate_dev_,
-                                st));
-    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + ho, buf_.grads + ho, buf_.adam_m + ho, buf_.adam_v + ho, tr_size_[hm],
-                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, head, st, s.chunk_part, 1, gate_dev_, mode));
+    const ChunkTable &s = seg_[hm].dev, &t = seg_[M_TRUNK].dev;
+    const ArenaSlice ha = arena_slice(hm), ta = arena_slice(M_TRUNK);
+    CDRL_TRY(gate_chunk_sqnorms(ha.g, s, ta.g, t, hp_dev_, gate_dev_, head, flags, st));
+    CDRL_TRY(gate_decide(s, t, hp_dev_, gate_dev_, head, flags, st));
+    if (!frozen() && with_trunk) CDRL_TRY(clip_update(opt, 1.0f, ta, ChunkTable{}, hp_dev_, WHICH_TRUNK, st, TICKED, gate_dev_, mode));
+    if (head == 0) CDRL_TRY(update_old_policy_impl(st, gate_dev_));
+    CDRL_TRY(clip_update(opt, cfg_.polyak, ha, s, hp_dev_, head, st, TICKED, gate_dev_, mode));
     return cfg_.train_stats > 0 ? stats_row(head, st) : 0;
 }
 
@@ -2242,21 +2239,17 @@ int Learner::gated_apply(int head, hipStream_t st, bool with_trunk) {
 // (another cdrl_config.optimizer: its step in place of Adam's, same launches; polyak < 1: the head is averaged in its update)
 int Learner::head_apply(int head, bool with_trunk, hipStream_t st) {
     const int hm = head == 0 ? M_POLICY : M_VALUE;
-    const int64_t to = tr_offset(M_TRUNK), ho = tr_offset(hm);
     const int opt = cfg_.optimizer;
     const bool trunk = with_trunk && !frozen();
-    if (trunk)
-        CDRL_TRY(clip_update(opt, 1.0f, buf_.params + to, buf_.grads + to, buf_.adam_m + to, buf_.adam_v + to, tr_size_[M_TRUNK],
-                             nullptr, nullptr, 0, nullptr, nullptr, hp_dev_, 2, st));
-    SegTable& s = seg_[hm];
-    // four launches instead of seven (round 6): the chunk kernel of the norms also advances the trunk's step counter (its update ran in front)
-    // and the head's (its update runs behind and is told so); the per-tensor fold of the chunk partials happens inside clip_adam
+    if (trunk) CDRL_TRY(clip_update(opt, 1.0f, arena_slice(M_TRUNK), ChunkTable{}, hp_dev_, WHICH_TRUNK, st));
+    const ChunkTable& s = seg_[hm].dev;
+    const ArenaSlice ha = arena_slice(hm);
+    // four launches: the chunk kernel of the norms also advances the trunk's step counter (its update ran in front) and the head's (its
+    // update runs behind and is told so); the per-tensor fold of the chunk partials happens inside the head's update kernel
     const int tick = (head == 0 ? TICK_POLICY : TICK_VALUE) | (trunk ? TICK_TRUNK : 0) | (opt == CDRL_OPT_NADAM ? TICK_NADAM : 0);
-    CDRL_TRY(tensor_sqnorms(buf_.grads + ho, s.segs, s.ntensors, s.chunk_tensor, s.chunk_off, s.nchunks, s.chunk_part, s.sqnorms, st,
-                            hp_dev_, tick, true));
+    CDRL_TRY(chunk_sqnorms_tick(ha.g, s, hp_dev_, tick, st));
     if (head == 0) CDRL_TRY(update_old_policy_impl(st));
-    CDRL_TRY(clip_update(opt, cfg_.polyak, buf_.params + ho, buf_.grads + ho, buf_.adam_m + ho, buf_.adam_v + ho, tr_size_[hm],
-                         s.chunk_tensor, s.chunk_off, s.nchunks, s.segs, nullptr, hp_dev_, head, st, s.chunk_part, 1));
+    CDRL_TRY(clip_update(opt, cfg_.polyak, ha, s, hp_dev_, head, st, TICKED));
     return cfg_.train_stats > 0 ? stats_row(head, st) : 0;
 }
 
@@ -2268,12 +2261,9 @@ int Learner::value_apply_impl(hipStream_t st) { return gate_on() ? gated_apply(1
 // behind the updates: one extra read of the trunk gradient, a fold per tensor, the row writer.
 int Learner::stats_row(int kind, hipStream_t st) {
     const int head = kind == 0 ? M_POLICY : M_VALUE;
-    SegTable &h = seg_[head], &t = seg_[M_TRUNK];
-    const int nt = stats_tensors(M_TRUNK);
-    if (nt > 0)
-        CDRL_TRY(stats_chunk_sqnorms(buf_.grads + tr_offset(M_TRUNK), t.segs, t.chunk_tensor, t.chunk_off, t.nchunks, t.chunk_part, st));
-    CDRL_TRY(stats_fold_norms(stats_ring_, STATS_HEADER, stats_rows(), stats_width(), h.segs, h.ntensors, h.chunk_part, stats_off_norms(),
-                              t.segs, nt, t.chunk_part, stats_off_trunk(), st));
+    const ChunkTable &h = seg_[head].dev, &t = seg_[M_TRUNK].dev;      // (frozen trunk: it has no table, t is empty)
+    CDRL_TRY(stats_chunk_sqnorms(arena_slice(M_TRUNK).g, t, st));
+    CDRL_TRY(stats_fold_norms(stats_ring_, STATS_HEADER, stats_rows(), stats_width(), h, stats_off_norms(), t, stats_off_trunk(), st));
     StatsRowArgs a;
     a.ring = stats_ring_;
     a.header = STATS_HEADER;
@@ -2292,7 +2282,7 @@ int Learner::stats_row(int kind, hipStream_t st) {
     a.off_norms = stats_off_norms();
     a.off_trunk = stats_off_trunk();
     a.n_head = h.ntensors;
-    a.n_trunk = nt;
+    a.n_trunk = t.ntensors;
     return stats_write_row(a, st);
 }
 

@@ -1,39 +1,20 @@
-// Per-tensor clip-by-norm + Keras Adam over flat parameter arenas (gfx950).
+// Per-tensor clip-by-norm + the optimizer step over flat parameter arenas (gfx950).
 //
 // Reference: utils.clip_gradients -> tf.clip_by_norm per tensor (rl/utils.py:120-121), applied to
 // the policy / value heads only (F9); Keras Adam (beta1 .9, beta2 .999, eps 1e-7) in the fused
 // `ResourceApplyAdam` form:
 //     alpha = lr * sqrt(1 - b2^t) / (1 - b1^t);  m += (g - m)(1 - b1);  v += (g*g - v)(1 - b2)
 //     theta -= m * alpha / (sqrt(v) + eps)
-// Hyper-parameters and the Adam step counters live in a device block (DevHP) so that a captured
+// Hyper-parameters and the step counters live in a device block (DevHP) so that a captured
 // hipGraph of the whole update step can be replayed while learning rates change between steps.
 // One workgroup handles one 1024-element chunk of one tensor: HBM-bound streaming, no atomics,
-// norms reduced in two deterministic stages.
-// The seven other Keras optimizers of cdrl_config.optimizer and polyak averaging: clip_update (table in include/cdrl.h).
-#include "cdrl_kernels.h"
+// norms reduced in two deterministic stages (bodies: optim_bodies.h).
+// One update kernel, clip_update_kernel<OPT, GATE>, serves Adam, the seven other Keras optimizers of cdrl_config.optimizer (table in
+// include/cdrl.h), polyak averaging and the gated forms.
+#include "optim_bodies.h"
 #include "../../include/cdrl.h"
 
 namespace cdrl {
-
-#define CHUNK 1024
-
-// Keras Nadam's momentum schedule (schedule decay 0.004), float32 as TensorFlow computes it: mu_t = beta1 (1 - 0.5 * 0.96^(0.004 t)).
-// S_t = m_cache * mu_t is formed by the trunk's update (ahead of its tick) and stored by the chunk kernel that ticks the counter:
-// one function, so both produce the same bits.
-__device__ __forceinline__ float nadam_mu(float b1, int t) { return b1 * (1.0f - 0.5f * powf(0.96f, 0.004f * (float)t)); }
-
-// Step counters advanced by `tick` (TickMask bits: 1 policy, 2 value, 4 trunk; 8: Nadam -- each ticked optimizer's m_cache also
-// becomes S_t of its new count).  One thread.
-__device__ __forceinline__ void tick_counters(DevHP* hp, int tick) {
-    if (tick & 1) hp->t_policy += 1;
-    if (tick & 2) hp->t_value += 1;
-    if (tick & 4) hp->t_dynamics += 1;
-    if (tick & 8) {
-        if (tick & 1) hp->m_cache_policy = hp->m_cache_policy * nadam_mu(hp->beta1, hp->t_policy);
-        if (tick & 2) hp->m_cache_value = hp->m_cache_value * nadam_mu(hp->beta1, hp->t_value);
-        if (tick & 4) hp->m_cache_dynamics = hp->m_cache_dynamics * nadam_mu(hp->beta1, hp->t_dynamics);
-    }
-}
 
 // the tick without a norm (the trunk-only apply: its update ran in front, nothing runs behind)
 __global__ void tick_kernel(DevHP* hp, int tick) {
@@ -50,165 +31,50 @@ int tick_steps(DevHP* hp, int tick_mask, hipStream_t st) {
     return 0;
 }
 
-__global__ void __launch_bounds__(256) sqnorm_chunk_kernel(const float* __restrict__ g,
-                                                           const TensorSeg* __restrict__ segs,
-                                                           const int* __restrict__ chunk_tensor,
-                                                           const int64_t* __restrict__ chunk_off,
-                                                           double* __restrict__ chunk_part, DevHP* hp, int tick) {
+// Step counters advanced here instead of by a launch of their own: the trunk's (its update ran in FRONT of this kernel) and the head's,
+// whose update runs BEHIND it and is told so (clip_update's `ticked`).
+__global__ void __launch_bounds__(256) sqnorm_chunk_kernel(const float* __restrict__ g, ChunkTable tab, DevHP* hp, int tick) {
     __shared__ double sm[256];
     const int c = blockIdx.x;
-    // Adam step counters advanced here instead of by launches of their own: the trunk's (its update ran in FRONT of this kernel) and the
-    // head's, whose update runs BEHIND it and is told so (clip_adam's `ticked`)
     if (tick > 0 && c == 0 && threadIdx.x == 0) tick_counters(hp, tick);
-    const TensorSeg s = segs[chunk_tensor[c]];
-    const int64_t beg = chunk_off[c];
-    int64_t end = beg + CHUNK;
-    if (end > s.off + s.n) end = s.off + s.n;
-    double acc = 0.0;
-    for (int64_t i = beg + threadIdx.x; i < end; i += 256) {
-        const double v = (double)g[i];
-        acc += v * v;
-    }
-    sm[threadIdx.x] = acc;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) sm[threadIdx.x] += sm[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) chunk_part[c] = sm[0];
-}
-
-// one wave per tensor: lane l sums the chunks l, l + 64, ... in order, then a fixed shuffle tree (one THREAD per tensor walked up to
-// 768 chunk partials one dependent load at a time: 17 us)
-__global__ void __launch_bounds__(256) sqnorm_final_kernel(const TensorSeg* __restrict__ segs, int ntensors,
-                                                           const double* __restrict__ chunk_part, float* __restrict__ sqnorms) {
-    const int lane = threadIdx.x & 63;
-    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= ntensors) return;
-    const TensorSeg s = segs[t];
-    double acc = 0.0;
-    for (int c = lane; c < s.nchunks; c += 64) acc += chunk_part[s.first_chunk + c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if (lane == 0) sqnorms[t] = (float)acc;
-}
-
-int tensor_sqnorms(const float* g, const TensorSeg* segs_dev, int ntensors, const int* chunk_tensor_dev,
-                   const int64_t* chunk_off_dev, int nchunks, double* chunk_part, float* sqnorms, hipStream_t st, DevHP* tick_hp,
-                   int tick_mask, bool fold_final) {
-    hipLaunchKernelGGL(sqnorm_chunk_kernel, dim3(nchunks), dim3(256), 0, st, g, segs_dev, chunk_tensor_dev, chunk_off_dev,
-                       chunk_part, tick_hp, tick_hp ? tick_mask : 0);
-    CDRL_LAUNCH_CHECK();
-    if (fold_final) return 0;           // the consumer (clip_adam with chunk_part) folds the chunk partials of its tensor itself
-    hipLaunchKernelGGL(sqnorm_final_kernel, dim3(cdiv(ntensors, 4)), dim3(256), 0, st, segs_dev, ntensors, chunk_part,
-                       sqnorms);
-    CDRL_LAUNCH_CHECK();
-    return 0;
-}
-
-__global__ void __launch_bounds__(256) clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                        const int* __restrict__ chunk_tensor,
-                                                        const int64_t* __restrict__ chunk_off,
-                                                        const TensorSeg* __restrict__ segs,
-                                                        const float* __restrict__ sqnorms, const DevHP* __restrict__ hp,
-                                                        int which, const double* __restrict__ chunk_part, int ticked) {
     int64_t beg, end;
-    float cn = 0.0f, denom = 1.0f;
-    const float clip_norm = which == 0 ? hp->clip_norm_policy : (which == 1 ? hp->clip_norm_value : 0.0f);
-    if (chunk_tensor) {
-        const int c = blockIdx.x;
-        const int t = chunk_tensor[c];
-        const TensorSeg s = segs[t];
-        beg = chunk_off[c];
-        end = beg + CHUNK;
-        if (end > s.off + s.n) end = s.off + s.n;
-        if ((sqnorms || chunk_part) && clip_norm > 0.0f) {
-            float l2;
-            if (chunk_part) {
-                // the tensor's squared norm from its chunk partials, exactly as sqnorm_final_kernel folds them (lane l: chunks l, l + 64,
-                // ... in order, fixed shuffle tree) -- every wave of every block of the tensor computes the same bits
-                const int lane = threadIdx.x & 63;
-                double acc = 0.0;
-                for (int cc = lane; cc < s.nchunks; cc += 64) acc += chunk_part[s.first_chunk + cc];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-                l2 = (float)__shfl(acc, 0, 64);
-            } else {
-                l2 = sqnorms[t];
-            }
-            const float norm = l2 > 0.0f ? sqrtf(l2) : l2;
-            cn = clip_norm;
-            denom = fmaxf(norm, clip_norm);
-        }
-    } else {
-        beg = (int64_t)blockIdx.x * CHUNK;
-        end = beg + CHUNK;
-        if (end > n) end = n;
-    }
-    const float lr = which == 0 ? hp->lr_policy : (which == 1 ? hp->lr_value : hp->lr_dynamics);
-    const int t1 = (which == 0 ? hp->t_policy : (which == 1 ? hp->t_value : hp->t_dynamics)) + (ticked ? 0 : 1);
-    const float b1 = hp->beta1, b2 = hp->beta2, eps = hp->eps;
-    const float alpha = lr * sqrtf(1.0f - powf(b2, (float)t1)) / (1.0f - powf(b1, (float)t1));
-    for (int64_t i = beg + threadIdx.x; i < end; i += 256) {
-        float gi = g[i];
-        if (cn > 0.0f) gi = (gi * cn) / denom;
-        float mi = m[i], vi = v[i];
-        mi += (gi - mi) * (1.0f - b1);
-        vi += (gi * gi - vi) * (1.0f - b2);
-        m[i] = mi;
-        v[i] = vi;
-        p[i] -= (mi * alpha) / (sqrtf(vi) + eps);
-    }
+    chunk_bounds(tab, c, beg, end);
+    const double sum = chunk_sqsum(g, beg, end, sm);
+    if (threadIdx.x == 0) tab.chunk_part[c] = sum;
 }
 
-int clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev,
-              const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms, DevHP* hp,
-              int which, hipStream_t st, const double* chunk_part, int ticked) {
-    const int grid = chunk_tensor_dev ? nchunks : (int)cdiv64(n, CHUNK);
-    hipLaunchKernelGGL(clip_adam_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, n, chunk_tensor_dev, chunk_off_dev,
-                       segs_dev, sqnorms, hp, which, chunk_part, ticked);
+int chunk_sqnorms_tick(const float* g, const ChunkTable& tab, DevHP* hp, int tick_mask, hipStream_t st) {
+    hipLaunchKernelGGL(sqnorm_chunk_kernel, dim3(tab.nchunks), dim3(256), 0, st, g, tab, hp, tick_mask);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
 
-// clip + one step of the optimizer OPT (include/cdrl.h table) + optional polyak averaging.  The chunk / clip prologue is
-// clip_adam_kernel's, kept as a copy so that Adam's own kernel stays exactly as it was.  Per element one streaming pass over p, g
+// clip + one step of the optimizer OPT (include/cdrl.h table) + optional polyak averaging.  Per element one streaming pass over p, g
 // and the slots the optimizer uses (none for SGD; never the others).
+// chunk_tensor (or null: plain chunks of [0, n), no clip): the chunk table; with a positive threshold every block folds the chunk
+// partials of its tensor into the norm the tensor is clipped by.
 // GATE (GATE_MODE_*): the gated forms.  Both return before touching anything when the gate block says skip; GATE_MODE_GLOBAL takes
 // the list's scale s from the block in place of the per-tensor clip (cn = s, denom = 1: the loop's g * cn / denom is g * s).
-template <int OPT, int GATE = GATE_MODE_OFF>
+template <int OPT, int GATE>
 __global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                           const int* __restrict__ chunk_tensor,
                                                           const int64_t* __restrict__ chunk_off,
-                                                          const TensorSeg* __restrict__ segs,
-                                                          const float* __restrict__ sqnorms, const DevHP* __restrict__ hp,
+                                                          const TensorSeg* __restrict__ segs, const DevHP* __restrict__ hp,
                                                           int which, const double* __restrict__ chunk_part, int ticked,
                                                           int blend, float pa, float pc, const GateBlock* __restrict__ gate) {
     if (GATE != GATE_MODE_OFF && gate->skip) return;
     int64_t beg, end;
     float cn = 0.0f, denom = 1.0f;
-    const float clip_norm = which == 0 ? hp->clip_norm_policy : (which == 1 ? hp->clip_norm_value : 0.0f);
+    const float clip_norm = hp_clip_norm(hp, which);
     if (chunk_tensor) {
         const int c = blockIdx.x;
-        const int t = chunk_tensor[c];
-        const TensorSeg s = segs[t];
+        const TensorSeg s = segs[chunk_tensor[c]];
         beg = chunk_off[c];
         end = beg + CHUNK;
         if (end > s.off + s.n) end = s.off + s.n;
-        if (GATE != GATE_MODE_GLOBAL && (sqnorms || chunk_part) && clip_norm > 0.0f) {
-            float l2;
-            if (chunk_part) {       // (clip_adam_kernel: same fold, same bits)
-                const int lane = threadIdx.x & 63;
-                double acc = 0.0;
-                for (int cc = lane; cc < s.nchunks; cc += 64) acc += chunk_part[s.first_chunk + cc];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-                l2 = (float)__shfl(acc, 0, 64);
-            } else {
-                l2 = sqnorms[t];
-            }
+        if (GATE != GATE_MODE_GLOBAL && clip_norm > 0.0f) {
+            const float l2 = (float)fold_chunk_parts(chunk_part, s);
             const float norm = l2 > 0.0f ? sqrtf(l2) : l2;
             cn = clip_norm;
             denom = fmaxf(norm, clip_norm);
@@ -218,9 +84,9 @@ __global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p,
         end = beg + CHUNK;
         if (end > n) end = n;
     }
-    if (GATE == GATE_MODE_GLOBAL) cn = which == 2 ? gate->scale_trunk : gate->scale_head;
-    const float lr = which == 0 ? hp->lr_policy : (which == 1 ? hp->lr_value : hp->lr_dynamics);
-    const int t1 = (which == 0 ? hp->t_policy : (which == 1 ? hp->t_value : hp->t_dynamics)) + (ticked ? 0 : 1);
+    if (GATE == GATE_MODE_GLOBAL) cn = which == WHICH_TRUNK ? gate->scale_trunk : gate->scale_head;
+    const float lr = hp_lr(hp, which);
+    const int t1 = hp_t(hp, which) + (ticked ? 0 : 1);
     const float b1 = hp->beta1, b2 = hp->beta2, eps = hp->eps;
     // per-step scalars, float32 (Keras _prepare_local / the training ops' scalar operands)
     float k0 = 0.0f, k1 = 0.0f, k2 = 0.0f, k3 = 0.0f, k4 = 0.0f;
@@ -235,9 +101,9 @@ __global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p,
     } else if (OPT == CDRL_OPT_ADAMAX) {
         k0 = lr / (1.0f - powf(b1, (float)t1));
     } else if (OPT == CDRL_OPT_NADAM) {
-        const float mc = which == 0 ? hp->m_cache_policy : (which == 1 ? hp->m_cache_value : hp->m_cache_dynamics);
+        const float mc = hp_m_cache(hp, which);
         const float mu = nadam_mu(b1, t1), mu1 = nadam_mu(b1, t1 + 1);
-        const float st = ticked ? mc : mc * mu;      // S_t (ticked: the chunk kernel stored it already)
+        const float st = ticked ? mc : mc * mu;      // S_t (ticked: the tick stored it already)
         k0 = 1.0f - mu;                              // one_minus_m_t
         k1 = 1.0f - st;                              // one_minus_m_schedule_new
         k2 = 1.0f - st * mu1;                        // one_minus_m_schedule_next
@@ -300,22 +166,18 @@ __global__ void __launch_bounds__(256) clip_update_kernel(float* __restrict__ p,
     }
 }
 
-int clip_update(int opt, float polyak, float* p, const float* g, float* m, float* v, int64_t n, const int* chunk_tensor_dev,
-                const int64_t* chunk_off_dev, int nchunks, const TensorSeg* segs_dev, const float* sqnorms, DevHP* hp, int which,
-                hipStream_t st, const double* chunk_part, int ticked, const GateBlock* gate, int gate_mode) {
+int clip_update(int opt, float polyak, const ArenaSlice& a, const ChunkTable& tab, DevHP* hp, int which, hipStream_t st, int ticked,
+                const GateBlock* gate, int gate_mode) {
     const int blend = polyak < 1.0f;
     if (gate_mode != GATE_MODE_OFF && !gate) {
         set_error("clip_update: gated form without a gate block");
         return -1;
     }
-    if (opt == CDRL_OPT_ADAM && !blend && gate_mode == GATE_MODE_OFF)
-        return clip_adam(p, g, m, v, n, chunk_tensor_dev, chunk_off_dev, nchunks, segs_dev, sqnorms, hp, which, st, chunk_part, ticked);
     const float pa = polyak, pc = (float)(1.0 - (double)polyak);
-    const int grid = chunk_tensor_dev ? nchunks : (int)cdiv64(n, CHUNK);
+    const int grid = tab.chunk_tensor ? tab.nchunks : (int)cdiv64(a.n, CHUNK);
 #define CDRL_CLIP_UPDATE_G(O, G)                                                                                                 \
-    hipLaunchKernelGGL((clip_update_kernel<O, G>), dim3(grid), dim3(256), 0, st, p, g, m, v, n, chunk_tensor_dev, chunk_off_dev,  \
-                       segs_dev, sqnorms, hp, which, chunk_part, ticked, blend, pa, pc, gate)
-    // (a gated Adam step runs clip_update_kernel<CDRL_OPT_ADAM, ...>: the arithmetic of clip_adam_kernel, operation for operation)
+    hipLaunchKernelGGL((clip_update_kernel<O, G>), dim3(grid), dim3(256), 0, st, a.p, a.g, a.m, a.v, a.n, tab.chunk_tensor,       \
+                       tab.chunk_off, tab.segs, hp, which, tab.chunk_part, ticked, blend, pa, pc, gate)
 #define CDRL_CLIP_UPDATE(O)                                                                                                      \
     do {                                                                                                                         \
         if (gate_mode == GATE_MODE_OFF) CDRL_CLIP_UPDATE_G(O, GATE_MODE_OFF);                                                    \
@@ -372,17 +234,20 @@ int set_steps(DevHP* hp, const int t[3], const float m_cache[3], hipStream_t st)
 }
 
 // two device-to-device copies as ONE launch of the library's own (old_policy <- policy: trainable and state slices): hipMemcpyAsync ran
-// two blit kernels of the runtime with their own fences in the middle of the apply
+// two blit kernels of the runtime with their own fences in the middle of the apply.  gate (or null): the gated apply's form, which
+// copies nothing when the gate block says skip.
 __global__ void __launch_bounds__(256) copy_two_kernel(float* __restrict__ d0, const float* __restrict__ s0, int64_t n0,
-                                                       float* __restrict__ d1, const float* __restrict__ s1, int64_t n1) {
+                                                       float* __restrict__ d1, const float* __restrict__ s1, int64_t n1,
+                                                       const GateBlock* __restrict__ gate) {
+    if (gate && gate->skip) return;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n0) d0[i] = s0[i];
     else if (i < n0 + n1) d1[i - n0] = s1[i - n0];
 }
 
-int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, hipStream_t st) {
+int copy_two(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, hipStream_t st, const GateBlock* gate) {
     if (n0 + n1 <= 0) return 0;
-    hipLaunchKernelGGL(copy_two_kernel, dim3((unsigned)cdiv64(n0 + n1, 256)), dim3(256), 0, st, d0, s0, n0, d1, s1, n1);
+    hipLaunchKernelGGL(copy_two_kernel, dim3((unsigned)cdiv64(n0 + n1, 256)), dim3(256), 0, st, d0, s0, n0, d1, s1, n1, gate);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
@@ -394,51 +259,31 @@ __device__ __forceinline__ bool gate_needs(const DevHP* hp, const GateBlock* gat
     if (list == 1 && !(flags & GATE_TRUNK)) return false;
     if (flags & GATE_GUARD) return true;
     if (!(flags & GATE_GLOBAL)) return false;
-    return (list == 1 ? gate->clip_norm_dynamics : (head == 0 ? hp->clip_norm_policy : hp->clip_norm_value)) > 0.0f;
+    return (list == 1 ? gate->clip_norm_dynamics : hp_clip_norm(hp, head)) > 0.0f;
 }
 
-// blocks [0, nchunks_h): the head's chunk table, [nchunks_h, nchunks_h + nchunks_t): the trunk's.  The per-chunk sum is
-// sqnorm_chunk_kernel's (256 lanes striding the chunk, double, LDS tree): same partials, no tick.
-__global__ void __launch_bounds__(256) gate_chunk_kernel(const float* __restrict__ g_head, const TensorSeg* __restrict__ segs_h,
-                                                         const int* __restrict__ chunk_tensor_h,
-                                                         const int64_t* __restrict__ chunk_off_h, int nchunks_h,
-                                                         double* __restrict__ part_h, const float* __restrict__ g_trunk,
-                                                         const TensorSeg* __restrict__ segs_t,
-                                                         const int* __restrict__ chunk_tensor_t,
-                                                         const int64_t* __restrict__ chunk_off_t, double* __restrict__ part_t,
+// blocks [0, tab_h.nchunks): the head's chunk table, the blocks behind them: the trunk's.  sqnorm_chunk_kernel's partials, no tick.
+__global__ void __launch_bounds__(256) gate_chunk_kernel(const float* __restrict__ g_head, ChunkTable tab_h,
+                                                         const float* __restrict__ g_trunk, ChunkTable tab_t,
                                                          const DevHP* __restrict__ hp, const GateBlock* __restrict__ gate, int head,
                                                          int flags) {
     __shared__ double sm[256];
-    const int list = (int)blockIdx.x < nchunks_h ? 0 : 1;
+    const int list = (int)blockIdx.x < tab_h.nchunks ? 0 : 1;
     if (!gate_needs(hp, gate, head, list, flags) && !(list == 0 && (flags & GATE_HEAD_PARTS))) return;      // (uniform per block)
-    const int c = list == 0 ? (int)blockIdx.x : (int)blockIdx.x - nchunks_h;
-    const float* g = list == 0 ? g_head : g_trunk;
-    const TensorSeg s = list == 0 ? segs_h[chunk_tensor_h[c]] : segs_t[chunk_tensor_t[c]];
-    const int64_t beg = list == 0 ? chunk_off_h[c] : chunk_off_t[c];
-    int64_t end = beg + CHUNK;
-    if (end > s.off + s.n) end = s.off + s.n;
-    double acc = 0.0;
-    for (int64_t i = beg + threadIdx.x; i < end; i += 256) {
-        const double v = (double)g[i];
-        acc += v * v;
-    }
-    sm[threadIdx.x] = acc;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (threadIdx.x < k) sm[threadIdx.x] += sm[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) (list == 0 ? part_h : part_t)[c] = sm[0];
+    const int c = list == 0 ? (int)blockIdx.x : (int)blockIdx.x - tab_h.nchunks;
+    const ChunkTable& tab = list == 0 ? tab_h : tab_t;
+    int64_t beg, end;
+    chunk_bounds(tab, c, beg, end);
+    const double sum = chunk_sqsum(list == 0 ? g_head : g_trunk, beg, end, sm);
+    if (threadIdx.x == 0) tab.chunk_part[c] = sum;
 }
 
-int gate_chunk_sqnorms(const float* g_head, const TensorSeg* segs_h, const int* chunk_tensor_h, const int64_t* chunk_off_h,
-                       int nchunks_h, double* part_h, const float* g_trunk, const TensorSeg* segs_t, const int* chunk_tensor_t,
-                       const int64_t* chunk_off_t, int nchunks_t, double* part_t, const DevHP* hp, const GateBlock* gate, int head,
-                       int flags, hipStream_t st) {
-    if (!(flags & GATE_TRUNK)) nchunks_t = 0;
-    if (nchunks_h + nchunks_t <= 0) return 0;
-    hipLaunchKernelGGL(gate_chunk_kernel, dim3(nchunks_h + nchunks_t), dim3(256), 0, st, g_head, segs_h, chunk_tensor_h, chunk_off_h,
-                       nchunks_h, part_h, g_trunk, segs_t, chunk_tensor_t, chunk_off_t, part_t, hp, gate, head, flags);
+int gate_chunk_sqnorms(const float* g_head, const ChunkTable& tab_h, const float* g_trunk, const ChunkTable& tab_t, const DevHP* hp,
+                       const GateBlock* gate, int head, int flags, hipStream_t st) {
+    const int nchunks_t = (flags & GATE_TRUNK) ? tab_t.nchunks : 0;
+    if (tab_h.nchunks + nchunks_t <= 0) return 0;
+    hipLaunchKernelGGL(gate_chunk_kernel, dim3(tab_h.nchunks + nchunks_t), dim3(256), 0, st, g_head, tab_h, g_trunk, tab_t, hp, gate,
+                       head, flags);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
@@ -474,7 +319,7 @@ __global__ void __launch_bounds__(256) gate_kernel(const double* __restrict__ pa
     const double n_h = sqrt(S_h), n_t = sqrt(S_t);
     float s_h = 1.0f, s_t = 1.0f;
     if (flags & GATE_GLOBAL) {      // s = (float)(c / max(sqrt(S), c)) in double, rounded once; at or below the threshold exactly 1
-        const double c_h = (double)(head == 0 ? hp->clip_norm_policy : hp->clip_norm_value), c_t = (double)gate->clip_norm_dynamics;
+        const double c_h = (double)hp_clip_norm(hp, head), c_t = (double)gate->clip_norm_dynamics;
         if (need_h && c_h > 0.0) s_h = (float)(c_h / fmax(n_h, c_h));
         if (need_t && c_t > 0.0) s_t = (float)(c_t / fmax(n_t, c_t));
     }
@@ -490,46 +335,18 @@ __global__ void __launch_bounds__(256) gate_kernel(const double* __restrict__ pa
         return;
     }
     gate->applied[head] += 1;
-    // the ticks of sqnorm_chunk_kernel, in front of BOTH updates of the step (they run with ticked = 1)
-    const bool nadam = (flags & GATE_NADAM) != 0;
-    if (head == 0) {
-        hp->t_policy += 1;
-        if (nadam) hp->m_cache_policy = hp->m_cache_policy * nadam_mu(hp->beta1, hp->t_policy);
-    } else {
-        hp->t_value += 1;
-        if (nadam) hp->m_cache_value = hp->m_cache_value * nadam_mu(hp->beta1, hp->t_value);
-    }
-    if (flags & GATE_TRUNK) {
-        hp->t_dynamics += 1;
-        if (nadam) hp->m_cache_dynamics = hp->m_cache_dynamics * nadam_mu(hp->beta1, hp->t_dynamics);
-    }
+    // the ticks of sqnorm_chunk_kernel, in front of BOTH updates of the step (they run TICKED)
+    tick_counters(hp, (head == 0 ? TICK_POLICY : TICK_VALUE) | ((flags & GATE_TRUNK) ? TICK_TRUNK : 0) |
+                          ((flags & GATE_NADAM) ? TICK_NADAM : 0));
 }
 
-int gate_decide(const double* part_h, int nchunks_h, const double* part_t, int nchunks_t, DevHP* hp, GateBlock* gate, int head,
-                int flags, hipStream_t st) {
+int gate_decide(const ChunkTable& tab_h, const ChunkTable& tab_t, DevHP* hp, GateBlock* gate, int head, int flags, hipStream_t st) {
     if (head != 0 && head != 1) {
         set_error("gate_decide: head %d", head);
         return -1;
     }
-    if (!(flags & GATE_TRUNK)) nchunks_t = 0;
-    hipLaunchKernelGGL(gate_kernel, dim3(1), dim3(256), 0, st, part_h, nchunks_h, part_t, nchunks_t, hp, gate, head, flags);
-    CDRL_LAUNCH_CHECK();
-    return 0;
-}
-
-__global__ void __launch_bounds__(256) copy_two_gated_kernel(float* __restrict__ d0, const float* __restrict__ s0, int64_t n0,
-                                                             float* __restrict__ d1, const float* __restrict__ s1, int64_t n1,
-                                                             const GateBlock* __restrict__ gate) {
-    if (gate->skip) return;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n0) d0[i] = s0[i];
-    else if (i < n0 + n1) d1[i - n0] = s1[i - n0];
-}
-
-int copy_two_gated(float* d0, const float* s0, int64_t n0, float* d1, const float* s1, int64_t n1, const GateBlock* gate,
-                   hipStream_t st) {
-    if (n0 + n1 <= 0) return 0;
-    hipLaunchKernelGGL(copy_two_gated_kernel, dim3((unsigned)cdiv64(n0 + n1, 256)), dim3(256), 0, st, d0, s0, n0, d1, s1, n1, gate);
+    hipLaunchKernelGGL(gate_kernel, dim3(1), dim3(256), 0, st, tab_h.chunk_part, tab_h.nchunks, tab_t.chunk_part,
+                       (flags & GATE_TRUNK) ? tab_t.nchunks : 0, hp, gate, head, flags);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

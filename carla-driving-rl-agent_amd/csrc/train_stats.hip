@@ -6,25 +6,21 @@
 // policy_apply / value_apply and appended to a ring the host reads once per update(); the row index is a device-side counter, so a
 // replayed hipGraph of the apply step writes successive rows.
 // Norms: float64 accumulation in two deterministic stages (1024-element chunk partials, then one wave per tensor), no atomics.  The
-// heads' chunk partials are the clip path's (sqnorm_chunk_kernel, optim.hip), folded in sqnorm_final_kernel's order.
-#include "cdrl_kernels.h"
+// heads' chunk partials are the clip path's (sqnorm_chunk_kernel, optim.hip); every tensor is folded by the body the update kernel
+// clips with (fold_chunk_parts, optim_bodies.h).
+#include "optim_bodies.h"
 
 namespace cdrl {
 
-#define CHUNK 1024
-
-// one wave per chunk: lane l takes elements l, l + 64, ... of the chunk (coalesced 256-byte rows), fixed shuffle tree
-__global__ void __launch_bounds__(256) stats_chunk_sqnorm_kernel(const float* __restrict__ g, const TensorSeg* __restrict__ segs,
-                                                                 const int* __restrict__ chunk_tensor,
-                                                                 const int64_t* __restrict__ chunk_off, int nchunks,
-                                                                 double* __restrict__ chunk_part) {
+// one wave per chunk: lane l takes elements l, l + 64, ... of the chunk (coalesced 256-byte rows), fixed shuffle tree.  Not
+// chunk_sqsum (optim_bodies.h): that one sums 256 threads through LDS, in another order, so the trunk norms of a row would get other
+// float64 bits.
+__global__ void __launch_bounds__(256) stats_chunk_sqnorm_kernel(const float* __restrict__ g, ChunkTable tab) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= nchunks) return;
-    const TensorSeg s = segs[chunk_tensor[c]];
-    const int64_t beg = chunk_off[c];
-    int64_t end = beg + CHUNK;
-    if (end > s.off + s.n) end = s.off + s.n;
+    if (c >= tab.nchunks) return;
+    int64_t beg, end;
+    chunk_bounds(tab, c, beg, end);
     double acc = 0.0;
 #pragma unroll 4
     for (int64_t i = beg + lane; i < end; i += 64) {
@@ -33,52 +29,41 @@ __global__ void __launch_bounds__(256) stats_chunk_sqnorm_kernel(const float* __
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if (lane == 0) chunk_part[c] = acc;
+    if (lane == 0) tab.chunk_part[c] = acc;
 }
 
-int stats_chunk_sqnorms(const float* g, const TensorSeg* segs_dev, const int* chunk_tensor_dev, const int64_t* chunk_off_dev,
-                        int nchunks, double* chunk_part, hipStream_t st) {
-    if (nchunks <= 0) return 0;
-    hipLaunchKernelGGL(stats_chunk_sqnorm_kernel, dim3(cdiv(nchunks, 4)), dim3(256), 0, st, g, segs_dev, chunk_tensor_dev,
-                       chunk_off_dev, nchunks, chunk_part);
+int stats_chunk_sqnorms(const float* g, const ChunkTable& tab, hipStream_t st) {
+    if (tab.nchunks <= 0) return 0;
+    hipLaunchKernelGGL(stats_chunk_sqnorm_kernel, dim3(cdiv(tab.nchunks, 4)), dim3(256), 0, st, g, tab);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
 
-// one wave per tensor (sqnorm_final_kernel's fold: a thread per tensor would walk up to 768 partials one dependent load at a time);
-// tensors [0, na) of table a, then [0, nb) of table b
+// one wave per tensor: the tensors of table a, then those of table b
 __global__ void __launch_bounds__(256) stats_fold_norms_kernel(float* __restrict__ ring, int header, int rows, int width,
-                                                               const TensorSeg* __restrict__ segs_a, int na,
-                                                               const double* __restrict__ part_a, int off_a,
-                                                               const TensorSeg* __restrict__ segs_b, int nb,
-                                                               const double* __restrict__ part_b, int off_b) {
-    const int lane = threadIdx.x & 63;
+                                                               ChunkTable tab_a, int off_a, ChunkTable tab_b, int off_b) {
     int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= na + nb) return;
-    const bool second = t >= na;
-    if (second) t -= na;
-    const TensorSeg s = second ? segs_b[t] : segs_a[t];
-    const double* part = second ? part_b : part_a;
-    double acc = 0.0;
-    for (int c = lane; c < s.nchunks; c += 64) acc += part[s.first_chunk + c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if (lane == 0) {
+    if (t >= tab_a.ntensors + tab_b.ntensors) return;
+    const bool second = t >= tab_a.ntensors;
+    if (second) t -= tab_a.ntensors;
+    const double sum = second ? fold_chunk_parts(tab_b.chunk_part, tab_b.segs[t]) : fold_chunk_parts(tab_a.chunk_part, tab_a.segs[t]);
+    if ((threadIdx.x & 63) == 0) {
         const unsigned count = reinterpret_cast<const unsigned*>(ring)[0];
         float* row = ring + header + (size_t)(count % (unsigned)rows) * width;
-        row[(second ? off_b : off_a) + t] = (float)sqrt(acc);
+        row[(second ? off_b : off_a) + t] = (float)sqrt(sum);
     }
 }
 
-int stats_fold_norms(float* ring, int header, int rows, int width, const TensorSeg* segs_a, int na, const double* part_a, int off_a,
-                     const TensorSeg* segs_b, int nb, const double* part_b, int off_b, hipStream_t st) {
+int stats_fold_norms(float* ring, int header, int rows, int width, const ChunkTable& tab_a, int off_a, const ChunkTable& tab_b,
+                     int off_b, hipStream_t st) {
+    const int na = tab_a.ntensors, nb = tab_b.ntensors;
     if (na + nb <= 0) return 0;
     if (rows <= 0 || off_a + na > width || off_b + nb > width) {
         set_error("stats_fold_norms: %d + %d / %d + %d tensors do not fit a row of %d floats", off_a, na, off_b, nb, width);
         return -1;
     }
-    hipLaunchKernelGGL(stats_fold_norms_kernel, dim3(cdiv(na + nb, 4)), dim3(256), 0, st, ring, header, rows, width, segs_a, na,
-                       part_a, off_a, segs_b, nb, part_b, off_b);
+    hipLaunchKernelGGL(stats_fold_norms_kernel, dim3(cdiv(na + nb, 4)), dim3(256), 0, st, ring, header, rows, width, tab_a, off_a,
+                       tab_b, off_b);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
@@ -113,9 +98,9 @@ __global__ void __launch_bounds__(256) stats_row_kernel(StatsRowArgs a) {
         float v = 0.0f;
         switch (tid) {
             case STATS_KIND: v = __int_as_float(a.kind); break;
-            case STATS_T_HEAD: v = __int_as_float(a.kind == 0 ? hp->t_policy : hp->t_value); break;
+            case STATS_T_HEAD: v = __int_as_float(hp_t(hp, a.kind)); break;
             case STATS_T_DYNAMICS: v = __int_as_float(hp->t_dynamics); break;
-            case STATS_LR: v = a.kind == 0 ? hp->lr_policy : hp->lr_value; break;
+            case STATS_LR: v = hp_lr(hp, a.kind); break;
             case STATS_LR_DYNAMICS: v = hp->lr_dynamics; break;
             case STATS_CLIP_RATIO: v = hp->clip_ratio; break;
             case STATS_ENTROPY_COEF: v = hp->entropy_coef; break;

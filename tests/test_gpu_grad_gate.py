@@ -162,6 +162,30 @@ def test_below_threshold_global_mode_is_the_unclipped_path(kw):
     assert all(st[h]['scale'] == 1.0 and st[h]['scale_dynamics'] == 1.0 and st[h]['skipped'] == 0 for h in HEADS)
 
 
+@pytest.mark.parametrize('kw', [dict(), dict(optimizer='nadam', polyak=0.9), dict(optimizer='sgd')])
+def test_finite_tensor_mode_gate_is_the_ungated_path(kw):
+    """skip_nonfinite alone (the gated form of the update kernel, per-tensor clip) against the plain engine on finite gradients: one
+    kernel serves both.  The head tables hold tensors of more than 64 chunks and tensors whose last chunk is partial."""
+    a, b = _engine(skip_nonfinite=True, **kw), _engine(**kw)
+    sizes = [c for _, c in _segs(a, 'policy')]
+    assert max(sizes) > 64 * 1024 and any(c % 1024 for c in sizes)
+    for k, (kind, lr, lr_t, scale) in enumerate(SEQ):
+        g = _grads(a, k, scale).numpy()
+        assert np.isfinite(g).all()
+        _apply(a, kind, g, lr, lr_t, 1.0, 0.0)
+        _apply(b, kind, g, lr, lr_t, 1.0, 0.0)
+    torch.cuda.synchronize()
+    for name in ('params', 'adam_m', 'adam_v'):
+        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    assert _hp(a) == _hp(b) and _hp(a)[0] == [2, 1, 3]
+    st = a.gate_stats()
+    assert all(st[h]['skipped'] == 0 for h in HEADS)
+    assert (st['policy']['applied'], st['value']['applied']) == (2, 1)
+    # the third step's head gradients (x 50) are above the threshold: the per-tensor clip was active on both sides
+    s, c = max(_segs(a, 'policy'), key=lambda sc: sc[1])
+    assert np.sqrt(list_sqnorm(_grads(a, 2, SEQ[2][3]).numpy(), [(s, c)])) > 1.0
+
+
 # ---------------------------------------------------------------------------------------------------------------- 3. skip
 def _state(eng):
     torch.cuda.synchronize()
