@@ -178,6 +178,8 @@ PROTOTYPES = {
     'cdrl_gae_returns': (_i, [_fp, _fp, _i, _d, _d, _f, _fp, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_gae_returns_segments': (_i, [_fp, _fp, _fp, _i, _i, _d, _d, _f, _fp, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_gae_segments_scratch_doubles': (_i64, [_i, _i]),
+    'cdrl_vtrace_segments': (_i, [_fp] * 7 + [_i, _i, _i, _d, _d, _d, _d, _f] + [_fp] * 7),
+    'cdrl_vtrace_segments_scratch_doubles': (_i64, [_i, _i]),
     'cdrl_gather_rows': (_i, [_fp, _fp, _fp, _i, _i64, _fp]),
     'cdrl_gemm_nn': (_i, [_fp, _i, _i, _fp, _i, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp]),
     'cdrl_gemm_tn_workspace_elems': (_i64, [_i, _i, _i]),

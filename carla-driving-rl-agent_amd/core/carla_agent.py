@@ -148,6 +148,13 @@ class CARLAgent(PPOAgent):
         A dict of draw_view_plans options (crop_scale, flip_prob, jitter_prob, drop_prob, blur_prob, blur_sigma) implies 'simclr'.
         An unknown name or option: ValueError."""
         assert aug_intensity >= 0.0
+        if kwargs.get('replay_rollouts', 0) and resample_actions:
+            raise ValueError('replay_rollouts > 0 needs the stored-action policy loss: the re-sampled loss (resample_actions=True, the '
+                             'default) evaluates a fresh sample of the new policy and has no importance ratio against the policy '
+                             'that collected a kept row; create the agent with resample_actions=False')
+        if kwargs.get('replay_rollouts', 0) and self._process_group()[3]:
+            raise RuntimeError('replay_rollouts > 0 runs on one GPU: the kept periods differ per rank in size, and every minibatch step '
+                               'is a collective; create the data-parallel agents with replay_rollouts=0')
         self.view_pipeline, self.view_options = self.parse_view_pipeline(view_pipeline)
         network_spec = dict(kwargs.pop('network', {}))
         network_spec.setdefault('network', CARLANetwork)
@@ -185,6 +192,14 @@ class CARLAgent(PPOAgent):
             self.restore_host_state(meta)
 
     # -- data parallelism (reference loop rl/agents/ppo.py:190-226 inside :464-548) ------------------------------
+    @staticmethod
+    def _process_group() -> tuple:
+        """-> (world size, rank, collectives forced at world size 1, data parallel) of the initialised process group, if any."""
+        on = dist.is_available() and dist.is_initialized()
+        world = dist.get_world_size() if on else 1
+        force = on and os.environ.get('CDRL_FORCE_COLLECTIVES') == '1'
+        return world, (dist.get_rank() if on else 0), force, world > 1 or force
+
     def _init_data_parallel(self):
         """One CARLAgent per GPU under torch.distributed: every rank rolls out ITS OWN environment shard (environment and
         rollout-sampler seeds offset by the rank), computes returns / GAE locally (per-episode quantities), runs the same
@@ -192,11 +207,7 @@ class CARLAgent(PPOAgent):
         all-reduced before the identical clip + Adam update (DataParallelLearner).  Parameters are broadcast from rank 0 here
         and after load(); BatchNorm moving statistics are averaged once per update().  Without an initialised process group
         (or at world size 1) nothing changes; CDRL_FORCE_COLLECTIVES=1 runs the collectives at world size 1 as well."""
-        on = dist.is_available() and dist.is_initialized()
-        self.world = dist.get_world_size() if on else 1
-        self.rank = dist.get_rank() if on else 0
-        force = on and os.environ.get('CDRL_FORCE_COLLECTIVES') == '1'
-        self.data_parallel = self.world > 1 or force
+        self.world, self.rank, force, self.data_parallel = self._process_group()
         self._dp = {}
         self._dp_force = force
         if not self.data_parallel:
@@ -311,6 +322,7 @@ class CARLAgent(PPOAgent):
         if small:
             print('[Not updated] memory too small!')
             self._reset_info()
+            self.discard_period()
             return
         super().update()
         if self.statistics.mode is not None:        # (reference core/carla_agent.py:137-140)
@@ -331,6 +343,7 @@ class CARLAgent(PPOAgent):
         return super().collect(shard, *args, **kwargs)
 
     def trajectory_stored(self, env_index, rollout, segment=None):
+        super().trajectory_stored(env_index, rollout, segment)
         # several environments: remember which slice of WHICH environment's info buffer belongs to the rows just appended
         if len(self._shard) > 1:
             have = len(self._shard[env_index].info_buffer['speed'])
@@ -364,14 +377,24 @@ class CARLAgent(PPOAgent):
         pad = torch.zeros(n - speed.shape[0], device=self.device)
         return torch.cat([speed, pad]), torch.cat([sim, pad])
 
+    def _info_with_replay(self, n):
+        """`_info` for the fresh rows among the `n` rows of a batch component, followed by the kept periods' own targets (the rows
+        behind the fresh ones when the running update() reuses kept periods; PPOAgent.with_replay)."""
+        speed, similarity = self._info(n - sum(p.rows for p in self._replay_active))
+        return self.with_replay(speed, 'speed'), self.with_replay(similarity, 'similarity')
+
+    def replay_info(self, rows):
+        speed, similarity = self._info(rows)
+        return dict(speed=speed, similarity=similarity)
+
     def policy_batch_tensors(self):
         states, advantages, actions, log_probabilities = super().policy_batch_tensors()
-        speed, similarity = self._info(advantages.shape[0])
+        speed, similarity = self._info_with_replay(advantages.shape[0])
         return states, advantages, actions, log_probabilities, speed, similarity
 
     def value_batch_tensors(self):
         states, returns = super().value_batch_tensors()
-        speed, similarity = self._info(returns.shape[0])
+        speed, similarity = self._info_with_replay(returns.shape[0])
         return states, returns, speed, similarity
 
     def _policy_pass(self, kind, batch, **extra):

@@ -167,6 +167,31 @@ class CARLANetwork(Network):
                                                          self.engine._stream()), 'cdrl_beta_sample_logp')
         return action, out['mean'].clone(), out['std'].clone(), log_prob, out['value'].clone()
 
+    def distribution_and_value(self, inputs: dict, chunk: int):
+        """The acting network on N stored rows -> (alpha (N, A), beta (N, A), value (N, 2)), fresh tensors: inference forwards as
+        predict() runs them (old_policy, moving statistics) through ONE engine, rollout_for(chunk), `chunk` rows at a time; the last
+        chunk is filled up by repeating the last row instead of planning an engine for its size.  Nothing is sampled: `action_index`
+        stays where it is.  What update() refreshes kept rollouts with (PPOAgent.refresh_replay)."""
+        st = self._pick(inputs)
+        n = st['state_image'].shape[0]
+        eng = self.rollout_for(chunk)
+        A = self.cfg['A']
+        alpha = torch.empty((n, A), dtype=torch.float32, device=self.device)
+        beta = torch.empty((n, A), dtype=torch.float32, device=self.device)
+        value = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        for start in range(0, n, chunk):
+            m = min(chunk, n - start)
+            if m == chunk:
+                rows = {k: v[start:start + chunk] for k, v in st.items()}
+            else:
+                index = torch.arange(start, start + chunk, device=self.device).clamp_(max=n - 1)
+                rows = {k: v.index_select(0, index) for k, v in st.items()}
+            out = eng.predict(rows)
+            alpha[start:start + m].copy_(out['alpha'][:m])
+            beta[start:start + m].copy_(out['beta'][:m])
+            value[start:start + m].copy_(out['value'][:m])
+        return alpha, beta, value
+
     def evaluate_step(self, inputs: dict, deterministic, active=None, stats=None):
         """One evaluation step for E environments -> (action, log_prob): one inference forward plus ONE cdrl_beta_act launch that
         also adds the step's action / mean / std / value to the device block `stats` (float64 (E, 3A + 2), engine.beta_act) for

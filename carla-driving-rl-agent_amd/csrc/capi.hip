@@ -699,6 +699,44 @@ int cdrl_gae_returns_segments(const float* rewards, const float* values_be, cons
                                 S(stream));
 }
 
+int64_t cdrl_vtrace_segments_scratch_doubles(int N, int nseg) {
+    if (nseg < 1 || N < nseg) return 0;
+    return 4 * (int64_t)N;
+}
+
+int cdrl_vtrace_segments(const float* rewards, const float* values_be, const float* alpha, const float* beta, const float* actions,
+                         const float* log_prob_old, const int32_t* seg_off, int nseg, int N, int A, double gamma, double lambda,
+                         double rho_bar, double c_bar, float scale, float* returns, float* returns_be, float* adv_raw, float* adv,
+                         float* rho, double* scratch, void* stream) {
+    if (!rewards || !values_be || !alpha || !beta || !actions || !log_prob_old || !seg_off || !returns || !returns_be || !adv_raw || !adv
+        || !rho || !scratch) {
+        cdrl::set_error("cdrl_vtrace_segments: null argument");
+        return -1;
+    }
+    if (nseg < 1) {
+        cdrl::set_error("cdrl_vtrace_segments: S = %d segments (at least one)", nseg);
+        return -1;
+    }
+    if (N < nseg) {
+        cdrl::set_error("cdrl_vtrace_segments: N = %d rows for S = %d segments (every segment holds at least one row)", N, nseg);
+        return -1;
+    }
+    if (A < 1 || A > 8) {
+        cdrl::set_error("cdrl_vtrace_segments: A = %d actions (1..8)", A);
+        return -1;
+    }
+    if ((int64_t)N + nseg > INT32_MAX) {
+        cdrl::set_error("cdrl_vtrace_segments: N + S = %lld padded entries exceed the 32-bit row offsets", (long long)N + nseg);
+        return -1;
+    }
+    if (!(rho_bar >= 0.0) || !(c_bar >= 0.0)) {
+        cdrl::set_error("cdrl_vtrace_segments: rho_bar = %g, c_bar = %g (clips must not be negative)", rho_bar, c_bar);
+        return -1;
+    }
+    return vtrace_segments(rewards, values_be, alpha, beta, actions, log_prob_old, seg_off, nseg, N, A, gamma, lambda, rho_bar, c_bar,
+                           scale, returns, returns_be, adv_raw, adv, rho, scratch, S(stream));
+}
+
 int64_t cdrl_pwconv_x3_packed_bytes(int K) { return pw_x3_packed_bytes(K); }
 int64_t cdrl_pwconv_x3_packed_bytes_n(int K, int N) { return pw_x3_packed_bytes_n(K, N); }
 int cdrl_pwconv_x3_partial_rows(int G, int Mg, int N, int K) { return pw_x3_partial_rows(G, Mg, N, K); }

@@ -719,4 +719,13 @@ int gae_returns_segments(const float* rewards, const float* values_be, const int
                          double lambda, float scale, float* returns, float* returns_be, float* adv_raw, float* adv, double* scratch,
                          hipStream_t st);
 
+// ---------------------------------------------------------------- V-trace (vtrace.hip)
+constexpr int VTRACE_CH = 2048;     // rows per LDS chunk of the two recurrences (3 x 8 bytes each)
+// S replayed trajectories in one launch, the layout of gae_returns_segments plus the dense [N][A] alpha / beta / actions / log_prob_old;
+// packed outputs [N] and the unclipped ratio rho [N]; scratch 4 * N doubles
+int vtrace_segments(const float* rewards, const float* values_be, const float* alpha, const float* beta, const float* actions,
+                    const float* log_prob_old, const int32_t* seg_off, int S, int N, int A, double gamma, double lambda, double rho_bar,
+                    double c_bar, float scale, float* returns, float* returns_be, float* adv_raw, float* adv, float* rho, double* scratch,
+                    hipStream_t st);
+
 }  // namespace cdrl

@@ -10,6 +10,7 @@
 // One workgroup per shard: the recurrences are latency-bound chains (staged through LDS, the two of them on two waves), everything
 // else is a wavefront-parallel map / reduction.
 #include "cdrl_kernels.h"
+#include "gae_bodies.h"
 
 namespace cdrl {
 
@@ -44,7 +45,6 @@ __device__ __forceinline__ void gae_trajectory(const float* __restrict__ rewards
                                                float* __restrict__ returns, float* __restrict__ returns_be,
                                                float* __restrict__ adv_raw, float* __restrict__ adv,
                                                double* __restrict__ scratch) {
-    __shared__ float smax[256], smin[256];
     const int tid = threadIdx.x;
     double* delta = scratch;             // [N]
     double* ret = scratch + (N + 1);     // [N+1]
@@ -85,42 +85,7 @@ __device__ __forceinline__ void gae_trajectory(const float* __restrict__ rewards
         }
     }
     __syncthreads();
-    float mx = -INFINITY, mn = INFINITY;
-    for (int i = tid; i < N; i += 256) {
-        const float a = (float)delta[i];
-        adv_raw[i] = a;
-        mx = fmaxf(mx, a);
-        mn = fminf(mn, a);
-        // decompose_number: while |x| > 1: x /= 10 (float32 division)
-        float x = (float)ret[i];
-        returns[i] = x;
-        int e = 0;
-        while (fabsf(x) > 1.0f) {
-            x = __fdiv_rn(x, 10.0f);
-            ++e;
-        }
-        returns_be[2 * i] = x;
-        returns_be[2 * i + 1] = (float)e;
-    }
-    smax[tid] = mx;
-    smin[tid] = mn;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if (tid < k) {
-            smax[tid] = fmaxf(smax[tid], smax[tid + k]);
-            smin[tid] = fminf(smin[tid], smin[tid + k]);
-        }
-        __syncthreads();
-    }
-    // tf_sp_norm: positives / (max + eps) + negatives / -(min - eps), then * scale
-    const float pden = __fadd_rn(smax[0], 1e-3f);
-    const float nden = -__fsub_rn(smin[0], 1e-3f);
-    for (int i = tid; i < N; i += 256) {
-        const float a = adv_raw[i];
-        const float pos = a > 0.0f ? a : __fmul_rn(a, 0.0f);
-        const float neg = a < 0.0f ? a : __fmul_rn(a, 0.0f);
-        adv[i] = __fmul_rn(__fadd_rn(__fdiv_rn(pos, pden), __fdiv_rn(neg, nden)), scale);
-    }
+    trajectory_tail(delta, ret, N, scale, returns, returns_be, adv_raw, adv);
 }
 
 __global__ void __launch_bounds__(256) gae_kernel(const float* __restrict__ rewards, const float* __restrict__ values_be,

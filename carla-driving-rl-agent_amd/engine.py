@@ -721,6 +721,50 @@ def gae_returns_segments(rewards: torch.Tensor, values_be: torch.Tensor, lengths
     return returns, returns_be, adv_raw, adv
 
 
+VTRACE_CHUNK = 2048     # VTRACE_CH (csrc/cdrl_kernels.h): rows per LDS chunk of cdrl_vtrace_segments' recurrences
+
+
+def vtrace_segments(rewards: torch.Tensor, values_be: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, actions: torch.Tensor,
+                    log_prob_old: torch.Tensor, lengths, gamma: float, lambda_: float, rho_bar: float = 1.0, c_bar: float = 1.0,
+                    scale: float = 2.0):
+    """V-trace targets for S replayed trajectories in ONE launch (cdrl_vtrace_segments), one workgroup per trajectory.
+    `lengths`, rewards (N+S,), values_be (N+S, 2) as `gae_returns_segments` takes them -- values_be from the CURRENT value head --;
+    alpha, beta (N, A) of the current policy, actions (N, A) in [0, 1] and log_prob_old (N, A) as stored.  -> packed returns (N,),
+    returns_be (N, 2), adv_raw (N,), adv (N,), rho (N,) = the unclipped joint ratio.  One host-to-device copy (the row offsets), no
+    device-to-host read."""
+    lengths = [int(n) for n in lengths]
+    S, n = len(lengths), sum(lengths)
+    if S < 1 or min(lengths) < 1:
+        raise ValueError(f'vtrace_segments: every trajectory needs at least one row (lengths {lengths})')
+    if n + S != rewards.numel() or 2 * (n + S) != values_be.numel():
+        raise ValueError(f'vtrace_segments: {S} trajectories of {n} rows in all need {n + S} rewards and ({n + S}, 2) values '
+                         f'(one bootstrap entry each), got {rewards.numel()} and {tuple(values_be.shape)}')
+    A = int(actions.shape[-1]) if actions.dim() == 2 else 0
+    dense = dict(alpha=alpha, beta=beta, actions=actions, log_prob_old=log_prob_old)
+    for name, t in dict(dense, rewards=rewards, values_be=values_be).items():
+        if t.dtype != torch.float32 or not t.is_contiguous() or (name in dense and tuple(t.shape) != (n, A)):
+            raise ValueError(f'vtrace_segments: {name} must be a contiguous float32 tensor'
+                             + (f' of shape ({n}, {A})' if name in dense else '') + f', got {tuple(t.shape)} {t.dtype}')
+    lib = _lib.load()
+    dev = rewards.device
+    offsets = [0] * (S + 1)
+    for s, k in enumerate(lengths):
+        offsets[s + 1] = offsets[s] + k
+    seg_off = torch.tensor(offsets, dtype=torch.int32, device=dev)
+    returns = torch.empty(n, dtype=torch.float32, device=dev)
+    returns_be = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    adv_raw = torch.empty(n, dtype=torch.float32, device=dev)
+    adv = torch.empty(n, dtype=torch.float32, device=dev)
+    rho = torch.empty(n, dtype=torch.float32, device=dev)
+    scratch = torch.empty(int(lib.cdrl_vtrace_segments_scratch_doubles(n, S)), dtype=torch.float64, device=dev)
+    _lib.check(lib.cdrl_vtrace_segments(_lib.ptr(rewards), _lib.ptr(values_be), _lib.ptr(alpha), _lib.ptr(beta), _lib.ptr(actions),
+                                        _lib.ptr(log_prob_old), _lib.ptr(seg_off), S, n, A, float(gamma), float(lambda_), float(rho_bar),
+                                        float(c_bar), float(scale), _lib.ptr(returns), _lib.ptr(returns_be), _lib.ptr(adv_raw),
+                                        _lib.ptr(adv), _lib.ptr(rho), _lib.ptr(scratch),
+                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'vtrace_segments')
+    return returns, returns_be, adv_raw, adv, rho
+
+
 ACT_SAMPLE, ACT_MODE = 0, 1
 
 

@@ -13,17 +13,20 @@ import torch
 
 from .. import utils
 from ..parameters import DynamicParameter
+from ..replay import ReplayPeriod, RolloutReplay, TrajectoryTable
 from .agents import Agent
 from ..._lib import CLIP_MODES, OPTIMIZERS
 from ... import traces, train_stats
 
 
 class PPOAgent(Agent):
+    replay, _replay_active = None, ()       # class-level defaults: an agent that never ran __init__ reuses nothing
+
     def __init__(self, *args, policy_lr=1e-3, gamma=0.99, lambda_=0.95, value_lr=3e-4, load=False,
                  optimization_steps=(1, 1), name='ppo-agent', optimizer='adam', clip_norm=(1.0, 1.0), clip_ratio=0.2,
                  seed_regularization=False, entropy_regularization=0.0, network: dict = None, update_frequency=1,
                  polyak=1.0, repeat_action=1, advantage_scale=2.0, train_stats_rows=256, clip_mode='tensor', skip_nonfinite=False,
-                 joint_update=False, **kwargs):
+                 joint_update=False, replay_rollouts=0, replay_rho_clip=1.0, replay_c_clip=1.0, **kwargs):
         """clip_mode: 'tensor' (default; utils.clip_gradients of the reference: tf.clip_by_norm per tensor of each head) or 'global'
         (tf.clip_by_global_norm of each optimizer's gradient list, the max_grad_norm of other PPO implementations; thresholds are
         those of clip_norm).  skip_nonfinite=True: a minibatch step whose gradients hold a NaN or an Inf leaves parameters and
@@ -34,13 +37,31 @@ class PPOAgent(Agent):
         to when the agent logs (log_mode is not None); update() reads it once.  An update() with more policy + value steps than
         that keeps the newest rows and reports how many it lost.
         joint_update=True: update() runs ONE minibatch loop whose steps take the policy and the value loss together (agents that
-        implement get_joint_gradients / apply_joint_gradients: CARLAgent); needs optimization_steps[0] == optimization_steps[1]."""
+        implement get_joint_gradients / apply_joint_gradients: CARLAgent); needs optimization_steps[0] == optimization_steps[1].
+        replay_rollouts=K > 0 (not in the reference, not written to config.json): update() keeps the K most recent
+        update-periods on the device (rl/replay.py) instead of discarding their rows, and trains on them again behind the fresh rows.
+        Before the minibatches are formed the kept rows are re-evaluated with the acting network (inference forwards in chunks of
+        batch_size) and their targets corrected for the policy lag by V-trace in ONE launch (utils.vtrace_segments) with the
+        importance ratio clipped at replay_rho_clip (TD weight) and replay_c_clip (trace cut); fresh rows keep their GAE targets bit
+        for bit.  Needs the stored-action policy loss (an agent with a re-sampled loss refuses) and one GPU.  The store is not saved
+        by save_state(); clear_replay() empties it.  Nobody has measured what reuse does to driving quality."""
         assert 0.0 < polyak <= 1.0
         self.joint_update = bool(joint_update)
         if self.joint_update and optimization_steps[0] != optimization_steps[1]:
             raise ValueError(f'joint_update=True runs one minibatch loop for both losses: optimization_steps must be equal, got '
                              f'{tuple(optimization_steps)}')
         assert repeat_action >= 1
+        if int(replay_rollouts) != replay_rollouts or replay_rollouts < 0:
+            raise ValueError(f'replay_rollouts={replay_rollouts!r}: the number of finished update-periods to keep, an integer >= 0 '
+                             f'(0 = no reuse)')
+        if not float(replay_rho_clip) >= 0.0 or not float(replay_c_clip) >= 0.0:
+            raise ValueError(f'replay_rho_clip={replay_rho_clip!r}, replay_c_clip={replay_c_clip!r}: V-trace clips the importance '
+                             f'ratio from above at these values, so they must be >= 0 (1.0 is the usual choice)')
+        self.replay_rollouts = int(replay_rollouts)
+        self.replay_rho_clip, self.replay_c_clip = float(replay_rho_clip), float(replay_c_clip)
+        self.replay = RolloutReplay(self.replay_rollouts) if self.replay_rollouts > 0 else None
+        self._replay_table = TrajectoryTable()      # trajectories stored since the last update()
+        self._replay_active = []                    # the kept periods whose rows ride along in the running update()
         # utils.get_optimizer_by_name (reference rl/utils.py:29-46): one Keras optimizer class, by name, for the policy and value
         # optimizers (and CARLAgent's dynamics optimizer); it and polyak reach the learner engines through the network
         if str(optimizer).lower() not in OPTIMIZERS:
@@ -132,6 +153,8 @@ class PPOAgent(Agent):
         t0 = time.time()
         self.seed_regularization()
         self.network.set_hparams(**self.hyper_parameters())
+        if self.replay is not None:
+            self.refresh_replay()
         if self.joint_update:
             return self._update_joint(t0)
         value_batches = list(self.get_value_batches())
@@ -152,6 +175,8 @@ class PPOAgent(Agent):
         self.after_update()
         self.log_train_stats()
         self.log_gate_stats()
+        if self.replay is not None:
+            self.keep_period()
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         print(f'Update took {round(time.time() - t0, 3)}s')
@@ -170,6 +195,8 @@ class PPOAgent(Agent):
         self.after_update()
         self.log_train_stats()
         self.log_gate_stats()
+        if self.replay is not None:
+            self.keep_period()
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         print(f'Update took {round(time.time() - t0, 3)}s')
@@ -239,10 +266,108 @@ class PPOAgent(Agent):
         raise NotImplementedError
 
     def value_batch_tensors(self):
-        return self.memory.states, self.memory.returns
+        return self.with_replay(self.memory.states, 'states'), self.with_replay(self.memory.returns, 'returns_be')
 
     def policy_batch_tensors(self):
-        return self.memory.states, self.memory.advantages, self.memory.actions, self.memory.log_probabilities
+        return (self.with_replay(self.memory.states, 'states'), self.with_replay(self.memory.advantages, 'advantages'),
+                self.with_replay(self.memory.actions, 'actions'), self.with_replay(self.memory.log_probabilities, 'log_probs'))
+
+    # -- reuse of recent rollouts (replay_rollouts > 0; rl/replay.py) ----------------------------------------------
+    def with_replay(self, fresh, name: str):
+        """`fresh` (the memory's tensor, or dict of tensors, of one batch component) followed by the same component of every kept
+        period that the running update() refreshed; `fresh` itself -- the same object -- when there is none.  name: 'states',
+        'actions', 'log_probs' (the stored behaviour log-probabilities), 'advantages' / 'returns_be' (the V-trace targets), or a key
+        of the periods' info targets."""
+        if not self._replay_active:
+            return fresh
+
+        def part(p):
+            if name in ('states', 'actions', 'log_probs'):
+                return getattr(p, name)
+            return p.targets[name] if name in p.targets else p.info[name]
+
+        parts = [part(p) for p in self._replay_active]
+        if isinstance(fresh, dict):
+            return {k: torch.cat([fresh[k]] + [q[k] for q in parts], dim=0) for k in fresh}
+        return torch.cat([fresh] + parts, dim=0)
+
+    def replay_info(self, rows: int):
+        """Hook: per-row auxiliary targets of the `rows` memory rows that a kept period must carry, as a dict of (rows,) device
+        tensors, or None (this class has none)."""
+        return None
+
+    def refresh_replay(self):
+        """First step of update() with a non-empty store: re-evaluates the acting network on every kept period's rows (inference
+        forwards in chunks of batch_size, the last chunk padded with repeated rows; one more forward for the observations behind the
+        truncated trajectories), then ONE V-trace launch over all kept trajectories gives the rows' advantages and value targets
+        under the current policy.  The periods ride along in this update()'s batches (with_replay).  No per-trajectory host read;
+        with logging on, one small copy (three scalars)."""
+        self._replay_active = []
+        periods = list(self.replay.periods)
+        if not periods:
+            return
+        dev = self.device
+        r_parts, v_parts, dense, lengths = [], [], dict(alpha=[], beta=[], actions=[], log_probs=[]), []
+        for p in periods:
+            alpha, beta, value = self.network.distribution_and_value(p.states, chunk=self.batch_size)
+            S = len(p.trajectories)
+            boot = torch.zeros((S, 2), dtype=torch.float32, device=dev)            # zero behind a terminal step
+            if p.finals is not None:
+                _, _, final_value = self.network.distribution_and_value(p.finals, chunk=self.batch_size)
+                boot[torch.as_tensor(p.truncated, dtype=torch.int64, device=dev)] = final_value
+            row_index, boot_index = (torch.as_tensor(i, device=dev) for i in p.padded_index())
+            values_be = torch.empty((p.rows + S, 2), dtype=torch.float32, device=dev)
+            values_be[row_index], values_be[boot_index] = value, boot
+            rewards = torch.empty(p.rows + S, dtype=torch.float32, device=dev)
+            rewards[row_index] = p.rewards
+            rewards[boot_index] = boot[:, 0] * torch.pow(torch.tensor(10.0, device=dev), boot[:, 1])      # as end_trajectory
+            r_parts.append(rewards)
+            v_parts.append(values_be)
+            for k, t in (('alpha', alpha), ('beta', beta), ('actions', p.actions), ('log_probs', p.log_probs)):
+                dense[k].append(t)
+            lengths += p.lengths
+        cat = lambda parts: parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+        inputs = dict(rewards=cat(r_parts), values_be=cat(v_parts), alpha=cat(dense['alpha']), beta=cat(dense['beta']),
+                      actions=cat(dense['actions']), log_prob_old=cat(dense['log_probs']))
+        scale = float(self.adv_scale.value)
+        out = utils.vtrace_segments(lengths=lengths, gamma=self.gamma, lambda_=self.lambda_, rho_bar=self.replay_rho_clip,
+                                    c_bar=self.replay_c_clip, scale=scale, device=dev, **inputs)
+        row = 0
+        for p in periods:
+            p.targets = dict(advantages=out['advantages'][row:row + p.rows], returns_be=out['returns_be'][row:row + p.rows])
+            row += p.rows
+        self.replay.last_refresh = dict(inputs, lengths=lengths, scale=scale, **out)
+        self._replay_active = periods
+        if self.statistics.mode is not None:
+            rho = out['rho'].double()
+            m = torch.stack([rho.mean(), (rho > self.replay_rho_clip).double().mean()]).cpu().numpy()       # the update()'s one copy
+            self.log(replay_rows=row, replay_rho_mean=float(m[0]), replay_rho_clipped=float(m[1]))
+
+    def keep_period(self):
+        """Last step of update(): the fresh period -- the memory's rows with the trajectory table trajectory_stored() collected --
+        moves into the store (the oldest kept period leaves when it is full); the periods that rode along drop their targets."""
+        for p in self._replay_active:
+            p.targets = None
+        self._replay_active = []
+        table, self._replay_table = self._replay_table, TrajectoryTable()
+        m = self.memory
+        n = len(m)
+        if n == 0 or sum(rows for rows, _ in table.entries) != n:
+            print(f'[replay] the trajectory table counts {sum(rows for rows, _ in table.entries)} rows, the memory holds {n}: period '
+                  f'not kept (rows must reach the memory through store())')
+            return
+        self.replay.add(ReplayPeriod(states=m.states, actions=m.actions, log_probs=m.log_probabilities, rewards=m.rewards[:n],
+                                     trajectories=table.entries, finals=table.stacked_finals(), info=self.replay_info(n)))
+
+    def discard_period(self):
+        """For an update() that returns without training (CARLAgent: memory too small): the rows are dropped, so is their table."""
+        self._replay_table = TrajectoryTable()
+
+    def clear_replay(self):
+        """Empties the store of kept periods (replay_rollouts > 0); the next update() trains on fresh rows only."""
+        if self.replay is not None:
+            self.replay.clear()
+        self._replay_active = []
 
     def _batches(self, tensors, shuffle, shuffle_batches):
         return utils.data_to_batches(tensors=tensors, batch_size=self.batch_size, drop_remainder=self.drop_batch_remainder,
@@ -256,7 +381,7 @@ class PPOAgent(Agent):
         return self._batches(self.policy_batch_tensors(), self.shuffle, self.shuffle_batches)
 
     def joint_batch_tensors(self):
-        return tuple(self.policy_batch_tensors()) + (self.memory.returns,)
+        return tuple(self.policy_batch_tensors()) + (self.with_replay(self.memory.returns, 'returns_be'),)
 
     def get_joint_batches(self):
         return self._batches(self.joint_batch_tensors(), self.shuffle, self.shuffle_batches)
@@ -729,7 +854,19 @@ class PPOAgent(Agent):
 
     def trajectory_stored(self, env_index: int, rollout: 'Rollout', segment=None):
         """Hook: environment `env_index`'s trajectory of this rollout now sits at the end of the memory.  `segment`: which one of the
-        environment's trajectories (an entry of `rollout.segments[env_index]`) when the rollout was collected with auto-reset."""
+        environment's trajectories (an entry of `rollout.segments[env_index]`) when the rollout was collected with auto-reset.
+        With replay_rollouts > 0 this class records the trajectory table here (overrides call super()): rows, terminal flag and, for
+        a truncated trajectory, the environment's row of `rollout.final`."""
+        if self.replay is None:
+            return
+        if segment is not None:
+            rows, terminal = segment[1] - segment[0], bool(segment[2])
+        else:
+            rows, terminal = rollout.length[env_index], bool(rollout.terminal[env_index])
+        final = None
+        if not terminal:
+            final = {k: v[env_index:env_index + 1].clone() for k, v in rollout.final.items()}
+        self._replay_table.record(rows, terminal, final)
 
     def get_memory(self):
         return PPOMemory(state_spec=self.state_spec, num_actions=self.num_actions, device=self.device)
@@ -770,6 +907,10 @@ class PPOAgent(Agent):
         if pending:
             print(f'[save_state] {pending} rollout rows pending in the memory are not saved: a run resumed from this state starts '
                   f'the update period over')
+        kept = self.replay.rows if getattr(self, 'replay', None) is not None else 0
+        if kept:
+            print(f'[save_state] {kept} kept rollout rows of the replay store ({len(self.replay)} periods) are not saved: a run '
+                  f'resumed from this state refills the store from its first updates')
         host = self.host_state()
         rank = self.state_rank()
         if self.is_writer():

@@ -4,6 +4,7 @@ device kernels of libcdrl_hip.so, torch tensors as plain device memory).
 
   discount_cumsum / gae / rewards_to_go / decompose_number / tf_sp_norm  -> cdrl_gae_returns
   (many trajectories at once: returns_and_advantages_segments)           -> cdrl_gae_returns_segments
+  (replayed, off-policy trajectories: vtrace_segments)                   -> cdrl_vtrace_segments
   data_to_batches                                                         -> index pipeline +
                                                                              cdrl_gather_rows
   space_to_flat_spec, to_tensor, Summary, makedir                         -> host bookkeeping
@@ -61,6 +62,18 @@ def returns_and_advantages_segments(rewards, values_be, lengths, gamma: float, l
     r, v = _f32(rewards, device), _f32(values_be, device)
     ret, ret_be, adv_raw, adv = gae_returns_segments(r, v, lengths, gamma, lambda_, scale)
     return dict(returns=ret, returns_be=ret_be, advantages_raw=adv_raw, advantages=adv)
+
+
+def vtrace_segments(rewards, values_be, alpha, beta, actions, log_prob_old, lengths, gamma: float, lambda_: float, rho_bar: float = 1.0,
+                    c_bar: float = 1.0, scale: float = 2.0, device='cuda:0'):
+    """`returns_and_advantages_segments` for REPLAYED trajectories (V-trace, one device launch): values_be (N+S, 2) are the current
+    value head's estimates, alpha / beta (N, A) the current policy's, actions / log_prob_old (N, A) what the rollout stored; the TD
+    errors are weighted by the importance ratios clipped at rho_bar / c_bar.  -> the same dict plus rho (N,), the unclipped ratio."""
+    from ..engine import vtrace_segments as launch
+    ret, ret_be, adv_raw, adv, rho = launch(_f32(rewards, device), _f32(values_be, device), _f32(alpha, device), _f32(beta, device),
+                                            _f32(actions, device), _f32(log_prob_old, device), lengths, gamma, lambda_, rho_bar, c_bar,
+                                            scale)
+    return dict(returns=ret, returns_be=ret_be, advantages_raw=adv_raw, advantages=adv, rho=rho)
 
 
 def discount_cumsum(x, discount: float, device='cuda:0'):

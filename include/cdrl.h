@@ -468,6 +468,28 @@ int cdrl_gae_returns_segments(const float* rewards, const float* values_be, cons
                               float* returns, float* returns_be, float* adv_raw, float* adv,
                               double* scratch, void* stream);
 int64_t cdrl_gae_segments_scratch_doubles(int N, int S);
+/* V-trace targets (Espeholt et al. 2018) for S REPLAYED trajectories in ONE launch, one 256-thread workgroup per segment: the rows were
+ * collected by an older policy, so the TD errors are weighted by truncated importance ratios.  seg_off, rewards (N + S) and values_be
+ * (N + S, 2) are laid out as for cdrl_gae_returns_segments; values_be holds the CURRENT value head's estimates.  alpha, beta (N, A): the
+ * current policy's Beta parameters; actions (N, A): the stored actions in [0, 1]; log_prob_old (N, A): the stored behaviour
+ * log-densities; A in 1..8.  Per row: V = base * 10^exp (float32), log pi = sum_a log Beta(u; alpha, beta) in float64 with u clipped
+ * to [eps, 1 - eps], eps = 1.1920929e-07f (the clip of cdrl_beta_sample_logp), ratio = exp(log pi - sum_a log_prob_old) -- the JOINT
+ * ratio over the A actions --, rho = min(rho_bar, ratio), c = min(c_bar, ratio), td = r + gamma V' - V, and two float64 recurrences
+ * from carries 0:
+ *   x_i = rho_i td_i + gamma lambda c_i x_{i+1},   adv_raw_i = td_i + gamma lambda x_{i+1}   (no rho factor: PPO's ratio supplies it)
+ *   y_i = rho_i td_i + gamma c_i y_{i+1},          returns_i = V_i + y_i                     (lambda = 1: the rewards-to-go form)
+ * then the tail of cdrl_gae_returns: returns_be = decompose_number(returns), adv = tf_sp_norm(adv_raw) * scale over the segment's own
+ * max / min.  rho (N): the UNCLIPPED ratio, for diagnostics (inf where it overflows float32; the clipped weights stay finite).  With
+ * every ratio >= 1 and rho_bar = c_bar = 1 the outputs are cdrl_gae_returns_segments' up to the float32 rounding of its deltas.
+ * Scratch: 4 * n_s doubles per segment from 4 * seg_off[s], 4 * N in all, which cdrl_vtrace_segments_scratch_doubles returns.  Every
+ * segment's outputs are the bits it gets when launched alone.  A segment whose offsets are malformed is skipped and nothing of it is
+ * written.  Errors (-1, nothing launched): null pointer, S < 1, N < S, A outside 1..8, N + S beyond 32 bits, rho_bar or c_bar < 0. */
+int cdrl_vtrace_segments(const float* rewards, const float* values_be, const float* alpha, const float* beta, const float* actions,
+                         const float* log_prob_old, const int32_t* seg_off, int S, int N, int A,
+                         double gamma, double lambda, double rho_bar, double c_bar, float scale,
+                         float* returns, float* returns_be, float* adv_raw, float* adv, float* rho,
+                         double* scratch, void* stream);
+int64_t cdrl_vtrace_segments_scratch_doubles(int N, int S);
 
 /* tfp.distributions.Beta(alpha, beta).sample() with reparameterisation gradients (core/networks.py:
  * 136-137): u = g1/(g1+g2), g ~ Gamma via Marsaglia-Tsang on a Philox-4x32-10 stream, du/dalpha and
