@@ -237,6 +237,16 @@ PROTOTYPES = {
     'cdrl_gemm_tn_ex': (_i, [_V, _fp, _V, _fp, _fp, _fp, _i, _i, _fp, _i, _i, _i, _i, _fp, _i, _i, _i, _fp]),
     'cdrl_reduce_partials_plan': (_i, [C.c_uint64, _i, _i64, _i64, C.POINTER(C.c_int32), _i]),
     'cdrl_reduce_partials_f32': (_i, [_fp, _i, _i64, _i64, _fp, _i, _fp]),
+    'cdrl_gemm_nn_plan': (_i, [_V, C.c_uint64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
+    'cdrl_gemm_nn_workspace_elems': (_i64, [_i, _i, _i]),
+    'cdrl_gemm_nn_ex': (_i, [_V, _fp, _i, _i, _fp, _V, _i, _i, _i, _i, _fp, _fp, _i, C.POINTER(C.c_int), _fp]),
+    'cdrl_act_fwd': (_i, [_fp, _fp, _i64, _i, _fp]),
+    'cdrl_act_bwd': (_i, [_fp, _fp, _fp, _i64, _i, _fp]),
+    'cdrl_colsum_partial_rows': (_i, [_i, _i]),
+    'cdrl_colsum': (_i, [_V, _i, _i, _fp, _fp]),
+    'cdrl_reduce_partials_cx': (_i, [_i, _i, _i]),
+    'cdrl_reduce_partials': (_i, [_fp, _i, _i, _i, _i64, _fp, _fp, _i, _fp]),
+    'cdrl_permute_bt': (_i, [_fp, _fp, _i, _i, _i, _fp]),
     'cdrl_bn_act_gap_fwd': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp]),
     'cdrl_gather_view': (_i, [_V, _i, _i, _i, _V, _i, _fp]),
     'cdrl_bn_inference_stats_table_bytes': (_i64, [_i]),

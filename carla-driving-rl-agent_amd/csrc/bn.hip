@@ -1398,10 +1398,12 @@ __global__ void __launch_bounds__(256) reduce_partials_kernel(const double* __re
     }
 }
 
+int reduce_partials_cx(int nparts, int n) { return (cdiv(n, 16) >= 128 || nparts <= 64) ? 16 : 4; }
+
 int reduce_partials2(const double* part, int nparts, int n1, int n2, int64_t stride, float* out1, float* out2, int accumulate,
                      hipStream_t st) {
     const int n = n1 + n2;
-    if (cdiv(n, 16) >= 128 || nparts <= 64)
+    if (reduce_partials_cx(nparts, n) == 16)
         hipLaunchKernelGGL(reduce_partials_kernel<16>, dim3(cdiv(n, 16)), dim3(256), 0, st, part, nparts, n, stride, out1, accumulate, n1, out2);
     else
         hipLaunchKernelGGL(reduce_partials_kernel<4>, dim3(cdiv(n, 4)), dim3(256), 0, st, part, nparts, n, stride, out1, accumulate, n1, out2);
@@ -1442,39 +1444,16 @@ int gather_view(View src, int shuffle_ctot, int rows, int C, View dst, int accum
 // ------------------------------------------------------------------------------------------
 // dense activations (relu6 for feature nets, swish6 for the control branches)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
+// (act_value / act_grad: cdrl_common.h, shared with the split-K reduce of gemm_nn)
 __global__ void act_fwd_kernel(const float* __restrict__ z, float* __restrict__ a, int64_t n, int act) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float x = z[i];
-        float o = x;
-        if (act == ACT_RELU6) o = fminf(fmaxf(x, 0.0f), 6.0f);
-        else if (act == ACT_SWISH6) o = fminf(x * sigmoidf_(x), 6.0f);      // rl/utils.py:420-421
-        else if (act == ACT_TANH) o = tanhf(x);
-        else if (act == ACT_SIGMOID) o = sigmoidf_(x);
-        a[i] = o;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        a[i] = act_value(z[i], act);
 }
 
 __global__ void act_bwd_kernel(const float* __restrict__ z, const float* __restrict__ da, float* __restrict__ dz,
                                int64_t n, int act) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float x = z[i];
-        float d = da[i];
-        if (act == ACT_RELU6) {
-            if (!relu6_open(x)) d = 0.0f;
-        } else if (act == ACT_SWISH6) {
-            const float s = sigmoidf_(x);
-            d = (x * s < 6.0f) ? d * (s * (1.0f + x * (1.0f - s))) : 0.0f;
-        } else if (act == ACT_TANH) {
-            const float t = tanhf(x);
-            d *= (1.0f - t * t);
-        } else if (act == ACT_SIGMOID) {
-            const float s = sigmoidf_(x);
-            d *= s * (1.0f - s);
-        }
-        dz[i] = d;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        dz[i] = act_grad(z[i], da[i], act);
 }
 
 static inline int flat_grid(int64_t n) {

@@ -900,8 +900,8 @@ int cdrl_gather_rows(const float* src, const int32_t* idx, float* dst, int nrows
 
 int cdrl_gemm_nn(const float* A, int lda, int a_coff, const float* B, int sbk, int sbn, const float* bias, float* C,
                  int ldc, int c_coff, int M, int N, int K, int accumulate, void* stream) {
-    return gemm_nn(make_view(const_cast<float*>(A), lda, a_coff), B, sbk, sbn, bias, make_view(C, ldc, c_coff), M, N, K,
-                   accumulate, S(stream));
+    const cdrl_view a{const_cast<float*>(A), lda, a_coff}, c{C, ldc, c_coff};
+    return cdrl_gemm_nn_ex(&a, B, sbk, sbn, bias, &c, M, N, K, accumulate, nullptr, nullptr, 0, nullptr, stream);
 }
 
 int64_t cdrl_gemm_tn_workspace_elems(int M, int N, int K) { return gemm_tn_part_elems(M, N, K); }
@@ -1475,6 +1475,109 @@ int cdrl_reduce_partials_f32(const float* part, int nparts, int64_t n, int64_t s
         return -1;
     }
     return reduce_partials_f32(part, nparts, n, stride, out, accumulate, S(stream));
+}
+
+// ---- dense GEMM family: the plan gemm_nn dispatches on, the entry with its whole contract, the activations, the bias-gradient sums ----
+static const char* nn_view_fits(const cdrl_view* v, int cols) {
+    if (!v) return "a view is missing";
+    if (v->coff < 0 || cols < 0 || v->coff + cols > v->ld) return "the columns of a view do not fit its rows";
+    return nullptr;
+}
+
+int cdrl_gemm_nn_plan(const cdrl_view* a, uint64_t b_addr, int sbk, int sbn, int M, int N, int K, int has_workspace, int32_t* fields,
+                      int n_out) {
+    const char* bad = (!fields && n_out > 0) ? "no field array" : nn_view_fits(a, K);
+    if (bad) {
+        cdrl::set_error("cdrl_gemm_nn_plan: %s", bad);
+        return -1;
+    }
+    const NnPlan p = gemm_nn_plan(view_of(a), reinterpret_cast<const float*>((uintptr_t)b_addr), sbk, sbn, M, N, K, has_workspace != 0);
+    const int32_t v[] = {p.kernel, p.NT, p.WR, p.BT, p.VEC, p.gx, p.gy, p.gz, p.kchunk, (int32_t)p.ws_elems, p.reduce_grid, p.act_fused, p.a16, p.b16};
+    int n = 0;
+    for (int32_t x : v) {
+        if (n < n_out) fields[n] = x;
+        ++n;
+    }
+    return n;
+}
+
+int64_t cdrl_gemm_nn_workspace_elems(int M, int N, int K) {
+    if (M < 1 || N < 1 || K < 1) return 0;
+    return gemm_nn_splitk_elems(M, N, K);
+}
+
+int cdrl_gemm_nn_ex(const cdrl_view* a, const float* B, int sbk, int sbn, const float* bias, const cdrl_view* c, int M, int N, int K,
+                    int accumulate, float* workspace, float* act_out, int act, int* act_done, void* stream) {
+    if (act_done) *act_done = 0;
+    const char* bad = nn_view_fits(a, K);
+    if (!bad) bad = nn_view_fits(c, N);
+    if (!bad && (!a->p || !c->p || !B)) bad = "null tensor";
+    if (!bad && act_out && !workspace) bad = "act_out is written by the split-K reduce: it needs the workspace";
+    if (!bad && (act < ACT_NONE || act > ACT_SIGMOID)) bad = "unknown activation";
+    if (bad) {
+        cdrl::set_error("cdrl_gemm_nn_ex: %s (M %d N %d K %d act %d)", bad, M, N, K, act);
+        return -1;
+    }
+    bool done = false;
+    const int rc = gemm_nn(view_of(a), B, sbk, sbn, bias, view_of(c), M, N, K, accumulate, S(stream), workspace, act_out, act,
+                           act_done ? &done : nullptr);
+    if (act_done) *act_done = done ? 1 : 0;
+    return rc;
+}
+
+static bool flat_args_ok(const char* fn, bool ptrs, int64_t n, int act) {
+    if (!ptrs || n < 1 || act < ACT_NONE || act > ACT_SIGMOID) {
+        cdrl::set_error("%s: null tensor, n %lld < 1 or unknown activation %d", fn, (long long)n, act);
+        return false;
+    }
+    return true;
+}
+
+int cdrl_act_fwd(const float* z, float* a, int64_t n, int act, void* stream) {
+    if (!flat_args_ok("cdrl_act_fwd", z && a, n, act)) return -1;
+    return act_fwd(z, a, n, act, S(stream));
+}
+
+int cdrl_act_bwd(const float* z, const float* da, float* dz, int64_t n, int act, void* stream) {
+    if (!flat_args_ok("cdrl_act_bwd", z && da && dz, n, act)) return -1;
+    return act_bwd(z, da, dz, n, act, S(stream));
+}
+
+int cdrl_colsum_partial_rows(int rows, int C) {
+    if (rows < 1 || C < 1) return 0;
+    return vcol_geom(rows, C).nb;
+}
+
+int cdrl_colsum(const cdrl_view* x, int rows, int C, double* part, void* stream) {
+    if (rows < 1 || C < 1 || !part) {
+        cdrl::set_error("cdrl_colsum: rows %d, C %d or a null partial buffer", rows, C);
+        return -1;
+    }
+    if (!view_ok("cdrl_colsum", "x", x, C, 0)) return -1;
+    return colsum(view_of(x), rows, C, part, S(stream));
+}
+
+int cdrl_reduce_partials_cx(int nparts, int n1, int n2) {
+    if (nparts < 1 || n1 < 1 || n2 < 0) return 0;
+    return reduce_partials_cx(nparts, n1 + n2);
+}
+
+int cdrl_reduce_partials(const double* part, int nparts, int n1, int n2, int64_t stride, float* out1, float* out2, int accumulate,
+                         void* stream) {
+    if (nparts < 1 || n1 < 1 || n2 < 0 || stride < (int64_t)n1 + n2 || !part || !out1 || (n2 > 0 && !out2)) {
+        cdrl::set_error("cdrl_reduce_partials: nparts %d, n1 %d, n2 %d, stride %lld, or a null tensor", nparts, n1, n2, (long long)stride);
+        return -1;
+    }
+    if (n2 == 0) return reduce_partials(part, nparts, n1, stride, out1, accumulate, S(stream));
+    return reduce_partials2(part, nparts, n1, n2, stride, out1, out2, accumulate, S(stream));
+}
+
+int cdrl_permute_bt(const float* src, float* dst, int B, int T, int D, void* stream) {
+    if (!src || !dst || B < 1 || T < 1 || D < 1) {
+        cdrl::set_error("cdrl_permute_bt: null tensor or bad shape B %d T %d D %d", B, T, D);
+        return -1;
+    }
+    return permute_bt(src, dst, B, T, D, S(stream));
 }
 
 int cdrl_bn_act_gap_fwd(const float* y, const float* stats, float* out, int G, int frames_per_group, int P, int C, int relu6,

@@ -35,6 +35,41 @@ enum Act : int { ACT_NONE = 0, ACT_RELU6 = 1, ACT_SWISH6 = 2, ACT_TANH = 3, ACT_
 // with another kernel's waves on the same SIMD the top lanes of that mask were occasionally stale.
 __device__ __forceinline__ bool relu6_open(float z) { return fminf(z, 6.0f - z) > 0.0f; }
 
+// The dense activations (relu6 for the feature nets, swish6 for the control branches, tanh / sigmoid for the gates), stated once:
+// act_fwd_kernel (bn.hip) and the split-K reduce of gemm_nn (gemm.hip) both call act_value, act_bwd_kernel calls act_grad.
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+__device__ __forceinline__ float act_value(float x, int act) {
+    float o = x;
+    if (act == ACT_RELU6) o = fminf(fmaxf(x, 0.0f), 6.0f);
+    else if (act == ACT_SWISH6) o = fminf(x * sigmoidf_(x), 6.0f);      // rl/utils.py:420-421
+    else if (act == ACT_TANH) o = tanhf(x);
+    else if (act == ACT_SIGMOID) o = sigmoidf_(x);
+    return o;
+}
+
+#define SWISH6_CLOSED 6.01465654f      // 0x1.80f022p+2
+
+// d = dL/da -> dL/dz at pre-activation x
+__device__ __forceinline__ float act_grad(float x, float d, int act) {
+    if (act == ACT_RELU6) {
+        if (!relu6_open(x)) d = 0.0f;
+    } else if (act == ACT_SWISH6) {
+        // SURVEY.md Appendix E.  The gate x sigmoid(x) < 6 is decided on x: the product is increasing for x > 0 and crosses 6 at
+        // x* = 6.014656129..., and SWISH6_CLOSED is the smallest float32 above x*.  The rounded float32 product reaches 6.0f one float32
+        // below x* already (x = 6.01465607), where the true product is still below 6: the gate was closed one input early.
+        const float s = sigmoidf_(x);
+        d = (x < SWISH6_CLOSED) ? d * (s * (1.0f + x * (1.0f - s))) : 0.0f;
+    } else if (act == ACT_TANH) {
+        const float t = tanhf(x);
+        d *= (1.0f - t * t);
+    } else if (act == ACT_SIGMOID) {
+        const float s = sigmoidf_(x);
+        d *= s * (1.0f - s);
+    }
+    return d;
+}
+
 __host__ __device__ inline int shuffle_dst(int i, int ctot) { return (i & 1) * (ctot >> 1) + (i >> 1); }
 
 void set_error(const char* fmt, ...);

@@ -71,6 +71,8 @@ int reduce_partials(const double* part, int nparts, int n, int64_t stride, float
 // two outputs from one partial row: columns [0, n1) -> out1, [n1, n1+n2) -> out2 (filter + bias in one launch)
 int reduce_partials2(const double* part, int nparts, int n1, int n2, int64_t stride, float* out1, float* out2, int accumulate,
                      hipStream_t st);
+// the CX (outputs per block: 16 or 4) of the reduce_partials_kernel both launch for nparts partials of n = n1 + n2 outputs
+int reduce_partials_cx(int nparts, int n);
 // column sums of a view: part [nb][C] with nb = col_geom(rows, C).nb
 int colsum(View x, int rows, int C, double* part, hipStream_t st);
 // dst(view) = src(view) gathered through the shuffle map on the *source* (backward of shuffle)
@@ -101,6 +103,21 @@ int gather_rows(const float* src, const int* idx, float* dst, int nrows, int64_t
 // fp32 MFMA (v_mfma_f32_32x32x2_f32): results are bit-identical to a k-ordered fmaf chain.
 // splitk_ws (>= gemm_nn_splitk_elems floats, or null): enables split-K for small-M / long-K products
 int64_t gemm_nn_splitk_elems(int M, int N, int K);
+// The one dispatch decision of gemm_nn: which kernel, which instantiation, which grid, how much workspace.  gemm_nn_plan is address
+// arithmetic only (reads no memory, launches nothing); gemm_nn launches from it and cdrl_gemm_nn_plan reports it.
+// Instantiations: gemm_nn_kernel<NT, BT, VEC, WR> for (NT, WR) in {(1, 4), (3, 4), (2, 2), (4, 2)}, gemm_nn_rt_kernel<3, BT>.
+struct NnPlan {
+    int kernel;                 // -1 empty product (M or N < 1), 0 gemm_nn_kernel, 1 gemm_nn_rt_kernel, 2 split-K: gemm_nn_kernel with
+                                // gridDim.z = gz slabs into the workspace, then splitk_reduce_kernel
+    int NT, WR, BT, VEC;        // template arguments (kernel 1: NT = RT = 3, WR 0, VEC 0)
+    int gx, gy, gz;             // grid; gz = number of K splits (1 unless kernel 2)
+    int kchunk;                 // K range of one split (a multiple of 32; 1 << 30 without split-K)
+    int64_t ws_elems;           // floats of workspace split-K writes: gz * M * N (<= gemm_nn_splitk_elems)
+    int reduce_grid;            // blocks of splitk_reduce_kernel (0 unless kernel 2)
+    int act_fused;              // kernel 2: the reduce can write act_out (gemm_nn does so when act_out and act_done are given)
+    int a16, b16;               // 16-byte alignment of the A rows / of the weight rows (what kernel 1 needs next to N >= 129, K >= 64, M >= 2048)
+};
+NnPlan gemm_nn_plan(View A, const float* Bp, int sbk, int sbn, int M, int N, int K, bool has_workspace);
 int gemm_nn(View A, const float* Bp, int sbk, int sbn, const float* bias, View C, int M, int N, int K,
             int accumulate, hipStream_t st, float* splitk_ws = nullptr,
             float* act_out = nullptr, int act = 0, bool* act_done = nullptr);

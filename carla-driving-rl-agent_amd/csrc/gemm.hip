@@ -314,7 +314,7 @@ static void launch_nn_rt(bool bt, hipStream_t st, View A, const float* Bp, int s
 
 template <int NT, int WR>
 static void launch_nn(bool bt, bool vec, dim3 grid, hipStream_t st, View A, const float* Bp, int sbk, int sbn,
-                      const float* bias, View C, int M, int N, int K, int acc, int kchunk = 1 << 30, int64_t czs = 0) {
+                      const float* bias, View C, int M, int N, int K, int acc, int kchunk, int64_t czs) {
     if (bt) {
         if (vec) hipLaunchKernelGGL((gemm_nn_kernel<NT, true, true, WR>), grid, dim3(256), 0, st, A, Bp, sbk, sbn, bias, C, M, N, K, acc, kchunk, czs);
         else hipLaunchKernelGGL((gemm_nn_kernel<NT, true, false, WR>), grid, dim3(256), 0, st, A, Bp, sbk, sbn, bias, C, M, N, K, acc, kchunk, czs);
@@ -324,11 +324,9 @@ static void launch_nn(bool bt, bool vec, dim3 grid, hipStream_t st, View A, cons
     }
 }
 
-static int g_nn_bm64_threshold = -1;
-
 // C(view) (+)= bias + sum_z part[z]  (fixed order)
-// act_out (dense [M][N], optional): the layer's activation of the reduced value as well -- same expressions as act_fwd_kernel (bn.hip),
-// which was a launch of its own behind every split-K Dense layer
+// act_out (dense [M][N], optional): the layer's activation of the reduced value as well -- act_value (cdrl_common.h), the function
+// act_fwd_kernel (bn.hip) applies, which was a launch of its own behind every split-K Dense layer
 __global__ void splitk_reduce_kernel(const float* __restrict__ part, int nsplit, int M, int N, const float* __restrict__ bias,
                                      View C, int accumulate, float* __restrict__ act_out, int act) {
     const int64_t n = (int64_t)M * N;
@@ -340,93 +338,102 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ part, int nsplit,
         float* o = &C.p[m * C.ld + C.coff + c];
         const float x = accumulate ? *o + s : s;
         *o = x;
-        if (act_out) {
-            float a = x;
-            if (act == ACT_RELU6) a = fminf(fmaxf(x, 0.0f), 6.0f);
-            else if (act == ACT_SWISH6) a = fminf(x * (1.0f / (1.0f + expf(-x))), 6.0f);
-            else if (act == ACT_TANH) a = tanhf(x);
-            else if (act == ACT_SIGMOID) a = 1.0f / (1.0f + expf(-x));
-            act_out[i] = a;
-        }
+        if (act_out) act_out[i] = act_value(x, act);
     }
 }
+
+// split-K is for few output tiles and a long reduction (GRU projections: M = B or T*B, K = 256 / 768), in at most NN_MAX_SPLIT slabs
+static constexpr int NN_MAX_SPLIT = 8;
+static inline bool nn_splitk_shape(int M, int K) { return M <= 2048 && K >= 256; }
 
 int64_t gemm_nn_splitk_elems(int M, int N, int K) {
-    if (M > 2048 || K < 256) return 0;
-    return (int64_t)8 * M * N;
+    if (!nn_splitk_shape(M, K)) return 0;
+    return (int64_t)NN_MAX_SPLIT * M * N;
 }
 
-int gemm_nn(View A, const float* Bp, int sbk, int sbn, const float* bias, View C, int M, int N, int K,
-            int accumulate, hipStream_t st, float* splitk_ws, float* act_out, int act, bool* act_done) {
-    if (act_done) *act_done = false;
-    if (M <= 0 || N <= 0) return 0;
-    if (splitk_ws && gemm_nn_splitk_elems(M, N, K) > 0) {
-        // few output tiles, long reduction (GRU projections: M = B or T*B, K = 256 / 768): split K over blockIdx.z so that
-        // the chip is filled, partial slabs + fixed-order reduction (the 4x2-workgroup launch took 60 us for 0.1 GFLOP)
-        int nt = cdiv(N, 32);
-        if (nt > 4) nt = 4;
-        const int ncb = cdiv(N, 32 * nt);
-        nt = cdiv(cdiv(N, ncb), 32);
-        if (nt % 2 == 0) {
-            const int gy = cdiv(N, 32 * nt), gx = cdiv(M, 64);
-            int nsplit = cdiv(512, gx * gy);
-            if (nsplit > 8) nsplit = 8;
-            int kchunk = cdiv(cdiv(K, nsplit), 32) * 32;
-            nsplit = cdiv(K, kchunk);
-            if (nsplit > 1) {
-                const bool bt = sbn != 1;
-                const bool vec = (K % 2 == 0) && (A.ld % 2 == 0) && (A.coff % 2 == 0) && ((reinterpret_cast<uintptr_t>(A.p) & 7) == 0);
-                dim3 grid(gx, gy, nsplit);
-                View P = make_view(splitk_ws, N);
-                if (nt == 2) launch_nn<2, 2>(bt, vec, grid, st, A, Bp, sbk, sbn, nullptr, P, M, N, K, 0, kchunk, (int64_t)M * N);
-                else launch_nn<4, 2>(bt, vec, grid, st, A, Bp, sbk, sbn, nullptr, P, M, N, K, 0, kchunk, (int64_t)M * N);
-                CDRL_LAUNCH_CHECK();
-                const int64_t n = (int64_t)M * N;
-                hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048)), dim3(256), 0, st,
-                                   splitk_ws, nsplit, M, N, bias, C, accumulate, act_done ? act_out : nullptr, act);
-                CDRL_LAUNCH_CHECK();
-                if (act_done && act_out) *act_done = true;
-                return 0;
-            }
-        }
-    }
-    if (g_nn_bm64_threshold < 0) {
-        g_nn_bm64_threshold = 1 << 30;   // use 64-row tiles below this many 128-row blocks; measured: 64-row tiles win at every learner shape
-    }
+NnPlan gemm_nn_plan(View A, const float* Bp, int sbk, int sbn, int M, int N, int K, bool has_workspace) {
+    NnPlan p{};
+    p.kernel = -1;
+    if (M <= 0 || N <= 0) return p;
     int nt = cdiv(N, 32);
     if (nt > 4) nt = 4;
     // balance column blocks: e.g. N=232 -> 2 blocks of 4 tiles; N=92 -> 1 block of 3 tiles
     const int ncb = cdiv(N, 32 * nt);
     nt = cdiv(cdiv(N, ncb), 32);
-    const int gy = cdiv(N, 32 * nt);
-    const bool bt = sbn != 1;
-    const bool vec = (K % 2 == 0) && (A.ld % 2 == 0) && (A.coff % 2 == 0) && ((reinterpret_cast<uintptr_t>(A.p) & 7) == 0);
-    {   // row-stacked tiles for the wide late layers
-        static constexpr int rt_minn = 129;
-        const bool a16 = (K % 4 == 0) && (A.ld % 4 == 0) && (A.coff % 4 == 0) && ((reinterpret_cast<uintptr_t>(A.p) & 15) == 0);
-        const bool b16 = ((reinterpret_cast<uintptr_t>(Bp) & 15) == 0) &&
-                         (bt ? (sbk == 1 && sbn % 4 == 0) : (sbn == 1 && sbk % 4 == 0 && N % 4 == 0));
-        if (N >= rt_minn && K >= 64 && M >= 2048 && a16 && b16) {
-            launch_nn_rt<3>(bt, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate);
-            CDRL_LAUNCH_CHECK();
-            return 0;
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(A.p), pb = reinterpret_cast<uintptr_t>(Bp);
+    p.NT = nt;
+    p.gy = cdiv(N, 32 * nt);
+    p.gz = 1;
+    p.kchunk = 1 << 30;
+    p.BT = sbn != 1;
+    p.VEC = (K % 2 == 0) && (A.ld % 2 == 0) && (A.coff % 2 == 0) && ((pa & 7) == 0);
+    p.a16 = (K % 4 == 0) && (A.ld % 4 == 0) && (A.coff % 4 == 0) && ((pa & 15) == 0);
+    p.b16 = ((pb & 15) == 0) && (p.BT ? (sbk == 1 && sbn % 4 == 0) : (sbn == 1 && sbk % 4 == 0 && N % 4 == 0));
+    // 64-row tiles (2 x 2 waves) whenever the column-tile count is even: measured, they win at every learner shape
+    p.WR = nt % 2 == 0 ? 2 : 4;
+    p.gx = cdiv(M, 32 * p.WR);
+    if (has_workspace && nn_splitk_shape(M, K) && nt % 2 == 0) {
+        // partial slabs + fixed-order reduction, enough slabs to fill the chip (the 4x2-workgroup launch took 60 us for 0.1 GFLOP)
+        int nsplit = cdiv(512, p.gx * p.gy);
+        if (nsplit > NN_MAX_SPLIT) nsplit = NN_MAX_SPLIT;
+        const int kchunk = cdiv(cdiv(K, nsplit), 32) * 32;
+        nsplit = cdiv(K, kchunk);
+        if (nsplit > 1) {
+            const int64_t n = (int64_t)M * N;
+            p.kernel = 2;
+            p.gz = nsplit;
+            p.kchunk = kchunk;
+            p.ws_elems = nsplit * n;
+            p.reduce_grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+            p.act_fused = 1;
+            return p;
         }
     }
-    const bool small = (nt % 2 == 0) && (cdiv(M, 128) * gy < g_nn_bm64_threshold);
-    if (small) {
-        dim3 grid(cdiv(M, 64), gy);
-        if (nt == 2) launch_nn<2, 2>(bt, vec, grid, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate);
-        else launch_nn<4, 2>(bt, vec, grid, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate);
+    // row-stacked tiles for the wide late layers
+    if (N >= 129 && K >= 64 && M >= 2048 && p.a16 && p.b16) {
+        p.kernel = 1;
+        p.NT = 3;           // RT
+        p.WR = 0;
+        p.VEC = 0;
+        p.gx = cdiv(M, 96);
+        p.gy = cdiv(N, 128);
+        return p;
+    }
+    p.kernel = 0;
+    return p;
+}
+
+int gemm_nn(View A, const float* Bp, int sbk, int sbn, const float* bias, View C, int M, int N, int K,
+            int accumulate, hipStream_t st, float* splitk_ws, float* act_out, int act, bool* act_done) {
+    if (act_done) *act_done = false;
+    const NnPlan p = gemm_nn_plan(A, Bp, sbk, sbn, M, N, K, splitk_ws != nullptr);
+    if (p.kernel < 0) return 0;
+    if (p.kernel == 1) {
+        launch_nn_rt<3>(p.BT, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate);
+        CDRL_LAUNCH_CHECK();
+        return 0;
+    }
+    // kernel 2: every slab is a plain product into its own dense [M][N] piece of the workspace
+    const bool split = p.kernel == 2;
+    const View out = split ? make_view(splitk_ws, N) : C;
+    const float* kb = split ? nullptr : bias;
+    const int kacc = split ? 0 : accumulate;
+    const int64_t czs = split ? (int64_t)M * N : 0;
+    const dim3 grid(p.gx, p.gy, p.gz);
+    if (p.WR == 2) {
+        if (p.NT == 2) launch_nn<2, 2>(p.BT, p.VEC, grid, st, A, Bp, sbk, sbn, kb, out, M, N, K, kacc, p.kchunk, czs);
+        else launch_nn<4, 2>(p.BT, p.VEC, grid, st, A, Bp, sbk, sbn, kb, out, M, N, K, kacc, p.kchunk, czs);
     } else {
-        dim3 grid(cdiv(M, 128), gy);
-        switch (nt) {
-            case 1: launch_nn<1, 4>(bt, vec, grid, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate); break;
-            case 2: launch_nn<2, 4>(bt, vec, grid, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate); break;
-            case 3: launch_nn<3, 4>(bt, vec, grid, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate); break;
-            default: launch_nn<4, 4>(bt, vec, grid, st, A, Bp, sbk, sbn, bias, C, M, N, K, accumulate); break;
-        }
+        if (p.NT == 1) launch_nn<1, 4>(p.BT, p.VEC, grid, st, A, Bp, sbk, sbn, kb, out, M, N, K, kacc, p.kchunk, czs);
+        else launch_nn<3, 4>(p.BT, p.VEC, grid, st, A, Bp, sbk, sbn, kb, out, M, N, K, kacc, p.kchunk, czs);
     }
     CDRL_LAUNCH_CHECK();
+    if (split) {
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)p.reduce_grid), dim3(256), 0, st, splitk_ws, p.gz, M, N, bias, C, accumulate,
+                           act_done ? act_out : nullptr, act);
+        CDRL_LAUNCH_CHECK();
+        if (act_done && act_out) *act_done = true;
+    }
     return 0;
 }
 

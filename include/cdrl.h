@@ -863,6 +863,42 @@ int cdrl_gemm_tn_ex(const cdrl_view* a, const float* a_stats, const cdrl_view* d
  * 4 / 5 scalar with 16 / 4 column lanes -- any alignment), grid, block x, block y.  -1: nparts < 1, n < 1 or stride < n. */
 int cdrl_reduce_partials_plan(uint64_t part_addr, int nparts, int64_t n, int64_t stride, int32_t* fields, int n_out);
 int cdrl_reduce_partials_f32(const float* part, int nparts, int64_t n, int64_t stride, float* out, int accumulate, void* stream);
+
+/* ---- The dense GEMM family  c[M][N] (+)= a[M][K] B(k, n) + bias[n],  B(k, n) = B[k * sbk + n * sbn]  (cdrl_gemm_nn above is its form without
+ * workspace), with the whole contract of the engine's calls: a and c are views; workspace (cdrl_gemm_nn_workspace_elems floats, or NULL)
+ * allows split-K; act_out (dense [M][N], or NULL) with act (0 none, 1 relu6, 2 swish6, 3 tanh, 4 sigmoid) and act_done (or NULL): when
+ * the product goes through split-K and act_done is given, the reduce also writes act(c) to act_out and sets *act_done = 1; otherwise
+ * *act_done = 0, act_out is not touched and the caller runs cdrl_act_fwd.  Refused (-1, cdrl_last_error) before any launch: a view
+ * whose columns do not fit its rows, null a / B / c, act_out without workspace, an act outside 0..4.
+ * cdrl_gemm_nn_plan: what gemm_nn dispatches on for these arguments (the launcher calls the same host function) -- launches nothing,
+ * reads no memory: only the address bits, ld and coff count.  Writes min(n_out, 14) int32 fields and returns 14 (-1: no field array, or
+ * the K columns of a do not fit its rows):
+ *    0 kernel   -1 M or N < 1: nothing to launch; 0 gemm_nn_kernel; 1 gemm_nn_rt_kernel (M >= 2048, N >= 129, K >= 64, a16 and b16);
+ *               2 split-K (workspace, M <= 2048, K >= 256, even NT, gz >= 2): gemm_nn_kernel over gz slabs, then splitk_reduce_kernel
+ *    1 NT  2 WR  3 BT  4 VEC   the instantiation gemm_nn_kernel<NT, BT, VEC, WR>, (NT, WR) one of (1, 4), (3, 4), (2, 2), (4, 2); BT: sbn != 1;
+ *               VEC: 8-byte loads of a (K, ld, coff even, pointer 8-byte aligned).  Kernel 1: gemm_nn_rt_kernel<NT = 3, BT>, WR = VEC = 0
+ *    5 gx  6 gy  7 gz (K splits; 1 without split-K)  8 kchunk (K range of one split, a multiple of 32; 1 << 30 without split-K)
+ *    9 ws_elems = gz * M * N floats the split writes (0 without)  10 reduce_grid  11 act_fused (the reduce can write act_out)
+ *   12 a16  13 b16   16-byte alignment of the rows of a (K, ld, coff multiples of 4, pointer) / of the weight rows */
+int cdrl_gemm_nn_plan(const cdrl_view* a, uint64_t b_addr, int sbk, int sbn, int M, int N, int K, int has_workspace, int32_t* fields,
+                      int n_out);
+int64_t cdrl_gemm_nn_workspace_elems(int M, int N, int K);
+int cdrl_gemm_nn_ex(const cdrl_view* a, const float* B, int sbk, int sbn, const float* bias, const cdrl_view* c, int M, int N, int K,
+                    int accumulate, float* workspace, float* act_out, int act, int* act_done, void* stream);
+/* a = act(z), dz = da * act'(z) on dense float32 arrays of n elements (act as above; relu6 gradient 1 strictly inside (0, 6), swish6 =
+ * min(z sigmoid(z), 6) with gradient 0 where z sigmoid(z) >= 6) */
+int cdrl_act_fwd(const float* z, float* a, int64_t n, int act, void* stream);
+int cdrl_act_bwd(const float* z, const float* da, float* dz, int64_t n, int act, void* stream);
+/* Bias gradient: part [cdrl_colsum_partial_rows(rows, C)][C] doubles = column sums of row blocks of the view x; cdrl_reduce_partials
+ * folds them: out1[i] (+)= float(sum_p part[p * stride + i]) for i < n1, out2[i - n1] likewise for n1 <= i < n1 + n2 (n2 = 0: out2
+ * unused).  cdrl_reduce_partials_cx: outputs per block (16 or 4) of the kernel form that call launches. */
+int cdrl_colsum_partial_rows(int rows, int C);
+int cdrl_colsum(const cdrl_view* x, int rows, int C, double* part, void* stream);
+int cdrl_reduce_partials_cx(int nparts, int n1, int n2);
+int cdrl_reduce_partials(const double* part, int nparts, int n1, int n2, int64_t stride, float* out1, float* out2, int accumulate,
+                         void* stream);
+/* (B, T, D) -> (T, B, D): dst[(t * B + b) * D + d] = src[(b * T + t) * D + d] */
+int cdrl_permute_bt(const float* src, float* dst, int B, int T, int D, void* stream);
 /* out[n][c] (float32) = mean over the P rows of frame n of [relu6](scale * y + shift); y dense [G*frames_per_group*P][C] */
 int cdrl_bn_act_gap_fwd(const float* y, const float* stats, float* out, int G, int frames_per_group, int P, int C, int relu6,
                         int act_type, void* stream);
