@@ -20,7 +20,6 @@
 
 namespace cdrl {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define BK 32
 
@@ -145,7 +144,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nn_kernel(View A, const float* __
         const float bv = bias ? bias[n] : 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int64_t m = acc_row(m0 + wr * 32, r, lk);
             if (m < M) {
                 float* c = &C.p[m * C.ld + C.coff + n];
                 float v = acc[j][r] + bv;
@@ -293,7 +292,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nn_rt_kernel(View A, const float*
     for (int i = 0; i < RT; ++i) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int64_t m = acc_row(m0 + i * 32, r, lk);
             if (m < M) {
                 float* c = &C.p[m * C.ld + C.coff + n];
                 float v = acc[i][r] + bv;

@@ -27,9 +27,6 @@
 
 namespace cdrl {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 struct PwArgs {
     View A;                     // PRO_BNBWD: gradient w.r.t. the BN output (the dz source)
@@ -229,24 +226,19 @@ __global__ void __launch_bounds__(256, (pw_occ(KSM, NT))) pw_nn_kernel(PwArgs a)
     // two tiles ahead, was measured slower: it costs a wave of occupancy, 25.6 -> 29.4 us at K = N = 58)
     const bool dz_vec = PRO == 2 && !a.a_shuffle && (a.A.ld % 2 == 0) && (a.A.coff % 2 == 0) &&
                         ((reinterpret_cast<uintptr_t>(a.A.p) & 7) == 0);
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
     float2 ra0[NA2], ry0[PRO == 2 ? NA2 : 1];
     // Tile loads through buffer descriptors: a thread's rows of a tile are r = tid / KSM + (256 / KSM) * i, so the row
     // offset of load i is wave-uniform (SGPR soffset) and the thread's byte offset inside it is a constant voffset --
     // no 64-bit address arithmetic and no address registers (the <64, 4, 2, 2> variant spilled 41 VGPRs with flat loads).
     // Masked lanes (k beyond K, rows beyond the group in the last tile) point out of range and read 0.
     constexpr int RSTEP = 256 / KSM;                 // rows between consecutive loads of a thread
-    const uint32_t OOR = 0x80000000u;               // host checks that the operands are < 2 GB
     const int r_t = tid / KSM;
     const int64_t Mtot = (int64_t)a.G * a.Mg;
-    const __amdgpu_buffer_rsrc_t rsA =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A.p), 0, (int)(Mtot * a.A.ld * ESZ), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(PRO == 2 ? a.a_y : a.A.p), 0, (int)(Mtot * (PRO == 2 ? K : a.A.ld) * ESZ), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = buffer_rsrc(a.A.p, (int)(Mtot * a.A.ld * ESZ));
+    const __amdgpu_buffer_rsrc_t rsY = buffer_rsrc(PRO == 2 ? a.a_y : a.A.p, (int)(Mtot * (PRO == 2 ? K : a.A.ld) * ESZ));
     // bf16 storage: descriptors for the epilogue's raw-BN-input tile (EPI_BNRED) and the old output tile (ACC)
-    const __amdgpu_buffer_rsrc_t rsE = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>((BH && EPI == 2) ? a.ey : a.A.p), 0,
-                                                                         (int)(Mtot * N * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(a.C.p, 0, (int)(Mtot * a.C.ld * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsE = buffer_rsrc((BH && EPI == 2) ? a.ey : a.A.p, (int)(Mtot * N * 2));
+    const __amdgpu_buffer_rsrc_t rsC = buffer_rsrc(a.C.p, (int)(Mtot * a.C.ld * 2));
     uint32_t voA0 = OOR, voA1 = OOR, voY = OOR;
     if (kon) {
         if (PRO == 2) {
@@ -384,13 +376,13 @@ __global__ void __launch_bounds__(256, (pw_occ(KSM, NT))) pw_nn_kernel(PwArgs a)
                 const int n = nb0 + (wc + j * WC) * 32 + lrow;
                 if constexpr (BH && EPI == 2) {         // paired 4-byte buffer loads, unconditional (out-of-range offsets read 0)
                     pair_load16(rsE, (lane & 1) != 0, [&](int r) -> uint32_t {
-                        const int64_t m = me0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                        const int64_t m = acc_row(me0, r, lk);
                         return (n < N && m < mend) ? (uint32_t)((m * N + (n & ~1)) * 2) : OOR;
                     }, &eyv[EPI == 2 ? j : 0][0]);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int64_t m = me0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                        const int64_t m = acc_row(me0, r, lk);
                         eyv[j][r] = (n < N && m < mend) ? a.ey[m * N + n] : 0.0f;
                     }
                 }
@@ -408,13 +400,13 @@ __global__ void __launch_bounds__(256, (pw_occ(KSM, NT))) pw_nn_kernel(PwArgs a)
                 const int n = nb0 + (wc + j * WC) * 32 + lrow;
                 if constexpr (BH && ACC_PF) {
                     pair_load16(rsC, (lane & 1) != 0, [&](int r) -> uint32_t {
-                        const int64_t m = mc0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                        const int64_t m = acc_row(mc0, r, lk);
                         return (n < N && m < mend) ? (uint32_t)((m * a.C.ld + a.C.coff + (n & ~1)) * 2) : OOR;
                     }, &cold[ACC_PF ? j : 0][0]);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int64_t m = mc0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                        const int64_t m = acc_row(mc0, r, lk);
                         cold[ACC_PF ? j : 0][ACC_PF ? r : 0] = (n < N && m < mend) ? a.C.p[m * a.C.ld + a.C.coff + n] : 0.0f;
                     }
                 }
@@ -451,7 +443,7 @@ __global__ void __launch_bounds__(256, (pw_occ(KSM, NT))) pw_nn_kernel(PwArgs a)
                     float v[16];
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                        const int64_t m = acc_row(m0, r, lk);
                         v[r] = acc[j][r] + bv[j];
                         if (EPI == 1) v[r] = (float)(bf16_t)v[r];       // statistics of the stored (rounded) values
                         if (m < mend) {
@@ -472,7 +464,7 @@ __global__ void __launch_bounds__(256, (pw_occ(KSM, NT))) pw_nn_kernel(PwArgs a)
                         const float recv = lane_swap1(odd ? v[2 * q] : v[2 * q + 1]);
                         const float lo = odd ? recv : v[2 * q], hi = odd ? v[2 * q + 1] : recv;
                         const int r = 2 * q + (odd ? 1 : 0);
-                        const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                        const int64_t m = acc_row(m0, r, lk);
                         if (m < mend) *reinterpret_cast<uint32_t*>(cp + m * a.C.ld) = bf_pack(lo, hi);
                     }
                     continue;
@@ -480,7 +472,7 @@ __global__ void __launch_bounds__(256, (pw_occ(KSM, NT))) pw_nn_kernel(PwArgs a)
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int64_t m = acc_row(m0, r, lk);
                 if (m < mend) {
                     T* c = vptr<T>(a.C) + m * a.C.ld + a.C.coff + n;
                     float v = acc[j][r] + bv[j];

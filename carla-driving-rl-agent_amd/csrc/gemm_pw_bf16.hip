@@ -11,13 +11,10 @@
 // per 32x32 tile (36 % MfmaUtil measured, profiles/r02_pmc_mfma.json); here it is 8 steps of 32 cycles.
 #include <stdlib.h>
 
-#include "cdrl_kernels.h"
+#include "mfma_x3.h"
 
 namespace cdrl {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 struct PwBf16Args {
     const __bf16* A;            // [G*Mg][lda] (+ a_coff)
@@ -78,11 +75,8 @@ __global__ void __launch_bounds__(256) pw_bf16_kernel(PwBf16Args a) {
     double s1 = 0.0, s2 = 0.0;
 
     // tile loads: chunk c = tid + 256 i -> row c / CPR, 4 bf16 at column 4 (c % CPR); 8-byte buffer loads, masked lanes read 0
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-    const uint32_t OOR = 0x80000000u;
     const int64_t Mtot = (int64_t)a.G * a.Mg;
-    const __amdgpu_buffer_rsrc_t rsA =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(a.A), 0, (int)(Mtot * a.lda * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = buffer_rsrc(a.A, (int)(Mtot * a.lda * 2));
     u32x2_t ra[NCH];
     auto load_tile = [&](int t) {
         const int64_t m0 = mbeg + (int64_t)t * BM;
@@ -123,7 +117,7 @@ __global__ void __launch_bounds__(256) pw_bf16_kernel(PwBf16Args a) {
         const int64_t m0 = mbeg + (int64_t)t * BM + wr * 32;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int64_t m = acc_row(m0, r, lk);
             if (m < mend) {
                 const __bf16 o = (__bf16)(acc[r] + bv);
                 if (EPI) {

@@ -1,5 +1,5 @@
 // Backward of a pointwise (1x1) convolution as ONE pass over its operands (gfx950, v_mfma_f32_32x32x16_bf16 on exact three-way
-// bf16 splits of float32 operands, see gemm_pw_x3.hip).
+// bf16 splits of float32 operands, see mfma_x3.h).
 //
 // Reference: the gradient of Conv2D(k=1) -> BatchNormalization (core/architectures.py:130-141) inside tape.gradient
 // (core/carla_agent.py:364-365).  For y = a W + b followed by a train-mode BatchNorm whose output gradient is dz:
@@ -23,14 +23,9 @@
 #include <stdlib.h>
 
 #include "colreduce.h"
+#include "mfma_x3.h"
 
 namespace cdrl {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));     // arithmetic on pairs compiles to v_pk_{add,mul,fma}_f32
 
 struct PwbArgs {
     View dz;                // gradient w.r.t. the BatchNorm output (columns optionally gathered through the shuffle map)
@@ -59,23 +54,6 @@ struct PwbArgs {
     int dbg;                // timing diagnostics (CDRL_DIAG=1 CDRL_DIAG_PWB=bits, wrong results): 1 no MFMA, 2 no LDS writes, 4 no stores, 8 no loads, 16 no partial-tile stores, 32 no W^T fragment loads
 };
 
-__device__ __forceinline__ void pwb_split3(float x, __bf16& h1, __bf16& h2, __bf16& h3) {
-    h1 = (__bf16)x;
-    const float r1 = x - (float)h1;
-    h2 = (__bf16)r1;
-    h3 = (__bf16)(r1 - (float)h2);
-}
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-// the same split on a pair, results as packed dwords {lo = first element, hi = second}: three packed conversions, two packed
-// subtractions, widening by shift / mask
-__device__ __forceinline__ void pwb_split3x2(f32x2 x, uint32_t& h1, uint32_t& h2, uint32_t& h3) {
-    auto widen = [](uint32_t w) -> f32x2 { return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; };
-    h1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2));
-    const f32x2 r1 = x - widen(h1);
-    h2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1, bf16x2));
-    h3 = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1 - widen(h2), bf16x2));
-}
 // {lo16(a), lo16(b)} and {hi16(a), hi16(b)} in one v_perm_b32 each: two rows of one column from two rows of a column pair
 __device__ __forceinline__ uint32_t pwb_lolo(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
 __device__ __forceinline__ uint32_t pwb_hihi(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
@@ -112,7 +90,6 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
     const int tiles_g = (a.Mg + BM - 1) / BM;
     const int t0 = (int)((int64_t)b * tiles_g / a.nbpg), t1 = (int)((int64_t)(b + 1) * tiles_g / a.nbpg);
     const int64_t Mtot = (int64_t)a.G * a.Mg;
-    const uint32_t OOR = 0x80000000u;
 
     if (a.fin_part) {
         // BatchNorm-backward finalize of this group's columns, by all eight waves before they part: wave w takes columns 16 w .. 16 w + 15,
@@ -191,8 +168,8 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
         }
         voy[0] = c0 < N ? (uint32_t)((4 * rg) * N + c0) * 4u : OOR;
         voy[1] = c0 + 2 < N ? (uint32_t)((4 * rg) * N + c0 + 2) * 4u : OOR;
-        const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(a.dz.p, 0, (int)(Mtot * a.dz.ld * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.y), 0, (int)(Mtot * N * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsD = buffer_rsrc(a.dz.p, (int)(Mtot * a.dz.ld * 4));
+        const __amdgpu_buffer_rsrc_t rsY = buffer_rsrc(a.y, (int)(Mtot * N * 4));
         const uint32_t rowD = (uint32_t)a.dz.ld * 4u, rowY = (uint32_t)N * 4u;
         const bool relu6 = a.act == ACT_RELU6;
         f32x2 rz[4][2], ry[4][2];                   // raw tile registers: dz, y of the micro-tile as column pairs
@@ -214,13 +191,13 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
                 } else {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsD, (vo[2 * h] + (uint32_t)j * rowD) | msk, mu * rowD, 0);
+                        const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rsD, (vo[2 * h] + (uint32_t)j * rowD) | msk, mu * rowD, 0);
                         rz[j][h] = __builtin_bit_cast(f32x2, v);
                     }
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsY, (voy[h] + (uint32_t)j * rowY) | msk, mu * rowY, 0);
+                    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rsY, (voy[h] + (uint32_t)j * rowY) | msk, mu * rowY, 0);
                     ry[j][h] = __builtin_bit_cast(f32x2, v);
                 }
             }
@@ -268,12 +245,12 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     ts[h] += vrow[h];
-                    pwb_split3x2(vrow[h], hw[0][j][h], hw[1][j][h], hw[2][j][h]);
+                    x3_split2(vrow[h], hw[0][j][h], hw[1][j][h], hw[2][j][h]);
                 }
                 if (!(a.dbg & 2)) {                 // row-major planes: the conversion results as they are
 #pragma unroll
                     for (int p = 0; p < 3; ++p)
-                        *reinterpret_cast<u32x2*>(&Rm[p * BM * LDR + (4 * rg + j) * LDR + c0]) = u32x2{hw[p][j][0], hw[p][j][1]};
+                        *reinterpret_cast<u32x2_t*>(&Rm[p * BM * LDR + (4 * rg + j) * LDR + c0]) = u32x2_t{hw[p][j][0], hw[p][j][1]};
                 }
             }
             cs[0] += (double)ts[0][0];
@@ -289,16 +266,16 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
             for (int p = 0; p < 3; ++p)
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    *reinterpret_cast<u32x2*>(&Dt[p * TPD + (c0 + 2 * h) * LDT + 4 * rg]) =
-                        u32x2{pwb_lolo(hw[p][0][h], hw[p][1][h]), pwb_lolo(hw[p][2][h], hw[p][3][h])};
-                    *reinterpret_cast<u32x2*>(&Dt[p * TPD + (c0 + 2 * h + 1) * LDT + 4 * rg]) =
-                        u32x2{pwb_hihi(hw[p][0][h], hw[p][1][h]), pwb_hihi(hw[p][2][h], hw[p][3][h])};
+                    *reinterpret_cast<u32x2_t*>(&Dt[p * TPD + (c0 + 2 * h) * LDT + 4 * rg]) =
+                        u32x2_t{pwb_lolo(hw[p][0][h], hw[p][1][h]), pwb_lolo(hw[p][2][h], hw[p][3][h])};
+                    *reinterpret_cast<u32x2_t*>(&Dt[p * TPD + (c0 + 2 * h + 1) * LDT + 4 * rg]) =
+                        u32x2_t{pwb_hihi(hw[p][0][h], hw[p][1][h]), pwb_hihi(hw[p][2][h], hw[p][3][h])};
                 }
         };
         // output tile through a buffer descriptor: the row offset of register r is wave-uniform (SGPR soffset), the lane's part
         // (its 4 lk rows + its column) one constant voffset -- no 64-bit address per register (the flat form kept 16 of them live
         // across the tile loop and spilled); lanes beyond K and rows beyond the group point out of range: store dropped, load 0
-        const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(a.da.p, 0, (int)(Mtot * a.da.ld * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsC = buffer_rsrc(a.da.p, (int)(Mtot * a.da.ld * 4));
         const uint32_t rowC = (uint32_t)a.da.ld * 4u;
         const int ncol = dwc * 32 + lrow;
         const uint32_t voC = ncol < K ? (uint32_t)((4 * lk) * a.da.ld + a.da.coff + ncol) * 4u : OOR;
@@ -313,7 +290,7 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
             if (ACC) {          // old values of the output tile, fetched before the MFMA chain (gemm_pw.hip ACC_PF)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int rr = (r & 3) + 8 * (r >> 2);
+                    const int rr = acc_row(r);
                     cold[ACC ? r : 0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsC, voC | (rr < left ? 0u : OOR), (mu + (uint32_t)rr) * rowC, 0));
                 }
             }
@@ -324,17 +301,12 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
                 const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&Rm[0 * BM * LDR + ao + 16 * s]);
                 const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(&Rm[1 * BM * LDR + ao + 16 * s]);
                 const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(&Rm[2 * BM * LDR + ao + 16 * s]);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, breg[0][s], acc, 0, 0, 0);       // smallest terms first
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, breg[2][s], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, breg[1][s], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, breg[0][s], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, breg[1][s], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, breg[0][s], acc, 0, 0, 0);
+                acc = x3_mfma(a1, a2, a3, breg[0][s], breg[1][s], breg[2][s], acc);
             }
             if (!(a.dbg & 4))
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int rr = (r & 3) + 8 * (r >> 2);
+                const int rr = acc_row(r);
                 const float v = ACC ? acc[r] + cold[ACC ? r : 0] : acc[r];
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsC, voC | (rr < left ? 0u : OOR), (mu + (uint32_t)rr) * rowC, 0);
             }
@@ -379,7 +351,7 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
         uint32_t vo[2];
         vo[0] = c0 < K ? (uint32_t)((4 * rg) * a.a.ld + a.a.coff + c0) * 4u : OOR;
         vo[1] = c0 + 2 < K ? (uint32_t)((4 * rg) * a.a.ld + a.a.coff + c0 + 2) * 4u : OOR;
-        const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(a.a.p, 0, (int)(Mtot * a.a.ld * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsA = buffer_rsrc(a.a.p, (int)(Mtot * a.a.ld * 4));
         const uint32_t rowA = (uint32_t)a.a.ld * 4u;
         f32x2 rz[4][2];
         auto load_row = [&](int t, int j) {
@@ -391,7 +363,7 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
                 const uint32_t msk = j < left ? 0u : OOR;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsA, (vo[h] + (uint32_t)j * rowA) | msk, mu * rowA, 0);
+                    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rsA, (vo[h] + (uint32_t)j * rowA) | msk, mu * rowA, 0);
                     rz[j][h] = __builtin_bit_cast(f32x2, v);
                 }
             }
@@ -415,7 +387,7 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
                 }
                 if (more) load_row(t + 1, j);
 #pragma unroll
-                for (int h = 0; h < 2; ++h) pwb_split3x2(vrow[h], hw[0][j][h], hw[1][j][h], hw[2][j][h]);
+                for (int h = 0; h < 2; ++h) x3_split2(vrow[h], hw[0][j][h], hw[1][j][h], hw[2][j][h]);
             }
             if (a.dbg & 2) {
                 if (hw[0][0][0] == 123u && hw[2][3][1] == 321u) At[0] = (__bf16)1.0f;
@@ -426,10 +398,10 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
                 for (int p = 0; p < 3; ++p)
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        *reinterpret_cast<u32x2*>(&At[p * TPA + (c0 + 2 * h) * LDT + 4 * rg]) =
-                            u32x2{pwb_lolo(hw[p][0][h], hw[p][1][h]), pwb_lolo(hw[p][2][h], hw[p][3][h])};
-                        *reinterpret_cast<u32x2*>(&At[p * TPA + (c0 + 2 * h + 1) * LDT + 4 * rg]) =
-                            u32x2{pwb_hihi(hw[p][0][h], hw[p][1][h]), pwb_hihi(hw[p][2][h], hw[p][3][h])};
+                        *reinterpret_cast<u32x2_t*>(&At[p * TPA + (c0 + 2 * h) * LDT + 4 * rg]) =
+                            u32x2_t{pwb_lolo(hw[p][0][h], hw[p][1][h]), pwb_lolo(hw[p][2][h], hw[p][3][h])};
+                        *reinterpret_cast<u32x2_t*>(&At[p * TPA + (c0 + 2 * h + 1) * LDT + 4 * rg]) =
+                            u32x2_t{pwb_hihi(hw[p][0][h], hw[p][1][h]), pwb_hihi(hw[p][2][h], hw[p][3][h])};
                     }
             }
         };
@@ -453,12 +425,7 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
                     const bf16x8 d1 = *reinterpret_cast<const bf16x8*>(&Dt[0 * TPD + bo]);
                     const bf16x8 d2 = *reinterpret_cast<const bf16x8*>(&Dt[1 * TPD + bo]);
                     const bf16x8 d3 = *reinterpret_cast<const bf16x8*>(&Dt[2 * TPD + bo]);
-                    qacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, d1, qacc[j], 0, 0, 0);
-                    qacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, d3, qacc[j], 0, 0, 0);
-                    qacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, d2, qacc[j], 0, 0, 0);
-                    qacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, d1, qacc[j], 0, 0, 0);
-                    qacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, d2, qacc[j], 0, 0, 0);
-                    qacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, d1, qacc[j], 0, 0, 0);
+                    qacc[j] = x3_mfma(a1, a2, a3, d1, d2, d3, qacc[j]);
                 }
             }
         };
@@ -480,7 +447,7 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
             const int n = (qnt0 + j) * 32 + lrow;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int k = qkt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int k = acc_row(qkt * 32, r, lk);
                 qp[k * NP + n] = qacc[j][r];
             }
         }
@@ -526,9 +493,6 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
     const int tiles_g = (a.Mg + BM - 1) / BM;
     const int t0 = (int)((int64_t)b * tiles_g / a.nbpg), t1 = (int)((int64_t)(b + 1) * tiles_g / a.nbpg);
     const int64_t Mtot = (int64_t)a.G * a.Mg;
-    const uint32_t OOR = 0x80000000u;
-    auto widen = [](uint32_t w) -> f32x2 { return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; };
-    auto pack = [](f32x2 v) -> uint32_t { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2)); };
 
     if (role == 0) {
         const int dwr = wave % DA_WR, dwc = wave / DA_WR;
@@ -570,8 +534,8 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
         }
         voy[0] = cok[0] ? (uint32_t)((4 * rg) * N + c0) * 2u : OOR;
         voy[1] = cok[2] ? (uint32_t)((4 * rg) * N + c0 + 2) * 2u : OOR;
-        const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc(a.dz.p, 0, (int)(Mtot * a.dz.ld * 2), 0x00020000);
-        const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.y), 0, (int)(Mtot * N * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsD = buffer_rsrc(a.dz.p, (int)(Mtot * a.dz.ld * 2));
+        const __amdgpu_buffer_rsrc_t rsY = buffer_rsrc(a.y, (int)(Mtot * N * 2));
         const uint32_t rowD = (uint32_t)a.dz.ld * 2u, rowY = (uint32_t)N * 2u;
         const bool relu6 = a.act == ACT_RELU6;
         uint32_t rz[4][2], ry[4][2];                // raw words (widened where they are used, not where they are loaded)
@@ -611,20 +575,20 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
                 const bool rok = j < left;
                 f32x2 dz2[2];
                 if (SHUF) {     // loaded (c0, c0 + 2), (c0 + 1, c0 + 3) -> pairs (c0, c0 + 1), (c0 + 2, c0 + 3)
-                    const f32x2 pa = widen(hi_half[0] ? rz[j][0] >> 16 : rz[j][0]), pb = widen(hi_half[1] ? rz[j][1] >> 16 : rz[j][1]);
+                    const f32x2 pa = bf16x2_widen(hi_half[0] ? rz[j][0] >> 16 : rz[j][0]), pb = bf16x2_widen(hi_half[1] ? rz[j][1] >> 16 : rz[j][1]);
                     dz2[0] = f32x2{pa[0], pb[0]};
                     dz2[1] = f32x2{pa[1], pb[1]};
                     if (!cok[2]) dz2[1][0] = 0.0f;      // (channel counts are even: c0 + 2 and c0 + 3 are valid together; the source
                     if (!cok[3]) dz2[1][1] = 0.0f;      //  words' second halves belong to other channels there)
                 } else {
-                    dz2[0] = widen(rz[j][0]);
-                    dz2[1] = widen(rz[j][1]);
+                    dz2[0] = bf16x2_widen(rz[j][0]);
+                    dz2[1] = bf16x2_widen(rz[j][1]);
                 }
                 f32x2 vrow[2];
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     f32x2 d = dz2[h];
-                    const f32x2 yv = widen(ry[j][h]);
+                    const f32x2 yv = bf16x2_widen(ry[j][h]);
                     if (relu6) {
                         const f32x2 z = __builtin_elementwise_fma(csc[h], yv, csh[h]);
                         if (!relu6_open(z[0])) d[0] = 0.0f;
@@ -639,9 +603,9 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     ts[h] += vrow[h];
-                    hw[j][h] = pack(vrow[h]);
+                    hw[j][h] = bf16x2_pack(vrow[h]);
                 }
-                *reinterpret_cast<u32x2*>(&Rm[(4 * rg + j) * LDR + c0]) = u32x2{hw[j][0], hw[j][1]};
+                *reinterpret_cast<u32x2_t*>(&Rm[(4 * rg + j) * LDR + c0]) = u32x2_t{hw[j][0], hw[j][1]};
             }
             cs[0] += (double)ts[0][0];
             cs[1] += (double)ts[0][1];
@@ -649,14 +613,14 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
             cs[3] += (double)ts[1][1];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                *reinterpret_cast<u32x2*>(&Dt[(c0 + 2 * h) * LDT + 4 * rg]) = u32x2{pwb_lolo(hw[0][h], hw[1][h]), pwb_lolo(hw[2][h], hw[3][h])};
-                *reinterpret_cast<u32x2*>(&Dt[(c0 + 2 * h + 1) * LDT + 4 * rg]) = u32x2{pwb_hihi(hw[0][h], hw[1][h]), pwb_hihi(hw[2][h], hw[3][h])};
+                *reinterpret_cast<u32x2_t*>(&Dt[(c0 + 2 * h) * LDT + 4 * rg]) = u32x2_t{pwb_lolo(hw[0][h], hw[1][h]), pwb_lolo(hw[2][h], hw[3][h])};
+                *reinterpret_cast<u32x2_t*>(&Dt[(c0 + 2 * h + 1) * LDT + 4 * rg]) = u32x2_t{pwb_hihi(hw[0][h], hw[1][h]), pwb_hihi(hw[2][h], hw[3][h])};
             }
         };
         // output tile as bf16: a lane owns ONE column (16 rows in 16 registers); lanes (2i, 2i + 1) own adjacent columns -- the even
         // lane takes the even registers of both columns, the odd lane the odd ones, the partner's half arrives by DPP: 8 four-byte
         // stores per lane instead of 16 two-byte ones (gemm_pw.hip pair_load16).  Row offsets of register pair q are wave-uniform.
-        const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(a.da.p, 0, (int)(Mtot * a.da.ld * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsC = buffer_rsrc(a.da.p, (int)(Mtot * a.da.ld * 2));
         const uint32_t rowC = (uint32_t)a.da.ld * 2u;
         const int ncol = dwc * 32 + lrow;
         const bool odd = (lane & 1) != 0;
@@ -674,7 +638,7 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
             if (ACC) {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
-                    const int rr = ((2 * q) & 3) + 8 * ((2 * q) >> 2);
+                    const int rr = acc_row(2 * q);
                     cold[ACC ? q : 0] = __builtin_amdgcn_raw_buffer_load_b32(rsC, voC | (rr < left ? 0u : OOR), (mu + (uint32_t)rr) * rowC, 0);
                 }
             }
@@ -694,8 +658,8 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
                 const int xo = ncol * LDT + dwr * 32 + 4 * lk;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const u32x2 xw = *reinterpret_cast<const u32x2*>(&At[xo + 8 * i]);
-                    const f32x2 x01 = widen(xw[0]), x23 = widen(xw[1]);
+                    const u32x2_t xw = *reinterpret_cast<const u32x2_t*>(&At[xo + 8 * i]);
+                    const f32x2 x01 = bf16x2_widen(xw[0]), x23 = bf16x2_widen(xw[1]);
                     sda += ((double)acc[4 * i] + (double)acc[4 * i + 1]) + ((double)acc[4 * i + 2] + (double)acc[4 * i + 3]);
                     sdx += ((double)acc[4 * i] * (double)x01[0] + (double)acc[4 * i + 1] * (double)x01[1]) +
                            ((double)acc[4 * i + 2] * (double)x23[0] + (double)acc[4 * i + 3] * (double)x23[1]);
@@ -710,7 +674,7 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
                     lo += bf_lo(cold[ACC ? q : 0]);
                     hi += bf_hi(cold[ACC ? q : 0]);
                 }
-                const int rr = ((2 * q) & 3) + 8 * ((2 * q) >> 2);
+                const int rr = acc_row(2 * q);
                 __builtin_amdgcn_raw_buffer_store_b32(bf_pack(lo, hi), rsC, voC | (rr < left ? 0u : OOR), (mu + (uint32_t)rr) * rowC, 0);
             }
         };
@@ -766,7 +730,7 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
         uint32_t vo[2];
         vo[0] = c0 < K ? (uint32_t)((4 * rg) * a.a.ld + a.a.coff + c0) * 2u : OOR;
         vo[1] = c0 + 2 < K ? (uint32_t)((4 * rg) * a.a.ld + a.a.coff + c0 + 2) * 2u : OOR;
-        const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(a.a.p, 0, (int)(Mtot * a.a.ld * 2), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsA = buffer_rsrc(a.a.p, (int)(Mtot * a.a.ld * 2));
         const uint32_t rowA = (uint32_t)a.a.ld * 2u;
         uint32_t rz[4][2];
         auto load_row = [&](int t, int j) {
@@ -787,9 +751,9 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
                 if (ANORM) {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        f32x2 v = (widen(rz[j][h]) - cmean[h]) * cinv[h];       // padded columns: loaded 0, mean 0, invstd 0 -> 0
+                        f32x2 v = (bf16x2_widen(rz[j][h]) - cmean[h]) * cinv[h];       // padded columns: loaded 0, mean 0, invstd 0 -> 0
                         if (!rok) v = f32x2{0.0f, 0.0f};
-                        hw[j][h] = pack(v);
+                        hw[j][h] = bf16x2_pack(v);
                     }
                 } else {
                     hw[j][0] = rz[j][0];            // plain input: the stored bf16 values ARE the operand
@@ -799,8 +763,8 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                *reinterpret_cast<u32x2*>(&At[(c0 + 2 * h) * LDT + 4 * rg]) = u32x2{pwb_lolo(hw[0][h], hw[1][h]), pwb_lolo(hw[2][h], hw[3][h])};
-                *reinterpret_cast<u32x2*>(&At[(c0 + 2 * h + 1) * LDT + 4 * rg]) = u32x2{pwb_hihi(hw[0][h], hw[1][h]), pwb_hihi(hw[2][h], hw[3][h])};
+                *reinterpret_cast<u32x2_t*>(&At[(c0 + 2 * h) * LDT + 4 * rg]) = u32x2_t{pwb_lolo(hw[0][h], hw[1][h]), pwb_lolo(hw[2][h], hw[3][h])};
+                *reinterpret_cast<u32x2_t*>(&At[(c0 + 2 * h + 1) * LDT + 4 * rg]) = u32x2_t{pwb_hihi(hw[0][h], hw[1][h]), pwb_hihi(hw[2][h], hw[3][h])};
             }
         };
         f32x16 qacc[NTW];
@@ -837,7 +801,7 @@ __global__ void __launch_bounds__(512, 4) pwb16_kernel(PwbArgs a) {
             const int n = (qnt0 + j) * 32 + lrow;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int k = qkt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int k = acc_row(qkt * 32, r, lk);
                 qp[k * NP + n] = qacc[j][r];
             }
         }

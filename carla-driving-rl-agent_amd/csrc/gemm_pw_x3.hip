@@ -2,13 +2,9 @@
 //
 // Reference: core/architectures.py:130,140 (Conv2D(k=1)).  The float32 MFMA (v_mfma_f32_32x32x2_f32) runs at 1/16 of the bf16
 // rate, and the persistent float32 kernel of gemm_pw.hip is measurably matrix-bound (MfmaUtil 0.36 at K = N = 116,
-// profiles/r02_pmc_mfma.json).  A float32 number is the exact sum of three bf16 numbers (3 x 8 significand bits):
-//     a = a1 + a2 + a3,   b = b1 + b2 + b3
-// and  a b = a1 b1 + (a1 b2 + a2 b1) + (a1 b3 + a2 b2 + a3 b1) + O(2^-24 |a b|):  six bf16 products accumulated in float32 carry
-// the product to float32 accuracy (the dropped terms are below half an ulp of the product).  Six K=16 steps of 32 cycles replace
-// eight K=2 steps of 64 cycles: 2.7x less matrix-pipe time for the same float32 inputs, outputs and HBM traffic.
-// The result is NOT bit-identical to a k-ordered fmaf chain (it is at least as accurate: every product is exact to 2^-24 and the
-// accumulation is float32 either way); parity is asserted against the float64 reference at 1e-5 (tests/test_gpu_ops.py).
+// profiles/r02_pmc_mfma.json).  Each operand is split exactly into three bf16 numbers and six bf16 products per K = 16 step carry
+// the product to float32 accuracy (mfma_x3.h has the split, the step and the argument): 2.7x less matrix-pipe time for the same
+// float32 inputs, outputs and HBM traffic.  Parity is asserted against the float64 reference at 1e-5 (tests/test_gpu_ops.py).
 // Same skeleton as gemm_pw.hip: persistent workgroups over the row tiles of one BatchNorm group, W (three bf16 planes, packed
 // once per weight version) in registers, A split on its way into LDS, BN-apply prologue, statistics epilogue.
 #include <stdlib.h>
@@ -17,10 +13,6 @@
 #include "pack_bodies.h"
 
 namespace cdrl {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 struct PwX3Args {
     View A;
@@ -32,11 +24,28 @@ struct PwX3Args {
     int N, K, G, Mg, nbpg;
 };
 
-__device__ __forceinline__ void split3(float x, __bf16& h1, __bf16& h2, __bf16& h3) {
-    h1 = (__bf16)x;
-    const float r1 = x - (float)h1;             // exact
-    h2 = (__bf16)r1;
-    h3 = (__bf16)(r1 - (float)h2);              // exact difference, final rounding below 2^-24 |x|
+// the three packed planes of one chunk (4 columns = 2 pairs) -> LDS row r (LDA elements per row), columns k4 .. k4 + 3: one 8-byte
+// store per plane
+template <int LDA, int SZ>
+__device__ __forceinline__ void pw_x3_store_planes(__bf16 (&As)[3][SZ], int r, int k4, const uint32_t (&hw)[3][2]) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2_t*>(&As[p][r * LDA + k4]) = u32x2_t{hw[p][0], hw[p][1]};
+}
+
+// pair h (columns k4 + 2 h, + 1) of a loaded chunk of A, BatchNorm applied (PRO), ready to be split
+template <bool PRO, int KP>
+__device__ __forceinline__ f32x2 pw_x3_chunk_pair(u32x4_t ra, int h, int k4, int K, const float (&pc)[2][KP]) {
+    f32x2 x = f32x2{__uint_as_float(ra[2 * h]), __uint_as_float(ra[2 * h + 1])};
+    // columns beyond K inside the last 4-wide chunk (K = 58: 58, 59) are whatever the neighbouring channels of a wider
+    // tensor hold: a non-finite value there would survive the zero weights (0 * NaN); zeroed here
+    if (k4 + 2 * h >= K) x[0] = 0.0f;
+    if (k4 + 2 * h + 1 >= K) x[1] = 0.0f;
+    if (PRO) {
+        // (columns beyond K carry scale 0 / shift 0 in pc)
+        const f32x2 sc = f32x2{pc[0][k4 + 2 * h], pc[0][k4 + 2 * h + 1]}, sh = f32x2{pc[1][k4 + 2 * h], pc[1][k4 + 2 * h + 1]};
+        x = __builtin_elementwise_fma(sc, x, sh);
+    }
+    return x;
 }
 
 template <int KP, int NT, bool PRO, bool EPI>
@@ -73,10 +82,8 @@ __global__ void __launch_bounds__(256, 2) pw_x3_kernel(PwX3Args a) {
         __syncthreads();
     }
     double s1 = 0.0, s2 = 0.0;
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-    const uint32_t OOR = 0x80000000u;
     const int64_t Mtot = (int64_t)a.G * a.Mg;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(a.A.p, 0, (int)(Mtot * a.A.ld * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = buffer_rsrc(a.A.p, (int)(Mtot * a.A.ld * 4));
     u32x4_t ra[NCH];
     auto load_tile = [&](int t) {
         const int64_t m0 = mbeg + (int64_t)t * BM;
@@ -89,35 +96,13 @@ __global__ void __launch_bounds__(256, 2) pw_x3_kernel(PwX3Args a) {
         }
     };
     auto store_tile = [&]() {
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-        typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-        // pairs: the arithmetic compiles to v_pk_{fma,add}_f32, the three conversions to one v_cvt_pk_bf16_f32 each, and the
-        // conversion results ARE the packed LDS words (no per-element repacking): 19.9 -> see DESIGN.md for the isolated timing
-        auto widen = [](uint32_t w) -> f32x2 { return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; };
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const int c = tid + 256 * i, r = c / CPR, k4 = 4 * (c % CPR);
             uint32_t hw[3][2];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x2 x = f32x2{__uint_as_float(ra[i][2 * h]), __uint_as_float(ra[i][2 * h + 1])};
-                // columns beyond K inside the last 4-wide chunk (K = 58: 58, 59) are whatever the neighbouring channels of a wider
-                // tensor hold: a non-finite value there would survive the zero weights (0 * NaN); zeroed here
-                if (k4 + 2 * h >= K) x[0] = 0.0f;
-                if (k4 + 2 * h + 1 >= K) x[1] = 0.0f;
-                if (PRO) {
-                    // (columns beyond K carry scale 0 / shift 0 in pc)
-                    const f32x2 sc = f32x2{pc[0][k4 + 2 * h], pc[0][k4 + 2 * h + 1]}, sh = f32x2{pc[1][k4 + 2 * h], pc[1][k4 + 2 * h + 1]};
-                    x = __builtin_elementwise_fma(sc, x, sh);
-                }
-                hw[0][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2));
-                const f32x2 r1 = x - widen(hw[0][h]);             // exact
-                hw[1][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1, bf16x2));
-                hw[2][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1 - widen(hw[1][h]), bf16x2));
-            }
-#pragma unroll
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2_t*>(&As[p][r * LDA + k4]) = u32x2_t{hw[p][0], hw[p][1]};
+            for (int h = 0; h < 2; ++h) x3_split2(pw_x3_chunk_pair<PRO>(ra[i], h, k4, K, pc), hw[0][h], hw[1][h], hw[2][h]);
+            pw_x3_store_planes<LDA>(As, r, k4, hw);
         }
     };
     auto compute_tile = [&](int t) {
@@ -130,19 +115,13 @@ __global__ void __launch_bounds__(256, 2) pw_x3_kernel(PwX3Args a) {
             const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&As[0][ao + 16 * s]);
             const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(&As[1][ao + 16 * s]);
             const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(&As[2][ao + 16 * s]);
-            // smallest terms first
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, breg[0][s], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, breg[2][s], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, breg[1][s], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, breg[0][s], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, breg[1][s], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, breg[0][s], acc, 0, 0, 0);
+            acc = x3_mfma(a1, a2, a3, breg[0][s], breg[1][s], breg[2][s], acc);
         }
         if (n >= N) return;
         const int64_t m0 = mbeg + (int64_t)t * BM + wr * 32;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int64_t m = acc_row(m0, r, lk);
             if (m < mend) {
                 const float v = acc[r] + bv;
                 if (EPI) {
@@ -189,6 +168,18 @@ __global__ void __launch_bounds__(256, 2) pw_x3_kernel(PwX3Args a) {
 // workgroup takes ONE 32-row tile and one block of 128 columns: W^(column block) as three bf16 planes in registers (16 K steps x 3 planes
 // x 4 VGPRs = 192), the A tile split into three planes in LDS (50 KB), 96 bf16 MFMAs of 32 cycles per wave, two workgroups per CU so
 // that one loads / stores while the other multiplies.  Grid = (groups x tiles, column blocks); statistics: one partial row per tile.
+//
+// The weight stream of the two wide kernels (this one and its backward-data twin below).  A workgroup uses every weight fragment ONCE
+// (one tile), so holding all 3 x 16 of them (192 VGPRs) buys nothing but the early issue of their loads -- and spilled next to the
+// prologue.  A ring of X3_PF K-steps (3 planes each) is requested ahead instead; pw_x3_wload fetches the three fragments of K-step s
+// (wp: the lane's fragment of step 0, plane 0 of its column block).
+constexpr int X3_PF = 6;
+template <int KS>
+__device__ __forceinline__ void pw_x3_wload(const __bf16* wp, int s, bf16x8* dst) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(wp + (int64_t)(p * KS + s) * 2 * 128 * 8);
+}
+
 template <bool PRO, bool EPI>
 __global__ void __launch_bounds__(256, 2) pw_x3_wide_kernel(PwX3Args a) {
     constexpr int KP = 256, BM = 32, KS = KP / 16, LDA = KP + 8, CPR = KP / 4, NCH = BM * CPR / 256;
@@ -201,13 +192,8 @@ __global__ void __launch_bounds__(256, 2) pw_x3_wide_kernel(PwX3Args a) {
     const int64_t mbeg = (int64_t)g * a.Mg, mend = mbeg + a.Mg;
     const int64_t m0 = mbeg + (int64_t)t * BM;
     const int nl = wave * 32 + lrow, n = blockIdx.y * 128 + nl;
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-    const uint32_t OOR = 0x80000000u;
     const int64_t Mtot = (int64_t)a.G * a.Mg;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(a.A.p, 0, (int)(Mtot * a.A.ld * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = buffer_rsrc(a.A.p, (int)(Mtot * a.A.ld * 4));
     // the A tile first (HBM / Infinity Cache), the weight fragments (L2) behind it: both in flight before anything is consumed
     u32x4_t ra[NCH];
 #pragma unroll
@@ -224,42 +210,19 @@ __global__ void __launch_bounds__(256, 2) pw_x3_wide_kernel(PwX3Args a) {
             pc[1][k] = k < K ? a.pro_stats[3 * GK + g * K + k] : 0.0f;
         }
     }
-    // A workgroup uses every weight fragment ONCE (one tile), so holding all 3 x 16 of them (192 VGPRs) buys nothing but the early issue
-    // of their loads -- and spilled next to the prologue.  A ring of PF K-steps (3 planes each) is requested ahead instead.
     const __bf16* wp = a.Wp + (int64_t)blockIdx.y * 3 * KS * 2 * 128 * 8 + ((int64_t)lk * 128 + nl) * 8;
-    constexpr int PF = 6;
-    bf16x8 ring[PF][3];
-    auto wload = [&](int s, bf16x8* dst) {
+    bf16x8 ring[X3_PF][3];
 #pragma unroll
-        for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(wp + (int64_t)(p * KS + s) * 2 * 128 * 8);
-    };
-#pragma unroll
-    for (int s = 0; s < PF; ++s) wload(s, ring[s]);
+    for (int s = 0; s < X3_PF; ++s) pw_x3_wload<KS>(wp, s, ring[s]);
     const float bv = (a.bias && n < N) ? a.bias[n] : 0.0f;
     if (PRO) __syncthreads();
-    {
-        auto widen = [](uint32_t w) -> f32x2 { return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; };
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            const int c = tid + 256 * i, r = c / CPR, k4 = 4 * (c % CPR);
-            uint32_t hw[3][2];
+    for (int i = 0; i < NCH; ++i) {
+        const int c = tid + 256 * i, r = c / CPR, k4 = 4 * (c % CPR);
+        uint32_t hw[3][2];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x2 x = f32x2{__uint_as_float(ra[i][2 * h]), __uint_as_float(ra[i][2 * h + 1])};
-                if (k4 + 2 * h >= K) x[0] = 0.0f;          // (columns beyond K inside the last chunk: see pw_x3_kernel)
-                if (k4 + 2 * h + 1 >= K) x[1] = 0.0f;
-                if (PRO) {
-                    const f32x2 sc = f32x2{pc[0][k4 + 2 * h], pc[0][k4 + 2 * h + 1]}, sh = f32x2{pc[1][k4 + 2 * h], pc[1][k4 + 2 * h + 1]};
-                    x = __builtin_elementwise_fma(sc, x, sh);
-                }
-                hw[0][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2));
-                const f32x2 r1 = x - widen(hw[0][h]);
-                hw[1][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1, bf16x2));
-                hw[2][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1 - widen(hw[1][h]), bf16x2));
-            }
-#pragma unroll
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2_t*>(&As[p][r * LDA + k4]) = u32x2_t{hw[p][0], hw[p][1]};
-        }
+        for (int h = 0; h < 2; ++h) x3_split2(pw_x3_chunk_pair<PRO>(ra[i], h, k4, K, pc), hw[0][h], hw[1][h], hw[2][h]);
+        pw_x3_store_planes<LDA>(As, r, k4, hw);
     }
     __syncthreads();
     f32x16 acc;
@@ -271,20 +234,15 @@ __global__ void __launch_bounds__(256, 2) pw_x3_wide_kernel(PwX3Args a) {
         const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&As[0][ao + 16 * s]);
         const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(&As[1][ao + 16 * s]);
         const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(&As[2][ao + 16 * s]);
-        const bf16x8 b1 = ring[s % PF][0], b2 = ring[s % PF][1], b3 = ring[s % PF][2];
-        if (s + PF < KS) wload(s + PF, ring[s % PF]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);       // smallest terms first
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
+        const bf16x8 b1 = ring[s % X3_PF][0], b2 = ring[s % X3_PF][1], b3 = ring[s % X3_PF][2];
+        if (s + X3_PF < KS) pw_x3_wload<KS>(wp, s + X3_PF, ring[s % X3_PF]);
+        acc = x3_mfma(a1, a2, a3, b1, b2, b3, acc);
     }
     if (n >= N) return;
     double s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+        const int64_t m = acc_row(m0, r, lk);
         if (m < mend) {
             const float v = acc[r] + bv;
             if (EPI) {
@@ -339,14 +297,9 @@ __global__ void __launch_bounds__(256, 2) pw_x3_wide_bwd_kernel(PwX3BwdArgs a) {
     const int64_t mbeg = (int64_t)g * a.Mg, mend = mbeg + a.Mg;
     const int64_t m0 = mbeg + (int64_t)t * BM;
     const int nl = wave * 32 + lrow, n = blockIdx.y * 128 + nl;
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const uint32_t OOR = 0x80000000u;
     const int64_t Mtot = (int64_t)a.G * a.Mg;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(a.A.p, 0, (int)(Mtot * a.A.ld * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.a_y), 0, (int)(Mtot * K * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = buffer_rsrc(a.A.p, (int)(Mtot * a.A.ld * 4));
+    const __amdgpu_buffer_rsrc_t rsY = buffer_rsrc(a.a_y, (int)(Mtot * K * 4));
     // a thread's chunks: rows r0 + 4 i, ALWAYS the same four columns k4 .. k4 + 3 (256 % CPR == 0)
     const int k4 = 4 * (tid % CPR), r0 = tid / CPR;
     const bool kon = k4 < K;                    // (K % 4 == 0: a chunk is valid or not as a whole)
@@ -385,7 +338,6 @@ __global__ void __launch_bounds__(256, 2) pw_x3_wide_bwd_kernel(PwX3BwdArgs a) {
     __syncthreads();
     double cs[4] = {0.0, 0.0, 0.0, 0.0};
     {
-        auto widen = [](uint32_t w) -> f32x2 { return f32x2{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; };
         const bool relu6 = a.a_act == ACT_RELU6;
         f32x2 cmean[2], cinv[2], csc[2], csh[2], ck1[2], ck2[2], ck3[2];
 #pragma unroll
@@ -417,35 +369,25 @@ __global__ void __launch_bounds__(256, 2) pw_x3_wide_bwd_kernel(PwX3BwdArgs a) {
                 if (!rok) v = f32x2{0.0f, 0.0f};
                 cs[2 * h] += (double)v[0];
                 cs[2 * h + 1] += (double)v[1];
-                hw[0][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-                const f32x2 r1 = v - widen(hw[0][h]);
-                hw[1][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1, bf16x2));
-                hw[2][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r1 - widen(hw[1][h]), bf16x2));
+                x3_split2(v, hw[0][h], hw[1][h], hw[2][h]);
             }
-#pragma unroll
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2_t*>(&As[p][r * LDA + k4]) = u32x2_t{hw[p][0], hw[p][1]};
+            pw_x3_store_planes<LDA>(As, r, k4, hw);
         }
     }
     // weight fragments + the epilogue's operands: requested now, consumed behind the barrier
     const __bf16* wp = a.Wp + (int64_t)blockIdx.y * 3 * KS * 2 * 128 * 8 + ((int64_t)lk * 128 + nl) * 8;
-    constexpr int PF = 6;                       // ring of K-steps requested ahead (see pw_x3_wide_kernel)
-    bf16x8 ring[PF][3];
-    auto wload = [&](int s, bf16x8* dst) {
+    bf16x8 ring[X3_PF][3];                      // ring of K-steps requested ahead (see pw_x3_wide_kernel)
 #pragma unroll
-        for (int p = 0; p < 3; ++p) dst[p] = *reinterpret_cast<const bf16x8*>(wp + (int64_t)(p * KS + s) * 2 * 128 * 8);
-    };
-#pragma unroll
-    for (int s = 0; s < PF; ++s) wload(s, ring[s]);
+    for (int s = 0; s < X3_PF; ++s) pw_x3_wload<KS>(wp, s, ring[s]);
     const bool non = n < N;
     float ext[(EPI || ACC) ? 16 : 1];           // EPI: raw input of the BatchNorm the output feeds; ACC: old output values
     if (EPI || ACC) {
-        const __amdgpu_buffer_rsrc_t rsE = EPI ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.ey), 0, (int)(Mtot * N * 4), 0x00020000)
-                                               : __builtin_amdgcn_make_buffer_rsrc(a.C.p, 0, (int)(Mtot * a.C.ld * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsE = EPI ? buffer_rsrc(a.ey, (int)(Mtot * N * 4)) : buffer_rsrc(a.C.p, (int)(Mtot * a.C.ld * 4));
         const uint32_t rowE = EPI ? (uint32_t)N * 4u : (uint32_t)a.C.ld * 4u;
         const uint32_t voE = non ? (uint32_t)((EPI ? 0 : a.C.coff) + n) * 4u : OOR;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int64_t m = acc_row(m0, r, lk);
             ext[(EPI || ACC) ? r : 0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsE, (voE + (uint32_t)m * rowE) | (m < mend ? 0u : OOR) | (voE & OOR), 0, 0));
         }
     }
@@ -464,20 +406,15 @@ __global__ void __launch_bounds__(256, 2) pw_x3_wide_bwd_kernel(PwX3BwdArgs a) {
         const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&As[0][ao + 16 * s]);
         const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(&As[1][ao + 16 * s]);
         const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(&As[2][ao + 16 * s]);
-        const bf16x8 b1 = ring[s % PF][0], b2 = ring[s % PF][1], b3 = ring[s % PF][2];
-        if (s + PF < KS) wload(s + PF, ring[s % PF]);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);       // smallest terms first
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b3, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b1, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b2, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);
+        const bf16x8 b1 = ring[s % X3_PF][0], b2 = ring[s % X3_PF][1], b3 = ring[s % X3_PF][2];
+        if (s + X3_PF < KS) pw_x3_wload<KS>(wp, s + X3_PF, ring[s % X3_PF]);
+        acc = x3_mfma(a1, a2, a3, b1, b2, b3, acc);
     }
     double s1 = 0.0, s2 = 0.0;
     if (non) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int64_t m = acc_row(m0, r, lk);
             if (m < mend) {
                 float v = acc[r];
                 if (EPI) {

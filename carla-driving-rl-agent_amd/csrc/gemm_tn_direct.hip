@@ -26,11 +26,10 @@
 #include <algorithm>
 
 #include "colreduce.h"
+#include "mfma_x3.h"
 
 namespace cdrl {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct TnDirectArgs {
     View A, D;
@@ -128,13 +127,9 @@ __global__ void __launch_bounds__(512) tn_direct_kernel(TnDirectArgs a) {
     // Loads go through buffer descriptors: the row offset of a batch is wave-uniform (SGPR soffset), the lane's column
     // offset is a fixed 32-bit voffset, masked lanes point out of range (the bounds check returns 0) -- no 64-bit address
     // arithmetic and no per-load select in the steady state, which is what lets U = 8 / 16 fit in registers.
-    const uint32_t OOR = 0x80000000u;           // host checks that every tensor is < 2 GB
-    const __amdgpu_buffer_rsrc_t rA =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A.p), 0, (int)((int64_t)a.M * a.A.ld * ESZ), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rD =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.D.p), 0, (int)((int64_t)a.M * a.D.ld * ESZ), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(DPRO ? a.db.y : a.D.p), 0, (int)((int64_t)a.M * (DPRO ? N : a.D.ld) * ESZ), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rA = buffer_rsrc(a.A.p, (int)((int64_t)a.M * a.A.ld * ESZ));
+    const __amdgpu_buffer_rsrc_t rD = buffer_rsrc(a.D.p, (int)((int64_t)a.M * a.D.ld * ESZ));
+    const __amdgpu_buffer_rsrc_t rY = buffer_rsrc(DPRO ? a.db.y : a.D.p, (int)((int64_t)a.M * (DPRO ? N : a.D.ld) * ESZ));
     const uint32_t voA = kon ? (uint32_t)(LHR * lh * a.A.ld + a.A.coff + k) * ESZ : OOR;
     uint32_t voD[NJW], voY[NJW];
 #pragma unroll
@@ -244,7 +239,7 @@ __global__ void __launch_bounds__(512) tn_direct_kernel(TnDirectArgs a) {
         if (!non[j]) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kk = k0 + ki * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int kk = acc_row(k0 + ki * 32, r, lh);
             if (kk < K) out[(int64_t)kk * N + ncol[j]] = acc[j][r];
         }
     }
@@ -323,13 +318,9 @@ __global__ void __launch_bounds__(512) tn_direct_tr_kernel(TnDirectArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
 
-    const uint32_t OOR = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rA =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A.p), 0, (int)((int64_t)a.M * a.A.ld * ESZ), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rD =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.D.p), 0, (int)((int64_t)a.M * a.D.ld * ESZ), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(DPRO ? a.db.y : a.D.p), 0, (int)((int64_t)a.M * (DPRO ? N : a.D.ld) * ESZ), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rA = buffer_rsrc(a.A.p, (int)((int64_t)a.M * a.A.ld * ESZ));
+    const __amdgpu_buffer_rsrc_t rD = buffer_rsrc(a.D.p, (int)((int64_t)a.M * a.D.ld * ESZ));
+    const __amdgpu_buffer_rsrc_t rY = buffer_rsrc(DPRO ? a.db.y : a.D.p, (int)((int64_t)a.M * (DPRO ? N : a.D.ld) * ESZ));
     const uint32_t voD = non ? (uint32_t)(LHR * lh * a.D.ld + dcol) * ESZ : OOR;
     const uint32_t voY = non ? (uint32_t)(LHR * lh * N + n) * ESZ : OOR;
     uint32_t voA[NJW];
@@ -424,7 +415,7 @@ __global__ void __launch_bounds__(512) tn_direct_tr_kernel(TnDirectArgs a) {
         if (j >= kjn) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int kk = k0 + (kj0 + j) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int kk = acc_row(k0 + (kj0 + j) * 32, r, lh);
             if (kk < K) out[(int64_t)kk * N + n] = acc[j][r];
         }
     }

@@ -21,11 +21,9 @@
 #include <stdlib.h>
 
 #include "colreduce.h"
+#include "mfma_x3.h"
 
 namespace cdrl {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct TnLdsArgs {
     View A, D;
@@ -41,8 +39,8 @@ constexpr int TNL_R = 32;               // rows per chunk
 // MODE 2: activation tensors (A, D, y) are bf16 in HBM, bf16 MFMA operands; MODE 1: float32 tensors, operands rounded to bf16 after
 // the prologues; MODE 0: float32 tensors AND float32 operands (v_mfma_f32_32x32x2_f32: the exact k-ordered fmaf chain of the
 // float32 engine) -- same staging, the LDS columns hold floats.  MODE 3: float32 tensors, float32-ACCURATE product on the bf16 pipe:
-// after the prologues every operand value is split into three bf16 planes (x = x1 + x2 + x3 to 24 mantissa bits, as gemm_x3.hip /
-// gemm_pw_x3.hip do for the forward GEMMs) and the product is the six plane products x1 d1 + x1 d2 + x2 d1 + x1 d3 + x3 d1 + x2 d2:
+// after the prologues every operand value is split into three bf16 planes (x = x1 + x2 + x3 to 24 mantissa bits, mfma_x3.h) and
+// the product is the six plane products x1 d1 + x1 d2 + x2 d1 + x1 d3 + x3 d1 + x2 d2:
 // 6 x 32 matrix-pipe cycles per 16 rows and tile pair instead of 8 x 64 for v_mfma_f32_32x32x2_f32.  Three planes per operand do
 // not leave room for a second LDS buffer at two workgroups per CU: one buffer, two barriers per chunk.
 template <int MODE, bool APRO, bool DPRO>
@@ -92,13 +90,9 @@ __global__ void __launch_bounds__(256, 2) tn_lds_kernel(TnLdsArgs a) {
     }
     const bool relu = DPRO && a.db.act == ACT_RELU6;
     // ---- global loads through buffer descriptors (masked lanes point out of range and read 0)
-    const uint32_t OOR = 0x80000000u;
-    const __amdgpu_buffer_rsrc_t rA =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A.p), 0, (int)((int64_t)a.M * a.A.ld * ESZ), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rD =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.D.p), 0, (int)((int64_t)a.M * a.D.ld * ESZ), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(DPRO ? a.db.y : a.D.p), 0, (int)((int64_t)a.M * (DPRO ? N : a.D.ld) * ESZ), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rA = buffer_rsrc(a.A.p, (int)((int64_t)a.M * a.A.ld * ESZ));
+    const __amdgpu_buffer_rsrc_t rD = buffer_rsrc(a.D.p, (int)((int64_t)a.M * a.D.ld * ESZ));
+    const __amdgpu_buffer_rsrc_t rY = buffer_rsrc(DPRO ? a.db.y : a.D.p, (int)((int64_t)a.M * (DPRO ? N : a.D.ld) * ESZ));
     // column offsets (elements) of the thread's 4 columns; pairs (j, j + 1) resp. (j, j + 2) are adjacent in memory
     const bool a4 = (ka + 3 < K);                        // all four A columns exist (K is even: otherwise the first two or none)
     const bool a2 = (ka + 1 < K);
@@ -121,11 +115,10 @@ __global__ void __launch_bounds__(256, 2) tn_lds_kernel(TnLdsArgs a) {
     }
     const uint32_t voY = d2 ? (uint32_t)nd * ESZ : OOR;
     const uint32_t sA = (uint32_t)a.A.ld * ESZ, sD = (uint32_t)a.D.ld * ESZ, sY = (uint32_t)N * ESZ;
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
     // two adjacent elements at a byte offset, as floats.  The row offset goes into the PER-LANE offset: a wave covers two row
     // groups, and a non-uniform scalar offset would be executed as a waterfall loop (one pass per distinct value)
     auto ld2 = [&](const __amdgpu_buffer_rsrc_t& rs, uint32_t vo, uint32_t ro, float& x0, float& x1) {
-        const uint32_t off = (vo & 0x80000000u) ? 0x80000000u : vo + ro;
+        const uint32_t off = (vo & OOR) ? OOR : vo + ro;
         if (BH) {
             const uint32_t w = __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0);
             x0 = bf_lo(w);
@@ -235,7 +228,6 @@ __global__ void __launch_bounds__(256, 2) tn_lds_kernel(TnLdsArgs a) {
     // fragment of a 16-row step: lane (column l32 of the tile, half lh) holds rows 16 s + 8 lh .. + 7 of its column
     auto frag = [&](const uint32_t* base, int col, int s) -> bf16x8 {
         const uint32_t* p = base + col * TNL_CS + 8 * s + 4 * lh;
-        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
         u32x4_t w;
         w[0] = p[0];
         w[1] = p[1];
@@ -270,7 +262,7 @@ __global__ void __launch_bounds__(256, 2) tn_lds_kernel(TnLdsArgs a) {
                     if (j < NT) {
                         const bf16x8 d1 = frag(DsT[0], j * 32 + l32, s), d2 = frag(DsT[X3 ? 1 : 0], j * 32 + l32, s),
                                      d3 = frag(DsT[X3 ? 2 : 0], j * 32 + l32, s);
-                        // smallest terms first
+                        // smallest terms first, but NOT in the order of x3_mfma (mfma_x3.h): this order is pinned by bit-identity
                         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, d2, acc[j], 0, 0, 0);
                         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, d1, acc[j], 0, 0, 0);
                         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, d3, acc[j], 0, 0, 0);
@@ -313,7 +305,7 @@ __global__ void __launch_bounds__(256, 2) tn_lds_kernel(TnLdsArgs a) {
         if (j >= NT || n >= N) continue;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int kk = k0 + wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * lh;
+            const int kk = acc_row(k0 + wave * 32, q, lh);
             if (kk < K) out[(int64_t)kk * N + n] = acc[j][q];
         }
     }

@@ -3,8 +3,8 @@
 // its backward-data product, where K and N exceed what gemm_pw_x3.hip keeps in registers.
 //
 // The float32-MFMA form of these products is the most matrix-bound kernel of the step (MfmaUtil 0.31-0.47,
-// profiles/r02_pmc_mfma.json: 8.7 GFLOP = 56 us at the float32 MFMA peak for 60 MB of HBM traffic).  As in gemm_pw_x3.hip:
-// a = a1 + a2 + a3, b = b1 + b2 + b3 exactly in bf16, six products per K = 16 step carry a b to 2^-24.
+// profiles/r02_pmc_mfma.json: 8.7 GFLOP = 56 us at the float32 MFMA peak for 60 MB of HBM traffic).  The split and the
+// six-product step (and why they carry a b to 2^-24) are those of mfma_x3.h.
 //   * B (the weights) is split and packed ONCE per pass into MFMA fragment order  Bp[plane][k step][k half][n][8]  (gemm_x3_pack);
 //     a wave reads its fragments straight from that array (16-byte loads, L2 resident), no LDS for B;
 //   * A is loaded as float32 (16-byte lanes), split on its way into LDS (three bf16 planes, 128 rows x 32 k per stage), double
@@ -15,10 +15,6 @@
 
 namespace cdrl {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 struct GemmX3Args {
     View A;
     const __bf16* Bp;           // [3][KS][2][NP][8], KS = ceil(K/16), NP = N padded to 128
@@ -27,13 +23,6 @@ struct GemmX3Args {
     int accumulate;
     int M, N, K, KS, NP;
 };
-
-__device__ __forceinline__ void gx3_split(float x, __bf16& h1, __bf16& h2, __bf16& h3) {
-    h1 = (__bf16)x;
-    const float r1 = x - (float)h1;
-    h2 = (__bf16)r1;
-    h3 = (__bf16)(r1 - (float)h2);
-}
 
 // NS = 3: exact three-way split (float32-accurate product).  NS = 1: the bf16-operand compute mode of configuration 3 -- both
 // operands rounded once to bf16 (plane 0 of the split = round-to-nearest-even), one MFMA per K = 16 step.
@@ -54,10 +43,7 @@ __global__ void __launch_bounds__(256, 2) gemm_x3_kernel(GemmX3Args a) {
     const int K = a.K, N = a.N;
     const int nstage = (K + BK - 1) / BK;
     // A stage loads: 128 rows x 8 chunks of 4 floats = 1024 chunks, 4 per thread
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-    const uint32_t OOR = 0x80000000u;
-    typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(a.A.p, 0, (int)((int64_t)a.M * a.A.ld * ESZ), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = buffer_rsrc(a.A.p, (int)((int64_t)a.M * a.A.ld * ESZ));
     const int cr = tid >> 3, ck = 4 * (tid & 7);            // chunk row (0..31, +32 i), chunk k
     auto load_stage = [&](int s, u32x4_t (&ra)[4]) {
         const int k = s * BK + ck;
@@ -89,7 +75,7 @@ __global__ void __launch_bounds__(256, 2) gemm_x3_kernel(GemmX3Args a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 __bf16 h1, h2, h3;
-                gx3_split(__uint_as_float(ra[i][e]), h1, h2, h3);
+                x3_split(__uint_as_float(ra[i][e]), h1, h2, h3);
                 h[0][e] = h1;
                 h[1][e] = h2;
                 h[2][e] = h3;
@@ -127,16 +113,8 @@ __global__ void __launch_bounds__(256, 2) gemm_x3_kernel(GemmX3Args a) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                f32x16 c = acc[i][j];           // smallest terms first
-                if constexpr (NS == 3) {
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], bf[0][j], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[2][j], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[1][j], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], bf[0][j], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[1][j], c, 0, 0, 0);
-                }
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], c, 0, 0, 0);
-                acc[i][j] = c;
+                if constexpr (NS == 3) acc[i][j] = x3_mfma(af[0][i], af[1][i], af[2][i], bf[0][j], bf[1][j], bf[2][j], acc[i][j]);
+                else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], bf[0][j], acc[i][j], 0, 0, 0);
             }
     };
     // B fragments (L2) are fetched one K = 16 step ahead; A stages (HBM, ~2 us under load) TWO stages ahead in two register
@@ -175,7 +153,7 @@ __global__ void __launch_bounds__(256, 2) gemm_x3_kernel(GemmX3Args a) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t m = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lk;
+                const int64_t m = acc_row(m0 + wr * 64 + i * 32, r, lk);
                 if (m < a.M) {
                     T* c = vptr<T>(a.C) + m * a.C.ld + a.C.coff + n;
                     float v = acc[i][j][r] + bv;

@@ -2,18 +2,9 @@
 // so that ONE launch can run all four at the start of a training pass (pack_all, gemm_pw.hip): they were four dependent 4-13 us
 // launches of the critical stream in front of every stem conv.  `bx` / `nbx` stand for blockIdx.x / gridDim.x of the original kernels.
 #pragma once
-#include "cdrl_kernels.h"
+#include "mfma_x3.h"
 
 namespace cdrl {
-
-typedef __bf16 pk_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void pk_split3(float x, __bf16& h1, __bf16& h2, __bf16& h3) {
-    h1 = (__bf16)x;
-    const float r1 = x - (float)h1;             // exact
-    h2 = (__bf16)r1;
-    h3 = (__bf16)(r1 - (float)h2);              // exact difference, final rounding below 2^-24 |x|
-}
 
 // B(k, n) = w[k * sbk + n * sbn] -> fragment order [ct = n / 32][lk = k & 1][n & 31][s = k >> 1] (zero padded to KSM, 32)
 __device__ __forceinline__ void pw_pack_body(const PwPack& d, int bx, int nbx) {
@@ -42,19 +33,19 @@ __device__ __forceinline__ void pw_x3_pack_body(const PwX3Pack& d, int bx, int n
     for (int ii = bx * 256 + threadIdx.x; ii < total * nblk; ii += nbx * 256) {
         const int blk = ii / total, i = ii % total;
         const int nl = i % 128, n = blk * 128 + nl, lk = (i / 128) % 2, s = i / 256;
-        pk_bf16x8 v[3];
+        bf16x8 v[3];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int k = 16 * s + 8 * lk + e;
             const float x = (k < d.K && n < d.N) ? d.w[(int64_t)k * d.sbk + (int64_t)n * d.sbn] : 0.0f;
             __bf16 h1, h2, h3;
-            pk_split3(x, h1, h2, h3);
+            x3_split(x, h1, h2, h3);
             v[0][e] = h1;
             v[1][e] = h2;
             v[2][e] = h3;
         }
 #pragma unroll
-        for (int p = 0; p < 3; ++p) *reinterpret_cast<pk_bf16x8*>(d.wp + (((int64_t)blk * 3 + p) * total + i) * 8) = v[p];
+        for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(d.wp + (((int64_t)blk * 3 + p) * total + i) * 8) = v[p];
     }
 }
 
@@ -64,19 +55,19 @@ __device__ __forceinline__ void gemm_x3_pack_body(const GemmX3Pack& d, int bx, i
     const int total = d.KS * 2 * d.NP;
     for (int i = bx * 256 + threadIdx.x; i < total; i += nbx * 256) {
         const int n = i % d.NP, lk = (i / d.NP) % 2, ks = i / (2 * d.NP);
-        pk_bf16x8 v[3];
+        bf16x8 v[3];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int k = 16 * ks + 8 * lk + e;
             const float x = (k < d.K && n < d.N) ? d.w[(int64_t)k * d.sbk + (int64_t)n * d.sbn] : 0.0f;
             __bf16 h1, h2, h3;
-            pk_split3(x, h1, h2, h3);
+            x3_split(x, h1, h2, h3);
             v[0][e] = h1;
             v[1][e] = h2;
             v[2][e] = h3;
         }
 #pragma unroll
-        for (int p = 0; p < 3; ++p) *reinterpret_cast<pk_bf16x8*>(d.wp + p * plane + (int64_t)i * 8) = v[p];
+        for (int p = 0; p < 3; ++p) *reinterpret_cast<bf16x8*>(d.wp + p * plane + (int64_t)i * 8) = v[p];
     }
 }
 

@@ -4,7 +4,8 @@ compute the same update bit for bit (the proof of a host-side refactor of the pa
 Per configuration: an engine at B = 4, H = 48, W = 64, init_engine_parameters(seed=4), three steps on tests/util.make_batches(seed=21),
 then one digest over params, adam_m, adam_v, grads, the two metrics buffers, get_optimizer_state() and, with train stats, the ring's rows.
 Configurations: pass kind (separate / joint, stored action / re-sampled with seed 9, offset 3 + step) x gradient gate x frozen trunk, and
-on top of the two stored kinds one of optimizer='nadam', train_stats=8, compute='bf16s'; on top of separate-stored the update kernel's
+on top of the two stored kinds one of optimizer='nadam', train_stats=8, compute='bf16s', compute='bf16' (bf16 MFMA operands on float32
+tensors); on top of separate-stored the update kernel's
 forms (word `update`): every optimizer, Adam and Nadam with polyak=0.9, skip_nonfinite alone.  CDRL_GRAPH is the caller's.
 
     python tools/arena_digest.py                         (every configuration)
@@ -32,7 +33,7 @@ def configurations():
             for frozen in (0, 1):
                 out.append((f'{kind} gate={gate} frozen={frozen}', kind, dict(GATE if gate else {}, freeze_trunk=bool(frozen))))
     for kind in ('separate-stored', 'joint-stored'):
-        for extra in (dict(optimizer='nadam'), dict(train_stats=8), dict(compute='bf16s')):
+        for extra in (dict(optimizer='nadam'), dict(train_stats=8), dict(compute='bf16s'), dict(compute='bf16')):
             (k, v), = extra.items()
             out.append((f'{kind} {k}={v}', kind, extra))
     # the update kernel: every optimizer, polyak averaging, and the tensor-mode gate (skip_nonfinite alone: per-tensor clip)
