@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "cdrl_host.h"
+
 namespace cdrl {
 
 // Channels-last 2-D view: element (row r, channel c) lives at p[r*ld + coff + c].
@@ -72,62 +74,19 @@ __device__ __forceinline__ float act_grad(float x, float d, int act) {
 
 __host__ __device__ inline int shuffle_dst(int i, int ctot) { return (i & 1) * (ctot >> 1) + (i >> 1); }
 
-void set_error(const char* fmt, ...);
-const char* last_error();
-// getenv for the library's CDRL_* switches: CDRL_DIAG_* (wrong-result timing diagnostics) only with the master CDRL_DIAG=1
-const char* cdrl_getenv(const char* name);
 int diag_active();                          // number of active CDRL_DIAG_* switches (0 unless CDRL_DIAG=1)
 int env_overrides(char* buf, int cap);      // "NAME=VALUE ..." of every CDRL_* variable in the environment; returns their count
 
-#define CDRL_HIP(expr)                                                                         \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess) {                                                                \
-            cdrl::set_error("%s:%d %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            return -2;                                                                         \
-        }                                                                                      \
-    } while (0)
-
 #define CDRL_LAUNCH_CHECK() CDRL_HIP(hipGetLastError())
 
-// Tail events (round 6): a fork to another stream used to be hipEventRecord on the critical stream -- a barrier packet of its own in
-// the queue, a bubble in front of the next kernel, ~70 times per update-step.  hipExtLaunchKernelGGL binds a STOP EVENT to the kernel's
-// own dispatch packet instead (its completion signal), so the other stream can wait for "the newest kernel of the critical stream"
-// without anything being enqueued there.  A stop event on EVERY kernel costs more than the bubbles it removes (+0.16 ms per
-// update-step), so the launches that need one are LEARNED: while a thread has a TailEvents installed (Learner::launch), launch number i
-// of the body carries an event iff a fork followed launch i the last time this body ran (`need`); a fork that finds no event behind the
-// newest kernel (`last` null: first run, a changed sequence, a copy or memset behind the kernel) records one the old way and marks the
-// launch for the next run.  Always correct; converges after one run of each body.
-struct TailEvents {
-    hipStream_t stream = nullptr;
-    hipEvent_t ring[32] = {};
-    int n = 0;
-    unsigned head = 0;
-    hipEvent_t last = nullptr;      // stop event of the newest kernel on `stream`, if it carries one
-    int idx = 0;                    // launches of this body on `stream` so far
-    uint8_t* need = nullptr;        // per launch index of the current body: 1 = a fork followed it
-    int need_cap = 0;
-};
-extern thread_local TailEvents* tl_tail;
-
+// Every kernel launch of the library: with the stop event the tail-event bookkeeping asks for (TailEvents, cdrl_host.h), or plain
 template <typename... Args, typename... Act>
 inline void launch_tracked(void (*kernel)(Args...), dim3 grid, dim3 block, uint32_t lds, hipStream_t st, Act&&... args) {
-    TailEvents* t = tl_tail;
-    if (t && st == t->stream) {
-        const int i = t->idx++;
-        if (i < t->need_cap && t->need[i]) {
-            hipEvent_t ev = t->ring[t->head++ % (unsigned)t->n];
-            hipExtLaunchKernelGGL(kernel, grid, block, lds, st, nullptr, ev, 0, static_cast<Args>(args)...);
-            t->last = ev;
-            return;
-        }
-        t->last = nullptr;
+    if (hipEvent_t ev = tail_note_launch(st)) {
+        hipExtLaunchKernelGGL(kernel, grid, block, lds, st, nullptr, ev, 0, static_cast<Args>(args)...);
+        return;
     }
     kernel<<<grid, block, lds, st>>>(static_cast<Args>(args)...);
-}
-inline void tail_invalidate(hipStream_t st) {
-    TailEvents* t = tl_tail;
-    if (t && st == t->stream) t->last = nullptr;
 }
 
 // "Set the dynamic-LDS attribute of this kernel once" guards: once PER DEVICE (a second engine on another device of the same process, or
@@ -146,12 +105,6 @@ struct LdsAttrOnce {
         done[d & 63] = 1;
     }
 };
-
-#define CDRL_TRY(expr)            \
-    do {                          \
-        int _r = (expr);          \
-        if (_r != 0) return _r;   \
-    } while (0)
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -232,6 +185,6 @@ inline VColGeom vcol_geom(int rows_per_group, int C, int max_blocks_per_group = 
 
 }  // namespace cdrl
 
-// every launch of the library goes through launch_tracked (see TailEvents above)
+// every launch of the library goes through launch_tracked
 #undef hipLaunchKernelGGL
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) ::cdrl::launch_tracked(kernel, dim3(grid), dim3(block), (uint32_t)(lds), stream, __VA_ARGS__)

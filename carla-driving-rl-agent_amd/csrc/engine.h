@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "cdrl_kernels.h"
+#include "sched.h"
 
 namespace cdrl {
 
@@ -124,8 +125,9 @@ public:
                                          hipStream_t st);
     float* sample_buffer() const { return sample_u_; }
     int policy_apply(hipStream_t st);
-    int sequence_begin(hipStream_t caller);
-    int sequence_end(hipStream_t caller);
+    // a sequence of calls on ONE caller stream: the hand-overs happen once, around the whole sequence
+    int sequence_begin(hipStream_t caller) { return sched_.sequence_begin(caller); }
+    int sequence_end(hipStream_t caller) { return sched_.sequence_end(caller); }
     int value_forward_backward(const ValueBatch& b, float inv_world, hipStream_t st);
     int value_apply(hipStream_t st);
     // Joint policy + value update (opt-in): ONE train-mode trunk forward (moving statistics updated once), both heads'
@@ -202,7 +204,7 @@ public:
     // Data-parallel overlap: `s` (a caller-owned stream, or null) is made to wait, in the middle of every backward pass, for
     // the point where the gradients of the heads and of the trunk tail (GRUs, feature nets, concat BN + Dense) are final --
     // a collective enqueued on `s` after the pass has been enqueued then runs UNDER the tower's backward.
-    void set_comm_stream(hipStream_t s) { comm_ = s; }
+    void set_comm_stream(hipStream_t s) { sched_.set_comm(s); }
     // First element (inside the trunk's trainable region) of the TAIL tensors: everything registered behind the image tower,
     // i.e. exactly the gradients that are final at the point the communication stream is released.  Fixed by the op list.
     // Frozen trunk: no trunk gradient is ever written and the stream is never released; the whole trunk counts as "not final".
@@ -214,7 +216,7 @@ public:
     // one device-to-host copy of the block behind everything on `st` (waits for it); counters to zero, enqueued on `st`
     int gate_stats(GateBlock* out, hipStream_t st);
     int gate_reset(hipStream_t st);
-    bool graphs_enabled() const { return graphs_enabled_; }
+    bool graphs_enabled() const { return sched_.graphs(); }
     // Named internal tensors (parity tests: the raw BatchNorm inputs, statistics blocks, max-pool argmax codes and dense
     // pre-activations from which the discrete ReLU6 / max-pool decisions of the last forward are reconstructed)
     // CDRL_GUARD=1: 64 KB canary bands behind every workspace tensor (filled at bind); counts the bands that lost their pattern
@@ -390,16 +392,14 @@ private:
                  bool need_dx);
     void note_scratch(size_t part_d, size_t part2_d, size_t dy_f, size_t tn_f, size_t fpart_d = 0);
 
-    // Every public step runs on the engine's own stream `main_` (bridged to the caller's stream with
+    // Every public step runs on the scheduler's main stream (bridged to the caller's stream with
     // events) and, when `graphable`, is captured once into a hipGraph (main + side stream, ~1000
     // kernel nodes per pass) and replayed afterwards: the update-step is launch-bound on the host
     // otherwise (measured: 22 ms of CPU enqueue time per 30 ms update-step).  The cache key is the
     // step kind + every pointer / scalar argument baked into the captured kernel arguments.
     int launch(hipStream_t caller, std::vector<uint64_t> key, bool graphable, const std::function<int(hipStream_t)>& body);
     void drop_graphs();
-    hipStream_t main_ = nullptr;
-    hipEvent_t ev_in_ = nullptr, ev_out_ = nullptr;
-    bool graphs_enabled_ = true;
+    StreamSched sched_;                 // the streams and everything that orders them (sched.h)
     std::map<std::vector<uint64_t>, hipGraphExec_t> graphs_;
     // One training pass as its entry point describes it: the state pointers, the policy part (adv .. du_db) and / or the value part
     // (returns; both: the joint pass), the one speed / similarity pair, the device re-sampling and the gradient scale
@@ -474,80 +474,25 @@ private:
     SlotSizes slot_sizes() const;
     void alloc_scratch();               // main / aux / shortcut scratch, the NSLOT rotating slots, the NQ ring
     Scratch scr_main_, scr_aux_, scr_sc_;
-    hipEvent_t ev_sc_fork_[3] = {}, ev_sc_done_[3] = {};   // shortcut branch of the stride-2 units on the side stream (forward)
     Scratch* build_scr_ = &scr_main_;
     std::vector<Op> aux_ops_;
-    hipEvent_t ev_aux_fork_ = nullptr, ev_aux_done_ = nullptr;
     void add_aux_fork(std::vector<Op>& ops);
     void add_aux_join(std::vector<Op>& ops);
-    // Backward-pass side stream: the filter / bias gradients of the tower (gemm_tn, depthwise and stem
-    // filter reductions, db) are off the critical path dy -> bwd-data -> next layer, so they run on a
-    // second HIP stream and overlap the latency-bound main chain.  NSLOT rotating scratch sets
-    // (dy, db partials, split-M partials, filter partials) + events make the hand-off race-free.
-    static constexpr int NSLOT = 8;
+    // Rotating scratch sets of the backward's side jobs (dy, db partials, split-M partials, filter partials), indexed by sched_.slot()
+    static constexpr int NSLOT = StreamSched::NSLOT;
     float* dys_[NSLOT] = {};
     double* part2s_[NSLOT] = {};
     float* tns_[NSLOT] = {};
     double* fparts_[NSLOT] = {};
     // fused conv backward: per-workgroup filter-product tiles / column sums.  Their own small ring (the tiles are large: 16-21 MB per
-    // conv at B = 256), guarded by events recorded behind the side-stream reduce that reads them
-    static constexpr int NQ = 3;
+    // conv at B = 256), indexed by sched_.q()
+    static constexpr int NQ = StreamSched::NQ;
     float* qparts_[NQ] = {};
     double* dbparts_[NQ] = {};
     double* fintots_[NQ] = {};           // [8][2][128] group totals of a finalize-on-load BatchNorm (gemm_pw_bwd.hip)
     bool fin_on_load_ = true;            // the fused conv backward finalizes the BatchNorm behind it on load (CDRL_FIN_ON_LOAD=0: stand-alone launches)
-    hipEvent_t ev_q_[NQ] = {};
-    bool q_used_[NQ] = {};
-    int qi_ = 0;
-    int next_q(hipStream_t st);          // main: claim the next buffer pair (waits for the side job that last read it)
     size_t max_qpart_ = 0, max_dbpart_ = 0;
-    int flush_side(hipStream_t st);      // enqueue the deferred side jobs now (one event record on `st`)
-    hipStream_t side_ = nullptr;
-    hipStream_t aux_ = nullptr;          // feature nets + small GRUs (forward and backward)
-    bool aux_pending_ = false;
-    hipEvent_t ev_in_sys_ = nullptr;                    // hand-over from the caller's stream with the fence (data-parallel use)
-    hipEvent_t ev_out_sys_ = nullptr;                   // hand-back to the caller's stream WITH the system-scope fence (data-parallel use)
-    bool dp_hint_ = false;                              // a pass ran with a gradient scale below 1 (world size > 1)
     bool packs_have_wt_ = false;                        // the last forward's pack launch also wrote the W^T copies of the backward
-    bool seq_open_ = false;                             // between sequence_begin and sequence_end on seq_caller_
-    hipStream_t seq_caller_ = nullptr;
-    TailEvents tail_;                                   // stop events of the critical stream's kernels (cdrl_common.h)
-    std::map<std::vector<uint64_t>, std::vector<uint8_t>> tail_need_;      // per body (launch key): which launches a fork follows
-    int mark_stream(hipStream_t st, hipEvent_t fallback, hipEvent_t* ev);
-    hipEvent_t ev_main_[NSLOT] = {};
-    hipEvent_t ev_side_[NSLOT] = {};
-    hipEvent_t ev_join_ = nullptr;
-    bool side_enabled_ = true;
-    bool slot_used_[NSLOT] = {};
-    // numbered records of the side stream and what the critical stream has waited for (engine.hip: wait_side_record)
-    struct SideRec { hipEvent_t ev = nullptr; uint64_t seq = 0; };
-    static constexpr int SIDE_HIST = 32;
-    SideRec side_hist_[SIDE_HIST];
-    uint64_t side_seq_ = 0, main_waited_ = 0;
-    uint64_t slot_seq_[NSLOT] = {}, q_seq_[NQ] = {};
-    int side_lag_ = 4;
-    // record `ev` on the side stream and number the record; seq / used: the scratch slot or ring entry that is free once it is covered
-    int record_side(hipEvent_t ev, uint64_t* seq = nullptr, bool* used = nullptr);
-    // `st` joins the side stream: `ev` recorded there (numbered) and waited for; the critical stream has then waited for that record
-    int join_side_at(hipStream_t st, hipEvent_t ev);
-    int release_q(int qi, hipStream_t sd);               // side job that read ring entry qi finished (fused conv backward's reduce)
-    int wait_side_record(hipStream_t st, uint64_t need, hipEvent_t need_ev);
-    int slot_ = 0;
-    int next_slot(hipStream_t st);                       // main: claim a scratch slot (waits for its last side job)
-    hipStream_t fork_side(hipStream_t st);               // main -> side dependency for the current slot
-    int done_side(hipStream_t side);                     // side job of the current slot finished
-    // Side jobs that hang off the main stream but are not urgent (partial reductions of bias / depthwise-filter gradients)
-    // are queued and enqueued by the NEXT fork_side (or join_side): one event record on the critical stream serves
-    // several side jobs (every record is a barrier packet between two dependent main-stream kernels).
-    struct Deferred {
-        int slot;
-        std::function<int(hipStream_t)> fn;
-    };
-    std::vector<Deferred> deferred_;
-    int deferred_rc_ = 0;
-    int defer_side(hipStream_t st, std::function<int(hipStream_t)> fn);
-    void flush_deferred();
-    int join_side(hipStream_t st);
 
     std::vector<Op> trunk_ops_, policy_ops_, value_ops_, old_policy_ops_;
     // live input pointers (read by the first ops through these slots)
@@ -618,9 +563,7 @@ private:
     GemmX3Pack* d_gpack_ = nullptr;
     const void* gemm_x3_packed(const float* w, int K, int N, int sbk, int sbn);
     int run_trunk_fwd(hipStream_t st, int training);
-    hipStream_t comm_ = nullptr;
     int64_t tail_off_ = 0;
-    hipEvent_t ev_tail_main_ = nullptr, ev_tail_side_ = nullptr;
     std::vector<std::pair<void*, size_t>> zero_once_;    // workspace regions that must read as zero and are never written
     float* pw_transposed(const std::string& name, const float* w, int cin, int cout);
     bool tables_uploaded_ = false;

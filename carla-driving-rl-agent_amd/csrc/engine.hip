@@ -55,31 +55,7 @@ Learner::Learner(const Config& cfg) : cfg_(cfg) {
 
 Learner::~Learner() {
     if (hp_stage_) (void)hipHostFree(hp_stage_);
-    for (int i = 0; i < NSLOT; ++i) {
-        if (ev_main_[i]) (void)hipEventDestroy(ev_main_[i]);
-        if (ev_side_[i]) (void)hipEventDestroy(ev_side_[i]);
-    }
     drop_graphs();
-    if (ev_in_) (void)hipEventDestroy(ev_in_);
-    if (ev_out_) (void)hipEventDestroy(ev_out_);
-    if (ev_out_sys_) (void)hipEventDestroy(ev_out_sys_);
-    if (ev_in_sys_) (void)hipEventDestroy(ev_in_sys_);
-    if (main_) (void)hipStreamDestroy(main_);
-    if (ev_join_) (void)hipEventDestroy(ev_join_);
-    for (int i = 0; i < NQ; ++i)
-        if (ev_q_[i]) (void)hipEventDestroy(ev_q_[i]);
-    for (int i = 0; i < 32; ++i)
-        if (tail_.ring[i]) (void)hipEventDestroy(tail_.ring[i]);
-    if (ev_tail_main_) (void)hipEventDestroy(ev_tail_main_);
-    if (ev_tail_side_) (void)hipEventDestroy(ev_tail_side_);
-    for (int i = 0; i < 3; ++i) {
-        if (ev_sc_fork_[i]) (void)hipEventDestroy(ev_sc_fork_[i]);
-        if (ev_sc_done_[i]) (void)hipEventDestroy(ev_sc_done_[i]);
-    }
-    if (ev_aux_fork_) (void)hipEventDestroy(ev_aux_fork_);
-    if (ev_aux_done_) (void)hipEventDestroy(ev_aux_done_);
-    if (side_) (void)hipStreamDestroy(side_);
-    if (aux_) (void)hipStreamDestroy(aux_);
 }
 
 void Learner::drop_graphs() {
@@ -89,41 +65,21 @@ void Learner::drop_graphs() {
 
 int Learner::launch(hipStream_t caller, std::vector<uint64_t> key, bool graphable,
                     const std::function<int(hipStream_t)>& body) {
-    if (!main_) {
-        set_error("learner not bound");
-        return -1;
-    }
-    // inside a sequence (sequence_begin .. sequence_end on this stream) the hand-overs between the caller's stream and the engine's happen
-    // once, around the whole sequence
-    const bool in_seq = seq_open_ && caller == seq_caller_;
-    if (!in_seq) {
-        hipEvent_t ei = (comm_ || dp_hint_) ? ev_in_sys_ : ev_in_;      // (data-parallel use: fenced both ways, see below)
-        CDRL_HIP(hipEventRecord(ei, caller));
-        CDRL_HIP(hipStreamWaitEvent(main_, ei, 0));
-    }
+    CDRL_TRY(sched_.hand_in(caller));       // (refuses a learner that is not bound)
+    hipStream_t main = sched_.main();
     int rc = 0;
-    if (!graphs_enabled_ || !graphable) {
-        // eager launches: kernels on the critical stream carry stop events (TailEvents, cdrl_common.h) while the body runs on this thread
-        if (tail_.n > 0) {
-            if (tail_need_.size() > 64) tail_need_.clear();
-            std::vector<uint8_t>& need = tail_need_[key];
-            if (need.empty()) need.assign(4096, 0);
-            tail_.need = need.data();
-            tail_.need_cap = (int)need.size();
-            tail_.idx = 0;
-            tail_.last = nullptr;
-            tl_tail = &tail_;
-        }
-        rc = body(main_);
-        tl_tail = nullptr;
+    if (!sched_.graphs() || !graphable) {
+        sched_.begin_body(key);
+        rc = body(main);
+        sched_.end_body();
     } else {
         auto it = graphs_.find(key);
         if (it == graphs_.end()) {
             if (graphs_.size() >= 32) drop_graphs();
             hipGraph_t graph = nullptr;
-            CDRL_HIP(hipStreamBeginCapture(main_, hipStreamCaptureModeRelaxed));
-            rc = body(main_);
-            hipError_t ce = hipStreamEndCapture(main_, &graph);
+            CDRL_HIP(hipStreamBeginCapture(main, hipStreamCaptureModeRelaxed));
+            rc = body(main);
+            hipError_t ce = hipStreamEndCapture(main, &graph);
             if (rc != 0 || ce != hipSuccess || !graph) {
                 if (graph) (void)hipGraphDestroy(graph);
                 if (rc == 0) {
@@ -141,191 +97,14 @@ int Learner::launch(hipStream_t caller, std::vector<uint64_t> key, bool graphabl
             }
             it = graphs_.emplace(std::move(key), exec).first;
         }
-        CDRL_HIP(hipGraphLaunch(it->second, main_));
+        CDRL_HIP(hipGraphLaunch(it->second, main));
     }
     if (rc != 0) return rc;
-    if (in_seq) return 0;
-    // data-parallel use (a communication stream is set, or a pass ran with a gradient scale below 1): what the caller enqueued before /
-    // enqueues next may be a collective whose peers write / read these buffers -- both hand-overs keep the system-scope fence there
-    // (unmeasurable on one GPU: insurance)
-    hipEvent_t eo = (comm_ || dp_hint_) ? ev_out_sys_ : ev_out_;
-    CDRL_HIP(hipEventRecord(eo, main_));
-    CDRL_HIP(hipStreamWaitEvent(caller, eo, 0));
-    return 0;
-}
-
-// A sequence of learner calls on ONE caller stream with nothing of the caller's own in between (an update-step on one GPU: policy pass,
-// apply, value pass, apply): every call used to hand the work from the caller's stream to the engine's and back -- two markers and two
-// barrier packets across two queues per call, ~10 us of signal latency each way with nothing to order.  Between begin and end the calls
-// on that stream skip the hand-overs; begin orders the engine behind the caller's stream, end the caller's stream behind the engine.
-int Learner::sequence_begin(hipStream_t caller) {
-    if (!main_) {
-        set_error("learner not bound");
-        return -1;
-    }
-    if (seq_open_) {
-        set_error("sequence_begin: a sequence is already open");
-        return -1;
-    }
-    hipEvent_t ei = (comm_ || dp_hint_) ? ev_in_sys_ : ev_in_;
-    CDRL_HIP(hipEventRecord(ei, caller));
-    CDRL_HIP(hipStreamWaitEvent(main_, ei, 0));
-    seq_open_ = true;
-    seq_caller_ = caller;
-    return 0;
-}
-
-int Learner::sequence_end(hipStream_t caller) {
-    if (!seq_open_ || caller != seq_caller_) {
-        set_error("sequence_end: no sequence open on this stream");
-        return -1;
-    }
-    seq_open_ = false;
-    hipEvent_t eo = (comm_ || dp_hint_) ? ev_out_sys_ : ev_out_;
-    CDRL_HIP(hipEventRecord(eo, main_));
-    CDRL_HIP(hipStreamWaitEvent(caller, eo, 0));
-    return 0;
+    return sched_.hand_out(caller);
 }
 
 static const int g_diag_skip_fin = cdrl_getenv("CDRL_DIAG_SKIP_FIN") ? atoi(cdrl_getenv("CDRL_DIAG_SKIP_FIN")) : 0;   // timing diagnostics only (stale statistics)
-static const int g_diag_noev = cdrl_getenv("CDRL_DIAG_NOEV") ? atoi(cdrl_getenv("CDRL_DIAG_NOEV")) : 0;   // timing diagnostics only (racy)
-
-// Records on the side stream are numbered (the stream is in order: whoever has waited for record s has waited for every record
-// before it), and the critical stream remembers the newest one it has waited for.  A scratch slot / partial-tile buffer is free once
-// the record of its last user is covered -- so instead of one hipStreamWaitEvent (a barrier packet of its own on the critical stream,
-// 0.23 ms per update-step for ~100 of them by the no-waits diagnostic) per claim, the critical stream waits for a record `side_lag_`
-// behind the newest one whenever the record it needs is not covered yet, and skips the claims that wait covers (round 6).
-int Learner::record_side(hipEvent_t ev, uint64_t* seq, bool* used) {
-    CDRL_HIP(hipEventRecord(ev, side_));
-    ++side_seq_;
-    side_hist_[side_seq_ % SIDE_HIST] = SideRec{ev, side_seq_};
-    if (seq) *seq = side_seq_;
-    if (used) *used = true;
-    return 0;
-}
-
-int Learner::join_side_at(hipStream_t st, hipEvent_t ev) {
-    CDRL_TRY(record_side(ev));
-    CDRL_HIP(hipStreamWaitEvent(st, ev, 0));
-    if (st == main_) main_waited_ = side_seq_;
-    return 0;
-}
-
-int Learner::release_q(int qi, hipStream_t sd) {
-    if (!side_enabled_ || sd != side_) return 0;
-    return record_side(ev_q_[qi], &q_seq_[qi], &q_used_[qi]);      // the buffer pair is free again once the side job has run
-}
-
-int Learner::wait_side_record(hipStream_t st, uint64_t need, hipEvent_t need_ev) {
-    if (st != main_ || side_lag_ < 0) {              // another stream than the critical one (or the scheme off): the claim's own event
-        CDRL_HIP(hipStreamWaitEvent(st, need_ev, 0));
-        return 0;
-    }
-    if (need <= main_waited_) return 0;
-    uint64_t target = need;
-    if (side_seq_ > (uint64_t)side_lag_ && side_seq_ - (uint64_t)side_lag_ > target) target = side_seq_ - (uint64_t)side_lag_;
-    hipEvent_t ev = need_ev;
-    uint64_t covered = need;
-    if (side_seq_ - target < SIDE_HIST && side_hist_[target % SIDE_HIST].seq == target) {
-        ev = side_hist_[target % SIDE_HIST].ev;
-        covered = target;
-    }
-    for (int i = 0; i < SIDE_HIST; ++i)             // the event may have been recorded again since: waiting for it covers that record too
-        if (side_hist_[i].ev == ev && side_hist_[i].seq > covered) covered = side_hist_[i].seq;
-    CDRL_HIP(hipStreamWaitEvent(st, ev, 0));
-    main_waited_ = covered;
-    return 0;
-}
-
-int Learner::next_slot(hipStream_t st) {
-    slot_ = (slot_ + 1) % NSLOT;
-    if (g_diag_noev & 1) return 0;
-    if (side_enabled_ && slot_used_[slot_]) CDRL_TRY(wait_side_record(st, slot_seq_[slot_], ev_side_[slot_]));
-    return 0;
-}
-
-hipStream_t Learner::fork_side(hipStream_t st) {
-    if (!side_enabled_) return st;
-    if (g_diag_noev & 2) return side_;
-    hipEvent_t ev = nullptr;
-    if (mark_stream(st, ev_main_[slot_], &ev) != 0) return st;
-    if (hipStreamWaitEvent(side_, ev, 0) != hipSuccess) return st;
-    flush_deferred();
-    return side_;
-}
-
-// An event that covers everything `st` holds so far: the stop event of its newest kernel when the tail events are on and nothing
-// else went in behind that kernel (nothing is enqueued on `st`), else `fallback` recorded on `st`.
-int Learner::mark_stream(hipStream_t st, hipEvent_t fallback, hipEvent_t* ev) {
-    TailEvents* t = tl_tail;
-    if (t && st == t->stream && t->last) {
-        *ev = t->last;
-        return 0;
-    }
-    if (t && st == t->stream && t->idx > 0 && t->idx <= t->need_cap) t->need[t->idx - 1] = 1;     // next run: a stop event on that launch
-    CDRL_HIP(hipEventRecord(fallback, st));
-    *ev = fallback;
-    return 0;
-}
-
-void Learner::flush_deferred() {
-    for (Deferred& d : deferred_) {
-        const int rc = d.fn(side_);
-        if (rc != 0 && deferred_rc_ == 0) deferred_rc_ = rc;
-        // (a job of the current slot is covered by the done_side() that follows)
-        if (d.slot != slot_ && record_side(ev_side_[d.slot], &slot_seq_[d.slot], &slot_used_[d.slot]) != 0 && deferred_rc_ == 0) deferred_rc_ = -3;
-    }
-    deferred_.clear();
-}
-
-int Learner::defer_side(hipStream_t st, std::function<int(hipStream_t)> fn) {
-    if (!side_enabled_ || (g_diag_noev & 2)) {
-        hipStream_t side = fork_side(st);
-        CDRL_TRY(fn(side));
-        return done_side(side);
-    }
-    deferred_.push_back(Deferred{slot_, std::move(fn)});
-    return 0;
-}
-
-int Learner::next_q(hipStream_t st) {
-    qi_ = (qi_ + 1) % NQ;
-    if (side_enabled_ && q_used_[qi_]) CDRL_TRY(wait_side_record(st, q_seq_[qi_], ev_q_[qi_]));
-    return 0;
-}
-
-int Learner::flush_side(hipStream_t st) {
-    if (!side_enabled_ || deferred_.empty()) return 0;
-    hipStream_t side = fork_side(st);       // flushes the queue behind an event recorded on `st`
-    return done_side(side);
-}
-
-int Learner::done_side(hipStream_t side) {
-    if (!side_enabled_ || side != side_) return 0;
-    if (deferred_rc_ != 0) {
-        const int rc = deferred_rc_;
-        deferred_rc_ = 0;
-        return rc;
-    }
-    if (g_diag_noev & 4) return 0;
-    return record_side(ev_side_[slot_], &slot_seq_[slot_], &slot_used_[slot_]);
-}
-
-int Learner::join_side(hipStream_t st) {
-    if (!side_enabled_) return 0;
-    if (!deferred_.empty()) {
-        hipStream_t side = fork_side(st);       // flushes the queue
-        CDRL_TRY(done_side(side));
-    }
-    CDRL_TRY(join_side_at(st, ev_join_));
-    if (aux_pending_) {
-        CDRL_HIP(hipStreamWaitEvent(st, ev_aux_done_, 0));
-        aux_pending_ = false;
-    }
-    for (int i = 0; i < NSLOT; ++i) slot_used_[i] = false;
-    for (int i = 0; i < NQ; ++i) q_used_[i] = false;
-    return 0;
-}
+static const int g_diag_skip_aux = cdrl_getenv("CDRL_DIAG_SKIP_AUX") ? atoi(cdrl_getenv("CDRL_DIAG_SKIP_AUX")) : 0;   // timing diagnostics only (wrong results)
 
 int64_t Learner::tr_offset(int model) const {
     switch (model) {
@@ -644,8 +423,8 @@ bool Learner::add_bn(std::vector<Op>& ops, const BnRec& bn, const BnOp& o) {
         CDRL_TRY(bn_bwd_finalize(sc->part, nb, G, Mg, C, bn.stats, bn.gamma.g, bn.beta.g, bn.coef, st));
         if (apply_by_conv) return 0;    // applied by the backward GEMMs of the conv in front on load
         if (o.dx) return bn_bwd_apply(dsrc, dsh, x, G, Mg, C, bn.stats, bn.coef, act, o.dx, sc->part2, st, nullptr, bc, at);
-        CDRL_TRY(next_slot(st));       // tower: dy + db partials go to a rotating scratch slot
-        return bn_bwd_apply(dsrc, dsh, x, G, Mg, C, bn.stats, bn.coef, act, dys_[slot_], part2s_[slot_], st, nullptr, bc, at);
+        CDRL_TRY(sched_.next_slot(st));       // tower: dy + db partials go to a rotating scratch slot
+        return bn_bwd_apply(dsrc, dsh, x, G, Mg, C, bn.stats, bn.coef, act, dys_[sched_.slot()], part2s_[sched_.slot()], st, nullptr, bc, at);
     };
     ops.push_back(op);
     return false;
@@ -780,10 +559,10 @@ std::function<int(hipStream_t)> Learner::pw_bwd_fused_op(const PwEmit& e) {
     Scratch* o_scr = e.bn_out.scr;
     return [=](hipStream_t st) -> int {
         PwBwdFused f = f0;
-        if (f.dz.ld) CDRL_TRY(next_slot(st));
-        else f.dz = make_view(dys_[slot_], f.N);
-        CDRL_TRY(next_q(st));
-        const int qi = qi_;
+        if (f.dz.ld) CDRL_TRY(sched_.next_slot(st));
+        else f.dz = make_view(dys_[sched_.slot()], f.N);
+        CDRL_TRY(sched_.next_q(st));
+        const int qi = sched_.q();
         f.qpart = qparts_[qi];
         f.dbpart = dbparts_[qi];
         if (fin) {
@@ -794,11 +573,11 @@ std::function<int(hipStream_t)> Learner::pw_bwd_fused_op(const PwEmit& e) {
         // the reduce also finalizes the BatchNorm in front of the conv (its coefficients are the next kernel's input): critical
         // stream; without one it only produces weight gradients -> side stream, flushed once per unit
         if (on_main) return pw_bwd_fused_reduce(f, st);
-        CDRL_TRY(defer_side(st, [=](hipStream_t sd) -> int {
+        CDRL_TRY(sched_.defer_side(st, [=](hipStream_t sd) -> int {
             CDRL_TRY(pw_bwd_fused_reduce(f, sd));
-            return release_q(qi, sd);
+            return sched_.release_q(qi, sd);
         }));
-        return flush_side(st);
+        return sched_.flush_side(st);
     };
 }
 
@@ -815,20 +594,20 @@ std::function<int(hipStream_t)> Learner::pw_bwd_prologue_op(const PwEmit& e) {
     const float* wpb = e.wpb;
     const void* wpx = e.wpx;
     return [=](hipStream_t st) -> int {
-        if (dz0.ld) CDRL_TRY(next_slot(st));
-        const View dz = dz0.ld ? dz0 : make_view(dys_[slot_], Cout);
-        hipStream_t side = fork_side(st);
-        CDRL_TRY(gemm_tn(in, dz, w.g, rows, Cout, Cin, tns_[slot_], 0, side, G, pro_stats, &tb, bfc, at));
-        CDRL_TRY(done_side(side));
-        PwBnBwd pb{tb.y, tb.stats, tb.coef, tb.shuffle_ctot, tb.act, part2s_[slot_]};
+        if (dz0.ld) CDRL_TRY(sched_.next_slot(st));
+        const View dz = dz0.ld ? dz0 : make_view(dys_[sched_.slot()], Cout);
+        hipStream_t side = sched_.fork_side(st);
+        CDRL_TRY(gemm_tn(in, dz, w.g, rows, Cout, Cin, tns_[sched_.slot()], 0, side, G, pro_stats, &tb, bfc, at));
+        CDRL_TRY(sched_.done_side(side));
+        PwBnBwd pb{tb.y, tb.stats, tb.coef, tb.shuffle_ctot, tb.act, part2s_[sched_.slot()]};
         if (wide)
             CDRL_TRY(pw_x3_wide_bwd(dz, pb, wpx, din, din_acc, G, Mg, Cin, Cout, bwd_ey, pro_stats, bn_in ? sc->part : nullptr, st));
         else
             CDRL_TRY(pw_nn(dz, nullptr, w.p, 1, Cout, nullptr, din, din_acc, G, Mg, Cin, Cout, bn_in ? 2 : 0, bwd_ey, pro_stats, sc->part, st, &pb,
                            wpb, bfc, at));
         // bias gradient = column sums of the (virtual) dy, reduced from the GEMM's partials: rides on the next fork
-        double* p2 = part2s_[slot_];
-        return defer_side(st, [=](hipStream_t sd) -> int { return reduce_partials(p2, G * nb, Cout, Cout, b.g, 0, sd); });
+        double* p2 = part2s_[sched_.slot()];
+        return sched_.defer_side(st, [=](hipStream_t sd) -> int { return reduce_partials(p2, G * nb, Cout, Cout, b.g, 0, sd); });
     };
 }
 
@@ -845,12 +624,12 @@ std::function<int(hipStream_t)> Learner::pw_bwd_plain_op(const PwEmit& e) {
     const float* wpb = e.wpb;
     const void* g3b = e.g3b;
     return [=](hipStream_t st) -> int {
-        const View dy = make_view(dys_[slot_], Cout);
+        const View dy = make_view(dys_[sched_.slot()], Cout);
         // side stream: bias gradient (column sums of dy, reduced per block by bn_bwd_apply) + filter gradient
-        hipStream_t side = fork_side(st);
-        CDRL_TRY(reduce_partials(part2s_[slot_], o_rows, Cout, Cout, b.g, 0, side));
-        CDRL_TRY(gemm_tn(in, dy, w.g, rows, Cout, Cin, tns_[slot_], 0, side, tn_groups, pro_stats, nullptr, bfc, at));
-        CDRL_TRY(done_side(side));
+        hipStream_t side = sched_.fork_side(st);
+        CDRL_TRY(reduce_partials(part2s_[sched_.slot()], o_rows, Cout, Cout, b.g, 0, side));
+        CDRL_TRY(gemm_tn(in, dy, w.g, rows, Cout, Cin, tns_[sched_.slot()], 0, side, tn_groups, pro_stats, nullptr, bfc, at));
+        CDRL_TRY(sched_.done_side(side));
         // main stream: the critical path to the previous layer
         if (!din.p) return 0;
         if (dgrad == PwGemm::PwNN)
@@ -875,10 +654,10 @@ void Learner::add_dw(std::vector<Op>& ops, const std::string& prefix, View in, i
     Op op;
     op.fwd = [=](hipStream_t st, int) -> int { return dw_fwd(in, w.p, b.p, y, N, H, W, C, stride, st); };
     op.bwd = [=](hipStream_t st) -> int {
-        float* dy = dys_[slot_];
-        hipStream_t side = fork_side(st);
-        CDRL_TRY(dw_bwd_filter(in, dy, w.g, b.g, N, H, W, C, stride, fparts_[slot_], side));
-        CDRL_TRY(done_side(side));
+        float* dy = dys_[sched_.slot()];
+        hipStream_t side = sched_.fork_side(st);
+        CDRL_TRY(dw_bwd_filter(in, dy, w.g, b.g, N, H, W, C, stride, fparts_[sched_.slot()], side));
+        CDRL_TRY(sched_.done_side(side));
         if (fuse)      // bwd-data + BN-backward sums of the layer that produced `in` in one pass over da
             return dw_bwd_data_bnreduce(dy, w.p, din, N, H, W, C, stride, pre_G, pre_y, pre_stats, pre_act, scr_main_.part, st);
         return dw_bwd_data(dy, w.p, din, N, H, W, C, stride, din_acc, st);
@@ -923,10 +702,10 @@ Learner::BnRec Learner::add_dw_block(std::vector<Op>& ops, const DwBlock& d) {
             if (pre_fin_by_conv) return 0;                 // folded by the fused backward of the 1x1 conv in front (finalize on load)
             CDRL_TRY(bn_bwd_finalize(sc->part, nbb, G, Mi, C, d.pre.stats, d.pre.gamma.g, d.pre.beta.g, d.pre.coef, st));
             if (pre_apply_by_conv) return 0;               // the 1x1 conv in front applies it on load
-            const float* dz = dys_[slot_];                 // masked gradient left there by the depthwise op
-            CDRL_TRY(next_slot(st));
-            return bn_bwd_apply(make_view(const_cast<float*>(dz), C), 0, xv, G, Mi, C, d.pre.stats, d.pre.coef, ACT_NONE, dys_[slot_],
-                                part2s_[slot_], st, nullptr, 0, at);
+            const float* dz = dys_[sched_.slot()];                 // masked gradient left there by the depthwise op
+            CDRL_TRY(sched_.next_slot(st));
+            return bn_bwd_apply(make_view(const_cast<float*>(dz), C), 0, xv, G, Mi, C, d.pre.stats, d.pre.coef, ACT_NONE, dys_[sched_.slot()],
+                                part2s_[sched_.slot()], st, nullptr, 0, at);
         };
         ops.push_back(op);
     }
@@ -936,11 +715,11 @@ Learner::BnRec Learner::add_dw_block(std::vector<Op>& ops, const DwBlock& d) {
             return dwf_fwd(x, d.pre.stats, w.p, b.p, y2, sc->part, G, B, H, W, C, stride, st, at);
         };
         op.bwd = [=](hipStream_t st) -> int {
-            CDRL_TRY(next_slot(st));
-            double* pw = fparts_[slot_];
-            const View dx = pre ? make_view(dys_[slot_], C) : din;
+            CDRL_TRY(sched_.next_slot(st));
+            double* pw = fparts_[sched_.slot()];
+            const View dx = pre ? make_view(dys_[sched_.slot()], C) : din;
             CDRL_TRY(dwf_bwd(x, d.pre.stats, dout.p, y2, post.stats, post.coef, w.p, dx, sc->part, pw, G, B, H, W, C, stride, st, at));
-            return defer_side(st, [=](hipStream_t sd) -> int {
+            return sched_.defer_side(st, [=](hipStream_t sd) -> int {
                 return reduce_partials2(pw, G * nbb, 9 * C, C, (int64_t)10 * C, w.g, b.g, 0, sd);
             });
         };
@@ -1055,12 +834,12 @@ void Learner::add_dense(std::vector<Op>& ops, int model, const std::string& pref
         // critical path first, then the weight / bias gradients on the side stream (main-stream layers only)
         if (need_din) CDRL_TRY(gemm_nn(dzv, w.p, 1, N, nullptr, din, M, K, N, din_acc, st, dsk));
         if (sc == &scr_main_) {
-            CDRL_TRY(next_slot(st));
-            hipStream_t side = fork_side(st);
-            CDRL_TRY(colsum(dzv, M, N, part2s_[slot_], side));
-            CDRL_TRY(reduce_partials(part2s_[slot_], nb, N, N, b.g, 0, side));
-            CDRL_TRY(gemm_tn(in, dzv, w.g, M, N, K, tns_[slot_], 0, side));
-            return done_side(side);
+            CDRL_TRY(sched_.next_slot(st));
+            hipStream_t side = sched_.fork_side(st);
+            CDRL_TRY(colsum(dzv, M, N, part2s_[sched_.slot()], side));
+            CDRL_TRY(reduce_partials(part2s_[sched_.slot()], nb, N, N, b.g, 0, side));
+            CDRL_TRY(gemm_tn(in, dzv, w.g, M, N, K, tns_[sched_.slot()], 0, side));
+            return sched_.done_side(side);
         }
         CDRL_TRY(colsum(dzv, M, N, sc->part, st));
         CDRL_TRY(reduce_partials(sc->part, nb, N, N, b.g, 0, st));
@@ -1127,10 +906,10 @@ void Learner::add_gru(std::vector<Op>& ops, const std::string& name, Tens& x, in
         double* part = sc->part;
         const bool on_side = sc == &scr_main_;
         if (on_side) {
-            CDRL_TRY(next_slot(st));
-            ws = fork_side(st);
-            tn = tns_[slot_];
-            part = part2s_[slot_];
+            CDRL_TRY(sched_.next_slot(st));
+            ws = sched_.fork_side(st);
+            tn = tns_[sched_.slot()];
+            part = part2s_[sched_.slot()];
         }
         CDRL_TRY(gemm_tn(xv, make_view(dXP, U3), Kp.g, T * B, U3, In, tn, 0, ws));
         CDRL_TRY(colsum(make_view(dXP, U3), T * B, U3, part, ws));
@@ -1138,7 +917,7 @@ void Learner::add_gru(std::vector<Op>& ops, const std::string& name, Tens& x, in
         CDRL_TRY(gemm_tn(make_view(Hs, u), make_view(dHP, U3), Rp.g, T * B, U3, u, tn, 0, ws));
         CDRL_TRY(colsum(make_view(dHP, U3), T * B, U3, part, ws));
         CDRL_TRY(reduce_partials(part, nbc, U3, U3, bp.g + U3, 0, ws));
-        if (on_side) CDRL_TRY(done_side(ws));
+        if (on_side) CDRL_TRY(sched_.done_side(ws));
         return 0;
     };
     ops.push_back(op);
@@ -1150,16 +929,12 @@ void Learner::add_gru(std::vector<Op>& ops, const std::string& name, Tens& x, in
 // gradient of the concat exists and run under the tower's backward.
 void Learner::add_aux_fork(std::vector<Op>& ops) {
     Op op;
-    static const int diag_skip_aux = cdrl_getenv("CDRL_DIAG_SKIP_AUX") ? atoi(cdrl_getenv("CDRL_DIAG_SKIP_AUX")) : 0;     // timing diagnostics only (wrong results)
     op.fwd = [=](hipStream_t st, int training) -> int {
-        if (diag_skip_aux & 1) return 0;
-        if (!side_enabled_) return run_fwd(aux_ops_, st, training);
-        hipEvent_t evf = nullptr;
-        CDRL_TRY(mark_stream(st, ev_aux_fork_, &evf));        // parameters / inputs produced on the main stream
-        CDRL_HIP(hipStreamWaitEvent(aux_, evf, 0));
-        CDRL_TRY(run_fwd(aux_ops_, aux_, training));
-        CDRL_HIP(hipEventRecord(ev_aux_done_, aux_));
-        return 0;
+        if (g_diag_skip_aux & 1) return 0;
+        if (!sched_.side_on()) return run_fwd(aux_ops_, st, training);
+        CDRL_TRY(sched_.fork_aux(st));        // parameters / inputs produced on the main stream
+        CDRL_TRY(run_fwd(aux_ops_, sched_.aux(), training));
+        return sched_.done_aux();
     };
     op.bwd = [](hipStream_t) -> int { return 0; };
     ops.push_back(op);
@@ -1168,22 +943,15 @@ void Learner::add_aux_fork(std::vector<Op>& ops) {
 void Learner::add_aux_join(std::vector<Op>& ops) {
     Op op;
     op.fwd = [=](hipStream_t st, int) -> int {
-        if (side_enabled_) CDRL_HIP(hipStreamWaitEvent(st, ev_aux_done_, 0));
-        return 0;
+        return sched_.join_aux(st);
     };
-    static const int diag_skip_aux = cdrl_getenv("CDRL_DIAG_SKIP_AUX") ? atoi(cdrl_getenv("CDRL_DIAG_SKIP_AUX")) : 0;     // timing diagnostics only (wrong results)
     op.bwd = [=](hipStream_t st) -> int {
-        if (diag_skip_aux & 2) return 0;
-        if (!side_enabled_) return run_bwd(aux_ops_, st);
-        // Own stream: ~90 tiny dependent kernels (0.8 ms).  On the filter-gradient side stream they blocked, in stream
-        // order, the slot events the main stream waits on (measured: a 0.84 ms hole in the critical stream per pass).
-        hipEvent_t evf = nullptr;
-        CDRL_TRY(mark_stream(st, ev_aux_fork_, &evf));        // gradient of the concat is ready
-        aux_pending_ = true;                                  // joined by join_side() at the end of the backward
-        CDRL_HIP(hipStreamWaitEvent(aux_, evf, 0));
-        CDRL_TRY(run_bwd(aux_ops_, aux_));
-        CDRL_HIP(hipEventRecord(ev_aux_done_, aux_));
-        return 0;
+        if (g_diag_skip_aux & 2) return 0;
+        if (!sched_.side_on()) return run_bwd(aux_ops_, st);
+        // the aux stream, not the side stream; joined by join_side() at the end of the backward
+        CDRL_TRY(sched_.fork_aux(st));        // gradient of the concat is ready
+        CDRL_TRY(run_bwd(aux_ops_, sched_.aux()));
+        return sched_.done_aux();
     };
     ops.push_back(op);
 }
@@ -1256,18 +1024,18 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         note_named("img.stem.pool.out.g", pool.g, (size_t)N * Hp0 * Wp0 * Cs * esz());
         op.bwd = [=](hipStream_t st) -> int {
             if (stem_fused) {
-                CDRL_TRY(next_slot(st));
+                CDRL_TRY(sched_.next_slot(st));
                 // the last kernel of the backward, on the critical stream: nothing is left there to run beside it, so a hand-over to the
                 // side stream and back would only cost its two event bubbles (rounds 1-4 ran it on the side stream)
                 PoolSrc ps = make_pool_src(argmax, pool.g, Hs, Ws);
                 static const bool diag_skip = cdrl_getenv("CDRL_DIAG_SKIP_STEMF") && atoi(cdrl_getenv("CDRL_DIAG_SKIP_STEMF")) == 1;    // timing diagnostics only (no stem filter gradient)
                 if (!diag_skip)
-                    CDRL_TRY(stem_bwd_filter_fused(in_image_, ps, y.p, stem_stats, stem_coef, w.g, b.g, B, T, H, W, Cs, fparts_[slot_], st, at));
+                    CDRL_TRY(stem_bwd_filter_fused(in_image_, ps, y.p, stem_stats, stem_coef, w.g, b.g, B, T, H, W, Cs, fparts_[sched_.slot()], st, at));
                 return 0;
             }
-            hipStream_t side = fork_side(st);
-            CDRL_TRY(stem_bwd_filter(in_image_, dys_[slot_], w.g, b.g, B, T, H, W, Cs, fparts_[slot_], side));
-            return done_side(side);
+            hipStream_t side = sched_.fork_side(st);
+            CDRL_TRY(stem_bwd_filter(in_image_, dys_[sched_.slot()], w.g, b.g, B, T, H, W, Cs, fparts_[sched_.slot()], side));
+            return sched_.done_side(side);
         };
         ops.push_back(op);
         // stem BN + ReLU6 + max-pool as one fused block: the BN op only produces statistics in the forward
@@ -1299,8 +1067,8 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                 }
                 CDRL_TRY(bn_bwd_reduce(none, 0, yv, G, Mg, C, stats, ACT_RELU6, scr_main_.part, st, &ps));
                 CDRL_TRY(bn_bwd_finalize(scr_main_.part, nb, G, Mg, C, stats, gamma.g, beta.g, coef, st));
-                CDRL_TRY(next_slot(st));
-                return bn_bwd_apply(none, 0, yv, G, Mg, C, stats, coef, ACT_RELU6, dys_[slot_], part2s_[slot_], st, &ps);
+                CDRL_TRY(sched_.next_slot(st));
+                return bn_bwd_apply(none, 0, yv, G, Mg, C, stats, coef, ACT_RELU6, dys_[sched_.slot()], part2s_[sched_.slot()], st, &ps);
             };
             ops.push_back(bn);
         }
@@ -1329,13 +1097,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                 const int sc_ev = s;
                 if (sc_overlap) {
                     Op fk;
-                    fk.fwd = [=](hipStream_t st, int) -> int {
-                        if (!side_enabled_) return 0;
-                        hipEvent_t evf = nullptr;
-                        CDRL_TRY(mark_stream(st, ev_sc_fork_[sc_ev], &evf));
-                        CDRL_HIP(hipStreamWaitEvent(side_, evf, 0));
-                        return 0;
-                    };
+                    fk.fwd = [=](hipStream_t st, int) -> int { return sched_.fork_shortcut(st, sc_ev); };
                     fk.bwd = [](hipStream_t) -> int { return 0; };
                     ops.push_back(fk);
                 }
@@ -1402,13 +1164,10 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                         build_scr_ = &scr_main_;
                         for (size_t i = sc_begin; i < ops.size(); ++i) {        // forward of the shortcut ops -> side stream
                             auto f = ops[i].fwd;
-                            ops[i].fwd = [=](hipStream_t st, int training) -> int { return f(side_enabled_ ? side_ : st, training); };
+                            ops[i].fwd = [=](hipStream_t st, int training) -> int { return f(sched_.side_on() ? sched_.side() : st, training); };
                         }
                         Op jn;
-                        jn.fwd = [=](hipStream_t st, int) -> int {
-                            if (!side_enabled_) return 0;
-                            return join_side_at(st, ev_sc_done_[sc_ev]);
-                        };
+                        jn.fwd = [=](hipStream_t st, int) -> int { return sched_.join_shortcut(st, sc_ev); };
                         jn.bwd = [](hipStream_t) -> int { return 0; };
                         ops.push_back(jn);
                     }
@@ -1474,20 +1233,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
         // the caller's communication stream (DataParallelLearner: early all-reduce bucket under the tower's backward)
         Op mark;
         mark.fwd = [](hipStream_t, int) -> int { return 0; };
-        mark.bwd = [=](hipStream_t st) -> int {
-            // under hipGraph capture the external communication stream must not be pulled into the capture (it would never be
-            // joined, and a replay would never release it): the caller falls back to the single post-pass all-reduce
-            if (!comm_ || graphs_enabled_) return 0;
-            CDRL_HIP(hipEventRecord(ev_tail_main_, st));          // (recorded, with its system-scope fence: the collectives read these bytes)
-            CDRL_HIP(hipStreamWaitEvent(comm_, ev_tail_main_, 0));
-            if (side_enabled_) {
-                CDRL_TRY(flush_side(st));       // (queued side jobs go out BEHIND an event of the critical stream, as everywhere else)
-                CDRL_HIP(hipEventRecord(ev_tail_side_, side_));
-                CDRL_HIP(hipStreamWaitEvent(comm_, ev_tail_side_, 0));
-                if (aux_pending_) CDRL_HIP(hipStreamWaitEvent(comm_, ev_aux_done_, 0));
-            }
-            return 0;
-        };
+        mark.bwd = [=](hipStream_t st) -> int { return sched_.publish_tail(st); };
         ops.push_back(mark);
     }
     add_gru(ops, "gru_image", feat_, c.last, c.rnn_image, cat.v(0), cat.gv(0), true);
@@ -1758,65 +1504,7 @@ int Learner::bind(const Buffers& b) {
         CDRL_LAUNCH_CHECK();
         CDRL_HIP(hipDeviceSynchronize());
     }
-    if (!side_) {
-        const char* env = cdrl_getenv("CDRL_SIDE_STREAM");
-        side_enabled_ = !(env && atoi(env) == 0);
-        // hipGraph replay is OFF by default: measured on MI355X / ROCm 7.2 at B=256 the captured update-step
-        // (4 graphs of ~500-1000 kernel nodes over two streams) replays in 32.7 ms vs 31.0 ms eager, and the
-        // host still spends 15 ms per step inside hipGraphLaunch (22 ms for eager launches): neither mode is
-        // host-bound.  CDRL_GRAPH=1 enables it (parity suite passes in both modes).
-        const char* genv = cdrl_getenv("CDRL_GRAPH");
-        graphs_enabled_ = genv && atoi(genv) != 0;
-        // All three streams at the default priority.  Giving the main stream (the dependent chain) the highest and the side /
-        // aux streams the lowest priority (measured in round 2) changes nothing for the update-step (15.98 vs 16.01 ms) but costs
-        // rollout inference 4.4 ms per call: whenever the high-priority queue sits on a barrier that waits for a kernel of a
-        // low-priority queue (the small-modality nets on the aux stream: at 1..128 environments the main stream reaches the join
-        // first), the command processor comes back to the low-priority queue only after milliseconds -- predict() 5.5 ms instead
-        // of 1.1 ms at E = 1 (tools/bench_rollout_rows.py).
-        const int prio_lo = 0, prio_hi = 0;
-        CDRL_HIP(hipStreamCreateWithPriority(&main_, hipStreamNonBlocking, prio_hi));
-        // Events between the engine's own streams carry no system-scope fence (hipEventDisableSystemFence): the marker packet of a default
-        // event writes the L2 back and invalidates it, in the middle of the critical stream.  The events that hand over to the communication
-        // stream (collectives: other devices read what they cover) keep it.  CDRL_EVENT_FENCE=1 -> default events everywhere (rounds 1-5).
-        const char* fe = cdrl_getenv("CDRL_EVENT_FENCE");
-        const unsigned evf_int = hipEventDisableTiming | ((fe && atoi(fe) == 1) ? 0u : (unsigned)hipEventDisableSystemFence);
-        CDRL_HIP(hipEventCreateWithFlags(&ev_in_, evf_int));      // (caller's stream: same device; what the host reads afterwards goes through a copy with its own fences)
-        CDRL_HIP(hipEventCreateWithFlags(&ev_out_, evf_int));
-        CDRL_HIP(hipEventCreateWithFlags(&ev_out_sys_, hipEventDisableTiming));
-        CDRL_HIP(hipEventCreateWithFlags(&ev_in_sys_, hipEventDisableTiming));
-        CDRL_HIP(hipStreamCreateWithPriority(&side_, hipStreamNonBlocking, prio_lo));
-        for (int i = 0; i < NSLOT; ++i) {
-            CDRL_HIP(hipEventCreateWithFlags(&ev_main_[i], evf_int));
-            CDRL_HIP(hipEventCreateWithFlags(&ev_side_[i], evf_int));
-        }
-        CDRL_HIP(hipEventCreateWithFlags(&ev_join_, evf_int));
-        for (int i = 0; i < NQ; ++i) CDRL_HIP(hipEventCreateWithFlags(&ev_q_[i], evf_int));
-        {
-            // CDRL_SIDE_LAG=-1 -> every claim of a scratch slot waits for its own event (rounds 1-5); n >= 0: see wait_side_record
-            const char* le = cdrl_getenv("CDRL_SIDE_LAG");
-            side_lag_ = le ? atoi(le) : 4;
-        }
-        {
-            // CDRL_TAIL_EVENTS=0 -> forks by hipEventRecord on the critical stream (rounds 1-5)
-            const char* te = cdrl_getenv("CDRL_TAIL_EVENTS");
-            const bool tail_on = !(te && atoi(te) == 0) && !graphs_enabled_;
-            tail_.stream = main_;
-            tail_.n = 0;
-            if (tail_on) {
-                for (int i = 0; i < 32; ++i) CDRL_HIP(hipEventCreateWithFlags(&tail_.ring[i], evf_int));
-                tail_.n = 32;
-            }
-        }
-        CDRL_HIP(hipEventCreateWithFlags(&ev_tail_main_, hipEventDisableTiming));
-        CDRL_HIP(hipEventCreateWithFlags(&ev_tail_side_, hipEventDisableTiming));
-        for (int i = 0; i < 3; ++i) {
-            CDRL_HIP(hipEventCreateWithFlags(&ev_sc_fork_[i], evf_int));
-            CDRL_HIP(hipEventCreateWithFlags(&ev_sc_done_[i], evf_int));
-        }
-        CDRL_HIP(hipStreamCreateWithPriority(&aux_, hipStreamNonBlocking, prio_lo));
-        CDRL_HIP(hipEventCreateWithFlags(&ev_aux_fork_, evf_int));
-        CDRL_HIP(hipEventCreateWithFlags(&ev_aux_done_, evf_int));
-    }
+    if (!sched_.created()) CDRL_TRY(sched_.create());
     if (!hp_stage_) CDRL_HIP(hipHostMalloc(reinterpret_cast<void**>(&hp_stage_), sizeof(DevHP) + sizeof(float), 0));
     CDRL_HIP(hipMemcpy(hp_dev_, &hp_host_, sizeof(DevHP), hipMemcpyHostToDevice));
     if (gate_dev_) CDRL_HIP(hipMemcpy(gate_dev_, &gate_host_, sizeof(GateBlock), hipMemcpyHostToDevice));
@@ -2060,10 +1748,10 @@ int Learner::trunk_backward_tail(hipStream_t st) {
     // into the trunk's output gradient.  That write has no consumer here, but up to 2048 rows it comes out of the same launch that
     // produces the BatchNorm's dgamma / dbeta (bn_small_bwd, one launch per direction): it stays, and the head gradients are those of
     // a full pass.
-    if (frozen()) return join_side(st);
+    if (frozen()) return sched_.join_side(st);
     if (!packs_have_wt_) CDRL_TRY(transpose_many(d_pwt_, (int)h_pwt_.size(), pwt_tiles_, st));      // W^T of the pointwise convs (normally packed with the forward's operands)
     CDRL_TRY(run_bwd(trunk_ops_, st));
-    return join_side(st);
+    return sched_.join_side(st);
 }
 
 int Learner::joint_refused() {
@@ -2088,7 +1776,7 @@ int Learner::repr_refused() {
 int Learner::run_pass(const PassSpec& s, hipStream_t caller, bool fwd, bool bwd) {
     if (s.joint()) CDRL_TRY(joint_refused());
     if (s.repr) CDRL_TRY(repr_refused());
-    if (s.inv_world != 1.0f) dp_hint_ = true;
+    if (s.inv_world != 1.0f) sched_.note_scaled_pass();
     // one half alone (the split form) is eager; so is re-sampling: (seed, offset) are kernel arguments that change every call
     const bool graphable = fwd && bwd && !s.resample;
     std::vector<uint64_t> key;
