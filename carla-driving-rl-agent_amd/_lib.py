@@ -119,6 +119,7 @@ PROTOTYPES = {
     'cdrl_learner_share_hparams': (_i, [_L, _L]),
     'cdrl_learner_set_comm_stream': (_i, [_L, _fp]),
     'cdrl_learner_tail_offset': (_i64, [_L]),
+    'cdrl_learner_pw_signatures': (_i, [_L, C.c_char_p, _i]),
     'cdrl_learner_reset_optimizer_steps': (_i, [_L, _fp]),
     'cdrl_learner_get_optimizer_state': (_i, [_L, C.POINTER(OptimizerState), _fp]),
     'cdrl_learner_set_optimizer_state': (_i, [_L, C.POINTER(OptimizerState), _fp]),
@@ -238,6 +239,10 @@ PROTOTYPES = {
     'cdrl_reduce_partials_plan': (_i, [C.c_uint64, _i, _i64, _i64, C.POINTER(C.c_int32), _i]),
     'cdrl_reduce_partials_f32': (_i, [_fp, _i, _i64, _i64, _fp, _i, _fp]),
     'cdrl_gemm_nn_plan': (_i, [_V, C.c_uint64, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i]),
+    'cdrl_pwconv_plan': (_i, [_V, _V, C.c_uint64] + [_i] * 11 + [C.POINTER(C.c_int32), _i]),
+    'cdrl_pwconv_ex': (_i, [_V, _fp, _fp, _fp, _i, _i, _fp, _fp, _i, _i, _fp, _V] + [_i] * 6 + [_fp] * 4 + [_i, _i, _fp]),
+    'cdrl_pwconv_x3_plan': (_i, [_V, _V] + [_i] * 8 + [C.POINTER(C.c_int32), _i]),
+    'cdrl_pwconv_x3_wide_bwd_plan': (_i, [_V, _V] + [_i] * 8 + [C.POINTER(C.c_int32), _i]),
     'cdrl_gemm_nn_workspace_elems': (_i64, [_i, _i, _i]),
     'cdrl_gemm_nn_ex': (_i, [_V, _fp, _i, _i, _fp, _V, _i, _i, _i, _i, _fp, _fp, _i, C.POINTER(C.c_int), _fp]),
     'cdrl_act_fwd': (_i, [_fp, _fp, _i64, _i, _fp]),

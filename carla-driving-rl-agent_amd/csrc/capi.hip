@@ -409,6 +409,14 @@ int cdrl_learner_set_comm_stream(cdrl_learner* l, void* stream) {
     return 0;
 }
 
+int cdrl_learner_pw_signatures(const cdrl_learner* l, char* buf, int n) {
+    if (!l || (!buf && n > 0)) return -1;
+    std::string all;
+    for (const std::string& r : l->impl->pw_signatures()) all += r + "\n";
+    if (n > 0) snprintf(buf, (size_t)n, "%s", all.c_str());
+    return (int)all.size() + 1;
+}
+
 int64_t cdrl_learner_tail_offset(const cdrl_learner* l) {
     if (!l) return -1;
     // with hipGraph replay the communication stream is never released mid-pass: no early bucket (everything is "tower")
@@ -1030,7 +1038,7 @@ int cdrl_stem_block_bwd_pooled(const float* x, const float* y, const float* stat
     return stem_bwd_filter_fused(x, ps, y, stats, coef, dw, db, B, T, H, W, Cout, fpart, st, act_type);
 }
 
-int cdrl_pwconv_fused_partial_rows(int G, int Mg, int N, int K) { return pw_nn_plan(G, Mg, N, K).nbpg; }
+int cdrl_pwconv_fused_partial_rows(int G, int Mg, int N, int K) { return pw_nn_shape_plan(G, Mg, N, K).nbpg; }
 
 int cdrl_pwconv_fused(const float* a, int lda, int a_coff, const float* pro_stats, const float* w, int sbk, int sbn,
                       const float* bias, float* c, int ldc, int c_coff, int accumulate, int G, int Mg, int N, int K,
@@ -1068,7 +1076,7 @@ int cdrl_pwconv_fused_packed(const float* a, int lda, int a_coff, const float* p
 static int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
 
 int64_t cdrl_pwconv_bn_bwd_workspace_bytes(int G, int Mg, int N, int K) {
-    const int64_t nbr = vcol_geom(Mg, N).nb, nbp = std::max(pw_nn_plan(G, Mg, K, N).nbpg, pw_x3_wide_bwd_rows(Mg));
+    const int64_t nbr = vcol_geom(Mg, N).nb, nbp = std::max(pw_nn_shape_plan(G, Mg, K, N).nbpg, pw_x3_wide_bwd_rows(Mg));
     return al256((int64_t)G * nbr * 2 * N * 8) + al256((int64_t)G * nbp * N * 8) + al256(gemm_tn_part_elems(G * Mg, N, K, G) * 4);
 }
 
@@ -1079,21 +1087,22 @@ static int pwconv_bn_bwd_impl(const float* dout, int dout_ld, int dout_coff, int
                               int packed_bf16, int act_type, void* stream) {
     hipStream_t st = S(stream);
     const int act = relu6 ? ACT_RELU6 : ACT_NONE;
-    const int nbr = vcol_geom(Mg, N).nb, nbp = pw_nn_plan(G, Mg, K, N).nbpg;
+    View vd = make_view(const_cast<float*>(dout), dout_ld, dout_coff), vy = make_view(const_cast<float*>(y), N);
+    View vx = make_view(const_cast<float*>(x), x_ld, x_coff);
+    // dx[m,k] = sum_n dy[m,n] W[k,n]: GEMM with "K" = N (reduction over the conv outputs) and "N" = K
+    const View vdx = make_view(dx, dx_ld, dx_coff);
+    const PwX3BwdPlan xb = pw_x3_wide_bwd_plan(vd, vdx, G, Mg, K, N, shuffle_ctot, false, accumulate, true);
+    const int nbr = vcol_geom(Mg, N).nb, nbp = pw_nn_shape_plan(G, Mg, K, N).nbpg;
     char* ws = static_cast<char*>(workspace);
     double* part = reinterpret_cast<double*>(ws);
     ws += al256((int64_t)G * nbr * 2 * N * 8);
     double* part2 = reinterpret_cast<double*>(ws);
-    ws += al256((int64_t)G * std::max(nbp, pw_x3_wide_bwd_rows(Mg)) * N * 8);
+    ws += al256((int64_t)G * std::max(nbp, xb.rows) * N * 8);
     float* tn = reinterpret_cast<float*>(ws);
-    View vd = make_view(const_cast<float*>(dout), dout_ld, dout_coff), vy = make_view(const_cast<float*>(y), N);
-    View vx = make_view(const_cast<float*>(x), x_ld, x_coff);
     CDRL_TRY(bn_bwd_reduce(vd, shuffle_ctot, vy, G, Mg, N, stats, act, part, st, nullptr, nullptr, nullptr, 0, act_type));
     CDRL_TRY(bn_bwd_finalize(part, nbr, G, Mg, N, stats, dgamma, dbeta, coef, st));
     PwBnBwd bb{y, stats, coef, shuffle_ctot, act, part2};
-    // dx[m,k] = sum_n dy[m,n] W[k,n]: GEMM with "K" = N (reduction over the conv outputs) and "N" = K
-    const View vdx = make_view(dx, dx_ld, dx_coff);
-    if (!act_type && !packed_bf16 && pw_x3_wide_bwd_supported(vd, vdx, K, N, shuffle_ctot)) {
+    if (!act_type && !packed_bf16 && xb.ok) {
         // 232-channel shapes, float32: the one-tile-per-workgroup split-precision kernel the engine runs (gemm_pw_x3.hip); the packed
         // operand is built here through a temporary device buffer (test / tooling entry point)
         void* wp = nullptr;
@@ -1106,7 +1115,7 @@ static int pwconv_bn_bwd_impl(const float* dout, int dout_ld, int dout_coff, int
         PwX3Pack e = pw_x3_pack_entry(w, wp, N, K, 1, N);
         int rc = hipMemcpy(d, &e, sizeof(e), hipMemcpyHostToDevice) == hipSuccess ? pw_x3_pack_many(d, 1, st) : -2;
         if (rc == 0) rc = pw_x3_wide_bwd(vd, bb, wp, vdx, accumulate, G, Mg, K, N, nullptr, nullptr, nullptr, st);
-        if (rc == 0) rc = reduce_partials(part2, G * pw_x3_wide_bwd_rows(Mg), N, N, db, 0, st);
+        if (rc == 0) rc = reduce_partials(part2, G * xb.rows, N, N, db, 0, st);
         (void)hipStreamSynchronize(st);
         (void)hipFree(d);
         (void)hipFree(wp);
@@ -1499,6 +1508,59 @@ int cdrl_gemm_nn_plan(const cdrl_view* a, uint64_t b_addr, int sbk, int sbn, int
         ++n;
     }
     return n;
+}
+
+// ---- 1x1-conv forward / backward-data family: the plans pw_nn, pw_x3 and pw_x3_wide_bwd launch from ----
+// fields always written (a refusal shows its code in fields[1]); 0 when the plan is ok, -1 with the refusal sentence otherwise
+static int pw_plan_result(const char* fn, bool views, const int32_t* v, int nf, int ok, const char* why, int32_t* fields, int n_fields) {
+    if (!views || !fields || n_fields != nf) {
+        cdrl::set_error("%s: the views (their pointers may be null) and an array of exactly %d fields are required", fn, nf);
+        return -1;
+    }
+    std::copy(v, v + nf, fields);
+    if (!ok) cdrl::set_error("%s", why);
+    return ok ? 0 : -1;
+}
+
+int cdrl_pwconv_plan(const cdrl_view* a, const cdrl_view* c, uint64_t y_addr, int G, int Mg, int N, int K, int pro, int epi, int accumulate,
+                     int packed, int packed_bf16, int act_type, int has_part, int32_t* fields, int n_fields) {
+    PwNnPlan p{};
+    if (a && c)
+        p = pw_nn_plan(view_of(a), view_of(c), G, Mg, N, K, pro, epi, accumulate, packed != 0, packed_bf16 != 0, act_type, has_part != 0,
+                       reinterpret_cast<const float*>((uintptr_t)y_addr));
+    const int32_t v[] = {p.ok, p.refusal, p.ksm, p.nt, p.pro, p.epi, p.mode, p.acc, p.wc, p.wr, p.bm, p.tiles_g, p.nbpg, p.tpb, p.gx, p.gy, p.occ,
+                         p.lds_bytes, (int32_t)p.packed_elems};
+    return pw_plan_result("cdrl_pwconv_plan", a && c, v, (int)(sizeof(v) / sizeof(v[0])), p.ok, p.why, fields, n_fields);
+}
+
+int cdrl_pwconv_ex(const cdrl_view* a, const float* pro_stats, const float* bwd_y, const float* bwd_coef, int bwd_shuffle, int bwd_relu6,
+                   double* part2, const float* w, int sbk, int sbn, const float* bias, const cdrl_view* c, int accumulate, int G, int Mg, int N,
+                   int K, int epilogue, const float* epi_y, const float* epi_stats, double* part, const float* w_packed, int packed_bf16,
+                   int act_type, void* stream) {
+    if (bad_act_type(act_type)) return -1;
+    if (!a || !c || !a->p || !c->p || !w || bwd_shuffle < 0 || (bwd_y && (!pro_stats || !bwd_coef)) || (epilogue == 2 && (!epi_y || !epi_stats))) {
+        cdrl::set_error("cdrl_pwconv_ex: null tensor, a BatchNorm-backward prologue without its stats / coef, or epilogue 2 without epi_y / epi_stats");
+        return -1;
+    }
+    const PwBnBwd bb{bwd_y, pro_stats, bwd_coef, bwd_shuffle, bwd_relu6 ? ACT_RELU6 : ACT_NONE, part2};
+    return pw_nn(view_of(a), bwd_y ? nullptr : pro_stats, w, sbk, sbn, bias, view_of(c), accumulate, G, Mg, N, K, epilogue, epi_y, epi_stats, part,
+                 S(stream), bwd_y ? &bb : nullptr, w_packed, packed_bf16 != 0, act_type);
+}
+
+int cdrl_pwconv_x3_plan(const cdrl_view* a, const cdrl_view* c, int G, int Mg, int N, int K, int pro, int epi, int packed, int nbpg,
+                        int32_t* fields, int n_fields) {
+    PwX3Plan p{};
+    if (a && c) p = pw_x3_plan(view_of(a), view_of(c), G, Mg, N, K, pro != 0, epi != 0, packed != 0, nbpg);
+    const int32_t v[] = {p.ok, p.refusal, p.form, p.kp, p.nt, p.pro, p.epi, p.bm, p.tiles_g, p.nbpg, p.gx, p.gy, (int32_t)p.packed_bytes};
+    return pw_plan_result("cdrl_pwconv_x3_plan", a && c, v, (int)(sizeof(v) / sizeof(v[0])), p.ok, p.why, fields, n_fields);
+}
+
+int cdrl_pwconv_x3_wide_bwd_plan(const cdrl_view* dz, const cdrl_view* c, int G, int Mg, int N, int K, int dz_shuffle, int epi, int accumulate,
+                                 int operands, int32_t* fields, int n_fields) {
+    PwX3BwdPlan p{};
+    if (dz && c) p = pw_x3_wide_bwd_plan(view_of(dz), view_of(c), G, Mg, N, K, dz_shuffle, epi != 0, accumulate, operands != 0);
+    const int32_t v[] = {p.ok, p.refusal, p.sh, p.epi, p.acc, p.rows, p.gx, p.gy};
+    return pw_plan_result("cdrl_pwconv_x3_wide_bwd_plan", dz && c, v, (int)(sizeof(v) / sizeof(v[0])), p.ok, p.why, fields, n_fields);
 }
 
 int64_t cdrl_gemm_nn_workspace_elems(int M, int N, int K) {

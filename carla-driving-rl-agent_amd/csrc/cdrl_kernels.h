@@ -172,8 +172,32 @@ int gemm_tn_lds(const TnPlan& p, View A, View D, float* Cout, int M, int N, int 
 //   pro_stats != null : A <- scale[g][k]*A + shift[g][k]  (BatchNorm apply of the previous layer)
 //   epilogue 1        : part[g][b][2][N] = (sum c, sum c^2)            -> bn_finalize(part, nb = pw_nn_plan().nbpg)
 //   epilogue 2        : part[g][b][2][N] = (sum c, sum c*xhat(ey))     -> bn_bwd_finalize(part, nb = ...nbpg)
-struct PwPlan {
-    int bm, tpb, nbpg;     // rows per tile, tiles per workgroup, workgroups (= partial rows) per group
+// What pw_nn launches for a call and why it refuses one: the ONE place that knows the column-tile count (N > 128: four tiles per
+// block and gy = 2), the K padding, which (ksm, nt) pairs are instantiated (nt == 3 needs ksm <= 32, ksm == 128 needs nt == 4), the
+// row split, the grid and the dynamic LDS size.  Address arithmetic only: launches nothing, reads no memory.  The geometry fields
+// are filled whenever G, Mg, N >= 1, also for a refused call (the partial-row queries read them).  DESIGN.md 3.9.
+enum PwRefusal {
+    PW_OK = 0,
+    PW_REFUSE_DIMS = 1,         // G < 1, Mg < 1, N < 1 or K < 2: nothing to launch
+    PW_REFUSE_SHAPE = 2,        // K or N above 256, K odd
+    PW_REFUSE_TILE = 3,         // a (ksm, nt) pair that is not instantiated
+    PW_REFUSE_ALIGN = 4,        // odd leading dimension / channel offset, pointer not 8-byte aligned
+    PW_REFUSE_PRO_EPI = 5,      // prologue / epilogue outside 0..2, or the pairs (1, 2) and (2, 1)
+    PW_REFUSE_PART = 6,         // an epilogue without its partial buffer
+    PW_REFUSE_2GB = 7,          // an operand of 2 GB or more (32-bit buffer offsets)
+    PW_REFUSE_STORAGE = 8,      // bf16 activation storage without packed bf16 weights
+    PW_REFUSE_COUNT = 9,
+};
+struct PwNnPlan {
+    int ok, refusal;
+    int ksm, nt, pro, epi, mode, acc;   // pw_nn_kernel<KSM, NT, PRO, EPI, MODE, ACC>; acc only with epi == 0 (else a run-time read-modify-write)
+    int wc, wr, bm;             // wave columns / rows, rows per tile
+    int tiles_g, nbpg, tpb;     // tiles per group, workgroups (= partial rows) per group, most tiles one workgroup walks
+    int gx, gy;                 // grid
+    int occ;                    // resident workgroups per CU the grid target counts with
+    int lds_bytes;              // dynamic LDS
+    int64_t packed_elems;       // floats of the packed weights (pw_packed_elems)
+    char why[160];              // the refusal in words
 };
 // BatchNorm-backward prologue: A[m,k] = k1*(dz - k2 - xhat*k3), dz = (A view, gathered through the shuffle map when
 // shuffle_ctot != 0) masked by ReLU6 of the BN output when act == ACT_RELU6, xhat from the BN's raw input y [M][K].
@@ -185,8 +209,12 @@ struct PwBnBwd {
     int act;
     double* part2;          // optional [G][nbpg][K]: column sums of the transformed A (bias gradient partials)
 };
-bool pw_nn_supported(View A, int N, int K);
-PwPlan pw_nn_plan(int G, int Mg, int N, int K);
+// A: the operand view -- with the BatchNorm-backward prologue (pro == 2) the dz view, and y = that prologue's raw BatchNorm input
+PwNnPlan pw_nn_plan(View A, View C, int G, int Mg, int N, int K, int pro, int epi, int accumulate, bool packed, bool packed_bf16, int at,
+                    bool has_part, const float* y = nullptr);
+// the shape-only reads of the plan: dense, aligned views, no prologue / epilogue
+inline PwNnPlan pw_nn_shape_plan(int G, int Mg, int N, int K) { return pw_nn_plan(make_view(nullptr, K), make_view(nullptr, N), G, Mg, N, K, 0, 0, 0, false, false, 0, false); }
+inline bool pw_nn_supported(View A, int N, int K) { return pw_nn_plan(A, make_view(nullptr, N), 1, 1, N, K, 0, 0, 0, false, false, 0, false).ok; }
 // Wp (optional): B pre-packed in MFMA fragment order by pw_pack_many (pw_packed_elems(N, K) floats)
 // wp_bf16: Wp holds bf16 fragments (PwPack::bf16) -> bf16-operand variant (both MFMA operands rounded to bf16, float32
 // tensors / accumulation / statistics: the compute mode of configuration 3)
@@ -351,8 +379,30 @@ struct PwX3Pack {
     __bf16* wp;
     int K, N, sbk, sbn, kp;
 };
-bool pw_x3_supported(View A, int N, int K);
-int pw_x3_partial_rows(int G, int Mg, int N, int K);
+// What pw_x3 launches: form 0 the persistent kernel pw_x3_kernel<KP, NT, PRO, EPI> (K, N <= 128), form 1 pw_x3_wide_kernel<PRO, EPI>
+// (K or N above 128: one 32-row tile per workgroup, column blocks of 128, KP = 256).  Alignment per form: both need a 16-byte aligned
+// pointer; form 0 even K / leading dimension / channel offset (16-byte buffer loads need dword alignment only, columns beyond K inside
+// the last chunk are zeroed), form 1 multiples of 4.  form / kp / nt are filled before anything is refused.
+enum PwX3Refusal {
+    PWX3_OK = 0,
+    PWX3_REFUSE_DIMS = 1,       // G < 1, Mg < 1 or N < 1
+    PWX3_REFUSE_SHAPE = 2,      // K below 4 or above 256, N above 256, K odd (form 0) / not a multiple of 4 (form 1)
+    PWX3_REFUSE_ALIGN = 3,
+    PWX3_REFUSE_PACKED = 4,     // no packed weights
+    PWX3_REFUSE_2GB = 5,
+    PWX3_REFUSE_NBPG = 6,       // a caller-supplied workgroup count outside [1, tiles] (form 1: other than tiles)
+    PWX3_REFUSE_COUNT = 7,
+};
+struct PwX3Plan {
+    int ok, refusal;
+    int form, kp, nt, pro, epi;
+    int bm, tiles_g, nbpg;      // nbpg = partial rows per group
+    int gx, gy;
+    int64_t packed_bytes;
+    char why[160];
+};
+PwX3Plan pw_x3_plan(View A, View C, int G, int Mg, int N, int K, bool pro, bool epi, bool packed, int nbpg = 0);
+inline int pw_x3_partial_rows(int G, int Mg, int N, int K) { return pw_x3_plan(make_view(nullptr, K), make_view(nullptr, N), G, Mg, N, K, false, false, true).nbpg; }
 int64_t pw_x3_packed_bytes(int K);                 // N <= 128 (one column block)
 int pw_x3_ksteps(int K);                           // K = 16 steps per plane of that pack
 int64_t pw_x3_packed_bytes_n(int K, int N);        // any N <= 256: column blocks of 128
@@ -360,9 +410,29 @@ PwX3Pack pw_x3_pack_entry(const float* w, void* wp, int K, int N, int sbk, int s
 int pw_x3_pack_many(const PwX3Pack* tab_dev, int n, hipStream_t st);
 // nbpg > 0: workgroups (= partial rows) per group chosen by the caller (the engine keeps pw_nn_plan's count)
 // backward-data of the wide convs (128 < K or N <= 256) with the BatchNorm-backward prologue, one 32-row tile per workgroup: C[M][N] (+)=
-// dy W^T, Wp = pw_x3_pack_entry(W, wp, K, N, 1, K) (B(k = conv output channel, n = conv input channel)); one part2 / part row per tile
-bool pw_x3_wide_bwd_supported(View dz, View C, int N, int K, int shuffle_ctot);
-int pw_x3_wide_bwd_rows(int Mg);
+// dy W^T, Wp = pw_x3_pack_entry(W, wp, K, N, 1, K) (B(k = conv output channel, n = conv input channel)); one part2 / part row per tile.
+// pw_x3_wide_bwd_kernel<SH, EPI, ACC>; N = conv input channels (columns of the output), K = conv output channels (columns of dz / y).
+// Alignment: dz 16-byte aligned with an even leading dimension; dense dz multiples of 4 in leading dimension and offset (one 16-byte
+// load per chunk), shuffled dz an even offset and an even half width (8-byte loads of adjacent source pairs).
+enum PwX3BwdRefusal {
+    PWX3B_OK = 0,
+    PWX3B_REFUSE_DIMS = 1,      // G < 1 or Mg < 1
+    PWX3B_REFUSE_SHAPE = 2,     // neither K nor N above 128, one above 256, K not a multiple of 4
+    PWX3B_REFUSE_ALIGN = 3,
+    PWX3B_REFUSE_OPERANDS = 4,  // packed weights, y, stats or coef missing
+    PWX3B_REFUSE_EPI_ACC = 5,   // epilogue and accumulate are not instantiated together
+    PWX3B_REFUSE_2GB = 6,
+    PWX3B_REFUSE_COUNT = 7,
+};
+struct PwX3BwdPlan {
+    int ok, refusal;
+    int sh, epi, acc;
+    int rows;                   // 32-row tiles per group = part2 / part rows per group
+    int gx, gy;
+    char why[160];
+};
+PwX3BwdPlan pw_x3_wide_bwd_plan(View dz, View C, int G, int Mg, int N, int K, int shuffle_ctot, bool epi, int accumulate, bool operands);
+inline int pw_x3_wide_bwd_rows(int Mg) { return pw_x3_wide_bwd_plan(make_view(nullptr, 4), make_view(nullptr, 4), 1, Mg, 0, 0, 0, false, 0, true).rows; }
 int pw_x3_wide_bwd(View dz, const PwBnBwd& bb, const void* Wp, View C, int accumulate, int G, int Mg, int N, int K, const float* ey,
                    const float* epi_stats, double* part, hipStream_t st);
 int pw_x3(View A, const float* pro_stats, const void* Wp, const float* bias, View C, int G, int Mg, int N, int K, double* part,

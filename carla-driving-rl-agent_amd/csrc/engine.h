@@ -5,6 +5,7 @@
 #include <functional>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -105,6 +106,7 @@ public:
     int64_t params_total() const;
     int64_t grads_total() const { return tr_size_[0] + tr_size_[1] + tr_size_[2]; }
     size_t workspace_bytes() const { return ws_bytes_; }
+    const std::set<std::string>& pw_signatures() const { return pw_sigs_; }
 
     int bind(const Buffers& b);
     DevHP* host_hp() { return &hp_host_; }
@@ -363,6 +365,13 @@ private:
     void add_dense_bn(std::vector<Op>& ops, int model, const std::string& prefix, const Tens& in, const Tens& out, int G);
     // emits what the plan says (bn_in: the record behind ConvPlan::bn_in, or none); the backward is one of three programs, chosen at build time
     void add_pw(std::vector<Op>& ops, const PwConv& c, const ConvPlan& plan, const BnRec& bn_in, const BnRec& bn_out);
+    // which instantiations of the 1x1-conv family the built ops launch ("nn ok ksm nt pro epi mode acc", "x3 ok form kp nt pro epi",
+    // "x3b ok sh epi acc"), noted while they are built
+    std::set<std::string> pw_sigs_;
+    void note_pw(const char* kind, std::initializer_list<int> fields);
+    void note_pw(const PwNnPlan& p);
+    void note_pw(const PwX3Plan& p);
+    void note_pw(const PwX3BwdPlan& p);
     struct PwEmit {                          // what add_pw hands to the backward emitter of the plan's form
         PwConv c;
         ConvPlan plan;

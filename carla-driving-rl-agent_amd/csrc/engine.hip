@@ -456,28 +456,29 @@ Learner::ConvPlan Learner::plan_pw(const PwConv& c, bool fused, bool bb, bool bn
     // pw_x3_wide_kernel), which writes one statistics row per 32-row tile
     // (measured at M = 12288 and 49152 rows: 16-20 against 26-36 us, ~60 against 80 us; beyond that every 32-row tile would still stream
     //  its own copy of W -- 196 KB per tile and column block -- and the persistent kernel keeps the shape)
-    auto wide_shape = [&](int N, int K) {
-        return cfg_.compute == 0 && x3_env && (K > 128 || N > 128) && K <= 256 && N <= 256 && K % 4 == 0 && (int64_t)G * Mg <= 49152;
-    };
-    const bool wide = wide_shape(Cout, Cin);
+    // The engine's measured policy only (row limits, CDRL_PW_X3); whether a kernel can take a shape and a view is the plans' answer.
+    auto wide_policy = [&](int64_t max_rows) { return cfg_.compute == 0 && x3_env && (int64_t)G * Mg <= max_rows; };
+    const View dz = c.dz.ld ? c.dz : make_view(nullptr, Cout);
+    const PwX3Plan xf = pw_x3_plan(c.in, make_view(c.y, Cout), G, Mg, Cout, Cin, bn_in, true, true);
+    const bool wide = wide_policy(49152) && xf.form == 1 && xf.refusal != PWX3_REFUSE_SHAPE;
     // backward-data of the same convs (N = conv input channels, K = conv output channels): pw_x3_wide_bwd_kernel, one part2 / part row per tile
     // Small products only (M = 12288 rows at B = 256: the 3x4-pixel maps of stage 2): every workgroup streams its block of W^T once, so at
     // M = 49152 (the stride-2 unit's first conv, on the 6x8 maps) the fragment traffic (3072 x 196 KB) outweighs what the persistent kernel
     // loses to its serial tiles -- measured in the step: 140 us against 100 us there, 36 against 53 us (BatchNorm-sum epilogue) at M = 12288.
-    const bool wide_bwd = wide_shape(Cin, Cout) && (int64_t)G * Mg <= 16384;
+    const PwX3BwdPlan xb = pw_x3_wide_bwd_plan(dz, c.din, G, Mg, Cin, Cout, c.dz_shuffle, false, 0, true);
+    const bool wide_bwd = wide_policy(16384) && xb.refusal != PWX3B_REFUSE_SHAPE;
     // forward on the bf16 matrix pipe (exact three-way operand split, gemm_pw_x3.hip) where the shape allows it
     // (dry build: `in.p` is null, which counts as aligned -- as every tens_a tensor is, dense and 256-byte aligned)
-    const bool x3f = !bfc && x3_env && ((Cin <= 128 && Cout <= 128) || wide) && pw_x3_supported(c.in, Cout, Cin);
+    const bool x3f = !bfc && x3_env && (xf.form == 0 || wide) && xf.ok;
     if (wide && !x3f)
         build_fail("%s: the wide split-precision forward needs 16-byte aligned input rows (ld %d, offset %d)", c.name.c_str(), c.in.ld, c.in.coff);
     p.fwd = x3f ? PwGemm::X3 : PwGemm::PwNN;
     p.dgrad = PwGemm::PwNN;
-    p.stats_nb = wide ? pw_x3_partial_rows(G, Mg, Cout, Cin) : pw_nn_plan(G, Mg, Cout, Cin).nbpg;
-    p.bwd_nb = wide_bwd ? pw_x3_wide_bwd_rows(Mg) : pw_nn_plan(G, Mg, Cin, Cout).nbpg;
+    p.stats_nb = wide ? xf.nbpg : pw_nn_shape_plan(G, Mg, Cout, Cin).nbpg;
+    p.bwd_nb = wide_bwd ? xb.rows : pw_nn_shape_plan(G, Mg, Cin, Cout).nbpg;
     if (!bb) return p;
     // Backward form of a unit conv whose BatchNorm-backward apply rides on its operand loads (dz: the gradient w.r.t. the output of the
     // BatchNorm behind the conv, bn_in: the input is a BatchNorm output applied on load)
-    const View dz = c.dz.ld ? c.dz : make_view(nullptr, Cout);
     // One kernel for backward-data + filter gradient + bias gradient (+ the backward sums of the BatchNorm in front of the conv):
     // float32 engine and bf16 activation storage (not the operand-only mode), both channel counts padded alike (gemm_pw_bwd.hip)
     // 24 input channels -- the first unit, the last conv of the backward -- pad to 64: 158 us against 104 us for the backward-data kernel of
@@ -493,11 +494,21 @@ Learner::ConvPlan Learner::plan_pw(const PwConv& c, bool fused, bool bb, bool bn
     // split-precision kernel (round 6; the filter gradient stays on the side stream)
     else if (!bfc && !at_ && wide_bwd) p.bwd = PwBwd::Wide;
     else p.bwd = PwBwd::Prologue;
-    if (p.bwd == PwBwd::Wide && !pw_x3_wide_bwd_supported(dz, c.din, Cin, Cout, c.dz_shuffle))
+    if (p.bwd == PwBwd::Wide && !xb.ok)
         build_fail("%s: the wide split-precision backward needs even / 16-byte aligned gradient rows (ld %d, offset %d, shuffle %d)", c.name.c_str(),
                    dz.ld, dz.coff, c.dz_shuffle);
     return p;
 }
+
+// The instantiations the learner's 1x1 convs reach, recorded while the ops are built (cdrl_learner_pw_signatures)
+void Learner::note_pw(const char* kind, std::initializer_list<int> fields) {
+    std::string r = kind;
+    for (int f : fields) r += " " + std::to_string(f);
+    pw_sigs_.insert(r);
+}
+void Learner::note_pw(const PwNnPlan& p) { note_pw("nn", {p.ok, p.ksm, p.nt, p.pro, p.epi, p.mode, p.acc}); }
+void Learner::note_pw(const PwX3Plan& p) { note_pw("x3", {p.ok, p.form, p.kp, p.nt, p.pro, p.epi}); }
+void Learner::note_pw(const PwX3BwdPlan& p) { note_pw("x3b", {p.ok, p.sh, p.epi, p.acc}); }
 
 void Learner::add_pw(std::vector<Op>& ops, const PwConv& c, const ConvPlan& plan, const BnRec& bn_in, const BnRec& bn_out) {
     PwEmit e{c, plan, bn_in, bn_out};
@@ -528,6 +539,8 @@ void Learner::add_pw(std::vector<Op>& ops, const PwConv& c, const ConvPlan& plan
         max_dbpart_ = std::max(max_dbpart_, (size_t)pw_bwd_fused_dbpart_elems(G, Mg, Cout, Cin, at));
     }
     if (plan.bwd == PwBwd::FusedFin && bn_out.bwd_nb <= 0) build_fail("%s: finalize on load without the BatchNorm's scratch block", c.name.c_str());
+    if (plan.fwd == PwGemm::X3) note_pw(pw_x3_plan(in, yv, G, Mg, Cout, Cin, pro_stats != nullptr, true, true, nb_fwd));
+    if (plan.fwd == PwGemm::PwNN) note_pw(pw_nn_plan(in, yv, G, Mg, Cout, Cin, pro_stats ? 1 : 0, 1, 0, true, bfc, at, true));
     Op op;
     op.fwd = [=](hipStream_t st, int) -> int {
         switch (plan.fwd) {
@@ -593,6 +606,9 @@ std::function<int(hipStream_t)> Learner::pw_bwd_prologue_op(const PwEmit& e) {
     const PRef w = e.w, b = e.b;
     const float* wpb = e.wpb;
     const void* wpx = e.wpx;
+    const View dzb = dz0.ld ? dz0 : make_view(nullptr, Cout);       // (the scratch slots are dense and 256-byte aligned)
+    if (wide) note_pw(pw_x3_wide_bwd_plan(dzb, din, G, Mg, Cin, Cout, tb.shuffle_ctot, bn_in, din_acc, true));
+    else note_pw(pw_nn_plan(dzb, din, G, Mg, Cin, Cout, 2, bn_in ? 2 : 0, din_acc, true, bfc, at, true, tb.y));
     return [=](hipStream_t st) -> int {
         if (dz0.ld) CDRL_TRY(sched_.next_slot(st));
         const View dz = dz0.ld ? dz0 : make_view(dys_[sched_.slot()], Cout);
@@ -623,6 +639,7 @@ std::function<int(hipStream_t)> Learner::pw_bwd_plain_op(const PwEmit& e) {
     const PRef w = e.w, b = e.b;
     const float* wpb = e.wpb;
     const void* g3b = e.g3b;
+    if (din.ld && dgrad == PwGemm::PwNN) note_pw(pw_nn_plan(make_view(nullptr, Cout), din, G, Mg, Cin, Cout, 0, epi, din_acc, true, bfc, at, true));
     return [=](hipStream_t st) -> int {
         const View dy = make_view(dys_[sched_.slot()], Cout);
         // side stream: bias gradient (column sums of dy, reduced per block by bn_bwd_apply) + filter gradient

@@ -616,103 +616,131 @@ int pw_pack_many(const PwPack* tab_dev, int n, hipStream_t st) {
     return 0;
 }
 
-bool pw_nn_supported(View A, int N, int K) {
-    if (K > 256 || N > 256 || (K & 1) || N < 1) return false;
-    const int nt = N > 128 ? 4 : cdiv(N, 32), ksm = pw_ksm(K);
-    if (nt == 3 && ksm > 32) return false;
-    if (ksm == 128 && nt != 4) return false;        // K > 128 is instantiated for 4 column tiles per block only
-    return (A.ld % 2 == 0) && (A.coff % 2 == 0) && ((reinterpret_cast<uintptr_t>(A.p) & 7) == 0);
-}
-
-PwPlan pw_nn_plan(int G, int Mg, int N, int K) {
-    PwPlan p;
-    const int nt = N <= 128 ? cdiv(N, 32) : 4, ksm = pw_ksm(K);     // N > 128: column blocks of 128 (grid.y)
-    p.bm = 32 * (4 / pw_wc(nt));
-    const int tiles_g = cdiv(Mg, p.bm);
+PwNnPlan pw_nn_plan(View A, View C, int G, int Mg, int N, int K, int pro, int epi, int accumulate, bool packed, bool packed_bf16, int at,
+                    bool has_part, const float* y) {
+    PwNnPlan p{};
+    auto refuse = [&p](int code, const char* fmt, auto... args) -> PwNnPlan {
+        p.ok = 0;
+        p.refusal = code;
+        snprintf(p.why, sizeof(p.why), fmt, args...);
+        return p;
+    };
+    p.pro = pro;
+    p.epi = epi;
+    p.mode = at ? 2 : ((packed && packed_bf16) ? 1 : 0);
+    p.acc = (accumulate && epi == 0) ? 1 : 0;
+    if (G < 1 || Mg < 1 || N < 1) return refuse(PW_REFUSE_DIMS, "pw_nn: nothing to launch for G=%d Mg=%d N=%d (each at least 1)", G, Mg, N);
+    p.ksm = pw_ksm(K);
+    p.nt = N > 128 ? 4 : cdiv(N, 32);               // N > 128: column blocks of 128 (grid.y)
+    p.wc = pw_wc(p.nt);
+    p.wr = 4 / p.wc;
+    p.bm = 32 * p.wr;
+    p.tiles_g = cdiv(Mg, p.bm);
     // grid = exactly the number of workgroups that are resident at once (256 CUs x occupancy of the variant), so every
     // CU gets the same share; the tiles of a group are split evenly over its workgroups
-    const int occ = pw_occ(ksm, nt) == 1 ? 1 : ((ksm <= 32 && nt != 1) ? 3 : 2);
-    int target = 256 * occ / (G * cdiv(N, 128));
+    p.occ = pw_occ(p.ksm, p.nt) == 1 ? 1 : ((p.ksm <= 32 && p.nt != 1) ? 3 : 2);
+    p.gy = cdiv(N, 128);
+    int target = 256 * p.occ / (G * p.gy);
     if (target < 1) target = 1;
-    p.nbpg = tiles_g < target ? tiles_g : target;
-    p.tpb = cdiv(tiles_g, p.nbpg);
+    p.nbpg = p.tiles_g < target ? p.tiles_g : target;
+    p.tpb = cdiv(p.tiles_g, p.nbpg);
+    p.gx = G * p.nbpg;
+    p.packed_elems = pw_packed_elems(N, K);
+    // A tile (+ the 7 coefficient rows of the BatchNorm-backward prologue); the partial reductions reuse it
+    size_t lds = (size_t)(p.bm * (2 * p.ksm + 2) + (pro == 2 ? 14 * p.ksm : 0)) * sizeof(float);
+    const size_t red = (size_t)p.wr * 2 * 32 * p.nt * sizeof(double);
+    if (lds < red) lds = red;
+    if (lds < (size_t)512 * sizeof(double)) lds = (size_t)512 * sizeof(double);      // PRO_BNBWD column-sum scratch
+    p.lds_bytes = (int)lds;
+    if (K < 2) return refuse(PW_REFUSE_DIMS, "pw_nn: K=%d: the reduction needs at least one column pair", K);
+    if (K > 256 || N > 256 || (K & 1)) return refuse(PW_REFUSE_SHAPE, "pw_nn: shape K=%d N=%d not supported (even K, both at most 256)", K, N);
+    if ((p.nt == 3 && p.ksm > 32) || (p.ksm == 128 && p.nt != 4))
+        return refuse(PW_REFUSE_TILE, "pw_nn: shape K=%d N=%d not supported: %d column tiles are instantiated for K <= 64 only, K > 128 for N > 96 only",
+                      K, N, p.nt);
+    // Alignment.  Plain operand and BatchNorm apply: the tile loads are 8-byte buffer loads of column pairs of A, so A needs an even
+    // leading dimension and channel offset and an 8-byte aligned pointer.  BatchNorm-backward prologue: the dz view needs NOTHING --
+    // the kernel tests it per launch (dz_vec) and gathers single elements otherwise, which is also what a channel shuffle needs; the
+    // 8-byte pair loads go to y, dense [M][K] with K even, so only its pointer is held to 8 bytes.  (The hardware asks dword alignment
+    // of a buffer load; the 8 bytes are what pw_nn has always asked, and what keeps a pair inside one 8-byte word.)
+    const View v = pro == 2 ? make_view(const_cast<float*>(y), K) : A;
+    if ((v.ld % 2 != 0) || (v.coff % 2 != 0) || (reinterpret_cast<uintptr_t>(v.p) & 7) != 0)
+        return refuse(PW_REFUSE_ALIGN, "pw_nn: shape K=%d N=%d / alignment not supported (ld %d, offset %d: even, pointer 8-byte aligned)", K, N, v.ld, v.coff);
+    if (epi != 0 && !has_part) return refuse(PW_REFUSE_PART, "pw_nn: epilogue %d needs a partial buffer", epi);
+    if ((int64_t)G * Mg * A.ld * 4 >= (1ll << 31) || (int64_t)G * Mg * K * 4 >= (1ll << 31))        // 32-bit buffer offsets
+        return refuse(PW_REFUSE_2GB, "pw_nn: operands of 2 GB or more are not supported (rows=%lld)", (long long)G * Mg);
+    if (at && !(packed && packed_bf16))
+        return refuse(PW_REFUSE_STORAGE, "pw_nn: bf16 activation storage needs the bf16-operand variant (packed bf16 weights; K=%d N=%d)", K, N);
+    if (pro < 0 || pro > 2 || epi < 0 || epi > 2 || (pro == 1 && epi == 2) || (pro == 2 && epi == 1))
+        return refuse(PW_REFUSE_PRO_EPI, "pw_nn: unsupported prologue/epilogue combination %d/%d", pro, epi);
+    p.ok = 1;
     return p;
 }
 
+// The launch ladder, one level per template argument, each driven by the plan's field; a pair the plan admits always finds its kernel.
 template <int KSM, int NT, int PRO, int EPI, int MODE, bool ACC>
-static int launch_pw_bf(const PwArgs& a, hipStream_t st) {
-    constexpr int WR = 4 / pw_wc(NT);
-    constexpr int BM = 32 * WR;
-    size_t lds = (size_t)(BM * (2 * KSM + 2) + (PRO == 2 ? 14 * KSM : 0)) * sizeof(float);
-    const size_t red = (size_t)WR * 2 * 32 * NT * sizeof(double);
-    if (lds < red) lds = red;
-    if (lds < (size_t)512 * sizeof(double)) lds = (size_t)512 * sizeof(double);      // PRO_BNBWD column-sum scratch
+static int launch_pw_bf(const PwNnPlan& p, const PwArgs& a, hipStream_t st) {
     auto kern = pw_nn_kernel<KSM, NT, PRO, EPI, MODE, ACC>;
+    const size_t lds = (size_t)p.lds_bytes;
     static size_t allowed = 64 * 1024;          // per instantiation: one runtime call per kernel and size, not one per launch
     if (lds > allowed) {
         CDRL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         allowed = lds;
     }
-    hipLaunchKernelGGL(kern, dim3(a.G * a.nbpg, cdiv(a.N, 128)), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(256), lds, st, a);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
 
 template <int KSM, int NT, int PRO, int EPI>
-static int launch_pw(const PwArgs& a, hipStream_t st) {
+static int launch_pw(const PwNnPlan& p, const PwArgs& a, hipStream_t st) {
     if constexpr (EPI == 0) {
-        if (a.accumulate) {
-            if (a.at) return launch_pw_bf<KSM, NT, PRO, EPI, 2, true>(a, st);
-            return a.bf ? launch_pw_bf<KSM, NT, PRO, EPI, 1, true>(a, st) : launch_pw_bf<KSM, NT, PRO, EPI, 0, true>(a, st);
+        if (p.acc) {
+            if (p.mode == 2) return launch_pw_bf<KSM, NT, PRO, EPI, 2, true>(p, a, st);
+            return p.mode == 1 ? launch_pw_bf<KSM, NT, PRO, EPI, 1, true>(p, a, st) : launch_pw_bf<KSM, NT, PRO, EPI, 0, true>(p, a, st);
         }
     }
-    if (a.at) return launch_pw_bf<KSM, NT, PRO, EPI, 2, false>(a, st);
-    return a.bf ? launch_pw_bf<KSM, NT, PRO, EPI, 1, false>(a, st) : launch_pw_bf<KSM, NT, PRO, EPI, 0, false>(a, st);
+    if (p.mode == 2) return launch_pw_bf<KSM, NT, PRO, EPI, 2, false>(p, a, st);
+    return p.mode == 1 ? launch_pw_bf<KSM, NT, PRO, EPI, 1, false>(p, a, st) : launch_pw_bf<KSM, NT, PRO, EPI, 0, false>(p, a, st);
 }
 
 template <int KSM, int NT>
-static int launch_pw_pe(int pro, int epi, const PwArgs& a, hipStream_t st) {
-    if (pro == 0 && epi == 0) return launch_pw<KSM, NT, 0, 0>(a, st);
-    if (pro == 0 && epi == 1) return launch_pw<KSM, NT, 0, 1>(a, st);
-    if (pro == 0 && epi == 2) return launch_pw<KSM, NT, 0, 2>(a, st);
-    if (pro == 1 && epi == 0) return launch_pw<KSM, NT, 1, 0>(a, st);
-    if (pro == 1 && epi == 1) return launch_pw<KSM, NT, 1, 1>(a, st);
-    if (pro == 2 && epi == 0) return launch_pw<KSM, NT, 2, 0>(a, st);
-    if (pro == 2 && epi == 2) return launch_pw<KSM, NT, 2, 2>(a, st);
-    set_error("pw_nn: unsupported prologue/epilogue combination %d/%d", pro, epi);
+static int launch_pw_pe(const PwNnPlan& p, const PwArgs& a, hipStream_t st) {
+    switch (p.pro * 3 + p.epi) {
+        case 0: return launch_pw<KSM, NT, 0, 0>(p, a, st);
+        case 1: return launch_pw<KSM, NT, 0, 1>(p, a, st);
+        case 2: return launch_pw<KSM, NT, 0, 2>(p, a, st);
+        case 3: return launch_pw<KSM, NT, 1, 0>(p, a, st);
+        case 4: return launch_pw<KSM, NT, 1, 1>(p, a, st);
+        case 6: return launch_pw<KSM, NT, 2, 0>(p, a, st);
+        case 8: return launch_pw<KSM, NT, 2, 2>(p, a, st);
+    }
+    set_error("pw_nn: no kernel for the plan (pro %d epi %d)", p.pro, p.epi);
     return -1;
 }
 
 template <int KSM>
-static int launch_pw_nt(int nt, int pro, int epi, const PwArgs& a, hipStream_t st) {
-    switch (nt) {
-        case 1: return launch_pw_pe<KSM, 1>(pro, epi, a, st);
-        case 2: return launch_pw_pe<KSM, 2>(pro, epi, a, st);
+static int launch_pw_nt(const PwNnPlan& p, const PwArgs& a, hipStream_t st) {
+    switch (p.nt) {
+        case 1: return launch_pw_pe<KSM, 1>(p, a, st);
+        case 2: return launch_pw_pe<KSM, 2>(p, a, st);
         case 3:
-            if constexpr (KSM <= 32) return launch_pw_pe<KSM, 3>(pro, epi, a, st);
+            if constexpr (KSM <= 32) return launch_pw_pe<KSM, 3>(p, a, st);
             break;
-        case 4: return launch_pw_pe<KSM, 4>(pro, epi, a, st);
+        case 4: return launch_pw_pe<KSM, 4>(p, a, st);
     }
-    set_error("pw_nn: unsupported tile shape");
+    set_error("pw_nn: no kernel for the plan (ksm %d nt %d)", p.ksm, p.nt);
     return -1;
 }
 
 int pw_nn(View A, const float* pro_stats, const float* W, int sbk, int sbn, const float* bias, View C, int accumulate, int G,
           int Mg, int N, int K, int epilogue, const float* ey, const float* epi_stats, double* part, hipStream_t st,
           const PwBnBwd* bb, const float* Wp, bool wp_bf16, int at) {
-    if (!pw_nn_supported(bb ? make_view(const_cast<float*>(bb->y), K) : A, N, K)) {
-        set_error("pw_nn: shape K=%d N=%d / alignment not supported", K, N);
+    const PwNnPlan p = pw_nn_plan(A, C, G, Mg, N, K, bb ? 2 : (pro_stats ? 1 : 0), epilogue, accumulate, Wp != nullptr, wp_bf16, at,
+                                  part != nullptr, bb ? bb->y : nullptr);
+    if (!p.ok) {
+        set_error("%s", p.why);
         return -1;
     }
-    if (epilogue != 0 && !part) {
-        set_error("pw_nn: epilogue needs a partial buffer");
-        return -1;
-    }
-    if ((int64_t)G * Mg * A.ld * 4 >= (1ll << 31) || (int64_t)G * Mg * K * 4 >= (1ll << 31)) {     // 32-bit buffer offsets
-        set_error("pw_nn: operands of 2 GB or more are not supported (rows=%lld)", (long long)G * Mg);
-        return -1;
-    }
-    const PwPlan p = pw_nn_plan(G, Mg, N, K);
     PwArgs a;
     a.A = A;
     a.a_shuffle = bb ? bb->shuffle_ctot : 0;
@@ -720,18 +748,13 @@ int pw_nn(View A, const float* pro_stats, const float* W, int sbk, int sbn, cons
     a.a_y = bb ? bb->y : nullptr;
     a.pro_coef = bb ? bb->coef : nullptr;
     a.part2 = bb ? bb->part2 : nullptr;
-    if (bb) pro_stats = bb->stats;
-    a.pro_stats = pro_stats;
+    a.pro_stats = bb ? bb->stats : pro_stats;
     a.W = W;
     a.sbk = sbk;
     a.sbn = sbn;
     a.Wp = Wp;
-    a.bf = (wp_bf16 && Wp) ? 1 : 0;
-    a.at = at ? 1 : 0;
-    if (a.at && !a.bf) {
-        set_error("pw_nn: bf16 activation storage needs the bf16-operand variant (packed bf16 weights)");
-        return -1;
-    }
+    a.bf = p.mode >= 1;
+    a.at = p.mode == 2;
     a.bias = bias;
     a.C = C;
     a.accumulate = accumulate;
@@ -744,12 +767,11 @@ int pw_nn(View A, const float* pro_stats, const float* W, int sbk, int sbn, cons
     a.Mg = Mg;
     a.nbpg = p.nbpg;
     a.tpb = p.tpb;
-    const int nt = N > 128 ? 4 : cdiv(N, 32), pro = bb ? 2 : (pro_stats ? 1 : 0);
-    switch (pw_ksm(K)) {
-        case 16: return launch_pw_nt<16>(nt, pro, epilogue, a, st);
-        case 32: return launch_pw_nt<32>(nt, pro, epilogue, a, st);
-        case 64: return launch_pw_nt<64>(nt, pro, epilogue, a, st);
-        default: return launch_pw_pe<128, 4>(pro, epilogue, a, st);
+    switch (p.ksm) {
+        case 16: return launch_pw_nt<16>(p, a, st);
+        case 32: return launch_pw_nt<32>(p, a, st);
+        case 64: return launch_pw_nt<64>(p, a, st);
+        default: return launch_pw_pe<128, 4>(p, a, st);
     }
 }
 

@@ -480,95 +480,136 @@ int pw_x3_pack_many(const PwX3Pack* tab_dev, int n, hipStream_t st) {
     return 0;
 }
 
-bool pw_x3_supported(View A, int N, int K) {
-    // K <= 128 (the persistent kernel): its A chunks are 16-byte BUFFER loads, which need dword alignment only, and columns beyond K
-    // inside the last chunk are zeroed -- so the 58-channel rows of stage 0 (232-byte pitch, channel offset 58) qualify (round 6;
-    // before, only 16-byte aligned rows did, and those convs stayed on the float32 matrix pipe)
-    if (K >= 4 && K <= 128 && N >= 1 && N <= 128 && K % 2 == 0 && A.ld % 2 == 0 && A.coff % 2 == 0 &&
-        (reinterpret_cast<uintptr_t>(A.p) & 15) == 0)
-        return true;
-    return K >= 4 && K <= 256 && N >= 1 && N <= 256 && K % 4 == 0 && A.ld % 4 == 0 && A.coff % 4 == 0 &&
-           (reinterpret_cast<uintptr_t>(A.p) & 15) == 0;
-}
-
 static constexpr int X3_OCC = 2;        // workgroups per CU of the grid: pw_x3_kernel's __launch_bounds__(256, 2)
 
-int pw_x3_partial_rows(int G, int Mg, int N, int K) {
-    if (x3_wide(N, K)) return cdiv(Mg, 32);         // one partial row per 32-row tile
-    const int bm = 32 * (4 / x3_nt(N)), tiles = cdiv(Mg, bm);
-    int nb = 256 * X3_OCC / G;
-    if (nb < 1) nb = 1;
-    return nb > tiles ? tiles : nb;
+PwX3Plan pw_x3_plan(View A, View C, int G, int Mg, int N, int K, bool pro, bool epi, bool packed, int nbpg) {
+    PwX3Plan p{};
+    auto refuse = [&p](int code, const char* fmt, auto... args) -> PwX3Plan {
+        p.ok = 0;
+        p.refusal = code;
+        snprintf(p.why, sizeof(p.why), fmt, args...);
+        return p;
+    };
+    p.form = x3_wide(N, K) ? 1 : 0;
+    p.kp = p.form ? 256 : x3_kp(K);             // (the wide form always runs with KP = 256: its kernel is instantiated for that padding only)
+    p.nt = p.form ? 4 : x3_nt(N);
+    p.pro = pro;
+    p.epi = epi;
+    p.packed_bytes = pw_x3_packed_bytes_n(K, N);
+    if (G < 1 || Mg < 1 || N < 1) return refuse(PWX3_REFUSE_DIMS, "pw_x3: nothing to launch for G=%d Mg=%d N=%d (each at least 1)", G, Mg, N);
+    p.bm = p.form ? 32 : 32 * (4 / p.nt);
+    p.tiles_g = cdiv(Mg, p.bm);
+    if (p.form) {
+        p.nbpg = p.tiles_g;                     // one workgroup and one partial row per 32-row tile
+    } else {
+        p.nbpg = 256 * X3_OCC / G;
+        if (p.nbpg < 1) p.nbpg = 1;
+        if (p.nbpg > p.tiles_g) p.nbpg = p.tiles_g;
+    }
+    p.gx = G * p.nbpg;
+    p.gy = p.form ? cdiv(N, 128) : 1;
+    if (K < 4 || K > 256 || N > 256 || K % (p.form ? 4 : 2) != 0)
+        return refuse(PWX3_REFUSE_SHAPE, "pw_x3: unsupported shape / alignment K=%d N=%d (K in 4..256, N <= 256, K even, a multiple of 4 in the wide form)", K, N);
+    // K <= 128 (the persistent kernel): its A chunks are 16-byte BUFFER loads, which need dword alignment only, and columns beyond K
+    // inside the last chunk are zeroed -- so the 58-channel rows of stage 0 (232-byte pitch, channel offset 58) qualify
+    const int al = p.form ? 4 : 2;
+    if (A.ld % al != 0 || A.coff % al != 0 || (reinterpret_cast<uintptr_t>(A.p) & 15) != 0)
+        return refuse(PWX3_REFUSE_ALIGN, "pw_x3: unsupported shape / alignment K=%d N=%d ld=%d coff=%d (multiples of %d, pointer 16-byte aligned)", K, N, A.ld,
+                      A.coff, al);
+    if (!packed) return refuse(PWX3_REFUSE_PACKED, "pw_x3: unsupported call K=%d N=%d: no packed weights", K, N);
+    if ((int64_t)G * Mg * A.ld * 4 >= (int64_t)1 << 31) return refuse(PWX3_REFUSE_2GB, "pw_x3: operand of 2 GB or more (%lld rows)", (long long)G * Mg);
+    if (nbpg > 0) {
+        if (p.form && nbpg != p.tiles_g)
+            return refuse(PWX3_REFUSE_NBPG, "pw_x3: the wide form writes one partial row per 32-row tile (%d), not %d", p.tiles_g, nbpg);
+        if (nbpg > p.tiles_g) return refuse(PWX3_REFUSE_NBPG, "pw_x3: %d workgroups per group for %d tiles: some would own none", nbpg, p.tiles_g);
+        p.nbpg = nbpg;
+        p.gx = G * nbpg;
+    }
+    p.ok = 1;
+    return p;
 }
 
-template <int KP, int NT>
-static void pw_x3_launch(const PwX3Args& a, bool pro, bool epi, hipStream_t st) {
-    const dim3 grid(a.G * a.nbpg), block(256);
-    if (pro && epi) hipLaunchKernelGGL((pw_x3_kernel<KP, NT, true, true>), grid, block, 0, st, a);
-    else if (pro) hipLaunchKernelGGL((pw_x3_kernel<KP, NT, true, false>), grid, block, 0, st, a);
-    else if (epi) hipLaunchKernelGGL((pw_x3_kernel<KP, NT, false, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((pw_x3_kernel<KP, NT, false, false>), grid, block, 0, st, a);
+// the prologue / epilogue level of both forward kernels
+#define CDRL_X3_PE(KERNEL, ...)                                                                              \
+    do {                                                                                                      \
+        if (p.pro && p.epi) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, true>), grid, block, 0, st, a);      \
+        else if (p.pro) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, false>), grid, block, 0, st, a);         \
+        else if (p.epi) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, true>), grid, block, 0, st, a);         \
+        else hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, false>), grid, block, 0, st, a);                   \
+    } while (0)
+
+template <int KP>
+static void pw_x3_launch(const PwX3Plan& p, const PwX3Args& a, hipStream_t st) {
+    const dim3 grid(p.gx, p.gy), block(256);
+    if (p.nt == 1) CDRL_X3_PE(pw_x3_kernel, KP, 1, );
+    else if (p.nt == 2) CDRL_X3_PE(pw_x3_kernel, KP, 2, );
+    else CDRL_X3_PE(pw_x3_kernel, KP, 4, );
 }
 
 int pw_x3(View A, const float* pro_stats, const void* Wp, const float* bias, View C, int G, int Mg, int N, int K, double* part,
           hipStream_t st, int nbpg) {
-    if (!pw_x3_supported(A, N, K) || !Wp) {
-        set_error("pw_x3: unsupported shape / alignment K=%d N=%d ld=%d coff=%d", K, N, A.ld, A.coff);
+    const PwX3Plan p = pw_x3_plan(A, C, G, Mg, N, K, pro_stats != nullptr, part != nullptr, Wp != nullptr, nbpg);
+    if (!p.ok) {
+        set_error("%s", p.why);
         return -1;
     }
-    if ((int64_t)G * Mg * A.ld * 4 >= (int64_t)1 << 31) {
-        set_error("pw_x3: operand of 2 GB or more");
-        return -1;
+    PwX3Args a{A, pro_stats, reinterpret_cast<const __bf16*>(Wp), bias, C, part, N, K, G, Mg, p.nbpg};
+    if (p.form) {
+        const dim3 grid(p.gx, p.gy), block(256);
+        CDRL_X3_PE(pw_x3_wide_kernel, );
+    } else if (p.kp == 32) {
+        pw_x3_launch<32>(p, a, st);
+    } else if (p.kp == 64) {
+        pw_x3_launch<64>(p, a, st);
+    } else {
+        pw_x3_launch<128>(p, a, st);
     }
-    PwX3Args a{A, pro_stats, reinterpret_cast<const __bf16*>(Wp), bias, C, part, N, K, G, Mg, nbpg > 0 ? nbpg : pw_x3_partial_rows(G, Mg, N, K)};
-    const int kp = x3_kp(K), nt = x3_nt(N);
-    const bool pro = pro_stats != nullptr, epi = part != nullptr;
-    if (x3_wide(N, K)) {
-        if (a.nbpg != cdiv(Mg, 32)) {
-            set_error("pw_x3: the wide form writes one partial row per 32-row tile (%d), not %d", cdiv(Mg, 32), a.nbpg);
-            return -1;
-        }
-        const dim3 grid(G * a.nbpg, cdiv(N, 128)), block(256);
-        if (pro && epi) hipLaunchKernelGGL((pw_x3_wide_kernel<true, true>), grid, block, 0, st, a);
-        else if (pro) hipLaunchKernelGGL((pw_x3_wide_kernel<true, false>), grid, block, 0, st, a);
-        else if (epi) hipLaunchKernelGGL((pw_x3_wide_kernel<false, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((pw_x3_wide_kernel<false, false>), grid, block, 0, st, a);
-        CDRL_LAUNCH_CHECK();
-        return 0;
-    }
-#define CDRL_X3(KPV, NTV) pw_x3_launch<KPV, NTV>(a, pro, epi, st)
-    if (kp == 32) { if (nt == 1) CDRL_X3(32, 1); else if (nt == 2) CDRL_X3(32, 2); else CDRL_X3(32, 4); }
-    else if (kp == 64) { if (nt == 1) CDRL_X3(64, 1); else if (nt == 2) CDRL_X3(64, 2); else CDRL_X3(64, 4); }
-    else { if (nt == 1) CDRL_X3(128, 1); else if (nt == 2) CDRL_X3(128, 2); else CDRL_X3(128, 4); }
-#undef CDRL_X3
     CDRL_LAUNCH_CHECK();
     return 0;
 }
+#undef CDRL_X3_PE
 
-
-bool pw_x3_wide_bwd_supported(View dz, View C, int N, int K, int shuffle_ctot) {
-    // N = conv input channels (columns of the output), K = conv output channels (columns of dz / y)
-    if (!(K > 128 || N > 128) || K > 256 || N > 256 || (K & 3)) return false;
-    if ((reinterpret_cast<uintptr_t>(dz.p) & 15) || (dz.ld & 1)) return false;
-    if (shuffle_ctot) return (dz.coff & 1) == 0 && ((shuffle_ctot >> 1) & 1) == 0;
-    return (dz.ld & 3) == 0 && (dz.coff & 3) == 0;
+PwX3BwdPlan pw_x3_wide_bwd_plan(View dz, View C, int G, int Mg, int N, int K, int shuffle_ctot, bool epi, int accumulate, bool operands) {
+    PwX3BwdPlan p{};
+    auto refuse = [&p](int code, const char* fmt, auto... args) -> PwX3BwdPlan {
+        p.ok = 0;
+        p.refusal = code;
+        snprintf(p.why, sizeof(p.why), fmt, args...);
+        return p;
+    };
+    p.sh = shuffle_ctot != 0;
+    p.epi = epi;
+    p.acc = accumulate != 0;
+    p.rows = cdiv(Mg, 32);
+    if (G < 1 || Mg < 1) return refuse(PWX3B_REFUSE_DIMS, "pw_x3_wide_bwd: nothing to launch for G=%d Mg=%d (each at least 1)", G, Mg);
+    p.gx = G * p.rows;
+    p.gy = cdiv(N, 128);
+    if (!x3_wide(N, K) || K > 256 || N > 256 || (K & 3))
+        return refuse(PWX3B_REFUSE_SHAPE, "pw_x3_wide_bwd: unsupported shape / alignment K=%d N=%d (one above 128, both at most 256, K a multiple of 4)", K, N);
+    const bool al = shuffle_ctot ? ((dz.coff & 1) == 0 && ((shuffle_ctot >> 1) & 1) == 0) : ((dz.ld & 3) == 0 && (dz.coff & 3) == 0);
+    if ((reinterpret_cast<uintptr_t>(dz.p) & 15) || (dz.ld & 1) || !al)
+        return refuse(PWX3B_REFUSE_ALIGN, "pw_x3_wide_bwd: unsupported shape / alignment K=%d N=%d ld=%d coff=%d shuffle=%d", K, N, dz.ld, dz.coff, shuffle_ctot);
+    if (!operands) return refuse(PWX3B_REFUSE_OPERANDS, "pw_x3_wide_bwd: unsupported call K=%d N=%d: packed weights, y, stats and coef are required", K, N);
+    if (p.epi && p.acc) return refuse(PWX3B_REFUSE_EPI_ACC, "pw_x3_wide_bwd: the BatchNorm-sum epilogue and accumulation are not instantiated together (K=%d N=%d)", K, N);
+    const int64_t Mtot = (int64_t)G * Mg, lim = (int64_t)1 << 31;
+    if (Mtot * dz.ld * 4 >= lim || Mtot * K * 4 >= lim || Mtot * C.ld * 4 >= lim) return refuse(PWX3B_REFUSE_2GB, "pw_x3_wide_bwd: operand of 2 GB or more (%lld rows)", (long long)Mtot);
+    p.ok = 1;
+    return p;
 }
 
-int pw_x3_wide_bwd_rows(int Mg) { return cdiv(Mg, 32); }
+template <bool SH>
+static void pw_x3_wide_bwd_launch(const PwX3BwdPlan& p, const PwX3BwdArgs& a, hipStream_t st) {
+    const dim3 grid(p.gx, p.gy), block(256);
+    if (p.epi) hipLaunchKernelGGL((pw_x3_wide_bwd_kernel<SH, true, false>), grid, block, 0, st, a);
+    else if (p.acc) hipLaunchKernelGGL((pw_x3_wide_bwd_kernel<SH, false, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((pw_x3_wide_bwd_kernel<SH, false, false>), grid, block, 0, st, a);
+}
 
 int pw_x3_wide_bwd(View dz, const PwBnBwd& bb, const void* Wp, View C, int accumulate, int G, int Mg, int N, int K, const float* ey,
                    const float* epi_stats, double* part, hipStream_t st) {
-    if (!pw_x3_wide_bwd_supported(dz, C, N, K, bb.shuffle_ctot) || !Wp || !bb.y || !bb.stats || !bb.coef) {
-        set_error("pw_x3_wide_bwd: unsupported shape / alignment K=%d N=%d ld=%d coff=%d", K, N, dz.ld, dz.coff);
-        return -1;
-    }
-    if ((ey != nullptr) && accumulate) {
-        set_error("pw_x3_wide_bwd: the BatchNorm-sum epilogue and accumulation are not instantiated together");
-        return -1;
-    }
-    const int64_t Mtot = (int64_t)G * Mg;
-    if (Mtot * dz.ld * 4 >= (int64_t)1 << 31 || Mtot * K * 4 >= (int64_t)1 << 31 || Mtot * C.ld * 4 >= (int64_t)1 << 31) {
-        set_error("pw_x3_wide_bwd: operand of 2 GB or more");
+    const PwX3BwdPlan p = pw_x3_wide_bwd_plan(dz, C, G, Mg, N, K, bb.shuffle_ctot, ey != nullptr, accumulate, Wp && bb.y && bb.stats && bb.coef);
+    if (!p.ok) {
+        set_error("%s", p.why);
         return -1;
     }
     PwX3BwdArgs a;
@@ -588,18 +629,9 @@ int pw_x3_wide_bwd(View dz, const PwBnBwd& bb, const void* Wp, View C, int accum
     a.K = K;
     a.G = G;
     a.Mg = Mg;
-    a.nbpg = cdiv(Mg, 32);
-    const dim3 grid(G * a.nbpg, cdiv(N, 128)), block(256);
-    const bool shuf = bb.shuffle_ctot != 0, epi = ey != nullptr, acc = accumulate != 0;
-#define CDRL_X3B(SH)                                                                                          \
-    do {                                                                                                      \
-        if (epi) hipLaunchKernelGGL((pw_x3_wide_bwd_kernel<SH, true, false>), grid, block, 0, st, a);         \
-        else if (acc) hipLaunchKernelGGL((pw_x3_wide_bwd_kernel<SH, false, true>), grid, block, 0, st, a);    \
-        else hipLaunchKernelGGL((pw_x3_wide_bwd_kernel<SH, false, false>), grid, block, 0, st, a);            \
-    } while (0)
-    if (shuf) CDRL_X3B(true);
-    else CDRL_X3B(false);
-#undef CDRL_X3B
+    a.nbpg = p.rows;
+    if (p.sh) pw_x3_wide_bwd_launch<true>(p, a, st);
+    else pw_x3_wide_bwd_launch<false>(p, a, st);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

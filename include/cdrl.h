@@ -223,6 +223,10 @@ int cdrl_learner_set_comm_stream(cdrl_learner* l, void* stream);
  * pass's own stream is.  Equals the trunk size when the stream is never released mid-pass (hipGraph replay, CDRL_GRAPH=1; a learner
  * created with freeze_trunk = 1, which writes no trunk gradient at all). */
 int64_t cdrl_learner_tail_offset(const cdrl_learner* l);
+/* The instantiations of the 1x1-conv forward / backward-data family that this learner's ops launch, noted while they
+ * were built (a learner without device works): one line per distinct plan signature, "nn ok ksm nt pro epi mode acc", "x3 ok form kp nt
+ * pro epi" or "x3b ok sh epi acc".  Writes at most n bytes (NUL-terminated) and returns the bytes needed; -1 without a learner. */
+int cdrl_learner_pw_signatures(const cdrl_learner* l, char* buf, int n);
 /* Step counters to 0 and the Nadam m_caches to 1 (a fresh optimizer; the slots in the arenas are the caller's to reset). */
 int cdrl_learner_reset_optimizer_steps(cdrl_learner* l, void* stream);
 /* The optimizer's device-side scalars: with the parameter arena and the two slot arenas (the caller's tensors) they are the whole
@@ -885,6 +889,39 @@ int cdrl_gemm_nn_plan(const cdrl_view* a, uint64_t b_addr, int sbk, int sbn, int
 int64_t cdrl_gemm_nn_workspace_elems(int M, int N, int K);
 int cdrl_gemm_nn_ex(const cdrl_view* a, const float* B, int sbk, int sbn, const float* bias, const cdrl_view* c, int M, int N, int K,
                     int accumulate, float* workspace, float* act_out, int act, int* act_done, void* stream);
+/* ---- The 1x1-conv forward / backward-data family: the plans cdrl_pwconv_fused[_packed] / cdrl_pwconv_bn_bwd (pw_nn), cdrl_pwconv_x3 and
+ * cdrl_pwconv_x3_wide_bwd launch from (the launchers call the same host functions).  The queries launch nothing and read no memory: only
+ * the address bits, ld and coff of the views count, and whether an operand is given.  Each takes an array of EXACTLY its number of int32
+ * fields, writes all of them, and returns 0 when the call would be launched, -1 with the refusal sentence in cdrl_last_error when it
+ * would be refused (field 1 then holds the refusal code) or when a view / the field array is missing.
+ * cdrl_pwconv_plan (19 fields): a = the operand view (pro == 2: the dz view, and y_addr the address of that prologue's raw BatchNorm
+ * input), pro 0 none / 1 BatchNorm apply / 2 BatchNorm backward, epi 0 / 1 statistics / 2 BatchNorm backward sums.
+ *    0 ok  1 refusal: 1 G, Mg, N < 1 or K < 2; 2 K or N above 256, K odd; 3 a (ksm, nt) pair that is not instantiated; 4 alignment;
+ *      5 prologue / epilogue pair; 6 epilogue without partial buffer; 7 an operand of 2 GB or more; 8 bf16 storage without packed bf16 weights
+ *    2 ksm  3 nt  4 pro  5 epi  6 mode  7 acc   pw_nn_kernel<KSM, NT, PRO, EPI, MODE, ACC>
+ *    8 wc  9 wr  10 bm (rows per tile)  11 tiles_g  12 nbpg (workgroups = partial rows per group)  13 tpb (most tiles per workgroup)
+ *   14 gx  15 gy  16 occ  17 lds_bytes  18 packed_elems
+ * cdrl_pwconv_x3_plan (13 fields): nbpg 0 = the kernel's own count, > 0 = the caller's (honoured inside [1, tiles_g], else refused).
+ *    0 ok  1 refusal: 1 G, Mg, N < 1; 2 shape; 3 alignment; 4 no packed weights; 5 2 GB; 6 nbpg
+ *    2 form (0 persistent, 1 wide)  3 kp  4 nt  5 pro  6 epi  7 bm  8 tiles_g  9 nbpg  10 gx  11 gy  12 packed_bytes
+ * cdrl_pwconv_x3_wide_bwd_plan (8 fields): N = conv input channels, K = conv output channels.
+ *    0 ok  1 refusal: 1 G, Mg < 1; 2 shape; 3 alignment; 4 operands missing; 5 epilogue and accumulate are not instantiated together; 6 2 GB
+ *    2 sh  3 epi  4 acc   pw_x3_wide_bwd_kernel<SH, EPI, ACC>   5 rows (partial rows per group)  6 gx  7 gy */
+int cdrl_pwconv_plan(const cdrl_view* a, const cdrl_view* c, uint64_t y_addr, int G, int Mg, int N, int K, int pro, int epi, int accumulate,
+                     int packed, int packed_bf16, int act_type, int has_part, int32_t* fields, int n_fields);
+/* pw_nn with its whole contract (cdrl_pwconv_fused[_packed] are its forms without the BatchNorm-backward prologue): bwd_y != NULL
+ * selects prologue 2 -- a is then the dz view (gathered through the channel shuffle of a bwd_shuffle-channel tensor when != 0, masked by
+ * ReLU6 of the BatchNorm output when bwd_relu6), bwd_y that BatchNorm's raw input [G*Mg][K] dense, pro_stats its [4][G][K] statistics,
+ * bwd_coef its [3][G][K] backward coefficients, part2 (or NULL) [G][nbpg][K] doubles: column sums of the transformed operand.  Refused
+ * (-1, cdrl_last_error) before any launch: whatever cdrl_pwconv_plan refuses, a null tensor, a prologue 2 or epilogue 2 without its operands. */
+int cdrl_pwconv_ex(const cdrl_view* a, const float* pro_stats, const float* bwd_y, const float* bwd_coef, int bwd_shuffle, int bwd_relu6,
+                   double* part2, const float* w, int sbk, int sbn, const float* bias, const cdrl_view* c, int accumulate, int G, int Mg, int N,
+                   int K, int epilogue, const float* epi_y, const float* epi_stats, double* part, const float* w_packed, int packed_bf16,
+                   int act_type, void* stream);
+int cdrl_pwconv_x3_plan(const cdrl_view* a, const cdrl_view* c, int G, int Mg, int N, int K, int pro, int epi, int packed, int nbpg,
+                        int32_t* fields, int n_fields);
+int cdrl_pwconv_x3_wide_bwd_plan(const cdrl_view* dz, const cdrl_view* c, int G, int Mg, int N, int K, int dz_shuffle, int epi, int accumulate,
+                                 int operands, int32_t* fields, int n_fields);
 /* a = act(z), dz = da * act'(z) on dense float32 arrays of n elements (act as above; relu6 gradient 1 strictly inside (0, 6), swish6 =
  * min(z sigmoid(z), 6) with gradient 0 where z sigmoid(z) >= 6) */
 int cdrl_act_fwd(const float* z, float* a, int64_t n, int act, void* stream);
