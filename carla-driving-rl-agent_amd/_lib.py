@@ -20,7 +20,7 @@ class Config(C.Structure):
                 ('feat', C.c_int32), ('rnn_image', C.c_int32), ('rnn_small', C.c_int32), ('dyn', C.c_int32),
                 ('head', C.c_int32), ('exp_scale', C.c_float), ('compute', C.c_int32),
                 ('freeze_trunk', C.c_int32), ('optimizer', C.c_int32), ('polyak', C.c_float), ('train_stats', C.c_int32),
-                ('clip_mode', C.c_int32), ('skip_nonfinite', C.c_int32)]
+                ('clip_mode', C.c_int32), ('skip_nonfinite', C.c_int32), ('trust', C.c_int32)]
 
 
 class TrainStatsLayout(C.Structure):
@@ -66,12 +66,24 @@ class GateStats(C.Structure):
                 ('norm_dynamics', C.c_float * 2), ('scale_dynamics', C.c_float * 2)]
 
 
+class TrustParams(C.Structure):
+    """cdrl_trust_params (include/cdrl.h): the host-written head of the trust-region block."""
+    _fields_ = [('target_kl', C.c_float), ('kl_stop_factor', C.c_float), ('kl_coef', C.c_float)]
+
+
+class TrustStats(C.Structure):
+    """cdrl_trust_stats (include/cdrl.h): the trust-region block as the device keeps it."""
+    _fields_ = [('target_kl', C.c_float), ('kl_stop_factor', C.c_float), ('kl_coef', C.c_float), ('kl_last', C.c_float),
+                ('kl_max', C.c_float), ('passes', C.c_int32), ('stop', C.c_int32), ('stop_pass', C.c_int32), ('armed', C.c_int32),
+                ('skipped', C.c_int32), ('kl_sum', C.c_double)]
+
+
 _fp = C.c_void_p   # device pointers travel as plain addresses
 
 
 class PolicyBatch(C.Structure):
     _fields_ = [(n, _fp) for n in ('image', 'road', 'vehicle', 'navigation', 'advantages', 'old_log_prob', 'speed',
-                                   'similarity', 'u', 'du_dalpha', 'du_dbeta')]
+                                   'similarity', 'u', 'du_dalpha', 'du_dbeta', 'anchor')]
 
 
 class ValueBatch(C.Structure):
@@ -125,6 +137,9 @@ PROTOTYPES = {
     'cdrl_learner_set_optimizer_state': (_i, [_L, C.POINTER(OptimizerState), _fp]),
     'cdrl_learner_gate_stats': (_i, [_L, C.POINTER(GateStats), _fp]),
     'cdrl_learner_gate_reset': (_i, [_L, _fp]),
+    'cdrl_learner_set_trust_params': (_i, [_L, C.POINTER(TrustParams), _fp]),
+    'cdrl_learner_trust_stats': (_i, [_L, C.POINTER(TrustStats), _fp]),
+    'cdrl_learner_trust_reset': (_i, [_L, _fp]),
     'cdrl_learner_train_stats_layout': (_i, [_L, C.POINTER(TrainStatsLayout)]),
     'cdrl_learner_train_stats_buffer': (_i, [_L, C.POINTER(C.c_void_p), C.POINTER(_i64)]),
     'cdrl_learner_train_stats_reset': (_i, [_L, _fp]),
@@ -258,6 +273,7 @@ PROTOTYPES = {
     'cdrl_bn_inference_stats': (_i, [_i, _pp, _pp, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_i), _fp, _fp]),
     'cdrl_bn_train_bwd_pooled': (_i, [_fp, _fp, _i, _i, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_beta_clone_loss': (_i, [_fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _f, _fp, _fp, _fp, _fp]),
+    'cdrl_beta_kl': (_i, [_fp, _fp, _i, _i, _f, _f, _fp, _fp, _fp]),
     'cdrl_ntxent_workspace_floats': (_i64, [_i, _i]),
     'cdrl_ntxent_loss': (_i, [_fp, _i, _i, _f, _f, _fp, _fp, _fp, _fp]),
     'cdrl_beta_ppo_loss': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _f, _fp, _fp, _fp, _fp, _fp]),

@@ -390,6 +390,8 @@ class CARLAgent(PPOAgent):
     def policy_batch_tensors(self):
         states, advantages, actions, log_probabilities = super().policy_batch_tensors()
         speed, similarity = self._info_with_replay(advantages.shape[0])
+        if self._trust_anchor is not None:      # target_kl / kl_penalty: the anchor rides along as a seventh component
+            return states, advantages, actions, log_probabilities, speed, similarity, self._trust_anchor
         return states, advantages, actions, log_probabilities, speed, similarity
 
     def value_batch_tensors(self):
@@ -399,7 +401,9 @@ class CARLAgent(PPOAgent):
 
     def _policy_pass(self, kind, batch, **extra):
         """The `kind` ('policy' / 'joint') pass on a policy batch (+ extra tensors), staged under that name; returns the engine."""
-        states, advantages, actions, log_probabilities, speed, similarity = batch
+        states, advantages, actions, log_probabilities, speed, similarity, *anchor = batch
+        if anchor:
+            extra = dict(extra, anchor=anchor[0])
         eng = self._step_engine = self.network.engine_for(advantages.shape[0])
         b = dict(states={k: states[k] for k in ('state_image', 'state_road', 'state_vehicle', 'state_navigation')},
                  advantages=advantages, old_log_prob=log_probabilities, speed=speed, similarity=similarity, u=actions, **extra)

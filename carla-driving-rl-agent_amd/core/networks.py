@@ -92,6 +92,8 @@ class CARLANetwork(Network):
                         head=p_branch['units'], exp_scale=self.exp_scale, compute=compute, freeze_trunk=not update_dynamics,
                         optimizer=getattr(agent, 'optimizer_name', 'adam'), polyak=float(getattr(agent, 'polyak_coeff', 1.0)),
                         clip_mode=getattr(agent, 'clip_mode', 'tensor'), skip_nonfinite=bool(getattr(agent, 'skip_nonfinite', False)))
+        if getattr(agent, 'trust', False):      # PPOAgent(target_kl=... / kl_penalty=...): the trust-region guard (cdrl_config.trust)
+            self.cfg['trust'] = True
         self.device = agent.device
         # update diagnostics: the learner engines only (main + ragged share one ring); off when the agent does not log
         self.train_stats_rows = int(getattr(agent, 'train_stats_rows', 0)) if agent.statistics.mode is not None else 0

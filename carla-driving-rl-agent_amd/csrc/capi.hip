@@ -35,7 +35,7 @@ static int policy_batch(const cdrl_policy_batch* b, bool need_u, const char* wha
         return -1;
     }
     *out = PolicyBatch{b->image, b->road, b->vehicle, b->navigation, b->advantages, b->old_log_prob, b->speed, b->similarity,
-                       need_u ? b->u : nullptr, need_u ? b->du_dalpha : nullptr, need_u ? b->du_dbeta : nullptr};
+                       need_u ? b->u : nullptr, need_u ? b->du_dalpha : nullptr, need_u ? b->du_dbeta : nullptr, b->anchor};
     if (!out->adv || !out->old_logp || !out->speed || !out->similarity || (need_u && !out->u)) {
         cdrl::set_error("%s: null tensor", what);
         return -1;
@@ -111,6 +111,7 @@ void cdrl_config_default(cdrl_config* c) {
     c->train_stats = d.train_stats;
     c->clip_mode = d.clip_mode;
     c->skip_nonfinite = d.skip_nonfinite;
+    c->trust = d.trust;
 }
 
 int cdrl_optimizer_slots(int optimizer, int32_t* used, float* init) {
@@ -190,6 +191,11 @@ int cdrl_learner_create(const cdrl_config* c, cdrl_learner** out) {
         return -1;
     }
     d.skip_nonfinite = c->skip_nonfinite;
+    if (c->trust != 0 && c->trust != 1) {
+        cdrl::set_error("cdrl_learner_create: trust must be 0 or 1 (got %d)", c->trust);
+        return -1;
+    }
+    d.trust = c->trust;
     if (cdrl::diag_active()) {      // loud, every time: results of this learner are WRONG by request (timing diagnostics)
         char ov[2048];
         cdrl::env_overrides(ov, (int)sizeof(ov));
@@ -320,6 +326,10 @@ int cdrl_learner_share_hparams(cdrl_learner* l, const cdrl_learner* owner) {
                         a.skip_nonfinite, b.clip_mode, b.skip_nonfinite);
         return -1;
     }
+    if (a.trust != b.trust) {      // one trust block: one latch
+        cdrl::set_error("cdrl_learner_share_hparams: trust differs (%d vs the owner's %d)", a.trust, b.trust);
+        return -1;
+    }
     if (a.train_stats > 0 && b.train_stats > 0 && (a.train_stats != b.train_stats || a.freeze_trunk != b.freeze_trunk)) {      // one ring: one layout
         cdrl::set_error("cdrl_learner_share_hparams: train_stats / freeze_trunk differ (%d, %d vs the owner's %d, %d)", a.train_stats,
                         a.freeze_trunk, b.train_stats, b.freeze_trunk);
@@ -401,6 +411,58 @@ int cdrl_learner_gate_reset(cdrl_learner* l, void* stream) {
         return -1;
     }
     return l->impl->gate_reset(S(stream));
+}
+
+int cdrl_learner_set_trust_params(cdrl_learner* l, const cdrl_trust_params* tp, void* stream) {
+    CHECK_L(l);
+    if (!tp) {
+        cdrl::set_error("cdrl_learner_set_trust_params: null parameters");
+        return -1;
+    }
+    if (!l->impl->trust_on()) {
+        cdrl::set_error("cdrl_learner_set_trust_params: the learner was created without trust = 1");
+        return -1;
+    }
+    // (NaN fails every comparison below)
+    if (!(tp->target_kl >= 0.0f) || !(tp->kl_stop_factor > 0.0f) || !(tp->kl_coef >= 0.0f)) {
+        cdrl::set_error("cdrl_learner_set_trust_params: target_kl = %g and kl_coef = %g must not be negative, kl_stop_factor = %g must be positive",
+                        (double)tp->target_kl, (double)tp->kl_coef, (double)tp->kl_stop_factor);
+        return -1;
+    }
+    cdrl::TrustBlock* t = l->impl->host_trust();
+    t->target_kl = tp->target_kl;
+    t->kl_stop_factor = tp->kl_stop_factor;
+    t->kl_coef = tp->kl_coef;
+    return l->impl->upload_trust(S(stream));
+}
+
+int cdrl_learner_trust_stats(const cdrl_learner* l, cdrl_trust_stats* out, void* stream) {
+    CHECK_L(l);
+    if (!out) {
+        cdrl::set_error("cdrl_learner_trust_stats: null output");
+        return -1;
+    }
+    if (!l->impl->trust_on()) {
+        cdrl::set_error("cdrl_learner_trust_stats: the learner was created without trust = 1");
+        return -1;
+    }
+    cdrl::TrustBlock t;
+    const int rc = l->impl->trust_stats(&t, S(stream));
+    if (rc) return rc;
+    out->target_kl = t.target_kl, out->kl_stop_factor = t.kl_stop_factor, out->kl_coef = t.kl_coef;
+    out->kl_last = t.kl_last, out->kl_max = t.kl_max;
+    out->passes = t.passes, out->stop = t.stop, out->stop_pass = t.stop_pass, out->armed = t.armed, out->skipped = t.skipped;
+    out->kl_sum = t.kl_sum;
+    return 0;
+}
+
+int cdrl_learner_trust_reset(cdrl_learner* l, void* stream) {
+    CHECK_L(l);
+    if (!l->impl->trust_on()) {
+        cdrl::set_error("cdrl_learner_trust_reset: the learner was created without trust = 1");
+        return -1;
+    }
+    return l->impl->trust_reset_block(S(stream));
 }
 
 int cdrl_learner_set_comm_stream(cdrl_learner* l, void* stream) {
@@ -1792,6 +1854,22 @@ int cdrl_beta_clone_loss(const float* lin, const float* u, const float* weight, 
     a.entropy_coef = entropy_coef; a.aux_weight = aux_weight; a.dlin = dlin; a.metrics = metrics; a.aux = aux;
     a.B = B; a.A = A; a.grad_scale = grad_scale;
     return clone_loss(a, S(stream));
+}
+
+int cdrl_beta_kl(const float* lin, const float* anchor, int B, int A, float kl_coef, float grad_scale, float* dlin, float* metrics,
+                 void* stream) {
+    if (!metrics) {
+        cdrl::set_error("cdrl_beta_kl: null metrics");
+        return -1;
+    }
+    if (!(kl_coef >= 0.0f)) {
+        cdrl::set_error("cdrl_beta_kl: kl_coef = %g must not be negative", (double)kl_coef);
+        return -1;
+    }
+    BetaKlArgs a;
+    a.lin = lin; a.anchor = anchor; a.dlin = dlin; a.trust = nullptr; a.kl_coef = kl_coef; a.metrics = metrics;
+    a.B = B; a.A = A; a.inv_world = grad_scale;
+    return beta_kl(a, S(stream));
 }
 
 int64_t cdrl_ntxent_workspace_floats(int B, int D) { return ntxent_workspace_floats(B, D); }

@@ -2,6 +2,7 @@
 // allocates, never synchronises, and returns 0 on success (<0: see cdrl::last_error()).
 #pragma once
 #include "cdrl_common.h"
+#include "trust_block.h"
 
 namespace cdrl {
 
@@ -598,6 +599,23 @@ struct CloneLossArgs {       // behaviour cloning: weighted Beta negative log-li
     float grad_scale;
 };
 int clone_loss(const CloneLossArgs& a, hipStream_t st);
+// Trust-region guard (trust.hip): the analytic KL(Beta(anchor) || Beta(policy)) of a policy minibatch, summed over a
+// row's actions and averaged over the rows, behind policy_loss and in front of the head's backward.
+struct BetaKlArgs {
+    const float* lin;        // [B][2A+2] as PolicyLossArgs::lin
+    const float* anchor;     // [B][2][A] alpha0, beta0 of the anchor policy
+    float* dlin;             // [B][2A+2], accumulated onto when the coefficient is positive; may be null when it is zero
+    TrustBlock* trust;       // device block: coefficient and thresholds read from it, statistics and latch written; or null ...
+    float kl_coef;           // ... then this coefficient, and nothing but metrics / dlin is written
+    float* metrics;          // [3] KL (clamped below at 0), its maximum over the rows, KL / A; or null
+    int B, A;
+    float inv_world;
+};
+int beta_kl(const BetaKlArgs& a, hipStream_t st);
+int trust_disarm(TrustBlock* trust, hipStream_t st);       // armed = 0, one thread
+// the host-written head, passed to the kernel by value (the caller's values may change as soon as the call returns)
+int trust_set_params(TrustBlock* trust, float target_kl, float kl_stop_factor, float kl_coef, hipStream_t st);
+int trust_reset(TrustBlock* trust, hipStream_t st);        // the device-owned fields to their initial values, one thread
 struct ValueLossArgs {
     const float* lin;        // [B][4]: base_pre, exp_pre, speed_pre, similarity_pre
     const float* returns;    // [B][2]
@@ -766,7 +784,9 @@ int gate_chunk_sqnorms(const float* g_head, const ChunkTable& tab_h, const float
 // One workgroup: folds the partials into the lists' squared norms (fixed order), writes scales, skip flag, last norms and the
 // skipped / applied counter, and -- unless the step is skipped -- ticks the step counters (head; trunk with GATE_TRUNK) and advances
 // the Nadam m_caches, as chunk_sqnorms_tick does on the ungated path.
-int gate_decide(const ChunkTable& tab_h, const ChunkTable& tab_t, DevHP* hp, GateBlock* gate, int head, int flags, hipStream_t st);
+// trust (or null): the apply is also skipped when the trust block says armed && stop, and counted there.
+int gate_decide(const ChunkTable& tab_h, const ChunkTable& tab_t, DevHP* hp, GateBlock* gate, int head, int flags, hipStream_t st,
+                TrustBlock* trust = nullptr);
 
 // ---------------------------------------------------------------- update diagnostics (train_stats.hip)
 // Chunk partials of a chunk table (sum of squares per 1024-element chunk, float64): one wave per chunk, no LDS.  Same partials

@@ -37,6 +37,8 @@ struct Config {
     int train_stats = 0;    // N > 0: device-resident ring of N update-diagnostics rows, one per apply step (include/cdrl.h)
     int clip_mode = 0;      // CDRL_CLIP_TENSOR: per-tensor clip of the heads; CDRL_CLIP_GLOBAL: every optimizer's list by its global norm
     int skip_nonfinite = 0; // 1: an apply step whose gradients hold a NaN / Inf writes nothing (include/cdrl.h, gradient gate)
+    int trust = 0;          // 1: trust-region guard of the policy steps (include/cdrl.h): policy passes with an anchor measure
+                            //    the Beta KL on the device, policy_apply takes the gated forms and obeys the block's latch
 };
 
 enum Model : int { M_TRUNK = 0, M_POLICY = 1, M_VALUE = 2, M_OLD_POLICY = 3 };
@@ -63,6 +65,7 @@ struct Buffers {
 struct PolicyBatch {
     const float *image, *road, *vehicle, *navigation;       // (B,T,...) reference layout
     const float *adv, *old_logp, *speed, *similarity, *u, *du_da, *du_db;
+    const float* anchor;                                    // (B,2,A) alpha0, beta0 of the anchor policy, or null (trust learners only)
 };
 struct ValueBatch {
     const float *image, *road, *vehicle, *navigation;
@@ -184,6 +187,7 @@ public:
         hp_dev_ = owner.hp_dev_;
         if (stats_ring_ && owner.stats_ring_) stats_ring_ = owner.stats_ring_;
         if (gate_dev_ && owner.gate_dev_) gate_dev_ = owner.gate_dev_;      // one gate block: one set of counters
+        if (trust_dev_ && owner.trust_dev_) trust_dev_ = owner.trust_dev_;  // one trust block: one latch
         drop_graphs();      // (captured kernel arguments name the block)
     }
     // Train-stats ring (cfg.train_stats rows; include/cdrl.h): STATS_HEADER int32 words -- [0] rows written since the last reset,
@@ -215,6 +219,15 @@ public:
     // Gradient gate (clip_mode = global and / or skip_nonfinite): the apply steps take the gated launch sequence (gated_apply)
     bool gate_on() const { return cfg_.clip_mode != 0 || cfg_.skip_nonfinite != 0; }
     GateBlock* host_gate() { return &gate_host_; }
+    // Trust-region guard (cfg.trust).  policy_apply of such a learner always takes the gated sequence (skip-only
+    // when neither gate option is on); value_apply, joint-free by construction, is never decided by the latch.
+    bool trust_on() const { return cfg_.trust != 0; }
+    TrustBlock* host_trust() { return &trust_host_; }
+    int upload_trust(hipStream_t st);       // the block's host-written head (target_kl, kl_stop_factor, kl_coef) -> device
+    // one device-to-host copy of the block behind everything on `st` (waits for it); the device-owned fields to their initial
+    // values, enqueued on `st`
+    int trust_stats(TrustBlock* out, hipStream_t st);
+    int trust_reset_block(hipStream_t st);
     // one device-to-host copy of the block behind everything on `st` (waits for it); counters to zero, enqueued on `st`
     int gate_stats(GateBlock* out, hipStream_t st);
     int gate_reset(hipStream_t st);
@@ -529,7 +542,10 @@ private:
     DevHP* hp_dev_ = nullptr;
     DevHP* hp_stage_ = nullptr;     // pinned host staging (DevHP, and one float behind it for the gate block's threshold)
     GateBlock gate_host_;           // only clip_norm_dynamics is the host's
-    GateBlock* gate_dev_ = nullptr; // in the workspace of a learner with gate_on() (this learner's, or the hyper-parameter owner's)
+    GateBlock* gate_dev_ = nullptr; // in the workspace of a learner with gate_on() or trust_on() (this learner's, or the hyper-parameter owner's)
+    TrustBlock trust_host_;         // its first TRUST_HOST_WORDS floats are the host's
+    TrustBlock* trust_dev_ = nullptr;       // in the workspace of a learner with trust_on() (this learner's, or the owner's)
+    int trust_refused(const PassSpec& s);   // an anchor without cfg.trust, a joint pass with it
     // with_trunk = false (the value head of a joint apply, whose trunk step the policy head's gated apply took): the head alone --
     // no trunk norm in the decision, no trunk update, no trunk tick
     int gated_apply(int head, hipStream_t st, bool with_trunk = true);

@@ -46,6 +46,9 @@ Learner::Learner(const Config& cfg) : cfg_(cfg) {
     memset(&gate_host_, 0, sizeof(gate_host_));
     gate_host_.scale_head = gate_host_.scale_trunk = 1.0f;
     for (int h = 0; h < 2; ++h) gate_host_.last_scale[h][0] = gate_host_.last_scale[h][1] = 1.0f;
+    memset(&trust_host_, 0, sizeof(trust_host_));
+    trust_host_.kl_stop_factor = 1.5f;
+    trust_host_.stop_pass = -1;
     at_ = cfg_.compute == 2 ? 1 : 0;
     guard_ = cdrl_getenv("CDRL_GUARD") && atoi(cdrl_getenv("CDRL_GUARD")) == 1;
     build(true);
@@ -1426,9 +1429,14 @@ void Learner::build(bool dry) {
         s.dev.chunk_part = alloc_d((size_t)nch);
         alloc((size_t)nt);      // unnamed padding: every offset behind the tables, and so the workspace size, is pinned by the planner's tests
     }
-    if (gate_on()) {
+    if (gate_on() || trust_on()) {
         gate_dev_ = reinterpret_cast<GateBlock*>(alloc(sizeof(GateBlock) / sizeof(float) + 4));
         note_named("gate", gate_dev_, sizeof(GateBlock));
+    }
+    if (trust_on()) {
+        trust_dev_ = reinterpret_cast<TrustBlock*>(alloc_d(sizeof(TrustBlock) / sizeof(double) + 2));
+        note_named("trust", trust_dev_, sizeof(TrustBlock));
+        note_named("policy.lin.g", lin_p_.g, (size_t)cfg_.B * (2 * A + 2) * sizeof(float));
     }
     if (cfg_.train_stats > 0) {
         stats_ring_ = alloc(stats_bytes() / sizeof(float));
@@ -1525,6 +1533,7 @@ int Learner::bind(const Buffers& b) {
     if (!hp_stage_) CDRL_HIP(hipHostMalloc(reinterpret_cast<void**>(&hp_stage_), sizeof(DevHP) + sizeof(float), 0));
     CDRL_HIP(hipMemcpy(hp_dev_, &hp_host_, sizeof(DevHP), hipMemcpyHostToDevice));
     if (gate_dev_) CDRL_HIP(hipMemcpy(gate_dev_, &gate_host_, sizeof(GateBlock), hipMemcpyHostToDevice));
+    if (trust_dev_) CDRL_HIP(hipMemcpy(trust_dev_, &trust_host_, sizeof(TrustBlock), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1538,6 +1547,38 @@ int Learner::upload_hp(hipStream_t st) {
         *stage = gate_host_.clip_norm_dynamics;
         CDRL_HIP(hipMemcpyAsync(gate_dev_, stage, sizeof(float), hipMemcpyHostToDevice, st));
     }
+    tail_invalidate(st);
+    return 0;
+}
+
+int Learner::upload_trust(hipStream_t st) {
+    if (!trust_dev_) {
+        set_error("set_trust_params: the learner was created without cdrl_config.trust = 1, or is not bound");
+        return -1;
+    }
+    // by value through a one-thread launch (as set_steps): no staging buffer that a later call could rewrite before this one has run
+    CDRL_TRY(trust_set_params(trust_dev_, trust_host_.target_kl, trust_host_.kl_stop_factor, trust_host_.kl_coef, st));
+    tail_invalidate(st);
+    return 0;
+}
+
+int Learner::trust_stats(TrustBlock* out, hipStream_t st) {
+    if (!trust_dev_) {
+        set_error("trust_stats: the learner was created without cdrl_config.trust = 1, or is not bound");
+        return -1;
+    }
+    CDRL_HIP(hipMemcpyAsync(out, trust_dev_, sizeof(TrustBlock), hipMemcpyDeviceToHost, st));
+    tail_invalidate(st);
+    CDRL_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int Learner::trust_reset_block(hipStream_t st) {
+    if (!trust_dev_) {
+        set_error("trust_reset: the learner was created without cdrl_config.trust = 1, or is not bound");
+        return -1;
+    }
+    CDRL_TRY(trust_reset(trust_dev_, st));
     tail_invalidate(st);
     return 0;
 }
@@ -1746,8 +1787,25 @@ int Learner::pass_backward(const PassSpec& s, hipStream_t st) {
     // gradients, and dyn_.g = d(policy loss)/d(dynamics) + d(value loss)/d(dynamics)
     const HeadBn0 &p0 = bn0_[0], &v0 = bn0_[1];
     if (s.repr) CDRL_TRY(ntxent_loss(ntxent_args(s), st));   // writes dyn_.g, where a head's bn0 backward would
+    // trust learner: a policy pass with an anchor measures its KL (and arms the latch for its apply) behind the policy loss; every
+    // other pass that an apply of the policy head or the trunk may follow disarms it, so that no old latch gates it
+    const bool measure = trust_on() && s.policy && s.policy->anchor;
+    if (trust_on() && !measure && (s.head() || s.repr)) CDRL_TRY(trust_disarm(trust_dev_, st));
     if (s.head()) {
         CDRL_TRY(s.policy ? policy_loss(policy_loss_args(s), st) : clone_loss(clone_loss_args(s), st));
+        if (measure) {
+            BetaKlArgs k;
+            k.lin = lin_p_.p;
+            k.anchor = s.policy->anchor;
+            k.dlin = lin_p_.g;
+            k.trust = trust_dev_;
+            k.kl_coef = 0.0f;
+            k.metrics = nullptr;
+            k.B = cfg_.B;
+            k.A = cfg_.A;
+            k.inv_world = s.inv_world;
+            CDRL_TRY(beta_kl(k, st));
+        }
         CDRL_TRY(run_bwd(policy_ops_, st, s.joint() ? p0.op + 1 : 0));
     }
     if (s.returns) {
@@ -1790,7 +1848,20 @@ int Learner::repr_refused() {
     return 0;
 }
 
+int Learner::trust_refused(const PassSpec& s) {
+    if (!trust_on() && s.policy && s.policy->anchor) {
+        set_error("policy batch: anchor given to a learner created without cdrl_config.trust = 1");
+        return -1;
+    }
+    if (trust_on() && s.joint()) {
+        set_error("joint pass: cdrl_config.trust = 1: the trust-region latch gates policy_apply only, half of a joint apply has no gated form");
+        return -1;
+    }
+    return 0;
+}
+
 int Learner::run_pass(const PassSpec& s, hipStream_t caller, bool fwd, bool bwd) {
+    CDRL_TRY(trust_refused(s));
     if (s.joint()) CDRL_TRY(joint_refused());
     if (s.repr) CDRL_TRY(repr_refused());
     if (s.inv_world != 1.0f) sched_.note_scaled_pass();
@@ -1801,6 +1872,7 @@ int Learner::run_pass(const PassSpec& s, hipStream_t caller, bool fwd, bool bwd)
         key = {s.repr ? KEY_REPR_PASS : s.clone_u ? KEY_CLONE_PASS : s.joint() ? KEY_JOINT_PASS : s.policy ? KEY_POLICY_PASS : KEY_VALUE_PASS,
                K(s.image), K(s.road), K(s.vehicle), K(s.navigation), K(s.speed), K(s.similarity), K(s.returns), Kf(s.inv_world)};
         if (const PolicyBatch* b = s.policy) key.insert(key.end(), {K(b->adv), K(b->old_logp), K(b->u), K(b->du_da), K(b->du_db)});
+        if (s.policy && s.policy->anchor) key.push_back(K(s.policy->anchor));
         if (s.clone_u) key.insert(key.end(), {K(s.clone_u), K(s.clone_w), Kf(s.policy_weight), Kf(s.value_weight), Kf(s.aux_weight)});
         if (s.repr) key.push_back(Kf(s.temperature));
     }
@@ -1889,6 +1961,10 @@ ArenaSlice Learner::arena_slice(int model) const {
 }
 
 int Learner::joint_apply(hipStream_t caller) {
+    if (trust_on()) {
+        set_error("joint_apply: cdrl_config.trust = 1: the trust-region latch gates policy_apply only, half of a joint apply has no gated form");
+        return -1;
+    }
     return launch(caller, {KEY_JOINT_APPLY}, true, [&](hipStream_t st) -> int { return joint_apply_impl(st); });
 }
 
@@ -1924,14 +2000,15 @@ int Learner::policy_apply(hipStream_t caller) {
 int Learner::gated_apply(int head, hipStream_t st, bool with_trunk) {
     const int hm = head == 0 ? M_POLICY : M_VALUE;
     const int opt = cfg_.optimizer;
+    // (a trust learner in tensor mode without the guard: the head's per-tensor clip still wants its chunk partials)
     const int flags = (cfg_.clip_mode == CDRL_CLIP_GLOBAL ? GATE_GLOBAL : 0) | (cfg_.skip_nonfinite ? GATE_GUARD : 0) |
                       (frozen() || !with_trunk ? 0 : GATE_TRUNK) | (opt == CDRL_OPT_NADAM ? GATE_NADAM : 0) |
-                      (cfg_.train_stats > 0 ? GATE_HEAD_PARTS : 0);
+                      (cfg_.train_stats > 0 || (trust_on() && cfg_.clip_mode != CDRL_CLIP_GLOBAL) ? GATE_HEAD_PARTS : 0);
     const int mode = cfg_.clip_mode == CDRL_CLIP_GLOBAL ? GATE_MODE_GLOBAL : GATE_MODE_TENSOR;
     const ChunkTable &s = seg_[hm].dev, &t = seg_[M_TRUNK].dev;
     const ArenaSlice ha = arena_slice(hm), ta = arena_slice(M_TRUNK);
     CDRL_TRY(gate_chunk_sqnorms(ha.g, s, ta.g, t, hp_dev_, gate_dev_, head, flags, st));
-    CDRL_TRY(gate_decide(s, t, hp_dev_, gate_dev_, head, flags, st));
+    CDRL_TRY(gate_decide(s, t, hp_dev_, gate_dev_, head, flags, st, head == 0 ? trust_dev_ : nullptr));      // (the latch: policy only)
     if (!frozen() && with_trunk) CDRL_TRY(clip_update(opt, 1.0f, ta, ChunkTable{}, hp_dev_, WHICH_TRUNK, st, TICKED, gate_dev_, mode));
     if (head == 0) CDRL_TRY(update_old_policy_impl(st, gate_dev_));
     CDRL_TRY(clip_update(opt, cfg_.polyak, ha, s, hp_dev_, head, st, TICKED, gate_dev_, mode));
@@ -1958,7 +2035,7 @@ int Learner::head_apply(int head, bool with_trunk, hipStream_t st) {
     return cfg_.train_stats > 0 ? stats_row(head, st) : 0;
 }
 
-int Learner::policy_apply_impl(hipStream_t st) { return gate_on() ? gated_apply(0, st) : head_apply(0, true, st); }
+int Learner::policy_apply_impl(hipStream_t st) { return gate_on() || trust_on() ? gated_apply(0, st) : head_apply(0, true, st); }
 int Learner::value_apply_impl(hipStream_t st) { return gate_on() ? gated_apply(1, st) : head_apply(1, true, st); }
 
 // Tail of an apply step with cfg.train_stats > 0: one ring row.  The gradients are read-only during the apply and the head's chunk

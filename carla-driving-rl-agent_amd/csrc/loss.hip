@@ -10,20 +10,9 @@
 //                action, with the entropy and auxiliary terms of policy_loss.
 // One workgroup, wavefront/LDS reductions in double: B is a few hundred rows, the kernels are
 // latency-bound, so everything transcendental (lgamma / digamma / trigamma) runs in double.
-#include "cdrl_kernels.h"
+#include "loss_bodies.h"      // digamma_d, softplus_d, sigmoid_d, block_reduce (shared with trust.hip)
 
 namespace cdrl {
-
-__device__ double digamma_d(double x) {
-    double r = 0.0;
-    while (x < 10.0) {
-        r -= 1.0 / x;
-        x += 1.0;
-    }
-    const double f = 1.0 / (x * x);
-    const double t = f * (-1.0 / 12.0 + f * (1.0 / 120.0 + f * (-1.0 / 252.0 + f * (1.0 / 240.0 + f * (-1.0 / 132.0)))));
-    return r + log(x) - 0.5 / x + t;
-}
 
 __device__ double trigamma_d(double x) {
     double r = 0.0;
@@ -35,27 +24,6 @@ __device__ double trigamma_d(double x) {
     const double t = 1.0 / x + 0.5 * f +
                      (1.0 / x) * f * (1.0 / 6.0 + f * (-1.0 / 30.0 + f * (1.0 / 42.0 + f * (-1.0 / 30.0 + f * (5.0 / 66.0)))));
     return r + t;
-}
-
-__device__ __forceinline__ double softplus_d(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
-__device__ __forceinline__ double sigmoid_d(double x) { return 1.0 / (1.0 + exp(-x)); }
-
-template <int NQ>
-__device__ void block_reduce(double* acc, double* sm) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) sm[q * blockDim.x + tid] = acc[q];
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) sm[q * blockDim.x + tid] += sm[q * blockDim.x + tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = sm[q * blockDim.x];
-    __syncthreads();
 }
 
 #define F32_EPS 1.1920929e-07f

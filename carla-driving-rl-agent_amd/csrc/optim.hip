@@ -309,13 +309,18 @@ __device__ __forceinline__ bool gate_finite(double s) { return s <= 1.7976931348
 
 __global__ void __launch_bounds__(256) gate_kernel(const double* __restrict__ part_h, int nchunks_h,
                                                    const double* __restrict__ part_t, int nchunks_t, DevHP* hp, GateBlock* gate,
-                                                   int head, int flags) {
+                                                   int head, int flags, TrustBlock* trust) {
     __shared__ double sm[256];
     const bool need_h = gate_needs(hp, gate, head, 0, flags), need_t = gate_needs(hp, gate, head, 1, flags);
     const double S_h = need_h ? gate_fold(part_h, nchunks_h, sm) : 0.0;
     const double S_t = need_t ? gate_fold(part_t, nchunks_t, sm) : 0.0;
     if (threadIdx.x != 0) return;
-    const int skip = (flags & GATE_GUARD) && !(gate_finite(S_h) && gate_finite(S_t)) ? 1 : 0;
+    int skip = (flags & GATE_GUARD) && !(gate_finite(S_h) && gate_finite(S_t)) ? 1 : 0;
+    // trust-region latch: the pass in front of this apply measured a KL (armed) and the run has left the region
+    if (trust && trust->armed && trust->stop) {
+        skip = 1;
+        trust->skipped += 1;
+    }
     const double n_h = sqrt(S_h), n_t = sqrt(S_t);
     float s_h = 1.0f, s_t = 1.0f;
     if (flags & GATE_GLOBAL) {      // s = (float)(c / max(sqrt(S), c)) in double, rounded once; at or below the threshold exactly 1
@@ -340,13 +345,14 @@ __global__ void __launch_bounds__(256) gate_kernel(const double* __restrict__ pa
                           ((flags & GATE_NADAM) ? TICK_NADAM : 0));
 }
 
-int gate_decide(const ChunkTable& tab_h, const ChunkTable& tab_t, DevHP* hp, GateBlock* gate, int head, int flags, hipStream_t st) {
+int gate_decide(const ChunkTable& tab_h, const ChunkTable& tab_t, DevHP* hp, GateBlock* gate, int head, int flags, hipStream_t st,
+                TrustBlock* trust) {
     if (head != 0 && head != 1) {
         set_error("gate_decide: head %d", head);
         return -1;
     }
     hipLaunchKernelGGL(gate_kernel, dim3(1), dim3(256), 0, st, tab_h.chunk_part, tab_h.nchunks, tab_t.chunk_part,
-                       (flags & GATE_TRUNK) ? tab_t.nchunks : 0, hp, gate, head, flags);
+                       (flags & GATE_TRUNK) ? tab_t.nchunks : 0, hp, gate, head, flags, trust);
     CDRL_LAUNCH_CHECK();
     return 0;
 }

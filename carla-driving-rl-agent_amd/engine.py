@@ -37,7 +37,7 @@ def make_config(B, T=4, H=90, W=120, road=9, vehicle=4, navigation=5, A=2, **kw)
             if v.lower() not in _lib.CLIP_MODES:
                 raise ValueError(f'unknown clip_mode {v!r}; select one of {_lib.CLIP_MODES}')
             v = _lib.CLIP_MODES.index(v.lower())
-        if k == 'skip_nonfinite' and isinstance(v, bool):
+        if k in ('skip_nonfinite', 'trust') and isinstance(v, bool):
             v = int(v)
         if k in ('stage_c', 'stage_n'):
             for i in range(3):
@@ -80,7 +80,11 @@ class LearnerEngine:
         or 'global' (every optimizer's gradient list clipped by its global norm: the heads with clip_norm_policy / clip_norm_value,
         the trunk with clip_norm_dynamics); an unknown name raises ValueError.  skip_nonfinite=True -> an apply step whose
         gradients hold a NaN or an Inf writes nothing and is counted (gate_stats).  Both are cdrl_config fields (include/cdrl.h,
-        gradient gate), off by default, and inherited through share_with (a different value there is refused by the library)."""
+        gradient gate), off by default, and inherited through share_with (a different value there is refused by the library).
+        trust=True -> the trust-region guard of the policy steps (cdrl_config.trust, include/cdrl.h): policy batches
+        may carry an 'anchor' (B, 2, A), whose Beta KL to the pass's policy is measured on the device; policy_apply obeys the
+        block's latch (set_hparams(target_kl=, kl_stop_factor=, kl_coef=), trust_stats, trust_reset).  Off by default, inherited
+        through share_with like the gate's options."""
         self.lib = _lib.load()
         if share_with is not None:
             cfg.setdefault('freeze_trunk', share_with.frozen)
@@ -88,6 +92,7 @@ class LearnerEngine:
             cfg.setdefault('polyak', share_with.polyak)
             cfg.setdefault('clip_mode', share_with.clip_mode)
             cfg.setdefault('skip_nonfinite', share_with.skip_nonfinite)
+            cfg.setdefault('trust', share_with.trust)
         self.cfg = make_config(B, **cfg)
         h = C.c_void_p()
         _lib.check(self.lib.cdrl_learner_create(C.byref(self.cfg), C.byref(h)), 'cdrl_learner_create')
@@ -98,6 +103,7 @@ class LearnerEngine:
         self.clip_mode = _lib.CLIP_MODES[self.cfg.clip_mode]
         self.skip_nonfinite = bool(self.cfg.skip_nonfinite)
         self.gated = self.clip_mode == 'global' or self.skip_nonfinite     # the apply steps run the gated sequence
+        self.trust = bool(self.cfg.trust)       # policy_apply runs the gated sequence and obeys the trust-region latch
         used, init = (C.c_int32 * 2)(), (C.c_float * 2)()
         _lib.check(self.lib.cdrl_optimizer_slots(self.cfg.optimizer, used, init), 'cdrl_optimizer_slots')
         self.slot_init = (float(init[0]), float(init[1]))       # initial value of the adam_m / adam_v arena's slot
@@ -111,6 +117,8 @@ class LearnerEngine:
         self.device = device
         self.hp = dict(policy_lr=3e-4, value_lr=3e-4, dynamics_lr=3e-4, clip_ratio=0.2, entropy_coef=1.0,
                        clip_norm_policy=1.0, clip_norm_value=1.0, beta1=0.9, beta2=0.999, eps=1e-7, clip_norm_dynamics=0.0)
+        if self.trust:
+            self.hp.update(target_kl=0.0, kl_stop_factor=1.5, kl_coef=0.0)
         self._keep = []
         self._keep_stage = {}
         self._pred_out = None
@@ -198,9 +206,14 @@ class LearnerEngine:
     def set_hparams(self, **kw):
         """Hyper-parameters of the following steps (cdrl_hparams).  clip_norm_* <= 0 or None: that clip is off.
         clip_norm_dynamics is the trunk's threshold with clip_mode='global'; with 'tensor' it is accepted and ignored (the trunk
-        is never clipped there, as in the reference)."""
+        is never clipped there, as in the reference).  target_kl / kl_stop_factor / kl_coef: the trust-region block's head
+        (cdrl_trust_params), on an engine built with trust=True only; target_kl None or 0: measure, never stop."""
         if getattr(self, '_hp_owner', None) is not None:
             return self._hp_owner.set_hparams(**kw)
+        if not self.trust:
+            for k in TRUST_PARAMS:
+                if k in kw:
+                    raise _lib.CdrlError(f'set_hparams({k}=...): this engine was built without trust=True')
         self.hp.update(kw)
         hp = _lib.HParams()
         for k in ('policy_lr', 'value_lr', 'dynamics_lr', 'clip_ratio', 'entropy_coef', 'beta1', 'beta2', 'eps'):
@@ -209,6 +222,9 @@ class LearnerEngine:
         hp.clip_norm_value = float(self.hp['clip_norm_value'] or 0.0)
         hp.clip_norm_dynamics = float(self.hp.get('clip_norm_dynamics') or 0.0)
         _lib.check(self.lib.cdrl_learner_set_hparams(self.h, C.byref(hp), self._stream()), 'set_hparams')
+        if self.trust:
+            tp = _lib.TrustParams(*(float(self.hp[k] or 0.0) for k in TRUST_PARAMS))
+            _lib.check(self.lib.cdrl_learner_set_trust_params(self.h, C.byref(tp), self._stream()), 'set_trust_params')
 
     def set_comm_stream(self, stream: Optional['torch.cuda.Stream']):
         """See cdrl_learner_set_comm_stream (data-parallel overlap); None switches it off."""
@@ -324,6 +340,20 @@ class LearnerEngine:
         """Skip / apply counters of the gradient gate to zero (enqueued on the current stream)."""
         self._need_device('gate_reset')
         _lib.check(self.lib.cdrl_learner_gate_reset(self.h, self._stream()), 'gate_reset')
+
+    def trust_stats(self) -> dict:
+        """The trust-region block (cdrl_trust_stats; the owner's under share_with): target_kl, kl_stop_factor, kl_coef as set;
+        kl_last, kl_max, kl_sum, passes of the measured passes since trust_reset; stop (the latch), stop_pass (-1 before), armed,
+        skipped (policy applies the latch left out).  ONE device-to-host copy behind everything on the current stream."""
+        self._need_device('trust_stats')
+        ts = _lib.TrustStats()
+        _lib.check(self.lib.cdrl_learner_trust_stats(self.h, C.byref(ts), self._stream()), 'trust_stats')
+        return {n: (float if t in (C.c_float, C.c_double) else int)(getattr(ts, n)) for n, t in ts._fields_}
+
+    def trust_reset(self):
+        """Latch, counters and sums of the trust-region block to their initial values (enqueued on the current stream)."""
+        self._need_device('trust_reset')
+        _lib.check(self.lib.cdrl_learner_trust_reset(self.h, self._stream()), 'trust_reset')
 
     def _stats_owner(self):
         owner = getattr(self, '_hp_owner', None)
@@ -443,7 +473,9 @@ class LearnerEngine:
         for k in ('speed', 'similarity'):
             if batch[k].numel() != c.B:
                 raise ValueError(f'{k}: expected {c.B} elements')
-        return _lib.PolicyBatch(image=img.data_ptr(), road=road.data_ptr(), vehicle=veh.data_ptr(),
+        self._chk(batch.get('anchor'), (c.B, 2, c.A), 'anchor')
+        return _lib.PolicyBatch(anchor=batch['anchor'].data_ptr() if batch.get('anchor') is not None else None,
+                                image=img.data_ptr(), road=road.data_ptr(), vehicle=veh.data_ptr(),
                                 navigation=nav.data_ptr(), advantages=batch['advantages'].data_ptr(),
                                 old_log_prob=batch['old_log_prob'].data_ptr(), speed=batch['speed'].data_ptr(),
                                 similarity=batch['similarity'].data_ptr(), u=batch['u'].data_ptr(),
@@ -645,6 +677,35 @@ class LearnerEngine:
         else:
             keys = ('loss', 'value_loss', 'speed_loss', 'similarity_loss')
         return {k: float(m[i]) for i, k in enumerate(keys)}
+
+
+TRUST_PARAMS = ('target_kl', 'kl_stop_factor', 'kl_coef')      # cdrl_trust_params, in this order
+BETA_KL_METRICS = ('kl', 'kl_row_max', 'kl_per_action')        # cdrl_beta_kl's metrics
+
+
+def beta_kl(lin: torch.Tensor, anchor: torch.Tensor, kl_coef: float = 0.0, grad_scale: float = 1.0, dlin: torch.Tensor = None,
+            metrics: torch.Tensor = None):
+    """Analytic KL(Beta(anchor) || Beta(policy head on lin)) (cdrl_beta_kl, one launch): lin (B, 2A+2) linear head outputs, anchor
+    (B, 2, A) alpha0 / beta0.  kl_coef > 0: dlin (B, 2A+2) += grad_scale * kl_coef * dKL/dlin in place; kl_coef == 0: dlin is not
+    touched (and may be None).  -> metrics (3,) device tensor: BETA_KL_METRICS."""
+    lib = _lib.load()
+    for name, t in (('lin', lin), ('anchor', anchor), ('dlin', dlin)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
+            raise ValueError(f'beta_kl: {name} must be a contiguous float32 device tensor, got {tuple(t.shape)} {t.dtype}')
+    if lin.dim() != 2 or lin.shape[1] < 4 or lin.shape[1] % 2:
+        raise ValueError(f'beta_kl: lin must be (B, 2A+2), got {tuple(lin.shape)}')
+    B, A = int(lin.shape[0]), (int(lin.shape[1]) - 2) // 2
+    if tuple(anchor.shape) != (B, 2, A):
+        raise ValueError(f'beta_kl: anchor must be ({B}, 2, {A}), got {tuple(anchor.shape)}')
+    if dlin is not None and tuple(dlin.shape) != tuple(lin.shape):
+        raise ValueError(f'beta_kl: dlin must have the shape of lin {tuple(lin.shape)}, got {tuple(dlin.shape)}')
+    if dlin is None and kl_coef != 0.0:
+        raise ValueError('beta_kl: kl_coef != 0 needs a dlin to add to')
+    if metrics is None:
+        metrics = torch.empty(3, dtype=torch.float32, device=lin.device)
+    _lib.check(lib.cdrl_beta_kl(_lib.ptr(lin), _lib.ptr(anchor), B, A, float(kl_coef), float(grad_scale), _lib.ptr(dlin),
+                                _lib.ptr(metrics), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cdrl_beta_kl')
+    return metrics
 
 
 # slots 0..7 of CDRL_BUF_METRICS_P after a clone pass (cdrl_beta_clone_loss, include/cdrl.h)

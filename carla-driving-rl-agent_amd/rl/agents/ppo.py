@@ -21,12 +21,14 @@ from ... import traces, train_stats
 
 class PPOAgent(Agent):
     replay, _replay_active = None, ()       # class-level defaults: an agent that never ran __init__ reuses nothing
+    trust, _trust_anchor, _trust_stats = False, None, None      # ... and has no trust-region guard
 
     def __init__(self, *args, policy_lr=1e-3, gamma=0.99, lambda_=0.95, value_lr=3e-4, load=False,
                  optimization_steps=(1, 1), name='ppo-agent', optimizer='adam', clip_norm=(1.0, 1.0), clip_ratio=0.2,
                  seed_regularization=False, entropy_regularization=0.0, network: dict = None, update_frequency=1,
                  polyak=1.0, repeat_action=1, advantage_scale=2.0, train_stats_rows=256, clip_mode='tensor', skip_nonfinite=False,
-                 joint_update=False, replay_rollouts=0, replay_rho_clip=1.0, replay_c_clip=1.0, **kwargs):
+                 joint_update=False, replay_rollouts=0, replay_rho_clip=1.0, replay_c_clip=1.0, target_kl=None, kl_penalty=0.0,
+                 kl_stop_factor=1.5, **kwargs):
         """clip_mode: 'tensor' (default; utils.clip_gradients of the reference: tf.clip_by_norm per tensor of each head) or 'global'
         (tf.clip_by_global_norm of each optimizer's gradient list, the max_grad_norm of other PPO implementations; thresholds are
         those of clip_norm).  skip_nonfinite=True: a minibatch step whose gradients hold a NaN or an Inf leaves parameters and
@@ -44,13 +46,36 @@ class PPOAgent(Agent):
         batch_size) and their targets corrected for the policy lag by V-trace in ONE launch (utils.vtrace_segments) with the
         importance ratio clipped at replay_rho_clip (TD weight) and replay_c_clip (trace cut); fresh rows keep their GAE targets bit
         for bit.  Needs the stored-action policy loss (an agent with a re-sampled loss refuses) and one GPU.  The store is not saved
-        by save_state(); clear_replay() empties it.  Nobody has measured what reuse does to driving quality."""
+        by save_state(); clear_replay() empties it.  Nobody has measured what reuse does to driving quality.
+        target_kl / kl_penalty / kl_stop_factor (not in the reference's constructor, not written to config.json): a
+        trust-region guard of the policy steps, on when target_kl is given or kl_penalty > 0.  update() then evaluates the acting
+        network once on all policy rows (the anchor), every policy minibatch pass measures the analytic Beta KL between the anchor
+        and its policy on the device, and -- with target_kl -- once a pass finds it above kl_stop_factor * target_kl (1.5: Spinning
+        Up's convention, not a measurement) the device leaves out every remaining policy apply of the update() and the remaining
+        policy epochs are not run (one small read per epoch); the value loop runs as before.  kl_penalty = c > 0 adds c * KL to the
+        policy objective.  Logged per update(): kl_divergence, kl_divergence_max, kl_stopped_steps, kl_stop_pass.  Needs the separate
+        policy / value loops (joint_update=True: ValueError) and one process (an initialised process group: ValueError -- the ranks
+        would decide differently); imitate() with a value weight runs joint passes, which such an agent's engines refuse.  Nobody has
+        measured what the guard does to learning or driving quality."""
         assert 0.0 < polyak <= 1.0
         self.joint_update = bool(joint_update)
         if self.joint_update and optimization_steps[0] != optimization_steps[1]:
             raise ValueError(f'joint_update=True runs one minibatch loop for both losses: optimization_steps must be equal, got '
                              f'{tuple(optimization_steps)}')
         assert repeat_action >= 1
+        self.target_kl = None if target_kl is None else float(target_kl)
+        self.kl_penalty, self.kl_stop_factor = float(kl_penalty), float(kl_stop_factor)
+        if (self.target_kl is not None and not self.target_kl >= 0.0) or not self.kl_penalty >= 0.0 or not self.kl_stop_factor > 0.0:
+            raise ValueError(f'target_kl={target_kl!r} and kl_penalty={kl_penalty!r} must not be negative and '
+                             f'kl_stop_factor={kl_stop_factor!r} must be positive')
+        self.trust = self.target_kl is not None or self.kl_penalty > 0.0        # reaches the learner engines through the network
+        if self.trust and self.joint_update:
+            raise ValueError('target_kl / kl_penalty need the separate policy and value loops: the trust-region latch gates the policy '
+                             'apply only, and half of a joint apply has no gated form; create the agent with joint_update=False')
+        if self.trust and torch.distributed.is_available() and torch.distributed.is_initialized():
+            raise ValueError('target_kl / kl_penalty run in one process: every rank would measure the KL of its own shard and decide '
+                             'on its own whether a collective step is taken; create the data-parallel agents without them')
+        self._trust_anchor = None                   # (N, 2, A) alpha0 / beta0 of the policy rows of the running update()
         if int(replay_rollouts) != replay_rollouts or replay_rollouts < 0:
             raise ValueError(f'replay_rollouts={replay_rollouts!r}: the number of finished update-periods to keep, an integer >= 0 '
                              f'(0 = no reuse)')
@@ -144,10 +169,13 @@ class PPOAgent(Agent):
 
     # -- update -----------------------------------------------------------------------------------
     def hyper_parameters(self) -> dict:
-        return dict(policy_lr=self.policy_lr(), value_lr=self.value_lr(), clip_ratio=self.clip_ratio(),
-                    entropy_coef=self.entropy_strength(),
-                    clip_norm_policy=self.grad_norm_policy if self.should_clip_policy_grads else 0.0,
-                    clip_norm_value=self.grad_norm_value if self.should_clip_value_grads else 0.0)
+        hp = dict(policy_lr=self.policy_lr(), value_lr=self.value_lr(), clip_ratio=self.clip_ratio(),
+                  entropy_coef=self.entropy_strength(),
+                  clip_norm_policy=self.grad_norm_policy if self.should_clip_policy_grads else 0.0,
+                  clip_norm_value=self.grad_norm_value if self.should_clip_value_grads else 0.0)
+        if self.trust:       # (only engines built with trust=True take them)
+            hp.update(target_kl=self.target_kl or 0.0, kl_stop_factor=self.kl_stop_factor, kl_coef=self.kl_penalty)
+        return hp
 
     def update(self):
         t0 = time.time()
@@ -157,6 +185,8 @@ class PPOAgent(Agent):
             self.refresh_replay()
         if self.joint_update:
             return self._update_joint(t0)
+        if self.trust:
+            self.begin_trust_region()
         value_batches = list(self.get_value_batches())
         policy_batches = list(self.get_policy_batches())
         policy_batches, value_batches = self.agree_on_batches(policy_batches, value_batches)
@@ -166,6 +196,8 @@ class PPOAgent(Agent):
                 total_loss, grads = self.get_policy_gradients(batch)
                 self.update_policy(grads)
                 self.log(loss_total=total_loss, lr_policy=self.policy_lr.value)
+            if self.trust and self.trust_region_left():
+                break
         for _ in range(self.optimization_steps['value']):
             for batch in value_batches:
                 self.seed_regularization()
@@ -175,11 +207,41 @@ class PPOAgent(Agent):
         self.after_update()
         self.log_train_stats()
         self.log_gate_stats()
+        if self.trust:
+            self.end_trust_region()
         if self.replay is not None:
             self.keep_period()
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         print(f'Update took {round(time.time() - t0, 3)}s')
+
+    # -- trust-region guard (target_kl / kl_penalty) -----------------------------------------------------------------
+    def begin_trust_region(self):
+        """Behind refresh_replay(), in front of the batch pipelines: the anchor of this update() -- (alpha0, beta0) of the acting
+        network on every policy row, fresh and kept, from ONE sweep of inference forwards in chunks of batch_size -- packed as
+        (N, 2, A), which travels through the batch pipeline as one more component of the policy batch; and the trust block's reset.
+        Nothing is sampled: the rollout sampler's offset and every generator stay where they were."""
+        states = self.with_replay(self.memory.states, 'states')
+        alpha, beta, _ = self.network.distribution_and_value(states, chunk=self.batch_size)
+        self._trust_anchor = torch.stack([alpha, beta], dim=1).contiguous()
+        self._trust_stats = None
+        self.network.engine.trust_reset()
+
+    def trust_region_left(self) -> bool:
+        """After a policy epoch: ONE small copy of the trust block (the only host read the guard adds).  True when the latch is
+        set: inside the epoch the device already left out every apply behind the pass that set it."""
+        self._trust_stats = self.network.engine.trust_stats()
+        return bool(self._trust_stats['stop'])
+
+    def end_trust_region(self):
+        st, self._trust_anchor = self._trust_stats, None
+        if st is None or not st['passes']:
+            return
+        self.log(kl_divergence=st['kl_sum'] / st['passes'], kl_divergence_max=st['kl_max'], kl_stopped_steps=st['skipped'],
+                 kl_stop_pass=st['stop_pass'])
+        if st['stop']:
+            print(f"[update] policy steps stopped early: KL {st['kl_max']:.3g} above {self.kl_stop_factor} * target_kl "
+                  f"{self.target_kl:.3g} at policy pass {st['stop_pass']}; {st['skipped']} minibatch steps left out")
 
     def _update_joint(self, t0):
         """update() with joint_update=True: one loop of optimization_steps['policy'] passes over the policy batch pipeline (the

@@ -44,6 +44,7 @@ typedef struct cdrl_config {
     int32_t train_stats;                   /* 0 (default, off) or N > 0: ring of N update-diagnostics rows; see cdrl_train_stats_layout */
     int32_t clip_mode;                     /* CDRL_CLIP_TENSOR (default) or CDRL_CLIP_GLOBAL; other values fail at create; see below   */
     int32_t skip_nonfinite;                /* 0 (default) or 1: skip apply steps with a non-finite gradient; other values fail; see below */
+    int32_t trust;                         /* 0 (default) or 1: trust-region guard of the policy steps; other values fail; see cdrl_trust_params */
 } cdrl_config;
 
 /* optimizer -- PPOAgent(optimizer=name) (reference rl/utils.py:29-46, rl/agents/ppo.py:105-106, core/carla_agent.py:123-124): one
@@ -160,6 +161,7 @@ typedef struct cdrl_policy_batch {
     const float *u;               /* (B, A) Beta sample (or stored action) */
     const float *du_dalpha;       /* (B, A) pathwise Jacobian or NULL */
     const float *du_dbeta;        /* (B, A) or NULL */
+    const float *anchor;          /* (B, 2, A) alpha0, beta0 of the anchor policy, or NULL; a learner with trust = 1 only (see cdrl_trust_params) */
 } cdrl_policy_batch;
 
 /* One value minibatch = CARLAgent.value_batch_tensors (core/carla_agent.py:333-349). */
@@ -257,6 +259,55 @@ typedef struct cdrl_gate_stats {
 } cdrl_gate_stats;
 int cdrl_learner_gate_stats(const cdrl_learner* l, cdrl_gate_stats* out, void* stream);
 int cdrl_learner_gate_reset(cdrl_learner* l, void* stream);
+
+/* ---- trust-region guard of the policy steps -----------------------------------
+ * cdrl_config.trust = 1, fixed at create and off by default: a learner without it enqueues exactly the launches it enqueues without
+ * the feature.  The ratio clip of the policy loss zeroes the surrogate's gradient of the rows outside its band; it does not keep the
+ * other rows, the entropy term or the auxiliary heads from carrying the policy further.  The guard measures how far the policy of
+ * the pass in flight is from an ANCHOR policy -- alpha0, beta0 per row and action, cdrl_policy_batch.anchor -- as the analytic
+ * KL(Beta(alpha0, beta0) || Beta(alpha, beta)) of cdrl_beta_kl (below), on the device, and latches when it leaves the region.
+ *
+ * On a learner with trust = 1:
+ *   policy_forward_backward(_resample), policy_backward with b->anchor != NULL: cdrl_beta_kl's kernel runs directly behind the policy
+ *     loss, in front of the head's backward.  It adds kl_coef * dKL/dlin to the head's dlin when kl_coef > 0 (and does not touch it
+ *     when kl_coef == 0), updates the block's statistics, sets `armed`, and sets the latch `stop` when target_kl > 0 and
+ *     !(kl <= kl_stop_factor * target_kl) -- a NaN KL (a broken anchor) stops the run.  The latch stays until _trust_reset.
+ *   a policy, clone or representation pass WITHOUT an anchor: one one-thread launch clears `armed`; its apply is never gated by an
+ *     old latch.
+ *   policy_apply: always the gated sequence of the gradient gate (per-tensor clip with CDRL_CLIP_TENSOR); the gate additionally
+ *     skips when armed && stop.  A skipped step leaves bit-identical what a skip_nonfinite skip leaves: the parameter arena
+ *     (old_policy included), the slot arenas, the three step counters, the Nadam m_caches -- the trunk's step is left out with the
+ *     head's -- and counts in `skipped` (and in cdrl_gate_stats.skipped[0]).  With finite gradients and no latch the step writes the
+ *     bits of the ungated step.  cdrl_learner_gate_stats / _gate_reset still fail unless clip_mode / skip_nonfinite ask for the gate.
+ *   value_apply: never decided by the latch (ungated unless clip_mode / skip_nonfinite gate it).
+ *   joint_forward_backward(_resample), clone_forward_backward with returns, joint_apply: -1 (gating half of a joint apply is not
+ *     defined).  An anchor handed to a learner WITHOUT trust: -1.  Both before any launch.
+ *   cdrl_learner_share_hparams: the two learners then also share the trust block (one latch); -1 when they disagree on trust.
+ * No pass or apply reads anything back to the host; all of them can be captured in a hipGraph.
+ *
+ * cdrl_learner_set_trust_params: the block's host-written head, enqueued on `stream` like cdrl_learner_set_hparams (of which it is
+ * the trust learner's extension: cdrl_hparams keeps its size).  Defaults at create: target_kl 0 (measure only, never latch),
+ * kl_stop_factor 1.5, kl_coef 0.  -1 for a negative or NaN value, a kl_stop_factor <= 0, or a learner without trust.
+ * cdrl_learner_trust_stats: ONE device-to-host copy of the block behind everything on `stream`, and waits for it.
+ * cdrl_learner_trust_reset: latch, counters and sums to their initial values (stop_pass -1), enqueued on `stream`, no host sync; the
+ * head stays.  The block is a diagnostic and a safeguard: it is neither part of cdrl_optimizer_state nor of a saved learner state. */
+typedef struct cdrl_trust_params {
+    float target_kl;        /* <= 0: never latch */
+    float kl_stop_factor;   /* the latch sets above kl_stop_factor * target_kl */
+    float kl_coef;          /* weight of the KL penalty's gradient; 0: none */
+} cdrl_trust_params;
+typedef struct cdrl_trust_stats {
+    float target_kl, kl_stop_factor, kl_coef;   /* as last set */
+    float kl_last, kl_max;                      /* KL of the last measured pass; largest since the reset */
+    int32_t passes;                             /* measured passes since the reset */
+    int32_t stop, stop_pass;                    /* the latch; index among the measured passes of the one that set it, -1 before */
+    int32_t armed;                              /* the last pass measured a KL */
+    int32_t skipped;                            /* policy applies the latch skipped since the reset */
+    double kl_sum;                              /* sum of kl_last over the measured passes */
+} cdrl_trust_stats;
+int cdrl_learner_set_trust_params(cdrl_learner* l, const cdrl_trust_params* tp, void* stream);
+int cdrl_learner_trust_stats(const cdrl_learner* l, cdrl_trust_stats* out, void* stream);
+int cdrl_learner_trust_reset(cdrl_learner* l, void* stream);
 
 /* ---- update diagnostics (train stats) --------------------------------------------------------
  * The scalars PPOAgent.update / CARLAgent.update log per minibatch (reference rl/agents/ppo.py:209-225; core/carla_agent.py:382,
@@ -1065,6 +1116,16 @@ int cdrl_beta_ppo_loss(const float* lin, const float* adv, const float* old_logp
                        float* hp_scratch16, void* stream);
 int cdrl_value_loss(const float* lin, const float* returns, const float* speed, const float* similarity, int B,
                     float exp_scale, float grad_scale, float* dlin, float* metrics, float* values, void* stream);
+/* Analytic KL between an anchor Beta policy and the Beta head on linear head outputs lin (B, 2A+2, as cdrl_beta_clone_loss): anchor
+ * (B, 2, A) = alpha0, beta0; alpha = softplus(lin) + 1.01 (beta likewise).  Per row and action
+ *   KL(Beta(a0,b0) || Beta(a,b)) = lnB(a,b) - lnB(a0,b0) + (a0-a) psi(a0) + (b0-b) psi(b0) + (a-a0+b-b0) psi(a0+b0);
+ * a row's KL is the sum over its actions (the joint distribution), kl = mean over the rows.  metrics: [0] max(kl, 0) (rounding can put
+ * a true zero slightly negative) [1] the largest row KL [2] metrics[0] / A.  A NaN in the anchor gives NaN in all three.
+ * kl_coef > 0: dlin (B, 2A+2) += grad_scale * kl_coef * d kl / d lin on the 2A distribution columns, one rounding per element
+ * (unclamped); kl_coef == 0: dlin is not read or written and may be NULL.  One workgroup; transcendentals and sums in double.
+ * A <= 8, kl_coef >= 0 (-1 and cdrl_last_error otherwise). */
+int cdrl_beta_kl(const float* lin, const float* anchor, int B, int A, float kl_coef, float grad_scale, float* dlin, float* metrics,
+                 void* stream);
 /* Behaviour-cloning loss of the Beta head on linear head outputs lin (B, 2A+2: A alpha, A beta, similarity, speed columns) and
  * expert actions u (B, A) in the unit interval.  alpha = softplus(lin) + 1.01 (beta likewise); x = clip(u, eps, 1 - eps) with the
  * float32 machine epsilon, no gradient through x; clone = mean_b w_b * (-mean_a log Beta(x; alpha, beta)), weight (B) or NULL = 1;
