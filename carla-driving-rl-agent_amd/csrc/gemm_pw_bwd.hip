@@ -59,6 +59,13 @@ __device__ __forceinline__ uint32_t pwb_lolo(uint32_t a, uint32_t b) { return __
 __device__ __forceinline__ uint32_t pwb_hihi(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
 
 // KP: padded input channels (k_in), NP: padded output channels (n_out); (128, 128) -> 32-row tiles, (64, 64) -> 64-row tiles.
+// LDS (float32 form): ONE row-major image per operand and split plane, [3][BM][LDR] of dy and [3][BM][LDA] of a, written as the
+// split produces them (8-byte stores, 16 lanes to 128 contiguous bytes).  da = dy W^T contracts over the columns of dy and reads its
+// rows (ds_read_b128); Q = a^T dy contracts over the tile's rows and reads 4-row x 16-column blocks of BOTH images column-major
+// (ds_read_b64_tr_b16, tr_frag in mfma_x3.h): element j of a lane's fragment is contraction index 8 lk + j, exactly what a 16-byte
+// read of a transposed copy delivered, so the MFMA sequence and every result bit are those of the transposed-copy layout this
+// replaced (three more planes of dy^T, a stored as a^T; two v_perm_b32 and a column-strided store per register pair).  The planes
+// use two thirds of the plan's lds_bytes or less; the plan's figure is still what is launched with (part of the plan's contract).
 // The two halves of the workgroup run DIFFERENT loops (scalar branch on the wave index: registers of one role are not live in
 // the other) with the same barrier sequence.
 template <int KP, int NP, bool SHUF, bool ANORM, bool ACC>
@@ -66,23 +73,30 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
     static_assert((KP == NP && (KP == 64 || KP == 128)) || (KP == 64 && NP == 128), "instantiated paddings: 64/64, 128/128, 64 -> 128");
     constexpr int BM = (KP == 128 || NP == 128) ? 32 : 64;
     constexpr int NRG = BM / 4;                     // row groups of 4
-    constexpr int LDR = NP + 8;                     // row-major planes: bf16 per row (16-byte fragment reads, conflict-free)
-    constexpr int LDT = BM + 8;                     // transposed planes: bf16 per column ((BM + 8) / 8 odd: conflict-free b128 reads)
-    constexpr int TPD = NP * LDT, TPA = KP * LDT;   // elements of one transposed plane of dy / of a
+    constexpr int NCG = NP / 4;                     // column groups of 4 (NRG * NCG = 256 micro-tiles, one per thread of a role)
+    // bf16 per plane row.  Bank step of a row (dwords mod 64): 36 (144-byte rows) | 12 (304-byte rows).  16-byte row reads: the 16
+    // rows of a ds_read_b128 lane group land on 16 different 4-bank slots (conflict-free, both); transposed reads: a 32-lane half
+    // takes 4 rows x 64 bytes, rows 0 / 2 and 1 / 3 overlap in 8 banks (36) or neighbours in 4 (12): 2-way.  (NP + 8 = 272-byte rows
+    // step 4 banks: the four rows of a transposed read would share 12 of their 16 banks, 4-way.)
+    constexpr int LDR = NP == 128 ? 152 : 72;       // dy planes
+    constexpr int LDA = KP == 128 ? 152 : 72;       // planes of a
+    constexpr int PLD = BM * LDR, PLA = BM * LDA;   // elements of one plane of dy / of a
+    static_assert((3 * PLD + 3 * PLA) * 2 <= (3 * BM * (NP + 8) + 3 * (NP + KP) * (BM + 8)) * 2, "inside the plan's lds_bytes (pwb_launch)");
     constexpr int KS_DA = NP / 16, KS_Q = BM / 16;
     constexpr int DA_WC = KP / 32, DA_WR = BM / 32; // backward-data tiles: DA_WC x DA_WR waves are busy (2 of 4 in the 64 -> 128 form)
     constexpr int Q_KT = KP / 32, Q_NT = NP / 32;
     constexpr int NTW = Q_KT * Q_NT / 4;            // Q tiles per wave (4 | 1 | 2): wave w owns k tile w % Q_KT, column tiles from (w / Q_KT) * NTW
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    __bf16* Rm = reinterpret_cast<__bf16*>(smem_raw);       // [3][BM][LDR]   dy, row-major
-    __bf16* Dt = Rm + 3 * BM * LDR;                         // [3][NP][LDT]   dy, transposed
-    __bf16* At = Dt + 3 * TPD;                              // [3][KP][LDT]   a (or xhat(a)), transposed
-    float* cf = reinterpret_cast<float*>(At + 3 * TPA);     // [7][NP] mean, invstd, scale, shift, k1, k2, k3 of the dy columns
+    __bf16* Rm = reinterpret_cast<__bf16*>(smem_raw);       // [3][BM][LDR]   dy: read by rows for da = dy W^T, by columns for Q
+    __bf16* Am = Rm + 3 * PLD;                              // [3][BM][LDA]   a (or xhat(a)): read by columns for Q
+    float* cf = reinterpret_cast<float*>(Am + 3 * PLA);     // [7][NP] mean, invstd, scale, shift, k1, k2, k3 of the dy columns
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lrow = lane & 31, lk = lane >> 5;
     const int role = __builtin_amdgcn_readfirstlane(tid >> 8);     // 0: waves 0-3 (dy + backward-data), 1: waves 4-7 (a + filter product)
     const int t2 = tid & 255;
-    const int rg = t2 % NRG, cg = t2 / NRG;         // micro-tile: rows 4 rg .. 4 rg + 3, columns 4 cg .. 4 cg + 3
+    // micro-tile: rows 4 rg .. 4 rg + 3, columns 4 cg .. 4 cg + 3.  Consecutive lanes take consecutive column groups: 16 lanes write
+    // 128 contiguous bytes of a plane row (one ds_write_b64 lane group, conflict-free) and load 256 contiguous bytes of a tensor row
+    const int cg = t2 % NCG, rg = t2 / NCG;
     const int c0 = 4 * cg;
     const int g = blockIdx.x / a.nbpg, b = blockIdx.x % a.nbpg;
     const int K = a.K, N = a.N;
@@ -257,20 +271,7 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
             cs[1] += (double)ts[0][1];
             cs[2] += (double)ts[1][0];
             cs[3] += (double)ts[1][1];
-            if (a.dbg & 2) {
-                if (hw[0][0][0] == 123u && hw[2][3][1] == 321u) Rm[0] = (__bf16)1.0f;      // keep the math alive
-                return;
-            }
-            // transposed planes: column c0 + e, rows 4 rg .. 4 rg + 3 = one v_perm_b32 per row pair
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    *reinterpret_cast<u32x2_t*>(&Dt[p * TPD + (c0 + 2 * h) * LDT + 4 * rg]) =
-                        u32x2_t{pwb_lolo(hw[p][0][h], hw[p][1][h]), pwb_lolo(hw[p][2][h], hw[p][3][h])};
-                    *reinterpret_cast<u32x2_t*>(&Dt[p * TPD + (c0 + 2 * h + 1) * LDT + 4 * rg]) =
-                        u32x2_t{pwb_hihi(hw[p][0][h], hw[p][1][h]), pwb_hihi(hw[p][2][h], hw[p][3][h])};
-                }
+            if ((a.dbg & 2) && hw[0][0][0] == 123u && hw[2][3][1] == 321u) Rm[0] = (__bf16)1.0f;      // keep the math alive
         };
         // output tile through a buffer descriptor: the row offset of register r is wave-uniform (SGPR soffset), the lane's part
         // (its 4 lk rows + its column) one constant voffset -- no 64-bit address per register (the flat form kept 16 of them live
@@ -388,43 +389,35 @@ __global__ void __launch_bounds__(512, 1) pwb_kernel(PwbArgs a) {
                 if (more) load_row(t + 1, j);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) x3_split2(vrow[h], hw[0][j][h], hw[1][j][h], hw[2][j][h]);
-            }
-            if (a.dbg & 2) {
-                if (hw[0][0][0] == 123u && hw[2][3][1] == 321u) At[0] = (__bf16)1.0f;
-                return;
-            }
-            if (aon) {
+                if (aon && !(a.dbg & 2)) {          // the conversion results as they are, as the dy planes
 #pragma unroll
-                for (int p = 0; p < 3; ++p)
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        *reinterpret_cast<u32x2_t*>(&At[p * TPA + (c0 + 2 * h) * LDT + 4 * rg]) =
-                            u32x2_t{pwb_lolo(hw[p][0][h], hw[p][1][h]), pwb_lolo(hw[p][2][h], hw[p][3][h])};
-                        *reinterpret_cast<u32x2_t*>(&At[p * TPA + (c0 + 2 * h + 1) * LDT + 4 * rg]) =
-                            u32x2_t{pwb_hihi(hw[p][0][h], hw[p][1][h]), pwb_hihi(hw[p][2][h], hw[p][3][h])};
-                    }
+                    for (int p = 0; p < 3; ++p)
+                        *reinterpret_cast<u32x2_t*>(&Am[p * PLA + (4 * rg + j) * LDA + c0]) = u32x2_t{hw[p][j][0], hw[p][j][1]};
+                }
             }
+            if ((a.dbg & 2) && hw[0][0][0] == 123u && hw[2][3][1] == 321u) Am[0] = (__bf16)1.0f;
         };
         f32x16 qacc[NTW];
 #pragma unroll
         for (int j = 0; j < NTW; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) qacc[j][r] = 0.0f;
+        // Q = a^T dy contracts over the tile's ROWS: both operands come out of the row-major planes by transposed reads (every lane
+        // of the wave is active here: the role split above is a scalar branch, and nothing below is lane-dependent)
+        const int ao = tr_frag_off(lane, LDA) + qkt * 32, bo = tr_frag_off(lane, LDR) + qnt0 * 32;
         auto compute_tile = [&]() {
-            const int ao = (qkt * 32 + lrow) * LDT + 8 * lk;
             if (!(a.dbg & 1))
 #pragma unroll
             for (int s = 0; s < KS_Q; ++s) {
                 __builtin_amdgcn_sched_barrier(0);
-                const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&At[0 * TPA + ao + 16 * s]);
-                const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(&At[1 * TPA + ao + 16 * s]);
-                const bf16x8 a3 = *reinterpret_cast<const bf16x8*>(&At[2 * TPA + ao + 16 * s]);
+                const bf16x8 a1 = tr_frag<LDA>(&Am[0 * PLA + 16 * s * LDA + ao]);
+                const bf16x8 a2 = tr_frag<LDA>(&Am[1 * PLA + 16 * s * LDA + ao]);
+                const bf16x8 a3 = tr_frag<LDA>(&Am[2 * PLA + 16 * s * LDA + ao]);
 #pragma unroll
                 for (int j = 0; j < NTW; ++j) {
-                    const int bo = ((qnt0 + j) * 32 + lrow) * LDT + 8 * lk + 16 * s;
-                    const bf16x8 d1 = *reinterpret_cast<const bf16x8*>(&Dt[0 * TPD + bo]);
-                    const bf16x8 d2 = *reinterpret_cast<const bf16x8*>(&Dt[1 * TPD + bo]);
-                    const bf16x8 d3 = *reinterpret_cast<const bf16x8*>(&Dt[2 * TPD + bo]);
+                    const bf16x8 d1 = tr_frag<LDR>(&Rm[0 * PLD + 16 * s * LDR + bo + 32 * j]);
+                    const bf16x8 d2 = tr_frag<LDR>(&Rm[1 * PLD + 16 * s * LDR + bo + 32 * j]);
+                    const bf16x8 d3 = tr_frag<LDR>(&Rm[2 * PLD + 16 * s * LDR + bo + 32 * j]);
                     qacc[j] = x3_mfma(a1, a2, a3, d1, d2, d3, qacc[j]);
                 }
             }

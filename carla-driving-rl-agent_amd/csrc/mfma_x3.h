@@ -63,6 +63,26 @@ __device__ __forceinline__ void x3_split2(f32x2 x, uint32_t& h1, uint32_t& h2, u
     h3 = bf16x2_pack(r1 - bf16x2_widen(h2));
 }
 
+// Operand fragments of v_mfma_f32_32x32x16_bf16 whose CONTRACTION index runs down the ROWS of a row-major LDS plane [m][ld]
+// (ds_read_b64_tr_b16: per 16 lanes a block of 4 rows x 16 columns, delivered column-major).  Both operands have the same shape
+// -- lane l owns index l & 31 (row of A / column of B) and contraction elements 8 (l >> 5) + j, j = 0..7 -- so one pair serves both:
+//     tr_frag_off(lane, ld):  element offset of the lane's address inside a block of 16 rows x 32 columns:
+//                             row 8 (l >> 5) + ((l & 15) >> 2), column 16 ((l >> 4) & 1) + 4 (l & 3)
+//     tr_frag(p):             p = plane + (first row) * ld + (first column) + tr_frag_off; element j of the result is row
+//                             8 (l >> 5) + j, column l & 31 of the block: two reads, rows +0..3 and +4..7, contraction order as a
+//                             16-byte read of the transposed plane would give
+// Conditions: every lane of the wave active (the gather crosses lanes), ld a multiple of 4 elements and the block's first column a
+// multiple of 4 (8-byte aligned lane addresses).  `ld` is a template argument so that the second read is an offset: immediate.
+__device__ __forceinline__ int tr_frag_off(int lane, int ld) { return (8 * (lane >> 5) + ((lane & 15) >> 2)) * ld + 16 * ((lane >> 4) & 1) + 4 * (lane & 3); }
+template <int LD>
+__device__ __forceinline__ bf16x8 tr_frag(const __bf16* p) {
+    static_assert(LD % 4 == 0, "8-byte aligned lane addresses");
+    typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p + 4 * LD));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 // one K = 16 step of the split product, smallest terms first (see the file header)
 __device__ __forceinline__ f32x16 x3_mfma(bf16x8 a1, bf16x8 a2, bf16x8 a3, bf16x8 b1, bf16x8 b2, bf16x8 b3, f32x16 acc) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3, b1, acc, 0, 0, 0);
