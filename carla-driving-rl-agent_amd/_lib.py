@@ -234,6 +234,7 @@ PROTOTYPES = {
     'cdrl_pwconv_bn_bwd': (_i, [_fp, _i, _i, _i, _i, _fp, _fp, _fp, _i, _i, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp]),
     'cdrl_dwconv_bn_workspace_doubles': (_i64, [_i] * 6),
     'cdrl_dwconv_bn_plan': (_i, [_i] * 6 + [C.POINTER(C.c_int32), _i]),
+    'cdrl_dwconv_bn_plan_ex': (_i, [_i] * 6 + [C.POINTER(C.c_int32), _i]),
     'cdrl_dwconv_bn_fwd': (_i, [_fp] * 5 + [_i] * 6 + [_fp] * 4 + [_i, _fp, _fp, _fp]),
     'cdrl_dwconv_bn_bwd': (_i, [_fp] * 6 + [_i] * 6 + [_fp] * 11),
     'cdrl_maxpool_fwd': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _fp]),

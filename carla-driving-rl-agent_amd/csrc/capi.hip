@@ -1213,44 +1213,72 @@ int cdrl_pwconv_bn_bwd_packed(const float* dout, int dout_ld, int dout_coff, int
 }
 
 int64_t cdrl_dwconv_bn_workspace_doubles(int G, int B, int H, int W, int C, int stride) {
-    const int Ho = same_out(H, stride), Wo = same_out(W, stride);
-    const int64_t nb_out = vcol_geom(B * Ho * Wo, C).nb, nb_in = vcol_geom(B * H * W, C).nb;
+    const DwfPlan p = dwf_plan(B, G, H, W, C, stride);
+    if (p.fwd.refusal == DWF_REFUSE_STRIDE) return 0;
+    const int64_t nb_out = vcol_geom(B * p.Ho * p.Wo, C).nb, nb_in = vcol_geom(B * H * W, C).nb;
     const int64_t nbm = nb_out > nb_in ? nb_out : nb_in;
-    return dwf_stats_part_elems(B, G, H, W, C, stride) + dwf_filter_part_elems(B, G, H, W, C, stride) + (int64_t)G * nbm * 3 * C;
+    return p.stats_part_elems + p.filter_part_elems + (int64_t)G * nbm * 3 * C;
+}
+
+// the plan as plain numbers, field order in include/cdrl.h: nothing here decides anything.  cdrl_dwconv_bn_plan reports the first
+// `count` = 22 of them (its callers size their arrays by that count), cdrl_dwconv_bn_plan_ex all of them.
+static int dwconv_bn_plan_fields(int G, int B, int H, int W, int C, int stride, int32_t* out, int n_out, int count) {
+    if (stride != 1 && stride != 2) return dwf_refuse("dwf_plan", DwfPlan(), DWF_REFUSE_STRIDE);
+    if (G < 1 || B < 1 || H < 1 || W < 1 || C < 1 || (!out && n_out > 0)) {
+        cdrl::set_error("dwf_plan: bad shape %dx%dx%dx%dx%d or null output", G, B, H, W, C);
+        return -1;
+    }
+    const DwfPlan p = dwf_plan(B, G, H, W, C, stride);
+    const DwsGeom& d = p.strip;
+    const int32_t v[] = {p.vec, p.nch, p.cchunk, p.cy, p.fpb, p.nb, p.vec_bwd, p.fpb_bwd, p.nb_bwd, p.bwd.form, d.sw, d.R, d.F, d.nch, d.cy,
+                         same_pad_before(W, 2),        // (= p.pl, the PL of form 2, for stride 2; reported for stride 1 as well)
+                         p.lds_bwd_over, p.fwd.refusal == DWF_REFUSE_LDS, p.cx, p.cx_bwd, p.cy_bwd, d.cx,
+                         d.cchunk, d.S, (int32_t)p.fwd.lds, (int32_t)p.bwd.lds, p.fwd.grid, p.bwd.grid, d.tile_floats * (int32_t)sizeof(float),
+                         p.fwd.refusal, p.bwd.refusal};
+    int n = 0;
+    for (int32_t x : v) {
+        if (n == count) break;
+        if (n < n_out) out[n] = x;
+        ++n;
+    }
+    return n;
 }
 
 int cdrl_dwconv_bn_plan(int G, int B, int H, int W, int C, int stride, int32_t* out, int n_out) {
-    return dwf_plan(B, G, H, W, C, stride, out, n_out);
+    return dwconv_bn_plan_fields(G, B, H, W, C, stride, out, n_out, 22);
+}
+
+int cdrl_dwconv_bn_plan_ex(int G, int B, int H, int W, int C, int stride, int32_t* out, int n_out) {
+    return dwconv_bn_plan_fields(G, B, H, W, C, stride, out, n_out, 1 << 30);
 }
 
 int cdrl_dwconv_bn_fwd(const float* x, const float* pre_stats, const float* w, const float* bias, float* y, int G, int B,
                        int H, int W, int C, int stride, const float* gamma, const float* beta, float* moving_mean,
                        float* moving_var, int bessel, float* post_stats, double* workspace, int act_type, void* stream) {
-    const int Ho = same_out(H, stride), Wo = same_out(W, stride);
-    CDRL_TRY(dwf_fwd(x, pre_stats, w, bias, y, workspace, G, B, H, W, C, stride, S(stream), act_type));
-    return bn_finalize(workspace, dwf_geom(B, G, H, W, C, stride).nb, G, B * Ho * Wo, C, gamma, beta, moving_mean, moving_var,
-                       bessel, 1, post_stats, S(stream));
+    const DwfPlan p = dwf_plan(B, G, H, W, C, stride);
+    CDRL_TRY(dwf_fwd(p, DwfFwdArgs{x, pre_stats, w, bias, y, workspace, S(stream), act_type}));
+    return bn_finalize(workspace, p.nb, G, B * p.Ho * p.Wo, C, gamma, beta, moving_mean, moving_var, bessel, 1, post_stats, S(stream));
 }
 
 int cdrl_dwconv_bn_bwd(const float* x, const float* pre_stats, const float* dout, const float* y, const float* post_stats,
                        const float* w, int G, int B, int H, int W, int C, int stride, float* dx, float* dw, float* db,
                        float* dgamma_post, float* dbeta_post, float* coef_post, float* dgamma_pre, float* dbeta_pre,
                        float* coef_pre, double* workspace, int act_type, void* stream) {
-    const int Ho = same_out(H, stride), Wo = same_out(W, stride);
-    const int Mo = B * Ho * Wo, Mi = B * H * W;
-    const DwfGeom g = dwf_geom(B, G, H, W, C, stride);
+    const DwfPlan p = dwf_plan(B, G, H, W, C, stride);
+    if (p.bwd.refusal == DWF_REFUSE_STRIDE) return dwf_refuse("dwf_bwd", p, p.bwd.refusal);
+    const int Mo = B * p.Ho * p.Wo, Mi = B * H * W;
     double* part_bn = workspace;
-    double* part_w = part_bn + dwf_stats_part_elems(B, G, H, W, C, stride);
-    double* part_r = part_w + dwf_filter_part_elems(B, G, H, W, C, stride);
+    double* part_w = part_bn + p.stats_part_elems;
+    double* part_r = part_w + p.filter_part_elems;
     hipStream_t st = S(stream);
     View vd = make_view(const_cast<float*>(dout), C), vy = make_view(const_cast<float*>(y), C);
     CDRL_TRY(bn_bwd_reduce(vd, 0, vy, G, Mo, C, post_stats, ACT_NONE, part_r, st, nullptr, nullptr, nullptr, 0, act_type));
     CDRL_TRY(bn_bwd_finalize(part_r, vcol_geom(Mo, C).nb, G, Mo, C, post_stats, dgamma_post, dbeta_post, coef_post, st));
-    CDRL_TRY(dwf_bwd(x, pre_stats, dout, y, post_stats, coef_post, w, make_view(dx, C), part_bn, part_w, G, B, H, W, C, stride, st, act_type));
-    CDRL_TRY(reduce_partials(part_w, G * g.nb_bwd, 9 * C, (int64_t)10 * C, dw, 0, st));
-    CDRL_TRY(reduce_partials(part_w + 9 * C, G * g.nb_bwd, C, (int64_t)10 * C, db, 0, st));
+    CDRL_TRY(dwf_bwd(p, DwfBwdArgs{x, pre_stats, dout, y, post_stats, coef_post, w, make_view(dx, C), part_bn, part_w, st, act_type}));
+    CDRL_TRY(reduce_partials(part_w, G * p.nb_bwd, 9 * C, (int64_t)10 * C, dw, 0, st));
+    CDRL_TRY(reduce_partials(part_w + 9 * C, G * p.nb_bwd, C, (int64_t)10 * C, db, 0, st));
     if (pre_stats) {
-        CDRL_TRY(bn_bwd_finalize(part_bn, g.nb_bwd, G, Mi, C, pre_stats, dgamma_pre, dbeta_pre, coef_pre, st));
+        CDRL_TRY(bn_bwd_finalize(part_bn, p.nb_bwd, G, Mi, C, pre_stats, dgamma_pre, dbeta_pre, coef_pre, st));
         View vx = make_view(const_cast<float*>(x), C);
         CDRL_TRY(bn_bwd_apply(make_view(dx, C), 0, vx, G, Mi, C, pre_stats, coef_pre, ACT_NONE, dx, part_r, st, nullptr, 0, act_type));
     }

@@ -322,38 +322,70 @@ int64_t dw_bwd_part_elems(int N, int H, int W, int C, int stride);
 int dw_bwd_filter(View a, const float* dy, float* dw, float* db, int N, int H, int W, int C, int stride,
                   double* part, hipStream_t st);
 // ---- fused depthwise block (dwfused.hip): whole frames staged in LDS.  G groups x B frames per group.
-// strip form of the backward (round 5): thread = channel pair x row strip of `sw` pixels; ok == false -> the pixel-mapped kernel runs
+// Every host decision of the family is one DwfPlan filled by dwf_plan: dwf_fwd / dwf_bwd launch from it, the engine
+// and the op-level entry points size their partial rows and workspaces from it, cdrl_dwconv_bn_plan reports it.
+// strip form of the backward (round 5): thread = channel pair x row strip of `sw` pixels; ok == false (every field 0) -> pixel-mapped
 struct DwsGeom {
-    bool ok;
-    int sw, S, R, F, cchunk, nch, cx, cy, wdp, tile_floats;    // S strips per row, R strips per thread and tile batch (stride 1), F frames
-    size_t lds;                                                // per tile batch, wdp padded tile width (stride 2)
+    bool ok = false;
+    int sw = 0, S = 0, R = 0, F = 0;           // S strips per row, R strips per thread and tile batch (stride 1), F frames per tile batch
+    int cchunk = 0, nch = 0, cx = 0, cy = 0;   // channels per chunk, chunks per frame, channel-pair lanes x strip lanes
+    int wdp = 0, tile_floats = 0;              // padded tile width (stride 2; 0 for stride 1), floats of the D tile
+    size_t lds = 0;
 };
-struct DwfGeom {
-    int vec, nch, cchunk, cx, cy, fpb, nb;     // nb: partial blocks per group (B / frames-per-block) of the FORWARD kernel
-    int vec_bwd, cx_bwd, cy_bwd;               // backward lane shape (fewer channels per thread: register budget)
-    size_t lds_fwd, lds_bwd;
-    int fpb_bwd, nb_bwd;                       // frames per workgroup / partial rows per group of the BACKWARD kernel
-    DwsGeom strip;
-};
-DwfGeom dwf_geom(int B, int G, int H, int W, int C, int stride);
-// dwf_fwd / the pixel-mapped dwf_bwd refuse a frame whose LDS tile (lds_fwd / lds_bwd) exceeds this even at the smallest channel chunk
+// a tile over this even at the smallest channel chunk is refused (forward, pixel-mapped backward)
 static constexpr size_t DWF_LDS_LIMIT = 150 * 1024;
-// dwf_geom's plan and the further inputs of the launch ladders as int32 fields (cdrl_dwconv_bn_plan); returns the field count
-int dwf_plan(int B, int G, int H, int W, int C, int stride, int32_t* out, int n_out);
-int64_t dwf_stats_part_elems(int B, int G, int H, int W, int C, int stride);      // doubles: [G][nb][2][C]
-int64_t dwf_filter_part_elems(int B, int G, int H, int W, int C, int stride);     // doubles: [G*nb][10][C]
+enum DwfRefusal {
+    DWF_OK = 0,
+    DWF_REFUSE_STRIDE = 1,      // stride is not 1 or 2
+    DWF_REFUSE_LDS = 2,         // the frame's tile exceeds DWF_LDS_LIMIT
+    DWF_REFUSE_OFFSETS = 3,     // strip forms: a gradient view of 2 GB or more (32-bit buffer offsets)
+};
+struct DwfLaunch {              // what one direction launches
+    int refusal = DWF_OK;
+    int form = 0;               // backward: 0 pixel-mapped, 1 stride-1 strips, 2 stride-2 strips; forward: 0
+    int a0 = 0, a1 = 0;         // the form's template arguments: (stride, VEC) | (SW, R) | (PL, 0)
+    int grid = 0, bx = 0, by = 0;
+    size_t lds = 0;
+};
+struct DwfPlan {
+    int G = 0, B = 0, H = 0, W = 0, C = 0, stride = 0, dx_ld = 0;
+    int Ho = 0, Wo = 0, pt = 0, pl = 0;                        // 'same' output size and top / left padding at `stride`
+    int vec = 0, nch = 0, cchunk = 0, cx = 0, cy = 0;          // forward lanes; nch, cchunk also of the pixel-mapped backward
+    int fpb = 0, nb = 0;                                       // forward: frames per workgroup, partial rows per group (B / fpb)
+    int vec_bwd = 0, cx_bwd = 0, cy_bwd = 0;                   // pixel-mapped backward lanes (fewer channels per thread: register budget)
+    size_t lds_fwd = 0, lds_bwd = 0;                           // tiles of the forward / the pixel-mapped backward
+    bool lds_bwd_over = false;                                 // lds_bwd > DWF_LDS_LIMIT, whichever form runs
+    int fpb_bwd = 0, nb_bwd = 0;                               // backward, the form that runs: frames per workgroup, partial rows per group
+    DwsGeom strip;
+    DwfLaunch fwd, bwd;
+    int64_t stats_part_elems = 0, filter_part_elems = 0;       // doubles: [G][max(nb, nb_bwd)][2 | 10][C], either direction fits
+};
+// dx_ld: leading dimension of the gradient view the backward writes (0: dense, C)
+DwfPlan dwf_plan(int B, int G, int H, int W, int C, int stride, int dx_ld = 0);
+int dwf_refuse(const char* who, const DwfPlan& p, int refusal);      // sets the refusal's message, returns -1
 // y = dw3x3(pre_stats ? relu6(scale*x+shift) : x) + bias and the per-block (sum y, sum y^2) partials of the
-// BatchNorm that follows (layout of bn_finalize with nb = dwf_geom().nb).
-int dwf_fwd(const float* x, const float* pre_stats, const float* w, const float* bias, float* y, double* part, int G,
-            int B, int H, int W, int C, int stride, hipStream_t st, int at = 0);
+// BatchNorm that follows (layout of bn_finalize with nb = plan.nb).
+struct DwfFwdArgs {
+    const float *x, *pre_stats, *w, *bias;
+    float* y;
+    double* part;
+    hipStream_t st;
+    int at;
+};
+int dwf_fwd(const DwfPlan& p, const DwfFwdArgs& a);
 // dout: gradient w.r.t. the output of the BatchNorm (no activation) that follows the depthwise conv; y2: the raw
 // depthwise output; post_stats / post_coef: that BN's statistics and backward coefficients (k1,k2,k3).
-// Writes the filter / bias partials (part_w: reduce with reduce_partials over G*nb parts, row stride 10*C) and
+// Writes the filter / bias partials (part_w: reduce with reduce_partials over G*nb_bwd parts, row stride 10*C) and
 //   pre_stats != null: dx = ReLU6-masked gradient at the pre-BN's output + its (sum dz, sum dz*xhat) partials
 //   pre_stats == null: dx = gradient w.r.t. x.
-int dwf_bwd(const float* x, const float* pre_stats, const float* dout, const float* y2, const float* post_stats,
-            const float* post_coef, const float* w, View dx, double* part_bn, double* part_w, int G, int B, int H, int W,
-            int C, int stride, hipStream_t st, int at = 0);
+struct DwfBwdArgs {
+    const float *x, *pre_stats, *dout, *y2, *post_stats, *post_coef, *w;
+    View dx;                    // no wider than the plan's dx_ld
+    double *part_bn, *part_w;
+    hipStream_t st;
+    int at;
+};
+int dwf_bwd(const DwfPlan& p, const DwfBwdArgs& a);
 int maxpool_fwd(const float* a, float* p, uint8_t* argmax, int N, int H, int W, int C, hipStream_t st);
 int maxpool_bwd(const uint8_t* argmax, const float* dp, float* da, int N, int H, int W, int C, hipStream_t st);
 // fused BN-apply + ReLU6 + max-pool on the raw conv output y (frames of group g = [g*frames_per_group, ...))

@@ -27,129 +27,16 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <array>
 
 #include "colreduce.h"
 
 namespace cdrl {
 
-// 4 workgroups per CU (160 KB LDS): frames wider than ~60 channels at 6x8 pixels run as two channel chunks (adjacent on one XCD, see
-// the block map in the kernels).  Re-measured in round 3 (ms / update-step at 38 | 52 | 76 KB): float32 B = 256 15.91 | 15.94 | 16.07,
-// float32 B = 1024 49.0 | - | 49.7, bf16 storage B = 1024 41.1 | 41.7 | 43.6 -- the phases of these kernels are separated by
-// barriers, and two resident workgroups (8 waves per CU) do not cover them.
-static constexpr size_t DWF_LDS_BUDGET = 38 * 1024;
-#define DWF_T_FWD 512                                    // threads per workgroup, forward / backward
+#define DWF_T_FWD 512                                    // launch bound of the forward / backward kernel (the plan asks for DWF_THREADS_*)
 #define DWF_T_BWD 512
-#define DWF_T_FWD_DEFAULT 256                            // (tunable: CDRL_DWF_TF / CDRL_DWF_TB, <= the maxima above; 256 vs 512 forward: -0.1 ms/update-step at v39)
-#define DWF_T_BWD_DEFAULT 256
 #define DWF_UF 8                                         // forward: loads in flight per thread (one tensor)
 #define DWF_U 4                                          // global loads in flight per thread in the tile loads
-
-static DwsGeom dws_geom(int B, int G, int fpb, int H, int W, int C);
-static DwsGeom dws2_geom(int B, int G, int fpb, int H, int W, int C);
-
-DwfGeom dwf_geom(int B, int G, int H, int W, int C, int stride) {
-    DwfGeom g;
-    const int Ho = same_out(H, stride), Wo = same_out(W, stride);
-    g.vec = (C % 4 == 0) ? 4 : ((C % 2 == 0) ? 2 : 1);
-    // tiles are zero-padded by one pixel per side
-    const size_t a_px = (size_t)(H + 2) * (W + 2);
-    const size_t d_px = (size_t)(Ho + 2) * (Wo + 2);
-    const size_t per_c = (a_px + d_px) * sizeof(float);
-    // (a separate budget for the stride-2 blocks, CDRL_DWF_LDS_KB_S2: 38 | 52 | 76 | 110 KB -> 15.76 | 15.74 | 15.82 | 16.07 ms / update-step
-    //  at float32 B = 256 and 40.6 | - | 41.9 ms at bf16-storage B = 1024: their backward kernel alone is faster with the larger tile
-    //  (105 vs 119 us), the step is not)
-    static const size_t lds_budget_s1 = DWF_LDS_BUDGET;
-    static const size_t lds_budget_s2 = lds_budget_s1;
-    size_t lds_budget = stride == 2 ? lds_budget_s2 : lds_budget_s1;
-    // wide frames (three-camera 90x360, 135x180): at 38 KB their channel chunks drop below ~24 channels -- a dozen channel lanes
-    // per workgroup and 5-6 chunks per frame (40.9 vs 38.3 ms / update-step at 90x360 with 76 KB) -- so the budget grows in steps
-    // until a chunk holds at least CDRL_DWF_MINCHUNK channels (or the whole frame)
-    // (22: the 11x15x58 units of the 90x120 configuration sit exactly there and were measured best at 38 KB; the stride-2 blocks of that
-    //  configuration, 8 channels per chunk, likewise: see above)
-    static const int min_chunk = 22;
-    static const int min_chunk_s2 = 8;   // (22x30x24 at 38 KB: 8)
-    for (const size_t kb : {52, 76}) {
-        const int mc = (int)(lds_budget / per_c) / g.vec * g.vec;
-        if (mc >= C || mc >= (stride == 2 ? min_chunk_s2 : min_chunk)) break;
-        if (lds_budget < kb * 1024) lds_budget = kb * 1024;
-    }
-    int maxc = (int)(lds_budget / per_c) / g.vec * g.vec;
-    if (maxc < g.vec) maxc = g.vec;
-    if (maxc > 256) maxc = 256;
-    const int lanes = C / g.vec;
-    if (maxc >= C) {
-        g.nch = 1;
-        g.cchunk = C;
-    } else {
-        int nch = cdiv(C, maxc);
-        g.cchunk = cdiv(lanes, nch) * g.vec;
-        g.nch = cdiv(C, g.cchunk);
-    }
-    // wide workgroups: the tile loads are a latency chain of (pixels / cy) rounds that every thread sits through before
-    // the first barrier, so the pixel lanes are made as many as the frame has output pixels (<= 1024 threads forward)
-    const int Po_ = Ho * Wo;
-    static const int t_fwd = DWF_T_FWD_DEFAULT;
-    static const int t_bwd = DWF_T_BWD_DEFAULT;
-    g.cx = g.cchunk / g.vec;
-    g.cy = t_fwd / g.cx;
-    if (g.cy > Po_) g.cy = Po_;
-    if (g.cy < 1) g.cy = 1;
-    // small frames: several frames per workgroup (fewer partials, less per-block overhead), keeping >= 512 blocks
-    int fpb = 1;
-    const int work = Ho * Wo * g.cx;
-    while (fpb < 8 && work * fpb * 2 <= 4096 && B % (fpb * 2) == 0 && (int64_t)G * (B / (fpb * 2)) * g.nch >= 512) fpb *= 2;
-    // large batches (configuration 3): once every CU has two rounds of 4 workgroups anyway, more frames per workgroup only shrink
-    // the partial rows (10 + 2 doubles per channel and workgroup: 38 MB per launch at B = 1024 with one frame each) and the
-    // finalize kernels that read them
-    static const int min_blocks = 2048;
-    while (fpb < 8 && B % (fpb * 2) == 0 && (int64_t)G * (B / (fpb * 2)) * g.nch >= min_blocks) fpb *= 2;
-    g.fpb = fpb;
-    g.nb = B / fpb;
-    // backward: 12 double accumulators per channel lane -> at 4 channels per thread the kernel needs > 256 VGPRs (one
-    // workgroup per CU); 2 channels per thread keep it at ~150 (3 waves / SIMD)
-    g.vec_bwd = g.vec > 2 ? 2 : g.vec;
-    g.cx_bwd = g.cchunk / g.vec_bwd;
-    g.cy_bwd = t_bwd / g.cx_bwd;
-    if (g.cy_bwd > Po_) g.cy_bwd = Po_;
-    if (g.cy_bwd < 1) g.cy_bwd = 1;
-    const size_t red_f = (size_t)2 * g.cy * g.vec * g.cx * sizeof(double);
-    const size_t red_b = (size_t)10 * g.cy_bwd * g.vec_bwd * g.cx_bwd * sizeof(double);
-    g.lds_fwd = a_px * g.cchunk * sizeof(float);
-    g.lds_bwd = (a_px + d_px) * g.cchunk * sizeof(float);
-    if (g.lds_fwd < red_f) g.lds_fwd = red_f;
-    if (g.lds_bwd < red_b) g.lds_bwd = red_b;
-    // Backward in strip form (whole pixel rows per workgroup where LDS allows): its own frames-per-workgroup count -- the largest
-    // power of two (<= 8) that still leaves CDRL_DWS_WGS workgroups.  Measured on the seven shapes of the 90x120 tower at B = 256
-    // (isolated, cold; 128 | 256 | 512 | 1024 workgroups): ONE workgroup of 6-10 waves per CU is the optimum -- 11x15x58 - | 38.5 | 43.3 |
-    // 52.1 us, 6x8x116 35.7 | 26.7 | 31.0 | 39.6, stride 2: 22x30x58 141 | 83.6 | 86.4 | 93.8, 11x15x116 79.2 | 48.9 | 52.8 | 61.1 -- except
-    // for the 3x4 frames (18.0 | 16.2 at 256 | 512): frames of <= 16 pixels take two per CU
-    g.fpb_bwd = g.fpb;
-    g.nb_bwd = g.nb;
-    g.strip.ok = false;
-    static const bool strips = !(cdrl_getenv("CDRL_DWS") && atoi(cdrl_getenv("CDRL_DWS")) == 0);
-    const int want_wgs = H * W <= 16 ? 512 : 256;
-    if (strips && (stride == 1 || stride == 2) && (int64_t)G * B * H * W * C * 8 < (int64_t)1 << 31) {
-        // (the channel-chunk count of the plan does not depend on fpb: plan with 1 first)
-        DwsGeom d = stride == 1 ? dws_geom(B, G, 1, H, W, C) : dws2_geom(B, G, 1, H, W, C);
-        if (d.ok) {
-            int fb = 1;
-            while (fb < 8 && B % (fb * 2) == 0 && (int64_t)G * (B / (fb * 2)) * d.nch >= want_wgs) fb *= 2;
-            g.strip = stride == 1 ? dws_geom(B, G, fb, H, W, C) : dws2_geom(B, G, fb, H, W, C);
-            g.fpb_bwd = fb;
-            g.nb_bwd = B / fb;
-        }
-    }
-    return g;
-}
-
-int64_t dwf_stats_part_elems(int B, int G, int H, int W, int C, int stride) {
-    const DwfGeom g = dwf_geom(B, G, H, W, C, stride);
-    return (int64_t)G * std::max(g.nb, g.nb_bwd) * 2 * C;
-}
-int64_t dwf_filter_part_elems(int B, int G, int H, int W, int C, int stride) {
-    const DwfGeom g = dwf_geom(B, G, H, W, C, stride);
-    return (int64_t)G * std::max(g.nb, g.nb_bwd) * 10 * C;
-}
 
 // reduce one double per (channel lane, vec) over the pixel lanes through LDS; result valid on ty == 0
 template <int VEC>
@@ -1151,16 +1038,45 @@ __global__ void __launch_bounds__(512) dws2_bwd_kernel(const T* __restrict__ x, 
                               PRE ? part_bn + ((int64_t)g * nb + b) * 2 * C + c : nullptr, C);
 }
 
-// strip geometry of the stride-1 backward; ok == false -> the pixel-mapped kernel runs
-static DwsGeom dws_geom(int B, int G, int fpb, int H, int W, int C) {
+// ========================================================================================================================
+// Host side: dwf_plan fills one DwfPlan with every dispatch decision; one launcher per kernel template passes
+// that kernel's arguments; one table per direction maps the plan's template arguments to the launcher of the same arguments.
+
+// Pixel-mapped kernels, LDS per workgroup.  4 workgroups per CU (160 KB LDS): frames wider than ~60 channels at 6x8 pixels run as
+// two channel chunks (adjacent on one XCD, see the block map in the kernels).  Re-measured in round 3 (ms / update-step at 38 | 52 |
+// 76 KB): float32 B = 256 15.91 | 15.94 | 16.07, float32 B = 1024 49.0 | - | 49.7, bf16 storage B = 1024 41.1 | 41.7 | 43.6 -- the
+// phases of these kernels are separated by barriers, and two resident workgroups (8 waves per CU) do not cover them.
+static constexpr size_t DWF_LDS_BUDGET = 38 * 1024;
+// The stride-2 blocks with a budget of their own (38 | 52 | 76 | 110 KB) gave 15.76 | 15.74 | 15.82 | 16.07 ms / update-step at float32
+// B = 256 and 40.6 | - | 41.9 ms at bf16-storage B = 1024: their backward kernel alone is faster with the larger tile (105 vs 119 us),
+// the step is not.  So they share the budget.
+static constexpr size_t DWF_LDS_BUDGET_S2 = DWF_LDS_BUDGET;
+// Wide frames (three-camera 90x360, 135x180): at 38 KB their channel chunks drop below ~24 channels -- a dozen channel lanes per
+// workgroup and 5-6 chunks per frame (40.9 vs 38.3 ms / update-step at 90x360 with 76 KB) -- so the budget grows in steps until a
+// chunk holds at least this many channels (or the whole frame).  22: the 11x15x58 units of the 90x120 configuration sit exactly
+// there and were measured best at 38 KB; the stride-2 blocks of that configuration (22x30x24 at 38 KB: 8 channels per chunk) likewise.
+static constexpr int DWF_MIN_CHUNK = 22, DWF_MIN_CHUNK_S2 = 8;
+static constexpr size_t DWF_LDS_STEPS_KB[] = {52, 76};
+// threads per workgroup the plan asks for (<= DWF_T_FWD / DWF_T_BWD; 256 vs 512 forward: -0.1 ms/update-step at v39)
+static constexpr int DWF_THREADS_FWD = 256, DWF_THREADS_BWD = 256;
+// frame loop: small frames (<= DWF_LOOP_WORK / 2 channel-lane pixels each) share a workgroup while DWF_LOOP_WGS workgroups remain;
+// any frame does once DWF_LOOP_WGS_LARGE remain
+static constexpr int DWF_LOOP_WORK = 4096, DWF_LOOP_WGS = 512, DWF_LOOP_WGS_LARGE = 2048;
+// strip forms: tile budget (stride 1 | 2), threads per workgroup (first tries | the second try of 8-pixel strips: DWS_LB), workgroups
+// the frame loop leaves (frames of <= DWS_SMALL_FRAME pixels: DWS_WGS_SMALL)
+static constexpr size_t DWS_LDS_BUDGET = 56 * 1024, DWS2_LDS_BUDGET = 60 * 1024;
+static constexpr int DWS_THREADS = 384, DWS_THREADS_WIDE = DWS_LB;
+static constexpr int DWS_WGS = 256, DWS_WGS_SMALL = 512, DWS_SMALL_FRAME = 16;
+
+static size_t dws_lds(const DwsGeom& d) {         // D tile + coefficient table [16][cchunk], or the reduce scratch of the tail
+    const size_t red = (size_t)d.cx * d.cy * (10 * 2 * sizeof(float) + 2 * 2 * sizeof(double));
+    return std::max((size_t)(d.tile_floats + 16 * d.cchunk) * sizeof(float), red);
+}
+
+// strip geometry of the stride-1 backward for `fpb` frames per workgroup; ok == false -> the pixel-mapped kernel runs
+static DwsGeom dws_geom(int fpb, int H, int W, int C) {
     DwsGeom d;
-    d.ok = false;
     if (C % 2 != 0) return d;
-    static const int lds_kb = 56;
-    static const int max_thr = 384;
-    const size_t budget = (size_t)lds_kb * 1024;
-    // strips of 8 pixels when every thread then has ONE strip per tile batch (the activated strips live in registers across the
-    // barrier: 16 VGPRs per strip of 8), strips of 4 with up to 3 per thread otherwise
     struct Try {
         int sw, thr, rmax;
     };
@@ -1170,7 +1086,7 @@ static DwsGeom dws_geom(int B, int G, int fpb, int H, int W, int C) {
     for (int nch = 1; nch <= 16; ++nch) {
         const int cchunk = cdiv(C / 2, nch) * 2;
         if (cchunk < 8 && nch > 1) break;
-        for (const Try t : {Try{8, max_thr, 1}, Try{8, 640, 1}, Try{4, max_thr, 3}}) {
+        for (const Try t : {Try{8, DWS_THREADS, 1}, Try{8, DWS_THREADS_WIDE, 1}, Try{4, DWS_THREADS, 3}}) {
             const int sw = t.sw;
             if (sw == 8 && W <= 4) continue;
             const int S = cdiv(W, sw);
@@ -1179,12 +1095,12 @@ static DwsGeom dws_geom(int B, int G, int fpb, int H, int W, int C) {
             const int maxcy = t.thr / cx;
             if (maxcy < 1) continue;
             const size_t lds1 = (size_t)Hp * Wp * cchunk * sizeof(float);
-            if (lds1 > budget) continue;
+            if (lds1 > DWS_LDS_BUDGET) continue;
             const int R = cdiv(NS1, maxcy);
             if (R > t.rmax) continue;
             int F = 1;
             if (R == 1)
-                while (F * 2 <= fpb && fpb % (F * 2) == 0 && (size_t)(F * 2) * lds1 <= budget && F * 2 * NS1 <= maxcy) F *= 2;
+                while (F * 2 <= fpb && fpb % (F * 2) == 0 && (size_t)(F * 2) * lds1 <= DWS_LDS_BUDGET && F * 2 * NS1 <= maxcy) F *= 2;
             d.ok = true;
             d.sw = sw;
             d.S = S;
@@ -1195,20 +1111,16 @@ static DwsGeom dws_geom(int B, int G, int fpb, int H, int W, int C) {
             d.cx = cx;
             d.cy = cdiv(F * NS1, R);
             d.tile_floats = F * Hp * Wp * cchunk;
-            const size_t red = (size_t)d.cx * d.cy * (10 * 2 * sizeof(float) + 2 * 2 * sizeof(double));
-            d.lds = std::max((size_t)(d.tile_floats + 16 * cchunk) * sizeof(float), red);
+            d.lds = dws_lds(d);
             return d;
         }
     }
     return d;
 }
 
-static DwsGeom dws2_geom(int B, int G, int fpb, int H, int W, int C) {
+static DwsGeom dws2_geom(int fpb, int H, int W, int C) {
     DwsGeom d;
-    d.ok = false;
     if (C % 2 != 0) return d;
-    static const int lds_kb = 60;
-    static const int max_thr = 384;
     const int Ho = same_out(H, 2), Wo = same_out(W, 2);
     const int S = cdiv(W, 8), NS1 = H * S;
     const int Wdp = std::max(4 * S + 2, Wo + 2), Hdp = Ho + 2;
@@ -1216,12 +1128,12 @@ static DwsGeom dws2_geom(int B, int G, int fpb, int H, int W, int C) {
         const int cchunk = cdiv(C / 2, nch) * 2;
         if (cchunk < 8 && nch > 1) break;
         const int cx = cchunk / 2;
-        const int maxcy = max_thr / cx;
+        const int maxcy = DWS_THREADS / cx;
         if (maxcy < 1) continue;
         const size_t lds1 = (size_t)Hdp * Wdp * cchunk * sizeof(float);
-        if (lds1 > (size_t)lds_kb * 1024) continue;
+        if (lds1 > DWS2_LDS_BUDGET) continue;
         int F = 1;
-        while (F * 2 <= fpb && fpb % (F * 2) == 0 && (size_t)(F * 2) * lds1 <= (size_t)lds_kb * 1024 && F * NS1 < maxcy) F *= 2;
+        while (F * 2 <= fpb && fpb % (F * 2) == 0 && (size_t)(F * 2) * lds1 <= DWS2_LDS_BUDGET && F * NS1 < maxcy) F *= 2;
         d.ok = true;
         d.sw = 8;
         d.S = S;
@@ -1233,200 +1145,224 @@ static DwsGeom dws2_geom(int B, int G, int fpb, int H, int W, int C) {
         d.cx = cx;
         d.cy = std::min(maxcy, F * NS1);
         d.tile_floats = F * Hdp * Wdp * cchunk;
-        const size_t red = (size_t)d.cx * d.cy * (10 * 2 * sizeof(float) + 2 * 2 * sizeof(double));
-        d.lds = std::max((size_t)(d.tile_floats + 16 * cchunk) * sizeof(float), red);
+        d.lds = dws_lds(d);
         return d;
     }
     return d;
 }
 
-template <int PL, bool PRE, class T>
-static int launch_dws2_bwd(const DwfGeom& g, const DwsGeom& d, hipStream_t st, const float* x, const float* pre_stats, const float* dout,
-                           const float* y2, const float* post_stats, const float* post_coef, const float* w, View dx, double* part_bn,
-                           double* part_w, int G, int B, int H, int W, int C) {
-    CDRL_TRY((allow_lds<dws2_bwd_kernel<PL, PRE, T>>(d.lds)));
-    hipLaunchKernelGGL((dws2_bwd_kernel<PL, PRE, T>), dim3(cdiv(G * g.nb_bwd, 8) * 8 * d.nch), dim3(d.cx, d.cy), d.lds, st,
-                       reinterpret_cast<const T*>(x), pre_stats, reinterpret_cast<const T*>(dout), reinterpret_cast<const T*>(y2), post_stats,
-                       post_coef, w, dx, part_bn, part_w, B, H, W, same_out(H, 2), same_out(W, 2), C, G * C, same_pad_before(H, 2), g.fpb_bwd,
-                       g.nb_bwd, d.cchunk, view_aligned(dx, 2), G * g.nb_bwd, d.F, d.S, d.wdp, d.tile_floats);
+DwfPlan dwf_plan(int B, int G, int H, int W, int C, int stride, int dx_ld) {
+    DwfPlan p;
+    p.G = G, p.B = B, p.H = H, p.W = W, p.C = C, p.stride = stride, p.dx_ld = dx_ld > 0 ? dx_ld : C;
+    if (stride != 1 && stride != 2) {
+        p.fwd.refusal = p.bwd.refusal = DWF_REFUSE_STRIDE;
+        return p;
+    }
+    const int Ho = p.Ho = same_out(H, stride), Wo = p.Wo = same_out(W, stride);
+    p.pt = same_pad_before(H, stride), p.pl = same_pad_before(W, stride);
+    p.vec = (C % 4 == 0) ? 4 : ((C % 2 == 0) ? 2 : 1);
+    // tiles are zero-padded by one pixel per side
+    const size_t a_px = (size_t)(H + 2) * (W + 2);
+    const size_t d_px = (size_t)(Ho + 2) * (Wo + 2);
+    const size_t per_c = (a_px + d_px) * sizeof(float);
+    size_t lds_budget = stride == 2 ? DWF_LDS_BUDGET_S2 : DWF_LDS_BUDGET;
+    for (const size_t kb : DWF_LDS_STEPS_KB) {
+        const int mc = (int)(lds_budget / per_c) / p.vec * p.vec;
+        if (mc >= C || mc >= (stride == 2 ? DWF_MIN_CHUNK_S2 : DWF_MIN_CHUNK)) break;
+        if (lds_budget < kb * 1024) lds_budget = kb * 1024;
+    }
+    int maxc = (int)(lds_budget / per_c) / p.vec * p.vec;
+    if (maxc < p.vec) maxc = p.vec;
+    if (maxc > 256) maxc = 256;
+    const int lanes = C / p.vec;
+    if (maxc >= C) {
+        p.nch = 1;
+        p.cchunk = C;
+    } else {
+        int nch = cdiv(C, maxc);
+        p.cchunk = cdiv(lanes, nch) * p.vec;
+        p.nch = cdiv(C, p.cchunk);
+    }
+    // wide workgroups: the tile loads are a latency chain of (pixels / cy) rounds that every thread sits through before
+    // the first barrier, so the pixel lanes are made as many as the frame has output pixels
+    const int Po_ = Ho * Wo;
+    p.cx = p.cchunk / p.vec;
+    p.cy = DWF_THREADS_FWD / p.cx;
+    if (p.cy > Po_) p.cy = Po_;
+    if (p.cy < 1) p.cy = 1;
+    // small frames: several frames per workgroup (fewer partials, less per-block overhead), keeping >= DWF_LOOP_WGS blocks
+    int fpb = 1;
+    const int work = Ho * Wo * p.cx;
+    while (fpb < 8 && work * fpb * 2 <= DWF_LOOP_WORK && B % (fpb * 2) == 0 && (int64_t)G * (B / (fpb * 2)) * p.nch >= DWF_LOOP_WGS) fpb *= 2;
+    // large batches (configuration 3): once every CU has two rounds of 4 workgroups anyway, more frames per workgroup only shrink
+    // the partial rows (10 + 2 doubles per channel and workgroup: 38 MB per launch at B = 1024 with one frame each) and the
+    // finalize kernels that read them
+    while (fpb < 8 && B % (fpb * 2) == 0 && (int64_t)G * (B / (fpb * 2)) * p.nch >= DWF_LOOP_WGS_LARGE) fpb *= 2;
+    p.fpb = fpb;
+    p.nb = B / fpb;
+    // backward: 12 double accumulators per channel lane -> at 4 channels per thread the kernel needs > 256 VGPRs (one
+    // workgroup per CU); 2 channels per thread keep it at ~150 (3 waves / SIMD)
+    p.vec_bwd = p.vec > 2 ? 2 : p.vec;
+    p.cx_bwd = p.cchunk / p.vec_bwd;
+    p.cy_bwd = DWF_THREADS_BWD / p.cx_bwd;
+    if (p.cy_bwd > Po_) p.cy_bwd = Po_;
+    if (p.cy_bwd < 1) p.cy_bwd = 1;
+    const size_t red_f = (size_t)2 * p.cy * p.vec * p.cx * sizeof(double);
+    const size_t red_b = (size_t)10 * p.cy_bwd * p.vec_bwd * p.cx_bwd * sizeof(double);
+    p.lds_fwd = std::max(a_px * p.cchunk * sizeof(float), red_f);
+    p.lds_bwd = std::max((a_px + d_px) * p.cchunk * sizeof(float), red_b);
+    p.lds_bwd_over = p.lds_bwd > DWF_LDS_LIMIT;
+    // Backward in strip form (whole pixel rows per workgroup where LDS allows): its own frames-per-workgroup count -- the largest
+    // power of two (<= 8) that still leaves DWS_WGS workgroups.  Measured on the seven shapes of the 90x120 tower at B = 256
+    // (isolated, cold; 128 | 256 | 512 | 1024 workgroups): ONE workgroup of 6-10 waves per CU is the optimum -- 11x15x58 - | 38.5 | 43.3 |
+    // 52.1 us, 6x8x116 35.7 | 26.7 | 31.0 | 39.6, stride 2: 22x30x58 141 | 83.6 | 86.4 | 93.8, 11x15x116 79.2 | 48.9 | 52.8 | 61.1 -- except
+    // for the 3x4 frames (18.0 | 16.2 at 256 | 512): frames of <= 16 pixels take two per CU.
+    // CDRL_DWS=0 (read once per process) sends every shape to the pixel-mapped form.
+    p.fpb_bwd = p.fpb;
+    p.nb_bwd = p.nb;
+    static const bool strips = !(cdrl_getenv("CDRL_DWS") && atoi(cdrl_getenv("CDRL_DWS")) == 0);
+    const int want_wgs = H * W <= DWS_SMALL_FRAME ? DWS_WGS_SMALL : DWS_WGS;
+    if (strips && (int64_t)G * B * H * W * C * 8 < (int64_t)1 << 31) {
+        // (the channel-chunk count of the strip geometry does not depend on fpb: plan with 1 first)
+        const DwsGeom d = stride == 1 ? dws_geom(1, H, W, C) : dws2_geom(1, H, W, C);
+        if (d.ok) {
+            int fb = 1;
+            while (fb < 8 && B % (fb * 2) == 0 && (int64_t)G * (B / (fb * 2)) * d.nch >= want_wgs) fb *= 2;
+            p.strip = stride == 1 ? dws_geom(fb, H, W, C) : dws2_geom(fb, H, W, C);
+            p.fpb_bwd = fb;
+            p.nb_bwd = B / fb;
+        }
+    }
+    p.stats_part_elems = (int64_t)G * std::max(p.nb, p.nb_bwd) * 2 * C;
+    p.filter_part_elems = (int64_t)G * std::max(p.nb, p.nb_bwd) * 10 * C;
+    // the decisions: block -> (frame block, channel chunk) map of the kernels: 8 frame blocks per XCD round, chunks adjacent
+    const DwsGeom& d = p.strip;
+    p.fwd.a0 = stride, p.fwd.a1 = p.vec;
+    p.fwd.grid = cdiv(G * p.nb, 8) * 8 * p.nch, p.fwd.bx = p.cx, p.fwd.by = p.cy, p.fwd.lds = p.lds_fwd;
+    if (p.lds_fwd > DWF_LDS_LIMIT) p.fwd.refusal = DWF_REFUSE_LDS;
+    p.bwd.form = d.ok ? stride : 0;
+    p.bwd.a0 = p.bwd.form == 0 ? stride : p.bwd.form == 1 ? d.sw : p.pl;
+    p.bwd.a1 = p.bwd.form == 0 ? p.vec_bwd : p.bwd.form == 1 ? d.R : 0;
+    p.bwd.grid = cdiv(G * p.nb_bwd, 8) * 8 * (d.ok ? d.nch : p.nch);
+    p.bwd.bx = d.ok ? d.cx : p.cx_bwd, p.bwd.by = d.ok ? d.cy : p.cy_bwd, p.bwd.lds = d.ok ? d.lds : p.lds_bwd;
+    // (the strip kernels address x, dout, y2 and dx through 32-bit byte offsets; 2 C was checked above, a wider dx view is refused)
+    if (d.ok && (int64_t)G * B * H * W * std::max(C, p.dx_ld) * 4 >= (int64_t)1 << 31) p.bwd.refusal = DWF_REFUSE_OFFSETS;
+    if (!d.ok && p.lds_bwd_over) p.bwd.refusal = DWF_REFUSE_LDS;
+    return p;
+}
+
+int dwf_refuse(const char* who, const DwfPlan& p, int refusal) {
+    if (refusal == DWF_REFUSE_STRIDE) set_error("%s: stride must be 1 or 2", who);
+    else if (refusal == DWF_REFUSE_LDS) set_error("%s: frame %dx%d does not fit LDS even at %d channels", who, p.H, p.W, p.cchunk);
+    else set_error("%s: gradient view too large for the strip kernels' 32-bit buffer offsets", who);
+    return -1;
+}
+
+template <int S, int VEC, bool PRE, class T>
+static int launch_dwf_fwd(const DwfPlan& p, const DwfFwdArgs& a) {
+    CDRL_TRY((allow_lds<dwf_fwd_kernel<S, VEC, PRE, T>>(p.fwd.lds)));
+    hipLaunchKernelGGL((dwf_fwd_kernel<S, VEC, PRE, T>), dim3(p.fwd.grid), dim3(p.fwd.bx, p.fwd.by), p.fwd.lds, a.st,
+                       reinterpret_cast<const T*>(a.x), a.pre_stats, a.w, a.bias, reinterpret_cast<T*>(a.y), a.part, p.B, p.H, p.W, p.Ho, p.Wo,
+                       p.C, p.G * p.C, p.pt, p.pl, p.fpb, p.nb, p.cchunk, p.G * p.nb);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int S, int VEC, bool PRE, class T>
+static int launch_dwf_bwd(const DwfPlan& p, const DwfBwdArgs& a) {
+    CDRL_TRY((allow_lds<dwf_bwd_kernel<S, VEC, PRE, T>>(p.bwd.lds)));
+    hipLaunchKernelGGL((dwf_bwd_kernel<S, VEC, PRE, T>), dim3(p.bwd.grid), dim3(p.bwd.bx, p.bwd.by), p.bwd.lds, a.st,
+                       reinterpret_cast<const T*>(a.x), a.pre_stats, reinterpret_cast<const T*>(a.dout), reinterpret_cast<const T*>(a.y2),
+                       a.post_stats, a.post_coef, a.w, a.dx, a.part_bn, a.part_w, p.B, p.H, p.W, p.Ho, p.Wo, p.C, p.G * p.C, p.pt, p.pl,
+                       p.fpb_bwd, p.nb_bwd, p.cchunk, view_aligned(a.dx, VEC), p.G * p.nb_bwd);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
 
 template <int SW, int R, bool PRE, class T>
-static int launch_dws_bwd(const DwfGeom& g, const DwsGeom& d, hipStream_t st, const float* x, const float* pre_stats, const float* dout,
-                          const float* y2, const float* post_stats, const float* post_coef, const float* w, View dx, double* part_bn,
-                          double* part_w, int G, int B, int H, int W, int C) {
-    CDRL_TRY((allow_lds<dws_bwd_kernel<SW, R, PRE, T>>(d.lds)));
-    hipLaunchKernelGGL((dws_bwd_kernel<SW, R, PRE, T>), dim3(cdiv(G * g.nb_bwd, 8) * 8 * d.nch), dim3(d.cx, d.cy), d.lds, st,
-                       reinterpret_cast<const T*>(x), pre_stats, reinterpret_cast<const T*>(dout), reinterpret_cast<const T*>(y2), post_stats,
-                       post_coef, w, dx, part_bn, part_w, B, H, W, C, G * C, g.fpb_bwd, g.nb_bwd, d.cchunk, view_aligned(dx, 2), G * g.nb_bwd,
-                       d.F, d.S, d.tile_floats);
+static int launch_dws_bwd(const DwfPlan& p, const DwfBwdArgs& a) {
+    const DwsGeom& d = p.strip;
+    CDRL_TRY((allow_lds<dws_bwd_kernel<SW, R, PRE, T>>(p.bwd.lds)));
+    hipLaunchKernelGGL((dws_bwd_kernel<SW, R, PRE, T>), dim3(p.bwd.grid), dim3(p.bwd.bx, p.bwd.by), p.bwd.lds, a.st,
+                       reinterpret_cast<const T*>(a.x), a.pre_stats, reinterpret_cast<const T*>(a.dout), reinterpret_cast<const T*>(a.y2),
+                       a.post_stats, a.post_coef, a.w, a.dx, a.part_bn, a.part_w, p.B, p.H, p.W, p.C, p.G * p.C, p.fpb_bwd, p.nb_bwd, d.cchunk,
+                       view_aligned(a.dx, 2), p.G * p.nb_bwd, d.F, d.S, d.tile_floats);
     CDRL_LAUNCH_CHECK();
     return 0;
 }
 
+template <int PL, bool PRE, class T>
+static int launch_dws2_bwd(const DwfPlan& p, const DwfBwdArgs& a) {
+    const DwsGeom& d = p.strip;
+    CDRL_TRY((allow_lds<dws2_bwd_kernel<PL, PRE, T>>(p.bwd.lds)));
+    hipLaunchKernelGGL((dws2_bwd_kernel<PL, PRE, T>), dim3(p.bwd.grid), dim3(p.bwd.bx, p.bwd.by), p.bwd.lds, a.st,
+                       reinterpret_cast<const T*>(a.x), a.pre_stats, reinterpret_cast<const T*>(a.dout), reinterpret_cast<const T*>(a.y2),
+                       a.post_stats, a.post_coef, a.w, a.dx, a.part_bn, a.part_w, p.B, p.H, p.W, p.Ho, p.Wo, p.C, p.G * p.C, p.pt, p.fpb_bwd,
+                       p.nb_bwd, d.cchunk, view_aligned(a.dx, 2), p.G * p.nb_bwd, d.F, d.S, d.wdp, d.tile_floats);
+    CDRL_LAUNCH_CHECK();
+    return 0;
+}
+
+// One table row per instantiation: the template arguments are stored next to the launcher they instantiate, and the lookup matches
+// them against the plan -- no computed index, no default row.
+template <class Args>
+struct DwfRow {
+    int form, a0, a1;
+    bool pre, bf16;
+    int (*launch)(const DwfPlan&, const Args&);
+};
 template <int S, int VEC, bool PRE, class T>
-static int launch_dwf_fwd(const DwfGeom& g, hipStream_t st, const float* x, const float* pre_stats, const float* w,
-                          const float* bias, float* y, double* part, int G, int B, int H, int W, int C) {
-    const int Ho = same_out(H, S), Wo = same_out(W, S);
-    CDRL_TRY((allow_lds<dwf_fwd_kernel<S, VEC, PRE, T>>(g.lds_fwd)));
-    hipLaunchKernelGGL((dwf_fwd_kernel<S, VEC, PRE, T>), dim3(cdiv(G * g.nb, 8) * 8 * g.nch), dim3(g.cx, g.cy), g.lds_fwd, st,
-                       reinterpret_cast<const T*>(x), pre_stats, w, bias, reinterpret_cast<T*>(y), part, B, H, W, Ho, Wo, C, G * C,
-                       same_pad_before(H, S), same_pad_before(W, S), g.fpb, g.nb, g.cchunk, G * g.nb);
-    CDRL_LAUNCH_CHECK();
-    return 0;
+static constexpr DwfRow<DwfFwdArgs> fwd_row() {
+    return {0, S, VEC, PRE, sizeof(T) == 2, launch_dwf_fwd<S, VEC, PRE, T>};
+}
+// FORM 0: dwf_bwd_kernel<A0 = stride, A1 = VEC>, 1: dws_bwd_kernel<A0 = SW, A1 = R>, 2: dws2_bwd_kernel<A0 = PL>
+template <int FORM, int A0, int A1, bool PRE, class T>
+static constexpr DwfRow<DwfBwdArgs> bwd_row() {
+    if constexpr (FORM == 0) return {FORM, A0, A1, PRE, sizeof(T) == 2, launch_dwf_bwd<A0, A1, PRE, T>};
+    else if constexpr (FORM == 1) return {FORM, A0, A1, PRE, sizeof(T) == 2, launch_dws_bwd<A0, A1, PRE, T>};
+    else return {FORM, A0, A1, PRE, sizeof(T) == 2, launch_dws2_bwd<A0, PRE, T>};
+}
+template <int... A>
+struct DwfRows {        // the four (PRE, tensor type) rows of one set of template arguments
+    static constexpr std::array<DwfRow<DwfFwdArgs>, 4> fwd() {
+        return {fwd_row<A..., false, float>(), fwd_row<A..., true, float>(), fwd_row<A..., false, bf16_t>(), fwd_row<A..., true, bf16_t>()};
+    }
+    static constexpr std::array<DwfRow<DwfBwdArgs>, 4> bwd() {
+        return {bwd_row<A..., false, float>(), bwd_row<A..., true, float>(), bwd_row<A..., false, bf16_t>(), bwd_row<A..., true, bf16_t>()};
+    }
+};
+// 6 x 4 = 24 forward kernels; (4 + 4 + 2) x 4 = 16 pixel-mapped + 16 stride-1 strip + 8 stride-2 strip backward kernels
+static const std::array<DwfRow<DwfFwdArgs>, 4> DWF_FWD_TABLE[] = {
+    DwfRows<1, 4>::fwd(), DwfRows<1, 2>::fwd(), DwfRows<1, 1>::fwd(), DwfRows<2, 4>::fwd(), DwfRows<2, 2>::fwd(), DwfRows<2, 1>::fwd()};
+static const std::array<DwfRow<DwfBwdArgs>, 4> DWF_BWD_TABLE[] = {
+    DwfRows<0, 1, 2>::bwd(), DwfRows<0, 1, 1>::bwd(), DwfRows<0, 2, 2>::bwd(), DwfRows<0, 2, 1>::bwd(),
+    DwfRows<1, 4, 1>::bwd(), DwfRows<1, 4, 2>::bwd(), DwfRows<1, 4, 3>::bwd(), DwfRows<1, 8, 1>::bwd(),
+    DwfRows<2, 0, 0>::bwd(), DwfRows<2, 1, 0>::bwd()};
+
+template <class Args, size_t N>
+static int dwf_dispatch(const char* who, const std::array<DwfRow<Args>, 4> (&table)[N], const DwfPlan& p, const DwfLaunch& l, const Args& a) {
+    if (l.refusal) return dwf_refuse(who, p, l.refusal);
+    for (const auto& rows : table)
+        for (const DwfRow<Args>& r : rows)
+            if (r.form == l.form && r.a0 == l.a0 && r.a1 == l.a1 && r.pre == (a.pre_stats != nullptr) && r.bf16 == (a.at != 0)) return r.launch(p, a);
+    set_error("%s: no kernel for the plan of %dx%dx%dx%dx%d stride %d: form %d <%d, %d>, pre %d, tensor type %d", who, p.G, p.B, p.H, p.W, p.C,
+              p.stride, l.form, l.a0, l.a1, (int)(a.pre_stats != nullptr), a.at);
+    return -1;
 }
 
-template <int S, int VEC>
-static int launch_dwf_fwd_pre(const DwfGeom& g, hipStream_t st, const float* x, const float* pre_stats, const float* w,
-                              const float* bias, float* y, double* part, int G, int B, int H, int W, int C, int at) {
-    if (at) {
-        if (pre_stats) return launch_dwf_fwd<S, VEC, true, bf16_t>(g, st, x, pre_stats, w, bias, y, part, G, B, H, W, C);
-        return launch_dwf_fwd<S, VEC, false, bf16_t>(g, st, x, pre_stats, w, bias, y, part, G, B, H, W, C);
-    }
-    if (pre_stats) return launch_dwf_fwd<S, VEC, true, float>(g, st, x, pre_stats, w, bias, y, part, G, B, H, W, C);
-    return launch_dwf_fwd<S, VEC, false, float>(g, st, x, pre_stats, w, bias, y, part, G, B, H, W, C);
-}
+int dwf_fwd(const DwfPlan& p, const DwfFwdArgs& a) { return dwf_dispatch("dwf_fwd", DWF_FWD_TABLE, p, p.fwd, a); }
 
-int dwf_fwd(const float* x, const float* pre_stats, const float* w, const float* bias, float* y, double* part, int G,
-            int B, int H, int W, int C, int stride, hipStream_t st, int at) {
-    if (stride != 1 && stride != 2) {
-        set_error("dwf_fwd: stride must be 1 or 2");
-        return -1;
-    }
-    const DwfGeom g = dwf_geom(B, G, H, W, C, stride);
-    if (g.lds_fwd > DWF_LDS_LIMIT) {
-        set_error("dwf_fwd: frame %dx%d does not fit LDS even at %d channels", H, W, g.cchunk);
-        return -1;
-    }
-#define CDRL_DWF_FWD(S, V) return launch_dwf_fwd_pre<S, V>(g, st, x, pre_stats, w, bias, y, part, G, B, H, W, C, at)
-    if (stride == 1) {
-        if (g.vec == 4) CDRL_DWF_FWD(1, 4);
-        if (g.vec == 2) CDRL_DWF_FWD(1, 2);
-        CDRL_DWF_FWD(1, 1);
-    }
-    if (g.vec == 4) CDRL_DWF_FWD(2, 4);
-    if (g.vec == 2) CDRL_DWF_FWD(2, 2);
-    CDRL_DWF_FWD(2, 1);
-#undef CDRL_DWF_FWD
-}
-
-template <int S, int VEC, bool PRE, class T>
-static int launch_dwf_bwd(const DwfGeom& g, hipStream_t st, const float* x, const float* pre_stats, const float* dout,
-                          const float* y2, const float* post_stats, const float* post_coef, const float* w, View dx,
-                          double* part_bn, double* part_w, int G, int B, int H, int W, int C) {
-    const int Ho = same_out(H, S), Wo = same_out(W, S);
-    CDRL_TRY((allow_lds<dwf_bwd_kernel<S, VEC, PRE, T>>(g.lds_bwd)));
-    hipLaunchKernelGGL((dwf_bwd_kernel<S, VEC, PRE, T>), dim3(cdiv(G * g.nb, 8) * 8 * g.nch), dim3(g.cx_bwd, g.cy_bwd), g.lds_bwd, st,
-                       reinterpret_cast<const T*>(x), pre_stats, reinterpret_cast<const T*>(dout), reinterpret_cast<const T*>(y2),
-                       post_stats, post_coef, w, dx, part_bn, part_w, B, H, W, Ho, Wo, C, G * C, same_pad_before(H, S),
-                       same_pad_before(W, S), g.fpb, g.nb, g.cchunk, view_aligned(dx, g.vec_bwd), G * g.nb);
-    CDRL_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int S, int VEC>
-static int launch_dwf_bwd_pre(const DwfGeom& g, hipStream_t st, const float* x, const float* pre_stats, const float* dout,
-                              const float* y2, const float* post_stats, const float* post_coef, const float* w, View dx,
-                              double* part_bn, double* part_w, int G, int B, int H, int W, int C, int at) {
-    if (at) {
-        if (pre_stats)
-            return launch_dwf_bwd<S, VEC, true, bf16_t>(g, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C);
-        return launch_dwf_bwd<S, VEC, false, bf16_t>(g, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C);
-    }
-    if (pre_stats)
-        return launch_dwf_bwd<S, VEC, true, float>(g, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C);
-    return launch_dwf_bwd<S, VEC, false, float>(g, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C);
-}
-
-int dwf_bwd(const float* x, const float* pre_stats, const float* dout, const float* y2, const float* post_stats,
-            const float* post_coef, const float* w, View dx, double* part_bn, double* part_w, int G, int B, int H, int W,
-            int C, int stride, hipStream_t st, int at) {
-    if (stride != 1 && stride != 2) {
-        set_error("dwf_bwd: stride must be 1 or 2");
-        return -1;
-    }
-    if (pre_stats && !part_bn) {
+int dwf_bwd(const DwfPlan& p, const DwfBwdArgs& a) {
+    if (p.bwd.refusal == DWF_REFUSE_STRIDE) return dwf_refuse("dwf_bwd", p, p.bwd.refusal);
+    if (a.pre_stats && !a.part_bn) {
         set_error("dwf_bwd: part_bn is required with a pre-BN prologue");
         return -1;
     }
-    const DwfGeom g = dwf_geom(B, G, H, W, C, stride);
-    // strip form (planned by dwf_geom: the partial-row count nb_bwd the caller finalizes with belongs to it)
-    if (g.strip.ok) {
-        const DwsGeom& d = g.strip;
-        if ((int64_t)G * B * H * W * std::max(C, dx.ld) * 4 >= (int64_t)1 << 31) {
-            set_error("dwf_bwd: gradient view too large for the strip kernels' 32-bit buffer offsets");
-            return -1;
-        }
-        if (stride == 1) {
-#define CDRL_DWS(SWV, RV)                                                                                                                                  \
-    do {                                                                                                                                                   \
-        if (pre_stats)                                                                                                                                     \
-            return at ? launch_dws_bwd<SWV, RV, true, bf16_t>(g, d, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C) \
-                      : launch_dws_bwd<SWV, RV, true, float>(g, d, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C); \
-        return at ? launch_dws_bwd<SWV, RV, false, bf16_t>(g, d, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C)   \
-                  : launch_dws_bwd<SWV, RV, false, float>(g, d, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C);  \
-    } while (0)
-            if (d.sw == 4) {
-                if (d.R == 1) CDRL_DWS(4, 1);
-                if (d.R == 2) CDRL_DWS(4, 2);
-                CDRL_DWS(4, 3);
-            }
-            CDRL_DWS(8, 1);
-#undef CDRL_DWS
-        }
-        const int pl = same_pad_before(W, 2);
-#define CDRL_DWS2(PLV, PREV)                                                                                                                             \
-    return at ? launch_dws2_bwd<PLV, PREV, bf16_t>(g, d, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C) \
-              : launch_dws2_bwd<PLV, PREV, float>(g, d, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C)
-        if (pre_stats) {
-            if (pl) CDRL_DWS2(1, true);
-            CDRL_DWS2(0, true);
-        }
-        if (pl) CDRL_DWS2(1, false);
-        CDRL_DWS2(0, false);
-#undef CDRL_DWS2
-    }
-    if (g.lds_bwd > DWF_LDS_LIMIT) {
-        set_error("dwf_bwd: frame %dx%d does not fit LDS even at %d channels", H, W, g.cchunk);
+    if (a.dx.ld > std::max(p.C, p.dx_ld)) {      // (the strip forms' offset bound was checked for the planned width)
+        set_error("dwf_bwd: the plan was made for a gradient view of leading dimension %d, not %d", p.dx_ld, a.dx.ld);
         return -1;
     }
-#define CDRL_DWF_BWD(S, V) \
-    return launch_dwf_bwd_pre<S, V>(g, st, x, pre_stats, dout, y2, post_stats, post_coef, w, dx, part_bn, part_w, G, B, H, W, C, at)
-    if (stride == 1) {
-        if (g.vec_bwd == 2) CDRL_DWF_BWD(1, 2);
-        CDRL_DWF_BWD(1, 1);
-    }
-    if (g.vec_bwd == 2) CDRL_DWF_BWD(2, 2);
-    CDRL_DWF_BWD(2, 1);
-#undef CDRL_DWF_BWD
-}
-
-// The plan the two launch ladders above dispatch on, as plain numbers (cdrl_dwconv_bn_plan, field order in include/cdrl.h): read-only,
-// nothing here decides anything -- dwf_geom does, and the ladders' own inputs (strip.ok, strip.sw, strip.R, same_pad_before(W, 2),
-// the LDS limit) are reported as they are read there.
-int dwf_plan(int B, int G, int H, int W, int C, int stride, int32_t* out, int n_out) {
-    if (stride != 1 && stride != 2) {
-        set_error("dwf_plan: stride must be 1 or 2");
-        return -1;
-    }
-    if (G < 1 || B < 1 || H < 1 || W < 1 || C < 1 || (!out && n_out > 0)) {
-        set_error("dwf_plan: bad shape %dx%dx%dx%dx%d or null output", G, B, H, W, C);
-        return -1;
-    }
-    const DwfGeom g = dwf_geom(B, G, H, W, C, stride);
-    const DwsGeom& d = g.strip;
-    const int32_t f[] = {g.vec, g.nch, g.cchunk, g.cy, g.fpb, g.nb, g.vec_bwd, g.fpb_bwd, g.nb_bwd,
-                         d.ok ? stride : 0,
-                         d.ok ? d.sw : 0, d.ok ? d.R : 0, d.ok ? d.F : 0, d.ok ? d.nch : 0, d.ok ? d.cy : 0,
-                         same_pad_before(W, 2),
-                         g.lds_bwd > DWF_LDS_LIMIT,
-                         g.lds_fwd > DWF_LDS_LIMIT,
-                         g.cx, g.cx_bwd, g.cy_bwd, d.ok ? d.cx : 0};
-    const int n = (int)(sizeof(f) / sizeof(f[0]));
-    for (int i = 0; i < n && i < n_out; ++i) out[i] = f[i];
-    return n;
+    return dwf_dispatch("dwf_bwd", DWF_BWD_TABLE, p, p.bwd, a);
 }
 
 }  // namespace cdrl

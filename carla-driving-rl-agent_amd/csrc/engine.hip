@@ -701,11 +701,11 @@ Learner::BnRec Learner::add_dw_block(std::vector<Op>& ops, const DwBlock& d) {
     const bool pre_apply_by_conv = d.pre_conv.bwd != PwBwd::Plain, pre_fin_by_conv = d.pre_conv.bwd == PwBwd::FusedFin;
     const bool post_on_load = d.post_conv.bn_in, post_bwd_by_conv = pw_fused(d.post_conv.bwd);
     const int nb_in = vcol_geom(Mi, C).nb, nb_out = post.nb;
-    const int nbf = dwf_geom(B, G, H, W, C, stride).nb;              // partial rows of the forward kernel (BN2 statistics) ...
-    const int nbb = dwf_geom(B, G, H, W, C, stride).nb_bwd;          // ... and of the backward (BN1 sums, filter partials)
+    const DwfPlan dp = dwf_plan(B, G, H, W, C, stride, pre ? C : din.ld);      // (dx: a scratch slot behind BN1, the caller's view otherwise)
+    const int nbf = dp.nb;              // partial rows of the forward kernel (BN2 statistics) ...
+    const int nbb = dp.nb_bwd;          // ... and of the backward (BN1 sums, filter partials)
     const size_t nbmax = (size_t)std::max(std::max(std::max(nb_in, nb_out), std::max(nbf, nbb)), std::max(pre_stats_nb, post_bwd_nb));
-    note_scratch((size_t)G * nbmax * 2 * C, (size_t)G * nbmax * C, (size_t)N * H * W * C, 0,
-                 (size_t)dwf_filter_part_elems(B, G, H, W, C, stride));
+    note_scratch((size_t)G * nbmax * 2 * C, (size_t)G * nbmax * C, (size_t)N * H * W * C, 0, (size_t)dp.filter_part_elems);
     const View xv = make_view(x, C), y2v = make_view(y2, C);
     const int at = at_;
     std::shared_ptr<int> diag_calls = std::make_shared<int>(0);
@@ -732,13 +732,13 @@ Learner::BnRec Learner::add_dw_block(std::vector<Op>& ops, const DwBlock& d) {
     {
         Op op;
         op.fwd = [=](hipStream_t st, int) -> int {
-            return dwf_fwd(x, d.pre.stats, w.p, b.p, y2, sc->part, G, B, H, W, C, stride, st, at);
+            return dwf_fwd(dp, DwfFwdArgs{x, d.pre.stats, w.p, b.p, y2, sc->part, st, at});
         };
         op.bwd = [=](hipStream_t st) -> int {
             CDRL_TRY(sched_.next_slot(st));
             double* pw = fparts_[sched_.slot()];
             const View dx = pre ? make_view(dys_[sched_.slot()], C) : din;
-            CDRL_TRY(dwf_bwd(x, d.pre.stats, dout.p, y2, post.stats, post.coef, w.p, dx, sc->part, pw, G, B, H, W, C, stride, st, at));
+            CDRL_TRY(dwf_bwd(dp, DwfBwdArgs{x, d.pre.stats, dout.p, y2, post.stats, post.coef, w.p, dx, sc->part, pw, st, at}));
             return sched_.defer_side(st, [=](hipStream_t sd) -> int {
                 return reduce_partials2(pw, G * nbb, 9 * C, C, (int64_t)10 * C, w.g, b.g, 0, sd);
             });
@@ -1159,7 +1159,7 @@ void Learner::build_trunk(std::vector<Op>& ops) {
                 // of the depthwise backward too
                 const PwConv pw1{pre + ".pw1", xin, rows_in, main_in, mid, y1.p, xg, stride == 2 ? 1 : 0};
                 const ConvPlan p1 = plan_pw(pw1, fpw, bb1, false);
-                if (fpw) bn1.bwd_nb = dwf_geom(B, T, curH, curW, mid, stride).nb_bwd;
+                if (fpw) bn1.bwd_nb = dwf_plan(B, T, curH, curW, mid, stride).nb_bwd;
                 add_pw(ops, pw1, p1, BnRec(), bn1);
                 Half mh{pre, "dw", "bn2", "pw2", "bn3", DwBlock{y1.p, curH, curW, mid, stride}, out, sc_c};
                 mh.d.pre = bn1;

@@ -762,9 +762,10 @@ int cdrl_dwconv_bn_bwd(const float* x, const float* pre_stats, const float* dout
                        const float* w, int G, int B, int H, int W, int C, int stride, float* dx, float* dw, float* db,
                        float* dgamma_post, float* dbeta_post, float* coef_post, float* dgamma_pre, float* dbeta_pre,
                        float* coef_pre, double* workspace, int act_type, void* stream);
-/* Read-only query of the plan cdrl_dwconv_bn_fwd / _bwd dispatch on for (G, B, H, W, C, stride): which kernel instantiation runs
- * and with which loop structure.  Launches nothing and changes nothing.  Writes the first min(n_out, count) of these int32 fields
- * to `out` (host memory) and returns their count (22), or -1 for a bad argument:
+/* Read-only query of the plan cdrl_dwconv_bn_fwd / _bwd launch from for (G, B, H, W, C, stride): which kernel instantiation runs,
+ * with which loop structure, grid and LDS.  Launches nothing and changes nothing.  Writes the first min(n_out, count) of these
+ * int32 fields to `out` (host memory) and returns their count, or -1 for a bad stride, a bad shape or a null `out`.
+ * cdrl_dwconv_bn_plan reports fields 0..21 (count 22, as its callers size their arrays), cdrl_dwconv_bn_plan_ex all of them (31):
  *    0 vec        forward: channels per thread (1 | 2 | 4)
  *    1 nch        forward and pixel-mapped backward: channel chunks per frame
  *    2 cchunk     channels per chunk
@@ -775,7 +776,7 @@ int cdrl_dwconv_bn_bwd(const float* x, const float* pre_stats, const float* dout
  *    7 fpb_bwd    backward: frames looped per workgroup
  *    8 nb_bwd     backward: partial rows per group (B / fpb_bwd)
  *    9 form       backward form: 0 pixel-mapped, 1 stride-1 strips, 2 stride-2 strips
- *   10 strip_sw   strip form: pixels per strip (8 | 4); fields 10..14 and 21 are 0 in the pixel-mapped form
+ *   10 strip_sw   strip form: pixels per strip (8 | 4); fields 10..14, 21..23 and 28 are 0 in the pixel-mapped form
  *   11 strip_R    strips per thread and tile batch (1 | 2 | 3; stride 2: 1)
  *   12 strip_F    frames sharing one tile batch (1 | 2 | 4 | 8)
  *   13 strip_nch  channel chunks per frame
@@ -785,8 +786,17 @@ int cdrl_dwconv_bn_bwd(const float* x, const float* pre_stats, const float* dout
  *   17 lds_fwd_over    1: the forward's tile exceeds the LDS limit -- cdrl_dwconv_bn_fwd refuses the shape
  *   18 cx         forward: channel lanes per workgroup
  *   19 cx_bwd, 20 cy_bwd   pixel-mapped backward: channel / pixel lanes per workgroup
- *   21 strip_cx   strip form: channel-pair lanes per workgroup */
+ *   21 strip_cx   strip form: channel-pair lanes per workgroup
+ *   22 strip_cchunk    strip form: channels per chunk (2 * strip_cx)
+ *   23 strip_S    strip form: strips per pixel row
+ *   24 lds_fwd    forward: dynamic LDS bytes
+ *   25 lds_bwd    backward, the form that runs: dynamic LDS bytes
+ *   26 grid_fwd, 27 grid_bwd   workgroups of the forward / of the backward form that runs
+ *   28 strip_tile strip form: bytes of the gradient tile (without the coefficient table behind it)
+ *   29 refusal_fwd, 30 refusal_bwd   0, or why cdrl_dwconv_bn_fwd / _bwd refuse the shape: 2 the tile exceeds the LDS limit (fields
+ *                 17 / 16 with form 0), 3 strip form with a gradient view of 2 GB or more (never with the dense dx of these entries) */
 int cdrl_dwconv_bn_plan(int G, int B, int H, int W, int C, int stride, int32_t* out, int n_out);
+int cdrl_dwconv_bn_plan_ex(int G, int B, int H, int W, int C, int stride, int32_t* out, int n_out);
 /* MaxPooling2D(3, 2, 'same') (core/architectures.py:161) */
 int cdrl_maxpool_fwd(const float* a, float* p, uint8_t* argmax, int N, int H, int W, int C, void* stream);
 int cdrl_maxpool_bwd(const uint8_t* argmax, const float* dp, float* da, int N, int H, int W, int C, void* stream);
