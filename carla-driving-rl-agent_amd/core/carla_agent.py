@@ -16,7 +16,8 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib, traces, train_stats
-from ..engine import act_stats_width
+from ..engine import act_stats_width, occlusion_baseline
+from ..explain import BASELINES, MODALITIES, check_arguments, occlusion_frames, score_names
 from ..evaluation import RESULT_KEYS, evaluation_info, summarize, trial_seed
 from ..parallel import DataParallelLearner
 from ..rl import utils, spaces
@@ -779,6 +780,61 @@ class CARLAgent(PPOAgent):
                 for env in shard:
                     env.close()
         return results
+
+    def explain(self, state, *, grid=(6, 8), per_frame=False, baseline='mean', modalities=True, upsample='nearest', normalize=True,
+                chunk=32, row=0) -> dict:
+        """Which part of one observation moves the decision: occlusion saliency of the acting network (no reference counterpart,
+        DESIGN.md 6.15).  `state` is what predict() takes -- the dict observe([...], preprocess()) returns --, `row` the environment
+        looked at when its leading axis is larger than 1.  `grid` = (gh, gw) cuts every frame into gh x gw cells (cell (cy, cx): rows
+        [(cy*H)//gh, ((cy+1)*H)//gh), columns alike); one cell at a time is replaced by the `baseline` -- 'mean' (each frame's
+        channel mean), 'zero', or a (T, H, W, 3) stack of the caller's, e.g. a blurred one from Augmenter.views -- in all T frames
+        at once, or per frame with `per_frame` (F = T sets of cells instead of F = 1).  With `modalities`, four more variants
+        occlude the whole image, road, vehicle and navigation (the vectors are zeroed).  Every variant is scored against the
+        untouched observation: `kl` = KL(Beta(observation) || Beta(variant)) summed over the actions, `value` = the change of the
+        value estimate base * 10^exp, `mean_a` = the signed shift of action a's Beta mean, all in double on the device.
+        -> dict(alpha, beta, mean (A,), value (2,) -- the decision itself --, names = ['kl', 'value', 'mean_0', ...],
+                scores float64 (F, gh, gw, K), maps {name: float32 (F, H, W)}, grid, frames,
+                modalities {'image' | 'road' | 'vehicle' | 'navigation': {name: float}} when asked for).
+        maps: 'nearest' gives every pixel the score of its cell (the attribution itself), 'bilinear' a resized grid for display;
+        `normalize` divides each name's maps by its largest |score| over all cells (an all-zero name stays zero).  `scores` are
+        never normalised.  Tensors stay on the device; the `modalities` floats are the call's one host read (4 x K doubles).
+
+        Cost: N = 1 + F*gh*gw (+ 4) rows in ceil(N / chunk) inference forwards of the `chunk`-row engine, one rows launch per
+        chunk, and a baseline, a scores and a maps launch.  First use with a `chunk` builds that engine and the chunk buffers
+        (chunk x one observation); both are kept.
+        Not touched: parameters, moving statistics, optimizer state, memories, logs, the sampler's stream (`action_index`); the
+        forwards are predict()'s (old_policy, BatchNorm moving statistics).  Local to a rank: no collective.
+        Not measured: whether the maps of a trained agent point at what a driver would look at -- there is no simulator here and no
+        trained agent to look at; occlusion sensitivity depends on the baseline and the cell size, and a cell that scores 0 may
+        still matter together with another.
+        ValueError: a grid outside 1..H x 1..W, an unknown baseline or upsample name, a baseline of the wrong shape, chunk < 1 (or
+        above the 65535 rows one launch takes), `row` outside the batch."""
+        image = state['state_image']
+        if len(image.shape) != 5:
+            raise ValueError(f'explain: state_image must be (E, T, H, W, 3), got {tuple(image.shape)}')
+        gh, gw, mode, _ = check_arguments(image.shape, image.shape[0], grid, baseline, upsample, chunk, row)
+        row = int(row)
+        one = {k: state[k][row] for k in ('state_image', 'state_road', 'state_vehicle', 'state_navigation')}
+        stack = torch.as_tensor(one['state_image']).to(self.device, torch.float32).contiguous()
+        if mode is None:
+            base = torch.as_tensor(baseline).to(self.device, torch.float32).contiguous()
+        else:
+            base = occlusion_baseline(stack, BASELINES[mode])
+        one['state_image'] = stack
+        out = self.network.explain_rows(one, (gh, gw), base, per_frame=per_frame, modalities=modalities, upsample=upsample,
+                                        normalize=normalize, chunk=int(chunk))
+        T, H, W = stack.shape[:3]
+        F, A = occlusion_frames(T, per_frame), self.num_actions
+        names = score_names(A)
+        cells = F * gh * gw
+        alpha, beta = out['alpha'][0], out['beta'][0]
+        result = dict(alpha=alpha, beta=beta, mean=alpha / (alpha + beta), value=out['value'][0], names=names, grid=(gh, gw), frames=F,
+                      scores=out['scores'][:cells].view(F, gh, gw, len(names)),
+                      maps={name: out['maps'][k] for k, name in enumerate(names)})
+        if modalities:
+            extra = out['scores'][cells:cells + 4].cpu().tolist()
+            result['modalities'] = {m: dict(zip(names, extra[i])) for i, m in enumerate(MODALITIES)}
+        return result
 
     def record(self, *args, **kwargs):
         raise NotImplementedError('CARLAgent.record drives a CARLA simulator; outside the learner hot path')

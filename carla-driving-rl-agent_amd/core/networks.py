@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine import LearnerEngine, beta_act, ACT_SAMPLE, ACT_MODE
+from ..engine import LearnerEngine, beta_act, ACT_SAMPLE, ACT_MODE, occlusion_rows, occlusion_scores, occlusion_maps
+from ..explain import occlusion_row_count, occlusion_frames
 from ..init import init_engine_parameters
 from ..rl.networks import Network
 from ..rl import utils
@@ -100,6 +101,7 @@ class CARLANetwork(Network):
         self.engine = LearnerEngine(agent.batch_size, device=self.device, train_stats=self.train_stats_rows, **self.cfg)   # learner minibatches
         self._rollouts = {}                # number of environments E -> inference engine over the same arenas
         self.rollout = self.rollout_for(1)                                                       # B = 1 inference
+        self._explain_chunks = {}          # chunk rows -> the input buffers explain_rows fills (built on first use, kept)
         self._ragged = {}                  # minibatch rows -> engine for a ragged last minibatch (shares arenas + optimizer)
         init_engine_parameters(self.engine, seed=agent.seed if agent.seed is not None else 0)
         self.last_value = torch.zeros((1, 2), dtype=torch.float32, device=self.device)   # (base, exp) at terminal states
@@ -193,6 +195,42 @@ class CARLANetwork(Network):
             beta[start:start + m].copy_(out['beta'][:m])
             value[start:start + m].copy_(out['value'][:m])
         return alpha, beta, value
+
+    def explain_rows(self, inputs: dict, grid, baseline, per_frame=False, modalities=True, upsample='nearest', normalize=True, chunk=32):
+        """Occlusion saliency of ONE observation: inputs (T, ...) per key, baseline (T, H, W, 3) on the device.  The
+        N = occlusion_row_count(...) variants -- the observation, one row per cell with the cell taken from the baseline, and with
+        `modalities` the whole image / road / vehicle / navigation occluded -- go through rollout_for(chunk) as predict() runs it
+        (old_policy, moving statistics), `chunk` rows at a time: per chunk ONE cdrl_occlusion_rows launch into buffers the engine
+        reads directly, one inference forward, three small copies; then one cdrl_occlusion_scores and one cdrl_occlusion_maps
+        launch.  ceil(N / chunk) forwards, no host read.  Nothing is sampled, logged or stored; `action_index` stays where it is.
+        Kept between calls: the chunk buffers (chunk rows of inputs) and the engine for `chunk` rows.
+        -> dict(alpha (N, A), beta (N, A), value (N, 2), scores float64 (N - 1, 2 + A), maps float32 (2 + A, F, H, W))."""
+        st = self._pick(inputs)
+        image = st['state_image']
+        T, H, W = (int(x) for x in image.shape[:3])
+        gh, gw = (int(g) for g in grid)
+        chunk = int(chunk)
+        N = occlusion_row_count(T, gh, gw, per_frame, modalities)
+        eng = self.rollout_for(chunk)
+        rows = self._explain_chunks.get(chunk)
+        if rows is None:
+            rows = self._explain_chunks[chunk] = {k: torch.empty((chunk,) + tuple(v.shape), dtype=torch.float32, device=self.device)
+                                                  for k, v in st.items()}
+        A = self.cfg['A']
+        alpha = torch.empty((N, A), dtype=torch.float32, device=self.device)
+        beta = torch.empty((N, A), dtype=torch.float32, device=self.device)
+        value = torch.empty((N, 2), dtype=torch.float32, device=self.device)
+        for first in range(0, N, chunk):
+            occlusion_rows(image, baseline, st['state_road'], st['state_vehicle'], st['state_navigation'], (gh, gw), per_frame,
+                           modalities, first, rows)
+            out = eng.predict(rows)
+            m = min(chunk, N - first)
+            alpha[first:first + m].copy_(out['alpha'][:m])
+            beta[first:first + m].copy_(out['beta'][:m])
+            value[first:first + m].copy_(out['value'][:m])
+        scores = occlusion_scores(alpha, beta, value)
+        maps = occlusion_maps(scores, occlusion_frames(T, per_frame), (gh, gw), (H, W), upsample, normalize)
+        return dict(alpha=alpha, beta=beta, value=value, scores=scores, maps=maps)
 
     def evaluate_step(self, inputs: dict, deterministic, active=None, stats=None):
         """One evaluation step for E environments -> (action, log_prob): one inference forward plus ONE cdrl_beta_act launch that

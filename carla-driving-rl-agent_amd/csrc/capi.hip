@@ -1042,6 +1042,27 @@ int cdrl_augment_images_batch(const float* in, float* out, int E, int T, int H, 
     return augment_images_batch(in, out, E, T, H, W, reinterpret_cast<const AugPlan*>(plans_dev), workspace, S(stream));
 }
 
+int cdrl_occlusion_baseline(const float* image, float* baseline, int T, int H, int W, int mode, void* stream) {
+    return occlusion_baseline(image, baseline, T, H, W, mode, S(stream));
+}
+
+int cdrl_occlusion_rows(const float* image, const float* baseline, const float* road, const float* vehicle, const float* navigation,
+                        int T, int H, int W, int Dr, int Dv, int Dn, int gh, int gw, int per_frame, int modalities, int first,
+                        int count, float* out_image, float* out_road, float* out_vehicle, float* out_navigation, void* stream) {
+    const OcclusionRowsArgs a = {image, baseline, road, vehicle, navigation, out_image, out_road, out_vehicle, out_navigation,
+                                 T, H, W, Dr, Dv, Dn, gh, gw, per_frame != 0, modalities != 0, first, count};
+    return occlusion_rows(a, S(stream));
+}
+
+int cdrl_occlusion_scores(const float* alpha, const float* beta, const float* value, int N, int A, double* scores, void* stream) {
+    return occlusion_scores(alpha, beta, value, N, A, scores, S(stream));
+}
+
+int cdrl_occlusion_maps(const double* scores, int K, int F, int gh, int gw, int H, int W, int upsample, int normalize, float* maps,
+                        void* stream) {
+    return occlusion_maps(scores, K, F, gh, gw, H, W, upsample, normalize, maps, S(stream));
+}
+
 int64_t cdrl_views_workspace_floats(int V, int T, int H, int W) { return views_workspace_floats(V, T, H, W); }
 
 int cdrl_views_batch(const float* rows, int N, float* out, int V, int T, int H, int W, const cdrl_view_plan* plans_dev,

@@ -733,6 +733,25 @@ int64_t views_workspace_floats(int V, int T, int H, int W);
 int views_batch(const float* rows, int N, float* out, int V, int T, int H, int W, const ViewPlan* plans_dev, float* workspace,
                 hipStream_t st);
 
+// ---------------------------------------------------------------- occlusion saliency (explain.hip)
+struct OcclusionRowsArgs {
+    const float *image, *baseline;                  // [T][H][W][3] each
+    const float *road, *vehicle, *navigation;       // [T][Dr], [T][Dv], [T][Dn]
+    float* out_image;                               // [count][T][H][W][3]
+    float *out_road, *out_vehicle, *out_navigation; // [count][T][D*]
+    int T, H, W, Dr, Dv, Dn;
+    int gh, gw, per_frame, modalities;
+    int first, count;                               // rows [first, first + count) of the N rows; an index >= N is a copy of row 0
+};
+// one launch each; arguments checked here (-1 and cdrl_last_error)
+int occlusion_baseline(const float* image, float* baseline, int T, int H, int W, int mode, hipStream_t st);
+int occlusion_rows(const OcclusionRowsArgs& a, hipStream_t st);
+// alpha, beta [N][A], value [N][2] (base, exponent) -> scores [N-1][2 + A] doubles: KL, value difference, mean shifts vs row 0
+int occlusion_scores(const float* alpha, const float* beta, const float* value, int N, int A, double* scores, hipStream_t st);
+// the first F*gh*gw rows of scores [.][K] -> maps [K][F][H][W]; upsample 0 nearest, 1 bilinear
+int occlusion_maps(const double* scores, int K, int F, int gh, int gw, int H, int W, int upsample, int normalize, float* maps,
+                   hipStream_t st);
+
 // ---------------------------------------------------------------- optimiser (optim.hip)
 // Device hyper-parameter block, refreshed by the host before each step (graph-replay safe).
 struct DevHP {

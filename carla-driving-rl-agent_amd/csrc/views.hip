@@ -11,6 +11,7 @@
 // so no launch depends on which buffer an earlier one chose.  The work is bandwidth-shaped: three writes and four reads of the views.
 #include "aug_bodies.h"
 #include "cdrl_kernels.h"
+#include "resize_bodies.h"              // resize_src: the source taps of the crop resize
 
 namespace cdrl {
 
@@ -19,20 +20,6 @@ constexpr int VIEW_MAX_RADIUS = VIEW_MAX_TAPS / 2;
 
 __device__ __forceinline__ int view_taps_of(const ViewPlan& p) {
     return (p.blur_taps >= 3 && p.blur_taps <= VIEW_MAX_TAPS && (p.blur_taps & 1)) ? p.blur_taps : 0;
-}
-
-// Source position of destination index d when `crop` source pixels are resized to `full`: (d + 0.5) * crop / full - 0.5 clamped to
-// [0, crop - 1], in exact integer arithmetic (numerator over 2 * full), so the taps never depend on float rounding of the coordinate
-// and a full-size crop has fraction 0.  -> lower tap i0, upper tap i1 = min(i0 + 1, crop - 1), fraction in [0, 1)
-__device__ __forceinline__ void resize_src(int d, int crop, int full, int& i0, int& i1, float& frac) {
-    const int den = 2 * full;
-    int num = (2 * d + 1) * crop - full;
-    num = num < 0 ? 0 : num;
-    const int top = (crop - 1) * den;
-    num = num > top ? top : num;
-    i0 = num / den;
-    frac = (float)(num - i0 * den) / (float)den;
-    i1 = i0 + 1 < crop ? i0 + 1 : crop - 1;
 }
 
 // launch 1, grid (blocks per view, views): crop window of row v % N -> bilinear resize to H x W -> flip, into A[v]

@@ -858,3 +858,105 @@ def beta_act(dist: torch.Tensor, value, mode: int, seed: int = 0, offset: int = 
                                  _lib.ptr(action), _lib.ptr(log_prob), _lib.ptr(stats),
                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cdrl_beta_act')
     return action, log_prob
+
+
+# ---------------------------------------------------------------- occlusion saliency (csrc/explain.hip)
+def _occ_check(name, t, shape=None, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda \
+            or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f'{name} must be a contiguous {str(dtype)[6:]} device tensor' + (f' of shape {tuple(shape)}' if shape else '')
+                         + f', got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}'
+                         f' {getattr(t, "dtype", "")}')
+
+
+def occlusion_baseline(image: torch.Tensor, mode: str = 'mean', out: torch.Tensor = None):
+    """The neutral stack a cell is replaced by (cdrl_occlusion_baseline, one launch): image (T, H, W, 3) -> baseline of the same
+    shape, 'zero' or 'mean' (each frame's channel mean, fixed-order double sums: the same input gives the same bytes)."""
+    from .explain import BASELINES
+    if mode not in BASELINES:
+        raise ValueError(f'occlusion_baseline: mode {mode!r}: one of {BASELINES}')
+    _occ_check('occlusion_baseline: image', image)
+    if image.dim() != 4 or image.shape[3] != 3:
+        raise ValueError(f'occlusion_baseline: image must be (T, H, W, 3), got {tuple(image.shape)}')
+    if out is None:
+        out = torch.empty_like(image)
+    _occ_check('occlusion_baseline: out', out, image.shape)
+    T, H, W, _ = image.shape
+    _lib.check(_lib.load().cdrl_occlusion_baseline(_lib.ptr(image), _lib.ptr(out), T, H, W, BASELINES.index(mode),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cdrl_occlusion_baseline')
+    return out
+
+
+def occlusion_rows(image, baseline, road, vehicle, navigation, grid, per_frame: bool, modalities: bool, first: int, out: dict):
+    """Rows [first, first + count) of the N occluded variants of one observation (cdrl_occlusion_rows, one launch) into the chunk
+    `out`: dict(state_image (count, T, H, W, 3), state_road (count, T, Dr), state_vehicle, state_navigation), what
+    LearnerEngine.predict takes.  image, baseline (T, H, W, 3); road / vehicle / navigation (T, D*).  A row index >= N is a copy of
+    row 0: every chunk is written in full.  -> out."""
+    _occ_check('occlusion_rows: image', image)
+    if image.dim() != 4 or image.shape[3] != 3:
+        raise ValueError(f'occlusion_rows: image must be (T, H, W, 3), got {tuple(image.shape)}')
+    T, H, W, _ = (int(x) for x in image.shape)
+    _occ_check('occlusion_rows: baseline', baseline, (T, H, W, 3))
+    gh, gw = (int(g) for g in grid)
+    if not (1 <= gh <= H and 1 <= gw <= W):
+        raise ValueError(f'occlusion_rows: grid ({gh}, {gw}) outside 1..{H} x 1..{W}')
+    vectors = dict(road=road, vehicle=vehicle, navigation=navigation)
+    for name, t in vectors.items():
+        _occ_check(f'occlusion_rows: {name}', t)
+        if t.dim() != 2 or t.shape[0] != T:
+            raise ValueError(f'occlusion_rows: {name} must be ({T}, D), got {tuple(t.shape)}')
+    try:
+        chunk = [out['state_image'], out['state_road'], out['state_vehicle'], out['state_navigation']]
+    except (KeyError, TypeError):
+        raise ValueError('occlusion_rows: out must hold state_image, state_road, state_vehicle and state_navigation') from None
+    count = int(chunk[0].shape[0]) if isinstance(chunk[0], torch.Tensor) and chunk[0].dim() == 5 else 0
+    if count < 1 or int(first) < 0:
+        raise ValueError(f'occlusion_rows: first = {first} and a chunk of {count} rows: need first >= 0 and at least one row')
+    _occ_check('occlusion_rows: out state_image', chunk[0], (count, T, H, W, 3))
+    for t, (name, v) in zip(chunk[1:], vectors.items()):
+        _occ_check(f'occlusion_rows: out state_{name}', t, (count, T, int(v.shape[1])))
+    _lib.check(_lib.load().cdrl_occlusion_rows(_lib.ptr(image), _lib.ptr(baseline), _lib.ptr(road), _lib.ptr(vehicle), _lib.ptr(navigation),
+                                               T, H, W, int(road.shape[1]), int(vehicle.shape[1]), int(navigation.shape[1]), gh, gw,
+                                               int(bool(per_frame)), int(bool(modalities)), int(first), count, *(_lib.ptr(t) for t in chunk),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cdrl_occlusion_rows')
+    return out
+
+
+def occlusion_scores(alpha: torch.Tensor, beta: torch.Tensor, value: torch.Tensor, out: torch.Tensor = None):
+    """Rows 1 .. N-1 against row 0 (cdrl_occlusion_scores, one launch, double arithmetic): alpha, beta (N, A), value (N, 2) as
+    (base, exponent) -> float64 (N - 1, 2 + A): KL(Beta(row 0) || Beta(row g)) summed over the actions, the value difference
+    base_g * 10^exp_g - base_0 * 10^exp_0, and per action the signed shift of the Beta mean."""
+    _occ_check('occlusion_scores: alpha', alpha)
+    if alpha.dim() != 2 or alpha.shape[0] < 2 or not 1 <= alpha.shape[1] <= 8:
+        raise ValueError(f'occlusion_scores: alpha must be (N >= 2, 1 <= A <= 8), got {tuple(alpha.shape)}')
+    N, A = (int(x) for x in alpha.shape)
+    _occ_check('occlusion_scores: beta', beta, (N, A))
+    _occ_check('occlusion_scores: value', value, (N, 2))
+    if out is None:
+        out = torch.empty((N - 1, 2 + A), dtype=torch.float64, device=alpha.device)
+    _occ_check('occlusion_scores: out', out, (N - 1, 2 + A), torch.float64)
+    _lib.check(_lib.load().cdrl_occlusion_scores(_lib.ptr(alpha), _lib.ptr(beta), _lib.ptr(value), N, A, _lib.ptr(out),
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cdrl_occlusion_scores')
+    return out
+
+
+def occlusion_maps(scores: torch.Tensor, frames: int, grid, size, upsample: str = 'nearest', normalize: bool = True):
+    """Cell scores -> maps (cdrl_occlusion_maps, one launch): scores float64 (rows >= F*gh*gw, K), of which the first F*gh*gw rows
+    are the cells in row order -> float32 (K, F, H, W).  'nearest': a pixel takes the score of its cell (the attribution itself);
+    'bilinear': the gh x gw grid resized with the half-pixel rule of the contrastive views (display only).  normalize: each column
+    divided by its largest |score| over all its cells; an all-zero column gives zeros."""
+    from .explain import UPSAMPLES
+    if upsample not in UPSAMPLES:
+        raise ValueError(f'occlusion_maps: upsample {upsample!r}: one of {UPSAMPLES}')
+    F, (gh, gw), (H, W) = int(frames), (int(g) for g in grid), (int(s) for s in size)
+    if F < 1 or not (1 <= gh <= H and 1 <= gw <= W):
+        raise ValueError(f'occlusion_maps: {F} frames, grid ({gh}, {gw}) outside 1..{H} x 1..{W}')
+    _occ_check('occlusion_maps: scores', scores, None, torch.float64)
+    if scores.dim() != 2 or scores.shape[0] < F * gh * gw or not 1 <= scores.shape[1] <= 10:
+        raise ValueError(f'occlusion_maps: scores must be (rows >= {F * gh * gw}, 1 <= K <= 10), got {tuple(scores.shape)}')
+    K = int(scores.shape[1])
+    maps = torch.empty((K, F, H, W), dtype=torch.float32, device=scores.device)
+    _lib.check(_lib.load().cdrl_occlusion_maps(_lib.ptr(scores), K, F, gh, gw, H, W, UPSAMPLES.index(upsample), int(bool(normalize)),
+                                               _lib.ptr(maps), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+               'cdrl_occlusion_maps')
+    return maps

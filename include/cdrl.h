@@ -1118,6 +1118,41 @@ typedef struct cdrl_view_plan {
 int64_t cdrl_views_workspace_floats(int V, int T, int H, int W);
 int cdrl_views_batch(const float* rows, int N, float* out, int V, int T, int H, int W, const cdrl_view_plan* plans_dev,
                      float* workspace, void* stream);
+/* Occlusion saliency of one decision: the acting network on N variants of ONE observation -- image [T][H][W][3],
+ * road [T][Dr], vehicle [T][Dv], navigation [T][Dn] -- each with one part replaced by a neutral baseline.  A grid (gh, gw),
+ * 1 <= gh <= H, 1 <= gw <= W, cuts every frame into cells: cell (cy, cx) covers rows [(cy*H)/gh, ((cy+1)*H)/gh) and columns
+ * [(cx*W)/gw, ((cx+1)*W)/gw) (integer division: no cell is empty, the cells partition the frame).  F = T when per_frame, else 1
+ * (a cell is then occluded in all T frames at once).  N = 1 + F*gh*gw + (modalities ? 4 : 0) rows:
+ *   row 0                          the observation, bit for bit
+ *   row 1 + (f*gh + cy)*gw + cx    the pixels of cell (cy, cx) of frame f (every frame when F = 1) taken from the baseline
+ *   then, with modalities          the whole image taken from the baseline; road zeroed; vehicle zeroed; navigation zeroed
+ * Whatever a row does not occlude keeps its bits.
+ *   cdrl_occlusion_baseline  baseline [T][H][W][3] from the image: mode 0 zeros, mode 1 the mean of each frame and channel
+ *                            (fixed-order double sums, one rounding: the same input gives the same bytes).  One launch.
+ *   cdrl_occlusion_rows      rows [first, first + count) of the N rows into out_image [count][T][H][W][3] and out_road /
+ *                            out_vehicle / out_navigation [count][T][D*]; a row index >= N is written as a copy of row 0, so every
+ *                            chunk is written in full.  baseline: any stack of the image's shape.  One launch, the row is the
+ *                            grid's y dimension; 16-byte accesses when T*H*W*3 is a multiple of 4 and image, baseline and out_image
+ *                            are 16-byte aligned, 4-byte accesses otherwise.  count <= 65535; the chunk may not overlap the image
+ *                            or the baseline.
+ *   cdrl_occlusion_scores    alpha, beta [N][A], value [N][2] (base, exponent) -> scores [N-1][2 + A] doubles for rows 1 .. N-1
+ *                            against row 0, in double arithmetic: [0] sum_a KL(Beta(alpha_0, beta_0) || Beta(alpha_g, beta_g)) (the
+ *                            analytic form of cdrl_beta_kl, the anchor first), [1] base_g * 10^exp_g - base_0 * 10^exp_0,
+ *                            [2 + a] alpha_g / (alpha_g + beta_g) - alpha_0 / (alpha_0 + beta_0), signed.  A row equal to row 0
+ *                            scores exactly 0.  N >= 2, A <= 8.  One launch.
+ *   cdrl_occlusion_maps      the first F*gh*gw rows of scores [.][K] -> maps [K][F][H][W] floats.  upsample 0 (nearest): a pixel
+ *                            takes the score of its cell; 1 (bilinear, for display): the gh x gw grid of a frame resized to H x W
+ *                            with the half-pixel rule of cdrl_views_batch (a grid equal to (H, W) returns the scores).  normalize:
+ *                            a column's maps are divided by its largest |score| over all F*gh*gw cells (in double, before the one
+ *                            rounding to float); a column whose largest |score| is 0 gives zeros.  K <= 10.  One launch.
+ * No entry reads anything back, allocates or synchronises.  -1 and cdrl_last_error: null pointers, shapes or grids out of range. */
+int cdrl_occlusion_baseline(const float* image, float* baseline, int T, int H, int W, int mode, void* stream);
+int cdrl_occlusion_rows(const float* image, const float* baseline, const float* road, const float* vehicle, const float* navigation,
+                        int T, int H, int W, int Dr, int Dv, int Dn, int gh, int gw, int per_frame, int modalities, int first,
+                        int count, float* out_image, float* out_road, float* out_vehicle, float* out_navigation, void* stream);
+int cdrl_occlusion_scores(const float* alpha, const float* beta, const float* value, int N, int A, double* scores, void* stream);
+int cdrl_occlusion_maps(const double* scores, int K, int F, int gh, int gw, int H, int W, int upsample, int normalize, float* maps,
+                        void* stream);
 /* CARLAgent.policy_objective / value_objective on linear head outputs (core/carla_agent.py:394-428,
  * 469-486); writes d(loss)/d(lin) and 16 metric floats. */
 int cdrl_beta_ppo_loss(const float* lin, const float* adv, const float* old_logp, const float* speed,
