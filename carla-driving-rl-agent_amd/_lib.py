@@ -78,6 +78,12 @@ class TrustStats(C.Structure):
                 ('skipped', C.c_int32), ('kl_sum', C.c_double)]
 
 
+class DemoStats(C.Structure):
+    """cdrl_demo_stats (include/cdrl.h): the demonstration block, sums over the passes since the caller zeroed it."""
+    _fields_ = [('loss_sum', C.c_double), ('log_prob_sum', C.c_double), ('mode_error_sum', C.c_double), ('rows_sum', C.c_double),
+                ('passes', C.c_int64)]
+
+
 _fp = C.c_void_p   # device pointers travel as plain addresses
 
 
@@ -179,6 +185,9 @@ PROTOTYPES = {
     'cdrl_learner_joint_forward_backward_resample': (_i, [_L, C.POINTER(PolicyBatch), _fp, C.c_uint64, C.c_uint64, _f, _fp]),
     'cdrl_learner_joint_apply': (_i, [_L, _fp]),
     'cdrl_learner_clone_forward_backward': (_i, [_L, C.POINTER(CloneBatch), _f, _f, _f, _f, _fp]),
+    'cdrl_learner_set_demo_block': (_i, [_L, _fp]),
+    'cdrl_learner_demo_forward_backward': (_i, [_L, C.POINTER(PolicyBatch), _fp, _fp, _f, _fp]),
+    'cdrl_learner_demo_forward_backward_resample': (_i, [_L, C.POINTER(PolicyBatch), _fp, _fp, C.c_uint64, C.c_uint64, _f, _fp]),
     'cdrl_learner_repr_forward_backward': (_i, [_L, _fp, _fp, _fp, _fp, _f, _f, _fp]),
     'cdrl_learner_trunk_apply': (_i, [_L, _fp]),
     'cdrl_learner_sequence_begin': (_i, [_L, _fp]),
@@ -274,6 +283,7 @@ PROTOTYPES = {
     'cdrl_bn_inference_stats': (_i, [_i, _pp, _pp, _pp, _pp, _pp, C.POINTER(_i), C.POINTER(_i), _fp, _fp]),
     'cdrl_bn_train_bwd_pooled': (_i, [_fp, _fp, _i, _i, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     'cdrl_beta_clone_loss': (_i, [_fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _f, _fp, _fp, _fp, _fp]),
+    'cdrl_beta_mixed_policy_loss': (_i, [_fp] * 10 + [_f, _f, _i, _i, _f] + [_fp] * 6),
     'cdrl_beta_kl': (_i, [_fp, _fp, _i, _i, _f, _f, _fp, _fp, _fp]),
     'cdrl_occlusion_baseline': (_i, [_fp, _fp, _i, _i, _i, _i, _fp]),
     'cdrl_occlusion_rows': (_i, [_fp] * 5 + [_i] * 12 + [_fp] * 5),

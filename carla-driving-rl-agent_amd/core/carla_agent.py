@@ -147,7 +147,11 @@ class CARLAgent(PPOAgent):
         rollout augmentation (draw_plans -> Augmenter.batch), pixel-aligned views.  'simclr': the SimCLR view pipeline -- random
         crop resized back, flip, colour jitter, colour drop, Gaussian blur (draw_view_plans -> Augmenter.views).
         A dict of draw_view_plans options (crop_scale, flip_prob, jitter_prob, drop_prob, blur_prob, blur_sigma) implies 'simclr'.
-        An unknown name or option: ValueError."""
+        An unknown name or option: ValueError.
+        `demo_traces=dir` (PPOAgent; not in the reference): every policy minibatch keeps
+        D = round(demo_fraction * batch_size) rows of the expert traces in `dir` behind its batch_size - D fresh rows, trained on the
+        same trunk pass by `demo_weight` times the Beta log-likelihood of the expert's action (with_demonstrations, the engines'
+        demo_forward_backward(_resample)); works with both policy losses; the value loop is unchanged."""
         assert aug_intensity >= 0.0
         if kwargs.get('replay_rollouts', 0) and resample_actions:
             raise ValueError('replay_rollouts > 0 needs the stored-action policy loss: the re-sampled loss (resample_actions=True, the '
@@ -410,6 +414,8 @@ class CARLAgent(PPOAgent):
                  advantages=advantages, old_log_prob=log_probabilities, speed=speed, similarity=similarity, u=actions, **extra)
         b = eng.stage(b, kind)               # fixed addresses -> the captured hipGraph of the step is replayed
         b.update(du_da=None, du_db=None)
+        if kind == 'demo' and getattr(eng, '_demo_block', None) is not self._demo_block:
+            eng.set_demo_block(self._demo_block)        # (engines of every minibatch size add to the update()'s one block)
         scale = 1.0 / self.world
         if self.resample_actions:
             # Beta(alpha, beta) of the NEW policy is sampled on the device with pathwise Jacobians (rank-disjoint Philox offsets)
@@ -420,7 +426,24 @@ class CARLAgent(PPOAgent):
             getattr(eng, f'{kind}_forward_backward')(b, grad_scale=scale)
         return eng
 
+    def with_demonstrations(self, batch):
+        """A policy minibatch of n fresh rows -> (the six components with D demonstration rows behind the fresh ones, dict(demo_u,
+        demo_w)) for the mixed pass.  Fresh rows carry demo_w = 0; demonstration rows carry this update()'s weight, their trace's
+        speed / similarity targets, and zeros where the mixed loss reads nothing (advantages, stored log-probabilities)."""
+        states, advantages, actions, log_probabilities, speed, similarity = batch
+        d = self.draw_demonstrations()
+        n, D = int(advantages.shape[0]), self.demo_rows_per_batch
+        zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=advantages.device)
+        cat = lambda a, b: torch.cat([a, b], dim=0)
+        mixed = ({k: cat(states[k], d['states'][k]) for k in self.STATE_KEYS}, cat(advantages, zeros(D)), cat(actions, d['u']),
+                 cat(log_probabilities, zeros(D, self.num_actions)), cat(speed, d['speed']), cat(similarity, d['similarity']))
+        weight = torch.full((D,), self._demo_w, dtype=torch.float32, device=advantages.device)
+        return mixed, dict(demo_u=cat(zeros(n, self.num_actions), d['u']), demo_w=cat(zeros(n), weight))
+
     def get_policy_gradients(self, batch):
+        if self._demo_active:       # (batch, extras) of with_demonstrations
+            eng = self._policy_pass('demo', batch[0], **batch[1])
+            return eng.buffer(2)[0].clone(), 'policy'
         eng = self._policy_pass('policy', batch)
         if self.data_parallel:
             self._dp_for(eng).reduce_policy_gradients()

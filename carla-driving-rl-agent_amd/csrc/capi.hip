@@ -664,6 +664,34 @@ int cdrl_learner_clone_forward_backward(cdrl_learner* l, const cdrl_clone_batch*
     return l->impl->clone_forward_backward(cb, policy_weight, value_weight, aux_weight, grad_scale, S(stream));
 }
 
+static_assert(sizeof(cdrl_demo_stats) == sizeof(cdrl::DemoBlock), "cdrl_demo_stats mirrors DemoBlock");
+
+int cdrl_learner_set_demo_block(cdrl_learner* l, cdrl_demo_stats* device_block) {
+    CHECK_L(l);
+    if (reinterpret_cast<uintptr_t>(device_block) % alignof(cdrl::DemoBlock) != 0) {
+        cdrl::set_error("cdrl_learner_set_demo_block: the block must be 8-byte aligned");
+        return -1;
+    }
+    l->impl->set_demo_block(reinterpret_cast<cdrl::DemoBlock*>(device_block));
+    return 0;
+}
+
+int cdrl_learner_demo_forward_backward(cdrl_learner* l, const cdrl_policy_batch* b, const float* demo_u, const float* demo_w,
+                                       float grad_scale, void* stream) {
+    CHECK_L(l);
+    PolicyBatch pb;
+    CDRL_TRY(policy_batch(b, true, "demonstration batch", &pb));
+    return l->impl->demo_forward_backward(pb, demo_u, demo_w, grad_scale, S(stream));
+}
+
+int cdrl_learner_demo_forward_backward_resample(cdrl_learner* l, const cdrl_policy_batch* b, const float* demo_u, const float* demo_w,
+                                                uint64_t seed, uint64_t offset, float grad_scale, void* stream) {
+    CHECK_L(l);
+    PolicyBatch pb;
+    CDRL_TRY(policy_batch(b, false, "demonstration batch", &pb));
+    return l->impl->demo_forward_backward_resample(pb, demo_u, demo_w, seed, offset, grad_scale, S(stream));
+}
+
 int cdrl_learner_repr_forward_backward(cdrl_learner* l, const float* image, const float* road, const float* vehicle,
                                        const float* navigation, float temperature, float grad_scale, void* stream) {
     CHECK_L(l);
@@ -1903,6 +1931,30 @@ int cdrl_beta_clone_loss(const float* lin, const float* u, const float* weight, 
     a.entropy_coef = entropy_coef; a.aux_weight = aux_weight; a.dlin = dlin; a.metrics = metrics; a.aux = aux;
     a.B = B; a.A = A; a.grad_scale = grad_scale;
     return clone_loss(a, S(stream));
+}
+
+int cdrl_beta_mixed_policy_loss(const float* lin, const float* adv, const float* old_logp, const float* speed,
+                                const float* similarity, const float* u, const float* du_da, const float* du_db, const float* demo_u,
+                                const float* demo_w, float clip_ratio, float entropy_coef, int B, int A, float grad_scale, float* dlin,
+                                float* metrics, float* aux, float* hp_scratch16, cdrl_demo_stats* demo_block, void* stream) {
+    MixedPolicyLossArgs m;
+    PolicyLossArgs& a = m.ppo;
+    a.lin = lin; a.adv = adv; a.old_logp = old_logp; a.speed = speed; a.similarity = similarity;
+    a.u = u; a.du_da = du_da; a.du_db = du_db; a.hp = hp_scratch16; a.dlin = dlin; a.metrics = metrics; a.aux = aux;
+    a.B = B; a.A = A; a.inv_world = grad_scale;
+    m.demo_u = demo_u; m.demo_w = demo_w; m.block = reinterpret_cast<cdrl::DemoBlock*>(demo_block);
+    if (!adv || !old_logp || !speed || !similarity || !hp_scratch16) {
+        cdrl::set_error("cdrl_beta_mixed_policy_loss: a null adv / old_logp / speed / similarity / hp_scratch16");
+        return -1;
+    }
+    // (the wrapper's own refusals first: nothing is enqueued for a refused call)
+    if (A < 1 || A > 8 || B < 1 || !lin || !u || !demo_u || !demo_w || !dlin || !metrics) return mixed_policy_loss(m, S(stream));
+    DevHP h;
+    memset(&h, 0, sizeof(h));
+    h.clip_ratio = clip_ratio;
+    h.entropy_coef = entropy_coef;
+    CDRL_HIP(hipMemcpyAsync(hp_scratch16, &h, sizeof(h), hipMemcpyHostToDevice, S(stream)));
+    return mixed_policy_loss(m, S(stream));
 }
 
 int cdrl_beta_kl(const float* lin, const float* anchor, int B, int A, float kl_coef, float grad_scale, float* dlin, float* metrics,

@@ -3,6 +3,7 @@
 #pragma once
 #include "cdrl_common.h"
 #include "trust_block.h"
+#include "demo_block.h"
 
 namespace cdrl {
 
@@ -631,6 +632,17 @@ struct CloneLossArgs {       // behaviour cloning: weighted Beta negative log-li
     float grad_scale;
 };
 int clone_loss(const CloneLossArgs& a, hipStream_t st);
+// Mixed policy loss (demo.hip): row b is a demonstration row iff demo_w[b] > 0 -- weighted negative Beta
+// log-likelihood of demo_u[b], averaged over the ND such rows; its adv / old_logp / u / du_da / du_db are not read -- and a PPO row
+// otherwise (the surrogate of policy_loss, averaged over the NP = B - ND others).  Entropy and auxiliary terms over all B rows.
+struct MixedPolicyLossArgs {
+    PolicyLossArgs ppo;      // metrics: 0..6 as policy_loss ([1], [5], [6] over the PPO rows), [7] demonstration term, [8] mean logp and
+                             // [9] mean absolute mode error of the demonstration rows, [10] ND
+    const float* demo_u;     // [B][A] expert action in the unit interval
+    const float* demo_w;     // [B]
+    DemoBlock* block;        // device block that thread 0 adds metrics[7..10] and a pass count to; or null
+};
+int mixed_policy_loss(const MixedPolicyLossArgs& a, hipStream_t st);
 // Trust-region guard (trust.hip): the analytic KL(Beta(anchor) || Beta(policy)) of a policy minibatch, summed over a
 // row's actions and averaged over the rows, behind policy_loss and in front of the head's backward.
 struct BetaKlArgs {

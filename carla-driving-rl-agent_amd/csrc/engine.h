@@ -129,6 +129,15 @@ public:
     int policy_forward_backward_resample(const PolicyBatch& b, uint64_t seed, uint64_t offset, float inv_world,
                                          hipStream_t st);
     float* sample_buffer() const { return sample_u_; }
+    // Demonstration-augmented policy pass: the policy pass with mixed_policy_loss where policy_loss stands.  Rows with
+    // demo_w > 0 are demonstration rows (maximum likelihood of demo_u), the others PPO rows; everything else -- trunk and head forward,
+    // the re-sampling with its Philox offsets, head and trunk backward, freeze_trunk, the graph -- is the policy pass's.  Refuses a
+    // batch with an anchor (the anchor sweep has no demonstration rows).  Followed by policy_apply.
+    int demo_forward_backward(const PolicyBatch& b, const float* demo_u, const float* demo_w, float inv_world, hipStream_t st);
+    int demo_forward_backward_resample(const PolicyBatch& b, const float* demo_u, const float* demo_w, uint64_t seed, uint64_t offset,
+                                       float inv_world, hipStream_t st);
+    // caller-owned device block the demonstration passes add their statistics to (null: none); part of their graph key
+    void set_demo_block(DemoBlock* d) { demo_block_ = d; }
     int policy_apply(hipStream_t st);
     // a sequence of calls on ONE caller stream: the hand-overs happen once, around the whole sequence
     int sequence_begin(hipStream_t caller) { return sched_.sequence_begin(caller); }
@@ -434,6 +443,8 @@ private:
         uint64_t seed = 0, offset = 0;
         // clone mode (policy is null): the clone loss on (clone_u, clone_w) stands where the policy loss stands
         const float *clone_u = nullptr, *clone_w = nullptr;
+        // demonstration mode (policy is set): the mixed loss on (demo_u, demo_w) stands where the policy loss stands
+        const float *demo_u = nullptr, *demo_w = nullptr;
         float policy_weight = 1.0f, value_weight = 1.0f, aux_weight = 1.0f;
         // representation mode (policy, returns, clone_u all null): the NT-Xent loss on the trunk's output, no head at all
         bool repr = false;
@@ -447,6 +458,9 @@ private:
     }
     PolicyLossArgs policy_loss_args(const PassSpec& s) const;
     CloneLossArgs clone_loss_args(const PassSpec& s) const;
+    MixedPolicyLossArgs mixed_loss_args(const PassSpec& s) const;
+    DemoBlock* demo_block_ = nullptr;
+    int demo_pass(PassSpec s, const float* demo_u, const float* demo_w, hipStream_t caller);
     ValueLossArgs value_loss_args(const PassSpec& s) const;
     NtxentArgs ntxent_args(const PassSpec& s) const;
     // forward half: trunk, the heads present (dist: policy_dist behind the policy head; re-sampling: and the Beta draw, both in

@@ -1700,7 +1700,7 @@ static inline uint64_t Kf(float f) {
 // step kind: the first word of a graph key
 enum KeyKind : uint64_t {
     KEY_POLICY_PASS = 1, KEY_VALUE_PASS = 2, KEY_POLICY_APPLY = 3, KEY_VALUE_APPLY = 4, KEY_PREDICT = 5, KEY_JOINT_PASS = 6, KEY_JOINT_APPLY = 7,
-    KEY_CLONE_PASS = 8, KEY_REPR_PASS = 9, KEY_TRUNK_APPLY = 10
+    KEY_CLONE_PASS = 8, KEY_REPR_PASS = 9, KEY_TRUNK_APPLY = 10, KEY_DEMO_PASS = 11
 };
 
 PolicyLossArgs Learner::policy_loss_args(const PassSpec& s) const {
@@ -1739,6 +1739,15 @@ CloneLossArgs Learner::clone_loss_args(const PassSpec& s) const {
     a.B = cfg_.B;
     a.A = cfg_.A;
     a.grad_scale = s.inv_world * s.policy_weight;
+    return a;
+}
+
+MixedPolicyLossArgs Learner::mixed_loss_args(const PassSpec& s) const {
+    MixedPolicyLossArgs a;
+    a.ppo = policy_loss_args(s);
+    a.demo_u = s.demo_u;
+    a.demo_w = s.demo_w;
+    a.block = demo_block_;
     return a;
 }
 
@@ -1792,7 +1801,9 @@ int Learner::pass_backward(const PassSpec& s, hipStream_t st) {
     const bool measure = trust_on() && s.policy && s.policy->anchor;
     if (trust_on() && !measure && (s.head() || s.repr)) CDRL_TRY(trust_disarm(trust_dev_, st));
     if (s.head()) {
-        CDRL_TRY(s.policy ? policy_loss(policy_loss_args(s), st) : clone_loss(clone_loss_args(s), st));
+        CDRL_TRY(s.demo_u  ? mixed_policy_loss(mixed_loss_args(s), st)
+                 : s.policy ? policy_loss(policy_loss_args(s), st)
+                            : clone_loss(clone_loss_args(s), st));
         if (measure) {
             BetaKlArgs k;
             k.lin = lin_p_.p;
@@ -1869,11 +1880,17 @@ int Learner::run_pass(const PassSpec& s, hipStream_t caller, bool fwd, bool bwd)
     const bool graphable = fwd && bwd && !s.resample;
     std::vector<uint64_t> key;
     if (graphable) {
-        key = {s.repr ? KEY_REPR_PASS : s.clone_u ? KEY_CLONE_PASS : s.joint() ? KEY_JOINT_PASS : s.policy ? KEY_POLICY_PASS : KEY_VALUE_PASS,
+        key = {s.repr      ? KEY_REPR_PASS
+               : s.clone_u ? KEY_CLONE_PASS
+               : s.demo_u  ? KEY_DEMO_PASS
+               : s.joint() ? KEY_JOINT_PASS
+               : s.policy  ? KEY_POLICY_PASS
+                           : KEY_VALUE_PASS,
                K(s.image), K(s.road), K(s.vehicle), K(s.navigation), K(s.speed), K(s.similarity), K(s.returns), Kf(s.inv_world)};
         if (const PolicyBatch* b = s.policy) key.insert(key.end(), {K(b->adv), K(b->old_logp), K(b->u), K(b->du_da), K(b->du_db)});
         if (s.policy && s.policy->anchor) key.push_back(K(s.policy->anchor));
         if (s.clone_u) key.insert(key.end(), {K(s.clone_u), K(s.clone_w), Kf(s.policy_weight), Kf(s.value_weight), Kf(s.aux_weight)});
+        if (s.demo_u) key.insert(key.end(), {K(s.demo_u), K(s.demo_w), K(demo_block_)});
         if (s.repr) key.push_back(Kf(s.temperature));
     }
     return launch(caller, key, graphable, [&](hipStream_t st) -> int {
@@ -1899,6 +1916,29 @@ int Learner::policy_backward(const PolicyBatch& b, float inv_world, hipStream_t 
 int Learner::policy_forward_backward_resample(const PolicyBatch& b, uint64_t seed, uint64_t offset, float inv_world,
                                               hipStream_t caller) {
     return run_pass(policy_pass(b, nullptr, inv_world, true, seed, offset), caller);
+}
+
+int Learner::demo_pass(PassSpec s, const float* demo_u, const float* demo_w, hipStream_t caller) {
+    if (!demo_u || !demo_w) {
+        set_error("demonstration pass: null demo_u / demo_w");
+        return -1;
+    }
+    if (s.policy->anchor) {
+        set_error("demonstration pass: the batch carries an anchor: the trust-region sweep has no demonstration rows");
+        return -1;
+    }
+    s.demo_u = demo_u;
+    s.demo_w = demo_w;
+    return run_pass(s, caller);
+}
+
+int Learner::demo_forward_backward(const PolicyBatch& b, const float* demo_u, const float* demo_w, float inv_world, hipStream_t caller) {
+    return demo_pass(policy_pass(b, nullptr, inv_world), demo_u, demo_w, caller);
+}
+
+int Learner::demo_forward_backward_resample(const PolicyBatch& b, const float* demo_u, const float* demo_w, uint64_t seed, uint64_t offset,
+                                            float inv_world, hipStream_t caller) {
+    return demo_pass(policy_pass(b, nullptr, inv_world, true, seed, offset), demo_u, demo_w, caller);
 }
 
 int Learner::value_forward_backward(const ValueBatch& b, float inv_world, hipStream_t caller) {

@@ -10,23 +10,9 @@
 //                action, with the entropy and auxiliary terms of policy_loss.
 // One workgroup, wavefront/LDS reductions in double: B is a few hundred rows, the kernels are
 // latency-bound, so everything transcendental (lgamma / digamma / trigamma) runs in double.
-#include "loss_bodies.h"      // digamma_d, softplus_d, sigmoid_d, block_reduce (shared with trust.hip)
+#include "loss_bodies.h"      // the Beta action / row bodies, block_reduce (shared with trust.hip and demo.hip)
 
 namespace cdrl {
-
-__device__ double trigamma_d(double x) {
-    double r = 0.0;
-    while (x < 10.0) {
-        r += 1.0 / (x * x);
-        x += 1.0;
-    }
-    const double f = 1.0 / (x * x);
-    const double t = 1.0 / x + 0.5 * f +
-                     (1.0 / x) * f * (1.0 / 6.0 + f * (-1.0 / 30.0 + f * (1.0 / 42.0 + f * (-1.0 / 30.0 + f * (5.0 / 66.0)))));
-    return r + t;
-}
-
-#define F32_EPS 1.1920929e-07f
 
 __global__ void __launch_bounds__(256) policy_loss_kernel(PolicyLossArgs p) {
     __shared__ double sm[6 * 256];
@@ -37,66 +23,9 @@ __global__ void __launch_bounds__(256) policy_loss_kernel(PolicyLossArgs p) {
     const double gs = (double)p.inv_world;
     double acc[6] = {0, 0, 0, 0, 0, 0};   // policy term, entropy, speed sq, sim sq, ratio, logp
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        const float* lin = p.lin + (int64_t)b * L;
-        float* dlin = p.dlin + (int64_t)b * L;
-        double ea[8], dlp_da[8], dlp_db[8], dH_da[8], dH_db[8], sg_a[8], sg_b[8];
-        double ratio = 0.0;
-        for (int a = 0; a < A; ++a) {
-            const double la = (double)lin[a], lb = (double)lin[A + a];
-            const double al = softplus_d(la) + 1.01, be = softplus_d(lb) + 1.01;
-            const float uf = p.u[(int64_t)b * A + a];
-            const float xf = fminf(fmaxf(uf, F32_EPS), 1.0f - F32_EPS);      // _clip_actions
-            const bool inside = (uf >= F32_EPS) && (uf <= 1.0f - F32_EPS);
-            const double x = (double)xf;
-            const double lx = log(x), l1x = log1p(-x);
-            const double lnB = lgamma(al) + lgamma(be) - lgamma(al + be);
-            const double pa = digamma_d(al), pb = digamma_d(be), pab = digamma_d(al + be);
-            const double logp = (al - 1.0) * lx + (be - 1.0) * l1x - lnB;
-            const double ent = lnB - (al - 1.0) * pa - (be - 1.0) * pb + (al + be - 2.0) * pab;
-            const double e = exp(logp - (double)p.old_logp[(int64_t)b * A + a]);
-            ea[a] = e;
-            ratio += e;
-            double dlx = inside ? ((al - 1.0) / x - (be - 1.0) / (1.0 - x)) : 0.0;
-            const double ja = p.du_da ? (double)p.du_da[(int64_t)b * A + a] : 0.0;
-            const double jb = p.du_db ? (double)p.du_db[(int64_t)b * A + a] : 0.0;
-            dlp_da[a] = lx - pa + pab + dlx * ja;
-            dlp_db[a] = l1x - pb + pab + dlx * jb;
-            const double tab = trigamma_d(al + be);
-            dH_da[a] = -(al - 1.0) * trigamma_d(al) + (al + be - 2.0) * tab;
-            dH_db[a] = -(be - 1.0) * trigamma_d(be) + (al + be - 2.0) * tab;
-            sg_a[a] = sigmoid_d(la);
-            sg_b[a] = sigmoid_d(lb);
-            acc[1] += ent;
-            acc[5] += logp;
-            if (p.aux) {
-                float* ax = p.aux + (int64_t)b * 4 * A;
-                ax[a] = (float)al;
-                ax[A + a] = (float)be;
-                ax[2 * A + a] = (float)logp;
-                ax[3 * A + a] = (float)ent;
-            }
-        }
-        ratio *= invA;
-        const double adv = (double)p.adv[b];
-        const double minadv = adv > 0.0 ? (1.0 + clip) * adv : (1.0 - clip) * adv;
-        const double s = ratio * adv;
-        const bool pass = s <= minadv;                 // tf.minimum routes the gradient to x where x <= y
-        acc[0] += pass ? s : minadv;
-        acc[4] += ratio;
-        for (int a = 0; a < A; ++a) {
-            const double dL_dlogp = pass ? (-invB * adv * invA * ea[a]) : 0.0;
-            const double dL_dH = -cent * invB * invA;
-            dlin[a] = (float)(gs * (dL_dlogp * dlp_da[a] + dL_dH * dH_da[a]) * sg_a[a]);
-            dlin[A + a] = (float)(gs * (dL_dlogp * dlp_db[a] + dL_dH * dH_db[a]) * sg_b[a]);
-        }
-        const double sim = tanh((double)lin[2 * A]);
-        const double sgs = sigmoid_d((double)lin[2 * A + 1]);
-        const double spd = 2.0 * sgs;
-        const double dsim = sim - (double)p.similarity[b], dspd = spd - (double)p.speed[b];
-        acc[3] += dsim * dsim;
-        acc[2] += dspd * dspd;
-        dlin[2 * A] = (float)(gs * invB * dsim * (1.0 - sim * sim));
-        dlin[2 * A + 1] = (float)(gs * invB * dspd * 2.0 * sgs * (1.0 - sgs));
+        ppo_row(p, b, clip, cent, invB, invB, invA, gs, acc[0], acc[1], acc[4], acc[5]);
+        aux_heads_row(p.lin + (int64_t)b * L, p.dlin + (int64_t)b * L, A, (double)p.speed[b], (double)p.similarity[b], gs * invB, acc[2],
+                      acc[3]);
     }
     block_reduce<6>(acc, sm);
     if (threadIdx.x == 0) {
@@ -139,45 +68,10 @@ __global__ void __launch_bounds__(256) clone_loss_kernel(CloneLossArgs p) {
         const float* lin = p.lin + (int64_t)b * L;
         float* dlin = p.dlin + (int64_t)b * L;
         const double w = p.weight ? (double)p.weight[b] : 1.0;
-        const double dL_dlogp = -invB * w * invA, dL_dH = -cent * invB * invA;
-        double nll = 0.0;
-        for (int a = 0; a < A; ++a) {
-            const double la = (double)lin[a], lb = (double)lin[A + a];
-            const double al = softplus_d(la) + 1.01, be = softplus_d(lb) + 1.01;
-            const float uf = p.u[(int64_t)b * A + a];
-            const double x = (double)fminf(fmaxf(uf, F32_EPS), 1.0f - F32_EPS);      // _clip_actions
-            const double lx = log(x), l1x = log1p(-x);
-            const double lnB = lgamma(al) + lgamma(be) - lgamma(al + be);
-            const double pa = digamma_d(al), pb = digamma_d(be), pab = digamma_d(al + be);
-            const double logp = (al - 1.0) * lx + (be - 1.0) * l1x - lnB;
-            const double ent = lnB - (al - 1.0) * pa - (be - 1.0) * pb + (al + be - 2.0) * pab;
-            const double tab = trigamma_d(al + be);
-            const double dH_da = -(al - 1.0) * trigamma_d(al) + (al + be - 2.0) * tab;
-            const double dH_db = -(be - 1.0) * trigamma_d(be) + (al + be - 2.0) * tab;
-            dlin[a] = (float)(gs * (dL_dlogp * (lx - pa + pab) + dL_dH * dH_da) * sigmoid_d(la));
-            dlin[A + a] = (float)(gs * (dL_dlogp * (l1x - pb + pab) + dL_dH * dH_db) * sigmoid_d(lb));
-            nll -= logp;
-            acc[1] += ent;
-            acc[5] += logp;
-            acc[6] += fabs((al - 1.0) / (al + be - 2.0) - x);       // alpha, beta >= 1.01: the mode exists
-            if (p.aux) {
-                float* ax = p.aux + (int64_t)b * 4 * A;
-                ax[a] = (float)al;
-                ax[A + a] = (float)be;
-                ax[2 * A + a] = (float)logp;
-                ax[3 * A + a] = (float)ent;
-            }
-        }
-        acc[0] += w * nll * invA;
+        clone_row(lin, dlin, p.u, p.aux, b, A, w, cent, invB, invB, invA, gs, acc[0], acc[1], acc[5], acc[6]);
         acc[4] += w;
         if (targets) {
-            const double sim = tanh((double)lin[2 * A]);
-            const double sgs = sigmoid_d((double)lin[2 * A + 1]);
-            const double dsim = sim - (double)p.similarity[b], dspd = 2.0 * sgs - (double)p.speed[b];
-            acc[3] += dsim * dsim;
-            acc[2] += dspd * dspd;
-            dlin[2 * A] = (float)(gs * aw * invB * dsim * (1.0 - sim * sim));
-            dlin[2 * A + 1] = (float)(gs * aw * invB * dspd * 2.0 * sgs * (1.0 - sgs));
+            aux_heads_row(lin, dlin, A, (double)p.speed[b], (double)p.similarity[b], gs * aw * invB, acc[2], acc[3]);
         } else {
             dlin[2 * A] = 0.0f;
             dlin[2 * A + 1] = 0.0f;

@@ -588,6 +588,49 @@ class LearnerEngine:
             else:
                 self.policy_apply()
 
+    # Expert demonstrations inside the PPO update (include/cdrl.h).  `batch`: a policy batch dict plus 'demo_u' (B, A)
+    # expert actions in the unit interval and 'demo_w' (B): rows with demo_w > 0 are demonstration rows, the others PPO rows.
+    def _demo_batch(self, batch, resample=False):
+        c = self.cfg
+        for k, shape in (('demo_u', (c.B, c.A)), ('demo_w', (c.B,))):
+            if batch.get(k) is None:
+                raise ValueError(f'{k}: a demonstration batch needs it, shape {shape}')
+            self._chk(batch[k], shape, k)
+        if batch.get('anchor') is not None:
+            raise ValueError('anchor: a demonstration batch carries none (the trust-region sweep has no demonstration rows)')
+        return self._policy_batch(batch, resample)
+
+    def demo_forward_backward(self, batch, grad_scale=1.0):
+        """The policy pass with the mixed loss (stored actions / injected Jacobians on the PPO rows)."""
+        pb = self._demo_batch(batch)
+        _lib.check(self.lib.cdrl_learner_demo_forward_backward(self.h, C.byref(pb), _lib.ptr(batch['demo_u']), _lib.ptr(batch['demo_w']),
+                                                               float(grad_scale), self._stream()), 'demo_forward_backward')
+
+    def demo_forward_backward_resample(self, batch, seed: int, offset: int, grad_scale=1.0):
+        """... with the Beta re-sampling on the device: u is drawn for all B rows as in policy_forward_backward_resample, the draw
+        of a demonstration row is ignored."""
+        pb = self._demo_batch(batch, resample=True)
+        _lib.check(self.lib.cdrl_learner_demo_forward_backward_resample(self.h, C.byref(pb), _lib.ptr(batch['demo_u']),
+                                                                        _lib.ptr(batch['demo_w']), int(seed), int(offset),
+                                                                        float(grad_scale), self._stream()),
+                   'demo_forward_backward_resample')
+
+    def demo_step(self, batch):
+        with self.sequence():
+            self.demo_forward_backward(batch)
+            self.policy_apply()
+
+    def set_demo_block(self, block: Optional[torch.Tensor]):
+        """block: a zeroed float64 device tensor of DEMO_BLOCK_DOUBLES elements (cdrl_demo_stats) that every later demonstration pass
+        of this engine adds to, or None.  Engines of several minibatch sizes may share one."""
+        self._need_device('set_demo_block')
+        if block is not None and (block.dtype != torch.float64 or block.numel() != DEMO_BLOCK_DOUBLES or not block.is_cuda
+                                  or not block.is_contiguous()):
+            raise ValueError(f'set_demo_block: a contiguous float64 device tensor of {DEMO_BLOCK_DOUBLES} elements, got '
+                             f'{tuple(block.shape)} {block.dtype}')
+        self._demo_block = block        # (kept alive: the library holds its address)
+        _lib.check(self.lib.cdrl_learner_set_demo_block(self.h, _lib.ptr(block)), 'set_demo_block')
+
     # Contrastive pre-training of the trunk (include/cdrl.h, DESIGN.md 6.11).  `states`: the four state tensors of B = 2N rows, rows
     # i and i + N being two views of one observation.
     def repr_forward_backward(self, states, temperature=0.1, grad_scale=1.0):
@@ -669,11 +712,13 @@ class LearnerEngine:
         if which == 'representation':
             m = self.buffer(_lib.BUF_METRICS_R).cpu().numpy()
             return {k: float(m[i]) for i, k in enumerate(REPRESENTATION_METRICS)}
-        m = self.buffer(_lib.BUF_METRICS_P if which in ('policy', 'clone') else _lib.BUF_METRICS_V).cpu().numpy()
+        m = self.buffer(_lib.BUF_METRICS_P if which in ('policy', 'clone', 'demo') else _lib.BUF_METRICS_V).cpu().numpy()
         if which == 'policy':
             keys = ('loss', 'policy_loss', 'entropy', 'speed_loss', 'similarity_loss', 'ratio', 'log_prob')
         elif which == 'clone':      # the policy block as a clone pass leaves it
             keys = CLONE_METRICS
+        elif which == 'demo':       # ... as a demonstration pass leaves it
+            keys = DEMO_METRICS
         else:
             keys = ('loss', 'value_loss', 'speed_loss', 'similarity_loss')
         return {k: float(m[i]) for i, k in enumerate(keys)}
@@ -710,6 +755,47 @@ def beta_kl(lin: torch.Tensor, anchor: torch.Tensor, kl_coef: float = 0.0, grad_
 
 # slots 0..7 of CDRL_BUF_METRICS_P after a clone pass (cdrl_beta_clone_loss, include/cdrl.h)
 CLONE_METRICS = ('loss', 'clone_loss', 'entropy', 'speed_loss', 'similarity_loss', 'weight', 'log_prob', 'mode_error')
+
+
+# slots 0..10 of CDRL_BUF_METRICS_P after a demonstration pass (cdrl_beta_mixed_policy_loss, include/cdrl.h)
+DEMO_METRICS = ('loss', 'policy_loss', 'entropy', 'speed_loss', 'similarity_loss', 'ratio', 'log_prob', 'demo_loss', 'demo_log_prob',
+                'demo_mode_error', 'demo_rows')
+DEMO_BLOCK_DOUBLES = 5          # cdrl_demo_stats: four double sums and an int64 pass count
+
+
+def demo_block(device) -> torch.Tensor:
+    """A zeroed demonstration block (cdrl_demo_stats) for LearnerEngine.set_demo_block."""
+    return torch.zeros(DEMO_BLOCK_DOUBLES, dtype=torch.float64, device=device)
+
+
+def read_demo_block(block: torch.Tensor) -> dict:
+    """ONE device-to-host copy of a demonstration block: the four sums and the pass count."""
+    host = block.cpu()
+    out = {n: float(host[i]) for i, n in enumerate(('loss_sum', 'log_prob_sum', 'mode_error_sum', 'rows_sum'))}
+    out['passes'] = int(host.view(torch.int64)[4])
+    return out
+
+
+def mixed_policy_loss(lin, adv, old_logp, speed, similarity, u, demo_u, demo_w, clip_ratio: float, entropy_coef: float, du_da=None,
+                      du_db=None, grad_scale: float = 1.0, block: torch.Tensor = None):
+    """cdrl_beta_mixed_policy_loss, one launch: lin (B, 2A+2) -> (dlin (B, 2A+2), metrics (16,), aux (B, 4, A)) device tensors."""
+    lib = _lib.load()
+    B, A = int(lin.shape[0]), (int(lin.shape[1]) - 2) // 2
+    for name, t, shape in (('lin', lin, (B, 2 * A + 2)), ('adv', adv, (B,)), ('old_logp', old_logp, (B, A)), ('speed', speed, (B,)),
+                           ('similarity', similarity, (B,)), ('u', u, (B, A)), ('du_da', du_da, (B, A)), ('du_db', du_db, (B, A)),
+                           ('demo_u', demo_u, (B, A)), ('demo_w', demo_w, (B,))):
+        if t is not None:
+            LearnerEngine._chk(t, shape, f'mixed_policy_loss: {name}')
+    dlin = torch.empty_like(lin)
+    metrics = torch.zeros(16, dtype=torch.float32, device=lin.device)
+    aux = torch.empty((B, 4, A), dtype=torch.float32, device=lin.device)
+    hp = torch.empty(16, dtype=torch.float32, device=lin.device)
+    _lib.check(lib.cdrl_beta_mixed_policy_loss(_lib.ptr(lin), _lib.ptr(adv), _lib.ptr(old_logp), _lib.ptr(speed), _lib.ptr(similarity),
+                                               _lib.ptr(u), _lib.ptr(du_da), _lib.ptr(du_db), _lib.ptr(demo_u), _lib.ptr(demo_w),
+                                               float(clip_ratio), float(entropy_coef), B, A, float(grad_scale), _lib.ptr(dlin),
+                                               _lib.ptr(metrics), _lib.ptr(aux), _lib.ptr(hp), _lib.ptr(block),
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cdrl_beta_mixed_policy_loss')
+    return dlin, metrics, aux
 
 
 # slots 0..5 of CDRL_BUF_METRICS_R after a representation pass (cdrl_ntxent_loss, include/cdrl.h)

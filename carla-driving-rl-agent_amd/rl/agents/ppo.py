@@ -14,21 +14,30 @@ import torch
 from .. import utils
 from ..parameters import DynamicParameter
 from ..replay import ReplayPeriod, RolloutReplay, TrajectoryTable
+from ..demonstrations import DemonstrationStore, demo_split, draw_rows
 from .agents import Agent
 from ..._lib import CLIP_MODES, OPTIMIZERS
 from ... import traces, train_stats
 
 
+def demo_weight_checked(weight):
+    """demo_weight as given: a number must be finite and not negative (a schedule is taken as it is)."""
+    if isinstance(weight, (int, float)) and not isinstance(weight, bool) and not (np.isfinite(weight) and weight >= 0.0):
+        raise ValueError(f'demo_weight={weight!r} must be a finite number >= 0, or a DynamicParameter / schedule')
+    return weight
+
+
 class PPOAgent(Agent):
     replay, _replay_active = None, ()       # class-level defaults: an agent that never ran __init__ reuses nothing
     trust, _trust_anchor, _trust_stats = False, None, None      # ... and has no trust-region guard
+    demo_traces, _demo_active = None, False                     # ... and no demonstrations
 
     def __init__(self, *args, policy_lr=1e-3, gamma=0.99, lambda_=0.95, value_lr=3e-4, load=False,
                  optimization_steps=(1, 1), name='ppo-agent', optimizer='adam', clip_norm=(1.0, 1.0), clip_ratio=0.2,
                  seed_regularization=False, entropy_regularization=0.0, network: dict = None, update_frequency=1,
                  polyak=1.0, repeat_action=1, advantage_scale=2.0, train_stats_rows=256, clip_mode='tensor', skip_nonfinite=False,
                  joint_update=False, replay_rollouts=0, replay_rho_clip=1.0, replay_c_clip=1.0, target_kl=None, kl_penalty=0.0,
-                 kl_stop_factor=1.5, **kwargs):
+                 kl_stop_factor=1.5, demo_traces=None, demo_fraction=0.25, demo_weight=0.1, demo_rows=4096, demo_seed=None, **kwargs):
         """clip_mode: 'tensor' (default; utils.clip_gradients of the reference: tf.clip_by_norm per tensor of each head) or 'global'
         (tf.clip_by_global_norm of each optimizer's gradient list, the max_grad_norm of other PPO implementations; thresholds are
         those of clip_norm).  skip_nonfinite=True: a minibatch step whose gradients hold a NaN or an Inf leaves parameters and
@@ -56,7 +65,21 @@ class PPOAgent(Agent):
         policy objective.  Logged per update(): kl_divergence, kl_divergence_max, kl_stopped_steps, kl_stop_pass.  Needs the separate
         policy / value loops (joint_update=True: ValueError) and one process (an initialised process group: ValueError -- the ranks
         would decide differently); imitate() with a value weight runs joint passes, which such an agent's engines refuse.  Nobody has
-        measured what the guard does to learning or driving quality."""
+        measured what the guard does to learning or driving quality.
+        demo_traces / demo_fraction / demo_weight / demo_rows / demo_seed (not in the reference, not written to config.json;
+        DESIGN.md 6.16): expert demonstrations inside the PPO update, on when demo_traces is a directory of trace files.  At the
+        first update() the traces are loaded once, in sorted file order, into a device store of at most demo_rows rows (what does
+        not fit is counted in one printed line).  Every policy minibatch then holds batch_size - D fresh rows followed by
+        D = round(demo_fraction * batch_size) demonstration rows, drawn without replacement from the store by a generator of its
+        own (demo_seed) at every minibatch step; one trunk pass trains the fresh rows by the PPO surrogate and the demonstration
+        rows by the Beta log-likelihood of the expert's action with weight demo_weight -- a float or any DynamicParameter, read
+        once per update() and ticked per episode; at 0 the update() runs without demonstrations.  The value loop sees fresh rows
+        only.  Logged per update(): loss_demo, demo_log_prob, demo_mode_error, demo_rows_per_batch, demo_weight.  Refused with
+        ValueError: joint_update=True (no joint form of the mixed pass), replay_rollouts > 0 (kept rows and demonstration rows
+        would compete for the rows behind the fresh ones), target_kl / kl_penalty (the anchor sweep has no demonstration rows), an
+        initialised process group (the ranks would draw different rows for one collective step), a demo_fraction with D outside
+        1 .. batch_size - 1.  save_state() holds the generator and the schedule; the store is reloaded from the directory.  Nobody
+        has measured what demonstrations do to learning or driving quality."""
         assert 0.0 < polyak <= 1.0
         self.joint_update = bool(joint_update)
         if self.joint_update and optimization_steps[0] != optimization_steps[1]:
@@ -76,6 +99,7 @@ class PPOAgent(Agent):
             raise ValueError('target_kl / kl_penalty run in one process: every rank would measure the KL of its own shard and decide '
                              'on its own whether a collective step is taken; create the data-parallel agents without them')
         self._trust_anchor = None                   # (N, 2, A) alpha0 / beta0 of the policy rows of the running update()
+        self.demo_traces = demo_traces
         if int(replay_rollouts) != replay_rollouts or replay_rollouts < 0:
             raise ValueError(f'replay_rollouts={replay_rollouts!r}: the number of finished update-periods to keep, an integer >= 0 '
                              f'(0 = no reuse)')
@@ -99,6 +123,8 @@ class PPOAgent(Agent):
         self._gate_seen = dict(policy=0, value=0)      # skip counts already reported by an earlier update()
         self.train_stats_rows = int(train_stats_rows)
         super().__init__(*args, name=name, **kwargs)
+        if demo_traces is not None:         # (behind the base class: the split needs batch_size; in front of the network: a refusal allocates nothing)
+            self._init_demonstrations(demo_fraction, demo_weight, demo_rows, demo_seed, replay_rollouts)
         self.memory: PPOMemory = None
         self.gamma = gamma
         self.lambda_ = lambda_
@@ -187,12 +213,16 @@ class PPOAgent(Agent):
             return self._update_joint(t0)
         if self.trust:
             self.begin_trust_region()
+        if self.demo_traces is not None:
+            self.begin_demonstrations()
         value_batches = list(self.get_value_batches())
         policy_batches = list(self.get_policy_batches())
         policy_batches, value_batches = self.agree_on_batches(policy_batches, value_batches)
         for _ in range(self.optimization_steps['policy']):
             for batch in policy_batches:
                 self.seed_regularization()
+                if self._demo_active:
+                    batch = self.with_demonstrations(batch)
                 total_loss, grads = self.get_policy_gradients(batch)
                 self.update_policy(grads)
                 self.log(loss_total=total_loss, lr_policy=self.policy_lr.value)
@@ -209,11 +239,89 @@ class PPOAgent(Agent):
         self.log_gate_stats()
         if self.trust:
             self.end_trust_region()
+        if self.demo_traces is not None:
+            self.end_demonstrations()
         if self.replay is not None:
             self.keep_period()
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         print(f'Update took {round(time.time() - t0, 3)}s')
+
+    # -- expert demonstrations inside the update (demo_traces; rl/demonstrations.py) ---------------------------------
+    def _init_demonstrations(self, fraction, weight, rows, seed, replay_rollouts):
+        """Constructor half: every refusal, the split, the schedule and the generator.  Nothing touches the device."""
+        if not isinstance(self.demo_traces, (str, os.PathLike)) or not os.path.isdir(self.demo_traces):
+            raise ValueError(f'demo_traces={self.demo_traces!r} is not a directory of trace files (None turns demonstrations off)')
+        if self.joint_update:
+            raise ValueError('demo_traces needs the separate policy and value loops: the mixed policy pass has no joint form; create '
+                             'the agent with joint_update=False')
+        if replay_rollouts:
+            raise ValueError('demo_traces and replay_rollouts > 0 exclude each other: kept rollout rows and demonstration rows would '
+                             'both ride behind the fresh rows of a policy minibatch; create the agent with replay_rollouts=0')
+        if self.trust:
+            raise ValueError('demo_traces and target_kl / kl_penalty exclude each other: the anchor sweep of the trust-region guard '
+                             'covers the rollout rows and has no demonstration rows')
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            raise ValueError('demo_traces runs in one process: every rank would draw demonstration rows of its own for a collective '
+                             'step; create the data-parallel agents without it')
+        self.demo_rows_per_batch, self.demo_fresh_rows = demo_split(self.batch_size, fraction)
+        if int(rows) != rows or rows < self.demo_rows_per_batch:
+            raise ValueError(f'demo_rows={rows!r}: the cap of the demonstration store, an integer of at least the '
+                             f'{self.demo_rows_per_batch} rows a policy minibatch takes')
+        self.demo_fraction, self.demo_store_cap = float(fraction), int(rows)
+        self.demo_weight = DynamicParameter.create(value=demo_weight_checked(weight))
+        self.demo_rng = np.random.default_rng(seed)
+        self.demo_store, self._demo_block, self._demo_w = None, None, 0.0
+
+    def load_demonstrations(self) -> DemonstrationStore:
+        """The store, built at the first call: the traces of demo_traces in sorted file order through the checks and the windowing
+        of imitate() (need_info: the auxiliary heads train on every row), until demo_rows rows are on the device."""
+        if self.demo_store is None:
+            def tensors():
+                rows = 0
+                for trace in traces.load_traces(self.demo_traces):
+                    if rows >= self.demo_store_cap:      # counted, not uploaded
+                        yield dict(u=torch.empty((self._check_trace(trace, True, 0.0), 0)))
+                        continue
+                    t = self._trace_tensors(trace, None, True, 0.0)
+                    rows += int(t['u'].shape[0])
+                    yield t
+            self.demo_store = DemonstrationStore(tensors(), self.demo_store_cap, self.demo_rows_per_batch)
+            print(f'[demonstrations] {self.demo_store.rows} rows of {self.demo_store.traces} traces on the device'
+                  + (f'; {self.demo_store.left_out} rows left out (demo_rows={self.demo_store_cap})' if self.demo_store.left_out else ''))
+        return self.demo_store
+
+    def begin_demonstrations(self):
+        """In front of the batch pipelines: the store (first call), this update()'s weight, the zeroed statistics block."""
+        self._demo_w = float(self.demo_weight())
+        self._demo_active = bool(np.float32(self._demo_w) > 0.0)       # (as the device will see it: demo_w > 0 makes the row a demonstration row)
+        if not self._demo_active:
+            return
+        self.load_demonstrations()
+        if self._demo_block is None:
+            from ...engine import demo_block
+            self._demo_block = demo_block(self.device)
+        self._demo_block.zero_()
+
+    def draw_demonstrations(self) -> dict:
+        """D rows of the store for one minibatch step: one draw of the demonstration generator, one device gather per tensor."""
+        return self.demo_store.gather(draw_rows(self.demo_rng, self.demo_store.rows, self.demo_rows_per_batch))
+
+    def with_demonstrations(self, batch):
+        """Hook: a policy minibatch of fresh rows -> what get_policy_gradients takes for the mixed pass (CARLAgent)."""
+        raise NotImplementedError(f'{type(self).__name__} has no mixed policy pass: demo_traces is implemented by CARLAgent')
+
+    def end_demonstrations(self):
+        """Behind the minibatch loops: ONE small copy of the statistics block, logged as per-pass means."""
+        if not self._demo_active:
+            self.log(demo_weight=self._demo_w, demo_rows_per_batch=0)
+            return
+        self._demo_active = False
+        from ...engine import read_demo_block
+        st = read_demo_block(self._demo_block)
+        n = max(1, st['passes'])
+        self.log(loss_demo=st['loss_sum'] / n, demo_log_prob=st['log_prob_sum'] / n, demo_mode_error=st['mode_error_sum'] / n,
+                 demo_rows_per_batch=st['rows_sum'] / n, demo_weight=self._demo_w)
 
     # -- trust-region guard (target_kl / kl_penalty; DESIGN.md 6.14) -----------------------------------------------------------------
     def begin_trust_region(self):
@@ -431,8 +539,8 @@ class PPOAgent(Agent):
             self.replay.clear()
         self._replay_active = []
 
-    def _batches(self, tensors, shuffle, shuffle_batches):
-        return utils.data_to_batches(tensors=tensors, batch_size=self.batch_size, drop_remainder=self.drop_batch_remainder,
+    def _batches(self, tensors, shuffle, shuffle_batches, batch_size=None):
+        return utils.data_to_batches(tensors=tensors, batch_size=batch_size or self.batch_size, drop_remainder=self.drop_batch_remainder,
                                      skip=self.skip_count, num_shards=self.obs_skipping, shuffle=shuffle,
                                      shuffle_batches=shuffle_batches, seed=int(self.rng.integers(2 ** 31)))
 
@@ -440,7 +548,9 @@ class PPOAgent(Agent):
         return self._batches(self.value_batch_tensors(), True, False)
 
     def get_policy_batches(self):
-        return self._batches(self.policy_batch_tensors(), self.shuffle, self.shuffle_batches)
+        # (demonstrations: minibatches of the fresh rows alone; with_demonstrations puts D rows behind each)
+        return self._batches(self.policy_batch_tensors(), self.shuffle, self.shuffle_batches,
+                             self.demo_fresh_rows if self._demo_active else None)
 
     def joint_batch_tensors(self):
         return tuple(self.policy_batch_tensors()) + (self.with_replay(self.memory.returns, 'returns_be'),)
@@ -1030,6 +1140,24 @@ class PPOAgent(Agent):
         self.policy_lr.on_episode()
         self.value_lr.on_episode()
         self.adv_scale.on_episode()
+        if self.demo_traces is not None:
+            self.demo_weight.on_episode()
+
+    def host_state(self) -> dict:
+        """Agent.host_state; with demonstrations on also their generator and the weight's schedule step."""
+        state = super().host_state()
+        if self.demo_traces is not None:
+            state['demo'] = dict(rng=self.demo_rng.bit_generator.state, weight=self.demo_weight.serialize())
+        return state
+
+    def set_host_state(self, state: dict):
+        super().set_host_state(state)
+        if self.demo_traces is not None:
+            if 'demo' not in state:
+                print('[load_state] the state was saved without demonstrations: their generator and schedule start over')
+                return
+            self.demo_rng.bit_generator.state = state['demo']['rng']
+            self.demo_weight.load(config=state['demo']['weight'])
 
 
 class Rollout:

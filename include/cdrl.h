@@ -448,6 +448,41 @@ typedef struct cdrl_clone_batch {
 } cdrl_clone_batch;
 int cdrl_learner_clone_forward_backward(cdrl_learner* l, const cdrl_clone_batch* b, float policy_weight, float value_weight,
                                         float aux_weight, float grad_scale, void* stream);
+/* ---- expert demonstrations inside the PPO update -------------------------------
+ * A policy minibatch of fresh rows and demonstration rows through ONE trunk pass: the policy pass with the loss of
+ * cdrl_beta_mixed_policy_loss (below, where its definitions stand) in the place of the policy loss.  demo_u (B, A) is the expert
+ * action in the unit interval, demo_w (B) the row's weight: row b is a DEMONSTRATION row iff demo_w[b] > 0 and a PPO row otherwise.
+ * With ND demonstration rows and NP = B - ND PPO rows the objective is
+ *   sum_{PPO rows} surrogate_b / NP  +  sum_{demo rows} demo_w[b] * (-mean_a log Beta(clip(demo_u[b,a]); alpha, beta)) / ND
+ *   - entropy_coef * entropy + speed_loss + sim_loss,      the last three over all B rows as in the policy loss;
+ * a term whose row count is 0 is 0.  advantages, old_log_prob, u, du_dalpha and du_dbeta of a demonstration row are never read (they
+ * may hold anything, NaN included); speed / similarity of such a row are its trace's targets.
+ *
+ * cdrl_learner_demo_forward_backward / _resample: trunk forward, head forward, head and trunk backward, freeze_trunk, compute modes,
+ * the train-stats ring and the gradient gate are those of cdrl_learner_policy_forward_backward / _resample; the re-sampled form
+ * draws u for all B rows with the same Philox offsets as the policy pass (the draw of a demonstration row is ignored).  The
+ * stored-action form is captured and replayed as a hipGraph; batch pointers, demo_u, demo_w, grad_scale and the demonstration block
+ * are the key.  Writes CDRL_BUF_METRICS_P slots 0..10 and CDRL_BUF_AUX_P.  With demo_w all zero the pass writes the bits of the
+ * policy pass.  -1: a null demo_u / demo_w, a batch with an anchor (the trust-region sweep has no demonstration rows).  On a
+ * learner with trust = 1 the pass clears the latch's `armed`, like every pass without an anchor.  The apply is
+ * cdrl_learner_policy_apply as it is.
+ *
+ * cdrl_learner_set_demo_block: a caller-owned device block (cdrl_demo_stats, 40 bytes, 8-byte aligned, zeroed by the caller) that
+ * every later demonstration pass of this learner adds to -- metrics slots 7..10 as rounded to float, and a pass count -- by one
+ * thread behind the loss, in stream order, without atomics; NULL: none (the default).  Read it with one copy when the passes of an
+ * update are enqueued.  Learners of several minibatch sizes may be given the same block. */
+typedef struct cdrl_demo_stats {
+    double loss_sum;           /* sum over the passes of the demonstration term (metrics[7]) */
+    double log_prob_sum;       /* ... of the demonstration rows' mean log-probability (metrics[8]) */
+    double mode_error_sum;     /* ... of their mean absolute mode error (metrics[9]) */
+    double rows_sum;           /* ... of ND (metrics[10]) */
+    int64_t passes;
+} cdrl_demo_stats;
+int cdrl_learner_set_demo_block(cdrl_learner* l, cdrl_demo_stats* device_block);
+int cdrl_learner_demo_forward_backward(cdrl_learner* l, const cdrl_policy_batch* b, const float* demo_u, const float* demo_w,
+                                       float grad_scale, void* stream);
+int cdrl_learner_demo_forward_backward_resample(cdrl_learner* l, const cdrl_policy_batch* b, const float* demo_u, const float* demo_w,
+                                                uint64_t seed, uint64_t offset, float grad_scale, void* stream);
 /* ---- contrastive pre-training of the trunk ------------------------------------
  * The reference's curriculum calls agent.learn_representation and never defines it; rl/augmentations/simclr.py names the objective.
  * The definition here is the project's own: NT-Xent (table at the loss entry, below) on the trunk's output, B = 2N rows, rows i and
@@ -1184,6 +1219,25 @@ int cdrl_beta_kl(const float* lin, const float* anchor, int B, int A, float kl_c
 int cdrl_beta_clone_loss(const float* lin, const float* u, const float* weight, const float* speed, const float* similarity,
                          float entropy_coef, float aux_weight, int B, int A, float grad_scale, float* dlin, float* metrics, float* aux,
                          void* stream);
+/* Mixed policy loss on linear head outputs lin (B, 2A+2): the arguments of cdrl_beta_ppo_loss plus demo_u (B, A),
+ * demo_w (B) and an optional device block.  Row b is a demonstration row iff demo_w[b] > 0, a PPO row otherwise; ND and NP = B - ND
+ * are counted in a block reduction in front of the row loop.
+ *   PPO term   = that of cdrl_beta_ppo_loss (same clipped action, same rule for the pathwise Jacobians, same mean-over-actions ratio
+ *                and routing of the minimum), summed over the PPO rows and divided by NP; 0 when NP = 0.
+ *   demo term  = sum_b demo_w[b] * (-mean_a log Beta(x; alpha, beta)) / ND, x = clip(demo_u, eps, 1 - eps), no gradient through x;
+ *                adv, old_logp, u, du_da, du_db of such a row are not read; 0 when ND = 0.
+ *   entropy, speed_loss, sim_loss: over all B rows, as cdrl_beta_ppo_loss has them.
+ * dlin (B, 2A+2) = grad_scale * d total / d lin, every entry of every row written.  metrics: [0] total including the demo term
+ * [1] PPO term [2] entropy [3] speed_loss [4] sim_loss [5] mean ratio and [6] mean log-probability of the PPO rows [7] demo term
+ * [8] mean log-probability of the demonstration rows [9] their mean |mode - x| (as cdrl_beta_clone_loss slot 7) [10] ND.
+ * demo_block (device, or NULL): thread 0 adds slots 7..10 and one pass, see cdrl_learner_set_demo_block.
+ * With demo_w all zero, dlin and metrics[0..6] are bit-identical to cdrl_beta_ppo_loss on the same inputs, with and without
+ * du_da / du_db.  One workgroup of 256 threads; transcendentals and sums in double, one rounding per output.
+ * -1 (and cdrl_last_error): A outside 1..8, B < 1, a null lin / u / demo_u / demo_w / dlin / metrics. */
+int cdrl_beta_mixed_policy_loss(const float* lin, const float* adv, const float* old_logp, const float* speed,
+                                const float* similarity, const float* u, const float* du_da, const float* du_db, const float* demo_u,
+                                const float* demo_w, float clip_ratio, float entropy_coef, int B, int A, float grad_scale, float* dlin,
+                                float* metrics, float* aux, float* hp_scratch16, cdrl_demo_stats* demo_block, void* stream);
 /* NT-Xent, the normalised-temperature cross-entropy over pairs of views, on embeddings z (B, D), B = 2N: rows i and
  * pair(i) = (i + N) mod B are the two views of one observation.
  *   zn_i = z_i / max(||z_i||, 1e-12);  s_ij = zn_i . zn_j / temperature;  l_i = log sum_{j != i} exp(s_ij) - s_{i,pair(i)};
