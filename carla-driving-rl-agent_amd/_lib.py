@@ -289,6 +289,7 @@ PROTOTYPES = {
     'cdrl_occlusion_rows': (_i, [_fp] * 5 + [_i] * 12 + [_fp] * 5),
     'cdrl_occlusion_scores': (_i, [_fp, _fp, _fp, _i, _i, _fp, _fp]),
     'cdrl_occlusion_maps': (_i, [_fp] + [_i] * 8 + [_fp, _fp]),
+    'cdrl_beta_score': (_i, [_fp] * 6 + [_i, _i, _i, _fp, _fp, _fp]),
     'cdrl_ntxent_workspace_floats': (_i64, [_i, _i]),
     'cdrl_ntxent_loss': (_i, [_fp, _i, _i, _f, _f, _fp, _fp, _fp, _fp]),
     'cdrl_beta_ppo_loss': (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _f, _f, _i, _i, _f, _fp, _fp, _fp, _fp, _fp]),

@@ -16,7 +16,7 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib, traces, train_stats
-from ..engine import act_stats_width, occlusion_baseline
+from ..engine import act_stats_width, occlusion_baseline, read_score_block, score_block
 from ..explain import BASELINES, MODALITIES, check_arguments, occlusion_frames, score_names
 from ..evaluation import RESULT_KEYS, evaluation_info, summarize, trial_seed
 from ..parallel import DataParallelLearner
@@ -493,11 +493,111 @@ class CARLAgent(PPOAgent):
         eng.clone_step(eng.stage(b, 'clone'), policy_weight, value_weight, aux_weight)
         return eng
 
+    # -- held-out traces: scoring and validation -------------------------------------------------------
+    def score_traces(self, traces_dir=None, *, max_traces=None, chunk=None, value=True, aux=True, per_trace=False) -> dict:
+        """How well the ACTING network (old_policy, moving statistics: what predict() runs) fits expert traces, e.g. ones it was not
+        trained on.  The files are read in sorted order (no generator draw), each is checked and uploaded once like imitate() does
+        (returns with the agent's gamma), and goes through inference forwards of `chunk` rows (default batch_size) with one
+        cdrl_beta_score launch per chunk; ONE block and one host read for the whole call (per_trace: one block per trace, read
+        together at the end and returned under 'traces', the totals being their sums).
+        -> engine.read_score_block's dict: rows, log_prob, mode_error, bias, rmse, predicted_std, entropy (each also `_per_action`),
+        pit_histogram, coverage_50 / coverage_90 per action, value_bias / value_rmse / explained_variance, speed_rmse /
+        similarity_rmse, nonfinite, pit_unconverged, block.  value / aux: score the value head against the returns / the auxiliary
+        heads against info_speed (km/h, / 100 as in training) and info_similarity; switched off with one printed line for traces
+        that lack `reward` / `info_*` (the figures are then None).
+        Not touched: parameters, moving statistics, optimizer state, memories, the sampler's stream; nothing is logged.
+        RuntimeError under data parallelism; ValueError: no traces directory, no trace file in it, chunk outside 1..65535, a trace
+        that does not fit the agent (_check_trace)."""
+        if getattr(self, 'data_parallel', False):
+            raise RuntimeError('score_traces() runs on one GPU: score in a single process (save(), and load the weights there), not '
+                               'in the data-parallel run')
+        path = self._traces_dir(traces_dir)
+        chunk = self.batch_size if chunk is None else chunk
+        if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= 65535:
+            raise ValueError(f'score_traces: chunk = {chunk}: 1 to 65535 rows per forward')
+        if not traces.trace_files(path):
+            raise ValueError(f'score_traces: no trace-*.npz file in {path}')
+        A, chunk = self.num_actions, int(chunk)
+        total = None if per_trace else score_block(A, self.device)
+        blocks, told = [], set()
+        for trace in traces.load_traces(path, max_amount=max_traces, shuffle=False):
+            with_value = bool(value) and 'reward' in trace
+            with_aux = bool(aux) and 'info_speed' in trace and 'info_similarity' in trace
+            for asked, given, lacks, what in ((value, with_value, 'reward', 'the value head'),
+                                              (aux, with_aux, 'info_speed / info_similarity', 'the auxiliary heads')):
+                if asked and not given and what not in told:
+                    told.add(what)
+                    print(f'score_traces: a trace in {path} has no {lacks}: {what} are not scored on it')
+            data = self._trace_tensors(trace, None, with_aux, 1.0 if with_value else 0.0)
+            block = score_block(A, self.device) if per_trace else total
+            self.network.score_rows(data['states'], data['u'], data.get('returns'), data.get('speed'), data.get('similarity'),
+                                    chunk=chunk, block=block)
+            blocks.append(block)
+        if not per_trace:
+            return read_score_block(total, A)
+        each = read_score_block(torch.stack(blocks), A)
+        out = read_score_block(torch.as_tensor(np.sum([t['block'] for t in each], axis=0)), A)
+        out['traces'] = each
+        return out
+
+    def imitate(self, *args, validation_dir=None, validation_every=1, patience=None, **kw):
+        """PPOAgent.imitate (same arguments) with validation on held-out traces: with `validation_dir`, behind every
+        `validation_every`-th epoch the acting network is brought up to date (update_old_policy()) and scored on that directory
+        (score_traces); logged: validation_log_prob, validation_mode_error, validation_rmse, validation_coverage_90 (the mean over
+        the actions) and, with returns, validation_value_rmse.  patience=k ends the run after k validations in a row without a new
+        best validation_log_prob (one printed line); the weights stay those of the last epoch.  The defaults are imitate() as it
+        was: no launch more.  With polyak == 1 the validations do not change what imitate() leaves: the clone pass never reads
+        the old policy and the final update_old_policy() overwrites it.  With polyak < 1 every update_old_policy() averages, so
+        validating would change the result: ValueError.  ValueError also for patience without validation_dir."""
+        if validation_dir is None:
+            if patience is not None:
+                raise ValueError(f'imitate(patience={patience}) without validation_dir: early stopping needs held-out traces to score')
+            return super().imitate(*args, **kw)
+        if float(self.polyak_coeff) < 1.0:
+            raise ValueError(f'imitate(validation_dir=...): the agent was created with polyak={self.polyak_coeff}; every validation '
+                             f'calls update_old_policy(), which with polyak < 1 averages the old policy once more and so changes '
+                             f'what imitate() leaves; validate with score_traces() after the run instead')
+        if isinstance(validation_every, bool) or not isinstance(validation_every, (int, np.integer)) or validation_every < 1:
+            raise ValueError(f'imitate(validation_every={validation_every}): a number of epochs, at least 1')
+        if patience is not None and (isinstance(patience, bool) or not isinstance(patience, (int, np.integer)) or patience < 1):
+            raise ValueError(f'imitate(patience={patience}): a number of validations, at least 1 (or None)')
+        self._validation = dict(dir=validation_dir, every=int(validation_every), patience=patience, best=-np.inf, stale=0)
+        try:
+            return super().imitate(*args, **kw)
+        finally:
+            self._validation = None
+
+    _validation = None          # the run in flight of imitate(validation_dir=...)
+
+    def imitation_epoch_end(self, epoch: int) -> bool:
+        v = self._validation
+        if v is None or epoch % v['every']:
+            return False
+        self.network.update_old_policy()
+        s = self.score_traces(v['dir'])
+        entry = dict(validation_log_prob=s['log_prob'], validation_mode_error=s['mode_error'], validation_rmse=s['rmse'],
+                     validation_coverage_90=float(np.mean(s['coverage_90'])))
+        if s['value_rmse'] is not None:
+            entry['validation_value_rmse'] = s['value_rmse']
+        self.log(**entry)
+        self.write_summaries()
+        if v['patience'] is None:
+            return False
+        if s['log_prob'] > v['best']:
+            v['best'], v['stale'] = s['log_prob'], 0
+            return False
+        v['stale'] += 1
+        if v['stale'] < v['patience']:
+            return False
+        print(f"[{epoch}] imitate: no new best validation_log_prob ({v['best']:.6g}) in {v['stale']} validation(s): stopping")
+        return True
+
     def imitation_learning(self, alpha=0.5, beta=0.5, clip_grad=1.0, lr=1e-3, polyak=None, epochs=1, shuffle_data=True,
                            traces_dir=None, **kw):
         """The supervised stage of the reference's curriculum (Stage.imitation_learning, core/learning.py:180-181, calls this name
         with these keywords; the reference never defines it): imitate() with alpha as the policy weight, beta as the value weight,
-        clip_grad as every optimizer's clip threshold and lr as every optimizer's learning rate.  polyak: fixed when the learner
+        clip_grad as every optimizer's clip threshold and lr as every optimizer's learning rate; every other keyword of imitate()
+        (validation_dir, validation_every, patience among them) goes through.  polyak: fixed when the learner
         engines are created (CARLAgent(polyak=...)), so any other value is refused."""
         if polyak is not None and float(polyak) != float(self.polyak_coeff):
             raise ValueError(f'imitation_learning(polyak={polyak}): the agent was created with polyak={self.polyak_coeff}, which its '

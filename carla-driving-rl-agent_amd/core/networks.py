@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..engine import LearnerEngine, beta_act, ACT_SAMPLE, ACT_MODE, occlusion_rows, occlusion_scores, occlusion_maps
+from ..engine import LearnerEngine, beta_act, ACT_SAMPLE, ACT_MODE, occlusion_rows, occlusion_scores, occlusion_maps, \
+    beta_score, score_block
 from ..explain import occlusion_row_count, occlusion_frames
 from ..init import init_engine_parameters
 from ..rl.networks import Network
@@ -171,6 +172,18 @@ class CARLANetwork(Network):
                                                          self.engine._stream()), 'cdrl_beta_sample_logp')
         return action, out['mean'].clone(), out['std'].clone(), log_prob, out['value'].clone()
 
+    def _row_chunks(self, st: dict, chunk: int):
+        """The N rows of picked inputs, `chunk` at a time -> (start, rows that count, chunk of inputs): a full chunk is a view, the
+        last one is filled up by repeating the last row instead of planning an engine for its size."""
+        n = st['state_image'].shape[0]
+        for start in range(0, n, chunk):
+            m = min(chunk, n - start)
+            if m == chunk:
+                yield start, m, {k: v[start:start + chunk] for k, v in st.items()}
+            else:
+                index = torch.arange(start, start + chunk, device=self.device).clamp_(max=n - 1)
+                yield start, m, {k: v.index_select(0, index) for k, v in st.items()}
+
     def distribution_and_value(self, inputs: dict, chunk: int):
         """The acting network on N stored rows -> (alpha (N, A), beta (N, A), value (N, 2)), fresh tensors: inference forwards as
         predict() runs them (old_policy, moving statistics) through ONE engine, rollout_for(chunk), `chunk` rows at a time; the last
@@ -183,18 +196,32 @@ class CARLANetwork(Network):
         alpha = torch.empty((n, A), dtype=torch.float32, device=self.device)
         beta = torch.empty((n, A), dtype=torch.float32, device=self.device)
         value = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-        for start in range(0, n, chunk):
-            m = min(chunk, n - start)
-            if m == chunk:
-                rows = {k: v[start:start + chunk] for k, v in st.items()}
-            else:
-                index = torch.arange(start, start + chunk, device=self.device).clamp_(max=n - 1)
-                rows = {k: v.index_select(0, index) for k, v in st.items()}
+        for start, m, rows in self._row_chunks(st, chunk):
             out = eng.predict(rows)
             alpha[start:start + m].copy_(out['alpha'][:m])
             beta[start:start + m].copy_(out['beta'][:m])
             value[start:start + m].copy_(out['value'][:m])
         return alpha, beta, value
+
+    def score_rows(self, inputs: dict, u, returns=None, speed=None, similarity=None, chunk: int = 32, block=None):
+        """The acting network scored on N recorded rows: inference forwards exactly as distribution_and_value runs
+        them (rollout_for(chunk), old_policy, moving statistics, the last chunk filled up by repeating the last row), and per chunk
+        ONE cdrl_beta_score launch that reads the engine's persistent predict outputs where they lie and adds the chunk's sums to
+        `block` (engine.score_block; None: a fresh one) -- no per-chunk copy of an output, no host read.  u (N, A) expert actions in
+        the unit interval, returns (N, 2) as (base, exponent) or None, speed / similarity (N,) or None: contiguous float32 device
+        tensors, of which every chunk is a view.  Nothing is sampled: `action_index`, the memory and the logs stay as they are.
+        -> block."""
+        st = self._pick(inputs)
+        chunk = int(chunk)
+        eng = self.rollout_for(chunk)
+        if block is None:
+            block = score_block(self.cfg['A'], self.device)
+        part = lambda t, start, m: None if t is None else t[start:start + m]
+        for start, m, rows in self._row_chunks(st, chunk):
+            eng.predict(rows)
+            beta_score(eng._pred_out[0], eng._pred_out[1], u[start:start + m], part(returns, start, m), part(speed, start, m),
+                       part(similarity, start, m), count=m, block=block)
+        return block
 
     def explain_rows(self, inputs: dict, grid, baseline, per_frame=False, modalities=True, upsample='nearest', normalize=True, chunk=32):
         """Occlusion saliency of ONE observation: inputs (T, ...) per key, baseline (T, H, W, 3) on the device.  The

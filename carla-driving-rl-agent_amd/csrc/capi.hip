@@ -6,6 +6,7 @@
 
 #include "../../include/cdrl.h"
 #include "engine.h"
+#include "score_block.h"
 
 using namespace cdrl;
 
@@ -1971,6 +1972,17 @@ int cdrl_beta_kl(const float* lin, const float* anchor, int B, int A, float kl_c
     a.lin = lin; a.anchor = anchor; a.dlin = dlin; a.trust = nullptr; a.kl_coef = kl_coef; a.metrics = metrics;
     a.B = B; a.A = A; a.inv_world = grad_scale;
     return beta_kl(a, S(stream));
+}
+
+int cdrl_beta_score(const float* dist, const float* value, const float* u, const float* returns_be, const float* speed,
+                    const float* similarity, int rows, int count, int A, double* block, double* pit, void* stream) {
+    static_assert(CDRL_SCORE_BINS == SCORE_BINS && CDRL_SCORE_HEAD == SCORE_HEAD && CDRL_SCORE_PER_ACTION == SCORE_PER_ACTION &&
+                      CDRL_SCORE_BLOCK(8) == score_block_doubles(8),
+                  "cdrl.h and score_block.h disagree on the score block");
+    BetaScoreArgs a;
+    a.dist = dist; a.value = value; a.u = u; a.returns_be = returns_be; a.speed = speed; a.similarity = similarity;
+    a.rows = rows; a.count = count; a.A = A; a.block = block; a.pit = pit;
+    return beta_score(a, S(stream));
 }
 
 int64_t cdrl_ntxent_workspace_floats(int B, int D) { return ntxent_workspace_floats(B, D); }

@@ -764,6 +764,20 @@ int occlusion_scores(const float* alpha, const float* beta, const float* value, 
 int occlusion_maps(const double* scores, int K, int F, int gh, int gw, int H, int W, int upsample, int normalize, float* maps,
                    hipStream_t st);
 
+// ---------------------------------------------------------------- scoring on held-out rows (score.hip)
+struct BetaScoreArgs {
+    const float* dist;          // [rows][4][A] alpha, beta, mean, std as learner_predict writes them (mean and std are not read)
+    const float* value;         // [rows][4] base, exp, speed, similarity
+    const float* u;             // [count][A] expert actions in the unit interval
+    const float* returns_be;    // [count][2] (base, exp), or null
+    const float *speed, *similarity;    // [count] each, both or neither
+    int rows, count, A;         // the first count <= rows rows are scored
+    double* block;              // score_block_doubles(A) doubles (score_block.h), read-modify-written
+    double* pit;                // [count][A] or null: I_x(alpha, beta) of every scored element, NaN where it was not formed
+};
+// one launch of one workgroup; arguments checked here (-1 and cdrl_last_error)
+int beta_score(const BetaScoreArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- optimiser (optim.hip)
 // Device hyper-parameter block, refreshed by the host before each step (graph-replay safe).
 struct DevHP {

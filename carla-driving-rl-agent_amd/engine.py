@@ -1046,3 +1046,111 @@ def occlusion_maps(scores: torch.Tensor, frames: int, grid, size, upsample: str 
                                                _lib.ptr(maps), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
                'cdrl_occlusion_maps')
     return maps
+
+
+# ---------------------------------------------------------------- scoring on held-out rows (csrc/score.hip)
+SCORE_BINS = 10
+# the score block of cdrl_beta_score (include/cdrl.h, csrc/score_block.h): slot of every head entry, slot of every entry inside an
+# action's group, the size of both; all doubles
+SCORE_LAYOUT = dict(
+    head=dict(rows=0, rows_returns=1, rows_aux=2, nonfinite=3, pit_unconverged=4, value_error=8, value_error2=9, returns=10,
+              returns2=11, speed_error2=12, similarity_error2=13),
+    head_size=16,
+    action=dict(count=0, log_prob=1, mode_error=2, error=3, error2=4, variance=5, entropy=6, cover_50=7, cover_90=8, histogram=9),
+    action_size=9 + SCORE_BINS)
+
+
+def score_block_size(A: int) -> int:
+    """CDRL_SCORE_BLOCK(A) (include/cdrl.h): doubles of a score block."""
+    return SCORE_LAYOUT['head_size'] + SCORE_LAYOUT['action_size'] * int(A)
+
+
+def score_block(A: int, device) -> torch.Tensor:
+    """A zeroed score block for `A` actions: what beta_score adds to and read_score_block reads."""
+    if not 1 <= int(A) <= 8:
+        raise ValueError(f'score_block: A = {A} actions outside 1..8')
+    return torch.zeros(score_block_size(A), dtype=torch.float64, device=device)
+
+
+def beta_score(dist: torch.Tensor, value: torch.Tensor, u: torch.Tensor, returns: torch.Tensor = None, speed: torch.Tensor = None,
+               similarity: torch.Tensor = None, count: int = None, block: torch.Tensor = None, pit: torch.Tensor = None):
+    """The head outputs of one inference chunk against recorded rows (cdrl_beta_score, one launch, double arithmetic): dist
+    (rows, 4, A) and value (rows, 4) as LearnerEngine.predict leaves them, u (count, A) expert actions in the unit interval, returns
+    (count, 2) as (base, exponent) or None, speed / similarity (count,) -- both or neither.  Only the first `count` <= rows rows are
+    scored (default: the rows of u).  block: a score_block(A) the sums are ADDED to (None: a fresh one); pit: float64 (count, A) that
+    takes every element's Beta CDF at the expert action, or None.  -> block."""
+    _occ_check('beta_score: dist', dist)
+    if dist.dim() != 3 or dist.shape[1] != 4 or not 1 <= dist.shape[2] <= 8:
+        raise ValueError(f'beta_score: dist must be (rows, 4, 1 <= A <= 8), got {tuple(dist.shape)}')
+    rows, A = int(dist.shape[0]), int(dist.shape[2])
+    _occ_check('beta_score: value', value, (rows, 4))
+    _occ_check('beta_score: u', u)
+    count = int(u.shape[0]) if count is None else int(count)
+    if not 1 <= count <= rows:
+        raise ValueError(f'beta_score: count = {count} outside 1..{rows} (the rows of dist)')
+    _occ_check('beta_score: u', u, (count, A))
+    if (speed is None) != (similarity is None):
+        raise ValueError('beta_score: speed and similarity go together: both or neither')
+    for name, t, shape in (('returns', returns, (count, 2)), ('speed', speed, (count,)), ('similarity', similarity, (count,))):
+        if t is not None:
+            _occ_check(f'beta_score: {name}', t, shape)
+    if block is None:
+        block = score_block(A, dist.device)
+    _occ_check('beta_score: block', block, (score_block_size(A),), torch.float64)
+    if pit is not None:
+        _occ_check('beta_score: pit', pit, (count, A), torch.float64)
+    for name, t in (('value', value), ('u', u), ('returns', returns), ('speed', speed), ('similarity', similarity), ('block', block),
+                    ('pit', pit)):
+        if t is not None and t.device != dist.device:
+            raise ValueError(f'beta_score: {name} is on {t.device}, dist on {dist.device}')
+    _lib.check(_lib.load().cdrl_beta_score(_lib.ptr(dist), _lib.ptr(value), _lib.ptr(u), _lib.ptr(returns), _lib.ptr(speed),
+                                           _lib.ptr(similarity), rows, count, A, _lib.ptr(block), _lib.ptr(pit),
+                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'cdrl_beta_score')
+    return block
+
+
+def _score_figures(host: np.ndarray, A: int) -> dict:
+    """The derived figures of one score block on the host (numpy float64 of score_block_size(A) entries)."""
+    head, act = SCORE_LAYOUT['head'], SCORE_LAYOUT['action']
+    groups = host[SCORE_LAYOUT['head_size']:].reshape(A, SCORE_LAYOUT['action_size'])
+    div = lambda s, n: float(s) / float(n) if n > 0 else float('nan')
+    root = lambda s, n: float(np.sqrt(max(float(s), 0.0) / float(n))) if n > 0 else float('nan')
+    n = groups[:, act['count']]
+    total = float(n.sum())
+    out = dict(rows=int(host[head['rows']]), nonfinite=int(host[head['nonfinite']]), pit_unconverged=int(host[head['pit_unconverged']]))
+    for name, slot in (('log_prob', 'log_prob'), ('mode_error', 'mode_error'), ('bias', 'error'), ('entropy', 'entropy')):
+        out[name] = div(groups[:, act[slot]].sum(), total)
+        out[name + '_per_action'] = [div(groups[a, act[slot]], n[a]) for a in range(A)]
+    for name, slot in (('rmse', 'error2'), ('predicted_std', 'variance')):
+        out[name] = root(groups[:, act[slot]].sum(), total)
+        out[name + '_per_action'] = [root(groups[a, act[slot]], n[a]) for a in range(A)]
+    hist = groups[:, act['histogram']:act['histogram'] + SCORE_BINS]
+    out['pit_histogram'] = np.rint(hist).astype(np.int64)
+    with_pit = hist.sum(axis=1)                 # elements whose PIT was formed
+    out['coverage_50'] = [div(groups[a, act['cover_50']], with_pit[a]) for a in range(A)]
+    out['coverage_90'] = [div(groups[a, act['cover_90']], with_pit[a]) for a in range(A)]
+    nr, na = host[head['rows_returns']], host[head['rows_aux']]
+    out.update(value_bias=None, value_rmse=None, explained_variance=None, speed_rmse=None, similarity_rmse=None)
+    if nr > 0:
+        e, e2, r, r2 = (float(host[head[k]]) for k in ('value_error', 'value_error2', 'returns', 'returns2'))
+        var_e, var_r = e2 / nr - (e / nr) ** 2, r2 / nr - (r / nr) ** 2
+        out.update(value_bias=e / nr, value_rmse=root(e2, nr), explained_variance=1.0 - var_e / var_r if var_r > 0.0 else float('nan'))
+    if na > 0:
+        out.update(speed_rmse=root(host[head['speed_error2']], na), similarity_rmse=root(host[head['similarity_error2']], na))
+    out['block'] = host.copy()
+    return out
+
+
+def read_score_block(block: torch.Tensor, A: int) -> dict:
+    """ONE device-to-host copy of a score block (or of a (K, size) stack of blocks -> a list of K dicts) and the figures derived
+    from it on the host: rows; log_prob, mode_error, bias, rmse, predicted_std (the root of the mean predicted variance) and
+    entropy, each as the mean over all scored elements and `_per_action`; pit_histogram (A, SCORE_BINS) ints; coverage_50 /
+    coverage_90 per action (the share of PIT values inside the central 50 % / 90 %; 0.5 / 0.9 for a calibrated policy);
+    value_bias, value_rmse, explained_variance (None without returns); speed_rmse, similarity_rmse (None without auxiliary
+    targets); nonfinite, pit_unconverged; block, the sums themselves (numpy float64, SCORE_LAYOUT).  A mean over nothing is NaN."""
+    A = int(A)
+    if block.dtype != torch.float64 or block.dim() not in (1, 2) or block.shape[-1] != score_block_size(A):
+        raise ValueError(f'read_score_block: a float64 block of {score_block_size(A)} entries for A = {A}, got {tuple(block.shape)} '
+                         f'{block.dtype}')
+    host = block.cpu().numpy()
+    return _score_figures(host, A) if host.ndim == 1 else [_score_figures(h, A) for h in host]

@@ -784,6 +784,8 @@ class PPOAgent(Agent):
                             self.log(**entry)
                     self.write_summaries()
                     print(f'[{epoch}] Trace-{i} took {round(time.time() - t0, 3)}s.')
+                if self.imitation_epoch_end(epoch):
+                    break
             self.network.update_old_policy()
         finally:
             self.network.set_hparams(**base)
@@ -792,6 +794,17 @@ class PPOAgent(Agent):
                 fetch(fetch=False)          # the imitation steps' rows never reach the next update()'s log
             if close:
                 self.env.close()
+
+    def imitation_epoch_end(self, epoch: int) -> bool:
+        """Hook: called by imitate() behind every epoch; True ends the run early (the final update_old_policy() still runs).  An agent
+        that validates on held-out traces does it here (CARLAgent.imitate(validation_dir=...))."""
+        return False
+
+    def score_traces(self, traces_dir=None, *, max_traces=None, chunk=None, value=True, aux=True, per_trace=False) -> dict:
+        """Hook: how well the acting policy fits expert traces it is NOT trained on -- log-likelihood, mode error, bias, RMSE,
+        calibration of the Beta's spread, and the value head against the traces' returns.  Needs a device scoring pass over the
+        acting network's outputs; implemented by CARLAgent."""
+        raise NotImplementedError(f'{type(self).__name__} has no scoring pass: score_traces is implemented by CARLAgent')
 
     def learn_representation(self, epochs=1, batch_size: Union[None, int] = None, *, traces_dir=None, temperature=0.1, intensity=1.0,
                              vector_inputs='zero', lr=None, shuffle_data=True, max_traces=None, seed=None, close=False):

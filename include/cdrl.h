@@ -1188,6 +1188,40 @@ int cdrl_occlusion_rows(const float* image, const float* baseline, const float* 
 int cdrl_occlusion_scores(const float* alpha, const float* beta, const float* value, int N, int A, double* scores, void* stream);
 int cdrl_occlusion_maps(const double* scores, int K, int F, int gh, int gw, int H, int W, int upsample, int normalize, float* maps,
                         void* stream);
+/* Scoring the acting policy on held-out expert rows: the outputs of cdrl_learner_predict for one chunk of rows --
+ * dist [rows][4][A] (alpha, beta, mean, std; the two float columns mean and std are not read), value [rows][4] (base, exp, speed,
+ * similarity) -- against what a trace recorded for the first `count` <= rows of them (the tail of a padded last chunk is ignored):
+ * u [count][A] the expert actions in the unit interval, returns_be [count][2] (base, exp) or NULL, speed and similarity [count]
+ * (both or neither).  One launch of one workgroup; transcendentals and sums in double; fixed reduction order, no atomics: the same
+ * rows in the same chunks give the same bits.  `block` is read-modify-written: the caller zeroes it, a sweep is one launch per
+ * chunk and one host read at the end.  CDRL_SCORE_BLOCK(A) doubles (a count is a double too, exact up to 2^53):
+ *   head   [0] rows scored  [1] rows of the launches with returns  [2] rows of the launches with speed / similarity
+ *          [3] elements (row, action) with a non-finite alpha or beta: left out of EVERY sum below, their pit entry NaN
+ *          [4] elements whose PIT reached the iteration cap: left out of the histogram and the two coverage counts, pit entry NaN
+ *          [5..7] unused (0)
+ *   value  [8] sum (V - R)  [9] sum (V - R)^2  [10] sum R  [11] sum R^2, V = base * 10^exp of the value head, R = rbase * 10^rexp
+ *          of returns_be; written only with returns_be
+ *   aux    [12] sum (value[.][2] - speed)^2  [13] sum (value[.][3] - similarity)^2; written only with speed / similarity
+ *          [14..15] unused (0)
+ *   action a, at CDRL_SCORE_HEAD + a * CDRL_SCORE_PER_ACTION, with x = clip(u, eps, 1 - eps) (float32 machine epsilon, as
+ *   cdrl_beta_clone_loss) and alpha, beta widened to double:
+ *          [+0] elements summed  [+1] sum log Beta(x; alpha, beta)  [+2] sum |mode - x|, mode = (alpha - 1) / (alpha + beta - 2)
+ *          [+3] sum (mean - x)  [+4] sum (mean - x)^2, mean = alpha / (alpha + beta)
+ *          [+5] sum of the predicted variance alpha beta / ((alpha + beta)^2 (alpha + beta + 1))  [+6] sum of the entropy
+ *          [+7] elements with 0.25 <= F <= 0.75  [+8] elements with 0.05 <= F <= 0.95
+ *          [+9 .. +9 + CDRL_SCORE_BINS) histogram of F over equal bins, bin min(BINS - 1, floor(F * BINS))
+ *   F = I_x(alpha, beta), the Beta CDF at the expert action (probability integral transform, PIT): the continued fraction with
+ *   modified Lentz steps, directly for x < (alpha + 1) / (alpha + beta + 2), as 1 - I_{1-x}(beta, alpha) beyond; prefactor
+ *   exp(lgamma(a+b) - lgamma(a) - lgamma(b) + a log x + b log1p(-x)); stops when a step's factor is within 1e-15 of 1 or after
+ *   256 steps (alpha = beta = 1e6, x = 0.5 would need 526: counted in [4]).  pit: [count][A] doubles or NULL, every entry written.
+ * -1 and cdrl_last_error, before any launch: a null dist / value / u / block, rows < 1, count < 1 or > rows, A < 1 or > 8, exactly
+ * one of speed / similarity. */
+#define CDRL_SCORE_BINS 10
+#define CDRL_SCORE_HEAD 16
+#define CDRL_SCORE_PER_ACTION (9 + CDRL_SCORE_BINS)
+#define CDRL_SCORE_BLOCK(A) (CDRL_SCORE_HEAD + CDRL_SCORE_PER_ACTION * (A))
+int cdrl_beta_score(const float* dist, const float* value, const float* u, const float* returns_be, const float* speed,
+                    const float* similarity, int rows, int count, int A, double* block, double* pit, void* stream);
 /* CARLAgent.policy_objective / value_objective on linear head outputs (core/carla_agent.py:394-428,
  * 469-486); writes d(loss)/d(lin) and 16 metric floats. */
 int cdrl_beta_ppo_loss(const float* lin, const float* adv, const float* old_logp, const float* speed,
