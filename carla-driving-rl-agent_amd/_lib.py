@@ -101,6 +101,15 @@ class CloneBatch(C.Structure):
     _fields_ = [(n, _fp) for n in ('image', 'road', 'vehicle', 'navigation', 'u', 'weight', 'speed', 'similarity', 'returns')]
 
 
+TRACE_F32, TRACE_F16, TRACE_U8 = 0, 1, 2       # CDRL_TRACE_* (include/cdrl.h)
+
+
+class TraceSetKey(C.Structure):
+    """cdrl_traceset_key (include/cdrl.h): one key of a cdrl_traceset_batch launch."""
+    _fields_ = [('src', C.c_void_p), ('palette', C.c_void_p), ('dst', C.c_void_p), ('row_elems', C.c_int64),
+                ('src_stride', C.c_int64), ('code', C.c_int32), ('T', C.c_int32), ('direct', C.c_int32), ('reserved', C.c_int32)]
+
+
 class View(C.Structure):
     """cdrl_view (include/cdrl.h): element (r, c) at p[r * ld + coff + c], counted in elements of the tensor's type."""
     _fields_ = [('p', C.c_void_p), ('ld', C.c_int32), ('coff', C.c_int32)]
@@ -206,6 +215,7 @@ PROTOTYPES = {
     'cdrl_vtrace_segments': (_i, [_fp] * 7 + [_i, _i, _i, _d, _d, _d, _d, _f] + [_fp] * 7),
     'cdrl_vtrace_segments_scratch_doubles': (_i64, [_i, _i]),
     'cdrl_gather_rows': (_i, [_fp, _fp, _fp, _i, _i64, _fp]),
+    'cdrl_traceset_batch': (_i, [C.POINTER(TraceSetKey), _i, _fp, _fp, _fp, _i64, _i, _i, _fp]),
     'cdrl_gemm_nn': (_i, [_fp, _i, _i, _fp, _i, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp]),
     'cdrl_gemm_tn_workspace_elems': (_i64, [_i, _i, _i]),
     'cdrl_gemm_tn': (_i, [_fp, _i, _i, _fp, _i, _i, _fp, _i, _i, _i, _fp, _i, _fp]),

@@ -506,29 +506,43 @@ class CARLAgent(PPOAgent):
         heads against info_speed (km/h, / 100 as in training) and info_similarity; switched off with one printed line for traces
         that lack `reward` / `info_*` (the figures are then None).
         Not touched: parameters, moving statistics, optimizer state, memories, the sampler's stream; nothing is logged.
+        traces_dir may be a TraceSet (load_trace_set) in place of the directory: the same sweep over the set's traces in their sorted
+        order, every trace's tensors made by one launch instead of read from its file; the same blocks, bit for bit.
         RuntimeError under data parallelism; ValueError: no traces directory, no trace file in it, chunk outside 1..65535, a trace
-        that does not fit the agent (_check_trace)."""
+        that does not fit the agent (_check_trace), a trace set that does not."""
         if getattr(self, 'data_parallel', False):
             raise RuntimeError('score_traces() runs on one GPU: score in a single process (save(), and load the weights there), not '
                                'in the data-parallel run')
-        path = self._traces_dir(traces_dir)
+        path, trace_set, _ = self._trace_source(traces_dir, False, 'score_traces')
         chunk = self.batch_size if chunk is None else chunk
         if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= 65535:
             raise ValueError(f'score_traces: chunk = {chunk}: 1 to 65535 rows per forward')
-        if not traces.trace_files(path):
+        if trace_set is None and not traces.trace_files(path):
             raise ValueError(f'score_traces: no trace-*.npz file in {path}')
         A, chunk = self.num_actions, int(chunk)
         total = None if per_trace else score_block(A, self.device)
         blocks, told = [], set()
-        for trace in traces.load_traces(path, max_amount=max_traces, shuffle=False):
-            with_value = bool(value) and 'reward' in trace
-            with_aux = bool(aux) and 'info_speed' in trace and 'info_similarity' in trace
+        if trace_set is None:
+            source = traces.load_traces(path, max_amount=max_traces, shuffle=False)
+        else:
+            path = trace_set.dir
+            source = range(trace_set.traces if max_traces is None else min(trace_set.traces, int(max_traces)))
+        for trace in source:
+            if trace_set is None:
+                with_value = bool(value) and 'reward' in trace
+                with_aux = bool(aux) and 'info_speed' in trace and 'info_similarity' in trace
+            else:
+                with_value, with_aux = bool(value) and trace_set.has_value, bool(aux) and trace_set.has_info
             for asked, given, lacks, what in ((value, with_value, 'reward', 'the value head'),
                                               (aux, with_aux, 'info_speed / info_similarity', 'the auxiliary heads')):
                 if asked and not given and what not in told:
                     told.add(what)
                     print(f'score_traces: a trace in {path} has no {lacks}: {what} are not scored on it')
-            data = self._trace_tensors(trace, None, with_aux, 1.0 if with_value else 0.0)
+            if trace_set is None:
+                data = self._trace_tensors(trace, None, with_aux, 1.0 if with_value else 0.0)
+            else:
+                data = trace_set.trace_tensors(trace, ('u',) + (('speed', 'similarity') if with_aux else ()) +
+                                               (('returns',) if with_value else ()), self.gamma)
             block = score_block(A, self.device) if per_trace else total
             self.network.score_rows(data['states'], data['u'], data.get('returns'), data.get('speed'), data.get('similarity'),
                                     chunk=chunk, block=block)
@@ -540,7 +554,8 @@ class CARLAgent(PPOAgent):
         out['traces'] = each
         return out
 
-    def imitate(self, *args, validation_dir=None, validation_every=1, patience=None, **kw):
+    def imitate(self, *args, validation_dir=None, validation_every=1, patience=None, validation_set=None, trace_set=None,
+                mix_traces=False, **kw):
         """PPOAgent.imitate (same arguments) with validation on held-out traces: with `validation_dir`, behind every
         `validation_every`-th epoch the acting network is brought up to date (update_old_policy()) and scored on that directory
         (score_traces); logged: validation_log_prob, validation_mode_error, validation_rmse, validation_coverage_90 (the mean over
@@ -548,7 +563,22 @@ class CARLAgent(PPOAgent):
         best validation_log_prob (one printed line); the weights stay those of the last epoch.  The defaults are imitate() as it
         was: no launch more.  With polyak == 1 the validations do not change what imitate() leaves: the clone pass never reads
         the old policy and the final update_old_policy() overwrites it.  With polyak < 1 every update_old_policy() averages, so
-        validating would change the result: ValueError.  ValueError also for patience without validation_dir."""
+        validating would change the result: ValueError.  ValueError also for patience without validation_dir.
+        Device-resident trace sets (load_trace_set): trace_set= names the set to learn from instead of traces_dir,
+        mix_traces=True asks for minibatches mixed over the whole set (PPOAgent.imitate's traces_dir=set and shuffle_data='set'),
+        validation_set= the held-out set instead of validation_dir -- no file is read during the run.  ValueError when a set and
+        its directory are both given, or mix_traces without trace_set."""
+        if trace_set is not None:
+            if kw.get('traces_dir') is not None:
+                raise ValueError('imitate(): pass traces_dir or trace_set, not both')
+            kw['traces_dir'] = trace_set
+        if mix_traces:
+            if trace_set is None:
+                raise ValueError('imitate(mix_traces=True) draws minibatches across traces: it needs trace_set=')
+            kw['shuffle_data'] = 'set'
+        if validation_dir is not None and validation_set is not None:
+            raise ValueError('imitate(): pass validation_dir or validation_set, not both')
+        validation_dir = validation_set if validation_set is not None else validation_dir
         if validation_dir is None:
             if patience is not None:
                 raise ValueError(f'imitate(patience={patience}) without validation_dir: early stopping needs held-out traces to score')
@@ -677,7 +707,11 @@ class CARLAgent(PPOAgent):
         and would give the pair away -- 'keep' passes them through.  lr: dynamics_lr during the run (the agent's own comes back
         afterwards, also after an error).  seed: seeds the call's plan / shuffle generator; None: one draw from self.rng.
         Only self.rng advances (that draw and the trace order): the rollout sampler, the re-sampling offset and the rollout
-        augmentation's generator and counter stay where they are.  No head changes, so old_policy is not touched."""
+        augmentation's generator and counter stay where they are.  No head changes, so old_policy is not touched.
+        traces_dir may be a TraceSet (load_trace_set) in place of the directory: the same loop, every trace's states made from the
+        device-resident set by one launch -- the same order, draws and bits.  With a set, shuffle_data='set' mixes the traces: per
+        epoch one true permutation of the set's rows from the call's generator, uploaded once; every minibatch's batch_size / 2
+        rows come from all traces."""
         if getattr(self, 'data_parallel', False):
             raise RuntimeError('learn_representation() runs on one GPU: pre-train in a single process, save(), and load the weights '
                                'in the data-parallel run')
@@ -694,26 +728,56 @@ class CARLAgent(PPOAgent):
                              f'must be even')
         if not float(temperature) > 0.0:
             raise ValueError(f'learn_representation(temperature={temperature}) must be positive')
-        path = self._traces_dir(traces_dir)
+        path, trace_set, mix_traces = self._trace_source(traces_dir, shuffle_data, 'learn_representation')
+        if mix_traces and max_traces is not None:
+            raise ValueError(f"learn_representation(shuffle_data='set', max_traces={max_traces}): max_traces is a per-trajectory "
+                             f'notion; a mixed minibatch has no trajectory (load the set with max_traces instead)')
         rng_local = np.random.default_rng(int(self.rng.integers(2 ** 63 - 1)) if seed is None else int(seed))
         half, calls = batch_size // 2, 0
         base = self.hyper_parameters()
         run = dict(base) if lr is None else dict(base, dynamics_lr=float(lr))
+
+        def step(rows, kept):
+            nonlocal calls
+            plans = self.representation_plans(intensity, rng_local, 2 * half, calls + 1)
+            calls += 2 * half
+            eng = self.representation_minibatch(self.representation_views(rows, plans, vector_inputs), float(temperature))
+            kept.append(eng.buffer(_lib.BUF_METRICS_R)[:5].clone())      # copies stay on the device
+
+        def trace_states():
+            """One epoch's traces in an order drawn from self.rng: per trace a callable -> (rows, its states on the device)."""
+            def from_file(trace):
+                n = self._check_trace_states(trace)
+                return n, self._trace_states(trace, n)
+            if trace_set is None:
+                for trace in traces.load_traces(path, max_amount=max_traces, shuffle=True, rng=self.rng):
+                    yield lambda trace=trace: from_file(trace)
+                return
+            for j in trace_set.epoch_order(self.rng, max_traces):
+                yield lambda j=j: (trace_set.trace_rows(j)[1], trace_set.trace_states(j))
+
         try:
             self.network.set_hparams(**run)
             for epoch in range(1, epochs + 1):
-                for i, trace in enumerate(traces.load_traces(path, max_amount=max_traces, shuffle=True, rng=self.rng)):
+                if mix_traces:      # one true permutation of the set's rows per epoch, uploaded once; a ragged tail is dropped
                     t0 = time.time()
-                    n = self._check_trace_states(trace)
-                    states = self._trace_states(trace, n)
+                    order, cuts = trace_set.plan_epoch(rng_local, half, True)
+                    index, kept = trace_set.upload_index(order), []
+                    for offset, rows in cuts:
+                        step(trace_set.batch(index, offset, rows, ())['states'], kept)
+                    if kept:        # ONE device-to-host copy per epoch
+                        for m in torch.stack(kept).cpu().numpy():
+                            self.log(**{k: float(m[j]) for j, k in enumerate(self.REPRESENTATION_LOG)})
+                    self.write_summaries()
+                    print(f'[{epoch}] {len(cuts)} mixed minibatches took {round(time.time() - t0, 3)}s.')
+                for i, load in enumerate(() if mix_traces else trace_states()):
+                    t0 = time.time()
+                    n, states = load()
                     batches = utils.data_to_batches((states,), batch_size=half, shuffle=shuffle_data, seed=int(rng_local.integers(2 ** 31)),
                                                     skip=self.skip_count, num_shards=self.obs_skipping, drop_remainder=True)
                     kept = []
                     for (rows,) in batches:
-                        plans = self.representation_plans(intensity, rng_local, 2 * half, calls + 1)
-                        calls += 2 * half
-                        eng = self.representation_minibatch(self.representation_views(rows, plans, vector_inputs), float(temperature))
-                        kept.append(eng.buffer(_lib.BUF_METRICS_R)[:5].clone())      # copies stay on the device
+                        step(rows, kept)
                     if not kept:
                         print(f'[{epoch}] Trace-{i} skipped: {n} rows give no full minibatch of {half}.')
                         continue

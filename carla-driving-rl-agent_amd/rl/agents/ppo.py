@@ -637,6 +637,72 @@ class PPOAgent(Agent):
             raise ValueError('no traces directory: pass traces_dir=..., or create the agent with traces_dir=...')
         return path
 
+    # -- device-resident trace sets --------------------------------------------------------------------
+    def load_trace_set(self, traces_dir=None, **options):
+        """The traces of a directory read once and kept on the device in their most compact lossless code (rl/trace_set.py):
+        TraceSet.from_dir(self, traces_dir, **options) -- max_traces, storage, weights.  Wherever a call takes `traces_dir`
+        (imitate, learn_representation, score_traces) the set may be passed in its place.  Nothing of the agent changes."""
+        from ..trace_set import TraceSet
+        return TraceSet.from_dir(self, self._traces_dir(traces_dir), **options)
+
+    def _trace_source(self, traces_dir, shuffle_data=False, what='imitate'):
+        """What a `traces_dir` argument names: -> (directory, None, False), or for a TraceSet (None, the checked set, whether
+        shuffle_data='set' asks for minibatches mixed over the whole set)."""
+        from ..trace_set import TraceSet
+        mix = isinstance(shuffle_data, str)
+        if mix and shuffle_data != 'set':
+            raise ValueError(f"{what}(shuffle_data={shuffle_data!r}): True, False or 'set'")
+        if not isinstance(traces_dir, TraceSet):
+            if mix:
+                raise ValueError(f"{what}(shuffle_data='set') draws minibatches across traces: it needs a trace set "
+                                 f'(load_trace_set) in place of the directory')
+            return self._traces_dir(traces_dir), None, False
+        traces_dir.check_fits(self)
+        if mix and (self.skip_count > 0 or self.obs_skipping > 1):
+            raise ValueError(f"{what}(shuffle_data='set'): skip_data = {self.skip_count} and consider_obs_every = {self.obs_skipping} "
+                             f'are per-trajectory notions; a mixed minibatch has no trajectory')
+        return None, traces_dir, mix
+
+    def _set_columns(self, trace_set, need_info: bool, value_weight: float) -> tuple:
+        """The columns of a trace set that _trace_tensors would upload for these options; refuses what the set lacks in
+        _check_trace's words."""
+        if need_info and not trace_set.has_info:
+            raise ValueError('trace has no info_speed / info_similarity: the auxiliary and value losses need them -- set '
+                             'value_weight=0 and aux_weight=0 to clone the actions alone')
+        if value_weight > 0.0 and not trace_set.has_value:
+            raise ValueError('the trace set has no returns: a trace in it lacks a reward of one entry per step and the trailing one')
+        return ('u',) + (('weight',) if trace_set.has_weight else ()) + (('speed', 'similarity') if need_info else ()) + \
+            (('returns',) if value_weight > 0.0 else ())
+
+    def _imitation_traces(self, path, trace_set, max_traces, weights, need_info: bool, value_weight: float):
+        """One epoch's traces in an order drawn from self.rng: per trace a callable -> its tensors on the device (from its file, or
+        from the trace set by one launch)."""
+        if trace_set is None:
+            for trace in traces.load_traces(path, max_amount=max_traces, shuffle=True, rng=self.rng):
+                yield lambda trace=trace: self._trace_tensors(trace, weights, need_info, value_weight)
+            return
+        columns = self._set_columns(trace_set, need_info, value_weight)
+        for i in trace_set.epoch_order(self.rng, max_traces):
+            yield lambda i=i: trace_set.trace_tensors(i, columns, self.gamma)
+
+    def _log_imitation(self, kept: list, with_returns: bool):
+        """The metric rows the minibatches of imitate() left on the device: ONE device-to-host copy, one log entry per minibatch."""
+        names = ('total', 'clone', 'entropy', 'speed', 'similarity')
+        for m in torch.stack(kept).cpu().numpy():
+            entry = {f'imitation_loss_{k}': float(m[j]) for j, k in enumerate(names)}
+            entry['imitation_entropy'] = entry.pop('imitation_loss_entropy')
+            entry['imitation_mode_error'] = float(m[7])
+            if with_returns:
+                entry['imitation_loss_value'] = float(m[8])
+            self.log(**entry)
+
+    def _clone_and_keep(self, batch: dict, weights3: tuple, kept: list):
+        eng = self.clone_minibatch(batch, *weights3)
+        row = [eng.buffer(2)[:8].clone()]       # CDRL_BUF_METRICS_P as the clone loss left it; copies stay on the device
+        if 'returns' in batch:
+            row.append(eng.buffer(3)[:1].clone())
+        kept.append(torch.cat(row))
+
     def clone_minibatch(self, batch: dict, policy_weight: float, value_weight: float, aux_weight: float):
         """Hook: one behaviour-cloning minibatch step (pass + apply) on `batch` -- dict(states, u, and optionally weight, speed,
         similarity, returns) of device tensors.  -> the learner engine that ran it (imitate reads its metric buffers)."""
@@ -739,11 +805,23 @@ class PPOAgent(Agent):
         policy_weight / value_weight scale the two losses' gradients, aux_weight the speed / similarity terms of the clone loss.
         lr / clip_norm: one learning rate / clip threshold for all optimizers during the run (the agent's own come back afterwards,
         also after an error).  weights: callable(trace dict) -> (N,) per-row weights.  max_traces: read at most that many files.
-        No augmentation; the rollout sampler and the re-sampling offsets are not touched.  Ends with update_old_policy()."""
+        No augmentation; the rollout sampler and the re-sampling offsets are not touched.  Ends with update_old_policy().
+        traces_dir may be a TraceSet (load_trace_set) in place of the directory: the same loop with every trace's tensors made from the
+        device-resident set by one launch instead of read from its file -- the same order, the same draws, the same bits; its
+        weights are those it was loaded with.  With a set, shuffle_data='set' mixes the traces: per epoch ONE true permutation of
+        all rows of the set (plan_epoch, from a generator seeded by one self.rng draw) uploaded once, every minibatch drawn across
+        the traces by one launch, one device-to-host copy per epoch; skip_data, consider_obs_every and max_traces are
+        per-trajectory notions and refused."""
         if getattr(self, 'data_parallel', False):
             raise RuntimeError('imitate() runs on one GPU: pre-train in a single process, save(), and load the weights in the '
                                'data-parallel run')
-        path = self._traces_dir(traces_dir)
+        path, trace_set, mix_traces = self._trace_source(traces_dir, shuffle_data, 'imitate')
+        if trace_set is not None and weights is not None:
+            raise ValueError('imitate(weights=...) with a trace set: the set evaluates the weights when it is loaded '
+                             '(load_trace_set(weights=...))')
+        if mix_traces and max_traces is not None:
+            raise ValueError(f"imitate(shuffle_data='set', max_traces={max_traces}): max_traces is a per-trajectory notion; a mixed "
+                             f'minibatch has no trajectory (load the set with max_traces instead)')
         batch_size = self.batch_size if batch_size is None else int(batch_size)
         if seed is not None:
             self.set_random_seed(seed)
@@ -755,13 +833,27 @@ class PPOAgent(Agent):
             run.update({k: float(lr) for k in base if k.endswith('_lr')})
         if clip_norm is not None:
             run.update({k: float(clip_norm) for k in base if k.startswith('clip_norm_')})
-        names = ('total', 'clone', 'entropy', 'speed', 'similarity')
+        weights3 = (policy_weight, value_weight, aux_weight)
         try:
             self.network.set_hparams(**run)
             for epoch in range(1, epochs + 1):
-                for i, trace in enumerate(traces.load_traces(path, max_amount=max_traces, shuffle=True, rng=self.rng)):
+                if mix_traces:
                     t0 = time.time()
-                    data = self._trace_tensors(trace, weights, need_info, value_weight)
+                    columns = self._set_columns(trace_set, need_info, value_weight)
+                    order, cuts = trace_set.plan_epoch(np.random.default_rng(int(self.rng.integers(2 ** 31))), batch_size,
+                                                       self.drop_batch_remainder)
+                    index = trace_set.upload_index(order)       # the epoch's whole row order, uploaded once
+                    kept = []
+                    for offset, rows in cuts:
+                        self._clone_and_keep(trace_set.batch(index, offset, rows, columns, self.gamma), weights3, kept)
+                    if kept:        # ONE device-to-host copy per epoch
+                        self._log_imitation(kept, 'returns' in columns)
+                    self.write_summaries()
+                    print(f'[{epoch}] {len(cuts)} mixed minibatches took {round(time.time() - t0, 3)}s.')
+                for i, load in enumerate(() if mix_traces else self._imitation_traces(path, trace_set, max_traces, weights, need_info,
+                                                                                     value_weight)):
+                    t0 = time.time()
+                    data = load()
                     order = [k for k in ('u', 'weight', 'speed', 'similarity', 'returns') if k in data]
                     batches = utils.data_to_batches((data['states'],) + tuple(data[k] for k in order), batch_size=batch_size,
                                                     shuffle_batches=shuffle_batches, shuffle=shuffle_data,
@@ -769,19 +861,9 @@ class PPOAgent(Agent):
                                                     num_shards=self.obs_skipping, drop_remainder=self.drop_batch_remainder)
                     kept = []
                     for states, *rest in batches:
-                        eng = self.clone_minibatch(dict(zip(order, rest), states=states), policy_weight, value_weight, aux_weight)
-                        row = [eng.buffer(2)[:8].clone()]       # CDRL_BUF_METRICS_P as the clone loss left it; copies stay on the device
-                        if 'returns' in data:
-                            row.append(eng.buffer(3)[:1].clone())
-                        kept.append(torch.cat(row))
+                        self._clone_and_keep(dict(zip(order, rest), states=states), weights3, kept)
                     if kept:        # ONE device-to-host copy per trace
-                        for m in torch.stack(kept).cpu().numpy():
-                            entry = {f'imitation_loss_{k}': float(m[j]) for j, k in enumerate(names)}
-                            entry['imitation_entropy'] = entry.pop('imitation_loss_entropy')
-                            entry['imitation_mode_error'] = float(m[7])
-                            if 'returns' in data:
-                                entry['imitation_loss_value'] = float(m[8])
-                            self.log(**entry)
+                        self._log_imitation(kept, 'returns' in data)
                     self.write_summaries()
                     print(f'[{epoch}] Trace-{i} took {round(time.time() - t0, 3)}s.')
                 if self.imitation_epoch_end(epoch):

@@ -705,6 +705,37 @@ int cdrl_gru_step_bwd(const float* dh, int ld_dh, const float* z, const float* r
  * (rl/utils.py:365-393); dst[i, :] = src[idx[i], :], idx = int32 device array of row numbers. */
 int cdrl_gather_rows(const float* src, const int32_t* idx, float* dst, int nrows, int64_t row_elems, void* stream);
 
+/* Minibatches from a device-resident trace set (rl/trace_set.py): ONE launch writes `rows` output rows of up to 8
+ * keys.  A key's source is an array of slots, slot s at src + s * src_stride elements, row_elems (<= src_stride) elements of it
+ * read; one slot is one time step's row.  code: CDRL_TRACE_F32 the floats themselves; CDRL_TRACE_F16 IEEE halves, widened exactly
+ * (a NaN keeps its sign and its ten payload bits); CDRL_TRACE_U8 bytes that index `palette`, 256 float32 bit patterns (device
+ * memory; -0.0 and +0.0 are two entries, NaN payloads survive: a lookup, no arithmetic).  dst: [rows][T][row_elems] float32.
+ * With r = index[offset + i], frame t of output row i is slot max(slot[r] - (T - 1 - t), lo[r]): slot[r] the slot of the row's own
+ * step, lo[r] the lowest slot its window may reach (the first slot of its trace: the first frame repeats, as traces.window_index;
+ * slot[r] - (T - 1) for a trace stored with its time axis as T slots per row).  direct != 0: the key is indexed by r itself (a
+ * matrix of per-row columns, or with src_stride > row_elems a column range of one), T must be 1 and slot / lo are not read.
+ * index, slot, lo: device int32; duplicates allowed.  An index outside 0 .. set_rows - 1 is clamped into it so that no read
+ * leaves the tables: the kernel cannot report it, the caller checks indices before it uploads them.  16-byte loads and stores per
+ * key when row_elems and src_stride are multiples of 4 (float32), 8 (half), 16 (bytes) and src and dst are 16-byte aligned;
+ * element accesses otherwise.  No host synchronisation.
+ * -1 and cdrl_last_error, before any launch: a null keys / index / src / dst (palette for a byte key; slot / lo with a key that is
+ * not direct), nkeys outside 1..8, rows outside 1..65535, T outside 1..16, an unknown code, row_elems < 1 or > src_stride,
+ * set_rows < 1, offset < 0, a direct key with T != 1. */
+enum { CDRL_TRACE_F32 = 0, CDRL_TRACE_F16 = 1, CDRL_TRACE_U8 = 2 };
+typedef struct cdrl_traceset_key {
+    const void *src;
+    const float *palette;
+    float *dst;
+    int64_t row_elems;
+    int64_t src_stride;
+    int32_t code;
+    int32_t T;
+    int32_t direct;
+    int32_t reserved;
+} cdrl_traceset_key;
+int cdrl_traceset_batch(const cdrl_traceset_key* keys, int nkeys, const int32_t* slot, const int32_t* lo, const int32_t* index,
+                        int64_t offset, int rows, int set_rows, void* stream);
+
 /* ---- op-level entry points (Keras layer call -> one launch; used by the parity tests) -------- */
 /* Conv2D(k=1) / Dense forward: C[M,N] (+)= A[M,K] B[K,N] + bias (core/architectures.py:130,134,140,170) */
 int cdrl_gemm_nn(const float* A, int lda, int a_coff, const float* B, int sbk, int sbn, const float* bias, float* C,
